@@ -4,10 +4,15 @@
 A *step* is one pass of the hot path over one batch of 20 synthetic 1248x384 images that are already resident in HBM.
   inference step: stem -> pools -> 10 Fire modules -> ConvDet (HIP kernels) -> fused decode / top-64 / class-wise NMS
   training step : forward + multi-task loss + backward + (RCCL gradient all-reduce) + clip_grad_norm_(5) + SGD
-``value`` = inference images/sec over all ranks (BASELINE.json's target is stated on inference); the default run also
-times the training step and reports it in the same JSON line under ``"train"`` (the metric is "infer+train").
+``value`` = inference images/sec over all ranks (BASELINE.json's target is stated on inference).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode both|infer|train] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode both|infer|train] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of the last timed step
+(``--dump-outputs DIR``: ``DIR/<name>.npy``, float32 / float64, seeded inputs) and the result line.  ``--full`` adds everything
+else this script measures and checks: the training step under ``"train"`` (``--mode both``), a repeat window per measurement,
+the serial step beside the steps in flight, the per-kernel HIP-event pass (roofline, layer families, ``--layers``), the
+end-to-end legs, and the CPU oracle leg (baseline timing + parity check of the timed step).
 
 N > 1: one process per GPU over RCCL.  Either the launcher starts the ranks (``python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N``: RANK / LOCAL_RANK / WORLD_SIZE in the environment) or -- WORLD_SIZE unset --
@@ -51,7 +56,15 @@ def parse():
                          'alternately on two streams, so the serial tail of a step (every kernel\'s last round, the detect launch) '
                          'overlaps the head of the next; 1 = back-to-back replays on one stream (reported either way)')
     ap.add_argument('--no-pipeline', action='store_true', help='skip the end-to-end leg (pinned uint8 -> H2D -> preprocess -> net -> detect -> D2H)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: training under "train" (--mode both), repeat windows, the serial step, '
+                         'per-kernel event profile and roofline, end-to-end legs, CPU baseline + parity check')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step of the headline path returned as DIR/<name>.npy (float32 / float64)')
+    args = ap.parse_args()
+    if args.layers and not args.full:
+        ap.error('--layers comes from the per-kernel event pass: add --full')
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -306,6 +319,23 @@ def layer_families_of(summ):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DET_NAMES = ('count', 'class_ids', 'scores', 'boxes', 'anchor_idx')     # what Detector.detect_device / DetectStream return
+
+
+def dump_outputs(outdir, arrays):
+    """``arrays``: {name: numpy array} -> ``outdir/<name>.npy``.  float32 stays float32; every other dtype is written as float64
+    (exact for the integer outputs: counts, class ids, anchor indices)."""
+    import numpy as np
+    out = {k: (np.asarray(v, np.float32) if np.asarray(v).dtype == np.float32 else np.asarray(v, np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit')
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(outdir, f'{k}.npy'), a)
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -315,6 +345,9 @@ def main():
 
     import numpy as np  # noqa: F401
     import torch
+    # the dropout masks of the training step derive from torch's seed (per rank: attach_data_parallel offsets it): a fixed seed
+    # gives every run the same inputs, so that the outputs of two builds can be compared
+    torch.manual_seed(0)
 
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -370,10 +403,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def measure(step, capture):
+    def measure(step, capture, after=None):
         """W warm-up steps, optional hipGraph capture of one step, then EXACTLY K timed steps bracketed by barrier +
-        synchronize; a second identical window right behind it shows whether the first ran at steady clocks.
-        Returns (seconds for K steps (max over ranks), seconds of the repeat window, 'hipGraph replay' | 'eager launches', run)."""
+        synchronize; ``after()`` runs right behind them (it reads the outputs of the last timed step); with --full a second
+        identical window follows and shows whether the first ran at steady clocks.
+        Returns (seconds for K steps (max over ranks), seconds of the repeat window or None, 'hipGraph replay' | 'eager launches', run)."""
         for _ in range(max(1, args.warmup)):
             step()
         torch.cuda.synchronize()
@@ -412,12 +446,16 @@ def main():
             run()
         barrier()
         elapsed = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            run()
-        barrier()
-        repeat = time.perf_counter() - t0
-        return max_over_ranks(elapsed), max_over_ranks(repeat), ('hipGraph replay' if graph is not None else 'eager launches'), run
+        if after is not None:
+            after()
+        repeat = None
+        if args.full:
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                run()
+            barrier()
+            repeat = max_over_ranks(time.perf_counter() - t0)
+        return max_over_ranks(elapsed), repeat, ('hipGraph replay' if graph is not None else 'eager launches'), run
 
     def event_profile(step, run, nprof=5):
         """Per-kernel HIP-event pass inside the same process right behind the timed region: every kernel of `nprof` eager
@@ -435,6 +473,7 @@ def main():
 
     result = {}
     hip_pred = hip_det = train_probe = None
+    outputs = {}                                     # {name: host array} of the headline path's last timed step (--dump-outputs)
 
     # ---------------- end-to-end legs (reported beside the main line, never `value`) ----------------
     def pipeline_leg(det):
@@ -553,12 +592,23 @@ def main():
         def infer_step():
             eager_steps[0] += 1
             return det.detect_device(x, out=out_bufs)
-        elapsed, repeat, how, run = measure(infer_step, capture=True)
-        summ, nprof = event_profile(infer_step, run)
-        serial_ms = elapsed / args.steps * 1e3
+
+        def keep_serial():                           # what the last serial step returned: the five detection tensors
+            if args.dump_outputs:
+                outputs.update(zip(DET_NAMES, (t.cpu().numpy() for t in out_bufs[:5])))
+        # Steps in flight are the headline whenever the step is captured (--inflight >= 2, graphs on).  A plain run times them
+        # directly; --full (and the fall-back below) first times the serial replays they are compared with.
+        lanes = args.inflight >= 2 and not args.no_graph
+        elapsed = repeat = how = run = None
+        if args.full or not lanes:
+            elapsed, repeat, how, run = measure(infer_step, capture=True, after=keep_serial)
+            lanes = lanes and how == 'hipGraph replay'
+        if args.full:
+            summ, nprof = event_profile(infer_step, run)
+            serial_ms = elapsed / args.steps * 1e3
         inflight = 1
-        degraded = (how != 'hipGraph replay' and not args.no_graph)          # the serial step fell back to eager launches
-        if args.inflight >= 2 and how == 'hipGraph replay':
+        degraded = (how is not None and how != 'hipGraph replay' and not args.no_graph)          # the serial step fell back to eager launches
+        if lanes:
             # Steps in flight, through the package's own executor (Detector.stream() = lanes.DetectStream, the mode detect_dataset
             # runs in): the K timed steps are the same K passes over the resident batch, but step i + 1 goes to another lane than
             # step i (its own stream, captured graph, activations and packed result buffer), so it starts while step i drains -- the
@@ -584,45 +634,55 @@ def main():
                 last = run_lanes(args.steps)
                 barrier()
                 e2 = max_over_ranks(time.perf_counter() - t0)
-                t0 = time.perf_counter()
-                run_lanes(args.steps)
-                barrier()
-                r2 = max_over_ranks(time.perf_counter() - t0)
-                want = [t.cpu().numpy() for t in out_bufs[:5]]
                 got = (last.count, last.class_ids, last.scores, last.boxes, last.anchor_idx)
-                if not all((a == b).all() for a, b in zip(got, want)):
-                    raise RuntimeError('the lanes of the in-flight run disagree with the serial step')
+                r2 = None
+                if args.full:
+                    t0 = time.perf_counter()
+                    run_lanes(args.steps)
+                    barrier()
+                    r2 = max_over_ranks(time.perf_counter() - t0)
+                    want = [t.cpu().numpy() for t in out_bufs[:5]]
+                    if not all((a == b).all() for a, b in zip(got, want)):
+                        raise RuntimeError('the lanes of the in-flight run disagree with the serial step')
                 if ex.degraded or ex.captures < args.inflight:
                     raise RuntimeError('a lane did not capture its step')
                 elapsed, repeat, inflight = e2, r2, args.inflight
+                if args.dump_outputs:
+                    outputs.update(zip(DET_NAMES, got))
                 how = (f'Detector.stream(): lanes.DetectStream, {inflight} lanes, one captured hipGraph per lane, packed results copied to '
                        f'pinned memory and unpacked per step')
             except Exception as e:  # noqa: BLE001 -- the serial measurement stands, flagged
                 print(f'[bench] in-flight run failed ({type(e).__name__}: {e}); reporting the serial replays', file=sys.stderr)
                 torch.cuda.synchronize()
                 degraded = True
+                if elapsed is None:                  # a plain run has not timed the serial replays yet
+                    elapsed, repeat, how, run = measure(infer_step, capture=True, after=keep_serial)
         ms = elapsed / args.steps * 1e3
-        roof, kernels = roofline_of(summ, serial_ms, nprof)      # (kernel shares are of the serial step: in flight they overlap)
         value = B * joined * args.steps / elapsed
         gf = FWD_GFLOP_PER_IMAGE[args.arch]
         where = '1 MI355X' if joined == 1 else f'each of {joined} MI355X (independent replicas, no data-path collective)'
         result['infer'] = {
             'value': round(value, 1), 'ms_per_step': round(ms, 4), 'timed_with': how, 'degraded': bool(degraded),
-            'repeat_window_ms_per_step': round(repeat / args.steps * 1e3, 4),
-            'steps_in_flight': inflight, 'serial_ms_per_step': round(serial_ms, 4),      # (back-to-back replays on ONE stream)
-            'value_serial': round(B * joined / (serial_ms / 1e3), 1),                    # the bs=B step rate (what rounds 1-3 reported as value)
+            'steps_in_flight': inflight,
             f'value_inflight{inflight}': round(value, 1),
             'eager_steps_launched': eager_steps[0],      # (profiling scripts divide launch counts by this; with --no-graph = every step)
             'workload': (f'SqueezeDet KITTI 1248x384 bs={B} inference on {where} (Fire+ConvDet HIP kernels, fused NMS)' if args.arch == 'squeezedet'
                          else f'SqueezeDet+ wider Fire modules at 1248x384 bs={B} inference on {where}'),
-            'roofline': roof, 'kernels_event_profile': kernels, 'layer_families': layer_families_of(summ),
-            'layers': {f'{k} | {tag}': round(t[1] * 1e3, 1) for k, v in summ.items() for tag, t in v['tags'].items()},      # us per step
             'whole_network': {'direct_form_tflops': round(value * gf / 1e3, 2),
                               'direct_form_tflops_over_fp32_mfma_peak': round(value / joined * gf / 1e3 / PEAK_FP32_MFMA_TFLOPS, 4),
                               'note': 'NOT a utilisation: direct-form flops of the network / step time / peak; the layers run by the Winograd '
                                       'kernels execute 2.25x fewer multiply-adds (the achieved fraction of the matrix pipe is roofline.frac)'},
         }
-        if not args.no_pipeline and args.arch == 'squeezedet':
+        if args.full:
+            roof, kernels = roofline_of(summ, serial_ms, nprof)      # (kernel shares are of the serial step: in flight they overlap)
+            result['infer'].update({
+                'repeat_window_ms_per_step': round(repeat / args.steps * 1e3, 4),
+                'serial_ms_per_step': round(serial_ms, 4),                                   # (back-to-back replays on ONE stream)
+                'value_serial': round(B * joined / (serial_ms / 1e3), 1),                    # the bs=B step rate (what rounds 1-3 reported as value)
+                'roofline': roof, 'kernels_event_profile': kernels, 'layer_families': layer_families_of(summ),
+                'layers': {f'{k} | {tag}': round(t[1] * 1e3, 1) for k, v in summ.items() for tag, t in v['tags'].items()},      # us per step
+            })
+        if args.full and not args.no_pipeline and args.arch == 'squeezedet':
             try:
                 result['infer']['pipeline'] = pipeline_leg(det)
             except Exception as e:  # noqa: BLE001 -- the end-to-end leg is a reported extra: its failure must not cost the main line
@@ -635,7 +695,7 @@ def main():
                 print(f'[bench] detect_dataset leg failed ({type(e).__name__}: {e})', file=sys.stderr)
                 result['infer']['detect_dataset'] = None
                 torch.cuda.synchronize()
-        if rank == 0 and joined == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and joined == 1 and not args.no_cpu_baseline:
             # outputs of the step that was timed, for the parity check of the CPU leg: the detections the last replay left
             # in out_bufs, and pred from one more (bitwise identical: tests/test_headline_gpu.py) eager backbone pass
             run()
@@ -657,36 +717,54 @@ def main():
         step_parts = {}
         step, describe, probe = make_train_step(cfg, sd, x, rank, joined, dist, force_exchange=args.force_dist, parts=step_parts,
                                                 fused_optimizer=True)
-        if rank == 0 and joined == 1 and not args.no_cpu_baseline and args.mode == 'both':
+        if args.full and rank == 0 and joined == 1 and not args.no_cpu_baseline and args.mode == 'both':
             train_probe = probe()                    # (gt, eval-mode loss of the initial weights), before any optimizer step
         # the whole step (fwd, loss, bwd, gradient exchange, clip, SGD, weight re-pack) replays as a hipGraph: RCCL collectives
         # issued through torch.distributed are capturable (the bucketed all-reduces on the side stream fork from and join the
         # capturing stream); a gloo group copies through the host and stays eager
         eager_steps = [0]
         inner = step
+        dump = bool(args.dump_outputs) and args.mode == 'train'      # the headline is training: dump its loss and the updated weights
+        loss = [None]                                # the loss the step returns, detached (a captured step's: refreshed by every replay)
 
         def step():
             eager_steps[0] += 1
-            return inner()
+            out = inner()
+            if dump:
+                # detached: a loss kept with its autograd graph keeps that step's AccumulateGrad nodes alive into the next
+                # step, whose backward on the capture stream then no longer matches their stream (the capture crashed so)
+                loss[0] = out.detach()
+            return out
+
+        def keep_train():
+            if dump:
+                params = [p for p in step_parts['model'].parameters() if p.requires_grad]
+                outputs['loss'] = loss[0].detach().cpu().numpy()
+                outputs['weights'] = torch.cat([p.detach().reshape(-1) for p in params]).cpu().numpy()
         wanted_graph = (dist is None or args.backend == 'nccl') and not args.no_graph
         try:
-            elapsed, repeat, how, run = measure(step, capture=(dist is None or args.backend == 'nccl'))
+            elapsed, repeat, how, run = measure(step, capture=(dist is None or args.backend == 'nccl'), after=keep_train)
         except Exception as e:  # noqa: BLE001
             print(f'[bench] training step not captured ({type(e).__name__}: {e}); timing eager launches', file=sys.stderr)
             torch.cuda.synchronize()
             args.no_graph = True
-            elapsed, repeat, how, run = measure(step, capture=False)
-        summ, nprof = event_profile(step, run, nprof=3)
+            elapsed, repeat, how, run = measure(step, capture=False, after=keep_train)
+        if args.full:
+            summ, nprof = event_profile(step, run, nprof=3)
         ms = elapsed / args.steps * 1e3
-        roof, kernels = roofline_of(summ, ms, nprof, mode='train')
         result['train'] = {
             'value': round(B * joined * args.steps / elapsed, 1), 'unit': 'images/sec', 'ms_per_step': round(ms, 4), 'timed_with': how,
             'degraded': bool(wanted_graph and how != 'hipGraph replay'),       # a capture that failed: eager launches were timed instead
-            'repeat_window_ms_per_step': round(repeat / args.steps * 1e3, 4),
             'eager_steps_launched': eager_steps[0],
-            'workload': describe, 'roofline': roof, 'kernels_event_profile': kernels, 'layer_families': layer_families_of(summ),
-            'layers': {f'{k} | {tag}': round(t[1] * 1e3, 1) for k, v in summ.items() for tag, t in v['tags'].items()},
+            'workload': describe,
         }
+        if args.full:
+            roof, kernels = roofline_of(summ, ms, nprof, mode='train')
+            result['train'].update({
+                'repeat_window_ms_per_step': round(repeat / args.steps * 1e3, 4),
+                'roofline': roof, 'kernels_event_profile': kernels, 'layer_families': layer_families_of(summ),
+                'layers': {f'{k} | {tag}': round(t[1] * 1e3, 1) for k, v in summ.items() for tag, t in v['tags'].items()},
+            })
 
     # Order of the two halves: inference, then training, with or without a process group.  (Round 2 ran training first when ranks
     # communicate, after a two-ranks-on-one-GPU gloo rehearsal showed eager training steps behind the graph-replay phase at
@@ -696,17 +774,20 @@ def main():
     for half in ('infer', 'train'):
         if half == 'infer' and args.mode in ('both', 'infer'):
             bench_infer()
-        if half == 'train' and args.mode in ('both', 'train'):
+        if half == 'train' and (args.mode == 'train' or (args.mode == 'both' and args.full)):
             bench_train()
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         cpu = parity = None
-        if joined == 1 and not args.no_cpu_baseline and args.mode != 'train':
+        if args.full and joined == 1 and not args.no_cpu_baseline and args.mode != 'train':
             cpu, parity = cpu_baseline_and_parity(cfg, sd, B, hip_pred, hip_det, train_probe)
         result.pop('_keep', None)
         layer_detail = {m: r.pop('layers', None) for m, r in result.items()}
         head = result['infer'] if 'infer' in result else result['train']
         what = 'inference' if 'infer' in result else 'training'
+        full_only = {'roofline': head.get('roofline'), 'cpu_baseline': cpu, 'parity': parity} if args.full else {}
         line = {
             'metric': f'images/sec {net} 1248x384 bs={B} {what}' + (' (+ training under "train")' if args.mode == 'both' else ''),
             'value': head['value'], 'unit': 'images/sec', 'n_gpus': joined, 'steps': args.steps, 'warmup': args.warmup,
@@ -716,11 +797,10 @@ def main():
                        'input': '3x384x1248 fp32 NCHW, HBM resident', 'weights': 'synthetic Kaiming-scale, seed 1234',
                        'parallelism': (f'replicas x{joined}' if what == 'inference' else f'dp{joined}'),
                        **({'steps_in_flight': head['steps_in_flight']} if 'steps_in_flight' in head else {})},
-            'roofline': head['roofline'], 'cpu_baseline': cpu, 'parity': parity,
+            **full_only,
             'whole_network': head.get('whole_network'), 'timed_with': head['timed_with'],
-            'repeat_window_ms_per_step': head['repeat_window_ms_per_step'],
-            **({k: head[k] for k in head if k in ('steps_in_flight', 'serial_ms_per_step', 'value_serial', 'degraded') or k.startswith('value_inflight')}),
-            'layer_families': head['layer_families'], 'kernels_event_profile': head['kernels_event_profile'],
+            **({k: head[k] for k in head if k in ('repeat_window_ms_per_step', 'steps_in_flight', 'serial_ms_per_step', 'value_serial', 'degraded',
+                                                 'layer_families', 'kernels_event_profile') or k.startswith('value_inflight')}),
         }
         if 'eager_steps_launched' in head:
             line['eager_steps_launched'] = head['eager_steps_launched']
@@ -730,7 +810,7 @@ def main():
             line['detect_dataset'] = head['detect_dataset']
         if args.layers:
             line['layers'] = layer_detail
-        if args.mode == 'both':
+        if 'infer' in result and 'train' in result:
             line['train'] = result['train']
         print(json.dumps(line))
         if parity is not None and not parity['ok']:

@@ -9,7 +9,7 @@ REPO=$PWD
 for MODE in $MODES; do
   for C in FETCH_SIZE WRITE_SIZE; do
     OUT=$REPO/gpurun_out/pmc_${TAG}_${MODE}_$C; mkdir -p $OUT; cd /tmp
-    timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $OUT -o pmc -- python3 $REPO/bench.py --mode $MODE --steps 3 --warmup 2 --no-cpu-baseline --no-graph --no-pipeline > $OUT/out.json 2> $OUT/stderr.log || exit 1
+    timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $OUT -o pmc -- python3 $REPO/bench.py --mode $MODE --steps 3 --warmup 2 --full --no-cpu-baseline --no-graph --no-pipeline > $OUT/out.json 2> $OUT/stderr.log || exit 1
     cd $REPO
   done
 done

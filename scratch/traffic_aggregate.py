@@ -32,7 +32,7 @@ def aggregate(mode):
         if nf % steps == 0:
             out[k]["launches_per_step"] = nf // steps      # the launch set this average was taken over (checked by tests/test_profiles.py)
     what = "inference" if mode == "infer" else "training step: fwd + loss + bwd + clip + SGD"
-    out["_meta"] = {"workload": f"python bench.py --mode {mode} --steps 3 --warmup 2 --no-cpu-baseline --no-graph --no-pipeline (SqueezeDet bs=20 1248x384 {what})",
+    out["_meta"] = {"workload": f"python bench.py --mode {mode} --steps 3 --warmup 2 --full --no-cpu-baseline --no-graph --no-pipeline (SqueezeDet bs=20 1248x384 {what})",
                     "eager_steps_profiled": steps,
                     "counters": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes, KB units; fabric-side L2 request counters: Infinity-Cache hits are included (MI355X_MICROARCH.md, HBM section), so these are L2<->fabric bytes, an upper bound of HBM bytes"}
     print(f"--- {mode}: {steps} eager steps profiled")

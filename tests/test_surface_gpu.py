@@ -103,7 +103,7 @@ def _run_bench(*args, timeout=900):
 def test_bench_starts_its_own_ranks():
     """``python bench.py --gpus 2`` with no launcher: two fresh rank processes (gloo rehearsal, both on this box's one GPU),
     n_gpus counted by an all-reduce, ONE line with the training result inside."""
-    line = _run_bench('--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '2', '--no-cpu-baseline')
+    line = _run_bench('--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '2', '--full', '--no-cpu-baseline')
     assert line['n_gpus'] == 2 and line['config']['global_batch'] == 40
     assert line['train']['value'] > 0 and 'bucket' in line['train']['workload']
     assert line['value'] > 0 and line['scaling'] == 'weak'
@@ -133,10 +133,32 @@ def test_bench_rccl_training_step_is_captured():
     assert line['timed_with'] == 'hipGraph replay', line['timed_with']
 
 
+def test_bench_plain_run_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """A plain run (no --full) times the headline steps only and, with --dump-outputs, writes what the last of them returned:
+    the detections of the seeded bs=20 batch, equal to one eager Detector.detect_device pass over the same inputs."""
+    from squeezedet_pytorch_amd.detector import Detector
+    from squeezedet_pytorch_amd.model import SqueezeDet
+    line = _run_bench('--gpus', '1', '--steps', '4', '--warmup', '2', '--dump-outputs', str(tmp_path))
+    assert line['steps'] == 4 and line['ms_per_step'] > 0 and line['value'] > 0 and not line['degraded']
+    assert line['steps_in_flight'] == 2 and 'train' not in line and 'cpu_baseline' not in line and 'roofline' not in line
+    names = ('count', 'class_ids', 'scores', 'boxes', 'anchor_idx')
+    assert sorted(os.listdir(tmp_path)) == sorted(f'{n}.npy' for n in names)
+    got = {n: np.load(tmp_path / f'{n}.npy') for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    cfg = sqd.make_cfg(device='cuda')
+    m = SqueezeDet(cfg)
+    m.load_state_dict(synthetic.make_state_dict('squeezedet', seed=1234))
+    with torch.no_grad():
+        want = Detector(m, cfg).detect_device(synthetic.make_images(20, cfg.input_size, seed=0).cuda())
+    for n, w in zip(names, want):
+        assert np.array_equal(got[n], w.cpu().numpy()), n
+    assert got['count'].sum() > 0
+
+
 def test_bench_default_line_has_pipeline_and_cpu_legs():
-    """The default line carries the end-to-end leg (pinned uint8 -> H2D -> preprocess -> net -> detect -> D2H, never `value`) and
+    """The --full line carries the end-to-end leg (pinned uint8 -> H2D -> preprocess -> net -> detect -> D2H, never `value`) and
     the four CPU-baseline legs of BASELINE.md section 4."""
-    line = _run_bench('--steps', '10', '--warmup', '3', '--mode', 'infer')
+    line = _run_bench('--steps', '10', '--warmup', '3', '--mode', 'infer', '--full')
     pl = line['pipeline']
     assert pl['value'] > 0 and pl['results_on_host_ok'] and not pl['degraded']
     assert 20 * 375 * 1242 * 3 <= pl['h2d_bytes_per_step'] <= 1.05 * 20 * 375 * 1242 * 3      # (header + 4 KB-rounded image slots)

@@ -1,6 +1,6 @@
 """Per-LAUNCH hardware counters of one bench.py step ("per-launch FETCH/WRITE of the training conv_wino launches,
 not the per-kernel average"; "TCP/TCC counters for the 1x1 family").  Runs rocprofv3 --pmc once per counter group over
-`bench.py --mode <mode> --steps 3 --warmup 2 --no-graph --no-cpu-baseline --no-pipeline`, then averages every counter over the eager
+`bench.py --mode <mode> --steps 3 --warmup 2 --full --no-graph --no-cpu-baseline --no-pipeline`, then averages every counter over the eager
 steps per (kernel, k-th launch of that kernel inside a step) and tags the rows with the host-side launch plan (plan.py).
 usage (GPU box, repo root):  python tools/pmc_per_launch.py <tag> <infer|train> "<group1 counters>" ["<group2 counters>" ...]
  -> gpurun_out/pmc_launch_<tag>_<mode>.json / .txt"""
@@ -34,7 +34,7 @@ def main():
         out = os.path.join(ROOT, 'gpurun_out', f'pmcl_{tag}_{mode}_{gi}')
         os.makedirs(out, exist_ok=True)
         cmd = ['rocprofv3', '--pmc'] + grp.split() + ['--output-format', 'csv', '-d', out, '-o', 'pmc', '--', 'python3', os.path.join(ROOT, 'bench.py'),
-               '--mode', mode, '--steps', '3', '--warmup', '2', '--no-cpu-baseline', '--no-graph', '--no-pipeline']
+               '--mode', mode, '--steps', '3', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-graph', '--no-pipeline']
         with open(os.path.join(out, 'out.json'), 'w') as fo, open(os.path.join(out, 'stderr.log'), 'w') as fe:
             rc = subprocess.run(cmd, cwd='/tmp', env=env, stdout=fo, stderr=fe, timeout=400).returncode
         if rc != 0:

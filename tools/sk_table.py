@@ -1,5 +1,5 @@
 """Write a copy of tuning.json whose listed Winograd rows ('W:C:N:npix') point at another configuration (default: the balanced
-stream-K kernel, tiles.WINO_SK_CFG) -- for whole-step A/B runs:  SQD_TUNING_JSON=<out> python bench.py --layers.
+stream-K kernel, tiles.WINO_SK_CFG) -- for whole-step A/B runs:  SQD_TUNING_JSON=<out> python bench.py --full --layers.
 usage: python tools/sk_table.py <out.json> <row>[=cfg] [<row>[=cfg] ...]"""
 import json
 import os
