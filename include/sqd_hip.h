@@ -222,6 +222,18 @@ int sqd_preprocess_u8_fwd(const unsigned char* src, const long long* offsets, co
 int sqd_preprocess_u8_padcrop_fwd(const unsigned char* src, const long long* offsets, const int* sizes, float* out, float* shifts,
                                   int* padcrop, const float* mean3, const float* std3, int B, int H, int W, void* stream);
 
+/* Training forms of the two above: the reference's train phase (src/datasets/base.py:43-59 with drift / flip active,
+ * src/utils/image.py:22-74) in the same single launch.  aug: DEVICE int32 [B][3] = (dy, dx, flipped) per image.  The drifted
+ * image is (Hd, Wd) = (H0 - dy, W0 - dx); pixel (y, x) of it is the whitened source pixel (y + dy, x + dx) where both are >= 0,
+ * else 0.0f; a flipped image reads column Wd - 1 - x.  The resize / crop_or_pad rule then runs on (Hd, Wd): scales = (H/Hd, W/Wd),
+ * padding / crops / shifts those of (Hd, Wd).  dy < H0 and dx < W0 are expected (larger values are clamped).
+ * aug = (0, 0, 0) everywhere gives the results of sqd_preprocess_u8_fwd / sqd_preprocess_u8_padcrop_fwd bit for bit. */
+int sqd_preprocess_u8_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug, float* out,
+                              float* scales, const float* mean3, const float* std3, int B, int H, int W, void* stream);
+int sqd_preprocess_u8_padcrop_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug, float* out,
+                                      float* shifts, int* padcrop, const float* mean3, const float* std3, int B, int H, int W,
+                                      void* stream);
+
 /* Fused Fire expand (Fire.forward, src/model/squeezedet.py:18-22: expand1x1 and expand3x3 of the squeeze output,
  * concatenated): y[..., y_coff : y_coff+E] = ReLU(conv1x1(x)), y[..., y_coff+E : y_coff+2E] = ReLU(conv3x3(x)) in ONE
  * launch.  w_packed / bias: the 2E output channels in alternating 16-channel groups (group 2i = expand1x1 channels

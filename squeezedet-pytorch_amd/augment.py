@@ -1,0 +1,220 @@
+"""Training-time input pipeline: the reference's train-phase ``BaseDataset.preprocess`` (src/datasets/base.py:43-59 with drift and
+flip active; src/utils/image.py:22-74 ``drift`` / ``flip``, then ``resize`` :77-88 or ``crop_or_pad`` :91-124) on the GPU.
+
+The random parameters are drawn on the host, in the reference's order and with the reference's arguments
+(``draw_augmentation``); the boxes are transformed on the host in float32, op for op as the reference does (``transform_boxes``);
+the pixels go up as packed uint8 and ONE launch (``sqd_preprocess_u8_aug_fwd`` / ``sqd_preprocess_u8_padcrop_aug_fwd``)
+whitens, drifts, flips, resizes (or pads / crops) and transposes the whole batch.  The dense ``gt`` is then encoded on the device
+(``annotations.encode_annotations``).
+
+Two departures, both where the reference raises instead: an image without boxes draws its drift with the reference's
+``boxes is None`` bound (``max_boxes = max_drift``); an axis whose ``randint`` range is empty (an image under 4 rows or 8 columns)
+gets drift 0 on that axis and consumes no draw for it.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _native as nat
+from .preprocess import KITTI_RGB_MEAN, KITTI_RGB_STD, _staging
+
+HDR_ALIGN = 256          # the packed pixels start this many bytes into the upload, after the int header
+
+
+def clip_boxes(boxes, orig_size):
+    """``preprocess``' first step (base.py:45-46): a float32 copy of the xyxy boxes clipped to the original image."""
+    b = np.array(boxes, dtype=np.float32).reshape(-1, 4)
+    orig = np.asarray(orig_size, dtype=np.int32)
+    b[:, [0, 2]] = np.clip(b[:, [0, 2]], 0., orig[1] - 1.)
+    b[:, [1, 3]] = np.clip(b[:, [1, 3]], 0., orig[0] - 1.)
+    return b
+
+
+def draw_augmentation(rng, orig_sizes, boxes_list, drift_prob, flip_prob):
+    """Per image, in batch order: ``rng.uniform()`` for the drift, then (drift taken) ``rng.randint`` for dy and dx with the
+    reference's bounds (image.py:26-33, on the clipped boxes), then ``rng.uniform()`` for the flip (image.py:57).  ``rng`` is a
+    ``np.random.RandomState``.  Returns int32 [B, 3] = (dy, dx, flipped)."""
+    aug = np.zeros((len(orig_sizes), 3), dtype=np.int32)
+    for i, size in enumerate(orig_sizes):
+        orig = np.asarray(size, dtype=np.int32)
+        if rng.uniform() < drift_prob:
+            max_drift_y, max_drift_x = orig[0] // 4, orig[1] // 8
+            boxes = None if boxes_list[i] is None else clip_boxes(boxes_list[i], orig)
+            if boxes is None or boxes.shape[0] == 0:      # departure: the reference's ``boxes is None`` bound
+                max_boxes_y, max_boxes_x = max_drift_y, max_drift_x
+            else:
+                max_boxes_y, max_boxes_x = min(boxes[:, 1]), min(boxes[:, 0])
+            for k, (lo, hi) in enumerate(((-max_drift_y, min(max_drift_y, max_boxes_y)), (-max_drift_x, min(max_drift_x, max_boxes_x)))):
+                if int(hi) > int(lo):                     # numpy truncates the float bound; departure: empty range -> 0, no draw
+                    aug[i, k] = rng.randint(lo, hi)
+        aug[i, 2] = rng.uniform() < flip_prob
+    return aug
+
+
+def _pad_crop(size, target):
+    """crop_or_pad's integers for one axis (image.py:99-115): (pad front, pad back, crop front, crop back)."""
+    if size < target:
+        return (target - size) // 2, (target - size) - (target - size) // 2, 0, 0
+    if size > target:
+        return 0, 0, (size - target) // 2, (size - target) - (size - target) // 2
+    return 0, 0, 0, 0
+
+
+def transform_boxes(boxes, orig_size, aug, input_size, forbid_resize=False):
+    """The box half of the train-phase ``preprocess`` for one image, in float32 and in the reference's order: clip to the original
+    image, subtract the drift, flip with the drifted width, then scale by ``scales`` (or shift by padding / crops).
+    Returns (boxes float32 [n, 4], meta dict of that image: drifts, drifted_size, flipped, scales or padding / crops)."""
+    orig = np.asarray(orig_size, dtype=np.int32)
+    H0, W0 = int(orig[0]), int(orig[1])
+    dy, dx, flipped = int(aug[0]), int(aug[1]), bool(aug[2])
+    b = clip_boxes(boxes, orig)
+    b[:, [0, 2]] -= dx
+    b[:, [1, 3]] -= dy
+    Hd, Wd = H0 - dy, W0 - dx
+    if flipped:
+        widths = b[:, 2] - b[:, 0]
+        b[:, 0] = Wd - 1 - b[:, 2]
+        b[:, 2] = b[:, 0] + widths
+    meta = {'drifts': np.array([dy, dx], np.int32), 'drifted_size': np.array([Hd, Wd, 3], np.int32), 'flipped': flipped}
+    H, W = int(input_size[0]), int(input_size[1])
+    if not forbid_resize:
+        scales = np.array([H / Hd, W / Wd], dtype=np.float32)
+        b[:, [0, 2]] *= scales[1]
+        b[:, [1, 3]] *= scales[0]
+        meta['scales'] = scales
+        return b, meta
+    pt, pb, ct, cb = _pad_crop(Hd, H)
+    pl, pr, cl, cr = _pad_crop(Wd, W)
+    padding, crops = np.array([pt, pb, pl, pr], np.int16), np.array([ct, cb, cl, cr], np.int16)
+    if not np.all(padding == 0):
+        # as the reference's ``pad`` (image.py:133-137): it rebinds ``padding`` to np.pad's ((top, bottom), (left, right), (0, 0))
+        # before shifting, so x moves by (0, 0) and (y1, y2) by (top, bottom) -- reproduced for parity of the training targets
+        b[:, [0, 2]] += np.array([0, 0])
+        b[:, [1, 3]] += padding[:2]
+    if not np.all(crops == 0):
+        b[:, [0, 2]] -= crops[2]
+        b[:, [1, 3]] -= crops[0]
+        b = np.maximum(b, 0.)
+    meta.update(padding=padding, crops=crops)
+    return b, meta
+
+
+def batch_meta(metas, sizes, rgb_mean, rgb_std):
+    """Per-image meta dicts -> the stacked ``image_meta`` of a batch (the reference's default collate)."""
+    B = len(metas)
+    out = {'orig_size': np.concatenate([np.asarray(sizes, np.int32).reshape(B, 2), np.full((B, 1), 3, np.int32)], 1),
+           'rgb_mean': np.tile(np.asarray(rgb_mean, np.float32).reshape(1, 1, 1, 3), (B, 1, 1, 1)),
+           'rgb_std': np.tile(np.asarray(rgb_std, np.float32).reshape(1, 1, 1, 3), (B, 1, 1, 1)),
+           'flipped': [m['flipped'] for m in metas]}
+    for k in ('drifts', 'drifted_size', 'scales', 'padding', 'crops'):
+        if k in metas[0]:
+            out[k] = np.stack([m[k] for m in metas])
+    return out
+
+
+def as_u8_image(im, what):
+    """uint8 [H, W, 3] view / copy of ``im``; float pixels must be uint8-representable (the reference's ``skimage`` float32 loads)."""
+    im = np.asarray(im)
+    if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+        raise ValueError(f'{what}: expected an [H, W, 3] RGB image, got shape {im.shape}')
+    if im.dtype == np.uint8:
+        return im
+    u8 = im.astype(np.uint8)
+    if im.dtype.kind not in 'fiu' or not np.array_equal(u8, im):
+        raise ValueError(f'{what}: pixels must be uint8 or uint8-representable values, got {im.dtype} outside 0..255 or fractional')
+    return u8
+
+
+def pack_layout(sizes):
+    """Byte layout of one upload: int64 offsets [B], int32 sizes [B, 2], int32 aug [B, 3], then (at HDR_ALIGN) the pixels.
+    Returns (header bytes, pixel offsets int64 [B] relative to the pixel base, total bytes)."""
+    B = len(sizes)
+    hdr = -(-(8 * B + 20 * B) // HDR_ALIGN) * HDR_ALIGN
+    offsets = np.zeros(B, np.int64)
+    total = 0
+    for i, (h, w) in enumerate(sizes):
+        offsets[i] = total
+        total += int(h) * int(w) * 3
+    return hdr, offsets, hdr + total
+
+
+def write_header(buf_np, offsets, sizes, aug):
+    """Fill the int header of a packed upload (``buf_np``: the uint8 numpy view of the whole pinned buffer)."""
+    B = len(offsets)
+    buf_np[:8 * B].view(np.int64)[:] = offsets
+    buf_np[8 * B:16 * B].view(np.int32)[:] = np.asarray(sizes, np.int32).reshape(-1)
+    buf_np[16 * B:28 * B].view(np.int32)[:] = np.asarray(aug, np.int32).reshape(-1)
+
+
+def launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std):
+    """One augmented preprocessing launch on the device copy ``dev_buf`` of a packed upload.  Returns the device tensor the kernel
+    writes next to ``out``: scales fp32 [B, 2], or (forbid_resize) padcrop int32 [B, 8]."""
+    H, W = int(input_size[0]), int(input_size[1])
+    base = dev_buf.data_ptr()
+    p = lambda off: ctypes.c_void_p(base + off)      # noqa: E731
+    mean = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_mean).reshape(-1)])
+    std = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_std).reshape(-1)])
+    stream = nat.stream_handle(dev_buf.device)
+    if forbid_resize:
+        side = torch.empty(B, 8, device=dev_buf.device, dtype=torch.int32)
+        rc = nat.lib().sqd_preprocess_u8_padcrop_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), nat.ptr(out), None, nat.ptr(side),
+                                                         mean, std, B, H, W, stream)
+        nat.check(rc, 'sqd_preprocess_u8_padcrop_aug_fwd')
+    else:
+        side = torch.empty(B, 2, device=dev_buf.device, dtype=torch.float32)
+        rc = nat.lib().sqd_preprocess_u8_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), nat.ptr(out), nat.ptr(side), mean, std, B, H, W, stream)
+        nat.check(rc, 'sqd_preprocess_u8_aug_fwd')
+    return side
+
+
+def check_out(out, B, H, W, device):
+    if out is None:
+        return torch.empty(B, 3, H, W, device=device, dtype=torch.float32)
+    if tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise ValueError('preprocess_train_batch: out must be a contiguous float32 [B, 3, H, W] tensor on the device')
+    return out
+
+
+def _default_anchors(input_size):
+    from .boxes import KITTI_ANCHORS_SEED, generate_anchors
+    return generate_anchors(tuple(x // 16 for x in input_size), tuple(input_size), np.asarray(KITTI_ANCHORS_SEED))
+
+
+def preprocess_train_batch(images, class_ids_list, boxes_list, input_size, rng, drift_prob=1.0, flip_prob=0.5,
+                           rgb_mean=KITTI_RGB_MEAN, rgb_std=KITTI_RGB_STD, forbid_resize=False, device='cuda', out=None,
+                           anchors=None, num_classes=3, aug=None):
+    """A training batch the reference's way (``BaseDataset.__getitem__`` in the train phase + default collate), built on the GPU.
+
+    images: list of uint8 (or uint8-representable float) [H0, W0, 3] RGB arrays; class_ids_list / boxes_list: per image [n] and
+    xyxy [n, 4] in original-image coordinates; rng: ``np.random.RandomState`` the draws come from (``aug``: int32 [B, 3] to use
+    instead of drawing); anchors: ``cfg.anchors`` (default: the KITTI anchors of ``input_size``).  Returns (image fp32 NCHW on
+    ``device`` -- ``out`` when given --, image_meta with the reference's keys, dense gt [B, A, num_classes + 9] on ``device``).
+    Uploads: one packed uint8 buffer (int header included) and the boxes of ``encode_annotations``; nothing waits on the device."""
+    B = len(images)
+    if B == 0:
+        raise ValueError('preprocess_train_batch: empty batch')
+    H, W = int(input_size[0]), int(input_size[1])
+    ims = [as_u8_image(im, f'preprocess_train_batch: image {i}') for i, im in enumerate(images)]
+    sizes = [im.shape[:2] for im in ims]
+    if aug is None:
+        aug = draw_augmentation(rng, sizes, boxes_list, drift_prob, flip_prob)
+    aug = np.asarray(aug, np.int32).reshape(B, 3)
+    tb, metas = zip(*[transform_boxes(bx, (h, w), a, input_size, forbid_resize) for bx, (h, w), a in zip(boxes_list, sizes, aug)])
+    hdr, offsets, total = pack_layout(sizes)
+    packed = _staging(total)
+    pk = packed.numpy()
+    write_header(pk, offsets, sizes, aug)
+    for im, off in zip(ims, offsets):
+        pk[hdr + off:hdr + off + im.size] = np.ascontiguousarray(im).reshape(-1)
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    dev_buf = packed.to(dev, non_blocking=True)
+    out = check_out(out, B, H, W, dev)
+    launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std)
+    from .annotations import encode_annotations
+    gt = encode_annotations(class_ids_list, list(tb), _default_anchors(input_size) if anchors is None else anchors, num_classes, device=dev)
+    return out, batch_meta(metas, sizes, rgb_mean, rgb_std), gt

@@ -61,36 +61,62 @@ __device__ __forceinline__ int pre_stage(unsigned* dst, const unsigned char* img
   return shift;
 }
 
-__global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) {
+// Training augmentation (reference train phase, src/datasets/base.py:43-59 with drift / flip active; src/utils/image.py:22-74): per image
+// aug[b] = (dy, dx, flipped).  The drifted image V is Hd x Wd = (H0 - dy) x (W0 - dx); before the flip V[y][x] = whiten(I[y+dy][x+dx])
+// where y + dy >= 0 and x + dx >= 0, else exactly 0.0f (the reference zero-fills AFTER whitening); the flip reads V[y][Wd-1-x].  Both
+// kernels below are templates on AUG: the resize / crop_or_pad coordinate rule runs in V coordinates (Hd, Wd), and only then is a
+// V column mapped to a column of I, col(v) = (flipped ? Wd-1-v : v) + dx (a row: v + dy).  A tap in the fill region reads 0 and is
+// never loaded; a workgroup's source segment is bounded by the mapped columns of its two end pixels (min / max: under a flip the
+// column falls as x rises), clamped to the image, and a row wholly in the fill region is not staged.  dy / dx are clamped to
+// [-2^20, H0-1] / [-2^20, W0-1] so that Hd, Wd >= 1 whatever the buffer holds.  AUG = false is the untouched eval-time kernel.
+template <bool AUG>
+__device__ __forceinline__ int pre_drift(const int* aug, int k, int n0) {
+  return AUG ? max(min(aug[k], n0 - 1), -(1 << 20)) : 0;
+}
+
+template <bool AUG>
+__device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug) {
   __shared__ float lut[768];
   __shared__ unsigned rows[2][PRE_ROWB / 4];
   const int b = blockIdx.z;
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int H0 = a.sizes[2 * b], W0 = a.sizes[2 * b + 1];
+  const int dy = pre_drift<AUG>(aug, 3 * b, H0), dx = pre_drift<AUG>(aug, 3 * b + 1, W0);
+  const bool flip = AUG && aug[3 * b + 2] != 0;
+  const int Hd = AUG ? H0 - dy : H0, Wd = AUG ? W0 - dx : W0;     // the (drifted) image the resize rule sees
   if (x == 0 && blockIdx.y == 0 && a.scales) {
-    a.scales[2 * b] = (float)a.H / (float)H0;       // np.array([H/H0, W/W0], dtype=float32): float64 division then cast;
-    a.scales[2 * b + 1] = (float)a.W / (float)W0;   // identical for these integer ratios up to float32 rounding
+    a.scales[2 * b] = (float)a.H / (float)Hd;       // np.array([H/H0, W/W0], dtype=float32): float64 division then cast;
+    a.scales[2 * b + 1] = (float)a.W / (float)Wd;   // identical for these integer ratios up to float32 rounding
   }
   const unsigned char* img = a.src + a.offsets[b];
   const unsigned char* img_end = img + (long long)H0 * W0 * 3;
   // source coordinates (double scale like OpenCV, then float weights)
-  const double sclx = (double)W0 / (double)a.W, scly = (double)H0 / (double)a.H;
+  const double sclx = (double)Wd / (double)a.W, scly = (double)Hd / (double)a.H;
   auto src_x = [&](int xx, float& f) {
     f = (float)((xx + 0.5) * sclx - 0.5);
     int sx = (int)floorf(f); f -= (float)sx;
     if (sx < 0) { sx = 0; f = 0.f; }
-    if (sx >= W0 - 1) { sx = W0 - 1; f = 0.f; }
+    if (sx >= Wd - 1) { sx = Wd - 1; f = 0.f; }
     return sx;
   };
+  auto col = [&](int v) { return AUG ? (flip ? Wd - 1 - v : v) + dx : v; };     // V column -> image column
   // the workgroup's source column range [lo, hi] (sx is monotone in x): one segment per source row
   float fdummy;
   const int xa = blockIdx.x * 256, xb = min(a.W, xa + 256) - 1;
-  const int lo = src_x(xa, fdummy), hi = min(src_x(xb, fdummy) + 1, W0 - 1);
+  int lo = src_x(xa, fdummy), hi = min(src_x(xb, fdummy) + 1, Wd - 1);
+  if (AUG) {
+    const int ca = col(lo), cb = col(hi);
+    lo = max(min(ca, cb), 0); hi = min(max(ca, cb), W0 - 1);
+  }
+  const bool seg = !AUG || hi >= lo;                 // (AUG) false: every column of the workgroup lies in the fill region
   const int len = (hi - lo + 1) * 3;
   const bool staged = len + 8 <= PRE_ROWB;
   float fx;
   const int sx = src_x(min(x, a.W - 1), fx);
-  const int sx1 = min(sx + 1, W0 - 1);
+  const int sx1 = min(sx + 1, Wd - 1);
+  const int cx0 = col(sx), cx1 = col(sx1);
+  const bool vx0 = !AUG || cx0 >= 0, vx1 = !AUG || cx1 >= 0;
+  const int ux0 = AUG ? max(cx0, 0) : cx0, ux1 = AUG ? max(cx1, 0) : cx1;     // (a fill tap's address: any in-range one)
   const float ax0 = 1.f - fx, ax1 = fx;
   const long long plane = (long long)a.H * a.W;
   pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
@@ -100,13 +126,16 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) {
     float fy = (float)((y + 0.5) * scly - 0.5);
     int sy = (int)floorf(fy); fy -= (float)sy;
     if (sy < 0) { sy = 0; fy = 0.f; }
-    if (sy >= H0 - 1) { sy = H0 - 1; fy = 0.f; }
-    const int sy1 = min(sy + 1, H0 - 1);
+    if (sy >= Hd - 1) { sy = Hd - 1; fy = 0.f; }
+    const int sy1 = min(sy + 1, Hd - 1);
+    const int ry0 = sy + dy, ry1 = sy1 + dy;         // image rows (AUG: negative = fill)
+    const bool vy0 = !AUG || ry0 >= 0, vy1 = !AUG || ry1 >= 0;
+    const int uy0 = AUG ? max(ry0, 0) : ry0, uy1 = AUG ? max(ry1, 0) : ry1;
     int sh0 = 0, sh1 = 0;
     if (r) __syncthreads();                          // the previous row's readers are done with the segments
-    if (staged) {
-      sh0 = pre_stage(rows[0], img, img_end, ((long long)sy * W0 + lo) * 3, len);
-      sh1 = pre_stage(rows[1], img, img_end, ((long long)sy1 * W0 + lo) * 3, len);
+    if (staged && seg) {
+      if (vy0) sh0 = pre_stage(rows[0], img, img_end, ((long long)uy0 * W0 + lo) * 3, len);
+      if (vy1) sh1 = pre_stage(rows[1], img, img_end, ((long long)uy1 * W0 + lo) * 3, len);
     }
     __syncthreads();
     if (x >= a.W) continue;
@@ -116,21 +145,28 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) {
     if (staged) {
       const unsigned char* r0 = (const unsigned char*)rows[0] + sh0;
       const unsigned char* r1 = (const unsigned char*)rows[1] + sh1;
-      p00 = r0 + (sx - lo) * 3; p01 = r0 + (sx1 - lo) * 3; p10 = r1 + (sx - lo) * 3; p11 = r1 + (sx1 - lo) * 3;
+      const int ox0 = AUG ? (vx0 ? ux0 - lo : 0) : sx - lo, ox1 = AUG ? (vx1 ? ux1 - lo : 0) : sx1 - lo;
+      p00 = r0 + ox0 * 3; p01 = r0 + ox1 * 3; p10 = r1 + ox0 * 3; p11 = r1 + ox1 * 3;
     } else {
-      p00 = img + ((long long)sy * W0 + sx) * 3; p01 = img + ((long long)sy * W0 + sx1) * 3;
-      p10 = img + ((long long)sy1 * W0 + sx) * 3; p11 = img + ((long long)sy1 * W0 + sx1) * 3;
+      p00 = img + ((long long)uy0 * W0 + ux0) * 3; p01 = img + ((long long)uy0 * W0 + ux1) * 3;
+      p10 = img + ((long long)uy1 * W0 + ux0) * 3; p11 = img + ((long long)uy1 * W0 + ux1) * 3;
     }
+    const bool t00 = vy0 && vx0, t01 = vy0 && vx1, t10 = vy1 && vx0, t11 = vy1 && vx1;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float* l = lut + 256 * c;                                    // whiten (image.py:17) in float32: the table holds (v - mean) / std
-      const float v00 = l[p00[c]], v01 = l[p01[c]], v10 = l[p10[c]], v11 = l[p11[c]];
+      const float v00 = t00 ? l[p00[c]] : 0.f, v01 = t01 ? l[p01[c]] : 0.f;
+      const float v10 = t10 ? l[p10[c]] : 0.f, v11 = t11 ? l[p11[c]] : 0.f;
       const float r0 = v00 * ax0 + v01 * ax1;
       const float r1 = v10 * ax0 + v11 * ax1;
       o[c * plane] = r0 * ay0 + r1 * ay1;
     }
   }
 }
+
+__global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) { preprocess_body<false>(a, nullptr); }
+
+__global__ __launch_bounds__(256) void preprocess_aug_kernel(PreArgs a, const int* aug) { preprocess_body<true>(a, aug); }
 
 // src: device buffer holding the B images back to back (HWC uint8 RGB); offsets [B] byte offsets; sizes [B][2] =
 // (H0, W0) int32; out: NCHW fp32 [B][3][H][W]; scales: [B][2] fp32 or NULL; mean/std: 3 floats each (host).
@@ -160,47 +196,62 @@ struct PadCropArgs {
   int B, H, W;
 };
 
-__global__ __launch_bounds__(256) void preprocess_padcrop_kernel(PadCropArgs a) {
+// AUG: crop_or_pad of the drifted, flipped image V (Hd x Wd, see preprocess_body): padding / crops / shifts from (Hd, Wd).
+template <bool AUG>
+__device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, const int* aug) {
   __shared__ float lut[768];
   __shared__ unsigned row[PRE_ROWB / 4];
   const int b = blockIdx.z;
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int H0 = a.sizes[2 * b], W0 = a.sizes[2 * b + 1];
+  const int dy = pre_drift<AUG>(aug, 3 * b, H0), dx = pre_drift<AUG>(aug, 3 * b + 1, W0);
+  const bool flip = AUG && aug[3 * b + 2] != 0;
+  const int Hd = AUG ? H0 - dy : H0, Wd = AUG ? W0 - dx : W0;
   // (target - size) // 2 in front when padding, (size - target) // 2 cut in front when cropping
-  const int pt = H0 < a.H ? (a.H - H0) / 2 : 0, ct = H0 > a.H ? (H0 - a.H) / 2 : 0;
-  const int pl = W0 < a.W ? (a.W - W0) / 2 : 0, cl = W0 > a.W ? (W0 - a.W) / 2 : 0;
+  const int pt = Hd < a.H ? (a.H - Hd) / 2 : 0, ct = Hd > a.H ? (Hd - a.H) / 2 : 0;
+  const int pl = Wd < a.W ? (a.W - Wd) / 2 : 0, cl = Wd > a.W ? (Wd - a.W) / 2 : 0;
   if (x == 0 && blockIdx.y == 0) {
     if (a.padcrop) {
       int* pc = a.padcrop + 8 * b;
-      pc[0] = pt; pc[1] = H0 < a.H ? (a.H - H0) - pt : 0; pc[2] = pl; pc[3] = W0 < a.W ? (a.W - W0) - pl : 0;
-      pc[4] = ct; pc[5] = H0 > a.H ? (H0 - a.H) - ct : 0; pc[6] = cl; pc[7] = W0 > a.W ? (W0 - a.W) - cl : 0;
+      pc[0] = pt; pc[1] = Hd < a.H ? (a.H - Hd) - pt : 0; pc[2] = pl; pc[3] = Wd < a.W ? (a.W - Wd) - pl : 0;
+      pc[4] = ct; pc[5] = Hd > a.H ? (Hd - a.H) - ct : 0; pc[6] = cl; pc[7] = Wd > a.W ? (Wd - a.W) - cl : 0;
     }
     if (a.shifts) { a.shifts[2 * b] = (float)(ct - pt); a.shifts[2 * b + 1] = (float)(cl - pl); }
   }
+  auto col = [&](int v) { return AUG ? (flip ? Wd - 1 - v : v) + dx : v; };     // V column -> image column
   const int sx = x - pl + cl;
   const unsigned char* img = a.src + a.offsets[b];
   // the workgroup's source columns: [lo, hi] of the source row, clipped to the image (256 pixels = 768 bytes: always fits)
   const int xa = blockIdx.x * 256;
-  const int lo = max(xa - pl + cl, 0), hi = min(min(a.W, xa + 256) - 1 - pl + cl, W0 - 1);
+  int lo = max(xa - pl + cl, 0), hi = min(min(a.W, xa + 256) - 1 - pl + cl, Wd - 1);
+  if (AUG && hi >= lo) {
+    const int ca = col(lo), cb = col(hi);
+    lo = max(min(ca, cb), 0); hi = min(max(ca, cb), W0 - 1);
+  }
   const long long plane = (long long)a.H * a.W;
   pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
   for (int r = 0; r < PRE_ROWS; ++r) {
     const int y = blockIdx.y * PRE_ROWS + r;
     if (y >= a.H) break;                             // (uniform)
     const int sy = y - pt + ct;
-    const bool row_in = sy >= 0 && sy < H0 && hi >= lo;
+    const bool row_in = sy >= 0 && sy < Hd && hi >= lo && (!AUG || sy + dy >= 0);
     int sh = 0;
     if (r) __syncthreads();
-    if (row_in) sh = pre_stage(row, img, img + (long long)H0 * W0 * 3, ((long long)sy * W0 + lo) * 3, (hi - lo + 1) * 3);
+    if (row_in) sh = pre_stage(row, img, img + (long long)H0 * W0 * 3, ((long long)(AUG ? sy + dy : sy) * W0 + lo) * 3, (hi - lo + 1) * 3);
     __syncthreads();
     if (x >= a.W) continue;
-    const bool inside = row_in && sx >= 0 && sx < W0;
+    const int cx = col(sx);
+    const bool inside = row_in && sx >= 0 && sx < Wd && (!AUG || cx >= 0);
     float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
-    const unsigned char* p = (const unsigned char*)row + sh + (inside ? (sx - lo) * 3 : 0);
+    const unsigned char* p = (const unsigned char*)row + sh + (inside ? (cx - lo) * 3 : 0);
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c * plane] = inside ? lut[256 * c + p[c]] : 0.f;
   }
 }
+
+__global__ __launch_bounds__(256) void preprocess_padcrop_kernel(PadCropArgs a) { preprocess_padcrop_body<false>(a, nullptr); }
+
+__global__ __launch_bounds__(256) void preprocess_padcrop_aug_kernel(PadCropArgs a, const int* aug) { preprocess_padcrop_body<true>(a, aug); }
 
 // Arguments as sqd_preprocess_u8_fwd; shifts: [B][2] fp32 (dy, dx) or NULL; padcrop: [B][8] int32 = padding (top, bottom, left,
 // right) then crops (top, bottom, left, right), or NULL.
@@ -212,5 +263,29 @@ extern "C" int sqd_preprocess_u8_padcrop_fwd(const unsigned char* src, const lon
   a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.shifts = shifts; a.padcrop = padcrop; a.B = B; a.H = H; a.W = W;
   for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
   hipLaunchKernelGGL(preprocess_padcrop_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  return sqd_launch_status();
+}
+
+// Training forms (reference train phase: drift + flip before the resize / crop_or_pad).  aug: device int32 [B][3] = (dy, dx, flipped)
+// per image; scales = (H / Hd, W / Wd) and padding / crops / shifts are those of the drifted size (Hd, Wd) = (H0 - dy, W0 - dx).
+// Other arguments as sqd_preprocess_u8_fwd / sqd_preprocess_u8_padcrop_fwd.
+extern "C" int sqd_preprocess_u8_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug, float* out,
+                                         float* scales, const float* mean3, const float* std3, int B, int H, int W, void* stream) {
+  SQD_CHECK_ARG(src && offsets && sizes && aug && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
+  PreArgs a;
+  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.scales = scales; a.B = B; a.H = H; a.W = W;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
+  hipLaunchKernelGGL(preprocess_aug_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_preprocess_u8_padcrop_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                                 float* out, float* shifts, int* padcrop, const float* mean3, const float* std3, int B, int H,
+                                                 int W, void* stream) {
+  SQD_CHECK_ARG(src && offsets && sizes && aug && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
+  PadCropArgs a;
+  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.shifts = shifts; a.padcrop = padcrop; a.B = B; a.H = H; a.W = W;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
+  hipLaunchKernelGGL(preprocess_padcrop_aug_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug);
   return sqd_launch_status();
 }

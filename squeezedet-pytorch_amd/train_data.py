@@ -1,0 +1,202 @@
+"""``TrainLoader``: the training side of ``Detector.detect_dataset`` -- batches of a reference-protocol dataset (``load_image(i)``,
+``load_annotations(i)``, ``__len__``, ``rgb_mean``, ``rgb_std``; src/datasets/base.py, src/datasets/kitti.py) delivered on the
+device as ``{'image', 'image_meta', 'gt'}``, augmented the reference's train-phase way (``augment``), ready for
+``Trainer.run_epoch``.
+
+``cfg.num_workers`` threads load the next batch and pack its raw pixels into a pinned staging buffer owned by the loader (two,
+used alternately; one is refilled only after an event shows its previous host-to-device copy has finished).  The main thread
+draws the epoch permutation and every augmentation parameter from ONE ``np.random.RandomState``, in dataset order, so the batches
+do not depend on ``num_workers``.  This departs on purpose from the reference, whose forked DataLoader workers each start from
+the same numpy state and so repeat one another's draws; with ``shuffle=False`` and a fixed seed the draws here are those of a
+single-process reference run under ``np.random.seed(seed)``.
+
+Data parallel: every rank draws for the whole global batch (``cfg.batch_size`` images) and keeps its ``shard_sizes`` slice, so
+the union of the ranks' batches is the one-rank batch.  The other ranks' images are only needed for their sizes (the drift
+bounds); a dataset may provide ``image_size(i) -> (H, W)`` to spare loading them, and sizes are cached across epochs.
+"""
+from __future__ import annotations
+
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import augment
+from .annotations import encode_annotations
+from .trainer import shard_sizes
+
+
+class _Stage:
+    """One pinned upload buffer and the event of its latest host-to-device copy."""
+
+    def __init__(self):
+        self.buf = None
+        self.np = None
+        self.copied = None
+
+    def acquire(self, nbytes):
+        if self.copied is not None:
+            self.copied.synchronize()                 # the previous copy out of this buffer has finished
+            self.copied = None
+        if self.buf is None or self.buf.numel() < nbytes:
+            self.buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+            self.np = self.buf.numpy()
+        return self.np
+
+
+class TrainLoader:
+    """Iterable of device-resident training batches over ``dataset`` (see the module docstring).
+
+    cfg fields read: batch_size (global), input_size, num_workers, device, drift_prob, flip_prob, seed, forbid_resize, anchors,
+    num_classes.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState once; each epoch (``iter``) continues it."""
+
+    def __init__(self, dataset, cfg, seed=None, shuffle=True, drop_last=True, rank=0, world=1):
+        self.dataset, self.cfg = dataset, cfg
+        self.shuffle, self.drop_last = bool(shuffle), bool(drop_last)
+        self.rank, self.world = int(rank), int(world)
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f'TrainLoader: rank {rank} outside world {world}')
+        self.batch_size = int(cfg.batch_size)
+        self.rng = np.random.RandomState(getattr(cfg, 'seed', 42) if seed is None else seed)
+        self.drift_prob = float(getattr(cfg, 'drift_prob', 1.0))
+        self.flip_prob = float(getattr(cfg, 'flip_prob', 0.5))
+        self.forbid_resize = bool(getattr(cfg, 'forbid_resize', False))
+        self.workers = int(getattr(cfg, 'num_workers', 4))
+        self.device = torch.device(cfg.device)
+        self.rgb_mean = getattr(dataset, 'rgb_mean', augment.KITTI_RGB_MEAN)
+        self.rgb_std = getattr(dataset, 'rgb_std', augment.KITTI_RGB_STD)
+        self._sizes = {}
+        self._stages = [_Stage(), _Stage()]
+        n = len(dataset)
+        last = n % self.batch_size
+        if self.world > 1 and not self.drop_last and 0 < last < self.world:
+            raise ValueError(f'TrainLoader: the last batch ({last} images) leaves a rank without images; use drop_last')
+
+    def __len__(self):
+        n = len(self.dataset)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _global_batches(self):
+        n = len(self.dataset)
+        order = self.rng.permutation(n) if self.shuffle else np.arange(n)
+        return [order[i:i + self.batch_size] for i in range(0, len(self) * self.batch_size, self.batch_size) if i < n]
+
+    def _local(self, idxs):
+        sh = shard_sizes(len(idxs), self.world)
+        lo = sum(sh[:self.rank])
+        return lo, lo + sh[self.rank]
+
+    def _size_of(self, i):
+        if i not in self._sizes:
+            if hasattr(self.dataset, 'image_size'):
+                h, w = self.dataset.image_size(i)[:2]
+            else:
+                h, w = np.asarray(self.dataset.load_image(i)[0]).shape[:2]
+            self._sizes[i] = (int(h), int(w))
+        return self._sizes[i]
+
+    def _load(self, i):
+        im = self.dataset.load_image(i)
+        im = im[0] if isinstance(im, tuple) else im
+        im = augment.as_u8_image(im, f'TrainLoader: image {i}')
+        self._sizes[int(i)] = (int(im.shape[0]), int(im.shape[1]))
+        return im
+
+    def _prepare(self, pool, stage, idxs):
+        """Start loading the batch's own images and every annotation of the global batch and packing the pixels into ``stage``
+        (worker threads; inline without workers).  The global batch's other images only report their sizes.  Returns a function
+        that waits for all of it and returns (local sizes, header bytes, pixel offsets, total bytes, annotations, global sizes)."""
+        lo, hi = self._local(idxs)
+        mine = [int(i) for i in idxs[lo:hi]]
+
+        def others():
+            return {int(i): self._size_of(int(i)) for k, i in enumerate(idxs) if not lo <= k < hi}
+
+        def annotations():
+            return [self.dataset.load_annotations(int(i)) for i in idxs]
+
+        def pack(ims, parallel):
+            sizes = [im.shape[:2] for im in ims]
+            hdr, offsets, total = augment.pack_layout(sizes)
+            pk = stage.acquire(total)
+
+            def put(k):                               # (numpy releases the GIL while copying)
+                pk[hdr + offsets[k]:hdr + offsets[k] + ims[k].size] = np.ascontiguousarray(ims[k]).reshape(-1)
+            if parallel:
+                for f in [pool.submit(put, k) for k in range(len(ims))]:
+                    f.result()
+            else:
+                for k in range(len(ims)):
+                    put(k)
+            return sizes, hdr, offsets, total
+
+        if pool is None:
+            packed, oth, ann = pack([self._load(i) for i in mine], False), others(), annotations()
+            return lambda: self._gather(idxs, packed, oth, ann)
+        f_ims = [pool.submit(self._load, i) for i in mine]
+        f_oth = pool.submit(others)
+        f_ann = pool.submit(annotations)
+        # the packer waits only on tasks queued before it (no deadlock in a one-thread pool); it fans the copies out to the other
+        # threads when there are any
+        f_pack = pool.submit(lambda: pack([f.result() for f in f_ims], self.workers > 1))
+        return lambda: self._gather(idxs, f_pack.result(), f_oth.result(), f_ann.result())
+
+    def _gather(self, idxs, packed, oth, ann):
+        sizes, hdr, offsets, total = packed
+        lo, hi = self._local(idxs)
+        gsizes = [sizes[k - lo] if lo <= k < hi else oth[int(i)] for k, i in enumerate(idxs)]
+        return sizes, hdr, offsets, total, ann, gsizes
+
+    def _plan_batch(self, idxs, gsizes, ann):
+        """The host half of a batch: draws for the whole global batch (main thread, batch order), then this rank's slice of the
+        draws, transformed boxes, per-image metas and class ids."""
+        lo, hi = self._local(idxs)
+        box_all = [np.asarray(b, np.float32).reshape(-1, 4) for _, b in ann]
+        aug = augment.draw_augmentation(self.rng, gsizes, box_all, self.drift_prob, self.flip_prob)[lo:hi]
+        tb, metas = zip(*[augment.transform_boxes(b, s, a, self.cfg.input_size, self.forbid_resize)
+                          for b, s, a in zip(box_all[lo:hi], gsizes[lo:hi], aug)])
+        return {'index': np.asarray(idxs[lo:hi], np.int64), 'aug': aug, 'boxes': list(tb), 'metas': list(metas),
+                'class_ids': [np.asarray(c) for c, _ in ann[lo:hi]]}
+
+    def plan(self):
+        """One epoch's host side only (no pixels, no device): per batch this rank's dataset indices, draws, transformed boxes.
+        Consumes the loader's RandomState exactly as iterating the epoch does."""
+        for idxs in self._global_batches():
+            yield self._plan_batch(idxs, [self._size_of(int(i)) for i in idxs], [self.dataset.load_annotations(int(i)) for i in idxs])
+
+    def _emit(self, stage, idxs, prepared):
+        sizes, hdr, offsets, total, ann, gsizes = prepared
+        lo, hi = self._local(idxs)
+        p = self._plan_batch(idxs, gsizes, ann)
+        aug, tb, metas = p['aug'], p['boxes'], p['metas']
+        augment.write_header(stage.np, offsets, sizes, aug)
+        B = hi - lo
+        H, W = int(self.cfg.input_size[0]), int(self.cfg.input_size[1])
+        dev_buf = torch.empty(total, dtype=torch.uint8, device=self.device)
+        dev_buf.copy_(stage.buf[:total], non_blocking=True)
+        stage.copied = torch.cuda.Event()
+        stage.copied.record(torch.cuda.current_stream(self.device))
+        out = torch.empty(B, 3, H, W, device=self.device, dtype=torch.float32)
+        augment.launch(dev_buf, B, hdr, self.cfg.input_size, out, self.forbid_resize, self.rgb_mean, self.rgb_std)
+        gt = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device)
+        meta = augment.batch_meta(metas, sizes, self.rgb_mean, self.rgb_std)
+        meta['index'] = p['index']
+        return {'image': out, 'image_meta': meta, 'gt': gt}
+
+    def __iter__(self):
+        batches = self._global_batches()
+        if not batches:
+            return
+        pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix='sqd-train') if self.workers > 0 else None
+        try:
+            pending = self._prepare(pool, self._stages[0], batches[0])
+            for it, idxs in enumerate(batches):
+                prepared = pending()
+                with torch.cuda.device(self.device):
+                    batch = self._emit(self._stages[it % 2], idxs, prepared)
+                if it + 1 < len(batches):
+                    pending = self._prepare(pool, self._stages[(it + 1) % 2], batches[it + 1])
+                yield batch
+        finally:
+            if pool is not None:
+                pool.shutdown(wait=True, cancel_futures=True)
