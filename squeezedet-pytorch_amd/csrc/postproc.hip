@@ -426,7 +426,7 @@ __global__ __launch_bounds__(DET_SCORE_THREADS) void detect_kernel(DetArgs a) {
 static int launch_detect(DetArgs a, hipStream_t stream) {
   if (a.K < 1 || a.K > DET_K) return SQD_ERR_UNSUPPORTED;                 // one wave holds the NMS bit matrix
   const size_t lds = (size_t)((a.A + 3) & ~3) * 4 + (size_t)a.A * 2 + 16;  // keys + uint16 candidate indices
-  if (a.A > 65535 || lds > 150 * 1024) return SQD_ERR_UNSUPPORTED;        // A <= 25600 anchors per image
+  if (a.A > 65535 || lds > 150 * 1024) return SQD_ERR_UNSUPPORTED;        // A <= 25596 anchors per image
   static SqdDevOnce lds_once;                                              // raise the dynamic-LDS cap once per device
   if (lds > 48 * 1024 && sqd_max_lds_once(lds_once, (const void*)detect_kernel, 150 * 1024) != SQD_OK) return SQD_ERR_LAUNCH;
   // pred mode with a workspace: eight workgroups score an image, its last arriver selects and suppresses (the workspace holds B x

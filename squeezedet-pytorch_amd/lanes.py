@@ -18,7 +18,9 @@ batch i + 1.  Around the lanes:
 A batch shape a lane sees for the first time runs as eager launches on the lane's stream (which also warms the allocator);
 the second time it is captured; afterwards it replays.  The ragged last batch of a dataset therefore costs no capture.  Graph
 replay, eager launches and ``Detector.detect_images`` produce the same bits (tests/test_lanes_gpu.py).  A failed capture keeps
-that shape on eager launches and sets ``degraded`` (bench.py reports it next to ``value``).
+that shape on eager launches and sets ``degraded`` (bench.py reports it next to ``value``).  New weights drop the captured steps;
+new detection parameters (``cfg.keep_top_k``, ``nms_thresh``, ``score_thresh``, ``input_size``, ``num_classes``) drop the captured
+steps and the result buffers as well.
 """
 from __future__ import annotations
 
@@ -220,6 +222,7 @@ class DetectStream:
         self._seq = 0
         self._eager_done = None                              # (event, lane index) of the latest eager run: see _launch
         self._weights = self._weights_signature()
+        self._params = self._params_signature()         # detection parameters the lane buffers and graphs were made for (_bufs)
 
     # ------------------------------------------------------------------------------------------------------------------
     # raw-image path
@@ -385,6 +388,14 @@ class DetectStream:
         return lane
 
     def _bufs(self, lane, n, with_input=True):
+        sig = self._params_signature()
+        if sig != self._params:
+            # the detection parameters changed: captured steps hold the old thresholds and K, the packed result buffers are sized
+            # for the old K and input size -- drop both on every lane (batches still queued keep their own buffers until fetched)
+            torch.cuda.synchronize(self.device)
+            for ln in self._lanes:
+                ln.graphs.clear(); ln.seen.clear(); ln.bufs.clear()
+            self._params = sig
         nb = lane.bufs.get(n)
         K = int(self.cfg.keep_top_k)
         if nb is None:
@@ -463,6 +474,11 @@ class DetectStream:
 
     def _weights_signature(self):
         return tuple((p._version, p.data_ptr()) for p in self.det.model.parameters())
+
+    def _params_signature(self):
+        cfg = self.cfg
+        return (int(cfg.keep_top_k), float(cfg.nms_thresh), float(cfg.score_thresh), tuple(int(v) for v in cfg.input_size),
+                int(cfg.num_classes), int(cfg.num_anchors))
 
     def discard(self, st):
         """Give an un-submitted ``Staging`` back (its batch takes another route)."""

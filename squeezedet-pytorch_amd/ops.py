@@ -623,13 +623,36 @@ def _det_workspace(B, A, device):
     return torch.zeros(det_workspace_words(B, A), device=device, dtype=torch.int32)
 
 
+def _check_score_thresh(name, score_thresh):
+    # the kernel's candidate key is the fp32 score bits if score > score_thresh, else 0 ("no candidate"): exact for thresholds >= 0
+    # only (a negative one would drop scores of exactly 0 and, in the dense filter, rank negative scores first)
+    if not float(score_thresh) >= 0.0:
+        raise ValueError(f'{name}: score_thresh must be >= 0 (got {score_thresh})')
+
+
+def _check_det_out(bufs, B, K, device):
+    """A caller's result buffers must be exactly what the kernel writes: it stores B x K rows without knowing their sizes."""
+    if len(bufs) not in (5, 6):
+        raise ValueError(f'detect: out must hold 5 result tensors (+ an optional workspace), got {len(bufs)}')
+    want = (((B,), torch.int32), ((B, K), torch.int64), ((B, K), torch.float32), ((B, K, 4), torch.float32), ((B, K), torch.int32))
+    for i, (t, (shape, dt)) in enumerate(zip(bufs[:5], want)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or t.device != device or not t.is_contiguous():
+            got = (tuple(t.shape), t.dtype, str(t.device)) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f'detect: out[{i}] must be a contiguous {dt} {shape} tensor on {device}, got {got}')
+    if bufs[3].data_ptr() % 16:
+        raise ValueError('detect: out[3] (boxes) must be 16-byte aligned')
+
+
 def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None):
     """Fused decode + top-k + class-wise NMS + threshold for a batch.
     Returns (count int32 [B], class_ids int64 [B,K], scores [B,K], boxes [B,K,4], anchor_idx int32 [B,K]).  ``scales`` [B,2] =
     (sy, sx): boxes are divided by them; ``shifts`` [B,2] = (dy, dx): added afterwards (the padding / crops terms of
-    ``boxes_postprocess``, src/utils/boxes.py:149-155)."""
+    ``boxes_postprocess``, src/utils/boxes.py:149-155).  ``out``: the five result tensors (checked against B and ``keep_top_k``) and
+    optionally the key workspace; a workspace smaller than ``det_workspace_words`` means one workgroup per image.
+    ``score_thresh`` must be >= 0."""
     if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
         raise ValueError(f'detect: bad pred {tuple(pred.shape)}')
+    _check_score_thresh('detect', score_thresh)
     pred = pred.contiguous()
     B, A, _ = pred.shape
     if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
@@ -638,11 +661,13 @@ def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4
         raise ValueError('detect: scales must be fp32 [B,2] (sy, sx)')
     if shifts is not None and (tuple(shifts.shape) != (B, 2) or shifts.dtype != torch.float32 or shifts.device != pred.device or not shifts.is_contiguous()):
         raise ValueError('detect: shifts must be contiguous fp32 [B,2] (dy, dx)')
+    if out is not None:
+        _check_det_out(out, B, int(keep_top_k), pred.device)
     bufs = out if out is not None else _det_buffers(B, keep_top_k, pred.device, A)
     if len(bufs) == 5:
         bufs = tuple(bufs) + (_det_workspace(B, A, pred.device),)
     cnt, cls, sc, bx, idx, keys = bufs
-    if keys.dtype != torch.int32 or keys.device != pred.device:
+    if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int32 or keys.device != pred.device:
         raise ValueError('detect: workspace must be an int32 tensor on the same device')
     if keys.numel() < det_workspace_words(B, A) or not keys.is_contiguous():
         keys = None                                  # (a caller-made placeholder: one workgroup per image)
@@ -658,11 +683,13 @@ def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4
 
 
 def filter_dense(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3):
-    """``Detector.filter`` on already decoded dense tensors ([B,A] / [B,A,4])."""
+    """``Detector.filter`` on already decoded dense tensors ([B,A] / [B,A,4]).  ``score_thresh`` must be >= 0."""
     if scores.dim() != 2 or class_ids.shape != scores.shape or tuple(boxes.shape) != tuple(scores.shape) + (4,):
         raise ValueError('filter: shape mismatch')
-    if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda:
+    if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda \
+            or class_ids.device != scores.device or boxes.device != scores.device:
         raise ValueError('filter: dtype/device mismatch')
+    _check_score_thresh('filter', score_thresh)
     B, A = scores.shape
     bufs = _det_buffers(B, keep_top_k, scores.device, A)
     cnt, cls, sc, bx, idx, keys = bufs

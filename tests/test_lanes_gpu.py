@@ -163,6 +163,33 @@ def test_stream_sees_new_weights():
     assert differs
 
 
+def test_stream_follows_detection_parameters():
+    """Captured lane steps bake in keep_top_k / nms_thresh / score_thresh, and the packed result buffers are sized for keep_top_k: a
+    threshold sweep on one Detector must still give what detect_images gives, and a larger keep_top_k must get larger buffers."""
+    det, cfg = _detector(batch_size=2)
+    images = _images(2, [(375, 1242), (370, 1224)], seed=5)
+    ex = det.stream()
+
+    def stream_equals_detect_images():
+        want = det.detect_images(images)
+        got = list(det.detect_stream([images] * 5))                     # 2 lanes: eager, eager, capture, capture, replay
+        assert len(got) == 5
+        for res in got:
+            for r, w in zip(res, want):
+                _same(r, w)
+        return [len(w.get('scores', ())) for w in want]
+
+    n0 = stream_equals_detect_images()
+    assert stream_equals_detect_images() == n0 and ex.captures == 2   # second pass: replays only
+    cfg.score_thresh, cfg.nms_thresh = 0.05, 0.6
+    n1 = stream_equals_detect_images()
+    assert n1 != n0 and ex.captures == 4
+    cfg.keep_top_k = 8
+    assert max(stream_equals_detect_images()) <= 8
+    cfg.keep_top_k = 64
+    assert stream_equals_detect_images() == n1 and ex.captures == 8
+
+
 def test_stream_refuses_what_it_cannot_run():
     det, cfg = _detector(batch_size=2)
     ex = det.stream()
