@@ -1,0 +1,545 @@
+"""GPU tier: every GEMM-type launch of the four benchmarked steps (inference and training of SqueezeDet at bs=20 and SqueezeDet+ at
+bs=16, 384x1248, shipped tuning table) held to fp32 accuracy against a float64 reference, element by element.
+
+Each case is one distinct (arch, batch, kernel, shape tag) entry of ``plan.inference_launch_plan`` / ``plan.training_launch_plan``
+(``CASES``; tests/test_fp64_coverage.py keeps the list equal to the plans).  The cases run inside the real step: the model is built
+with the benchmark's synthetic weights, images and targets (fixed seeds), and every ``ops`` entry point it calls is wrapped.  The
+wrapper copies the launch's operands, runs the kernel, reads the (kernel, tag) its KernelTimer bracket recorded and compares every
+output with tests/fp64_ref.py evaluated on those same operands -- so each launch is checked on its own inputs, at the plan's batch and
+shape, on the kernel the plan names.  Weight gradients are checked after the slab reduction the step ships (``wgrad_reduce_batched``).
+Dropout runs at p = 0: the planned epilogue kernels launch with an all-keep mask (mask values are tested elsewhere).
+
+Two bars per output (fp64_ref.bars):
+* L: |got - ref64| <= 2^-18 * M for every element (exact where M = 0): no dropped, duplicated or misplaced term anywhere;
+* P: per 64-channel block rms(err) <= k * max(rms(err32), 2^-24 rms(ref64)), per tensor max|err| <= 2k * max(max|err32|, ...), with
+  err32 the plain fp32 chain's error: k = 2 for the direct-GEMM families, 4 for the Winograd ones (bridges included).
+  Weight and bias gradients sum 37k-599k pixels: there the plain chain is restated as the kernels' own algorithm
+  (fp64_ref.wgrad_split_k: the kernel's pixel blocks, its S slabs accumulated in order, the shipped
+  slab reduction) -- a whole-axis fp32 GEMM is 2-20x less accurate than the kernels and could not tell a 3-product bf16 split from
+  fp32.  k stays 2 for the direct weight gradients; the Winograd ones keep their family's 4 (the restatement is of the summation
+  structure, in the direct form: it does not restate the transforms).  The Winograd weight gradient
+  mixes every offset of its 4x4 input tile with its 2x2 output tile, so its bar L uses that form's magnitude
+  (fp64_ref.wgrad_wino_magnitude); the per-tap ratio is logged beside it.
+``maxpool_fwd`` does no arithmetic: bit-exact against the max of its own input.
+"""
+import re
+
+import pytest
+import torch
+
+import fp64_ref as R
+import squeezedet_pytorch_amd as sqd
+from squeezedet_pytorch_amd import synthetic
+
+pytestmark = pytest.mark.gpu
+
+INPUT = (384, 1248)
+STEPS = (('squeezedet', 20), ('squeezedetplus', 16))
+
+CASES = [
+    ('squeezedet', 20, 'stem_pool_sq<3>', 'stem+pool+squeeze 384x1248 S16'),
+    ('squeezedet', 20, 'fire_bridge', 'fire C16 E64+64 -> S16 96x312'),
+    ('squeezedet', 20, 'fire_pool_bridge', 'fire C16 E64+64 -> pool -> S32 96x312'),
+    ('squeezedet', 20, 'conv_ws<4,8>', '1tap C32 N128 48x156'),
+    ('squeezedet', 20, 'conv_wino_us<2,8>', '9tap C32 N128 48x156'),
+    ('squeezedet', 20, 'conv_ws<2,8>', '1tap C256 N32 48x156'),
+    ('squeezedet', 20, 'maxpool_fwd', 'pool C256 48x156'),
+    ('squeezedet', 20, 'conv_dma<1,32,1,3,4>', '1tap C256 N48 24x78'),
+    ('squeezedet', 20, 'conv_ws<4,8>', '1tap C48 N192 24x78'),
+    ('squeezedet', 20, 'conv_wino<2,4>', '9tap C48 N192 24x78'),
+    ('squeezedet', 20, 'conv_dma<1,32,1,3,4>', '1tap C384 N48 24x78'),
+    ('squeezedet', 20, 'conv_dma<1,32,1,2,4>', '1tap C384 N64 24x78'),
+    ('squeezedet', 20, 'conv_ws<4,8>', '1tap C64 N256 24x78'),
+    ('squeezedet', 20, 'conv_wino_us<2,4>', '9tap C64 N256 24x78'),
+    ('squeezedet', 20, 'conv_dma<1,32,1,2,4>', '1tap C512 N64 24x78'),
+    ('squeezedet', 20, 'conv_ws<2,8>', '1tap C512 N96 24x78'),
+    ('squeezedet', 20, 'conv_ws<6,8>', '1tap C96 N384 24x78'),
+    ('squeezedet', 20, 'conv_wino<2,4>', '9tap C96 N384 24x78'),
+    ('squeezedet', 20, 'conv_dma<1,32,1,6,4>', '1tap C768 N96 24x78'),
+    ('squeezedet', 20, 'conv_wino_vs', '9tap C768 N72 24x78'),
+    ('squeezedet', 20, 'stem_pool_sq_train<3>', 'stem+pool+squeeze 384x1248 S16'),
+    ('squeezedet', 20, 'fire_bridge_save', 'fire C16 E64+64 -> S16 96x312'),
+    ('squeezedet', 20, 'fire_pool_bridge_save', 'fire C16 E64+64 -> pool -> S32 96x312'),
+    ('squeezedet', 20, 'conv_wino_sk', '9tap C96 N384 24x78'),
+    ('squeezedet', 20, 'conv_wgrad_wino', 'wgrad 9tap C768 N72 24x78'),
+    ('squeezedet', 20, 'conv_wino_sk', '9tap C72 N768 24x78'),
+    ('squeezedet', 20, 'conv_dma<1,64,1,3,4>', '1tap C384 N96 24x78'),
+    ('squeezedet', 20, 'conv_wino<2,4>', '9tap C384 N96 24x78'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C768 N96 24x78'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C512 N96 24x78'),
+    ('squeezedet', 20, 'conv_dma<1,32,1,2,4>', '1tap C256 N64 24x78'),
+    ('squeezedet', 20, 'conv_wino<2,4>', '9tap C256 N64 24x78'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C512 N64 24x78'),
+    ('squeezedet', 20, 'conv_wgrad_group<1>', 'wgrad 1tap C96 N384 + C96 N384 + C64 N256 + C64 N256 24x78'),
+    ('squeezedet', 20, 'conv_wgrad_wino_group', 'wgrad 9tap C96 N384 + C96 N384 + C64 N256 + C64 N256 24x78'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C384 N64 24x78'),
+    ('squeezedet', 20, 'conv_dma<1,32,1,3,4>', '1tap C192 N48 24x78'),
+    ('squeezedet', 20, 'conv_wino<1,4>', '9tap C192 N48 24x78'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C384 N48 24x78'),
+    ('squeezedet', 20, 'conv_wgrad_group<1>', 'wgrad 1tap C48 N192 + C48 N192 24x78'),
+    ('squeezedet', 20, 'conv_wgrad_wino_group', 'wgrad 9tap C48 N192 + C48 N192 24x78'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C256 N48 24x78'),
+    ('squeezedet', 20, 'maxpool_bwd', 'poolbwd C256 48x156'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C32 N128 48x156'),
+    ('squeezedet', 20, 'conv_wino_us<1,4>', '9tap C128 N32 48x156'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C256 N32 48x156'),
+    ('squeezedet', 20, 'conv_wgrad_wino_group', 'wgrad 9tap C32 N128 + C32 N128 48x156'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C128 N32 48x156'),
+    ('squeezedet', 20, 'maxpool_bwd', 'poolbwd C128 96x312'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C16 N64 96x312'),
+    ('squeezedet', 20, 'conv_wino_us<1,4>', '9tap C64 N16 96x312'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C128 N16 96x312'),
+    ('squeezedet', 20, 'conv_wgrad_wino_group', 'wgrad 9tap C16 N64 + C16 N64 96x312'),
+    ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C64 N16 96x312'),
+    ('squeezedet', 20, 'stem_wgrad_pooled<3>', 'stem wgrad (pooled) 384x1248'),
+    ('squeezedet', 20, 'wgrad_reduce_batched', '31 layers'),
+    ('squeezedetplus', 16, 'stem_pool<7>', 'stem+pool 384x1248'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C96 N96 96x312'),
+    ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C96 N64 96x312'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C96 N64 96x312'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C128 N96 96x312'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C128 N192 96x312'),
+    ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C192 N128 96x312'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C192 N128 96x312'),
+    ('squeezedetplus', 16, 'maxpool_fwd', 'pool C256 96x312'),
+    ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C256 N192 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C192 N128 48x156'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C192 N128 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C256 N288 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C288 N192 48x156'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C288 N192 48x156'),
+    ('squeezedetplus', 16, 'conv_dma<1,32,1,6,4>', '1tap C384 N288 48x156'),
+    ('squeezedetplus', 16, 'conv_dma<1,32,1,6,4>', '1tap C384 N384 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C384 N256 48x156'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C384 N256 48x156'),
+    ('squeezedetplus', 16, 'maxpool_fwd', 'pool C512 48x156'),
+    ('squeezedetplus', 16, 'conv_dma<1,64,1,3,4>', '1tap C512 N384 24x78'),
+    ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C384 N256 24x78'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C384 N256 24x78'),
+    ('squeezedetplus', 16, 'conv_wino_vs', '9tap C512 N72 24x78'),
+    ('squeezedetplus', 16, 'conv_wino_sk', '9tap C384 N256 24x78'),
+    ('squeezedetplus', 16, 'conv_wgrad_wino', 'wgrad 9tap C512 N72 24x78'),
+    ('squeezedetplus', 16, 'conv_wino_sk', '9tap C72 N512 24x78'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C256 N384 24x78'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C256 N384 24x78'),
+    ('squeezedetplus', 16, 'conv_wgrad<1>', 'wgrad 1tap C512 N384 24x78'),
+    ('squeezedetplus', 16, 'conv_dma<1,64,1,4,4>', '1tap C384 N512 24x78'),
+    ('squeezedetplus', 16, 'conv_wgrad_group<1>', 'wgrad 1tap C384 N256 + C384 N256 + C384 N256 24x78'),
+    ('squeezedetplus', 16, 'conv_wgrad_wino_group', 'wgrad 9tap C384 N256 + C384 N256 + C384 N256 24x78'),
+    ('squeezedetplus', 16, 'maxpool_bwd', 'poolbwd C512 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C256 N384 48x156'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C256 N384 48x156'),
+    ('squeezedetplus', 16, 'conv_wgrad<1>', 'wgrad 1tap C384 N384 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C192 N288 48x156'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C192 N288 48x156'),
+    ('squeezedetplus', 16, 'conv_wgrad<1>', 'wgrad 1tap C384 N288 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C288 N384 48x156'),
+    ('squeezedetplus', 16, 'conv_wgrad_group<1>', 'wgrad 1tap C384 N256 + C288 N192 + C288 N192 48x156'),
+    ('squeezedetplus', 16, 'conv_wgrad<1>', 'wgrad 1tap C256 N288 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C288 N256 48x156'),
+    ('squeezedetplus', 16, 'conv_wgrad_wino_group', 'wgrad 9tap C384 N256 + C288 N192 + C288 N192 + C192 N128 48x156'),
+    ('squeezedetplus', 16, 'squeeze_bwd', 'sqbwd C192 N128 48x156'),
+    ('squeezedetplus', 16, 'conv_wino<2,8>', '9tap C128 N192 48x156'),
+    ('squeezedetplus', 16, 'conv_wgrad<1>', 'wgrad 1tap C256 N192 48x156'),
+    ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C192 N256 48x156'),
+    ('squeezedetplus', 16, 'maxpool_bwd', 'poolbwd C256 96x312'),
+    ('squeezedetplus', 16, 'squeeze_bwd', 'sqbwd C192 N128 96x312'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C128 N192 96x312'),
+    ('squeezedetplus', 16, 'conv_wgrad<1>', 'wgrad 1tap C128 N192 96x312'),
+    ('squeezedetplus', 16, 'squeeze_bwd', 'sqbwd C96 N64 96x312'),
+    ('squeezedetplus', 16, 'conv_wino<2,4>', '9tap C64 N96 96x312'),
+    ('squeezedetplus', 16, 'squeeze_bwd', 'sqbwd C128 N96 96x312'),
+    ('squeezedetplus', 16, 'conv_wgrad_wino_group', 'wgrad 9tap C192 N128 + C96 N64 + C96 N64 96x312'),
+    ('squeezedetplus', 16, 'squeeze_bwd', 'sqbwd C96 N96 96x312'),
+    ('squeezedetplus', 16, 'stem_wgrad_pooled<7>', 'stem wgrad (pooled) 384x1248'),
+    ('squeezedetplus', 16, 'wgrad_reduce_batched', '31 layers'),
+]
+
+# the families the teeth test runs through the degraded emulations (first launch of each in the steps above)
+FAMILIES = ['conv_ws', 'conv_dma', 'conv_wino', 'conv_wino_us', 'conv_wino_sk', 'conv_wino_vs', 'fire_bridge', 'fire_bridge_save',
+            'fire_pool_bridge', 'fire_pool_bridge_save', 'stem_pool', 'stem_pool_sq', 'stem_pool_sq_train', 'maxpool_bwd', 'squeeze_bwd',
+            'conv_wgrad', 'conv_wgrad_group', 'conv_wgrad_wino', 'conv_wgrad_wino_group', 'stem_wgrad_pooled']
+
+
+# how each weight-gradient kernel cuts the pixel axis into the blocks its split-K slabs take in turn (csrc/wgrad.hip, wino_wgrad.hip), and
+# the pixels per fp32 accumulation: 1 for the direct form (its 16x16x4 matrix-core steps are not taken as one exact 4-product sum),
+# 4 output tiles (16 pixels) for the Winograd form
+WGRAD_BLOCKING = {'conv_wgrad': (('px', 128), 1), 'conv_wgrad_group': (('px', 128), 1), 'squeeze_bwd': (('px', 32), 1),
+                  'conv_wgrad_wino': ('tile', 16), 'conv_wgrad_wino_group': ('tile', 16)}
+
+
+def family(kernel):
+    return re.sub(r'<.*>$', '', kernel)
+
+
+def k_of(kernel):
+    """Bar P's factor: 4 for the Winograd families (the F(2x2,3x3) transforms and the bridges built on them), 2 for direct GEMM."""
+    f = family(kernel)
+    return 4 if ('wino' in f or 'bridge' in f) else 2
+
+
+class _Harness:
+    """Wraps the ``ops`` entry points (and the slab reduction) for one step; collects per-(kernel, tag) output checks."""
+
+    def __init__(self, base, arch, batch, timer):
+        self.base, self.arch, self.batch, self.timer = base, arch, batch, timer
+        self.rows = {}                 # (arch, batch, kernel, tag) -> [(output, bars dict)]
+        self.teeth = {}                # family -> {emu: bars dict}
+        self.pending = {}              # slab data_ptr -> (entry, dy, x, taps) until the slab reduction
+        self.plan_map = self._plan_map()
+
+    def _mod(self, name):
+        name = name.split('@')[0]
+        if name == 'convdet':
+            return self.base.convdet
+        i, sub = name.split('.')
+        return getattr(self.base.features[int(i)], sub)
+
+    def _plan_map(self):
+        """id(plan) -> what it was packed from (the model's plan caches, filled by the warm-up step)."""
+        m = {}
+        for (name, _cfg, direction), (_v, p) in list(self.base._plans.items()) + list(self.base._wino_plans.items()):
+            m[id(p)] = ('conv', self._mod(name), direction)
+        for key, val in self.base._fused_plans.items():
+            if key[0] == 'firebridge':
+                m[id(val[1])] = ('bridge',) + tuple(val[2])
+        return m
+
+    def _weights(self, plan):
+        kind, mod, direction = self.plan_map[id(plan)]
+        assert kind == 'conv'
+        w = mod.weight.detach()
+        if direction != 'fwd':
+            return R.dgrad_weight(w), None
+        return w, mod.bias.detach()
+
+    def _entry(self, n0):
+        recs = self.timer.records[n0:]
+        assert len(recs) == 1, [r[:2] for r in recs]
+        return (self.arch, self.batch, recs[0][0], recs[0][1])
+
+    def _check(self, entry, outs):
+        """outs: [(name, got, ref_fn, kind)]; ref_fn(emu) -> Ref.  The first output of a family's first launch also goes through
+        both degraded emulations (teeth)."""
+        k = k_of(entry[2])
+        rows = self.rows.setdefault(entry, [])
+        fam = family(entry[2])
+        for j, (name, got, ref_fn, kind) in enumerate(outs):
+            r = ref_fn(None)
+            rows.append((name, R.bars(got, r, kind, k)))
+            if j == 0 and fam not in self.teeth:
+                self.teeth[fam] = {emu: R.bars(ref_fn(emu).b32, r, kind, k) for emu in ('bf16', 'split3')}
+            del r
+
+    def _wgrad_pending(self, entry, slab, dy, x, taps):
+        """A weight-gradient launch wrote its slabs: keep its operands; the check runs after the reduction (``reduce``)."""
+        self.pending[slab.data_ptr()] = (entry, dy.clone(), x.clone(), taps)
+
+    # ---- wrapped entry points ----
+    def conv(self, orig, x, x_coff, plan, y, y_coff, relu=False, accumulate=False, xmask=None, xmask_coff=0, ymask=None, ymask_coff=0,
+             ymul=None, ymul_coff=0, drop=None):
+        if drop is not None:
+            assert drop.keep16 == 65536 and drop.scale == 1.0
+        w, b = self._weights(plan)
+        xw = x[..., x_coff:x_coff + plan.C]
+        if xmask is not None:
+            xw = xw * (xmask[..., xmask_coff:xmask_coff + plan.C] > 0)
+        xw = xw.clone()
+        prev = y[..., y_coff:y_coff + plan.N].clone() if accumulate else None
+        ym = None if ymask is None else ymask[..., ymask_coff:ymask_coff + plan.N].clone()
+        yl = None if ymul is None else ymul[..., ymul_coff:ymul_coff + plan.N].clone()
+        n0 = len(self.timer.records)
+        out = orig(x, x_coff, plan, y, y_coff, relu=relu, accumulate=accumulate, xmask=xmask, xmask_coff=xmask_coff, ymask=ymask,
+                   ymask_coff=ymask_coff, ymul=ymul, ymul_coff=ymul_coff, drop=drop)
+        got = y[..., y_coff:y_coff + plan.N]
+        self._check(self._entry(n0), [('y', got, lambda e: R.epilogue(R.conv(xw, w, b, emu=e), prev, yl, 1.0, ym, relu), 'act')])
+        return out
+
+    def conv_wino(self, orig, x, x_coff, plan, y, y_coff, relu=False, accumulate=False, ymask=None, ymul=None, yscale=1.0, drop=None,
+                  drop_advance=None):
+        if drop is not None:
+            assert drop.keep16 == 65536 and drop.scale == 1.0
+        w, b = self._weights(plan)
+        xw = x[..., x_coff:x_coff + plan.C].clone()
+        prev = y[..., y_coff:y_coff + plan.N].clone() if accumulate else None
+        ym = None if ymask is None else ymask[..., y_coff:y_coff + plan.N].clone()
+        yl = None if ymul is None else ymul[..., y_coff:y_coff + plan.N].clone()
+        n0 = len(self.timer.records)
+        out = orig(x, x_coff, plan, y, y_coff, relu=relu, accumulate=accumulate, ymask=ymask, ymul=ymul, yscale=yscale, drop=drop,
+                   drop_advance=drop_advance)
+        got = y[..., y_coff:y_coff + plan.N]
+        self._check(self._entry(n0), [('y', got, lambda e: R.epilogue(R.conv(xw, w, b, emu=e), prev, yl, yscale, ym, relu), 'act')])
+        return out
+
+    def _bridge_weights(self, plan):
+        kind, e1, e3, sq = self.plan_map[id(plan)]
+        assert kind == 'bridge'
+        return tuple(t.detach() for t in (e1.weight, e1.bias, e3.weight, e3.bias, sq.weight, sq.bias))
+
+    def fire_bridge(self, orig, x, x_coff, plan, y, y_coff, save=None, save_coff1=0, save_coff3=None):
+        ws = self._bridge_weights(plan)
+        N1, N3 = ws[0].shape[0], ws[2].shape[0]
+        xw = x[..., x_coff:x_coff + plan.C].clone()
+        n0 = len(self.timer.records)
+        out = orig(x, x_coff, plan, y, y_coff, save=save, save_coff1=save_coff1, save_coff3=save_coff3)
+        outs = [('y', y[..., y_coff:y_coff + plan.Nsq], lambda e: R.fire_bridge(xw, *ws, emu=e)[0], 'act')]
+        if save is not None:
+            c3 = save_coff1 + N1 if save_coff3 is None else save_coff3
+            got = torch.cat([save[..., save_coff1:save_coff1 + N1], save[..., c3:c3 + N3]], -1)
+            outs.append(('save', got, lambda e: R.fire_bridge(xw, *ws, emu=e)[1], 'act'))
+        self._check(self._entry(n0), outs)
+        return out
+
+    def fire_pool_bridge(self, orig, x, x_coff, plan, y, y_coff, nseg=4, save=None, codes=None, save_coff1=0, save_coff3=None):
+        ws = self._bridge_weights(plan)
+        N1, N3 = ws[0].shape[0], ws[2].shape[0]
+        xw = x[..., x_coff:x_coff + plan.C].clone()
+        n0 = len(self.timer.records)
+        out = orig(x, x_coff, plan, y, y_coff, nseg=nseg, save=save, codes=codes, save_coff1=save_coff1, save_coff3=save_coff3)
+        outs = [('y', y[..., y_coff:y_coff + plan.Nsq], lambda e: R.fire_pool_bridge(xw, *ws, emu=e)[0], 'act')]
+        if save is not None:
+            c3 = save_coff1 + N1 if save_coff3 is None else save_coff3
+            got = torch.cat([save[..., save_coff1:save_coff1 + N1], save[..., c3:c3 + N3]], -1)
+            outs.append(('pooled', got, lambda e: R.fire_pool_bridge(xw, *ws, emu=e)[1], 'act'))
+        self._check(self._entry(n0), outs)
+        return out
+
+    def stem_pool(self, orig, image, weight, bias, argmax=None):
+        n0 = len(self.timer.records)
+        out = orig(image, weight, bias, argmax=argmax)
+        img, w, b = image.detach(), weight.detach(), bias.detach()
+        self._check(self._entry(n0), [('pooled', out, lambda e: R.stem_pool(img, w, b, emu=e), 'act')])
+        return out
+
+    def stem_pool_squeeze(self, orig, image, weight, bias, sq_weight, sq_bias, argmax=None):
+        n0 = len(self.timer.records)
+        res = orig(image, weight, bias, sq_weight, sq_bias, argmax=argmax)
+        img, w, b, ws, bs = (t.detach() for t in (image, weight, bias, sq_weight, sq_bias))
+        y = res[0] if argmax is not None else res
+        outs = [('y', y, lambda e: R.stem_pool_squeeze(img, w, b, ws, bs, emu=e)[0], 'act')]
+        if argmax is not None:
+            outs.append(('pooled', res[1], lambda e: R.stem_pool_squeeze(img, w, b, ws, bs, emu=e)[1], 'act'))
+        self._check(self._entry(n0), outs)
+        return res
+
+    def maxpool(self, orig, x, out=None, argmax=None, relu_codes=False):
+        n0 = len(self.timer.records)
+        y = orig(x, out=out, argmax=argmax, relu_codes=relu_codes)
+        entry = self._entry(n0)
+        exact = torch.equal(y, R.maxpool_exact(x))
+        self.rows.setdefault(entry, []).append(('y', dict(exact=exact, l_ok=exact, p_ok=exact, l_ratio=0.0 if exact else float('inf'),
+                                                          p_block=0.0, p_tensor=0.0, k=0)))
+        return y
+
+    def maxpool_bwd(self, orig, dy, argmax, in_hw, out=None, relu_src=None):
+        assert relu_src is None
+        d, am = dy.clone(), argmax.clone()
+        n0 = len(self.timer.records)
+        dx = orig(dy, argmax, in_hw, out=out, relu_src=relu_src)
+        self._check(self._entry(n0), [('dx', dx, lambda e: R.maxpool_bwd(d, am, in_hw, emu=e), 'act')])
+        return dx
+
+    def conv_wgrad(self, orig, dy, dy_coff, N, x, x_coff, C, taps, slab=None, wino=None):
+        assert slab is not None
+        n0 = len(self.timer.records)
+        res = orig(dy, dy_coff, N, x, x_coff, C, taps, slab=slab, wino=wino)
+        self._wgrad_pending(self._entry(n0), slab, dy[..., dy_coff:dy_coff + N], x[..., x_coff:x_coff + C], taps)
+        return res
+
+    def _group(self, orig, taps, items, *args):
+        n0 = len(self.timer.records)
+        res = orig(items, *args)
+        entry = self._entry(n0)
+        for dy, dy_coff, N, x, x_coff, C, slab in items:
+            self._wgrad_pending(entry, slab, dy[..., dy_coff:dy_coff + N], x[..., x_coff:x_coff + C], taps)
+        return res
+
+    def conv_wgrad_group(self, orig, items, S):
+        return self._group(orig, 1, items, S)
+
+    def conv_wgrad_wino_group(self, orig, items, S, tc):
+        return self._group(orig, 9, items, S, tc)
+
+    def squeeze_bwd(self, orig, dy, x, weight, slab, dx, relu_mask, dy_coff=0, N=None):
+        Nn = dy.shape[3] - dy_coff if N is None else int(N)
+        dyw, xc = dy[..., dy_coff:dy_coff + Nn].clone(), x.clone()
+        w = R.dgrad_weight(weight.detach())
+        n0 = len(self.timer.records)
+        res = orig(dy, x, weight, slab, dx, relu_mask, dy_coff=dy_coff, N=N)
+        entry = self._entry(n0)
+        self._check(entry, [('dx', dx, lambda e: R.epilogue(R.conv(dyw, w, emu=e), ymask=xc if relu_mask else None), 'act')])
+        self._wgrad_pending(entry, slab, dyw, xc, 1)
+        return res
+
+    def stem_wgrad_pooled(self, orig, dpool, pooled, argmax, image, N, ksize, out=None):
+        d, am, img = dpool.clone(), argmax.clone(), image.clone()
+        n0 = len(self.timer.records)
+        dw, db = orig(dpool, pooled, argmax, image, N, ksize, out=out)
+        self._check(self._entry(n0), [('dW', dw, lambda e: R.stem_wgrad_pooled(d, am, img, N, ksize, emu=e)[0], 'wgrad'),
+                                      ('db', db, lambda e: R.stem_wgrad_pooled(d, am, img, N, ksize, emu=e)[1], 'vec')])
+        return dw, db
+
+    def reduce(self, orig, wb, grad_flat, row_lo=0, row_hi=None, scale=1.0):
+        """After the slab reduction: every layer's (dW, db) against float64, b32 = the split-K restatement with the layer's own S."""
+        assert scale == 1.0
+        n0 = len(self.timer.records)
+        res = orig(wb, grad_flat, row_lo, row_hi, scale)
+        entry = self._entry(n0)
+        rows = wb.table.cpu().tolist()
+        row_hi = wb.nrows if row_hi is None else row_hi
+        base_ptr = wb.workspace.data_ptr()
+        for slab_off, dw_off, db_off, S, _stride, N, C, taps, _blk in rows[row_lo:row_hi]:
+            k = 3 if taps == 9 else 1
+            src, dy, x, taps_ = self.pending.pop(base_ptr + 4 * slab_off)
+            assert taps_ == taps and tuple(dy.shape[3:]) == (N,) and x.shape[3] == C
+            fam = family(src[2])
+            blocking, step = WGRAD_BLOCKING[fam]
+            kk = k_of(src[2])
+            dW, db = R.wgrad(dy, x, taps)
+            w32, b32 = R.wgrad_split_k(dy, x, taps, S, blocking, step)
+            dW, db = R.Ref(dW.ref64, dW.M, w32), R.Ref(db.ref64, db.M, b32)
+            gw = grad_flat[dw_off:dw_off + N * C * taps].view(N, C, k, k)
+            gb = grad_flat[db_off:db_off + N]
+            checks = []
+            if 'wino' in fam:
+                # bar L on the Winograd form's own magnitude (R.wgrad_wino_magnitude); the per-tap ratio is logged next to it
+                tap = R.bars(gw, dW, 'wgrad', kk)['l_ratio']
+                dW = R.Ref(dW.ref64, R.wgrad_wino_magnitude(dy, x), dW.b32)
+                bw = R.bars(gw, dW, 'wgrad', kk)
+                bw['l_ratio_tap'] = tap
+            else:
+                bw = R.bars(gw, dW, 'wgrad', kk)
+            checks = [(f'dW C{C} N{N} S{S}', bw), (f'db N{N} S{S}', R.bars(gb, db, 'vec', kk))]
+            for e in (src, entry):
+                self.rows.setdefault(e, []).extend(checks)
+            if fam not in self.teeth:
+                self.teeth[fam] = {emu: R.bars(R.wgrad_split_k(dy, x, taps, S, blocking, step, emu)[0], dW, 'wgrad', kk)
+                                   for emu in ('bf16', 'split3')}
+            del dy, x, dW, db
+        return res
+
+
+_NAMES = ('conv', 'conv_wino', 'fire_bridge', 'fire_pool_bridge', 'stem_pool', 'stem_pool_squeeze', 'maxpool', 'maxpool_bwd',
+          'conv_wgrad', 'conv_wgrad_group', 'conv_wgrad_wino_group', 'squeeze_bwd', 'stem_wgrad_pooled')
+
+
+def _run_step(arch, batch, mode):
+    """One benchmarked step (the same seeds as bench.py) with every GEMM-type launch checked.  -> (harness, [(kernel, tag)] recorded)."""
+    from squeezedet_pytorch_amd import ops, plans as plans_mod
+    from squeezedet_pytorch_amd.detector import Detector
+    from squeezedet_pytorch_amd.model import SqueezeDet, SqueezeDetWithLoss
+    torch.manual_seed(0)
+    cfg = sqd.make_cfg(arch=arch, device='cuda')
+    sd = synthetic.make_state_dict(arch, seed=1234)
+    x = synthetic.make_images(batch, INPUT, seed=0).cuda()
+    if mode == 'train':
+        m = SqueezeDetWithLoss(cfg)
+        m.load_state_dict(sd)
+        m = m.cuda().train()
+        base = m.base
+        base.dropout_prob = 0.0          # the planned dropout epilogues with an all-keep mask
+        batch_d = {'image': x, 'gt': synthetic.make_gt(batch, cfg.anchors, INPUT, seed=1).cuda()}
+
+        def step():
+            loss, _ = m(batch_d)
+            m.zero_grad()
+            loss.mean().backward()
+    else:
+        m = SqueezeDet(cfg)
+        m.load_state_dict(sd)
+        det = Detector(m, cfg)
+        base = det.model.base
+
+        def step():
+            det.detect_device(x)
+    step()                                # plans are packed here, outside the checked pass
+    torch.cuda.synchronize()
+    timer = ops.KernelTimer()
+    h = _Harness(base, arch, batch, timer)
+    saved = {n: getattr(ops, n) for n in _NAMES}
+    red = plans_mod.WgradBatch.reduce
+    for n in _NAMES:
+        setattr(ops, n, (lambda meth, orig: lambda *a, **kw: meth(orig, *a, **kw))(getattr(h, n), saved[n]))
+    plans_mod.WgradBatch.reduce = lambda wb, *a, **kw: h.reduce(red, wb, *a, **kw)
+    ops.set_timer(timer)
+    try:
+        step()
+        torch.cuda.synchronize()
+    finally:
+        ops.set_timer(None)
+        for n in _NAMES:
+            setattr(ops, n, saved[n])
+        plans_mod.WgradBatch.reduce = red
+    assert not h.pending, 'weight-gradient slabs that no reduction consumed'
+    return h, [(r[0], r[1]) for r in timer.records]
+
+
+_STATE = {}
+
+
+def _step_results(arch, batch):
+    """{(arch, batch, kernel, tag): rows} of the inference and the training step of ``arch`` (run once per module; a failure is kept and
+    raised again for every case of that arch instead of re-running the steps)."""
+    key = (arch, batch)
+    if key not in _STATE:
+        try:
+            _STATE[key] = _run_both(arch, batch)
+        except Exception as exc:            # noqa: BLE001 -- re-raised below, and by every later case of this arch
+            _STATE[key] = exc
+    res = _STATE[key]
+    if isinstance(res, Exception):
+        raise res
+    return res
+
+
+def _run_both(arch, batch):
+    from squeezedet_pytorch_amd import plan
+    rows, teeth = {}, {}
+    for mode, planner in (('infer', plan.inference_launch_plan), ('train', plan.training_launch_plan)):
+        h, got = _run_step(arch, batch, mode)
+        want = planner(arch, batch, INPUT)
+        assert got == want, [(i, a, b) for i, (a, b) in enumerate(zip(got, want)) if a != b][:4] + [len(got), len(want)]
+        for e, r in h.rows.items():
+            rows.setdefault(e, []).extend(r)
+        for f, t in h.teeth.items():
+            teeth.setdefault(f, t)
+        del h
+        torch.cuda.empty_cache()
+    return rows, teeth
+
+
+def _fmt(case, name, b):
+    if 'exact' in b:
+        return f'{case[0]:14s} b{case[1]:<3d} {case[2]:24s} {case[3]:56s} {name:20s} bit-exact={b["exact"]}'
+    tap = f'  (per-tap M: {b["l_ratio_tap"]:.2e})' if 'l_ratio_tap' in b else ''
+    return (f'{case[0]:14s} b{case[1]:<3d} {case[2]:24s} {case[3]:56s} {name:20s} max err/M {b["l_ratio"]:.2e} (bar {R.BAR_L:.2e})  '
+            f'P block {b["p_block"]:5.2f} (k {b["k"]})  P tensor {b["p_tensor"]:5.2f} (2k {2 * b["k"]}){tap}')
+
+
+@pytest.mark.parametrize('case', CASES, ids=[f'{a}-b{b}-{k}-{t}' for a, b, k, t in CASES])
+def test_launch_against_fp64(case):
+    """The planned (kernel, tag) ran in the benchmarked step, and every output it wrote holds bars L and P (or is bit-exact)."""
+    rows, _ = _step_results(case[0], case[1])
+    assert case in rows, f'{case} did not run in the step (fallback or plan drift)'
+    bad = []
+    for name, b in rows[case]:
+        print(_fmt(case, name, b))
+        if not (b['l_ok'] and b['p_ok']):
+            bad.append((name, b))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize('fam,emu', [(f, e) for f in FAMILIES for e in ('bf16', 'split3')])
+def test_teeth_bar_p_rejects_degraded_emulations(fam, emu):
+    """Bar P tells an fp32 kernel from reduced-precision ones: the first launch of each family, recomputed with bf16-rounded operands and
+    with the 3-product bf16 split instead of the kernel (the weight gradients: inside the same split-K slab structure), fails it."""
+    found = None
+    for arch, batch in STEPS:
+        t = _step_results(arch, batch)[1].get(fam)
+        if t is not None:
+            found = t
+            break
+    assert found is not None, f'no launch of family {fam} in the benchmarked steps'
+    b = found[emu]
+    print(f'teeth {fam:24s} {emu:7s} P block {b["p_block"]:9.2f}  P tensor {b["p_tensor"]:9.2f}  (k {b["k"]})')
+    assert not b['p_ok'], (fam, emu, b)
