@@ -394,13 +394,16 @@ def _rms(t):
 
 def blocks(t, kind):
     """The 64-channel blocks of an output: activations [..., N] by 64 output channels; weight gradients [N, C, k, k] by
-    (64 out x 64 in); vectors as one block."""
+    (64 out x 64 in); a loss gradient [B, A, C+5] by class logits / conf / deltas; vectors as one block."""
     if kind == 'act':
         N = t.shape[-1]
         return [t[..., i:i + 64] for i in range(0, N, 64)]
     if kind == 'wgrad':
         N, C = t.shape[:2]
         return [t[i:i + 64, j:j + 64] for i in range(0, N, 64) for j in range(0, C, 64)]
+    if kind == 'dpred':
+        C = t.shape[-1] - 5
+        return [t[..., :C], t[..., C:C + 1], t[..., C + 1:]]
     return []
 
 
@@ -426,3 +429,364 @@ def bars(got, r, kind, k):
     pt = num / den if den > 0 else (0.0 if num == 0 else float('inf'))
     p_ok = pb <= k and pt <= 2 * k
     return dict(l_ratio=l_ratio, l_ok=l_ok and exact_zero_ok, p_block=pb, p_tensor=pt, p_ok=p_ok, k=k)
+
+
+def _finite(t):
+    return torch.where(torch.isnan(t), torch.zeros((), dtype=t.dtype, device=t.device), t)
+
+
+def bars_nan(got, r, kind, k):
+    """``bars`` for outputs that hold NaN by design (an image with n_obj = 0 or n_obj = A): the NaN positions of ``got`` must equal
+    those of ref64 (``nan_ok``); the bars then run on the other elements (NaN positions count as exact)."""
+    nan = torch.isnan(r.ref64)
+    nan_ok = bool(torch.equal(torch.isnan(got.double()), nan))
+    keep = lambda t: torch.where(nan, torch.zeros((), dtype=t.dtype, device=t.device), t)    # noqa: E731
+    b = bars(keep(got.double()), Ref(keep(r.ref64), keep(r.M), keep(_finite(r.b32.double()))), kind, k)
+    b['nan_ok'] = nan_ok
+    b['l_ok'] = b['l_ok'] and nan_ok
+    return b
+
+
+# ---- multi-task loss: forward, analytic backward ----
+
+class _V(NamedTuple):
+    """A float64 value and its running error bound M: a float32 evaluation of the same chain errs by about 2^-24 M at most (to first
+    order; exact float32 inputs carry M = 0, every rounded operation adds |result|).  This is the magnitude of bar L for the loss: the
+    plain chain on absolute values multiplies sums of coordinates (|x2| + |x1| for a 10-pixel width at x = 90) through areas and the
+    squared IoU denominator, and left the IoU gradient's bar 10^3 - 10^6 times wider than the gradient itself."""
+    v: torch.Tensor
+    m: torch.Tensor
+
+
+# a float32 exp / sigmoid flushes below 2^-126: an absolute floor under their bound keeps that error inside bar L
+_TINY = 2.0 ** -100
+# rounding depth of a sum over the anchors of an image (the kernel: a strided serial run per thread, a 64-lane tree, 4 waves, 16 parts
+# in order) and over the images of a batch (a strided run per lane, a 64-lane tree)
+SUM_DEPTH_A = 32
+SUM_DEPTH_B = 16
+
+
+def _c(x):
+    return _V(x, 0.0 * abs(x))
+
+
+def _lf(t):
+    t = t.to(F64)
+    return _V(t, torch.zeros_like(t))
+
+
+def _add(a, b):
+    v = a.v + b.v
+    return _V(v, a.m + b.m + v.abs())
+
+
+def _sub(a, b):
+    v = a.v - b.v
+    return _V(v, a.m + b.m + v.abs())
+
+
+def _mul(a, b):
+    v = a.v * b.v
+    return _V(v, a.m * abs(b.v) + abs(a.v) * b.m + v.abs())
+
+
+def _div(a, b):
+    v = a.v / b.v
+    return _V(v, (a.m + v.abs() * b.m) / abs(b.v) + v.abs())
+
+
+def _neg(a):
+    return _V(-a.v, a.m)
+
+
+def _exp(a):
+    v = torch.exp(a.v)
+    return _V(v, v * (1 + a.m) + _TINY)
+
+
+def _log(a):
+    v = torch.log(a.v)
+    return _V(v, v.abs() + a.m / a.v.abs())
+
+
+def _sel(w, a):
+    """A branch weight (an exact 0, 0.5 or 1) times a chain value; a cut branch is a selection, as in torch's backward (a NaN upstream
+    stays out of it)."""
+    w = w.to(F64)
+    z = torch.zeros((), dtype=F64)
+    return _V(torch.where(w == 0, z, w * a.v), torch.where(w == 0, z, w.abs() * a.m))
+
+
+def _sum(a, dim, depth):
+    return _V(a.v.sum(dim), a.m.sum(dim) + depth * a.v.abs().sum(dim))
+
+
+LOSS_MUTANTS = ('clamp_exclusive', 'no_tie_split', 'clamp_min_strict', 'iou_detached', 'neg_den_A')
+
+
+def _decode32(pred, anchors, C):
+    """The kernel's box decode in float32 on the host, op for op (no contraction): -> x1u, y1u, x2u, y2u."""
+    d = pred[..., C + 1:].to(F32)
+    an = anchors.to(F32)
+    ax, ay, aw, ah = an[:, 0], an[:, 1], an[:, 2], an[:, 3]
+    cx = ax + aw * d[..., 0]
+    cy = ay + ah * d[..., 1]
+    w = aw * torch.exp(d[..., 2])
+    h = ah * torch.exp(d[..., 3])
+    hw, hh = 0.5 * (w - 1.0), 0.5 * (h - 1.0)
+    return cx - hw, cy - hh, cx + hw, cy + hh
+
+
+def _branches(x1u, y1u, x2u, y2u, gt, wmax, hmax, mutant=None):
+    """The 10 branch weights of the IoU gradient of each anchor, from one precision's unclamped box (torch 2.10's conventions: clamp
+    passes inclusively at its bounds, min / max ties split 0.5 / 0.5, clamp_min passes at 0) -> dict of [B, A] float64 weights."""
+    dt = x1u.dtype
+    t = lambda v: torch.tensor(v, dtype=dt)   # noqa: E731
+
+    def clamp_pass(x, hi):
+        if mutant == 'clamp_exclusive':
+            return (x > 0) & (x < hi)
+        return (x >= 0) & (x <= hi)
+
+    def tie_min(mine, other):
+        if mutant == 'no_tie_split':
+            return (mine <= other).to(F64)
+        return (mine < other).to(F64) + 0.5 * (mine == other).to(F64)
+
+    def tie_max(mine, other):
+        if mutant == 'no_tie_split':
+            return (mine >= other).to(F64)
+        return (mine > other).to(F64) + 0.5 * (mine == other).to(F64)
+
+    wm, hm = t(wmax), t(hmax)
+    px1, py1 = x1u.clamp(0, wm), y1u.clamp(0, hm)
+    px2, py2 = x2u.clamp(0, wm), y2u.clamp(0, hm)
+    g = gt[..., 1:5].to(dt)
+    gx1, gy1, gx2, gy2 = g.unbind(-1)
+    lr_raw = torch.minimum(gx2, px2) - torch.maximum(gx1, px1)
+    tb_raw = torch.minimum(gy2, py2) - torch.maximum(gy1, py1)
+    strict = mutant == 'clamp_min_strict'
+    return dict(cx1=clamp_pass(x1u, wm).to(F64), cx2=clamp_pass(x2u, wm).to(F64), cy1=clamp_pass(y1u, hm).to(F64),
+                cy2=clamp_pass(y2u, hm).to(F64), minx=tie_min(px2, gx2), maxx=tie_max(px1, gx1), miny=tie_min(py2, gy2), maxy=tie_max(py1, gy1),
+                plr=((lr_raw > 0) if strict else (lr_raw >= 0)).to(F64), ptb=((tb_raw > 0) if strict else (tb_raw >= 0)).to(F64))
+
+
+def _loss_chain(pred, gt, anchors, input_size, C, weights, u, br, mutant=None):
+    """The loss and its analytic gradient in the V algebra (float64 values + magnitudes), on the host, with given branch weights ``br``.
+    ``u`` = [3, B] upstream gradients of (class, score, bbox).  -> (terms [4, B, A] V, nobj [B], dpred V [B, A, C+5])."""
+    p = pred.to(F64)
+    g = gt.to(F64)
+    an = anchors.to(F32).to(F64)
+    B, A = p.shape[:2]
+    wmax, hmax = float(input_size[1] - 1), float(input_size[0] - 1)
+    w_c, w_p, w_n, w_b = (float(torch.tensor(w, dtype=F32)) for w in weights)
+    mask = g[..., 0]
+    onehot = g[..., 9:]
+    # class: log-softmax
+    mx = p[..., :C].max(-1, keepdim=True)[0]
+    zc = _sub(_lf(p[..., :C]), _lf(mx))
+    e = _exp(zc)
+    s = _sum(e, -1, C)
+    lse = _log(s)
+    logp = _sub(zc, _V(lse.v.unsqueeze(-1), lse.m.unsqueeze(-1)))
+    ce = _sum(_mul(_lf(onehot), _neg(logp)), -1, C)
+    prob = _div(e, _V(s.v.unsqueeze(-1), s.m.unsqueeze(-1)))
+    ohs = onehot.sum(-1)
+    # confidence: 1 / (1 + exp(-z))
+    conf = _div(_c(1.0), _add(_c(1.0), _exp(_neg(_lf(p[..., C])))))
+    # decode
+    d = [_lf(p[..., C + 1 + j]) for j in range(4)]
+    ax, ay, aw, ah = (_lf(an[:, j]) for j in range(4))
+    cx, cy = _add(ax, _mul(aw, d[0])), _add(ay, _mul(ah, d[1]))
+    w, h = _mul(aw, _exp(d[2])), _mul(ah, _exp(d[3]))
+    hw, hh = _mul(_c(0.5), _sub(w, _c(1.0))), _mul(_c(0.5), _sub(h, _c(1.0)))
+    x1u, y1u, x2u, y2u = _sub(cx, hw), _sub(cy, hh), _add(cx, hw), _add(cy, hh)
+    clampv = lambda a, hi: _V(a.v.clamp(0, hi), a.m)          # noqa: E731
+    px1, py1, px2, py2 = clampv(x1u, wmax), clampv(y1u, hmax), clampv(x2u, wmax), clampv(y2u, hmax)
+    gx1, gy1, gx2, gy2 = (_lf(g[..., 1 + j]) for j in range(4))
+    vmin = lambda a, b: _V(torch.minimum(a.v, b.v), torch.maximum(a.m, b.m))    # noqa: E731
+    vmax = lambda a, b: _V(torch.maximum(a.v, b.v), torch.maximum(a.m, b.m))    # noqa: E731
+    lr_raw = _sub(vmin(gx2, px2), vmax(gx1, px1))
+    tb_raw = _sub(vmin(gy2, py2), vmax(gy1, py1))
+    lr, tb = _V(lr_raw.v.clamp_min(0), lr_raw.m), _V(tb_raw.v.clamp_min(0), tb_raw.m)
+    inter = _mul(lr, tb)
+    pw, ph = _sub(px2, px1), _sub(py2, py1)
+    uni = _sub(_add(_mul(_sub(gx2, gx1), _sub(gy2, gy1)), _mul(pw, ph)), inter)
+    den = _add(uni, _c(float(torch.tensor(1e-10, dtype=F32))))
+    iou = _div(inter, den)
+    mk = _lf(mask)
+    ee = _sub(_mul(iou, mk), conf)
+    bbd = [_sub(d[j], _lf(g[..., 5 + j])) for j in range(4)]
+    bb = _add(_add(_mul(bbd[0], bbd[0]), _mul(bbd[1], bbd[1])), _add(_mul(bbd[2], bbd[2]), _mul(bbd[3], bbd[3])))
+    e2 = _mul(ee, ee)
+    omk = _sub(_c(1.0), mk)
+    terms = [_mul(mk, ce), _mul(mk, e2), _mul(omk, e2), _mul(mk, bb)]
+    nobj = mask.sum(1)
+    n = _lf(nobj.unsqueeze(1))                                     # (exact: a count below 2^24)
+    an_ = nobj.new_full((B, 1), float(A))
+    nneg = _lf(an_ if mutant == 'neg_den_A' else an_ - nobj.unsqueeze(1))
+    # backward, the upstream gradient per image and component
+    uu = u.to(F64).view(3, B, 1).expand(3, B, A)
+    uc, us, ub = (_V(uu[j], uu[j].abs()) for j in range(3))         # (gmean / B rounds once)
+    kc = _div(_mul(_mul(uc, _c(w_c)), mk), n)
+    kcx = _V(kc.v.unsqueeze(-1), kc.m.unsqueeze(-1))
+    o_cls = _mul(kcx, _sub(_mul(_lf(ohs.unsqueeze(-1).expand_as(onehot)), prob), _lf(onehot)))
+    k = _mul(us, _add(_div(_mul(_c(w_p), mk), n), _div(_mul(_c(w_n), omk), nneg)))
+    dL_de = _mul(_mul(_c(2.0), k), ee)
+    o_conf = _neg(_mul(_mul(dL_de, conf), _sub(_c(1.0), conf)))
+    dL_dov = _mul(dL_de, mk)
+    den2 = _mul(den, den)
+    dov_dinter = _add(_div(_c(1.0), den), _div(inter, den2))
+    dov_dap = _neg(_div(inter, den2))
+    dlr = _sel(br['plr'], _mul(_mul(dL_dov, dov_dinter), tb))
+    dtb = _sel(br['ptb'], _mul(_mul(dL_dov, dov_dinter), lr))
+    dap = _mul(dL_dov, dov_dap)
+    dpx2 = _sel(br['cx2'], _add(_sel(br['minx'], dlr), _mul(dap, ph)))
+    dpx1 = _sel(br['cx1'], _sub(_neg(_sel(br['maxx'], dlr)), _mul(dap, ph)))
+    dpy2 = _sel(br['cy2'], _add(_sel(br['miny'], dtb), _mul(dap, pw)))
+    dpy1 = _sel(br['cy1'], _sub(_neg(_sel(br['maxy'], dtb)), _mul(dap, pw)))
+    gd = [_mul(_add(dpx1, dpx2), aw), _mul(_add(dpy1, dpy2), ah),
+          _mul(_mul(_sub(dpx2, dpx1), _c(0.5)), w), _mul(_mul(_sub(dpy2, dpy1), _c(0.5)), h)]
+    if mutant == 'iou_detached':
+        gd = [_V(torch.zeros_like(x.v), torch.zeros_like(x.m)) for x in gd]
+    kb = _mul(_div(_mul(_mul(ub, _c(w_b)), mk), n), _c(2.0))
+    o_d = [_add(gd[j], _mul(kb, bbd[j])) for j in range(4)]
+    dp = _V(torch.cat([o_cls.v, o_conf.v.unsqueeze(-1)] + [x.v.unsqueeze(-1) for x in o_d], -1),
+            torch.cat([o_cls.m, o_conf.m.unsqueeze(-1)] + [x.m.unsqueeze(-1) for x in o_d], -1))
+    # per-image losses
+    S = [_sum(t, 1, SUM_DEPTH_A) for t in terms]
+    n1 = _lf(nobj)
+    nneg1 = _V(nneg.v[:, 0], nneg.m[:, 0])
+    cls = _div(_mul(_c(w_c), S[0]), n1)
+    pos = _div(_mul(_c(w_p), S[1]), n1)
+    neg = _div(_mul(_c(w_n), S[2]), nneg1)
+    bbx = _div(_mul(_c(w_b), S[3]), n1)
+    losses = [cls, _add(pos, neg), bbx, _add(_add(_add(cls, pos), neg), bbx)]
+    losses = _V(torch.stack([x.v for x in losses]), torch.stack([x.m for x in losses]))
+    return losses, nobj, dp, (x1u.v, y1u.v, x2u.v, y2u.v)
+
+
+def _oracle_loss(pred, gt, anchors, input_size, C, weights, dtype, coef=None, gmean=None):
+    """oracle.multitask_loss in ``dtype`` on the host (anchors rounded to float32 as the kernel sees them), with torch autograd for
+    the gradient.  -> (losses [4, B], dpred for gmean or None, dpred for coef or None)."""
+    import numpy as np
+    import oracle
+    an = anchors.detach().to(F32).cpu().numpy().astype(np.float32)
+    wts = [float(torch.tensor(w, dtype=F32)) for w in weights]
+    outs = []
+    for up in ('mean', 'coef', 'none'):
+        if (up == 'mean' and gmean is None) or (up == 'coef' and coef is None) or (up == 'none' and outs != [None, None]):
+            outs.append(None)
+            continue
+        with torch.enable_grad():                       # (also when called from inside an autograd.Function's forward)
+            p = pred.detach().cpu().to(dtype).requires_grad_(True)
+            lv, st = oracle.multitask_loss(p, gt.detach().cpu().to(dtype), an, tuple(input_size), C, *wts)
+            if up == 'mean':
+                (lv.mean() * float(torch.tensor(float(gmean), dtype=F32))).backward()
+            elif up == 'coef':
+                cf = coef.detach().cpu().to(F32).to(dtype)
+                (cf[0] * st['class_loss'] + cf[1] * st['score_loss'] + cf[2] * st['bbox_loss']).sum().backward()
+        outs.append((torch.stack([st['class_loss'], st['score_loss'], st['bbox_loss'], lv]).detach(), p.grad))
+    lo = next(o[0] for o in outs if o is not None)
+    return lo, (outs[0][1] if outs[0] else None), (outs[1][1] if outs[1] else None)
+
+
+def loss(pred, gt, anchors, input_size, C, weights, gmean=None, coef=None, mutant=None):
+    """float64 references of one loss launch pair, on the host.  -> dict:
+
+    * ``losses`` [4, B], ``mean4`` [4]: Ref (ref64: oracle.multitask_loss in float64; M: the chain on magnitudes; b32: the oracle in
+      float32);
+    * ``nobj`` [B]: exact;
+    * ``dmean`` (upstream ``gmean`` at mean(total)) and ``dcoef`` (upstream ``coef`` [3, B] at class / score / bbox): Ref of dpred
+      [B, A, C+5] (ref64 by float64 autograd);
+    * ``dmean_alt`` / ``dcoef_alt``: the same gradient with every branch taken as a float32 evaluation of the kernel's decode takes
+      it; ``flips`` [B, A]: the positive anchors where the two precisions take different branches (either reference is accepted
+      there, ``pick``).
+
+    ``mutant`` (one of LOSS_MUTANTS; the CPU teeth only): ref64 from the analytic chain under a wrong convention."""
+    assert mutant is None or mutant in LOSS_MUTANTS
+    pred, gt, anchors = pred.detach().cpu(), gt.detach().cpu(), anchors.detach().cpu()
+    B, A = pred.shape[:2]
+    wmax, hmax = float(input_size[1] - 1), float(input_size[0] - 1)
+    lo64, dm64, dc64 = _oracle_loss(pred, gt, anchors, input_size, C, weights, F64, coef, gmean)
+    lo32, dm32, dc32 = _oracle_loss(pred, gt, anchors, input_size, C, weights, F32, coef, gmean)
+    mask = gt[..., 0].to(F64)
+    out = {'nobj': mask.sum(1)}
+    ups = {}
+    if gmean is not None:
+        g = float(torch.tensor(float(gmean), dtype=F32)) / B
+        ups['dmean'] = (torch.full((3, B), g, dtype=F64), dm64, dm32)
+    if coef is not None:
+        ups['dcoef'] = (coef.detach().cpu().to(F32).to(F64), dc64, dc32)
+    # the branches of float64 and of the kernel's float32 decode
+    br64 = _branches(*_box64(pred, anchors, C), gt, wmax, hmax)
+    br32 = _branches(*_decode32(pred, anchors, C), gt, wmax, hmax)
+    flips = torch.zeros(B, A, dtype=torch.bool)
+    for key in br64:
+        flips |= (br64[key] != br32[key]) & (mask > 0)
+    out['flips'] = flips
+    brm = br64 if mutant is None else _branches(*_box64(pred, anchors, C), gt, wmax, hmax, mutant)
+    losses = None
+    for name, (u, ref64, b32) in ups.items():
+        losses, _n, dp, _ = _loss_chain(pred, gt, anchors, input_size, C, weights, u, brm, mutant)
+        _l, _n, dp32b, _ = _loss_chain(pred, gt, anchors, input_size, C, weights, u, br32)
+        M = torch.where(flips.unsqueeze(-1), torch.maximum(dp.m, dp32b.m), dp.m)
+        r64 = dp.v if mutant is not None else ref64
+        out[name] = Ref(r64, M, b32)
+        out[name + '_alt'] = torch.where(flips.unsqueeze(-1), dp32b.v, r64)
+    if losses is None:
+        losses = _loss_chain(pred, gt, anchors, input_size, C, weights, torch.zeros(3, B, dtype=F64), brm, mutant)[0]
+    l64 = losses.v if mutant is not None else lo64
+    out['losses'] = Ref(l64, losses.m, lo32)
+    out['mean4'] = Ref(l64.mean(1), (losses.m.sum(1) + SUM_DEPTH_B * losses.v.abs().sum(1)) / B, lo32.mean(1))
+    return out
+
+
+def loss_bf16(pred, gt, anchors, input_size, C, weights, gmean=None, coef=None):
+    """The float32 oracle chain on bf16-rounded ``pred`` and ``gt`` (the teeth of bar P) -> (losses [4, B], dpred for gmean, dpred for
+    coef)."""
+    return _oracle_loss(_bf16(pred.detach().cpu().float()), _bf16(gt.detach().cpu().float()), anchors, input_size, C, weights, F32,
+                        coef, gmean)
+
+
+def _box64(pred, anchors, C):
+    """The unclamped box in float64 (the chain's own decode) -> x1u, y1u, x2u, y2u."""
+    d = pred[..., C + 1:].to(F64)
+    an = anchors.to(F32).to(F64)
+    cx = an[:, 0] + an[:, 2] * d[..., 0]
+    cy = an[:, 1] + an[:, 3] * d[..., 1]
+    w = an[:, 2] * torch.exp(d[..., 2])
+    h = an[:, 3] * torch.exp(d[..., 3])
+    return cx - 0.5 * (w - 1), cy - 0.5 * (h - 1), cx + 0.5 * (w - 1), cy + 0.5 * (h - 1)
+
+
+def pick(got, r, alt, flips):
+    """dpred Ref with ref64 taken, on each flipped anchor row, from the branch (float64's or float32's) closer to ``got``."""
+    got = got.detach().cpu().double()
+    e64 = ((got - r.ref64).abs() / r.M.clamp_min(1e-300)).nan_to_num(0.0).amax(-1)
+    e32 = ((got - alt).abs() / r.M.clamp_min(1e-300)).nan_to_num(0.0).amax(-1)
+    use = flips & (e32 < e64)
+    return Ref(torch.where(use.unsqueeze(-1), alt, r.ref64), r.M, r.b32)
+
+
+# ---- gradient clipping + SGD with momentum ----
+
+def clip_sgd(params, grads, bufs, lr, momentum, wd, max_norm):
+    """clip_grad_norm_(max_norm) + torch.optim.SGD(lr, momentum, wd).step() in float64 from float32 snapshots (lists of tensors; bufs: the
+    momentum buffers, zero on the first step).  -> (tn64, coef64, [Ref of each new parameter], [Ref of each new buffer]); b32 is None.
+    M = |p| + lr (momentum |buf| + coef |g| + wd |p|) for a parameter, the bracket alone for a buffer."""
+    g64 = [g.detach().double().cpu() for g in grads]
+    tn64 = float(torch.sqrt(sum((g * g).sum() for g in g64)))
+    coef = min(1.0, max_norm / (tn64 + 1e-6)) if max_norm > 0 else 1.0
+    lr, momentum, wd = (float(torch.tensor(v, dtype=F32)) for v in (lr, momentum, wd))
+    ps, bs = [], []
+    for p, g, b in zip(params, g64, bufs):
+        p = p.detach().double().cpu()
+        g = g.reshape(p.shape)
+        b = b.detach().double().cpu().reshape(p.shape)
+        d = g * coef + wd * p
+        nb = momentum * b + d
+        mb = momentum * b.abs() + coef * g.abs() + wd * p.abs()
+        ps.append(Ref(p - lr * nb, p.abs() + lr * mb, None))
+        bs.append(Ref(nb, mb, None))
+    return tn64, coef, ps, bs

@@ -21,6 +21,9 @@ Two bars per output (fp64_ref.bars):
   mixes every offset of its 4x4 input tile with its 2x2 output tile, so its bar L uses that form's magnitude
   (fp64_ref.wgrad_wino_magnitude); the per-tap ratio is logged beside it.
 ``maxpool_fwd`` does no arithmetic: bit-exact against the max of its own input.
+The loss launches (``loss_fwd`` / ``loss_bwd``: the mean forms that bench.py's step differentiates) are held to fp64_ref.loss: losses
+[4, B], mean4 and dpred at bars L (M: the chain's running error bound) and P (k = 2; dpred in class-logit / conf / delta blocks), nobj
+exact, and at most 4 anchors of a launch on a branch where float64 and float32 disagree (either branch's reference is accepted there).
 """
 import re
 
@@ -93,6 +96,8 @@ CASES = [
     ('squeezedet', 20, 'squeeze_bwd', 'sqbwd C64 N16 96x312'),
     ('squeezedet', 20, 'stem_wgrad_pooled<3>', 'stem wgrad (pooled) 384x1248'),
     ('squeezedet', 20, 'wgrad_reduce_batched', '31 layers'),
+    ('squeezedet', 20, 'loss_fwd', 'loss A16848'),
+    ('squeezedet', 20, 'loss_bwd', 'lossbwd A16848'),
     ('squeezedetplus', 16, 'stem_pool<7>', 'stem+pool 384x1248'),
     ('squeezedetplus', 16, 'conv_ws<6,8>', '1tap C96 N96 96x312'),
     ('squeezedetplus', 16, 'conv_ws<4,8>', '1tap C96 N64 96x312'),
@@ -153,12 +158,16 @@ CASES = [
     ('squeezedetplus', 16, 'squeeze_bwd', 'sqbwd C96 N96 96x312'),
     ('squeezedetplus', 16, 'stem_wgrad_pooled<7>', 'stem wgrad (pooled) 384x1248'),
     ('squeezedetplus', 16, 'wgrad_reduce_batched', '31 layers'),
+    ('squeezedetplus', 16, 'loss_fwd', 'loss A16848'),
+    ('squeezedetplus', 16, 'loss_bwd', 'lossbwd A16848'),
 ]
 
 # the families the teeth test runs through the degraded emulations (first launch of each in the steps above)
 FAMILIES = ['conv_ws', 'conv_dma', 'conv_wino', 'conv_wino_us', 'conv_wino_sk', 'conv_wino_vs', 'fire_bridge', 'fire_bridge_save',
             'fire_pool_bridge', 'fire_pool_bridge_save', 'stem_pool', 'stem_pool_sq', 'stem_pool_sq_train', 'maxpool_bwd', 'squeeze_bwd',
             'conv_wgrad', 'conv_wgrad_group', 'conv_wgrad_wino', 'conv_wgrad_wino_group', 'stem_wgrad_pooled']
+# the loss families: their teeth are bf16-rounded pred / gt through the float32 oracle chain (there is no product split to emulate)
+LOSS_FAMILIES = ['loss_fwd', 'loss_bwd']
 
 
 # how each weight-gradient kernel cuts the pixel axis into the blocks its split-K slabs take in turn (csrc/wgrad.hip, wino_wgrad.hip), and
@@ -379,6 +388,58 @@ class _Harness:
                                       ('db', db, lambda e: R.stem_wgrad_pooled(d, am, img, N, ksize, emu=e)[1], 'vec')])
         return dw, db
 
+    # ---- the loss launches: every output against fp64_ref.loss on the launch's own operands (bar P at k = 2) ----
+    def _loss_rows(self, entry, outs):
+        rows = self.rows.setdefault(entry, [])
+        for name, got, r, kind in outs:
+            rows.append((name, R.bars_nan(got.cpu(), r, kind, 2)))
+
+    def _loss_fwd(self, orig, pred, gt, anchors, input_size, num_classes, weights, mean):
+        p, g, a = (t.detach().clone() for t in (pred, gt, anchors))
+        n0 = len(self.timer.records)
+        res = orig(pred, gt, anchors, input_size, num_classes, weights)
+        entry = self._entry(n0)
+        ref = R.loss(p, g, a, input_size, num_classes, weights)
+        nobj_exact = bool(torch.equal(res[1].cpu().double(), ref['nobj']))
+        outs = [('losses', res[0], ref['losses'], 'vec')] + ([('mean4', res[2], ref['mean4'], 'vec')] if mean else [])
+        self._loss_rows(entry, outs)
+        self.rows[entry].append(('nobj', dict(exact=nobj_exact, l_ok=nobj_exact, p_ok=nobj_exact, l_ratio=0.0, p_block=0.0,
+                                               p_tensor=0.0, k=0)))
+        if 'loss_fwd' not in self.teeth:
+            l16 = R.loss_bf16(p, g, a, input_size, num_classes, weights)[0]
+            self.teeth['loss_fwd'] = {'bf16': R.bars(l16, ref['losses'], 'vec', 2)}
+        return res
+
+    def loss_fwd(self, orig, pred, gt, anchors, input_size, num_classes, weights):
+        return self._loss_fwd(orig, pred, gt, anchors, input_size, num_classes, weights, False)
+
+    def loss_mean_fwd(self, orig, pred, gt, anchors, input_size, num_classes, weights):
+        return self._loss_fwd(orig, pred, gt, anchors, input_size, num_classes, weights, True)
+
+    def _loss_bwd(self, orig, args, input_size, num_classes, weights, gmean=None, coef=None):
+        p, g, a = (t.detach().clone() for t in args[:3])
+        n0 = len(self.timer.records)
+        dpred = orig(*args, input_size, num_classes, weights)
+        entry = self._entry(n0)
+        ref = R.loss(p, g, a, input_size, num_classes, weights, gmean=gmean, coef=coef)
+        name = 'dmean' if gmean is not None else 'dcoef'
+        got = dpred.cpu()
+        self._loss_rows(entry, [('dpred', got, R.pick(got, ref[name], ref[name + '_alt'], ref['flips']), 'dpred')])
+        flips = int(ref['flips'].sum())
+        print(f'{entry[2]} {entry[3]}: {flips} anchors where float64 and float32 take different branches')
+        self.rows[entry].append(('flips', dict(exact=flips <= 4, l_ok=flips <= 4, p_ok=True, l_ratio=0.0, p_block=0.0, p_tensor=0.0,
+                                                k=0, flips=flips)))
+        if 'loss_bwd' not in self.teeth:
+            d16 = R.loss_bf16(p, g, a, input_size, num_classes, weights, gmean=gmean, coef=coef)[1 if gmean is not None else 2]
+            self.teeth['loss_bwd'] = {'bf16': R.bars(d16, ref[name], 'dpred', 2)}
+        return dpred
+
+    def loss_mean_bwd(self, orig, pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
+        return self._loss_bwd(orig, (pred, gt, anchors, nobj, gmean), input_size, num_classes, weights, gmean=float(gmean.reshape(-1)[0]))
+
+    def loss_bwd(self, orig, pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
+        return self._loss_bwd(orig, (pred, gt, anchors, nobj, coef), input_size, num_classes, weights, coef=coef.detach().cpu())
+
     def reduce(self, orig, wb, grad_flat, row_lo=0, row_hi=None, scale=1.0):
         """After the slab reduction: every layer's (dW, db) against float64, b32 = the split-K restatement with the layer's own S."""
         assert scale == 1.0
@@ -420,7 +481,8 @@ class _Harness:
 
 
 _NAMES = ('conv', 'conv_wino', 'fire_bridge', 'fire_pool_bridge', 'stem_pool', 'stem_pool_squeeze', 'maxpool', 'maxpool_bwd',
-          'conv_wgrad', 'conv_wgrad_group', 'conv_wgrad_wino_group', 'squeeze_bwd', 'stem_wgrad_pooled')
+          'conv_wgrad', 'conv_wgrad_group', 'conv_wgrad_wino_group', 'squeeze_bwd', 'stem_wgrad_pooled',
+          'loss_fwd', 'loss_mean_fwd', 'loss_bwd', 'loss_mean_bwd')
 
 
 def _run_step(arch, batch, mode):
@@ -440,10 +502,10 @@ def _run_step(arch, batch, mode):
         base.dropout_prob = 0.0          # the planned dropout epilogues with an all-keep mask
         batch_d = {'image': x, 'gt': synthetic.make_gt(batch, cfg.anchors, INPUT, seed=1).cuda()}
 
-        def step():
-            loss, _ = m(batch_d)
+        def step():                      # bench.py's form (trainer.make_train_step): the mean and its backward in the loss launches
+            loss, _ = m.forward_mean(batch_d)
             m.zero_grad()
-            loss.mean().backward()
+            loss.backward()
     else:
         m = SqueezeDet(cfg)
         m.load_state_dict(sd)
@@ -509,6 +571,8 @@ def _run_both(arch, batch):
 
 
 def _fmt(case, name, b):
+    if 'flips' in b:
+        return f'{case[0]:14s} b{case[1]:<3d} {case[2]:24s} {case[3]:56s} {name:20s} branch flips {b["flips"]} (at most 4)'
     if 'exact' in b:
         return f'{case[0]:14s} b{case[1]:<3d} {case[2]:24s} {case[3]:56s} {name:20s} bit-exact={b["exact"]}'
     tap = f'  (per-tap M: {b["l_ratio_tap"]:.2e})' if 'l_ratio_tap' in b else ''
@@ -529,10 +593,11 @@ def test_launch_against_fp64(case):
     assert not bad, bad
 
 
-@pytest.mark.parametrize('fam,emu', [(f, e) for f in FAMILIES for e in ('bf16', 'split3')])
+@pytest.mark.parametrize('fam,emu', [(f, e) for f in FAMILIES for e in ('bf16', 'split3')] + [(f, 'bf16') for f in LOSS_FAMILIES])
 def test_teeth_bar_p_rejects_degraded_emulations(fam, emu):
     """Bar P tells an fp32 kernel from reduced-precision ones: the first launch of each family, recomputed with bf16-rounded operands and
-    with the 3-product bf16 split instead of the kernel (the weight gradients: inside the same split-K slab structure), fails it."""
+    with the 3-product bf16 split instead of the kernel (the weight gradients: inside the same split-K slab structure), fails it.  The
+    loss launches: the float32 oracle chain on bf16-rounded pred and gt fails it, for the losses and for dpred."""
     found = None
     for arch, batch in STEPS:
         t = _step_results(arch, batch)[1].get(fam)
