@@ -3,14 +3,14 @@ pixel count into the live table, times hipGraph replays of the step with fuse_fi
 import sys, json; sys.path.insert(0, '.')
 import torch
 import squeezedet_pytorch_amd as sqd
-from squeezedet_pytorch_amd import ops, synthetic
+from squeezedet_pytorch_amd import ops, plan, synthetic
 from squeezedet_pytorch_amd.detector import Detector
 from squeezedet_pytorch_amd.model import SqueezeDet
 cfg = sqd.make_cfg(arch='squeezedet', device='cuda')
 m = SqueezeDet(cfg); m.load_state_dict(synthetic.make_state_dict('squeezedet', seed=1234)); det = Detector(m, cfg)
 tab = ops._tuning()
 def step_ms(x, bufs):
-    m.base.invalidate_plans()
+    m.base.invalidate_plans(); plan.forward_schedule.cache_clear()
     with torch.no_grad():
         for _ in range(3): det.detect_device(x, out=bufs)
         torch.cuda.synchronize()

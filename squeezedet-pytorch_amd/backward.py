@@ -11,41 +11,19 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import ops, plan
 from .autograd import run_backbone_forward
 from .synthetic import layer_table
 
 
-def _wgrad_layout(base, saved, B, H, W):
+def _wgrad_layout(base, wgrad):
     """Flat gradient layout (named_parameters order: every gradient is a view of ONE buffer) and the batched-reduction
-    entries of all Fire / ConvDet weight gradients for the shapes of this step."""
+    entries of all Fire / ConvDet weight gradients (``wgrad``: plan.backward_schedule, in backward order)."""
     slots, off = {}, 0
     for n, p in base.named_parameters():
         slots[n] = (off, tuple(p.shape)); off += p.numel()
-    layers = layer_table(base.arch)
-    entries = []
-    # expand3x3 weight gradients that share a launch: the Fire modules between two pools (same grid), same tile form
-    e3s = [(f'features.{i}.expand3x3', layers[i][4], layers[i][2]) + tuple(saved[f'fire{i}'][2].shape[:3])
-           for i in range(len(layers) - 1, 1, -1) if layers[i][0] == 'fire']
-    groups = ops.wino_wgrad_groups(e3s, enabled=getattr(base, 'group_wgrad', None))
-    # ... and the expand1x1 weight gradients that are too wide for the fused squeeze backward (their own direct-form launch otherwise)
-    fsb = bool(getattr(base, 'fuse_squeeze_bwd', False))
-    e1s = [(f'features.{i}.expand1x1', layers[i][3], layers[i][2]) + tuple(saved[f'fire{i}'][2].shape[:3])
-           for i in range(len(layers) - 1, 1, -1) if layers[i][0] == 'fire' and not (fsb and ops.squeeze_bwd_ok(layers[i][3], layers[i][2]))]
-    groups.update(ops.wgrad1x1_groups(e1s, enabled=getattr(base, 'group_wgrad', None)))
-
-    def add(pre, N, C, taps, shp, fused=False):
-        entries.append((pre, N, C, taps, shp[0], shp[1], shp[2], slots[pre + '.weight'][0], slots[pre + '.bias'][0], fused,
-                        None if fused else groups.get(pre)))
-    add('convdet', base.convdet.out_channels, base.convdet.in_channels, 9, (B, H, W))
-    for i in range(len(layers) - 1, 1, -1):
-        if layers[i][0] != 'fire':
-            continue
-        _, cin, s, e1, e3 = layers[i]
-        shp = saved[f'fire{i}'][2].shape
-        add(f'features.{i}.expand1x1', e1, s, 1, shp, fused=bool(getattr(base, 'fuse_squeeze_bwd', False)) and ops.squeeze_bwd_ok(e1, s))
-        add(f'features.{i}.expand3x3', e3, s, 9, shp)
-        add(f'features.{i}.squeeze', s, cin, 1, shp, fused=bool(getattr(base, 'fuse_squeeze_bwd', False)) and ops.squeeze_bwd_ok(s, cin))
+    entries = [(pre, w.N, w.C, w.taps, *w.shape, slots[pre + '.weight'][0], slots[pre + '.bias'][0], w.fused, w.group)
+               for pre, w in wgrad.items()]
     return entries, slots, off
 
 
@@ -59,8 +37,11 @@ def run_backbone_backward(base, saved, dpred):
     cd = base.convdet
     a_in = saved['convdet_in']
     cin_cd = a_in.shape[3]
-    shape_key = (B, H, W, bool(getattr(base, 'fuse_squeeze_bwd', False)), getattr(base, 'group_wgrad', None)) + tuple(tuple(saved[f'fire{i}'][2].shape) for i in range(len(layers)) if layers[i][0] == 'fire')
-    wb, slots, total = base.wgrad_batch(lambda: _wgrad_layout(base, saved, B, H, W), shape_key)
+    shapes = tuple(tuple(saved[f'fire{i}'][2].shape) for i in range(len(layers)) if layers[i][0] == 'fire')
+    wgrad, convdet_sk = plan.backward_schedule(base.arch, [s[:3] for s in shapes], ncd, base.fuse_squeeze_bwd, base.group_wgrad,
+                                               saved['drop_scale'] is not None)
+    shape_key = (B, H, W, bool(base.fuse_squeeze_bwd), base.group_wgrad) + shapes
+    wb, slots, total = base.wgrad_batch(lambda: _wgrad_layout(base, wgrad), shape_key)
     # + 1: the data-parallel exchange carries this rank's image count through the same all-reduce (trainer.GradientExchange)
     grad_buf = torch.empty(total + 1, device=dpred.device, dtype=torch.float32)
     grad_flat = grad_buf[:total]
@@ -97,10 +78,10 @@ def run_backbone_backward(base, saved, dpred):
     assert layers[last][0] == 'fire'
     out_last = saved[f'fire{last}'][2]
     dA = torch.empty_like(out_last)
-    if saved.get('drop_scale') is not None:
+    if saved['drop_scale'] is not None:
         # fused dropout: out_last IS the dropped ReLU output (> 0 exactly where kept and active), so the gradient is masked by it and
         # scaled by the constant 1 / (1 - p): no mask tensor is read
-        if ncd % 8 == 0:
+        if convdet_sk:
             ops.conv_wino(dpred, 0, base.wino_plan('convdet', cd, ops.WINO_SK_CFG, 'dgrad'), dA, 0, ymask=out_last, yscale=saved['drop_scale'])
         else:
             base.dgrad3x3('convdet', cd, dpred, 0, dA, ymask=out_last)
@@ -120,9 +101,7 @@ def run_backbone_backward(base, saved, dpred):
             continue
         _, cin, s, e1, e3 = l
         fire = feats[i]
-        x_in, sq, out = saved[f'fire{i}']
-        Bq, Hq, Wq, _ = out.shape
-        npix = Bq * Hq * Wq
+        x_in, sq, _ = saved[f'fire{i}']
         pre = f'features.{i}.'
         fused_e1 = bool(wb.fused.get(pre + 'expand1x1'))
 
@@ -150,7 +129,7 @@ def run_backbone_backward(base, saved, dpred):
             # expand1x1 half of dA; the expand3x3 data gradient below accumulates onto it and applies the squeeze's ReLU mask
             ops.squeeze_bwd(dA, sq, fire.expand1x1.weight, wb.slab(pre + 'expand1x1'), dSq, relu_mask=False, dy_coff=0, N=e1)
         else:
-            ops.conv(dA, 0, base.plan(f'{i}.expand1x1', fire.expand1x1, ops.choose_cfg(1, e1, s, npix), 'dgrad'), dSq, 0)
+            ops.conv(dA, 0, base.plan(f'{i}.expand1x1', fire.expand1x1, wgrad[pre + 'expand1x1'].dgrad_cfg, 'dgrad'), dSq, 0)
         base.dgrad3x3(f'{i}.expand3x3', fire.expand3x3, dA, e1, dSq, accumulate=True, ymask=sq)
         dIn = torch.empty_like(x_in)
         prev_is_fire = layers[i - 1][0] == 'fire'
@@ -160,7 +139,7 @@ def run_backbone_backward(base, saved, dpred):
             ops.squeeze_bwd(dSq, x_in, fire.squeeze.weight, wb.slab(pre + 'squeeze'), dIn, relu_mask=prev_is_fire)
         else:
             ops.conv_wgrad(dSq, 0, s, x_in, 0, cin, 1, slab=wb.slab(pre + 'squeeze'))
-            ops.conv(dSq, 0, base.plan(f'{i}.squeeze', fire.squeeze, ops.choose_cfg(1, s, cin, npix), 'dgrad'), dIn, 0,
+            ops.conv(dSq, 0, base.plan(f'{i}.squeeze', fire.squeeze, wgrad[pre + 'squeeze'].dgrad_cfg, 'dgrad'), dIn, 0,
                      ymask=x_in if prev_is_fire else None)
         dA = dIn
     stem = feats[0]

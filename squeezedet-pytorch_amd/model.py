@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .plan import conv3x3_cfg
 from .synthetic import layer_table, convdet_in_channels
 
 
@@ -265,23 +266,22 @@ class SqueezeDetBase(nn.Module):
         implicit-GEMM kernel."""
         Bq, H, W, _ = x.shape
         C, N = mod.in_channels, mod.out_channels
-        wc = ops.choose_wino_cfg(C, N, Bq * H * W) if self.use_winograd else None
-        if wc is not None and (ymul is None or tuple(ymul.shape) == tuple(y.shape)):
-            return ops.conv_wino(x, x_coff, self.wino_plan(name, mod, wc), y, y_coff, relu=relu, ymul=ymul)
-        return ops.conv(x, x_coff, self.plan(name, mod, ops.choose_cfg(9, C, N, Bq * H * W)), y, y_coff, relu=relu,
-                        ymul=ymul, ymul_coff=y_coff)
+        # (the Winograd kernel reads ymul with y's geometry)
+        wino, cfg = conv3x3_cfg(C, N, Bq * H * W, self.use_winograd and (ymul is None or tuple(ymul.shape) == tuple(y.shape)))
+        if wino:
+            return ops.conv_wino(x, x_coff, self.wino_plan(name, mod, cfg), y, y_coff, relu=relu, ymul=ymul)
+        return ops.conv(x, x_coff, self.plan(name, mod, cfg), y, y_coff, relu=relu, ymul=ymul, ymul_coff=y_coff)
 
     def dgrad3x3(self, name, mod, dy, dy_coff, dx, accumulate=False, ymask=None, ymul=None):
         """dx (=|+=) data gradient of ``mod``'s 3x3 convolution (transposed, tap-flipped weights), ymul / ymask fused into the
         epilogue; Winograd kernel where the measured table prefers it."""
         Bq, H, W, _ = dy.shape
         C, N = mod.out_channels, mod.in_channels                  # the dgrad convolves dY (out channels) into dX (in channels)
-        wc = ops.choose_wino_cfg(C, N, Bq * H * W) if self.use_winograd else None
         same_geom = all(t is None or tuple(t.shape) == tuple(dx.shape) for t in (ymask, ymul))
-        if wc is not None and same_geom:
-            return ops.conv_wino(dy, dy_coff, self.wino_plan(name, mod, wc, 'dgrad'), dx, 0, accumulate=accumulate, ymask=ymask, ymul=ymul)
-        return ops.conv(dy, dy_coff, self.plan(name, mod, ops.choose_cfg(9, C, N, Bq * H * W), 'dgrad'), dx, 0,
-                        accumulate=accumulate, ymask=ymask, ymul=ymul)
+        wino, cfg = conv3x3_cfg(C, N, Bq * H * W, self.use_winograd and same_geom)
+        if wino:
+            return ops.conv_wino(dy, dy_coff, self.wino_plan(name, mod, cfg, 'dgrad'), dx, 0, accumulate=accumulate, ymask=ymask, ymul=ymul)
+        return ops.conv(dy, dy_coff, self.plan(name, mod, cfg, 'dgrad'), dx, 0, accumulate=accumulate, ymask=ymask, ymul=ymul)
 
     # ---- dropout state ----
     def drop_state(self, device):

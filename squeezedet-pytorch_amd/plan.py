@@ -1,32 +1,218 @@
-"""The launch plan of one inference or training step, computed on the host WITHOUT a GPU: which kernel instance (tile
-configuration from the measured table ``tuning.json``) every layer launches for a given architecture / batch / input
-size.  ``inference_launch_plan`` mirrors the decisions of ``autograd.run_backbone_forward`` + the fused detect launch,
-``training_launch_plan`` those of the saving forward, ``LossFn`` and ``backward.run_backbone_backward``; GPU tests assert
-both agree with the real launches name for name and shape for shape (tests/test_surface_gpu.py), for the default and for
-non-default model flags.  They exist so that profiles can be checked against the code that shipped:
-``profiles/traffic.json`` records the launch set it was measured on (inference at top level, training under ``"train"``)
-and a CPU test recomputes that set here.
+"""Every launch decision of one inference or training step, taken on the host WITHOUT a GPU: which kernel instance (tile
+configuration from the measured table ``tuning.json``) every layer launches for a given architecture / batch / input size.
+``forward_schedule`` decides the forward (stem form, pools, squeeze, which launch takes a Fire's expand pair, dropout),
+``backward_schedule`` the backward (fused squeeze backward, grouped weight gradients, ConvDet's data gradient) and
+``conv3x3_cfg`` a plain 3x3 launch.  The executors (``autograd.run_backbone_forward``, ``backward.run_backbone_backward``,
+``SqueezeDetBase.conv3x3``) walk these schedules; ``inference_launch_plan`` / ``training_launch_plan`` render the same schedules as
+(kernel name, shape tag) lists.  GPU tests assert the rendering equals the real launches name for name and shape for shape
+(tests/test_surface_gpu.py), for the default and for non-default model flags, so that profiles can be checked against the code
+that shipped: ``profiles/traffic.json`` records the launch set it was measured on (inference at top level, training under
+``"train"``) and a CPU test recomputes that set here.
 
 Reference for the layer sequence: src/model/squeezedet.py:33-87, src/engine/detector.py:20-50, src/engine/trainer.py:42-50.
 """
 from __future__ import annotations
 
-from collections import Counter
+import functools
+from collections import Counter, namedtuple
 
 from . import ops
 from .synthetic import convdet_in_channels, layer_table
 
+# the model switches (``SqueezeDetBase`` attributes of the same names) the forward schedule depends on
+Flags = namedtuple('Flags', 'use_winograd fuse_expand fuse_expand_wino fuse_fire_bridge fuse_pool_squeeze fuse_stem_squeeze '
+                            'fuse_train_forward fused_dropout')
+# One record per stem / pool / Fire / ConvDet, in layer order; (H, W, C) = the layer's input.
+# form: stem_conv | stem_pool | stem_pool_sq | stem_pool_sq_train (the last two also run the first Fire's squeeze, width sq)
+StemStep = namedtuple('StemStep', 'form ks sq')
+# how: launch | folded (into the next squeeze: pool_squeeze) | done (by the previous launch)
+PoolStep = namedtuple('PoolStep', 'i H W C how')
+# squeeze: conv (cfg sq_cfg) | pool_squeeze | done.  expand: fire_pool_bridge[_save] (cfg = segments) | fire_bridge[_save] | fire_wino |
+# fire_expand | conv_drop (cfg: expand1x1 with the fused dropout, expand3x3 on the balanced Winograd kernel) | plain (cfg: expand1x1);
+# nsq: width of the next Fire's squeeze a bridge also runs.  mask_launch: the stand-alone dropout_mask launch precedes this Fire's
+# squeeze; ymul: the plain pair multiplies a mask tensor (given or just drawn) in.
+FireStep = namedtuple('FireStep', 'i H W C s e1 e3 mask_launch squeeze sq_cfg expand cfg nsq ymul')
+ConvDetStep = namedtuple('ConvDetStep', 'H W C fused_rng')      # fused_rng: the dropout ran inside the last Fire's expand launches
+# One record per weight gradient, keyed by the parameter prefix.  fused: it comes out of squeeze_bwd; group: its launch group
+# (a ``tiles.wino_wgrad_groups`` value) or None; dgrad_cfg: configuration of a 1x1 layer's own data-gradient launch.
+WgradStep = namedtuple('WgradStep', 'N C taps shape fused group dgrad_cfg')
+
+_CHOOSERS = ('choose_cfg', 'choose_wino_cfg', 'choose_fire_wino_cfg', 'choose_fused_cfg', 'choose_fire_bridge_cfg', 'choose_fire_pool_bridge',
+             'conv_drop_cfg', 'stem_pool_squeeze_ok', 'pool_squeeze_ok', 'squeeze_bwd_ok', 'wino_wgrad_groups', 'wgrad1x1_groups')
+
+
+def _choosers():
+    """The table look-ups as they stand in ``ops`` now.  Part of the memo keys below: a schedule is only answered from the memo while
+    the look-ups are the ones it was built with (tests force forms by swapping them).  Whoever edits the loaded tuning table in place
+    calls ``forward_schedule.cache_clear()`` / ``backward_schedule.cache_clear()``."""
+    return tuple(getattr(ops, n) for n in _CHOOSERS)
+
+
+def conv3x3_cfg(C, N, npix, use_winograd):
+    """A plain 3x3 launch (forward, or data gradient with C / N swapped): (True, Winograd configuration) where the measured table has
+    the row, else (False, configuration of the direct kernel)."""
+    wc = ops.choose_wino_cfg(C, N, npix) if use_winograd else None
+    return (True, wc) if wc is not None else (False, ops.choose_cfg(9, C, N, npix))
+
+
+def forward_schedule(arch, batch, input_size, flags, save=False, dropout=None):
+    """-> tuple of StemStep / PoolStep / FireStep ... ConvDetStep.  ``save``: the forward keeps what the backward reads.  ``dropout``
+    (in front of ConvDet): None, 'stream' (the counter-based stream) or 'mask' (a given mask tensor)."""
+    return _forward_schedule(arch, int(batch), (int(input_size[0]), int(input_size[1])), flags, bool(save), dropout, _choosers())
+
+
+@functools.lru_cache(maxsize=256)
+def _forward_schedule(arch, batch, input_size, flags, save, dropout, _key):
+    layers = layer_table(arch)
+    assert layers[-1][0] == 'fire'                     # (ConvDet and the dropout in front of it sit behind a Fire)
+
+    def kind(j):
+        return layers[j][0] if j < len(layers) else None
+    C, ks = layers[0][2], layers[0][3]
+    H, W = ops.stem_out_size(input_size[0], input_size[1], ks)
+    first, bridged, folded = 2, False, False           # bridged: the next Fire's squeeze already ran inside the previous launch
+    if kind(2) == 'pool':
+        # conv + ReLU + pool in one launch; with the first Fire's squeeze riding in it (a saving forward: in its storing form)
+        bridged = bool(flags.fuse_stem_squeeze and (flags.fuse_train_forward if save else True) and kind(3) == 'fire'
+                       and ops.stem_pool_squeeze_ok((batch, 3) + input_size, (C, 3, ks, ks), layers[3][2]))
+        steps = [StemStep(('stem_pool_sq_train' if save else 'stem_pool_sq') if bridged else 'stem_pool', ks, layers[3][2] if bridged else None),
+                 PoolStep(2, H, W, C, 'done')]
+        H, W = ops.pool_out_size(H, W)
+        first = 3
+    else:
+        steps = [StemStep('stem_conv', ks, None)]
+    for i in range(first, len(layers)):
+        if kind(i) == 'pool':
+            folded = bool(not bridged and not save and flags.fuse_pool_squeeze and kind(i + 1) == 'fire' and ops.pool_squeeze_ok(C, layers[i + 1][2]))
+            steps.append(PoolStep(i, H, W, C, 'done' if bridged else 'folded' if folded else 'launch'))
+            H, W = ops.pool_out_size(H, W)
+            continue
+        _, cin, s, e1, e3 = layers[i]
+        assert C == cin, f'layer {i}: expected {cin} channels, got {C}'
+        npix = batch * H * W
+        is_last = i == len(layers) - 1
+        drop_here = dropout if is_last else None       # (the last Fire carries the dropout in its expand epilogues: two plain launches)
+        if bridged:
+            squeeze, sq_cfg = 'done', None
+        elif folded:
+            squeeze, sq_cfg = 'pool_squeeze', ops.POOL_SQUEEZE_CFG
+        else:
+            squeeze, sq_cfg = 'conv', ops.choose_cfg(1, cin, s, npix)
+        # which launch takes the expand pair, in the order the forms are tried.  The bridges also run the next Fire's squeeze:
+        # inference forms (the expand output is never written), or -- a saving forward -- storing forms
+        bridge = flags.fuse_fire_bridge and flags.use_winograd and (flags.fuse_train_forward if save else not drop_here)
+        expand, cfg, nsq = 'plain', None, None
+        if bridge and kind(i + 1) == 'pool' and kind(i + 2) == 'fire':
+            cfg = ops.choose_fire_pool_bridge(s, e1, e3, layers[i + 2][2], npix)
+            if cfg is not None:
+                expand, nsq = 'fire_pool_bridge', layers[i + 2][2]
+        if cfg is None and bridge and kind(i + 1) == 'fire' and not (is_last and dropout):
+            cfg = ops.choose_fire_bridge_cfg(s, e1, e3, layers[i + 1][2], npix)
+            if save and cfg is not None and cfg % 1000 != 12:          # (only the small-C form has a storing variant)
+                cfg = None
+            if cfg is not None:
+                expand, nsq = 'fire_bridge', layers[i + 1][2]
+        if cfg is not None and save:
+            expand += '_save'
+        if cfg is None and not save and not drop_here:
+            if flags.fuse_expand_wino and flags.use_winograd:
+                cfg = ops.choose_fire_wino_cfg(s, e1, e3, npix)
+                expand = 'fire_wino' if cfg is not None else expand
+            if cfg is None and flags.fuse_expand and e1 == e3:
+                cfg = ops.choose_fused_cfg(s, e1, npix)
+                expand = 'fire_expand' if cfg is not None else expand
+        mask_launch = False
+        if drop_here == 'stream':
+            # the fused form needs a weight-stationary 1x1 configuration and the balanced Winograd kernel (8 | squeeze width);
+            # otherwise this step's mask is drawn as a tensor by the stand-alone kernel and multiplied in like a given mask
+            cfg = ops.conv_drop_cfg(s, e1, npix) if (flags.fused_dropout and s % 8 == 0 and flags.use_winograd) else None
+            expand, mask_launch = ('conv_drop', False) if cfg is not None else ('plain', True)
+        if expand == 'plain':
+            cfg = ops.choose_cfg(1, s, e1, npix)
+        steps.append(FireStep(i, H, W, C, s, e1, e3, mask_launch, squeeze, sq_cfg, expand, cfg, nsq, bool(drop_here) and expand == 'plain'))
+        bridged, folded = nsq is not None, False
+        C = e1 + e3
+    steps.append(ConvDetStep(H, W, C, steps[-1].expand == 'conv_drop'))
+    return tuple(steps)
+
+
+forward_schedule.cache_clear = _forward_schedule.cache_clear
+
+
+def backward_schedule(arch, shapes, ncd, fuse_squeeze_bwd, group_wgrad, fused_rng):
+    """-> ({parameter prefix ('convdet', 'features.{i}.expand1x1', ...): WgradStep} in backward order, whether ConvDet's data
+    gradient runs on the balanced Winograd kernel).  ``shapes``: (B, H, W) of every Fire, in layer order; ``ncd``: ConvDet's
+    output channels; ``fused_rng``: ``ConvDetStep.fused_rng`` of the forward."""
+    return _backward_schedule(arch, tuple(tuple(s) for s in shapes), ncd, bool(fuse_squeeze_bwd), group_wgrad, bool(fused_rng), _choosers())
+
+
+@functools.lru_cache(maxsize=256)
+def _backward_schedule(arch, shapes, ncd, fuse_squeeze_bwd, group_wgrad, fused_rng, _key):
+    layers = layer_table(arch)
+    back = [i for i in range(len(layers) - 1, 1, -1) if layers[i][0] == 'fire']
+    shp = dict(zip(back[::-1], shapes))
+
+    def fused(N, C):
+        return fuse_squeeze_bwd and ops.squeeze_bwd_ok(N, C)
+    # expand3x3 weight gradients that share a launch: the Fire modules between two pools (same grid), same tile form ...
+    groups = ops.wino_wgrad_groups([(f'features.{i}.expand3x3', layers[i][4], layers[i][2]) + shp[i] for i in back], enabled=group_wgrad)
+    # ... and the expand1x1 weight gradients that are too wide for the fused squeeze backward (their own direct-form launch otherwise)
+    groups.update(ops.wgrad1x1_groups([(f'features.{i}.expand1x1', layers[i][3], layers[i][2]) + shp[i] for i in back
+                                       if not fused(layers[i][3], layers[i][2])], enabled=group_wgrad))
+    out = {'convdet': WgradStep(ncd, convdet_in_channels(arch), 9, shp[back[0]], False, None, None)}
+    for i in back:
+        _, cin, s, e1, e3 = layers[i]
+        npix = shp[i][0] * shp[i][1] * shp[i][2]
+        for name, N, C, taps in (('expand1x1', e1, s, 1), ('expand3x3', e3, s, 9), ('squeeze', s, cin, 1)):
+            f = taps == 1 and fused(N, C)
+            out[f'features.{i}.{name}'] = WgradStep(N, C, taps, shp[i], f, None if f else groups.get(f'features.{i}.{name}'),
+                                                   None if (f or taps == 9) else ops.choose_cfg(1, N, C, npix))
+    return out, fused_rng and ncd % 8 == 0
+
+
+backward_schedule.cache_clear = _backward_schedule.cache_clear
+
+
+def _tap1(cfg, Cin, N, H, W):
+    return (ops.cfg_kernel_name(cfg), f'1tap C{Cin} N{N} {H}x{W}')
+
 
 def _conv3x3(batch, H, W, Cin, N, use_winograd):
-    npix = batch * H * W
-    wc = ops.choose_wino_cfg(Cin, N, npix) if use_winograd else None
-    if wc is not None:
-        return (ops.wino_kernel_name(wc), f'9tap C{Cin} N{N} {H}x{W}')
-    return (ops.cfg_kernel_name(ops.choose_cfg(9, Cin, N, npix)), f'9tap C{Cin} N{N} {H}x{W}')
+    wino, cfg = conv3x3_cfg(Cin, N, batch * H * W, use_winograd)
+    return (ops.wino_kernel_name(cfg) if wino else ops.cfg_kernel_name(cfg), f'9tap C{Cin} N{N} {H}x{W}')
 
 
-def _conv1x1(batch, H, W, Cin, N):
-    return (ops.cfg_kernel_name(ops.choose_cfg(1, Cin, N, batch * H * W)), f'1tap C{Cin} N{N} {H}x{W}')
+def _render_forward(steps, batch, input_size, use_winograd):
+    """The forward schedule up to the last Fire as (kernel name, shape tag), as ``ops`` brackets the launches."""
+    h, w = input_size
+    plan = []
+    for prev, st in zip((None,) + steps, steps[:-1]):
+        if type(st) is StemStep:
+            tag = 'stem' if st.form == 'stem_conv' else 'stem+pool' if st.sq is None else 'stem+pool+squeeze'
+            plan.append((f'{st.form}<{st.ks}>', f'{tag} {h}x{w}' + (f' S{st.sq}' if st.sq is not None else '')))
+        elif type(st) is PoolStep:
+            if st.how == 'launch':
+                plan.append(('maxpool_fwd', f'pool C{st.C} {st.H}x{st.W}'))
+        else:
+            H, W, s, e1, e3 = st.H, st.W, st.s, st.e1, st.e3
+            if st.mask_launch:
+                plan.append(('dropout_mask', f'{batch * H * W * (e1 + e3)} elements'))
+            if st.squeeze == 'pool_squeeze':
+                plan.append(('pool_squeeze', f'pool+squeeze C{st.C} N{s} {prev.H}x{prev.W}'))
+            elif st.squeeze == 'conv':
+                plan.append(_tap1(st.sq_cfg, st.C, s, H, W))
+            if st.expand.startswith('fire_pool_bridge'):
+                plan.append((st.expand, f'fire C{s} E{e1}+{e3} -> pool -> S{st.nsq} {H}x{W}'))
+            elif st.expand.startswith('fire_bridge'):
+                plan.append((st.expand, f'fire C{s} E{e1}+{e3} -> S{st.nsq} {H}x{W}'))
+            elif st.expand == 'fire_wino':
+                plan.append((ops.fire_wino_kernel_name(st.cfg), f'fire C{s} E{e1}+{e3} {H}x{W}'))
+            elif st.expand == 'fire_expand':
+                plan.append((ops.cfg_kernel_name(st.cfg).replace('conv_dma', 'fire_expand'), f'expand C{s} E{e1} {H}x{W}'))
+            else:
+                plan.append(_tap1(st.cfg, s, e1, H, W))
+                plan.append(('conv_wino_sk', f'9tap C{s} N{e3} {H}x{W}') if st.expand == 'conv_drop' else _conv3x3(batch, H, W, s, e3, use_winograd))
+    return plan
 
 
 def inference_launch_plan(arch='squeezedet', batch=20, input_size=(384, 1248), anchors_per_grid=9, num_classes=3,
@@ -34,74 +220,10 @@ def inference_launch_plan(arch='squeezedet', batch=20, input_size=(384, 1248), a
                           fuse_pool_squeeze=False, fuse_stem_squeeze=True):
     """-> list of (kernel name as bench.py / KernelTimer prints it, shape tag), in launch order.  The six switches are
     ``SqueezeDetBase``'s attributes of the same names, one to one."""
-    layers = layer_table(arch)
-    H, W = ops.stem_out_size(input_size[0], input_size[1], layers[0][3])
-    C = layers[0][2]
-    plan = []
-    first = 2
-    bridged = False
-    if layers[2][0] == 'pool':
-        nxt = layers[3] if len(layers) > 3 else None
-        if (fuse_stem_squeeze and nxt is not None and nxt[0] == 'fire'
-                and ops.stem_pool_squeeze_ok((batch, 3, input_size[0], input_size[1]), (layers[0][2], 3, layers[0][3], layers[0][3]), nxt[2])):
-            plan.append((f'stem_pool_sq<{layers[0][3]}>', f'stem+pool+squeeze {input_size[0]}x{input_size[1]} S{nxt[2]}'))
-            bridged = True
-        else:
-            plan.append((f'stem_pool<{layers[0][3]}>', f'stem+pool {input_size[0]}x{input_size[1]}'))
-        H, W = ops.pool_out_size(H, W)
-        first = 3
-    else:
-        plan.append((f'stem_conv<{layers[0][3]}>', f'stem {input_size[0]}x{input_size[1]}'))
-
-    unpooled = None                        # (H, W) of the un-pooled map when the pool is folded into the next squeeze
-    for i in range(first, len(layers)):
-        l = layers[i]
-        if l[0] == 'pool':
-            nxt = layers[i + 1] if i + 1 < len(layers) else None
-            if bridged:
-                pass
-            elif fuse_pool_squeeze and nxt is not None and nxt[0] == 'fire' and ops.pool_squeeze_ok(C, nxt[2]):
-                unpooled = (H, W)
-            else:
-                plan.append(('maxpool_fwd', f'pool C{C} {H}x{W}'))
-            H, W = ops.pool_out_size(H, W)
-            continue
-        _, cin, s, e1, e3 = l
-        npix = batch * H * W
-        nxt = layers[i + 1] if i + 1 < len(layers) else None
-        nxt2 = layers[i + 2] if i + 2 < len(layers) else None
-        zseg = ycfg = xcfg = fcfg = None
-        if nxt is not None and nxt[0] == 'pool' and nxt2 is not None and nxt2[0] == 'fire' and fuse_fire_bridge and use_winograd:
-            zseg = ops.choose_fire_pool_bridge(s, e1, e3, nxt2[2], npix)
-        if zseg is None and nxt is not None and nxt[0] == 'fire' and fuse_fire_bridge and use_winograd:
-            ycfg = ops.choose_fire_bridge_cfg(s, e1, e3, nxt[2], npix)
-        if zseg is None and ycfg is None:
-            xcfg = ops.choose_fire_wino_cfg(s, e1, e3, npix) if (fuse_expand_wino and use_winograd) else None
-            fcfg = ops.choose_fused_cfg(s, e1, npix) if (xcfg is None and fuse_expand and e1 == e3) else None
-        if bridged:
-            pass
-        elif unpooled is not None:
-            plan.append(('pool_squeeze', f'pool+squeeze C{cin} N{s} {unpooled[0]}x{unpooled[1]}'))
-            unpooled = None
-        else:
-            plan.append(_conv1x1(batch, H, W, cin, s))
-        bridged = False
-        C = e1 + e3
-        if zseg is not None:
-            plan.append(('fire_pool_bridge', f'fire C{s} E{e1}+{e3} -> pool -> S{nxt2[2]} {H}x{W}'))
-            bridged = True
-            continue
-        if ycfg is not None:
-            plan.append(('fire_bridge', f'fire C{s} E{e1}+{e3} -> S{nxt[2]} {H}x{W}'))
-            bridged = True
-            continue
-        if xcfg is not None:
-            plan.append((ops.fire_wino_kernel_name(xcfg), f'fire C{s} E{e1}+{e3} {H}x{W}'))
-        elif fcfg is not None:
-            plan.append((ops.cfg_kernel_name(fcfg).replace('conv_dma', 'fire_expand'), f'expand C{s} E{e1} {H}x{W}'))
-        else:
-            plan.append(_conv1x1(batch, H, W, s, e1))
-            plan.append(_conv3x3(batch, H, W, s, e3, use_winograd))
+    flags = Flags(use_winograd, fuse_expand, fuse_expand_wino, fuse_fire_bridge, fuse_pool_squeeze, fuse_stem_squeeze, True, True)
+    steps = forward_schedule(arch, batch, input_size, flags)
+    plan = _render_forward(steps, batch, input_size, use_winograd)
+    H, W = steps[-1].H, steps[-1].W
     plan.append(_conv3x3(batch, H, W, convdet_in_channels(arch), anchors_per_grid * (num_classes + 5), use_winograd))
     plan.append(('detect', f'detect A{H * W * anchors_per_grid}'))
     return plan
@@ -119,148 +241,66 @@ def training_launch_plan(arch='squeezedet', batch=20, input_size=(384, 1248), an
     """Launches of one training iteration's forward (activations saved; ``fuse_train_forward``: the stem + squeeze launch and the
     two small-C bridges run in their STORING forms -- what the backward reads is written by the fused launch -- where the table has
     their rows; the other inference-only fusions stay off), multi-task loss forward / backward and the backbone backward, as
-    (kernel name, shape tag) in launch order.  The optimizer launch and torch's own elementwise kernels (dropout mask,
-    ``loss.mean()``) are not KernelTimer-bracketed and not listed.  ``data_parallel_stages``: with a gradient exchange
-    attached the slab reduction runs once per backward stage instead of once at the end.  ``fuse_squeeze_bwd`` =
-    ``SqueezeDetBase.fuse_squeeze_bwd``.  ``dropout`` (``cfg.dropout_prob > 0``): the counter-based dropout in front of ConvDet rides
+    (kernel name, shape tag) in launch order.  The optimizer launch and torch's own elementwise kernels (``loss.mean()``) are not
+    KernelTimer-bracketed and not listed.  ``data_parallel_stages``: with a gradient exchange
+    attached the slab reduction runs once per backward stage instead of once at the end.  ``fuse_squeeze_bwd`` / ``group_wgrad`` =
+    ``SqueezeDetBase``'s attributes.  ``dropout`` (``cfg.dropout_prob > 0``): the counter-based dropout in front of ConvDet rides
     in the last Fire's expand launches (a weight-stationary 1x1 configuration + the balanced Winograd kernel) and ConvDet's data
-    gradient runs on the balanced Winograd kernel (mask = its own input, constant scale); where that form does not apply (``fused_dropout`` off, squeeze width not a
-    multiple of 8) the mask is drawn by the stand-alone ``dropout_mask`` launch."""
-    layers = layer_table(arch)
-    ks = layers[0][3]
-    H, W = ops.stem_out_size(input_size[0], input_size[1], ks)
-    C = layers[0][2]
-    plan = []
-    fused_stem = layers[2][0] == 'pool'
-    first = 2
-    bridged = False                                     # the next Fire's squeeze already ran inside the previous launch
-    if fused_stem:
-        nxt = layers[3] if len(layers) > 3 else None
-        if (fuse_train_forward and fuse_stem_squeeze and nxt is not None and nxt[0] == 'fire'
-                and ops.stem_pool_squeeze_ok((batch, 3, input_size[0], input_size[1]), (layers[0][2], 3, ks, ks), nxt[2])):
-            plan.append((f'stem_pool_sq_train<{ks}>', f'stem+pool+squeeze {input_size[0]}x{input_size[1]} S{nxt[2]}'))
-            bridged = True
-        else:
-            plan.append((f'stem_pool<{ks}>', f'stem+pool {input_size[0]}x{input_size[1]}'))
-        H, W = ops.pool_out_size(H, W)
-        first = 3
-    else:
-        plan.append((f'stem_conv<{ks}>', f'stem {input_size[0]}x{input_size[1]}'))
-    geo = {}                                            # layer index -> (H, W, C_in) at its input
-    for i in range(first, len(layers)):
-        l = layers[i]
-        geo[i] = (H, W, C)
-        if l[0] == 'pool':
-            if not bridged:
-                plan.append(('maxpool_fwd', f'pool C{C} {H}x{W}'))
-            H, W = ops.pool_out_size(H, W)
-            continue
-        _, cin, s, e1, e3 = l
-        # (the last Fire carries the dropout in its expand epilogues: two plain launches)
-        is_last = i == len(layers) - 1
-        nxt = layers[i + 1] if i + 1 < len(layers) else None
-        nxt2 = layers[i + 2] if i + 2 < len(layers) else None
-        npix = batch * H * W
-        zseg_t = ycfg_t = None
-        if fuse_train_forward and fuse_fire_bridge and use_winograd:
-            if nxt is not None and nxt[0] == 'pool' and nxt2 is not None and nxt2[0] == 'fire':
-                zseg_t = ops.choose_fire_pool_bridge(s, e1, e3, nxt2[2], npix)
-            if nxt is not None and nxt[0] == 'fire' and not (is_last and dropout):
-                ycfg_t = ops.choose_fire_bridge_cfg(s, e1, e3, nxt[2], npix)
-                if ycfg_t is not None and ycfg_t % 1000 != 12:
-                    ycfg_t = None
-        if zseg_t is not None or ycfg_t is not None:
-            if not bridged:
-                plan.append(_conv1x1(batch, H, W, cin, s))
-            if zseg_t is not None:
-                plan.append(('fire_pool_bridge_save', f'fire C{s} E{e1}+{e3} -> pool -> S{nxt2[2]} {H}x{W}'))
-            else:
-                plan.append(('fire_bridge_save', f'fire C{s} E{e1}+{e3} -> S{nxt[2]} {H}x{W}'))
-            bridged = True
-            C = e1 + e3
-            continue
-        dcfg = None
-        if is_last and dropout:
-            dcfg = ops.conv_drop_cfg(s, e1, batch * H * W) if (fused_dropout and s % 8 == 0 and use_winograd) else None
-            if dcfg is None:
-                plan.append(('dropout_mask', f'{batch * H * W * (e1 + e3)} elements'))
-        if not bridged:
-            plan.append(_conv1x1(batch, H, W, cin, s))
-        bridged = False
-        if dcfg is not None:
-            plan.append((ops.cfg_kernel_name(dcfg), f'1tap C{s} N{e1} {H}x{W}'))
-            plan.append(('conv_wino_sk', f'9tap C{s} N{e3} {H}x{W}'))
-        else:
-            plan.append(_conv1x1(batch, H, W, s, e1))
-            plan.append(_conv3x3(batch, H, W, s, e3, use_winograd))
-        C = e1 + e3
+    gradient runs on the balanced Winograd kernel (mask = its own input, constant scale); where that form does not apply
+    (``fused_dropout`` off, squeeze width not a multiple of 8) the mask is drawn by the stand-alone ``dropout_mask`` launch."""
+    flags = Flags(use_winograd, True, True, fuse_fire_bridge, False, fuse_stem_squeeze, fuse_train_forward, fused_dropout)
+    steps = forward_schedule(arch, batch, input_size, flags, True, 'stream' if dropout else None)
+    plan = _render_forward(steps, batch, input_size, use_winograd)
+    H, W = steps[-1].H, steps[-1].W
     ncd = anchors_per_grid * (num_classes + 5)
     ccd = convdet_in_channels(arch)
-    fused_rng = dropout and layers[-1][0] == 'fire' and (fused_dropout and layers[-1][2] % 8 == 0 and use_winograd
-                                                           and ops.conv_drop_cfg(layers[-1][2], layers[-1][3], batch * H * W) is not None)
     plan.append(_conv3x3(batch, H, W, ccd, ncd, use_winograd))
     A = H * W * anchors_per_grid
     plan.append(('loss_fwd', f'loss A{A}'))
     plan.append(('loss_bwd', f'lossbwd A{A}'))
-    # ---- backward (backward.run_backbone_backward) ----
+    # ---- backward ----
+    wgrad, convdet_sk = backward_schedule(arch, [(batch, st.H, st.W) for st in steps if type(st) is FireStep], ncd, fuse_squeeze_bwd,
+                                          group_wgrad, steps[-1].fused_rng)
     plan.append(_wgrad(batch, H, W, ncd, ccd, 9))
-    if fused_rng and ncd % 8 == 0:
-        plan.append(('conv_wino_sk', f'9tap C{ncd} N{ccd} {H}x{W}'))                 # ConvDet data gradient (mask = its own input, constant scale)
-    else:
-        plan.append(_conv3x3(batch, H, W, ncd, ccd, use_winograd))                   # ConvDet data gradient
+    # ConvDet data gradient (balanced kernel: mask = its own input, constant scale)
+    plan.append(('conv_wino_sk', f'9tap C{ncd} N{ccd} {H}x{W}') if convdet_sk else _conv3x3(batch, H, W, ncd, ccd, use_winograd))
     rows_total, rows_done = 1, 0                       # slab-reduction records: ConvDet, then 3 per Fire in backward order
-    last = len(layers) - 1
-    # expand3x3 weight gradients that share a launch (``group_wgrad`` = ``SqueezeDetBase.group_wgrad``): issued when the last member is reached
-    groups = ops.wino_wgrad_groups([(i, layers[i][4], layers[i][2], batch, geo[i][0], geo[i][1]) for i in range(last, 1, -1)
-                                    if layers[i][0] == 'fire'], enabled=group_wgrad)
-    fire_idx = [i for i in range(last, 1, -1) if layers[i][0] == 'fire']
-    groups.update(ops.wgrad1x1_groups([(('e1', i), layers[i][3], layers[i][2], batch, geo[i][0], geo[i][1]) for i in fire_idx
-                                       if not (fuse_squeeze_bwd and ops.squeeze_bwd_ok(layers[i][3], layers[i][2]))], enabled=group_wgrad))
-    pending = {}
-    for i in range(last, 1, -1):
-        l = layers[i]
-        Hi, Wi, Ci = geo[i] if i in geo else (None, None, None)
-        if l[0] == 'pool':
+    pending = {}                                       # group id -> shape tags of the members seen so far (issued with the last one)
+    ks = steps[0].ks
+    for st in reversed(steps[1:-1]):
+        if type(st) is PoolStep:
             if data_parallel_stages and rows_total > rows_done:         # a stage of the backward is complete: its bucket goes out
                 plan.append(('wgrad_reduce_batched', f'{rows_total - rows_done} layers'))
                 rows_done = rows_total
-            if i == 2 and fused_stem:
-                continue
-            plan.append(('maxpool_bwd', f'poolbwd C{Ci} {Hi}x{Wi}'))
+            if st.i != 2:                                               # (the stem's pool is folded into the stem weight gradient)
+                plan.append(('maxpool_bwd', f'poolbwd C{st.C} {st.H}x{st.W}'))
             continue
-        _, cin, s, e1, e3 = l
-        fused_e1 = fuse_squeeze_bwd and ops.squeeze_bwd_ok(e1, s)
-        if not fused_e1:
-            if ('e1', i) in groups:
-                gid, _S, _tc, members = groups[('e1', i)]
-                pending.setdefault(gid, []).append(f'C{s} N{e1}')
+        H, W, s, e1, e3 = st.H, st.W, st.s, st.e1, st.e3
+        w1, w3, wsq = (wgrad[f'features.{st.i}.{n}'] for n in ('expand1x1', 'expand3x3', 'squeeze'))
+        for w, kernel in ((w1, 'conv_wgrad_group<1>'), (w3, 'conv_wgrad_wino_group')):
+            if w.group is not None:
+                gid, _S, _tc, members = w.group
+                pending.setdefault(gid, []).append(f'C{w.C} N{w.N}')
                 if len(pending[gid]) == len(members):
-                    plan.append(('conv_wgrad_group<1>', f'wgrad 1tap {" + ".join(pending.pop(gid))} {Hi}x{Wi}'))
-            else:
-                plan.append(_wgrad(batch, Hi, Wi, e1, s, 1))
-        if i in groups:
-            gid, _S, _tc, members = groups[i]
-            pending.setdefault(gid, []).append(f'C{s} N{e3}')
-            if len(pending[gid]) == len(members):
-                plan.append(('conv_wgrad_wino_group', f'wgrad 9tap {" + ".join(pending.pop(gid))} {Hi}x{Wi}'))
+                    plan.append((kernel, f'wgrad {w.taps}tap {" + ".join(pending.pop(gid))} {H}x{W}'))
+            elif not w.fused:
+                plan.append(_wgrad(batch, H, W, w.N, w.C, w.taps))
+        if w1.fused:
+            plan.append(('squeeze_bwd', f'sqbwd C{s} N{e1} {H}x{W}'))                  # expand1x1 weight + data gradient, one launch
         else:
-            plan.append(_wgrad(batch, Hi, Wi, e3, s, 9))
-        if fused_e1:
-            plan.append(('squeeze_bwd', f'sqbwd C{s} N{e1} {Hi}x{Wi}'))                # expand1x1 weight + data gradient, one launch
+            plan.append(_tap1(w1.dgrad_cfg, e1, s, H, W))                             # expand1x1 data gradient
+        plan.append(_conv3x3(batch, H, W, e3, s, use_winograd))                       # expand3x3 data gradient (accumulates)
+        if wsq.fused:
+            plan.append(('squeeze_bwd', f'sqbwd C{st.C} N{s} {H}x{W}'))               # squeeze weight + data gradient, one launch
         else:
-            plan.append(_conv1x1(batch, Hi, Wi, e1, s))                               # expand1x1 data gradient
-        plan.append(_conv3x3(batch, Hi, Wi, e3, s, use_winograd))                     # expand3x3 data gradient (accumulates)
-        if fuse_squeeze_bwd and ops.squeeze_bwd_ok(s, cin):
-            plan.append(('squeeze_bwd', f'sqbwd C{cin} N{s} {Hi}x{Wi}'))              # squeeze weight + data gradient, one launch
-        else:
-            plan.append(_wgrad(batch, Hi, Wi, s, cin, 1))
-            plan.append(_conv1x1(batch, Hi, Wi, s, cin))                              # squeeze data gradient
+            plan.append(_wgrad(batch, H, W, s, st.C, 1))
+            plan.append(_tap1(wsq.dgrad_cfg, s, st.C, H, W))                          # squeeze data gradient
         rows_total += 3
     Hs, Ws = input_size
-    if fused_stem:
-        plan.append((f'stem_wgrad_pooled<{ks}>', f'stem wgrad (pooled) {Hs}x{Ws}'))
-    else:
+    if steps[0].form == 'stem_conv':
         plan.append((f'stem_wgrad<{ks}>', f'stem wgrad {Hs}x{Ws}'))
+    else:
+        plan.append((f'stem_wgrad_pooled<{ks}>', f'stem wgrad (pooled) {Hs}x{Ws}'))
     if rows_total > rows_done:
         plan.append(('wgrad_reduce_batched', f'{rows_total - rows_done} layers'))
     return plan

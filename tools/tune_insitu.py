@@ -104,6 +104,8 @@ def main():
     def step_ms():
         """Median hipGraph replay time of the whole step with the current table."""
         (tmodel.base if args.mode == 'train' else model.base).invalidate_plans()
+        planmod.forward_schedule.cache_clear()          # (the memoised schedules were built from the table as it stood)
+        planmod.backward_schedule.cache_clear()
         if args.mode == 'train':
             tmodel.base._wgrad_batches.clear()          # (slab workspaces are sized by the splits)
         for _ in range(2):
