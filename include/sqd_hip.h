@@ -205,6 +205,24 @@ int sqd_filter_fwd(const long long* class_ids, const float* scores, const float*
                    long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
                    int num_classes, int keep_top_k, float nms_thresh, float score_thresh, void* stream);
 
+/* Wide fused detect: sqd_detect_shift_fwd / sqd_filter_fwd for 1 <= keep_top_k <= 1024 and 1 <= A <= 2^20 (num_classes <= 16 as
+ * everywhere), bit for bit the same results where both run.  Two stream-ordered launches (score every anchor into the workspace;
+ * one 1024-thread workgroup per image selects, ranks, suppresses and compacts), no host synchronisation, capturable.
+ * keys_ws: 16-byte aligned workspace of ws_words >= sqd_detect_wide_workspace_words(B, A, keep_top_k) uint32; its contents need no
+ * initialisation and nothing in it carries over between launches.  Status 2 for a keep_top_k, A or num_classes past these limits,
+ * status 1 for a null pointer, keep_top_k < 1 or a short / misaligned workspace -- decided on the host, nothing is launched. */
+int sqd_detect_wide_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                        int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                        int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                        int ws_words, void* stream);
+
+int sqd_filter_wide_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
+                        long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                        int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words, void* stream);
+
+/* int32 words of the wide workspace (B x ceil4(A)), or -1 for a (B, A, keep_top_k) the wide path does not take. */
+int sqd_detect_wide_workspace_words(int B, int A, int keep_top_k);
+
 /* GPU-side input pipeline: whiten + cv2.resize(INTER_LINEAR) + HWC->CHW of
  * DataWrapper.__getitem__ / BaseDataset.preprocess / whiten / resize (src/engine/detector.py:132-142,
  * src/datasets/base.py:43-59, src/utils/image.py:9-19,77-88) for a batch of uint8 RGB images of arbitrary sizes.

@@ -487,3 +487,352 @@ extern "C" int sqd_filter_fwd(const long long* class_ids, const float* scores, c
   a.wmax = 0.f; a.hmax = 0.f; a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
   return launch_detect(a, (hipStream_t)stream);
 }
+
+// ---- wide fused detection: 1 <= K <= 1024, 1 <= A <= 2^20 -------------------------------------------------------------------------------
+// The kernel above keeps an image's keys and its 64 x 64 suppression matrix in one workgroup's LDS and one wave's registers: K <= 64,
+// A <= 25596.  This second path has the same inputs, outputs and semantics (oracle.filter_detections bit for bit: same key, same
+// tie rule, same rank, same IoU expression, same output order, anchor_score / anchor_box shared with decode_kernel) without the two
+// caps.  Two launches, stream-ordered, nothing carried from call to call:
+//   1. detect_wide_score_kernel, grid over (image, 256-anchor slab): one key per anchor into the workspace [B][ceil4(A)] (the pad
+//      keys of the last quad are written as 0, so the workspace needs no zeroing and every launch leaves it reusable);
+//   2. detect_wide_select_kernel, one 1024-thread workgroup per image.  The keys stay in the workspace (L2-resident: 4 MB at A = 2^20)
+//      and are streamed: 4 x 8-bit radix select of the K-th largest key (the first pass also counts the candidates M; M <= K skips the
+//      rest), then one ordered sweep -- a contiguous run of quads per thread -- appends the keys above the K-th key (any order) and
+//      the first `need` ties in ascending anchor order.  The <= K (key, ~anchor) pairs are ranked as 64-bit words by counting, one
+//      per thread; thread r decodes the box of rank r.  The K x ceil(K/64) suppression bit matrix lives in LDS (128 KB at K = 1024):
+//      its upper triangle is built in 64 x 64 blocks dealt round-robin to the 16 waves, wave 0 runs the greedy scan with the alive mask
+//      held one 64-bit word per lane and eight row loads in flight ahead of the alive tests, and every thread places its own survivor
+//      from per-wave per-class counts.
+// Limits: K <= 1024 = one candidate per thread, and the matrix + candidates fit the 160 KB LDS; A <= 2^20 = gt_encode's limit.
+#define DETW_THREADS 1024
+#define DETW_MAX_K 1024
+#define DETW_MAX_A (1 << 20)
+#define DETW_SCORE_THREADS 256
+#define DETW_LDS_FIXED (256 * 4 + 16 * 4 + 256 * 4 + 16 * 8 + 16)      // histogram, wave totals, class counts, alive words, scalars
+
+typedef unsigned int u32x4_w __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(DETW_SCORE_THREADS) void detect_wide_score_kernel(DetArgs a) {
+  const int A = a.A, C = a.C, A4 = (A + 3) & ~3;
+  const int slabs = (A4 + DETW_SCORE_THREADS - 1) / DETW_SCORE_THREADS;
+  const int b = (int)blockIdx.x / slabs;
+  const int i = ((int)blockIdx.x - b * slabs) * DETW_SCORE_THREADS + (int)threadIdx.x;
+  if (i >= A4) return;
+  unsigned key = 0u;
+  if (i < A) {
+    if (a.in_score) {
+      const float s = a.in_score[(long long)b * A + i];
+      key = (s > a.score_thresh) ? __float_as_uint(s) : 0u;
+    } else {
+      // confidence first, as in detect_kernel: score <= conf, so conf <= threshold already decides key = 0, exactly
+      const float* p = a.pred + ((long long)b * A + i) * (C + 5);
+      const float conf = 1.f / (1.f + expf(-p[C]));
+      if (conf > a.score_thresh) {
+        float s; int c;
+        anchor_score(p, C, s, c);
+        key = (s > a.score_thresh) ? __float_as_uint(s) : 0u;
+      }
+    }
+  }
+  a.keys[(long long)b * A4 + i] = key;
+}
+
+// block-wide exclusive scan over one value per thread (fixed order -> deterministic); every thread of the workgroup calls it
+__device__ __forceinline__ unsigned detw_excl_scan(unsigned c, unsigned& total, unsigned* wave_tot, int lane, int wave) {
+  unsigned incl = c;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned t = __shfl_up(incl, off);
+    if (lane >= off) incl += t;
+  }
+  __syncthreads();
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  unsigned woff = 0u, tot = 0u;
+  for (int w = 0; w < DETW_THREADS / 64; ++w) { const unsigned t = wave_tot[w]; if (w < wave) woff += t; tot += t; }
+  total = tot;
+  return incl - c + woff;
+}
+
+// one histogram count per active lane.  Scores cluster (a few exponent bins in the leading pass, one bin in every pass when thousands
+// of keys tie): the two most common bins of the wave are counted with one atomic each, only the rest lane by lane.  Whole waves call it.
+__device__ __forceinline__ void detw_hist_add(unsigned* hist, bool act, unsigned bin, int lane) {
+  unsigned long long todo = __ballot(act);
+  for (int round = 0; round < 2 && todo; ++round) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const unsigned lb = __shfl(bin, leader);
+    const unsigned long long same = __ballot(act && bin == lb);
+    if (lane == leader) atomicAdd(&hist[lb], (unsigned)__popcll(same));
+    todo &= ~same;
+    act = act && bin != lb;
+  }
+  if (act) atomicAdd(&hist[bin], 1u);
+}
+
+__global__ __launch_bounds__(DETW_THREADS) void detect_wide_select_kernel(DetArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int K = a.K, Kp = (K + 63) & ~63;                     // Kp <= 1024: one candidate slot per thread
+  unsigned long long* cand = (unsigned long long*)smem_raw;   // [Kp] (key << 32) | ~anchor: larger word = earlier rank
+  f32x4* boxL = (f32x4*)(cand + Kp);                          // [Kp] boxes in rank order
+  int* clsL = (int*)(boxL + Kp);                              // [Kp] classes in rank order, -1 past the candidates
+  unsigned* hist = (unsigned*)(clsL + Kp);                    // [256]
+  unsigned* wave_tot = hist + 256;                            // [16]
+  unsigned* cls_cnt = wave_tot + 16;                          // [16 waves][16 classes] survivors
+  unsigned long long* aliveL = (unsigned long long*)(cls_cnt + 256);   // [16]
+  unsigned* sv = (unsigned*)(aliveL + 16);                    // prefix, need, appended
+  unsigned long long* mat = (unsigned long long*)(sv + 4);    // [64 Wn][Wn] suppression bits, Wn = ceil(candidates / 64) <= Kp / 64
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = (int)blockIdx.x;
+  const int A = a.A, C = a.C, A4 = (A + 3) & ~3, nq = A4 >> 2;
+  const u32x4_w* __restrict__ ws4 = (const u32x4_w*)(a.keys + (long long)b * A4);
+  const bool dense = a.in_score != nullptr;
+
+  if (tid == 0) { sv[0] = 0u; sv[1] = (unsigned)K; sv[2] = 0u; }
+  if (tid < Kp) { clsL[tid] = -1; boxL[tid] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+  __syncthreads();
+
+  // 1. radix select of the K-th largest key among the M non-zero keys (pass 0 counts M)
+  unsigned mask = 0u, M = 0u;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) hist[tid] = 0u;
+    __syncthreads();
+    const unsigned prefix = sv[0];
+    for (int q0 = 0; q0 < nq; q0 += DETW_THREADS) {
+      const int q = q0 + tid;
+      u32x4_w v = (u32x4_w){0u, 0u, 0u, 0u};
+      if (q < nq) v = ws4[q];
+      const unsigned ks[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) detw_hist_add(hist, ks[e] != 0u && (ks[e] & mask) == prefix, (ks[e] >> shift) & 255u, lane);
+    }
+    __syncthreads();
+    const unsigned need = sv[1];
+    const unsigned h = (tid < 256) ? hist[255 - tid] : 0u;     // thread t owns bin 255 - t: the scan counts the keys in higher bins
+    unsigned tot;
+    const unsigned above = detw_excl_scan(h, tot, wave_tot, lane, wave);
+    if (pass == 0) { M = tot; if (M <= (unsigned)K) break; }   // (uniform) every candidate is taken
+    if (tid < 256 && above < need && above + h >= need) {      // exactly one thread
+      sv[1] = need - above;
+      sv[0] = prefix | ((unsigned)(255 - tid) << shift);
+    }
+    mask |= 255u << shift;
+    __syncthreads();
+  }
+  const bool sel = M > (unsigned)K;
+  const unsigned tkey = sel ? sv[0] : 0u;                      // K-th largest key (>= 1), or 0: take every non-zero key
+  const unsigned need = sel ? sv[1] : 0u;                      // keys == tkey to take, in ascending anchor order
+  const unsigned n_gt = sel ? (unsigned)K - need : M;
+  const int ncand = sel ? K : (int)M;
+
+  // 2. one ordered sweep, a contiguous run of quads per thread: keys above tkey are appended in any order (ranked below), the ties
+  //    at tkey take the slots behind them in anchor order
+  {
+    const int chunk = (nq + DETW_THREADS - 1) / DETW_THREADS;
+    const int lo = min(nq, tid * chunk), hi = min(nq, lo + chunk);
+    unsigned r = 0u;
+    if (sel) {
+      unsigned c2 = 0u;
+      for (int q = lo; q < hi; ++q) {
+        const u32x4_w v = ws4[q];
+        c2 += (v.x == tkey ? 1u : 0u) + (v.y == tkey ? 1u : 0u) + (v.z == tkey ? 1u : 0u) + (v.w == tkey ? 1u : 0u);
+      }
+      unsigned tot2;
+      r = detw_excl_scan(c2, tot2, wave_tot, lane, wave);
+    }
+    for (int q = lo; q < hi; ++q) {
+      const u32x4_w v = ws4[q];
+      const unsigned ks[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const unsigned k = ks[e];
+        const unsigned long long word = ((unsigned long long)k << 32) | (unsigned long long)(0xffffffffu - (unsigned)(4 * q + e));
+        if (k > tkey) {
+          const unsigned pos = atomicAdd(&sv[2], 1u);
+          if (pos < n_gt) cand[pos] = word;
+        } else if (sel && k == tkey && r < need) {
+          cand[n_gt + r] = word; ++r;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // 3. rank: score descending, anchor index ascending = the 64-bit words descending; they are distinct, so the ranks are a permutation
+  {
+    unsigned long long mine = 0ull;
+    int rank = 0;
+    if (tid < ncand) {
+      mine = cand[tid];
+      for (int j = 0; j < ncand; ++j) rank += (cand[j] > mine) ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid < ncand) cand[rank] = mine;
+    __syncthreads();
+  }
+
+  // 4. thread r decodes the candidate of rank r
+  const bool ok = tid < ncand;
+  float score = 0.f; int cls = -1, idx = 0;
+  BoxF bx = {0.f, 0.f, 0.f, 0.f};
+  if (ok) {
+    idx = (int)(0xffffffffu - (unsigned)(cand[tid] & 0xffffffffull));
+    if (dense) {
+      const long long o = (long long)b * A + idx;
+      score = a.in_score[o]; cls = (int)a.in_class[o];
+      const f32x4 v = *(const f32x4*)(a.in_box + 4 * o);
+      bx.x1 = v.x; bx.y1 = v.y; bx.x2 = v.z; bx.y2 = v.w;
+    } else {
+      const float* p = a.pred + ((long long)b * A + idx) * (C + 5);
+      anchor_score(p, C, score, cls);
+      bx = anchor_box(p + C + 1, a.anchors + 4 * idx, a.wmax, a.hmax);
+    }
+    boxL[tid] = (f32x4){bx.x1, bx.y1, bx.x2, bx.y2};
+    clsL[tid] = cls;
+  }
+  __syncthreads();
+
+  // 5. suppression matrix: bit j of row i set if j ranks after i, same class, IoU > thresh.  Only blocks on or above the diagonal
+  //    can hold bits: those Wn (Wn + 1) / 2 blocks of 64 rows x 64 columns go round-robin to the waves, lane = row; the rest is zeroed
+  const int Wn = (ncand + 63) >> 6;
+  for (int t = tid; t < 64 * Wn * Wn; t += DETW_THREADS) {
+    const int i = t / Wn, w = t - i * Wn;
+    if (w < (i >> 6)) mat[t] = 0ull;
+  }
+  for (int t = wave; t < Wn * (Wn + 1) / 2; t += DETW_THREADS / 64) {
+    int rb = 0, rem = t;
+    while (rem >= Wn - rb) { rem -= Wn - rb; ++rb; }
+    const int w = rb + rem, i = rb * 64 + lane;
+    const f32x4 me = boxL[i];
+    const int mcls = clsL[i];
+    const float area = (me.z - me.x) * (me.w - me.y);
+    unsigned long long row = 0ull;
+    for (int jj = 0; jj < 64; ++jj) {
+      const int j = w * 64 + jj;
+      const f32x4 o = boxL[j];
+      const int jcls = clsL[j];
+      const float jarea = (o.z - o.x) * (o.w - o.y);
+      const float iw = fmaxf(0.f, fminf(me.z, o.z) - fmaxf(me.x, o.x));
+      const float ih = fmaxf(0.f, fminf(me.w, o.w) - fmaxf(me.y, o.y));
+      const float inter = iw * ih;
+      const float ovr = inter / ((area + jarea) - inter);
+      if (j > i && jcls == mcls && mcls >= 0 && ovr > a.nms_thresh) row |= 1ull << jj;
+    }
+    mat[(long long)i * Wn + w] = row;
+  }
+  __syncthreads();
+
+  // 6. greedy scan on wave 0: lane w holds the alive bits of ranks 64 w .. 64 w + 63; the rows of eight ranks are loaded before
+  //    their alive bits are tested (a row is applied only if its rank is still alive)
+  if (wave == 0) {
+    unsigned long long alive = 0ull;
+    if (lane < Wn) { const int n = min(64, ncand - lane * 64); alive = (n >= 64) ? ~0ull : ((1ull << n) - 1ull); }
+    for (int i0 = 0; i0 < ncand; i0 += 8) {
+      unsigned long long rws[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) rws[u] = (lane < Wn) ? mat[(long long)(i0 + u) * Wn + lane] : 0ull;   // i0 + 7 < 64 Wn
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u;
+        const unsigned half = (i & 32) ? (unsigned)(alive >> 32) : (unsigned)alive;
+        if ((__shfl(half, i >> 6) >> (i & 31)) & 1u) alive &= ~rws[u];
+      }
+    }
+    if (lane < DETW_THREADS / 64) aliveL[lane] = alive;
+  }
+  __syncthreads();
+
+  // 7. compaction: class 0..C-1, each class by rank, then the score threshold
+  const bool keep = ok && ((aliveL[wave] >> lane) & 1ull) && score > a.score_thresh && cls >= 0 && cls < C;
+  unsigned long long mine = 0ull;
+  for (int c = 0; c < C; ++c) {
+    const unsigned long long m = __ballot(keep && cls == c);
+    if (lane == 0) cls_cnt[wave * 16 + c] = (unsigned)__popcll(m);
+    if (cls == c) mine = m;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned total = 0u;
+    for (int w = 0; w < DETW_THREADS / 64; ++w)
+      for (int c = 0; c < C; ++c) total += cls_cnt[w * 16 + c];
+    a.det_count[b] = (int)total;
+  }
+  if (keep) {
+    unsigned pos = (unsigned)__popcll(mine & ((1ull << lane) - 1ull));
+    for (int w = 0; w < DETW_THREADS / 64; ++w) {
+      for (int c = 0; c < cls; ++c) pos += cls_cnt[w * 16 + c];
+      if (w < wave) pos += cls_cnt[w * 16 + cls];
+    }
+    float sx = 1.f, sy = 1.f;
+    if (a.scales) { sy = a.scales[2 * b]; sx = a.scales[2 * b + 1]; }
+    const long long o = (long long)b * K + pos;
+    a.det_class[o] = cls;
+    a.det_score[o] = score;
+    a.det_anchor[o] = idx;
+    f32x4 ob = (f32x4){bx.x1 / sx, bx.y1 / sy, bx.x2 / sx, bx.y2 / sy};
+    // (the padding / crops shift: see detect_kernel)
+    if (a.shifts) { const float dy = a.shifts[2 * b], dx = a.shifts[2 * b + 1]; ob.x += dx; ob.y += dy; ob.z += dx; ob.w += dy; }
+    *(f32x4*)(a.det_box + 4 * o) = ob;
+  }
+}
+
+// int32 words of the wide workspace: B x ceil4(A) keys.  -1: (B, A, K) is outside what the wide path takes.
+extern "C" int sqd_detect_wide_workspace_words(int B, int A, int keep_top_k) {
+  if (B < 1 || A < 1 || A > DETW_MAX_A || keep_top_k < 1 || keep_top_k > DETW_MAX_K) return -1;
+  const long long words = (long long)B * ((A + 3) & ~3);
+  return words > 0x7fffffffll ? -1 : (int)words;
+}
+
+static int launch_detect_wide(DetArgs a, int ws_words, hipStream_t stream) {
+  SQD_CHECK_ARG(a.B > 0 && a.A > 0 && a.C >= 1 && a.K >= 1);
+  if (a.K > DETW_MAX_K || a.A > DETW_MAX_A || a.C > SQD_MAX_CLASSES) return SQD_ERR_UNSUPPORTED;
+  const int words = sqd_detect_wide_workspace_words(a.B, a.A, a.K);
+  if (words < 0) return SQD_ERR_UNSUPPORTED;                  // (B x ceil4(A) past 2^31 - 1 words)
+  SQD_CHECK_ARG(a.keys && ws_words >= words && ((uintptr_t)a.keys & 15) == 0);
+  const int Kp = (a.K + 63) & ~63, A4 = (a.A + 3) & ~3;
+  const size_t lds = (size_t)Kp * (8 + 16 + 4) + DETW_LDS_FIXED + (size_t)Kp * (Kp / 64) * 8;   // <= 162000 bytes at K = 1024
+  static SqdDevOnce lds_once;
+  if (lds > 48 * 1024 && sqd_max_lds_once(lds_once, (const void*)detect_wide_select_kernel, 160 * 1024) != SQD_OK) return SQD_ERR_LAUNCH;
+  const int slabs = (A4 + DETW_SCORE_THREADS - 1) / DETW_SCORE_THREADS;          // B x slabs <= 2^23 + B
+  hipLaunchKernelGGL(detect_wide_score_kernel, dim3((unsigned)(a.B * slabs)), dim3(DETW_SCORE_THREADS), 0, stream, a);
+  hipLaunchKernelGGL(detect_wide_select_kernel, dim3((unsigned)a.B), dim3(DETW_THREADS), lds, stream, a);
+  return sqd_launch_status();
+}
+
+// sqd_detect_shift_fwd for any 1 <= keep_top_k <= 1024 and 1 <= A <= 2^20: same outputs bit for bit where both run.  keys_ws: a
+// 16-byte aligned workspace of ws_words >= sqd_detect_wide_workspace_words(B, A, keep_top_k) uint32, any contents; nothing in it
+// carries over from launch to launch.  Status 2 for keep_top_k, A or num_classes past the limits, 1 for anything malformed
+// (a null pointer, keep_top_k < 1, a short or misaligned workspace); nothing is launched then.
+extern "C" int sqd_detect_wide_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                                   int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                   int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                                   int ws_words, void* stream) {
+  SQD_CHECK_ARG(pred && anchors && keys_ws && det_count && det_class && det_score && det_box && det_anchor);
+  SQD_CHECK_ARG(((uintptr_t)pred & 15) == 0 && ((uintptr_t)det_box & 15) == 0);
+  DetArgs a;
+  a.shifts = shifts;
+  a.pred = pred; a.anchors = anchors; a.scales = scales; a.in_class = nullptr; a.in_score = nullptr; a.in_box = nullptr; a.keys = keys_ws;
+  a.S = 1; a.per = 0;
+  a.det_count = det_count; a.det_class = det_class; a.det_score = det_score; a.det_box = det_box; a.det_anchor = det_anchor;
+  a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
+  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
+  a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
+  return launch_detect_wide(a, ws_words, (hipStream_t)stream);
+}
+
+// sqd_filter_fwd for the same ranges (dense class_ids int64 [B][A], scores [B][A], boxes [B][A][4])
+extern "C" int sqd_filter_wide_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
+                                   long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                   int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words, void* stream) {
+  SQD_CHECK_ARG(class_ids && scores && boxes && keys_ws && det_count && det_class && det_score && det_box && det_anchor);
+  SQD_CHECK_ARG(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)det_box & 15) == 0);
+  DetArgs a;
+  a.shifts = nullptr;
+  a.pred = nullptr; a.anchors = nullptr; a.scales = nullptr; a.in_class = class_ids; a.in_score = scores; a.in_box = boxes; a.keys = keys_ws;
+  a.S = 1; a.per = 0;
+  a.det_count = det_count; a.det_class = det_class; a.det_score = det_score; a.det_box = det_box; a.det_anchor = det_anchor;
+  a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
+  a.wmax = 0.f; a.hmax = 0.f; a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
+  return launch_detect_wide(a, ws_words, (hipStream_t)stream);
+}

@@ -37,8 +37,9 @@ class Detector(object):
         cfg = self.cfg
         pred = self.model.base(image)
         anchors = self.model.resolver.anchors_on(pred.device)
-        return ops.detect(pred, anchors, cfg.input_size, cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh,
-                          cfg.score_thresh, scales=scales, out=out, shifts=shifts)
+        fused = ops.detect if ops.detect_path(cfg.keep_top_k, pred.shape[1]) == 'narrow' else ops.detect_wide
+        return fused(pred, anchors, cfg.input_size, cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh,
+                     cfg.score_thresh, scales=scales, out=out, shifts=shifts)
 
     @torch.no_grad()
     def detect(self, batch):
@@ -221,8 +222,9 @@ class Detector(object):
         """One image's dense ``{'class_ids' [A], 'scores' [A], 'boxes' [A,4]}`` (GPU tensors) ->
         filtered dict of GPU tensors (plus ``anchor_idx``) or ``None``."""
         cfg = self.cfg
-        cnt, cls, sc, bx, idx = ops.filter_dense(det['class_ids'][None], det['scores'][None], det['boxes'][None],
-                                                 cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh, cfg.score_thresh)
+        dense = ops.filter_dense if ops.detect_path(cfg.keep_top_k, det['scores'].shape[0]) == 'narrow' else ops.filter_dense_wide
+        cnt, cls, sc, bx, idx = dense(det['class_ids'][None], det['scores'][None], det['boxes'][None],
+                                      cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh, cfg.score_thresh)
         n = int(cnt[0].item())
         if n == 0:
             return None

@@ -584,7 +584,7 @@ def _det_buffers(B, K, device, A=None):
             torch.zeros(B, K, device=device, dtype=torch.float32), torch.zeros(B, K, 4, device=device, dtype=torch.float32),
             torch.zeros(B, K, device=device, dtype=torch.int32))
     if A is not None:
-        bufs = bufs + (_det_workspace(B, A, device),)
+        bufs = bufs + (_det_workspace(B, A, device, K),)
     return bufs
 
 
@@ -608,7 +608,7 @@ def det_buffers_packed(B, K, device, A=None):
     flat = torch.zeros(total, device=device, dtype=torch.uint8)
     bufs = tuple(flat[o:o + n * torch.empty(0, dtype=dt).element_size()].view(dt).view(shp) for o, n, dt, shp in secs)
     if A is not None:
-        bufs = bufs + (_det_workspace(B, A, device),)
+        bufs = bufs + (_det_workspace(B, A, device, K),)
     return bufs, flat
 
 
@@ -617,9 +617,42 @@ def det_workspace_words(B, A):
     return B * (-(-A // 4) * 4) + B
 
 
-def _det_workspace(B, A, device):
-    """Workspace of the fused detect launch (``keys_ws``): the keys the eight scoring workgroups of an image hand to its last arriver
-    + one arrival counter per image.  Zeroed once: every launch returns the counters to zero."""
+DET_NARROW_MAX_K = 64          # detect_kernel: one wave holds the 64 x 64 suppression matrix
+DET_NARROW_MAX_A = 25596       # ... and an image's keys + uint16 candidate indices fit 150 KB of LDS
+DET_WIDE_MAX_K = 1024          # the wide path: one candidate per thread of a 1024-thread workgroup, 128 KB bit matrix in LDS
+DET_WIDE_MAX_A = 1 << 20       # gt_encode's own limit
+
+
+def detect_path(K, A):
+    """Which fused detect serves ``keep_top_k = K`` on ``A`` anchors: 'narrow' (``detect`` / ``filter_dense``: one launch, the
+    benchmarked kernel) for K <= 64 and A <= 25 596, else 'wide' (``detect_wide`` / ``filter_dense_wide``).  ValueError past the
+    wide path's limits."""
+    K, A = int(K), int(A)
+    if K < 1 or A < 1:
+        raise ValueError(f'detect: keep_top_k and the anchor count must be >= 1 (got {K}, {A})')
+    if K > DET_WIDE_MAX_K:
+        raise ValueError(f'detect: keep_top_k {K} exceeds the limit of {DET_WIDE_MAX_K}')
+    if A > DET_WIDE_MAX_A:
+        raise ValueError(f'detect: {A} anchors exceed the limit of {DET_WIDE_MAX_A} (2^20)')
+    return 'narrow' if K <= DET_NARROW_MAX_K and A <= DET_NARROW_MAX_A else 'wide'
+
+
+def det_workspace_words_wide(B, A, K):
+    """int32 words of the wide detect workspace (``sqd_detect_wide_workspace_words``: B x ceil4(A) keys)."""
+    n = int(nat.lib().sqd_detect_wide_workspace_words(int(B), int(A), int(K)))
+    if n < 0:
+        detect_path(K, A)                                  # names the limit
+        raise ValueError(f'detect: no wide workspace for B={B}, A={A}, keep_top_k={K}')
+    return n
+
+
+def _det_workspace(B, A, device, K=DET_NARROW_MAX_K):
+    """Workspace of the fused detect launch (``keys_ws``).  Narrow path: the keys the eight scoring workgroups of an image hand to
+    its last arriver + one arrival counter per image; zeroed once, every launch returns the counters to zero.  Parameters only the
+    wide path takes (``detect_path``): its key workspace.  (Parameters neither takes get the narrow size: that launch refuses them.)"""
+    K, A = int(K), int(A)
+    if (K > DET_NARROW_MAX_K or A > DET_NARROW_MAX_A) and 1 <= K <= DET_WIDE_MAX_K and 1 <= A <= DET_WIDE_MAX_A:
+        return torch.zeros(det_workspace_words_wide(B, A, K), device=device, dtype=torch.int32)
     return torch.zeros(det_workspace_words(B, A), device=device, dtype=torch.int32)
 
 
@@ -698,6 +731,71 @@ def filter_dense(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thres
                                   int(keep_top_k), float(nms_thresh), float(score_thresh), nat.stream_handle(scores.device))
     nat.check(rc, 'sqd_filter_fwd')
     return bufs[:5]
+
+
+def _wide_workspace(name, bufs, B, A, K, device):
+    """The key workspace of a wide launch: the caller's sixth ``out`` tensor if it is large enough, else a fresh one."""
+    need = det_workspace_words_wide(B, A, K)
+    keys = bufs[5] if len(bufs) == 6 else None
+    if keys is not None and (not isinstance(keys, torch.Tensor) or keys.dtype != torch.int32 or keys.device != device):
+        raise ValueError(f'{name}: workspace must be an int32 tensor on the same device')
+    if keys is None or keys.numel() < need or not keys.is_contiguous() or keys.data_ptr() % 16:
+        keys = torch.empty(need, device=device, dtype=torch.int32)
+    return keys
+
+
+def detect_wide(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None):
+    """``detect`` for any 1 <= ``keep_top_k`` <= 1024 and up to 2^20 anchors (two launches: score into a workspace, then one
+    workgroup per image selects, suppresses and compacts); same arguments, same results bit for bit where both run.  ``out``: the
+    five result tensors and optionally a workspace of ``det_workspace_words_wide(B, A, keep_top_k)`` int32 (any contents)."""
+    if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
+        raise ValueError(f'detect_wide: bad pred {tuple(pred.shape)}')
+    _check_score_thresh('detect_wide', score_thresh)
+    pred = pred.contiguous()
+    B, A, _ = pred.shape
+    K = int(keep_top_k)
+    detect_path(K, A)                                      # ValueError naming the limit, before anything is allocated or written
+    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
+        raise ValueError('detect_wide: anchors must be fp32 [A,4] on the same device')
+    if scales is not None and (tuple(scales.shape) != (B, 2) or scales.dtype != torch.float32 or scales.device != pred.device):
+        raise ValueError('detect_wide: scales must be fp32 [B,2] (sy, sx)')
+    if shifts is not None and (tuple(shifts.shape) != (B, 2) or shifts.dtype != torch.float32 or shifts.device != pred.device or not shifts.is_contiguous()):
+        raise ValueError('detect_wide: shifts must be contiguous fp32 [B,2] (dy, dx)')
+    if out is not None:
+        _check_det_out(out, B, K, pred.device)
+    bufs = tuple(out) if out is not None else _det_buffers(B, K, pred.device)
+    keys = _wide_workspace('detect_wide', bufs, B, A, K, pred.device)
+    cnt, cls, sc, bx, idx = bufs[:5]
+    br = _Bracket('detect', f'detect_wide A{A} K{K}', 0.0, 4.0 * B * A * (num_classes + 5)) if timing._timer is not None else None
+    rc = nat.lib().sqd_detect_wide_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
+                                       nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                       int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
+                                       keys.numel(), nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_detect_wide_fwd')
+    if br is not None:
+        br.done()
+    return bufs[:5]
+
+
+def filter_dense_wide(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3):
+    """``filter_dense`` for any 1 <= ``keep_top_k`` <= 1024 and up to 2^20 anchors."""
+    if scores.dim() != 2 or class_ids.shape != scores.shape or tuple(boxes.shape) != tuple(scores.shape) + (4,):
+        raise ValueError('filter_wide: shape mismatch')
+    if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda \
+            or class_ids.device != scores.device or boxes.device != scores.device:
+        raise ValueError('filter_wide: dtype/device mismatch')
+    _check_score_thresh('filter_wide', score_thresh)
+    B, A = scores.shape
+    K = int(keep_top_k)
+    detect_path(K, A)
+    bufs = _det_buffers(B, K, scores.device)
+    keys = _wide_workspace('filter_wide', bufs, B, A, K, scores.device)
+    cnt, cls, sc, bx, idx = bufs
+    rc = nat.lib().sqd_filter_wide_fwd(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
+                                       nat.ptr(keys), nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                       K, float(nms_thresh), float(score_thresh), keys.numel(), nat.stream_handle(scores.device))
+    nat.check(rc, 'sqd_filter_wide_fwd')
+    return bufs
 
 
 def conv_wgrad(dy, dy_coff, N, x, x_coff, C, taps, slab=None, wino=None):
