@@ -223,6 +223,35 @@ int sqd_filter_wide_fwd(const long long* class_ids, const float* scores, const f
 /* int32 words of the wide workspace (B x ceil4(A)), or -1 for a (B, A, keep_top_k) the wide path does not take. */
 int sqd_detect_wide_workspace_words(int B, int A, int keep_top_k);
 
+/* ConvDet of any width (csrc/convdet_pad.hip): a ConvDet whose anchors_per_grid * (num_classes + 5) the convolution forms do not take
+ * runs at a padded width Npad (zero weight / bias rows past N).  sqd_channel_pack_fwd: dst [rows][N] = src [rows][Npad][:N] (the
+ * contiguous pred); sqd_channel_unpack_fwd: dst [rows][Npad] = src [rows][N], zero past N (dpred for the gradient launches);
+ * sqd_wgrad_reduce_rows: the S split-K slabs an Npad-wide weight gradient wrote (Npad * taps * C + Npad floats each), reduced over the
+ * first N rows into dw [N][C][k][k] and db [N], times scale.  Status 1 for anything malformed. */
+int sqd_channel_pack_fwd(const float* src, float* dst, long long rows, int N, int Npad, void* stream);
+int sqd_channel_unpack_fwd(const float* src, float* dst, long long rows, int N, int Npad, void* stream);
+int sqd_wgrad_reduce_rows(const float* slab, float* dw, float* db, int S, int N, int Npad, int C, int taps, float scale, void* stream);
+
+/* Many-class head: the dense decode, PredictionResolver, the fused detect from pred and the dense filter for
+ * 1 <= num_classes <= 256.  A group of 16 lanes owns an anchor row, lane j holding classes j, j + 16, ... in at most 16 registers
+ * (256 = 16 lanes x 16 registers); arguments, outputs and semantics are those of sqd_decode_fwd / sqd_resolve_fwd /
+ * sqd_detect_wide_fwd / sqd_filter_wide_fwd (workspace: sqd_detect_wide_workspace_words; every 1 <= keep_top_k <= 1024 and
+ * 1 <= A <= 2^20).  score = max_c softmax_c * sigmoid(conf), class = the lowest index attaining it.  The fused detect equals
+ * Detector.filter on sqd_decode_many_fwd's output bit for bit.  Status 1 for anything malformed (null pointer, num_classes < 1,
+ * keep_top_k < 1, short or misaligned workspace), 2 for num_classes > 256, keep_top_k > 1024 or A > 2^20; nothing is launched then.
+ * The <= 16-class entry points above keep their own limit. */
+int sqd_decode_many_fwd(const float* pred, const float* anchors, long long* class_ids, float* scores, float* boxes,
+                        int B, int A, int num_classes, int input_h, int input_w, void* stream);
+int sqd_resolve_many_fwd(const float* pred, const float* anchors, float* probs, float* logp, float* scores, float* deltas,
+                         float* boxes, int B, int A, int num_classes, int input_h, int input_w, void* stream);
+int sqd_detect_many_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                        int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                        int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                        int ws_words, void* stream);
+int sqd_filter_many_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
+                        long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                        int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words, void* stream);
+
 /* GPU-side input pipeline: whiten + cv2.resize(INTER_LINEAR) + HWC->CHW of
  * DataWrapper.__getitem__ / BaseDataset.preprocess / whiten / resize (src/engine/detector.py:132-142,
  * src/datasets/base.py:43-59, src/utils/image.py:9-19,77-88) for a batch of uint8 RGB images of arbitrary sizes.
@@ -385,6 +414,20 @@ int sqd_loss_mean_fwd(const float* pred, const float* gt, const float* anchors, 
 int sqd_loss_mean_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* gmean, float* dpred,
                       int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
                       float w_bbox, void* stream);
+/* The four loss launches for 1 <= num_classes <= 256 (16-lane row groups as in the many-class head; same arguments and
+ * workspace; deterministic two-stage sums).  Status 1 for anything malformed, 2 for num_classes > 256. */
+int sqd_loss_many_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses, float* nobj,
+                      int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                      float w_bbox, void* stream);
+int sqd_loss_many_mean_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses, float* nobj,
+                           float* mean4, int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos,
+                           float w_neg, float w_bbox, void* stream);
+int sqd_loss_many_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* coef,
+                      float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                      float w_pos, float w_neg, float w_bbox, void* stream);
+int sqd_loss_many_mean_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* gmean,
+                           float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos,
+                           float w_neg, float w_bbox, void* stream);
 
 
 /* Fire.forward's two expand convolutions + torch.cat (src/model/squeezedet.py:18-22) in ONE Winograd launch (inference):

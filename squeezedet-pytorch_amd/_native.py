@@ -56,6 +56,13 @@ _SIGNATURES = {
     'sqd_detect_wide_fwd': [c_p] * 10 + [c_i] * 6 + [c_f, c_f, c_i, c_p],
     'sqd_filter_wide_fwd': [c_p] * 9 + [c_i] * 4 + [c_f, c_f, c_i, c_p],
     'sqd_detect_wide_workspace_words': [c_i, c_i, c_i],
+    'sqd_channel_pack_fwd': [c_p, c_p, ctypes.c_longlong, c_i, c_i, c_p],
+    'sqd_channel_unpack_fwd': [c_p, c_p, ctypes.c_longlong, c_i, c_i, c_p],
+    'sqd_wgrad_reduce_rows': [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p],
+    'sqd_decode_many_fwd': [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    'sqd_resolve_many_fwd': [c_p] * 7 + [c_i] * 5 + [c_p],
+    'sqd_detect_many_fwd': [c_p] * 10 + [c_i] * 6 + [c_f, c_f, c_i, c_p],
+    'sqd_filter_many_fwd': [c_p] * 9 + [c_i] * 4 + [c_f, c_f, c_i, c_p],
     'sqd_preprocess_u8_fwd': [c_p] * 5 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],
     'sqd_preprocess_u8_padcrop_fwd': [c_p] * 6 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],
     'sqd_preprocess_u8_aug_fwd': [c_p] * 6 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],
@@ -95,6 +102,10 @@ _SIGNATURES = {
     'sqd_loss_bwd': [c_p] * 6 + [c_i] * 5 + [c_f] * 4 + [c_p],
     'sqd_loss_mean_fwd': [c_p] * 7 + [c_i] * 5 + [c_f] * 4 + [c_p],
     'sqd_loss_mean_bwd': [c_p] * 6 + [c_i] * 5 + [c_f] * 4 + [c_p],
+    'sqd_loss_many_fwd': [c_p] * 6 + [c_i] * 5 + [c_f] * 4 + [c_p],
+    'sqd_loss_many_bwd': [c_p] * 6 + [c_i] * 5 + [c_f] * 4 + [c_p],
+    'sqd_loss_many_mean_fwd': [c_p] * 7 + [c_i] * 5 + [c_f] * 4 + [c_p],
+    'sqd_loss_many_mean_bwd': [c_p] * 6 + [c_i] * 5 + [c_f] * 4 + [c_p],
 }
 # symbols added by later build stages; bound when present in the library
 _OPTIONAL = {}

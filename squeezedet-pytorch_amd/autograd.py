@@ -41,6 +41,7 @@ def run_backbone_forward(base, image, save=False, drop_mask=None, drop=None):
     def empty(*shape, dtype=torch.float32):
         return torch.empty(B, *shape, device=dev, dtype=dtype)
     saved = {} if save else None
+    cd = base.convdet_exec()                   # (a padded ConvDet's stand-in is brought up to date before the plans are refreshed)
     base.refresh_plans()                       # one batched re-pack if the optimizer touched the parameters
     stem = feats[0]
     bridged = None                             # the next Fire's squeeze output, produced by the previous launch
@@ -140,9 +141,11 @@ def run_backbone_forward(base, image, save=False, drop_mask=None, drop=None):
         if save:
             saved[f'fire{i}'] = (a, sq, out)
         a = out
-    cd = base.convdet
     pred = empty(steps[-1].H, steps[-1].W, cd.out_channels)
     base.conv3x3('convdet', cd, a, 0, pred, 0, relu=False)
+    if cd is not base.convdet:
+        # a width the convolution forms do not take ran zero-padded into a scratch: pack it into the contiguous reference layout
+        pred = ops.convdet_pack(pred, base.convdet.out_channels)
     if drop is not None:
         # this forward's mask is consumed: step += 1 on the device.  (The balanced Winograd kernel can carry the advance inside its
         # launch -- ops.conv_wino(..., drop_advance=) -- but measured inside the step it runs ConvDet's forward slower than the unit

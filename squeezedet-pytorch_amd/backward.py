@@ -16,14 +16,15 @@ from .autograd import run_backbone_forward
 from .synthetic import layer_table
 
 
-def _wgrad_layout(base, wgrad):
+def _wgrad_layout(base, wgrad, skip=()):
     """Flat gradient layout (named_parameters order: every gradient is a view of ONE buffer) and the batched-reduction
-    entries of all Fire / ConvDet weight gradients (``wgrad``: plan.backward_schedule, in backward order)."""
+    entries of all Fire / ConvDet weight gradients (``wgrad``: plan.backward_schedule, in backward order; ``skip``: prefixes
+    reduced on their own -- a padded ConvDet, whose slabs are wider than its gradient)."""
     slots, off = {}, 0
     for n, p in base.named_parameters():
         slots[n] = (off, tuple(p.shape)); off += p.numel()
     entries = [(pre, w.N, w.C, w.taps, *w.shape, slots[pre + '.weight'][0], slots[pre + '.bias'][0], w.fused, w.group)
-               for pre, w in wgrad.items()]
+               for pre, w in wgrad.items() if pre not in skip]
     return entries, slots, off
 
 
@@ -34,14 +35,19 @@ def run_backbone_backward(base, saved, dpred):
     feats = base.features
     dpred = dpred.contiguous()
     B, H, W, ncd = dpred.shape
-    cd = base.convdet
+    cd = base.convdet_exec()
+    padded = cd is not base.convdet
+    if padded:
+        # ConvDet ran zero-padded (ops.convdet_width): its gradient launches read dpred spread to that width, zero past ncd
+        n_true, ncd = ncd, cd.out_channels
+        dpred = ops.convdet_unpack(dpred, ncd)
     a_in = saved['convdet_in']
     cin_cd = a_in.shape[3]
     shapes = tuple(tuple(saved[f'fire{i}'][2].shape) for i in range(len(layers)) if layers[i][0] == 'fire')
     wgrad, convdet_sk = plan.backward_schedule(base.arch, [s[:3] for s in shapes], ncd, base.fuse_squeeze_bwd, base.group_wgrad,
                                                saved['drop_scale'] is not None)
     shape_key = (B, H, W, bool(base.fuse_squeeze_bwd), base.group_wgrad) + shapes
-    wb, slots, total = base.wgrad_batch(lambda: _wgrad_layout(base, wgrad), shape_key)
+    wb, slots, total = base.wgrad_batch(lambda: _wgrad_layout(base, wgrad, ('convdet',) if padded else ()), shape_key)
     # + 1: the data-parallel exchange carries this rank's image count through the same all-reduce (trainer.GradientExchange)
     grad_buf = torch.empty(total + 1, device=dpred.device, dtype=torch.float32)
     grad_flat = grad_buf[:total]
@@ -73,7 +79,16 @@ def run_backbone_backward(base, saved, dpred):
         for d in shape:
             n *= d
         return grad_flat[off:off + n].view(shape)
-    ops.conv_wgrad(dpred, 0, ncd, a_in, 0, cin_cd, 9, slab=wb.slab('convdet'))
+    if padded:
+        # slabs of the padded width in a workspace of their own, reduced over the first n_true rows straight into the parameter-shaped
+        # views of the flat buffer (times the data-parallel weight, as wb.reduce would)
+        S_cd, stride_cd = ops.wgrad_split(ncd, cin_cd, 9, B, H, W)
+        slab_cd = base.convdet_slab(S_cd * stride_cd)
+        ops.conv_wgrad(dpred, 0, ncd, a_in, 0, cin_cd, 9, slab=slab_cd)
+        ops.wgrad_reduce_rows(slab_cd, S_cd, n_true, ncd, cin_cd, 9, gview('convdet.weight'), gview('convdet.bias'),
+                              scale=1.0 if sync is None else sync.scale)
+    else:
+        ops.conv_wgrad(dpred, 0, ncd, a_in, 0, cin_cd, 9, slab=wb.slab('convdet'))
     last = len(layers) - 1
     assert layers[last][0] == 'fire'
     out_last = saved[f'fire{last}'][2]
@@ -185,7 +200,7 @@ class LossFn(torch.autograd.Function):
         res = loss_mod.resolver
         weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
                    loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
-        losses, nobj = ops.loss_fwd(pred.detach(), gt, anchors, res.input_size, res.num_classes, weights)
+        losses, nobj = ops.loss_fns(res.num_classes)[0](pred.detach(), gt, anchors, res.input_size, res.num_classes, weights)
         ctx.save_for_backward(pred.detach(), gt, anchors, nobj)
         ctx.meta = (res.input_size, res.num_classes, weights)
         return losses                      # [4,B] = (class, score, bbox, total)
@@ -195,7 +210,7 @@ class LossFn(torch.autograd.Function):
         pred, gt, anchors, nobj = ctx.saved_tensors
         input_size, num_classes, weights = ctx.meta
         coef = (g[:3] + g[3:4]).contiguous()       # gradient of `total` reaches all three components
-        dpred = ops.loss_bwd(pred, gt, anchors, nobj, coef, input_size, num_classes, weights)
+        dpred = ops.loss_fns(num_classes)[2](pred, gt, anchors, nobj, coef, input_size, num_classes, weights)
         return dpred, None, None, None
 
 
@@ -209,7 +224,7 @@ class LossMeanFn(torch.autograd.Function):
         res = loss_mod.resolver
         weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
                    loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
-        losses, nobj, mean4 = ops.loss_mean_fwd(pred.detach(), gt, anchors, res.input_size, res.num_classes, weights)
+        losses, nobj, mean4 = ops.loss_fns(res.num_classes)[1](pred.detach(), gt, anchors, res.input_size, res.num_classes, weights)
         ctx.save_for_backward(pred.detach(), gt, anchors, nobj)
         ctx.meta = (res.input_size, res.num_classes, weights)
         ctx.mark_non_differentiable(losses)
@@ -220,4 +235,4 @@ class LossMeanFn(torch.autograd.Function):
     def backward(ctx, g, _gl):
         pred, gt, anchors, nobj = ctx.saved_tensors
         input_size, num_classes, weights = ctx.meta
-        return ops.loss_mean_bwd(pred, gt, anchors, nobj, g.reshape(1), input_size, num_classes, weights), None, None, None
+        return ops.loss_fns(num_classes)[3](pred, gt, anchors, nobj, g.reshape(1), input_size, num_classes, weights), None, None, None

@@ -13,11 +13,22 @@ import numpy as np
 
 from .boxes import KITTI_ANCHORS_SEED, KITTI_INPUT_SIZE, generate_anchors
 
+MAX_CLASSES = 256                # ops.HEAD_MANY_MAX_CLASSES (this module imports no kernels)
+KITTI_CLASS_NAMES = ('Car', 'Pedestrian', 'Cyclist')
+
 
 def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_ANCHORS_SEED,
-             num_classes=3, class_names=('Car', 'Pedestrian', 'Cyclist'), device='cuda', **overrides):
+             num_classes=3, class_names=None, device='cuda', **overrides):
     """Namespace with the reference's defaults (src/utils/config.py:23-85) plus the
-    dataset-derived fields of ``Config.update_dataset_info`` (:121-131)."""
+    dataset-derived fields of ``Config.update_dataset_info`` (:121-131).  ``num_classes``: 1 .. 256 (the head kernels' limit: 16
+    lanes x 16 registers per anchor row); ``class_names``: one name per class (default: KITTI's three, else 'class0', 'class1', ...)."""
+    num_classes = int(num_classes)
+    if not 1 <= num_classes <= MAX_CLASSES:
+        raise ValueError(f'make_cfg: num_classes must be in 1 .. {MAX_CLASSES}, got {num_classes}')
+    if class_names is None:
+        class_names = KITTI_CLASS_NAMES if num_classes == len(KITTI_CLASS_NAMES) else tuple(f'class{i}' for i in range(num_classes))
+    if len(class_names) != num_classes:
+        raise ValueError(f'make_cfg: {len(class_names)} class_names for num_classes = {num_classes} (one name per class, at most {MAX_CLASSES})')
     grid_size = tuple(x // 16 for x in input_size)           # src/datasets/kitti.py:26
     anchors = generate_anchors(grid_size, input_size, np.asarray(anchors_seed))
     cfg = SimpleNamespace(

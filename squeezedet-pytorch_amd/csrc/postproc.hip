@@ -20,6 +20,7 @@
 // Arithmetic mirrors the oracle op for op in fp32 (built with -ffp-contract=off, IEEE division), so
 // that, given identical pred, the kept anchor indices are bit-exact.
 #include "sqd_common.h"
+#include "many_class.h"
 #include <math.h>
 
 #define SQD_MAX_CLASSES 16
@@ -569,6 +570,9 @@ __device__ __forceinline__ void detw_hist_add(unsigned* hist, bool act, unsigned
   if (act) atomicAdd(&hist[bin], 1u);
 }
 
+// MANY = false: the <= 16-class form (thread r re-decodes rank r with anchor_score, placement from per-wave per-class counts).
+// MANY = true: the many-class form (see "many-class head" below); everything that does not depend on C is shared.
+template <bool MANY>
 __global__ __launch_bounds__(DETW_THREADS) void detect_wide_select_kernel(DetArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int K = a.K, Kp = (K + 63) & ~63;                     // Kp <= 1024: one candidate slot per thread
@@ -676,7 +680,30 @@ __global__ __launch_bounds__(DETW_THREADS) void detect_wide_select_kernel(DetArg
   const bool ok = tid < ncand;
   float score = 0.f; int cls = -1, idx = 0;
   BoxF bx = {0.f, 0.f, 0.f, 0.f};
-  if (ok) {
+  if (MANY && !dense) {
+    // a 16-lane group per candidate (64 groups, <= 16 rounds): the class comes from the same mc_anchor_score that made the key, so
+    // the score IS the key; lane 0 of the group decodes the box
+    const int j = tid & (MC_LANES - 1);
+    for (int r = tid / MC_LANES; r < ncand; r += DETW_THREADS / MC_LANES) {
+      const int ai = (int)(0xffffffffu - (unsigned)(cand[r] & 0xffffffffull));
+      const float* p = a.pred + ((long long)b * A + ai) * (C + 5);
+      float s; int c;
+      mc_anchor_score<MC_REGS>(p, C, j, s, c);
+      if (j == 0) {
+        const BoxF bb = anchor_box(p + C + 1, a.anchors + 4 * ai, a.wmax, a.hmax);
+        boxL[r] = (f32x4){bb.x1, bb.y1, bb.x2, bb.y2};
+        clsL[r] = c;
+      }
+    }
+    __syncthreads();
+    if (ok) {
+      idx = (int)(0xffffffffu - (unsigned)(cand[tid] & 0xffffffffull));
+      score = __uint_as_float((unsigned)(cand[tid] >> 32));
+      cls = clsL[tid];
+      const f32x4 v = boxL[tid];
+      bx.x1 = v.x; bx.y1 = v.y; bx.x2 = v.z; bx.y2 = v.w;
+    }
+  } else if (ok) {
     idx = (int)(0xffffffffu - (unsigned)(cand[tid] & 0xffffffffull));
     if (dense) {
       const long long o = (long long)b * A + idx;
@@ -745,6 +772,38 @@ __global__ __launch_bounds__(DETW_THREADS) void detect_wide_select_kernel(DetArg
 
   // 7. compaction: class 0..C-1, each class by rank, then the score threshold
   const bool keep = ok && ((aliveL[wave] >> lane) & 1ull) && score > a.score_thresh && cls >= 0 && cls < C;
+  if (MANY) {
+    // placement by counting (class, rank) pairs: a [16 waves][256 classes] count table does not fit beside the matrix at K = 1024,
+    // and clsL is dead after the matrix was built -- it now holds the class of every survivor (-1: dropped); a survivor's row is the
+    // number of survivors with a smaller (class, rank).  <= 1024 LDS broadcast reads per thread, independent of C.
+    __syncthreads();
+    if (tid < Kp) clsL[tid] = keep ? cls : -1;
+    const unsigned long long km = __ballot(keep);
+    if (lane == 0) wave_tot[wave] = (unsigned)__popcll(km);
+    __syncthreads();
+    if (tid == 0) {
+      unsigned total = 0u;
+      for (int w = 0; w < DETW_THREADS / 64; ++w) total += wave_tot[w];
+      a.det_count[b] = (int)total;
+    }
+    if (keep) {
+      unsigned pos = 0u;
+      for (int r = 0; r < ncand; ++r) {
+        const int cr = clsL[r];
+        pos += (cr >= 0 && (cr < cls || (cr == cls && r < tid))) ? 1u : 0u;
+      }
+      float sx = 1.f, sy = 1.f;
+      if (a.scales) { sy = a.scales[2 * b]; sx = a.scales[2 * b + 1]; }
+      const long long o = (long long)b * K + pos;
+      a.det_class[o] = cls;
+      a.det_score[o] = score;
+      a.det_anchor[o] = idx;
+      f32x4 ob = (f32x4){bx.x1 / sx, bx.y1 / sy, bx.x2 / sx, bx.y2 / sy};
+      if (a.shifts) { const float dy = a.shifts[2 * b], dx = a.shifts[2 * b + 1]; ob.x += dx; ob.y += dy; ob.z += dx; ob.w += dy; }
+      *(f32x4*)(a.det_box + 4 * o) = ob;
+    }
+    return;
+  }
   unsigned long long mine = 0ull;
   for (int c = 0; c < C; ++c) {
     const unsigned long long m = __ballot(keep && cls == c);
@@ -793,10 +852,10 @@ static int launch_detect_wide(DetArgs a, int ws_words, hipStream_t stream) {
   const int Kp = (a.K + 63) & ~63, A4 = (a.A + 3) & ~3;
   const size_t lds = (size_t)Kp * (8 + 16 + 4) + DETW_LDS_FIXED + (size_t)Kp * (Kp / 64) * 8;   // <= 162000 bytes at K = 1024
   static SqdDevOnce lds_once;
-  if (lds > 48 * 1024 && sqd_max_lds_once(lds_once, (const void*)detect_wide_select_kernel, 160 * 1024) != SQD_OK) return SQD_ERR_LAUNCH;
+  if (lds > 48 * 1024 && sqd_max_lds_once(lds_once, (const void*)detect_wide_select_kernel<false>, 160 * 1024) != SQD_OK) return SQD_ERR_LAUNCH;
   const int slabs = (A4 + DETW_SCORE_THREADS - 1) / DETW_SCORE_THREADS;          // B x slabs <= 2^23 + B
   hipLaunchKernelGGL(detect_wide_score_kernel, dim3((unsigned)(a.B * slabs)), dim3(DETW_SCORE_THREADS), 0, stream, a);
-  hipLaunchKernelGGL(detect_wide_select_kernel, dim3((unsigned)a.B), dim3(DETW_THREADS), lds, stream, a);
+  hipLaunchKernelGGL(detect_wide_select_kernel<false>, dim3((unsigned)a.B), dim3(DETW_THREADS), lds, stream, a);
   return sqd_launch_status();
 }
 
@@ -835,4 +894,187 @@ extern "C" int sqd_filter_wide_fwd(const long long* class_ids, const float* scor
   a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
   a.wmax = 0.f; a.hmax = 0.f; a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
   return launch_detect_wide(a, ws_words, (hipStream_t)stream);
+}
+
+// ---- many-class head: 1 <= num_classes <= 256 = 16 lanes x 16 registers (many_class.h) ------------------------------------------------
+// The same five roles as above -- decode, resolve, fused detect from pred, dense filter -- with a 16-lane group per anchor row instead
+// of one lane.  mc_anchor_score is the only scoring routine (decode, the detect scoring kernel and the re-decode of the <= K
+// candidates), so the fused detect equals the dense decode + filter bit for bit.  The detect is the wide two-launch structure:
+// detect_many_score_kernel -> keys, then detect_wide_select_kernel<true>, which differs from the <= 16-class form in the re-decode
+// and in the final placement only.  There is no one-launch narrow form past 16 classes.  The <= 16-class entry points keep their
+// limit and their answers; these are separate functions that take any class count up to 256.
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void decode_many_kernel(const float* __restrict__ pred, const float* __restrict__ anchors,
+                                                                 long long* __restrict__ class_ids, float* __restrict__ scores,
+                                                                 float* __restrict__ boxes, int B, int A, int C, float wmax, float hmax) {
+  const long long total = (long long)B * A;
+  const int j = threadIdx.x & (MC_LANES - 1);
+  for (long long i = (long long)blockIdx.x * MC_GROUPS + threadIdx.x / MC_LANES; i < total; i += (long long)gridDim.x * MC_GROUPS) {
+    const float* p = pred + i * (C + 5);
+    float s; int c;
+    mc_anchor_score<R>(p, C, j, s, c);
+    if (j == 0) {
+      const BoxF b = anchor_box(p + C + 1, anchors + 4 * (int)(i % A), wmax, hmax);
+      class_ids[i] = c; scores[i] = s;
+      *(f32x4*)(boxes + 4 * i) = (f32x4){b.x1, b.y1, b.x2, b.y2};
+    }
+  }
+}
+
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void resolve_many_kernel(const float* __restrict__ pred, const float* __restrict__ anchors,
+                                                                  float* __restrict__ probs, float* __restrict__ logp, float* __restrict__ scores,
+                                                                  float* __restrict__ deltas, float* __restrict__ boxes, int B, int A, int C,
+                                                                  float wmax, float hmax) {
+  const long long total = (long long)B * A;
+  const int j = threadIdx.x & (MC_LANES - 1);
+  for (long long i = (long long)blockIdx.x * MC_GROUPS + threadIdx.x / MC_LANES; i < total; i += (long long)gridDim.x * MC_GROUPS) {
+    const float* p = pred + i * (C + 5);
+    float l[R], e[R];
+    const float m = mc_load_logits<R>(p, C, j, l);
+    const float sum = mc_exp_sum<R>(C, j, m, l, e);
+    const float lse = logf(sum);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int c = j + MC_LANES * r;
+      if (c < C) {
+        probs[i * C + c] = e[r] / sum;                           // safe_softmax (modules.py:66-68)
+        if (logp) logp[i * C + c] = (l[r] - m) - lse;            // torch.log_softmax
+      }
+    }
+    if (j == 0) {
+      scores[i] = 1.f / (1.f + expf(-p[C]));
+      const float* d = p + C + 1;
+      *(f32x4*)(deltas + 4 * i) = (f32x4){d[0], d[1], d[2], d[3]};
+      const BoxF b = anchor_box(d, anchors + 4 * (int)(i % A), wmax, hmax);
+      *(f32x4*)(boxes + 4 * i) = (f32x4){b.x1, b.y1, b.x2, b.y2};
+    }
+  }
+}
+
+// keys of one 256-anchor slab of one image: a group takes the slab's anchors g, g + 16, ... (16 rounds); dense mode (in_score) and
+// the pad keys of the last quad go one per thread as in detect_wide_score_kernel
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void detect_many_score_kernel(DetArgs a) {
+  const int A = a.A, C = a.C, A4 = (A + 3) & ~3;
+  const int slabs = (A4 + MC_THREADS - 1) / MC_THREADS;
+  const int b = (int)blockIdx.x / slabs;
+  const int base = ((int)blockIdx.x - b * slabs) * MC_THREADS;
+  unsigned* __restrict__ keys = a.keys + (long long)b * A4;
+  if (a.in_score) {
+    const int i = base + (int)threadIdx.x;
+    if (i >= A4) return;
+    unsigned key = 0u;
+    if (i < A) {
+      const float s = a.in_score[(long long)b * A + i];
+      key = (s > a.score_thresh) ? __float_as_uint(s) : 0u;
+    }
+    keys[i] = key;
+    return;
+  }
+  const int j = threadIdx.x & (MC_LANES - 1), g = threadIdx.x / MC_LANES;
+  for (int it = 0; it < MC_THREADS / MC_GROUPS; ++it) {
+    const int i = base + it * MC_GROUPS + g;                   // (group-uniform)
+    if (i >= A4) break;
+    unsigned key = 0u;
+    if (i < A) {
+      // confidence first, as in detect_kernel: score <= conf, so conf <= threshold already decides key = 0, exactly
+      const float* p = a.pred + ((long long)b * A + i) * (C + 5);
+      const float conf = 1.f / (1.f + expf(-p[C]));
+      if (conf > a.score_thresh) {
+        float s; int c;
+        mc_anchor_score<R>(p, C, j, s, c);
+        key = (s > a.score_thresh) ? __float_as_uint(s) : 0u;
+      }
+    }
+    if (j == 0) keys[i] = key;
+  }
+}
+
+#define MC_CHECK_CLASSES(C) do { SQD_CHECK_ARG((C) >= 1); if ((C) > SQD_MANY_MAX_CLASSES) return SQD_ERR_UNSUPPORTED; } while (0)
+
+static inline unsigned mc_row_blocks(long long rows) {
+  const long long blocks = (rows + MC_GROUPS - 1) / MC_GROUPS;
+  return (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));   // grid-stride past 2^24 rows
+}
+
+// sqd_decode_fwd for 1 <= num_classes <= 256.  Status 1 for anything malformed, 2 for num_classes > 256.
+extern "C" int sqd_decode_many_fwd(const float* pred, const float* anchors, long long* class_ids, float* scores, float* boxes, int B, int A,
+                                   int num_classes, int input_h, int input_w, void* stream) {
+  SQD_CHECK_ARG(pred && anchors && class_ids && scores && boxes && B > 0 && A > 0);
+  MC_CHECK_CLASSES(num_classes);
+  SQD_CHECK_ARG(((uintptr_t)boxes & 15) == 0);
+  const unsigned blocks = mc_row_blocks((long long)B * A);
+#define CALL(R) hipLaunchKernelGGL(decode_many_kernel<R>, dim3(blocks), dim3(MC_THREADS), 0, (hipStream_t)stream, pred, anchors, class_ids, \
+                                   scores, boxes, B, A, num_classes, (float)(input_w - 1), (float)(input_h - 1))
+  MC_DISPATCH(num_classes, CALL);
+#undef CALL
+  return sqd_launch_status();
+}
+
+// sqd_resolve_fwd for 1 <= num_classes <= 256 (logp may be NULL)
+extern "C" int sqd_resolve_many_fwd(const float* pred, const float* anchors, float* probs, float* logp, float* scores, float* deltas,
+                                    float* boxes, int B, int A, int num_classes, int input_h, int input_w, void* stream) {
+  SQD_CHECK_ARG(pred && anchors && probs && scores && deltas && boxes && B > 0 && A > 0);
+  MC_CHECK_CLASSES(num_classes);
+  SQD_CHECK_ARG(((uintptr_t)deltas & 15) == 0 && ((uintptr_t)boxes & 15) == 0);
+  const unsigned blocks = mc_row_blocks((long long)B * A);
+#define CALL(R) hipLaunchKernelGGL(resolve_many_kernel<R>, dim3(blocks), dim3(MC_THREADS), 0, (hipStream_t)stream, pred, anchors, probs, logp, \
+                                   scores, deltas, boxes, B, A, num_classes, (float)(input_w - 1), (float)(input_h - 1))
+  MC_DISPATCH(num_classes, CALL);
+#undef CALL
+  return sqd_launch_status();
+}
+
+static int launch_detect_many(DetArgs a, int ws_words, hipStream_t stream) {
+  SQD_CHECK_ARG(a.B > 0 && a.A > 0 && a.C >= 1 && a.K >= 1);
+  if (a.K > DETW_MAX_K || a.A > DETW_MAX_A || a.C > SQD_MANY_MAX_CLASSES) return SQD_ERR_UNSUPPORTED;
+  const int words = sqd_detect_wide_workspace_words(a.B, a.A, a.K);
+  if (words < 0) return SQD_ERR_UNSUPPORTED;                  // (B x ceil4(A) past 2^31 - 1 words)
+  SQD_CHECK_ARG(a.keys && ws_words >= words && ((uintptr_t)a.keys & 15) == 0);
+  const int Kp = (a.K + 63) & ~63, A4 = (a.A + 3) & ~3;
+  const size_t lds = (size_t)Kp * (8 + 16 + 4) + DETW_LDS_FIXED + (size_t)Kp * (Kp / 64) * 8;   // the <= 16-class form's, unchanged
+  static SqdDevOnce lds_once;
+  if (lds > 48 * 1024 && sqd_max_lds_once(lds_once, (const void*)detect_wide_select_kernel<true>, 160 * 1024) != SQD_OK) return SQD_ERR_LAUNCH;
+  const int slabs = (A4 + MC_THREADS - 1) / MC_THREADS;
+#define CALL(R) hipLaunchKernelGGL(detect_many_score_kernel<R>, dim3((unsigned)(a.B * slabs)), dim3(MC_THREADS), 0, stream, a)
+  MC_DISPATCH(a.C, CALL);
+#undef CALL
+  hipLaunchKernelGGL(detect_wide_select_kernel<true>, dim3((unsigned)a.B), dim3(DETW_THREADS), lds, stream, a);
+  return sqd_launch_status();
+}
+
+// sqd_detect_wide_fwd for 1 <= num_classes <= 256: same arguments, same workspace (sqd_detect_wide_workspace_words), every
+// 1 <= keep_top_k <= 1024 and 1 <= A <= 2^20.  Status 2 for num_classes > 256, keep_top_k > 1024 or A > 2^20; 1 for anything malformed.
+extern "C" int sqd_detect_many_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                                   int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                   int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                                   int ws_words, void* stream) {
+  SQD_CHECK_ARG(pred && anchors && keys_ws && det_count && det_class && det_score && det_box && det_anchor);
+  SQD_CHECK_ARG(((uintptr_t)det_box & 15) == 0);
+  DetArgs a;
+  a.shifts = shifts;
+  a.pred = pred; a.anchors = anchors; a.scales = scales; a.in_class = nullptr; a.in_score = nullptr; a.in_box = nullptr; a.keys = keys_ws;
+  a.S = 1; a.per = 0;
+  a.det_count = det_count; a.det_class = det_class; a.det_score = det_score; a.det_box = det_box; a.det_anchor = det_anchor;
+  a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
+  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
+  a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
+  return launch_detect_many(a, ws_words, (hipStream_t)stream);
+}
+
+// sqd_filter_wide_fwd for class ids up to 255
+extern "C" int sqd_filter_many_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
+                                   long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                   int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words, void* stream) {
+  SQD_CHECK_ARG(class_ids && scores && boxes && keys_ws && det_count && det_class && det_score && det_box && det_anchor);
+  SQD_CHECK_ARG(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)det_box & 15) == 0);
+  DetArgs a;
+  a.shifts = nullptr;
+  a.pred = nullptr; a.anchors = nullptr; a.scales = nullptr; a.in_class = class_ids; a.in_score = scores; a.in_box = boxes; a.keys = keys_ws;
+  a.S = 1; a.per = 0;
+  a.det_count = det_count; a.det_class = det_class; a.det_score = det_score; a.det_box = det_box; a.det_anchor = det_anchor;
+  a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
+  a.wmax = 0.f; a.hmax = 0.f; a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
+  return launch_detect_many(a, ws_words, (hipStream_t)stream);
 }

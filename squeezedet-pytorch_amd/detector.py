@@ -37,7 +37,7 @@ class Detector(object):
         cfg = self.cfg
         pred = self.model.base(image)
         anchors = self.model.resolver.anchors_on(pred.device)
-        fused = ops.detect if ops.detect_path(cfg.keep_top_k, pred.shape[1]) == 'narrow' else ops.detect_wide
+        fused = ops.detect_fn(cfg.num_classes, cfg.keep_top_k, pred.shape[1])
         return fused(pred, anchors, cfg.input_size, cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh,
                      cfg.score_thresh, scales=scales, out=out, shifts=shifts)
 
@@ -222,7 +222,7 @@ class Detector(object):
         """One image's dense ``{'class_ids' [A], 'scores' [A], 'boxes' [A,4]}`` (GPU tensors) ->
         filtered dict of GPU tensors (plus ``anchor_idx``) or ``None``."""
         cfg = self.cfg
-        dense = ops.filter_dense if ops.detect_path(cfg.keep_top_k, det['scores'].shape[0]) == 'narrow' else ops.filter_dense_wide
+        dense = ops.filter_fn(cfg.num_classes, cfg.keep_top_k, det['scores'].shape[0])
         cnt, cls, sc, bx, idx = dense(det['class_ids'][None], det['scores'][None], det['boxes'][None],
                                       cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh, cfg.score_thresh)
         n = int(cnt[0].item())

@@ -400,7 +400,7 @@ class DetectStream:
         K = int(self.cfg.keep_top_k)
         if nb is None:
             with torch.cuda.stream(lane.comp):
-                out, flat = ops.det_buffers_packed(n, K, self.device, int(self.cfg.num_anchors))
+                out, flat = ops.det_buffers_packed(n, K, self.device, int(self.cfg.num_anchors), int(self.cfg.num_classes))
             secs, total = ops.det_packed_layout(n, K)
             nb = {'out': out, 'flat': flat, 'secs': secs, 'img': None, 'aux': None,
                   'res': [torch.empty(total, dtype=torch.uint8, pin_memory=True) for _ in range(2)],

@@ -49,6 +49,7 @@ class _ConvParams(nn.Module):
         self.weight = nn.Parameter(torch.empty(cout, cin, ksize, ksize))
         self.bias = nn.Parameter(torch.empty(cout))
         self._own_plan = None
+        self._own_pad = None               # run_nhwc's zero-padded stand-in (a 3x3 layer of a width that is no multiple of 4)
 
     def extra_repr(self):
         return f'{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}'
@@ -66,6 +67,11 @@ class _ConvParams(nn.Module):
     def run_nhwc(self, x, relu=False, out=None, out_coff=0):
         """NHWC in -> NHWC out (channel window ``out_coff`` of ``out`` when given)."""
         Bq, H, W, _ = x.shape
+        if self.kernel_size[0] == 3 and ops.convdet_pad_width(self.out_channels) != self.out_channels and out is None:
+            # a ConvDet of a width the convolution forms do not take, called on its own: zero-padded stand-in, then the pack launch
+            if self._own_pad is None or self._own_pad.weight.device != self.weight.device:
+                self._own_pad = _PaddedConvDet(self, ops.convdet_pad_width(self.out_channels))
+            return ops.convdet_pack(self._own_pad.sync().run_nhwc(x, relu=relu), self.out_channels)
         y = out if out is not None else torch.empty(Bq, H, W, self.out_channels, device=x.device, dtype=torch.float32)
         plan = self._plan(Bq * H * W)
         if isinstance(plan, ops.WinoPlan):
@@ -78,6 +84,35 @@ class _ConvParams(nn.Module):
                 raise RuntimeError('stem conv: expected an fp32 CUDA/HIP NCHW image')
             return ops.stem_conv_relu(x.detach(), self.weight, self.bias, relu=False).permute(0, 3, 1, 2)
         return self.run_nhwc(_nhwc_input(x, self.in_channels, 'conv')).permute(0, 3, 1, 2)
+
+
+class _PaddedConvDet:
+    """ConvDet as the executors launch it when its width N = anchors_per_grid * (num_classes + 5) is one the convolution forms do not
+    take (``ops.convdet_width``): zero-padded copies [Npad, Cin, 3, 3] / [Npad] of the canonical parameters, which keep the
+    reference's shapes.  ``sync`` copies the parameters into the first N rows when they changed (a contiguous prefix: two
+    device-to-device copies); the rows past N stay zero, so the padded output channels are zero and the padded gradient rows are never
+    read.  Not a module: nothing of it reaches ``state_dict`` / ``parameters``."""
+
+    def __init__(self, mod, Npad):
+        self.src, self.true_channels = mod, mod.out_channels
+        self.in_channels, self.out_channels = mod.in_channels, int(Npad)
+        self.kernel_size, self.stride, self.padding = mod.kernel_size, mod.stride, mod.padding
+        dev = mod.weight.device
+        self.weight = torch.zeros(self.out_channels, mod.in_channels, 3, 3, device=dev, dtype=torch.float32)
+        self.bias = torch.zeros(self.out_channels, device=dev, dtype=torch.float32)
+        self._ver = None
+        self._own_plan = None                 # (_ConvParams.run_nhwc / _plan run on this object for a stand-alone call)
+
+    _plan, run_nhwc = _ConvParams._plan, _ConvParams.run_nhwc      # (a stand-alone call launches it like any 3x3 layer)
+
+    def sync(self):
+        m, N = self.src, self.true_channels
+        ver = (m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr())
+        if ver != self._ver:
+            self.weight[:N].copy_(m.weight.detach())
+            self.bias[:N].copy_(m.bias.detach())
+            self._ver = ver
+        return self
 
 
 class _Marker(nn.Module):
@@ -137,6 +172,8 @@ class SqueezeDetBase(nn.Module):
         self.dropout_prob = float(cfg.dropout_prob)
         self.dropout = nn.Dropout(cfg.dropout_prob, inplace=True) if cfg.dropout_prob > 0 else None
         self.convdet = _ConvParams(convdet_in_channels(cfg.arch), cfg.anchors_per_grid * (cfg.num_classes + 5), 3, padding=1)
+        self._convdet_pad = None                  # _PaddedConvDet when the width is padded (convdet_exec)
+        self._convdet_slab = None                 # its weight-gradient slab workspace
         self._plans = {}
         self._fused_plans = {}
         self._wino_plans = {}
@@ -169,6 +206,26 @@ class SqueezeDetBase(nn.Module):
             if isinstance(m, _ConvParams):
                 nn.init.normal_(m.weight, mean=0.0, std=0.002 if m is self.convdet else 0.005)
                 nn.init.constant_(m.bias, 0)
+
+    def convdet_exec(self):
+        """The ConvDet the executors launch: the module itself where the convolution forms take its width (every width that ran
+        before: exactly the launches of before), else its zero-padded stand-in, brought up to date with the parameters."""
+        cd = self.convdet
+        N, Npad = cd.out_channels, ops.convdet_pad_width(cd.out_channels)
+        if Npad == N:
+            return cd
+        pad = self._convdet_pad
+        if pad is None or pad.weight.device != cd.weight.device or pad.out_channels != Npad:
+            pad = self._convdet_pad = _PaddedConvDet(cd, Npad)
+            self._convdet_slab = None
+        return pad.sync()
+
+    def convdet_slab(self, numel):
+        """Slab workspace of the padded ConvDet's weight gradient (allocated once per size: pointer-stable)."""
+        ws = self._convdet_slab
+        if ws is None or ws.numel() != numel or ws.device != self.convdet.weight.device:
+            ws = self._convdet_slab = torch.empty(numel, device=self.convdet.weight.device, dtype=torch.float32)
+        return ws
 
     # ---- packed-weight cache ----
     def plan(self, name, mod, cfg_id, direction='fwd'):
@@ -318,7 +375,7 @@ class SqueezeDetBase(nn.Module):
         self._plans.clear(); self._fused_plans.clear(); self._wino_plans.clear()
         for m in self.modules():
             if isinstance(m, _ConvParams):
-                m._own_plan = None
+                m._own_plan = m._own_pad = None
 
     def refresh_plans(self):
         """Re-pack every cached plan whose parameter changed since it was packed (after an optimizer step that
@@ -327,7 +384,7 @@ class SqueezeDetBase(nn.Module):
         for key, (ver, plan) in self._plans.items():
             name, _cfg, direction = key
             name = name.split('@')[0]                  # 'N.squeeze@pool': the same module packed for the fused pool+squeeze
-            mod = self.convdet if name == 'convdet' else getattr(self.features[int(name.split('.')[0])], name.split('.')[1]) \
+            mod = self.convdet_exec() if name == 'convdet' else getattr(self.features[int(name.split('.')[0])], name.split('.')[1]) \
                 if '.' in name else self.features[int(name)]
             now = (mod.weight._version, mod.weight.data_ptr(), mod.bias._version, mod.bias.data_ptr())
             if now != ver:
@@ -350,7 +407,7 @@ class SqueezeDetBase(nn.Module):
         stale, dg, keys = [], [], []
         for key, (ver, plan) in self._wino_plans.items():
             name, _cfg, direction = key
-            mod = self.convdet if name == 'convdet' else getattr(self.features[int(name.split('.')[0])], name.split('.')[1])
+            mod = self.convdet_exec() if name == 'convdet' else getattr(self.features[int(name.split('.')[0])], name.split('.')[1])
             now = (mod.weight._version, mod.weight.data_ptr(), mod.bias._version, mod.bias.data_ptr())
             if now != ver:
                 stale.append((plan, mod.weight)); dg.append(direction != 'fwd'); keys.append((key, now, mod))
@@ -400,12 +457,14 @@ class PredictionResolver(nn.Module):
         """Same five outputs as the reference (src/model/squeezedet.py:109-120): (pred_class_probs [B,A,C],
         pred_log_class_probs | None, pred_scores [B,A,1], pred_deltas [B,A,4], pred_boxes [B,A,4]) -- inference only
         (not differentiable; the training path differentiates through ``Loss``, whose kernel has the analytic backward)."""
-        return ops.resolve(pred.detach(), self.anchors_on(pred.device), self.input_size, self.num_classes, self.log_softmax)
+        resolve = ops.resolve if ops.head_path(self.num_classes) == 'narrow' else ops.resolve_many
+        return resolve(pred.detach(), self.anchors_on(pred.device), self.input_size, self.num_classes, self.log_softmax)
 
     def decode(self, pred):
         """Fused resolver + ``probs *= score; argmax; max`` of ``SqueezeDet.forward`` (:199-202):
         (class_ids int64 [B,A], scores [B,A], boxes [B,A,4])."""
-        return ops.decode(pred, self.anchors_on(pred.device), self.input_size, self.num_classes)
+        decode = ops.decode if ops.head_path(self.num_classes) == 'narrow' else ops.decode_many
+        return decode(pred, self.anchors_on(pred.device), self.input_size, self.num_classes)
 
 
 class SqueezeDet(nn.Module):

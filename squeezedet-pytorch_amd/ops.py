@@ -539,8 +539,97 @@ def maxpool_bwd(dy, argmax, in_hw, out=None, relu_src=None):
     return out
 
 
+HEAD_NARROW_MAX_CLASSES = 16   # the one-lane-per-row kernels: float l[16] per lane
+HEAD_MANY_MAX_CLASSES = 256    # the lane-group kernels: 16 lanes x 16 registers per anchor row
+
+
+def head_path(num_classes):
+    """Which head kernels serve ``num_classes``: 'narrow' (<= 16: ``decode`` / ``resolve`` / ``detect`` / ``detect_wide`` / ``loss_*``,
+    the benchmarked kernels) or 'many' (17 .. 256: ``decode_many`` / ``resolve_many`` / ``detect_many`` / ``filter_dense_many`` /
+    ``loss_*_many``).  ValueError outside 1 .. 256."""
+    C = int(num_classes)
+    if C < 1 or C > HEAD_MANY_MAX_CLASSES:
+        raise ValueError(f'num_classes must be in 1 .. {HEAD_MANY_MAX_CLASSES} (16 lanes x 16 registers per anchor row), got {C}')
+    return 'narrow' if C <= HEAD_NARROW_MAX_CLASSES else 'many'
+
+
+def convdet_width(anchors_per_grid, num_classes):
+    """(N, Npad) of ConvDet: N = anchors_per_grid * (num_classes + 5) output channels; Npad = the width the executors run it at.
+    Npad == N (not padded) where the convolution forms take N as it is (N % 4 == 0 -- every width that ran before, 72 and 108
+    among them); otherwise the next multiple of 64: the Winograd data gradient reads the padded gradient as its C (a multiple of
+    8), and the Winograd weight gradient takes N <= 80 or N % 64 == 0 (``tiles.wgrad_uses_wino``)."""
+    N = int(anchors_per_grid) * (int(num_classes) + 5)
+    return N, convdet_pad_width(N)
+
+
+def convdet_pad_width(N):
+    """The width a ConvDet of N output channels runs at (``convdet_width``)."""
+    N = int(N)
+    return N if N % 4 == 0 else -(-N // 64) * 64
+
+
+def convdet_padded(anchors_per_grid, num_classes):
+    """Whether ConvDet runs at a padded width (``convdet_width``)."""
+    N, Npad = convdet_width(anchors_per_grid, num_classes)
+    return Npad != N
+
+
+def convdet_pack(y_pad, N, out=None):
+    """[B,H,W,Npad] -> contiguous [B,H,W,N] (the first N channels): ConvDet's padded scratch to the reference's pred layout."""
+    _check_nhwc(y_pad, 'y_pad')
+    B, H, W, Npad = y_pad.shape
+    if not 1 <= N <= Npad:
+        raise ValueError(f'convdet_pack: N = {N} outside 1 .. {Npad}')
+    if out is None:
+        out = torch.empty(B, H, W, N, device=y_pad.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, H, W, N) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y_pad.device:
+        raise ValueError('convdet_pack: bad out tensor')
+    br = _Bracket('convdet_pack', f'pack N{N} <- {Npad} {H}x{W}', 0.0, 8.0 * B * H * W * N) if timing._timer is not None else None
+    nat.check(nat.lib().sqd_channel_pack_fwd(nat.ptr(y_pad), nat.ptr(out), B * H * W, int(N), Npad, nat.stream_handle(y_pad.device)),
+              'sqd_channel_pack_fwd')
+    if br is not None:
+        br.done()
+    return out
+
+
+def convdet_unpack(dy, Npad):
+    """Contiguous [B,H,W,N] -> [B,H,W,Npad], zero past N: dpred as the padded ConvDet's gradient launches read it."""
+    _check_nhwc(dy, 'dy')
+    B, H, W, N = dy.shape
+    if Npad < N:
+        raise ValueError(f'convdet_unpack: Npad = {Npad} < N = {N}')
+    out = torch.empty(B, H, W, Npad, device=dy.device, dtype=torch.float32)
+    br = _Bracket('convdet_unpack', f'unpack N{N} -> {Npad} {H}x{W}', 0.0, 4.0 * B * H * W * (N + Npad)) if timing._timer is not None else None
+    nat.check(nat.lib().sqd_channel_unpack_fwd(nat.ptr(dy), nat.ptr(out), B * H * W, N, int(Npad), nat.stream_handle(dy.device)),
+              'sqd_channel_unpack_fwd')
+    if br is not None:
+        br.done()
+    return out
+
+
+def wgrad_reduce_rows(slab, S, N, Npad, C, taps, dw, db, scale=1.0):
+    """The S slabs of an Npad-wide weight gradient (``conv_wgrad(..., slab=)``) reduced over the first N rows into ``dw``
+    [N,C,k,k] / ``db`` [N] (contiguous views of the flat gradient buffer), times ``scale``."""
+    k = 3 if taps == 9 else 1
+    stride = Npad * taps * C + Npad
+    if slab.numel() != S * stride or not slab.is_contiguous() or slab.dtype != torch.float32:
+        raise ValueError('wgrad_reduce_rows: slab workspace does not match the layer')
+    if tuple(dw.shape) != (N, C, k, k) or tuple(db.shape) != (N,) or not dw.is_contiguous() or not db.is_contiguous() \
+            or dw.dtype != torch.float32 or db.dtype != torch.float32 or N > Npad:
+        raise ValueError('wgrad_reduce_rows: dw / db must be contiguous fp32 [N,C,k,k] / [N] with N <= Npad')
+    br = _Bracket('wgrad_reduce_rows', f'N{N} of {Npad} C{C}', 0.0, 4.0 * (S + 1) * (N * taps * C + N)) if timing._timer is not None else None
+    nat.check(nat.lib().sqd_wgrad_reduce_rows(nat.ptr(slab), nat.ptr(dw), nat.ptr(db), int(S), int(N), int(Npad), int(C), int(taps),
+                                              float(scale), nat.stream_handle(slab.device)), 'sqd_wgrad_reduce_rows')
+    if br is not None:
+        br.done()
+
+
 def decode(pred, anchors, input_size, num_classes):
     """pred [B,A,C+5], anchors [A,4] fp32 -> class_ids int64 [B,A], scores [B,A], boxes [B,A,4]."""
+    return _decode('sqd_decode_fwd', pred, anchors, input_size, num_classes)
+
+
+def _decode(_entry, pred, anchors, input_size, num_classes):
     if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
         raise ValueError(f'decode: bad pred {tuple(pred.shape)}')
     pred = pred.contiguous()
@@ -550,15 +639,25 @@ def decode(pred, anchors, input_size, num_classes):
     ids = torch.empty(B, A, device=pred.device, dtype=torch.int64)
     scores = torch.empty(B, A, device=pred.device, dtype=torch.float32)
     boxes = torch.empty(B, A, 4, device=pred.device, dtype=torch.float32)
-    rc = nat.lib().sqd_decode_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(ids), nat.ptr(scores), nat.ptr(boxes),
-                                  B, A, num_classes, int(input_size[0]), int(input_size[1]), nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_decode_fwd')
+    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(ids), nat.ptr(scores), nat.ptr(boxes),
+                                    B, A, num_classes, int(input_size[0]), int(input_size[1]), nat.stream_handle(pred.device))
+    nat.check(rc, _entry)
     return ids, scores, boxes
+
+
+def decode_many(pred, anchors, input_size, num_classes):
+    """``decode`` for 1 <= num_classes <= 256 (a 16-lane group per anchor row; class = the lowest index attaining the score)."""
+    head_path(num_classes)
+    return _decode('sqd_decode_many_fwd', pred, anchors, input_size, num_classes)
 
 
 def resolve(pred, anchors, input_size, num_classes, log_softmax=False):
     """The reference's PredictionResolver outputs: (probs [B,A,C], log_probs [B,A,C] | None, scores [B,A,1],
     deltas [B,A,4], boxes [B,A,4])."""
+    return _resolve('sqd_resolve_fwd', pred, anchors, input_size, num_classes, log_softmax)
+
+
+def _resolve(_entry, pred, anchors, input_size, num_classes, log_softmax=False):
     if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
         raise ValueError(f'resolve: bad pred {tuple(pred.shape)}')
     pred = pred.contiguous()
@@ -571,20 +670,27 @@ def resolve(pred, anchors, input_size, num_classes, log_softmax=False):
     scores = torch.empty(B, A, 1, device=dev, dtype=torch.float32)
     deltas = torch.empty(B, A, 4, device=dev, dtype=torch.float32)
     boxes = torch.empty(B, A, 4, device=dev, dtype=torch.float32)
-    rc = nat.lib().sqd_resolve_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(probs), nat.ptr(logp), nat.ptr(scores),
-                                   nat.ptr(deltas), nat.ptr(boxes), B, A, num_classes, int(input_size[0]), int(input_size[1]),
-                                   nat.stream_handle(dev))
-    nat.check(rc, 'sqd_resolve_fwd')
+    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(probs), nat.ptr(logp), nat.ptr(scores),
+                                    nat.ptr(deltas), nat.ptr(boxes), B, A, num_classes, int(input_size[0]), int(input_size[1]),
+                                    nat.stream_handle(dev))
+    nat.check(rc, _entry)
     return probs, logp, scores, deltas, boxes
 
 
-def _det_buffers(B, K, device, A=None):
-    """(count, class_ids, scores, boxes, anchor_idx[, keys workspace]) for the fused detection kernels."""
+def resolve_many(pred, anchors, input_size, num_classes, log_softmax=False):
+    """``resolve`` for 1 <= num_classes <= 256."""
+    head_path(num_classes)
+    return _resolve('sqd_resolve_many_fwd', pred, anchors, input_size, num_classes, log_softmax)
+
+
+def _det_buffers(B, K, device, A=None, num_classes=None):
+    """(count, class_ids, scores, boxes, anchor_idx[, keys workspace]) for the fused detection kernels (``num_classes``: sizes the
+    workspace for the many-class detect past 16 classes)."""
     bufs = (torch.zeros(B, device=device, dtype=torch.int32), torch.zeros(B, K, device=device, dtype=torch.int64),
             torch.zeros(B, K, device=device, dtype=torch.float32), torch.zeros(B, K, 4, device=device, dtype=torch.float32),
             torch.zeros(B, K, device=device, dtype=torch.int32))
     if A is not None:
-        bufs = bufs + (_det_workspace(B, A, device, K),)
+        bufs = bufs + (_det_workspace(B, A, device, K, num_classes),)
     return bufs
 
 
@@ -601,14 +707,14 @@ def det_packed_layout(B, K):
     return secs, -(-off // 16) * 16
 
 
-def det_buffers_packed(B, K, device, A=None):
+def det_buffers_packed(B, K, device, A=None, num_classes=None):
     """The same five result tensors as views of ONE allocation (16-byte aligned sections), so that a whole batch's compact
     detections leave the GPU with a single device-to-host copy.  -> (bufs as ``_det_buffers``, flat uint8 tensor)."""
     secs, total = det_packed_layout(B, K)
     flat = torch.zeros(total, device=device, dtype=torch.uint8)
     bufs = tuple(flat[o:o + n * torch.empty(0, dtype=dt).element_size()].view(dt).view(shp) for o, n, dt, shp in secs)
     if A is not None:
-        bufs = bufs + (_det_workspace(B, A, device, K),)
+        bufs = bufs + (_det_workspace(B, A, device, K, num_classes),)
     return bufs, flat
 
 
@@ -646,12 +752,13 @@ def det_workspace_words_wide(B, A, K):
     return n
 
 
-def _det_workspace(B, A, device, K=DET_NARROW_MAX_K):
+def _det_workspace(B, A, device, K=DET_NARROW_MAX_K, num_classes=None):
     """Workspace of the fused detect launch (``keys_ws``).  Narrow path: the keys the eight scoring workgroups of an image hand to
     its last arriver + one arrival counter per image; zeroed once, every launch returns the counters to zero.  Parameters only the
     wide path takes (``detect_path``): its key workspace.  (Parameters neither takes get the narrow size: that launch refuses them.)"""
     K, A = int(K), int(A)
-    if (K > DET_NARROW_MAX_K or A > DET_NARROW_MAX_A) and 1 <= K <= DET_WIDE_MAX_K and 1 <= A <= DET_WIDE_MAX_A:
+    many = num_classes is not None and int(num_classes) > HEAD_NARROW_MAX_CLASSES      # (the many-class detect is always two launches)
+    if (many or K > DET_NARROW_MAX_K or A > DET_NARROW_MAX_A) and 1 <= K <= DET_WIDE_MAX_K and 1 <= A <= DET_WIDE_MAX_A:
         return torch.zeros(det_workspace_words_wide(B, A, K), device=device, dtype=torch.int32)
     return torch.zeros(det_workspace_words(B, A), device=device, dtype=torch.int32)
 
@@ -748,6 +855,10 @@ def detect_wide(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thres
     """``detect`` for any 1 <= ``keep_top_k`` <= 1024 and up to 2^20 anchors (two launches: score into a workspace, then one
     workgroup per image selects, suppresses and compacts); same arguments, same results bit for bit where both run.  ``out``: the
     five result tensors and optionally a workspace of ``det_workspace_words_wide(B, A, keep_top_k)`` int32 (any contents)."""
+    return _detect_wide('sqd_detect_wide_fwd', pred, anchors, input_size, num_classes, keep_top_k, nms_thresh, score_thresh, scales, out, shifts)
+
+
+def _detect_wide(_entry, pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None):
     if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
         raise ValueError(f'detect_wide: bad pred {tuple(pred.shape)}')
     _check_score_thresh('detect_wide', score_thresh)
@@ -766,19 +877,30 @@ def detect_wide(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thres
     bufs = tuple(out) if out is not None else _det_buffers(B, K, pred.device)
     keys = _wide_workspace('detect_wide', bufs, B, A, K, pred.device)
     cnt, cls, sc, bx, idx = bufs[:5]
-    br = _Bracket('detect', f'detect_wide A{A} K{K}', 0.0, 4.0 * B * A * (num_classes + 5)) if timing._timer is not None else None
-    rc = nat.lib().sqd_detect_wide_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
-                                       nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
-                                       int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
-                                       keys.numel(), nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_detect_wide_fwd')
+    br = _Bracket('detect', f'{_entry[4:-4]} A{A} K{K}', 0.0, 4.0 * B * A * (num_classes + 5)) if timing._timer is not None else None
+    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
+                                    nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                    int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
+                                    keys.numel(), nat.stream_handle(pred.device))
+    nat.check(rc, _entry)
     if br is not None:
         br.done()
     return bufs[:5]
 
 
+def detect_many(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None):
+    """``detect_wide`` for 1 <= num_classes <= 256: every 1 <= ``keep_top_k`` <= 1024 and up to 2^20 anchors, same arguments, same
+    workspace size.  Equals ``Detector.filter`` on ``decode_many``'s output bit for bit."""
+    head_path(num_classes)
+    return _detect_wide('sqd_detect_many_fwd', pred, anchors, input_size, num_classes, keep_top_k, nms_thresh, score_thresh, scales, out, shifts)
+
+
 def filter_dense_wide(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3):
     """``filter_dense`` for any 1 <= ``keep_top_k`` <= 1024 and up to 2^20 anchors."""
+    return _filter_dense_wide('sqd_filter_wide_fwd', class_ids, scores, boxes, num_classes, keep_top_k, nms_thresh, score_thresh)
+
+
+def _filter_dense_wide(_entry, class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3):
     if scores.dim() != 2 or class_ids.shape != scores.shape or tuple(boxes.shape) != tuple(scores.shape) + (4,):
         raise ValueError('filter_wide: shape mismatch')
     if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda \
@@ -791,11 +913,34 @@ def filter_dense_wide(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_
     bufs = _det_buffers(B, K, scores.device)
     keys = _wide_workspace('filter_wide', bufs, B, A, K, scores.device)
     cnt, cls, sc, bx, idx = bufs
-    rc = nat.lib().sqd_filter_wide_fwd(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
-                                       nat.ptr(keys), nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
-                                       K, float(nms_thresh), float(score_thresh), keys.numel(), nat.stream_handle(scores.device))
-    nat.check(rc, 'sqd_filter_wide_fwd')
+    rc = getattr(nat.lib(), _entry)(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
+                                    nat.ptr(keys), nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                    K, float(nms_thresh), float(score_thresh), keys.numel(), nat.stream_handle(scores.device))
+    nat.check(rc, _entry)
     return bufs
+
+
+def filter_dense_many(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3):
+    """``filter_dense_wide`` for class ids up to 255 (1 <= num_classes <= 256)."""
+    head_path(num_classes)
+    return _filter_dense_wide('sqd_filter_many_fwd', class_ids, scores, boxes, num_classes, keep_top_k, nms_thresh, score_thresh)
+
+
+def detect_fn(num_classes, keep_top_k, A):
+    """The fused detect that serves (num_classes, keep_top_k, A): ``detect`` / ``detect_wide`` up to 16 classes (``detect_path``),
+    ``detect_many`` past them."""
+    if head_path(num_classes) == 'many':
+        detect_path(keep_top_k, A)
+        return detect_many
+    return detect if detect_path(keep_top_k, A) == 'narrow' else detect_wide
+
+
+def filter_fn(num_classes, keep_top_k, A):
+    """The dense filter that serves (num_classes, keep_top_k, A), as ``detect_fn``."""
+    if head_path(num_classes) == 'many':
+        detect_path(keep_top_k, A)
+        return filter_dense_many
+    return filter_dense if detect_path(keep_top_k, A) == 'narrow' else filter_dense_wide
 
 
 def conv_wgrad(dy, dy_coff, N, x, x_coff, C, taps, slab=None, wino=None):
@@ -1011,16 +1156,20 @@ def _check_loss_args(pred, gt, anchors, num_classes):
 
 def loss_fwd(pred, gt, anchors, input_size, num_classes, weights):
     """-> (losses [4,B] = class, score, bbox, total; nobj [B])."""
+    return _loss_fwd('sqd_loss_fwd', pred, gt, anchors, input_size, num_classes, weights)
+
+
+def _loss_fwd(_entry, pred, gt, anchors, input_size, num_classes, weights):
     B, A = _check_loss_args(pred, gt, anchors, num_classes)
     pred, gt, anchors = pred.contiguous(), gt.contiguous(), anchors.contiguous()
     ws = torch.empty(B * 16 * 5, device=pred.device, dtype=torch.float32)
     losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
     nobj = torch.empty(B, device=pred.device, dtype=torch.float32)
     br = _Bracket('loss_fwd', f'loss A{A}', 0.0, 4.0 * B * A * (2 * num_classes + 14)) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_fwd(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj), B, A,
+    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj), B, A,
                                 num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
                                 nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_fwd')
+    nat.check(rc, _entry)
     if br is not None:
         br.done()
     return losses, nobj
@@ -1028,6 +1177,10 @@ def loss_fwd(pred, gt, anchors, input_size, num_classes, weights):
 
 def loss_mean_fwd(pred, gt, anchors, input_size, num_classes, weights):
     """-> (losses [4,B], nobj [B], mean4 [4] = batch means of class / score / bbox / total): ``loss.mean()`` inside the loss launches."""
+    return _loss_mean_fwd('sqd_loss_mean_fwd', pred, gt, anchors, input_size, num_classes, weights)
+
+
+def _loss_mean_fwd(_entry, pred, gt, anchors, input_size, num_classes, weights):
     B, A = _check_loss_args(pred, gt, anchors, num_classes)
     pred, gt, anchors = pred.contiguous(), gt.contiguous(), anchors.contiguous()
     ws = torch.empty(B * 16 * 5, device=pred.device, dtype=torch.float32)
@@ -1035,10 +1188,10 @@ def loss_mean_fwd(pred, gt, anchors, input_size, num_classes, weights):
     nobj = torch.empty(B, device=pred.device, dtype=torch.float32)
     mean4 = torch.empty(4, device=pred.device, dtype=torch.float32)
     br = _Bracket('loss_fwd', f'loss A{A}', 0.0, 4.0 * B * A * (2 * num_classes + 14)) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_mean_fwd(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj), nat.ptr(mean4),
+    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj), nat.ptr(mean4),
                                      B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
                                      nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_mean_fwd')
+    nat.check(rc, _entry)
     if br is not None:
         br.done()
     return losses, nobj, mean4
@@ -1046,16 +1199,20 @@ def loss_mean_fwd(pred, gt, anchors, input_size, num_classes, weights):
 
 def loss_mean_bwd(pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
     """gmean: device scalar (gradient arriving at mean(total)) -> dpred [B,A,C+5]."""
+    return _loss_mean_bwd('sqd_loss_mean_bwd', pred, gt, anchors, nobj, gmean, input_size, num_classes, weights)
+
+
+def _loss_mean_bwd(_entry, pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
     B, A = _check_loss_args(pred, gt, anchors, num_classes)
     if gmean.numel() != 1 or gmean.dtype != torch.float32 or gmean.device != pred.device:
         raise ValueError('loss_mean_bwd: gmean must be one fp32 value on the same device')
     pred, gt, anchors = pred.contiguous(), gt.contiguous(), anchors.contiguous()
     dpred = torch.empty_like(pred)
     br = _Bracket('loss_bwd', f'lossbwd A{A}', 0.0, 4.0 * B * A * (3 * num_classes + 19)) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_mean_bwd(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(gmean.contiguous()), nat.ptr(dpred), B, A,
+    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(gmean.contiguous()), nat.ptr(dpred), B, A,
                                      num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
                                      nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_mean_bwd')
+    nat.check(rc, _entry)
     if br is not None:
         br.done()
     return dpred
@@ -1063,19 +1220,54 @@ def loss_mean_bwd(pred, gt, anchors, nobj, gmean, input_size, num_classes, weigh
 
 def loss_bwd(pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
     """coef [3,B] -> dpred [B,A,C+5]."""
+    return _loss_bwd('sqd_loss_bwd', pred, gt, anchors, nobj, coef, input_size, num_classes, weights)
+
+
+def _loss_bwd(_entry, pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
     B, A = _check_loss_args(pred, gt, anchors, num_classes)
     if tuple(coef.shape) != (3, B) or tuple(nobj.shape) != (B,):
         raise ValueError('loss_bwd: coef must be [3,B], nobj [B]')
     pred, gt, anchors, coef = pred.contiguous(), gt.contiguous(), anchors.contiguous(), coef.contiguous().float()
     dpred = torch.empty_like(pred)
     br = _Bracket('loss_bwd', f'lossbwd A{A}', 0.0, 4.0 * B * A * (3 * num_classes + 19)) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_bwd(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(coef), nat.ptr(dpred), B, A,
+    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(coef), nat.ptr(dpred), B, A,
                                 num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
                                 nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_bwd')
+    nat.check(rc, _entry)
     if br is not None:
         br.done()
     return dpred
+
+
+def loss_fwd_many(pred, gt, anchors, input_size, num_classes, weights):
+    """``loss_fwd`` for 1 <= num_classes <= 256 (a 16-lane group per anchor row)."""
+    head_path(num_classes)
+    return _loss_fwd('sqd_loss_many_fwd', pred, gt, anchors, input_size, num_classes, weights)
+
+
+def loss_mean_fwd_many(pred, gt, anchors, input_size, num_classes, weights):
+    """``loss_mean_fwd`` for 1 <= num_classes <= 256; the per-image values equal ``loss_fwd_many``'s bit for bit."""
+    head_path(num_classes)
+    return _loss_mean_fwd('sqd_loss_many_mean_fwd', pred, gt, anchors, input_size, num_classes, weights)
+
+
+def loss_mean_bwd_many(pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
+    """``loss_mean_bwd`` for 1 <= num_classes <= 256."""
+    head_path(num_classes)
+    return _loss_mean_bwd('sqd_loss_many_mean_bwd', pred, gt, anchors, nobj, gmean, input_size, num_classes, weights)
+
+
+def loss_bwd_many(pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
+    """``loss_bwd`` for 1 <= num_classes <= 256."""
+    head_path(num_classes)
+    return _loss_bwd('sqd_loss_many_bwd', pred, gt, anchors, nobj, coef, input_size, num_classes, weights)
+
+
+def loss_fns(num_classes):
+    """(loss_fwd, loss_mean_fwd, loss_bwd, loss_mean_bwd) that serve ``num_classes`` (``head_path``)."""
+    if head_path(num_classes) == 'many':
+        return loss_fwd_many, loss_mean_fwd_many, loss_bwd_many, loss_mean_bwd_many
+    return loss_fwd, loss_mean_fwd, loss_bwd, loss_mean_bwd
 
 
 def encode_gt(boxes, class_ids, box_offsets, anchors64, num_classes, dense=True, parallel=True):

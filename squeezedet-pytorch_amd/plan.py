@@ -217,15 +217,22 @@ def _render_forward(steps, batch, input_size, use_winograd):
 
 def inference_launch_plan(arch='squeezedet', batch=20, input_size=(384, 1248), anchors_per_grid=9, num_classes=3,
                           use_winograd=True, fuse_expand=True, fuse_fire_bridge=True, fuse_expand_wino=True,
-                          fuse_pool_squeeze=False, fuse_stem_squeeze=True):
+                          fuse_pool_squeeze=False, fuse_stem_squeeze=True, keep_top_k=64):
     """-> list of (kernel name as bench.py / KernelTimer prints it, shape tag), in launch order.  The six switches are
-    ``SqueezeDetBase``'s attributes of the same names, one to one."""
+    ``SqueezeDetBase``'s attributes of the same names, one to one; ``keep_top_k`` = ``cfg.keep_top_k`` (with the class and anchor
+    counts it decides which fused detect runs: ``ops.detect_fn``)."""
     flags = Flags(use_winograd, fuse_expand, fuse_expand_wino, fuse_fire_bridge, fuse_pool_squeeze, fuse_stem_squeeze, True, True)
     steps = forward_schedule(arch, batch, input_size, flags)
     plan = _render_forward(steps, batch, input_size, use_winograd)
     H, W = steps[-1].H, steps[-1].W
-    plan.append(_conv3x3(batch, H, W, convdet_in_channels(arch), anchors_per_grid * (num_classes + 5), use_winograd))
-    plan.append(('detect', f'detect A{H * W * anchors_per_grid}'))
+    ncd, npad = ops.convdet_width(anchors_per_grid, num_classes)
+    # (a width the convolution forms do not take runs zero-padded into a scratch and is packed into the contiguous pred)
+    plan.append(_conv3x3(batch, H, W, convdet_in_channels(arch), npad, use_winograd))
+    if npad != ncd:
+        plan.append(('convdet_pack', f'pack N{ncd} <- {npad} {H}x{W}'))
+    A = H * W * anchors_per_grid
+    fused = ops.detect_fn(num_classes, keep_top_k, A)
+    plan.append(('detect', f'detect A{A}' if fused is ops.detect else f'{fused.__name__} A{A} K{int(keep_top_k)}'))
     return plan
 
 
@@ -252,19 +259,26 @@ def training_launch_plan(arch='squeezedet', batch=20, input_size=(384, 1248), an
     steps = forward_schedule(arch, batch, input_size, flags, True, 'stream' if dropout else None)
     plan = _render_forward(steps, batch, input_size, use_winograd)
     H, W = steps[-1].H, steps[-1].W
-    ncd = anchors_per_grid * (num_classes + 5)
+    ntrue, ncd = ops.convdet_width(anchors_per_grid, num_classes)      # ncd: the width ConvDet's launches run at
+    padded = ncd != ntrue
     ccd = convdet_in_channels(arch)
     plan.append(_conv3x3(batch, H, W, ccd, ncd, use_winograd))
+    if padded:
+        plan.append(('convdet_pack', f'pack N{ntrue} <- {ncd} {H}x{W}'))
     A = H * W * anchors_per_grid
     plan.append(('loss_fwd', f'loss A{A}'))
     plan.append(('loss_bwd', f'lossbwd A{A}'))
     # ---- backward ----
     wgrad, convdet_sk = backward_schedule(arch, [(batch, st.H, st.W) for st in steps if type(st) is FireStep], ncd, fuse_squeeze_bwd,
                                           group_wgrad, steps[-1].fused_rng)
+    if padded:
+        plan.append(('convdet_unpack', f'unpack N{ntrue} -> {ncd} {H}x{W}'))
     plan.append(_wgrad(batch, H, W, ncd, ccd, 9))
+    if padded:                                         # its slabs are reduced on their own, over the first ntrue rows
+        plan.append(('wgrad_reduce_rows', f'N{ntrue} of {ncd} C{ccd}'))
     # ConvDet data gradient (balanced kernel: mask = its own input, constant scale)
     plan.append(('conv_wino_sk', f'9tap C{ncd} N{ccd} {H}x{W}') if convdet_sk else _conv3x3(batch, H, W, ncd, ccd, use_winograd))
-    rows_total, rows_done = 1, 0                       # slab-reduction records: ConvDet, then 3 per Fire in backward order
+    rows_total, rows_done = (0 if padded else 1), 0    # slab-reduction records: ConvDet (unless padded), then 3 per Fire in backward order
     pending = {}                                       # group id -> shape tags of the members seen so far (issued with the last one)
     ks = steps[0].ks
     for st in reversed(steps[1:-1]):
