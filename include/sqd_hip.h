@@ -428,6 +428,34 @@ int sqd_loss_many_bwd(const float* pred, const float* gt, const float* anchors, 
 int sqd_loss_many_mean_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* gmean,
                            float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos,
                            float w_neg, float w_bbox, void* stream);
+/* The four loss launches on a SPARSE ground truth, 1 <= num_classes <= 256: the positives as a list instead of the dense
+ * gt [B][A][C+9].  anchor_idx [total] int32 (the anchor a box was assigned), boxes [total][4] fp32 (xyxy, network-input
+ * coordinates: dense columns 1..4), deltas [total][4] fp32 (dense columns 5..8), class_ids [total] int32, offsets [B+1] int32
+ * (image b owns entries offsets[b] .. offsets[b+1]-1) -- what sqd_encode_gt_fwd takes and returns.  Meaning: the dense gt with
+ * mask = 1, box, deltas and a one-hot class at anchor_idx, zeros elsewhere.  Contract: within one image the anchor indices are
+ * distinct (the encoder's greedy assignment guarantees it); the order within an image is free; an entry with anchor_idx
+ * outside [0, A) (the encoder's "unassigned" value A) is ignored and does not count toward n_obj; a class id outside [0, C)
+ * gives a row with no class term (as the dense encoder leaves its one-hot empty); total = 0 (the four list pointers may then
+ * be NULL) and images without entries are legal and give the NaNs of n_obj = 0.  A negative row costs one float of pred (its
+ * confidence logit); the backward writes all of dpred [B][A][C+5] in one launch.  Workspace, losses, nobj, mean4, coef, gmean
+ * as for sqd_loss_many_*; no floating-point atomics: the same operands give the same bits, and the plain and the mean forward
+ * give bitwise-equal per-image values.  Status 1 for anything malformed, 2 for num_classes > 256 or A > 2^20. */
+int sqd_loss_sparse_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                        const int* offsets, const float* anchors, float* workspace, float* losses, float* nobj, int total,
+                        int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                        float w_bbox, void* stream);
+int sqd_loss_sparse_mean_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                             const int* class_ids, const int* offsets, const float* anchors, float* workspace, float* losses,
+                             float* nobj, float* mean4, int total, int B, int A, int num_classes, int input_h, int input_w,
+                             float w_class, float w_pos, float w_neg, float w_bbox, void* stream);
+int sqd_loss_sparse_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                        const int* offsets, const float* anchors, const float* nobj, const float* coef, float* dpred, int total,
+                        int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                        float w_bbox, void* stream);
+int sqd_loss_sparse_mean_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                             const int* class_ids, const int* offsets, const float* anchors, const float* nobj,
+                             const float* gmean, float* dpred, int total, int B, int A, int num_classes, int input_h,
+                             int input_w, float w_class, float w_pos, float w_neg, float w_bbox, void* stream);
 
 
 /* Fire.forward's two expand convolutions + torch.cat (src/model/squeezedet.py:18-22) in ONE Winograd launch (inference):

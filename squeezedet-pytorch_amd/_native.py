@@ -106,6 +106,10 @@ _SIGNATURES = {
     'sqd_loss_many_bwd': [c_p] * 6 + [c_i] * 5 + [c_f] * 4 + [c_p],
     'sqd_loss_many_mean_fwd': [c_p] * 7 + [c_i] * 5 + [c_f] * 4 + [c_p],
     'sqd_loss_many_mean_bwd': [c_p] * 6 + [c_i] * 5 + [c_f] * 4 + [c_p],
+    'sqd_loss_sparse_fwd': [c_p] * 10 + [c_i] * 6 + [c_f] * 4 + [c_p],
+    'sqd_loss_sparse_bwd': [c_p] * 10 + [c_i] * 6 + [c_f] * 4 + [c_p],
+    'sqd_loss_sparse_mean_fwd': [c_p] * 11 + [c_i] * 6 + [c_f] * 4 + [c_p],
+    'sqd_loss_sparse_mean_bwd': [c_p] * 10 + [c_i] * 6 + [c_f] * 4 + [c_p],
 }
 # symbols added by later build stages; bound when present in the library
 _OPTIONAL = {}

@@ -53,10 +53,12 @@ def pack_annotations(class_ids_list, boxes_list):
     return np.concatenate(bl, 0) if bl else np.zeros((0, 4), np.float32), np.concatenate(cl, 0), offs
 
 
-def encode_annotations(class_ids_list, boxes_list, anchors, num_classes, device='cuda', return_sparse=False):
+def encode_annotations(class_ids_list, boxes_list, anchors, num_classes, device='cuda', return_sparse=False, dense=True):
     """Batch version of ``prepare_annotations``: lists (one entry per image) of class ids [n_i] and xyxy boxes
     [n_i,4] in network-input coordinates -> gt fp32 [B, A, num_classes+9] on ``device``.  With ``return_sparse``
-    also returns (anchor_idx [total] i32, deltas [total,4] f32, box_offsets [B+1] i32), all on the device."""
+    also returns (anchor_idx [total] i32, deltas [total,4] f32, box_offsets [B+1] i32), all on the device.
+    ``dense=False``: -> an ``ops.SparseGT`` (the positives as a list, what ``ops.loss_sparse_*`` consume); the dense
+    tensor is neither allocated nor written."""
     boxes, cls, offs = pack_annotations(class_ids_list, boxes_list)
     A = np.asarray(anchors).shape[0]
     if np.any(np.diff(offs) > A):
@@ -67,6 +69,9 @@ def encode_annotations(class_ids_list, boxes_list, anchors, num_classes, device=
     d_boxes = torch.from_numpy(boxes).to(dev, non_blocking=True)
     d_cls = torch.from_numpy(cls).to(dev, non_blocking=True)
     d_offs = torch.from_numpy(offs).to(dev, non_blocking=True)
+    if not dense:
+        _, idx, deltas = ops.encode_gt(d_boxes, d_cls, d_offs, anchors_f64_on(anchors, dev), num_classes, dense=False)
+        return ops.SparseGT(idx, d_boxes, deltas, d_cls, d_offs)
     gt, idx, deltas = ops.encode_gt(d_boxes, d_cls, d_offs, anchors_f64_on(anchors, dev), num_classes)
     if return_sparse:
         return gt, idx, deltas, d_offs

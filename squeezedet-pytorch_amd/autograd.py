@@ -186,9 +186,12 @@ def backbone_apply(base, image):
 
 
 def loss_apply(loss_mod, pred, gt):
-    from .backward import LossFn
+    from .backward import LossFn, LossSparseFn
     anchors = loss_mod.resolver.anchors_on(pred.device)
-    vec = LossFn.apply(pred, gt, anchors, loss_mod)
+    if isinstance(gt, ops.SparseGT):
+        vec = LossSparseFn.apply(pred, anchors, loss_mod, *gt)
+    else:
+        vec = LossFn.apply(pred, gt, anchors, loss_mod)
     # vec: [4, B] = (class, pos+neg score, bbox, total) -- reference returns (loss, stats dict), :166-174
     class_loss, score_loss, bbox_loss, loss = vec[0], vec[1], vec[2], vec[3]
     return loss, {'loss': loss, 'class_loss': class_loss, 'score_loss': score_loss, 'bbox_loss': bbox_loss}

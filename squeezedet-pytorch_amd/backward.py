@@ -236,3 +236,48 @@ class LossMeanFn(torch.autograd.Function):
         pred, gt, anchors, nobj = ctx.saved_tensors
         input_size, num_classes, weights = ctx.meta
         return ops.loss_fns(num_classes)[3](pred, gt, anchors, nobj, g.reshape(1), input_size, num_classes, weights), None, None, None
+
+
+class LossSparseFn(torch.autograd.Function):
+    """``LossFn`` on a sparse ground truth (ops.SparseGT): the loss launches read the list of positives, no dense gt exists."""
+
+    @staticmethod
+    def forward(ctx, pred, anchors, loss_mod, *sgt):
+        res = loss_mod.resolver
+        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
+                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
+        losses, nobj = ops.loss_sparse_fwd(pred.detach(), ops.SparseGT(*sgt), anchors, res.input_size, res.num_classes, weights)
+        ctx.save_for_backward(pred.detach(), anchors, nobj, *sgt)
+        ctx.meta = (res.input_size, res.num_classes, weights)
+        return losses                      # [4,B] = (class, score, bbox, total)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, anchors, nobj, *sgt = ctx.saved_tensors
+        input_size, num_classes, weights = ctx.meta
+        coef = (g[:3] + g[3:4]).contiguous()       # gradient of `total` reaches all three components
+        dpred = ops.loss_sparse_bwd(pred, ops.SparseGT(*sgt), anchors, nobj, coef, input_size, num_classes, weights)
+        return (dpred, None, None) + (None,) * len(sgt)
+
+
+class LossSparseMeanFn(torch.autograd.Function):
+    """``LossMeanFn`` on a sparse ground truth: mean(total) and its backward inside the sparse loss launches."""
+
+    @staticmethod
+    def forward(ctx, pred, anchors, loss_mod, *sgt):
+        res = loss_mod.resolver
+        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
+                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
+        losses, nobj, mean4 = ops.loss_sparse_mean_fwd(pred.detach(), ops.SparseGT(*sgt), anchors, res.input_size, res.num_classes, weights)
+        ctx.save_for_backward(pred.detach(), anchors, nobj, *sgt)
+        ctx.meta = (res.input_size, res.num_classes, weights)
+        ctx.mark_non_differentiable(losses)
+        ctx.set_materialize_grads(False)
+        return mean4[3], losses
+
+    @staticmethod
+    def backward(ctx, g, _gl):
+        pred, anchors, nobj, *sgt = ctx.saved_tensors
+        input_size, num_classes, weights = ctx.meta
+        dpred = ops.loss_sparse_mean_bwd(pred, ops.SparseGT(*sgt), anchors, nobj, g.reshape(1), input_size, num_classes, weights)
+        return (dpred, None, None) + (None,) * len(sgt)

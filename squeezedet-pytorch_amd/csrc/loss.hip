@@ -465,3 +465,289 @@ extern "C" int sqd_loss_many_mean_bwd(const float* pred, const float* gt, const 
   launch_loss_many_bwd(a, nobj, nullptr, dpred, gmean, (hipStream_t)stream);
   return sqd_launch_status();
 }
+
+// ---- sparse ground truth: the positives as a list, 1 <= num_classes <= 256 -----------------------------------------------------------
+// The dense gt [B][A][C+9] is zero except for the ~0.1 % rows the encoder assigned a box (csrc/gt_encode.hip), and the encoder already
+// returns those rows as a list.  These launches take the list: anchor_idx / boxes / deltas / class_ids [total] and offsets [B+1]
+// (image b owns entries offsets[b] .. offsets[b+1] - 1), meaning the dense gt with mask = 1, the box, the deltas and a one-hot class at
+// anchor_idx and zeros elsewhere.  Contract: the anchor indices of one image are distinct (the encoder's greedy assignment); their order
+// is free; an entry with anchor_idx outside [0, A) (the encoder's "unassigned" value A) is ignored; a class id outside [0, C) gives a row
+// without a class term (as the dense encoder leaves the one-hot empty); total = 0 and images without entries are legal (n_obj = 0: NaN).
+//
+// A negative row costs ONE float of pred, its confidence logit: with mask = 0 the dense kernels' e is -sigmoid(conf) and every other
+// term is multiplied by the mask.  A positive row gets a 16-lane group (many_class.h) that synthesises the row's nine gt floats in
+// registers, so the class-independent chain is anchor_geom / anchor_geom_grad, the dense kernels' own.  The forward keeps the
+// [B][LOSS_NPART][5] partial layout and loss_finalize_kernel; no floating-point atomics anywhere (the LDS atomics are integer or / max,
+// which do not depend on the order they arrive in), so the same operands give the same bits and the plain and the mean forward agree.
+#define LS_MAX_ANCHORS (1 << 20)
+#define LS_BITMAP_WORDS (LS_MAX_ANCHORS / LOSS_NPART / 32)      // one bit per anchor of a block's slice: 8 KB
+#define LS_ROWS MC_THREADS                                       // dpred rows per workgroup of the backward
+
+struct SparseGT {
+  const int* anchor_idx; const float* boxes; const float* deltas; const int* class_ids; const int* offsets;
+  int total;
+};
+
+// image b's entries [beg, end), cut to the list (a malformed offsets table reads nothing out of bounds)
+__device__ __forceinline__ void sparse_range(const SparseGT& sg, int b, int& beg, int& end) {
+  beg = max(0, sg.offsets[b]);
+  end = min(sg.total, sg.offsets[b + 1]);
+}
+
+// the first nine floats of the dense gt row that entry e stands for: mask, xyxy, deltas
+__device__ __forceinline__ void sparse_gt_row(const SparseGT& sg, int e, float (&g)[9]) {
+  g[0] = 1.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { g[1 + k] = sg.boxes[4 * (long long)e + k]; g[5 + k] = sg.deltas[4 * (long long)e + k]; }
+}
+
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArgs a, SparseGT sg, float* __restrict__ partial) {
+  __shared__ unsigned bitmap[LS_BITMAP_WORDS];
+  __shared__ float red[5][MC_THREADS / 64];
+  const int b = blockIdx.y, blk = blockIdx.x, C = a.C, tid = threadIdx.x;
+  const int per = (a.A + LOSS_NPART - 1) / LOSS_NPART;
+  const int lo = blk * per, hi = min(a.A, lo + per);
+  // 1. mark the slice's positives (integer atomic-or: the result does not depend on the list's order)
+  for (int w = tid; w < (hi - lo + 31) / 32; w += MC_THREADS) bitmap[w] = 0u;
+  __syncthreads();
+  int beg, end;
+  sparse_range(sg, b, beg, end);
+  for (int e = beg + tid; e < end; e += MC_THREADS) {
+    const int i = sg.anchor_idx[e];
+    if (i >= lo && i < hi) atomicOr(&bitmap[(i - lo) >> 5], 1u << ((i - lo) & 31));
+  }
+  __syncthreads();
+  float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  // 2. every row of the slice: a marked row counts toward n_obj, any other adds sigmoid(conf)^2 (the dense e * e at mask = 0)
+  for (int i = lo + tid; i < hi; i += MC_THREADS) {
+    if ((bitmap[(i - lo) >> 5] >> ((i - lo) & 31)) & 1u) {
+      s[0] += 1.f;
+    } else {
+      const float conf = 1.f / (1.f + expf(-a.pred[((long long)b * a.A + i) * (C + 5) + C]));
+      const float e = 0.f - conf;
+      s[3] += e * e;
+    }
+  }
+  // 3. the positives: group g takes the image's entries g, g + MC_GROUPS, ... that fall in the slice (a fixed assignment)
+  const int j = tid & (MC_LANES - 1), grp = tid / MC_LANES;
+  for (int e = beg + grp; e < end; e += MC_GROUPS) {          // (group-uniform)
+    const int i = sg.anchor_idx[e];
+    if (i < lo || i >= hi) continue;
+    const float* p = a.pred + ((long long)b * a.A + i) * (C + 5);
+    float g[9];
+    sparse_gt_row(sg, e, g);
+    const int cls = sg.class_ids[e];
+    float l[R], ex[R];
+    const float m = mc_load_logits<R>(p, C, j, l);
+    const float lse = logf(mc_exp_sum<R>(C, j, m, l, ex));
+    float ce = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (j + MC_LANES * r == cls && cls < C) ce += -((l[r] - m) - lse);
+    ce = mc_group_sum(ce);
+    AnchorGeom t;
+    anchor_geom(a, p, g, a.anchors + 4 * i, t);
+    if (j == 0) {
+      s[1] += ce;
+      s[2] += t.e * t.e;
+      s[4] += t.bb;
+    }
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    float v = s[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+    if (lane == 0) red[k][wave] = v;
+  }
+  __syncthreads();
+  if (tid < 5) {
+    float v = 0.f;
+    for (int w = 0; w < MC_THREADS / 64; ++w) v += red[tid][w];
+    partial[((long long)b * LOSS_NPART + blk) * 5 + tid] = v;
+  }
+}
+
+// One launch writes all of dpred.  Workgroup (x, b) owns rows x * LS_ROWS .. of image b: it looks its rows up in the image's list
+// (slot[row] = entry + 1), writes every negative row as zeros with the confidence gradient in column C (anchor_geom_grad at mask = 0),
+// consecutive lanes storing consecutive 16-byte pieces, and hands each positive row to a lane group as loss_many_bwd_kernel does.
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a, SparseGT sg, const float* __restrict__ nobj,
+                                                                     const float* __restrict__ coef, float* __restrict__ dpred,
+                                                                     const float* __restrict__ gmean) {
+  __shared__ int slot[LS_ROWS];
+  __shared__ float cgrad[LS_ROWS];
+  const int b = blockIdx.y, row0 = blockIdx.x * LS_ROWS, C = a.C, W = C + 5, tid = threadIdx.x;
+  const int nrows = min(LS_ROWS, a.A - row0);
+  slot[tid] = 0;
+  __syncthreads();
+  int beg, end;
+  sparse_range(sg, b, beg, end);
+  for (int e = beg + tid; e < end; e += MC_THREADS) {
+    const int i = sg.anchor_idx[e];
+    if (i >= row0 && i < row0 + nrows) atomicMax(&slot[i - row0], e - beg + 1);      // (distinct by contract; max: defined anyway)
+  }
+  const float n = nobj[b];
+  const float gm = gmean ? gmean[0] / (float)a.B : 0.f;
+  const float uc = gmean ? gm : coef[0 * a.B + b], us = gmean ? gm : coef[1 * a.B + b], ub = gmean ? gm : coef[2 * a.B + b];
+  // mask = 0 in the dense formulas: the score coefficient, and what the class / delta columns hold (0, or NaN where n_obj = 0)
+  const float kneg = us * (a.w_pos * 0.f / n + a.w_neg * (1.f - 0.f) / ((float)a.A - n));
+  const float zc = (uc * a.w_class * 0.f / n) * 0.f;
+  const float zd = kneg * 0.f + (ub * a.w_bbox * 0.f / n * 2.f) * 0.f;
+  __syncthreads();
+  const long long base = (long long)b * a.A + row0;
+  if (tid < nrows && slot[tid] == 0) {
+    const float conf = 1.f / (1.f + expf(-a.pred[(base + tid) * W + C]));
+    const float dL_de = 2.f * kneg * (0.f - conf);
+    cgrad[tid] = -dL_de * conf * (1.f - conf);
+  }
+  __syncthreads();
+  float* __restrict__ o = dpred + base * W;
+  {
+    // the workgroup's nrows * W floats are contiguous: up to three floats to the first 16-byte boundary, 16-byte stores, a tail.  A
+    // vector covers at most two rows (W >= 6); one that touches a positive row stores its other floats one by one.
+    const int nfl = nrows * W;
+    const auto val = [&](int r, int col) { return col < C ? zc : (col == C ? cgrad[r] : zd); };
+    int head = (int)((4 - ((base * W) & 3)) & 3);
+    if ((reinterpret_cast<uintptr_t>(dpred) & 15) != 0 || head > nfl) head = nfl;          // (an unaligned dpred: all of it one by one)
+    const int nv = (nfl - head) / 4;
+    const auto put = [&](int f) {
+      const int r = f / W, col = f - r * W;
+      if (slot[r] == 0) o[f] = val(r, col);
+    };
+    for (int f = tid; f < head; f += MC_THREADS) put(f);
+    for (int f = head + 4 * nv + tid; f < nfl; f += MC_THREADS) put(f);
+    f32x4* __restrict__ o4 = reinterpret_cast<f32x4*>(o + head);
+    const int q = (4 * MC_THREADS) / W, rem = (4 * MC_THREADS) % W;      // (row, column) advance by 4 * MC_THREADS floats: no division
+    int r = (head + 4 * tid) / W, col = head + 4 * tid - r * W;
+    for (int v = tid; v < nv; v += MC_THREADS) {
+      float x[4]; int rk[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int ck = col + k >= W ? col + k - W : col + k;
+        rk[k] = col + k >= W ? r + 1 : r;
+        x[k] = val(rk[k], ck);
+      }
+      if (slot[r] == 0 && slot[rk[3]] == 0) {
+        o4[v] = (f32x4){x[0], x[1], x[2], x[3]};
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (slot[rk[k]] == 0) o[head + 4 * v + k] = x[k];
+      }
+      r += q; col += rem;
+      if (col >= W) { col -= W; ++r; }
+    }
+  }
+  const int j = tid & (MC_LANES - 1);
+  for (int r = tid / MC_LANES; r < nrows; r += MC_GROUPS) {     // (group-uniform)
+    const int sl = slot[r];
+    if (sl == 0) continue;
+    const int e = beg + sl - 1;
+    const float* p = a.pred + (base + r) * W;
+    float g[9];
+    sparse_gt_row(sg, e, g);
+    const int cls = sg.class_ids[e];
+    const float ohs = (cls >= 0 && cls < C) ? 1.f : 0.f;
+    float l[R], ex[R];
+    const float m = mc_load_logits<R>(p, C, j, l);
+    const float sum = mc_exp_sum<R>(C, j, m, l, ex);
+    AnchorGeom t;
+    anchor_geom(a, p, g, a.anchors + 4 * (row0 + r), t);
+    float* orow = o + (long long)r * W;
+    const float kc = uc * a.w_class * t.mask / n;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int c = j + MC_LANES * k;
+      if (c < C) orow[c] = kc * (ohs * (ex[k] / sum) - (c == cls ? 1.f : 0.f));
+    }
+    float og[5];
+    anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
+    if (j < 5) orow[C + j] = (j == 0) ? og[0] : (j == 1) ? og[1] : (j == 2) ? og[2] : (j == 3) ? og[3] : og[4];
+  }
+}
+
+static int fill_args_sparse(LossArgs& a, SparseGT& sg, const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                            const int* class_ids, const int* offsets, const float* anchors, int total, int B, int A, int C,
+                            int input_h, int input_w, float w_class, float w_pos, float w_neg, float w_bbox) {
+  SQD_CHECK_ARG(pred && anchors && offsets && B > 0 && B <= 65535 && A > 0 && C >= 1 && total >= 0);
+  SQD_CHECK_ARG(total == 0 || (anchor_idx && boxes && deltas && class_ids));
+  if (C > SQD_MANY_MAX_CLASSES || A > LS_MAX_ANCHORS) return SQD_ERR_UNSUPPORTED;
+  a.pred = pred; a.gt = nullptr; a.anchors = anchors; a.B = B; a.A = A; a.C = C;
+  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
+  a.w_class = w_class; a.w_pos = w_pos; a.w_neg = w_neg; a.w_bbox = w_bbox;
+  sg.anchor_idx = anchor_idx; sg.boxes = boxes; sg.deltas = deltas; sg.class_ids = class_ids; sg.offsets = offsets; sg.total = total;
+  return SQD_OK;
+}
+
+static void launch_loss_sparse_partial(const LossArgs& a, const SparseGT& sg, float* workspace, hipStream_t s) {
+#define CALL(R) hipLaunchKernelGGL(loss_sparse_partial_kernel<R>, dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), 0, s, a, sg, workspace)
+  MC_DISPATCH(a.C, CALL);
+#undef CALL
+}
+
+static void launch_loss_sparse_bwd(const LossArgs& a, const SparseGT& sg, const float* nobj, const float* coef, float* dpred,
+                                   const float* gmean, hipStream_t s) {
+  const dim3 grid((unsigned)sqd_cdiv(a.A, LS_ROWS), (unsigned)a.B);
+#define CALL(R) hipLaunchKernelGGL(loss_sparse_bwd_kernel<R>, grid, dim3(MC_THREADS), 0, s, a, sg, nobj, coef, dpred, gmean)
+  MC_DISPATCH(a.C, CALL);
+#undef CALL
+}
+
+// The four loss launches on the sparse ground truth (all device pointers; the list pointers may be null when total = 0).  Workspace,
+// losses, nobj, mean4, coef, gmean, dpred as for sqd_loss_many_*.  Status 1 for anything malformed, 2 for num_classes > 256 or
+// A > 2^20.
+extern "C" int sqd_loss_sparse_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                                   const int* offsets, const float* anchors, float* workspace, float* losses, float* nobj, int total,
+                                   int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                                   float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
+                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(workspace && losses && nobj);
+  hipStream_t s = (hipStream_t)stream;
+  launch_loss_sparse_partial(a, sg, workspace, s);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3((unsigned)sqd_cdiv(B, 64)), dim3(64), 0, s, workspace, losses, nobj, B, A,
+                     w_class, w_pos, w_neg, w_bbox, (float*)nullptr);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_loss_sparse_mean_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                        const int* class_ids, const int* offsets, const float* anchors, float* workspace, float* losses,
+                                        float* nobj, float* mean4, int total, int B, int A, int num_classes, int input_h, int input_w,
+                                        float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
+                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(workspace && losses && nobj && mean4);
+  hipStream_t s = (hipStream_t)stream;
+  launch_loss_sparse_partial(a, sg, workspace, s);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, losses, nobj, B, A, w_class, w_pos, w_neg, w_bbox, mean4);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_loss_sparse_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                                   const int* offsets, const float* anchors, const float* nobj, const float* coef, float* dpred, int total,
+                                   int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                                   float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
+                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(nobj && coef && dpred);
+  launch_loss_sparse_bwd(a, sg, nobj, coef, dpred, nullptr, (hipStream_t)stream);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_loss_sparse_mean_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                        const int* class_ids, const int* offsets, const float* anchors, const float* nobj,
+                                        const float* gmean, float* dpred, int total, int B, int A, int num_classes, int input_h,
+                                        int input_w, float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
+                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(nobj && gmean && dpred);
+  launch_loss_sparse_bwd(a, sg, nobj, nullptr, dpred, gmean, (hipStream_t)stream);
+  return sqd_launch_status();
+}

@@ -12,6 +12,8 @@ writing ``ops.choose_cfg`` / ``ops.ConvPlan`` / ``ops.KernelTimer``.
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
+
 import torch
 
 from . import _native as nat
@@ -1268,6 +1270,184 @@ def loss_fns(num_classes):
     if head_path(num_classes) == 'many':
         return loss_fwd_many, loss_mean_fwd_many, loss_bwd_many, loss_mean_bwd_many
     return loss_fwd, loss_mean_fwd, loss_bwd, loss_mean_bwd
+
+
+class SparseGT(NamedTuple):
+    """The ground truth of a batch of B images as the list of its positives (device tensors): what the dense ``gt [B,A,C+9]``
+    holds outside its all-zero rows.  ``anchor_idx`` int32 [total]: the anchor each box was assigned; ``boxes`` fp32 [total,4]: xyxy in
+    network-input coordinates (dense columns 1..4); ``deltas`` fp32 [total,4] (dense columns 5..8); ``class_ids`` int32 [total];
+    ``offsets`` int32 [B+1]: image b owns the entries ``offsets[b] .. offsets[b+1]``.  Meaning: the dense gt with mask = 1, these boxes
+    and deltas and a one-hot class at ``anchor_idx``, zeros elsewhere.
+
+    Contract (include/sqd_hip.h): within one image the anchor indices are distinct (the encoder's greedy assignment guarantees it);
+    the order within an image is free; an entry with ``anchor_idx`` outside [0, A) -- the encoder's "unassigned" value A -- is ignored
+    and does not count toward n_obj; a class id outside [0, C) gives a row with no class term, as the dense encoder does; ``total = 0``
+    and images without entries are legal and give the NaNs that n_obj = 0 gives with a dense gt."""
+    anchor_idx: torch.Tensor
+    boxes: torch.Tensor
+    deltas: torch.Tensor
+    class_ids: torch.Tensor
+    offsets: torch.Tensor
+
+    def to(self, device, non_blocking=False):
+        return SparseGT(*(t.to(device=device, non_blocking=non_blocking) for t in self))
+
+
+def sparse_gt_from_dense(gt):
+    """Dense gt [B,A,C+9] -> SparseGT (torch only; tests and conversions): the rows with ``gt[..., 0] > 0`` in ascending anchor
+    order, class = arg-max of the one-hot."""
+    if gt.dim() != 3 or gt.shape[2] < 10:
+        raise ValueError(f'sparse_gt_from_dense: gt must be [B,A,C+9], got {tuple(gt.shape)}')
+    B = gt.shape[0]
+    pos = gt[..., 0] > 0
+    b_idx, a_idx = torch.nonzero(pos, as_tuple=True)          # row-major: ascending image, then ascending anchor
+    rows = gt[b_idx, a_idx]
+    offsets = torch.zeros(B + 1, dtype=torch.int32, device=gt.device)
+    offsets[1:] = torch.cumsum(pos.sum(1), 0).to(torch.int32)
+    cls = rows[:, 9:].argmax(1).to(torch.int32) if rows.shape[0] else torch.zeros(0, dtype=torch.int32, device=gt.device)
+    return SparseGT(a_idx.to(torch.int32), rows[:, 1:5].float().contiguous(), rows[:, 5:9].float().contiguous(), cls, offsets)
+
+
+def sparse_gt_to_dense(sgt, A, C):
+    """SparseGT -> the dense gt fp32 [B,A,C+9] it stands for (torch only): entries with ``anchor_idx`` outside [0, A) are dropped, a
+    class id outside [0, C) leaves the row's one-hot empty."""
+    B = sgt.offsets.shape[0] - 1
+    dev = sgt.offsets.device
+    gt = torch.zeros(B, A, C + 9, dtype=torch.float32, device=dev)
+    counts = (sgt.offsets[1:] - sgt.offsets[:-1]).long()
+    img = torch.repeat_interleave(torch.arange(B, device=dev), counts)
+    idx = sgt.anchor_idx.long()
+    keep = (idx >= 0) & (idx < A)
+    img, idx = img[keep], idx[keep]
+    gt[img, idx, 0] = 1.0
+    gt[img, idx, 1:5] = sgt.boxes[keep]
+    gt[img, idx, 5:9] = sgt.deltas[keep]
+    cls = sgt.class_ids.long()[keep]
+    ok = (cls >= 0) & (cls < C)
+    gt[img[ok], idx[ok], 9 + cls[ok]] = 1.0
+    return gt
+
+
+def _check_sparse_loss_args(name, pred, sgt, anchors, num_classes):
+    """Everything the sparse launches assume about their operands, before the library is touched: kinds and shapes first, devices
+    last.  -> (B, A, total, sgt with contiguous members)."""
+    head_path(num_classes)
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32:
+        raise ValueError(f'{name}: pred must be fp32 [B,A,C+5]')
+    B, A, _ = pred.shape
+    if A > 2 ** 20:
+        raise ValueError(f'{name}: at most 2^20 anchors, got {A}')
+    if not isinstance(sgt, SparseGT):
+        raise ValueError(f'{name}: sgt must be an ops.SparseGT')
+    fields = ((sgt.anchor_idx, 'anchor_idx', torch.int32), (sgt.boxes, 'boxes', torch.float32), (sgt.deltas, 'deltas', torch.float32),
+              (sgt.class_ids, 'class_ids', torch.int32), (sgt.offsets, 'offsets', torch.int32))
+    for t, nm, dt in fields:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f'{name}: sgt.{nm} must be a {dt} tensor')
+    if tuple(sgt.offsets.shape) != (B + 1,):
+        raise ValueError(f'{name}: sgt.offsets must be [B+1] = [{B + 1}], got {tuple(sgt.offsets.shape)}')
+    total = sgt.anchor_idx.shape[0] if sgt.anchor_idx.dim() == 1 else -1
+    if total < 0 or tuple(sgt.boxes.shape) != (total, 4) or tuple(sgt.deltas.shape) != (total, 4) or tuple(sgt.class_ids.shape) != (total,):
+        raise ValueError(f'{name}: anchor_idx [total], boxes [total,4], deltas [total,4], class_ids [total] must agree on total, got '
+                         f'{tuple(sgt.anchor_idx.shape)} {tuple(sgt.boxes.shape)} {tuple(sgt.deltas.shape)} {tuple(sgt.class_ids.shape)}')
+    if not isinstance(anchors, torch.Tensor) or tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32:
+        raise ValueError(f'{name}: anchors must be fp32 [A,4]')
+    if not pred.is_cuda:
+        raise ValueError(f'{name}: pred must be on the GPU, got {pred.device}')
+    for t, nm in [(t, 'sgt.' + nm) for t, nm, _ in fields] + [(anchors, 'anchors')]:
+        if t.device != pred.device:
+            raise ValueError(f'{name}: {nm} is on {t.device}, pred on {pred.device}')
+    return B, A, total, SparseGT(*(t.contiguous() for t in sgt))
+
+
+def _sparse_ptrs(sgt):
+    return [nat.ptr(t) for t in sgt]
+
+
+def _sparse_fwd_bytes(B, A, total, num_classes):
+    """Bytes the sparse forward reads: one confidence logit per row, the list once per slice of an image, a positive's pred row,
+    box, deltas and anchor."""
+    return 4.0 * (B * A + 16 * total + total * (num_classes + 5 + 13))
+
+
+def loss_sparse_fwd(pred, sgt, anchors, input_size, num_classes, weights):
+    """``loss_fwd`` on a sparse ground truth (``SparseGT``), 1 <= num_classes <= 256: -> (losses [4,B], nobj [B]).  A negative row
+    costs one float of ``pred``; the dense gt is never read or built."""
+    B, A, total, sgt = _check_sparse_loss_args('loss_sparse_fwd', pred, sgt, anchors, num_classes)
+    pred, anchors = pred.contiguous(), anchors.contiguous()
+    ws = torch.empty(B * 16 * 5, device=pred.device, dtype=torch.float32)
+    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
+    nobj = torch.empty(B, device=pred.device, dtype=torch.float32)
+    br = _Bracket('loss_sparse_fwd', f'loss A{A}', 0.0, _sparse_fwd_bytes(B, A, total, num_classes)) if timing._timer is not None else None
+    rc = nat.lib().sqd_loss_sparse_fwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj),
+                                       total, B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
+                                       nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_loss_sparse_fwd')
+    if br is not None:
+        br.done()
+    return losses, nobj
+
+
+def loss_sparse_mean_fwd(pred, sgt, anchors, input_size, num_classes, weights):
+    """``loss_mean_fwd`` on a sparse ground truth: -> (losses [4,B], nobj [B], mean4 [4]); the per-image values equal
+    ``loss_sparse_fwd``'s bit for bit."""
+    B, A, total, sgt = _check_sparse_loss_args('loss_sparse_mean_fwd', pred, sgt, anchors, num_classes)
+    pred, anchors = pred.contiguous(), anchors.contiguous()
+    ws = torch.empty(B * 16 * 5, device=pred.device, dtype=torch.float32)
+    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
+    nobj = torch.empty(B, device=pred.device, dtype=torch.float32)
+    mean4 = torch.empty(4, device=pred.device, dtype=torch.float32)
+    br = _Bracket('loss_sparse_fwd', f'loss A{A}', 0.0, _sparse_fwd_bytes(B, A, total, num_classes)) if timing._timer is not None else None
+    rc = nat.lib().sqd_loss_sparse_mean_fwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj),
+                                            nat.ptr(mean4), total, B, A, num_classes, int(input_size[0]), int(input_size[1]),
+                                            *[float(w) for w in weights], nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_loss_sparse_mean_fwd')
+    if br is not None:
+        br.done()
+    return losses, nobj, mean4
+
+
+def _sparse_bwd_bytes(B, A, total, num_classes):
+    """Bytes the sparse backward moves: all of dpred written, one confidence logit per row and a positive's operands read, the
+    list once per workgroup of an image."""
+    return 4.0 * (B * A * (num_classes + 5) + B * A + -(-A // 256) * total + total * (num_classes + 5 + 13))
+
+
+def loss_sparse_bwd(pred, sgt, anchors, nobj, coef, input_size, num_classes, weights):
+    """``loss_bwd`` on a sparse ground truth: coef [3,B] -> dpred [B,A,C+5] (dense: ConvDet's backward reads it whole)."""
+    B, A, total, sgt = _check_sparse_loss_args('loss_sparse_bwd', pred, sgt, anchors, num_classes)
+    if tuple(coef.shape) != (3, B) or tuple(nobj.shape) != (B,) or nobj.dtype != torch.float32 or nobj.device != pred.device \
+            or coef.device != pred.device:
+        raise ValueError('loss_sparse_bwd: coef must be [3,B], nobj fp32 [B], both on the device of pred')
+    pred, anchors, coef, nobj = pred.contiguous(), anchors.contiguous(), coef.contiguous().float(), nobj.contiguous()
+    dpred = torch.empty_like(pred)
+    br = _Bracket('loss_sparse_bwd', f'lossbwd A{A}', 0.0, _sparse_bwd_bytes(B, A, total, num_classes)) if timing._timer is not None else None
+    rc = nat.lib().sqd_loss_sparse_bwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(coef), nat.ptr(dpred),
+                                       total, B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
+                                       nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_loss_sparse_bwd')
+    if br is not None:
+        br.done()
+    return dpred
+
+
+def loss_sparse_mean_bwd(pred, sgt, anchors, nobj, gmean, input_size, num_classes, weights):
+    """``loss_mean_bwd`` on a sparse ground truth: gmean, a device scalar (the gradient arriving at mean(total)) -> dpred [B,A,C+5]."""
+    B, A, total, sgt = _check_sparse_loss_args('loss_sparse_mean_bwd', pred, sgt, anchors, num_classes)
+    if gmean.numel() != 1 or gmean.dtype != torch.float32 or gmean.device != pred.device:
+        raise ValueError('loss_sparse_mean_bwd: gmean must be one fp32 value on the same device')
+    if tuple(nobj.shape) != (B,) or nobj.dtype != torch.float32 or nobj.device != pred.device:
+        raise ValueError('loss_sparse_mean_bwd: nobj must be fp32 [B] on the device of pred')
+    pred, anchors, nobj = pred.contiguous(), anchors.contiguous(), nobj.contiguous()
+    dpred = torch.empty_like(pred)
+    br = _Bracket('loss_sparse_bwd', f'lossbwd A{A}', 0.0, _sparse_bwd_bytes(B, A, total, num_classes)) if timing._timer is not None else None
+    rc = nat.lib().sqd_loss_sparse_mean_bwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(gmean.contiguous()),
+                                            nat.ptr(dpred), total, B, A, num_classes, int(input_size[0]), int(input_size[1]),
+                                            *[float(w) for w in weights], nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_loss_sparse_mean_bwd')
+    if br is not None:
+        br.done()
+    return dpred
 
 
 def encode_gt(boxes, class_ids, box_offsets, anchors64, num_classes, dense=True, parallel=True):

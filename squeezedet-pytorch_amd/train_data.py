@@ -1,7 +1,7 @@
 """``TrainLoader``: the training side of ``Detector.detect_dataset`` -- batches of a reference-protocol dataset (``load_image(i)``,
 ``load_annotations(i)``, ``__len__``, ``rgb_mean``, ``rgb_std``; src/datasets/base.py, src/datasets/kitti.py) delivered on the
-device as ``{'image', 'image_meta', 'gt'}``, augmented the reference's train-phase way (``augment``), ready for
-``Trainer.run_epoch``.
+device as ``{'image', 'image_meta', 'gt'}`` (with ``cfg.sparse_gt``: ``'gt_sparse'``, an ``ops.SparseGT``, in place of the dense ``'gt'``),
+augmented the reference's train-phase way (``augment``), ready for ``Trainer.run_epoch``.
 
 ``cfg.num_workers`` threads load the next batch and pack its raw pixels into a pinned staging buffer owned by the loader (two,
 used alternately; one is refilled only after an event shows its previous host-to-device copy has finished).  The main thread
@@ -178,10 +178,11 @@ class TrainLoader:
         stage.copied.record(torch.cuda.current_stream(self.device))
         out = torch.empty(B, 3, H, W, device=self.device, dtype=torch.float32)
         augment.launch(dev_buf, B, hdr, self.cfg.input_size, out, self.forbid_resize, self.rgb_mean, self.rgb_std)
-        gt = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device)
+        sparse = bool(getattr(self.cfg, 'sparse_gt', False))      # the positives as a list (ops.SparseGT): no dense tensor is built
+        gt = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device, dense=not sparse)
         meta = augment.batch_meta(metas, sizes, self.rgb_mean, self.rgb_std)
         meta['index'] = p['index']
-        return {'image': out, 'image_meta': meta, 'gt': gt}
+        return {'image': out, 'image_meta': meta, 'gt_sparse' if sparse else 'gt': gt}
 
     def __iter__(self):
         batches = self._global_batches()

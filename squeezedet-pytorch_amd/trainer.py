@@ -272,12 +272,16 @@ def allreduce_gradients(params, world=None, group=None, local_batch=None):
 def encode_sparse_batch(batch, cfg):
     """Collate helper: a batch carrying sparse annotations (``gt_boxes`` / ``gt_class_ids``: per-image lists, network-input
     coordinates) instead of the dense ``gt`` gets the dense tensor built ON THE GPU (``annotations.encode_annotations``;
-    the reference does it per image in DataLoader workers, src/datasets/base.py:61-76).  Dense batches pass through."""
-    if 'gt' in batch or 'gt_boxes' not in batch:
+    the reference does it per image in DataLoader workers, src/datasets/base.py:61-76).  With ``cfg.sparse_gt`` the batch gets
+    ``'gt_sparse'`` (an ``ops.SparseGT``: the positives as a list, read by the sparse loss launches) instead and no dense tensor is
+    built.  Dense batches pass through, whatever the flag."""
+    if 'gt' in batch or 'gt_sparse' in batch or 'gt_boxes' not in batch:
         return batch
     from .annotations import encode_annotations
     out = {k: v for k, v in batch.items() if k not in ('gt_boxes', 'gt_class_ids')}
-    out['gt'] = encode_annotations(batch['gt_class_ids'], batch['gt_boxes'], cfg.anchors, cfg.num_classes, device=cfg.device)
+    sparse = bool(getattr(cfg, 'sparse_gt', False))
+    out['gt_sparse' if sparse else 'gt'] = encode_annotations(batch['gt_class_ids'], batch['gt_boxes'], cfg.anchors, cfg.num_classes,
+                                                               device=cfg.device, dense=not sparse)
     return out
 
 
@@ -327,8 +331,16 @@ class Trainer(object):
 
     def _to_device(self, batch):
         batch = encode_sparse_batch(batch, self.cfg)
-        return {k: (v.to(device=self.cfg.device, non_blocking=True) if ('image_meta' not in k and isinstance(v, torch.Tensor)) else v)
-                for k, v in batch.items()}
+
+        def move(k, v):
+            if 'image_meta' in k:
+                return v
+            if isinstance(v, torch.Tensor):
+                return v.to(device=self.cfg.device, non_blocking=True)
+            if isinstance(v, tuple) and hasattr(v, '_fields') and all(isinstance(t, torch.Tensor) for t in v):
+                return type(v)(*(t.to(device=self.cfg.device, non_blocking=True) for t in v))       # a NamedTuple of tensors (ops.SparseGT)
+            return v
+        return {k: move(k, v) for k, v in batch.items()}
 
     def _iteration(self, batch, train):
         fused = train and hasattr(self.model, 'forward_mean')

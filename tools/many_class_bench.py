@@ -8,10 +8,14 @@ in --out.  B = 20, A = 16 848 (24 x 78 x 9):
            alternating: they are the reference there.
   convdet: for 20 and 80 classes ConvDet's forward at its padded width followed by the pack launch, against the same convolution
            alone; the pack and the unpack launch on their own.
+  sparse : for C in {3, 20, 80, 256} the dense ground truth against the sparse one (ops.SparseGT, DESIGN.md section 3 "Sparse ground
+           truth"): the encoder with and without the dense write, the loss forward (mean form) and the loss backward on the kernels
+           that serve C (ops.loss_fns) and on the sparse launches, same operands, alternating in one process.  GB/s of a sparse leg
+           is against the sparse launch's own bytes (ops._sparse_fwd_bytes / _sparse_bwd_bytes).
 
 Device events around each call after warm-up.  Nothing here has a pass mark.
 
-    python tools/many_class_bench.py [--reps 100] [--out profiles/many_class_bench.json]
+    python tools/many_class_bench.py [--reps 100] [--sections head,convdet,sparse] [--out profiles/many_class_bench.json]
 """
 import argparse
 import json
@@ -98,6 +102,32 @@ def head_case(C, A, anchors, reps):
     return out
 
 
+def sparse_case(C, A, anchors, anchors64, reps):
+    dev = anchors.device
+    pred, gt = make_inputs(A, C, anchors, seed=C)
+    sgt = ops.sparse_gt_from_dense(gt)
+    total = int(sgt.anchor_idx.shape[0])
+    gmean = torch.ones(1, device=dev)
+    _, mean_fwd, _, mean_bwd = ops.loss_fns(C)
+    _, nobj, _ = ops.loss_sparse_mean_fwd(pred, sgt, anchors, SIZE, C, WEIGHTS)
+    calls = {'encode_dense': lambda: ops.encode_gt(sgt.boxes, sgt.class_ids, sgt.offsets, anchors64, C),
+             'encode_sparse': lambda: ops.encode_gt(sgt.boxes, sgt.class_ids, sgt.offsets, anchors64, C, dense=False),
+             'loss_fwd_dense': lambda: mean_fwd(pred, gt, anchors, SIZE, C, WEIGHTS),
+             'loss_fwd_sparse': lambda: ops.loss_sparse_mean_fwd(pred, sgt, anchors, SIZE, C, WEIGHTS),
+             'loss_bwd_dense': lambda: mean_bwd(pred, gt, anchors, nobj, gmean, SIZE, C, WEIGHTS),
+             'loss_bwd_sparse': lambda: ops.loss_sparse_mean_bwd(pred, sgt, anchors, nobj, gmean, SIZE, C, WEIGHTS)}
+    us = time_alternating(calls, reps)
+    rows = B * A
+    byts = {'encode_dense': 4.0 * rows * (C + 9), 'loss_fwd_dense': 4.0 * rows * (2 * C + 14), 'loss_bwd_dense': 4.0 * rows * (3 * C + 19),
+            'loss_fwd_sparse': ops._sparse_fwd_bytes(B, A, total, C), 'loss_bwd_sparse': ops._sparse_bwd_bytes(B, A, total, C)}
+    out = {'positives': total, 'dense_path': ops.head_path(C), 'gt_MB': 4e-6 * rows * (C + 9), 'dpred_MB': 4e-6 * rows * (C + 5)}
+    for k, v in us.items():
+        out[k + '_us'] = v
+        if k in byts:
+            out[k + '_GBps'] = byts[k] / v * 1e-3
+    return out
+
+
 def convdet_case(C, reps):
     N, Npad = ops.convdet_width(9, C)
     conv = _ConvParams(768, Npad, 3, padding=1).cuda()
@@ -123,6 +153,7 @@ def convdet_case(C, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=100)
+    ap.add_argument('--sections', default='head,convdet,sparse', help='comma-separated subset of head, convdet, sparse')
     ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'many_class_bench.json'))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -131,8 +162,16 @@ def main():
     anchors = torch.from_numpy(cfg.anchors).float().cuda()
     A = cfg.num_anchors
     res = {'batch': B, 'anchors': A, 'reps': args.reps, 'keep_top_k': 64, 'unit': 'us (median, device events); GB/s against the algorithmic bytes'}
-    res['head'] = {f'C{C}': head_case(C, A, anchors, args.reps) for C in (16, 20, 80, 256)}
-    res['convdet'] = {f'C{C}': convdet_case(C, args.reps) for C in (20, 80)}
+    sections = [x for x in args.sections.split(',') if x]
+    if not sections or set(sections) - {'head', 'convdet', 'sparse'}:
+        raise SystemExit(f'many_class_bench: --sections takes head, convdet, sparse; got {args.sections!r}')
+    if 'head' in sections:
+        res['head'] = {f'C{C}': head_case(C, A, anchors, args.reps) for C in (16, 20, 80, 256)}
+    if 'convdet' in sections:
+        res['convdet'] = {f'C{C}': convdet_case(C, args.reps) for C in (20, 80)}
+    if 'sparse' in sections:
+        anchors64 = torch.from_numpy(np.asarray(cfg.anchors, np.float64)).cuda()
+        res['sparse'] = {f'C{C}': sparse_case(C, A, anchors, anchors64, args.reps) for C in (3, 20, 80, 256)}
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as fh:
