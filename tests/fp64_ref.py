@@ -69,14 +69,17 @@ def _cast(t, dtype, absval):
     return t.abs() if absval else t
 
 
-def _conv_core(x, w, dtype, absval, emu):
-    """Stride-1 'same' convolution, NHWC x [B,H,W,C] and OIHW w [N,C,k,k] (k = 1 or 3): sum over taps of shifted matmuls."""
+def _conv_core(x, w, dtype, absval, emu, chain_kc=None):
+    """Stride-1 'same' convolution, NHWC x [B,H,W,C] and OIHW w [N,C,k,k] (k = 1 or 3): sum over taps of shifted matmuls.
+    ``chain_kc`` (float32 chain only): the direct kernels' own summation structure instead (``_conv_chain``)."""
     B, H, W, C = x.shape
     N, Cw, k, _ = w.shape
     assert Cw == C and k in (1, 3)
     x = _cast(x, dtype, absval); w = _cast(w, dtype, absval)
     p = k // 2
     xp = torch.nn.functional.pad(x, (0, 0, p, p, p, p)) if p else x
+    if chain_kc is not None and dtype == F32 and not absval:
+        return _conv_chain(xp, w, H, W, k, chain_kc, emu)
     y = None
     for ky in range(k):
         for kx in range(k):
@@ -86,10 +89,30 @@ def _conv_core(x, w, dtype, absval, emu):
     return y.view(B, H, W, N)
 
 
-def conv(x, w, bias=None, relu=False, emu=None):
-    """y = conv(x, w) (+ bias) (ReLU), 1x1 or 3x3 pad 1."""
+def _conv_chain(xp, w, H, W, k, kc, emu):
+    """The float32 chain of the direct kernels (csrc/conv_igemm.hip: conv_igemm, conv_dma, conv_ws, fire_expand): ONE fp32 accumulator
+    per output over input-channel chunks of ``kc``, inside a chunk over the taps, inside a tap over matrix-core steps of 4 channels
+    (the 4 products of a step as one fp32 dot).  On a 3x3 layer one chain of 9 C / 4 additions errs 2-5x more than nine chains of
+    C / 4 summed afterwards (the per-tap matmuls of the plain chain); on a 1x1 layer the two differ only where the matmul library picks
+    another algorithm than the sequential one (it does for a few pixels: 3x3 grids at batch 1).  xp: the padded float32 input;
+    ``emu``: the degraded products."""
+    B, C = xp.shape[0], xp.shape[3]
+    N = w.shape[0]
+
+    acc = torch.zeros(B * H * W, N, dtype=F32, device=xp.device)
+    for c0 in range(0, C, kc):
+        for ky in range(k):
+            for kx in range(k):
+                for c in range(c0, min(c0 + kc, C), 4):
+                    acc = acc + _mm(xp[:, ky:ky + H, kx:kx + W, c:c + 4].reshape(-1, min(4, C - c)), w[:, c:c + 4, ky, kx].t(), F32, emu)
+    return acc.view(B, H, W, N)
+
+
+def conv(x, w, bias=None, relu=False, emu=None, chain_kc=None):
+    """y = conv(x, w) (+ bias) (ReLU), 1x1 or 3x3 pad 1.  ``chain_kc``: b32 restates the direct kernels' single accumulator
+    (``_conv_core``); ref64 and M do not depend on it."""
     def f(dtype, absval, e):
-        y = _conv_core(x, w, dtype, absval, e)
+        y = _conv_core(x, w, dtype, absval, e, chain_kc)
         if bias is not None:
             y = y + _cast(bias, dtype, absval)
         return y.clamp_min(0) if (relu and not absval) else y
@@ -288,7 +311,7 @@ def _pool_max(x):
     """MaxPool2d(3, 2, ceil_mode=True) values of an NHWC tensor (no padding on the leading edges; ceil windows are clipped)."""
     B, H, W, C = x.shape
     Ho, Wo = pool_out_size(H, W)
-    xp = torch.nn.functional.pad(x, (0, 0, 0, 2 * Ho + 1 - H, 0, 2 * Wo + 1 - W), value=float('-inf'))
+    xp = torch.nn.functional.pad(x, (0, 0, 0, 2 * Wo + 1 - W, 0, 2 * Ho + 1 - H), value=float('-inf'))
     y = None
     for ky in range(3):
         for kx in range(3):
@@ -355,9 +378,10 @@ def stem_wgrad_pooled(dpool, codes, img, N, k, emu=None):
 
 # ---- fused forward launches ----
 
-def fire_expand(x, w1, b1, w3, b3, emu=None):
-    """cat(relu(expand1x1(x)), relu(expand3x3(x)))."""
-    return cat([conv(x, w1, b1, relu=True, emu=emu), conv(x, w3, b3, relu=True, emu=emu)])
+def fire_expand(x, w1, b1, w3, b3, emu=None, chain_kc=None):
+    """cat(relu(expand1x1(x)), relu(expand3x3(x))).  ``chain_kc``: the one-launch direct form (``ops.fire_expand``), which accumulates
+    like the direct kernels (its 1x1 half runs the centre tap only)."""
+    return cat([conv(x, w1, b1, relu=True, emu=emu, chain_kc=chain_kc), conv(x, w3, b3, relu=True, emu=emu, chain_kc=chain_kc)])
 
 
 def fire_bridge(x, w1, b1, w3, b3, wsq, bsq, emu=None):

@@ -3,7 +3,10 @@
 or fusion that changes a plan fails here until it has a float64 case.  The plain references of tests/fp64_ref.py are checked against
 torch's own convolution, pooling and autograd on small shapes; the loss reference against float64 autograd, its bound against the
 float32 oracle chain (attainability), and each wrong branch convention against the loss edge cases (teeth); the clip + SGD reference
-against torch.optim.SGD + clip_grad_norm_, and the norm bar against a norm that drops the tail or a part."""
+against torch.optim.SGD + clip_grad_norm_, and the norm bar against a norm that drops the tail or a part.
+The off-benchmark sweep (tests/test_fp64_offbench_gpu.py) is held the same way: its two lists equal the planners' output at its points
+(the forced-forms point recomputed under the same swap of look-ups), and every kernel name the planners produce over a grid of batches
+and input sizes has a float64 case in one of the lists."""
 import os
 import sys
 
@@ -15,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fp64_ref as R  # noqa: E402
 import test_fp64_launches_gpu as L  # noqa: E402
 import test_fp64_loss_gpu as LG  # noqa: E402
+import test_fp64_offbench_gpu as OB  # noqa: E402
 import test_fp64_optim_gpu as OG  # noqa: E402
 
 # launches outside the float64 sweep, each with the test that covers it
@@ -52,6 +56,107 @@ def test_every_case_family_has_a_bar():
         assert f == 'maxpool_fwd' or f == 'wgrad_reduce_batched' or f in L.FAMILIES or f in L.LOSS_FAMILIES, c
 
 
+def offbench_entries(points):
+    from squeezedet_pytorch_amd import plan
+    out = []
+    for arch, batch, size in points:
+        for planner in (plan.inference_launch_plan, plan.training_launch_plan):
+            for kernel, tag in planner(arch, batch, size):
+                e = (arch, batch, size, kernel, tag)
+                if e not in out:
+                    out.append(e)
+    return out
+
+
+def _same_as_plans(cases, entries, what):
+    assert len(set(cases)) == len(cases), 'duplicate cases'
+    missing = [e for e in entries if e not in set(cases) and e[3] not in ALLOWED]
+    assert not missing, f'launches of {what} without a float64 case: {missing}'
+    stale = [c for c in cases if c not in entries]
+    assert not stale, f'cases the plans of {what} no longer launch: {stale}'
+    assert all(c[3] not in ALLOWED for c in cases)
+
+
+def test_every_offbench_plan_entry_has_a_case():
+    assert OB.POINTS == [('squeezedet', 1, (192, 624)), ('squeezedetplus', 1, (192, 624)), ('squeezedet', 3, (70, 100)),
+                         ('squeezedetplus', 3, (70, 100)), ('squeezedet', 2, (186, 310)), ('squeezedet', 1, (48, 48))]
+    _same_as_plans(OB.OFFBENCH, offbench_entries(OB.POINTS), 'the off-benchmark points')
+
+
+def test_every_forced_form_entry_has_a_case():
+    """The forced-forms point, recomputed under the same swap of look-ups the GPU test runs with; the swap reaches the forms it is for,
+    and leaves the look-ups and the schedule memo as it found them."""
+    from squeezedet_pytorch_amd import ops, plan
+    assert OB.FORCED_POINT == ('squeezedet', 3, (70, 100))
+    before = (ops.choose_fire_bridge_cfg, ops.choose_fire_pool_bridge, ops.choose_wino_cfg)
+    plain = plan.training_launch_plan(*OB.FORCED_POINT)
+    with OB.forced_forms():
+        entries = offbench_entries([OB.FORCED_POINT])
+    assert (ops.choose_fire_bridge_cfg, ops.choose_fire_pool_bridge, ops.choose_wino_cfg) == before
+    assert plan.training_launch_plan(*OB.FORCED_POINT) == plain
+    _same_as_plans(OB.FORCED, entries, 'the forced-forms point')
+    fams = {L.family(c[3]) for c in OB.FORCED}
+    assert {'conv_wino_us', 'conv_wino_vs', 'fire_bridge', 'fire_bridge_save', 'fire_pool_bridge', 'fire_pool_bridge_save'} <= fams
+
+
+def test_every_offbench_case_family_has_a_bar():
+    known = set(L.FAMILIES) | set(L.LOSS_FAMILIES) | set(OB.NEW_FAMILIES) | {'maxpool_fwd', 'wgrad_reduce_batched'}
+    for c in OB.OFFBENCH + OB.FORCED:
+        assert L.family(c[3]) in known, c
+    # the new families launch at the point their teeth are taken from
+    for f in OB.NEW_FAMILIES:
+        assert f not in L.FAMILIES and any(c[:3] == OB.TEETH_POINT and L.family(c[3]) == f for c in OB.OFFBENCH), f
+
+
+# the grid of the reachability check: both architectures at these batches and input sizes
+GRID_BATCHES = (1, 2, 3, 4, 5, 8, 16, 20, 32, 64)
+GRID_SIZES = ((384, 1248), (192, 624), (256, 832), (512, 1664), (64, 96), (70, 100))
+
+
+def test_every_reachable_kernel_has_a_case():
+    """Every kernel name either planner produces over the grid has a float64 case, in the benchmarked sweep or the off-benchmark one.
+    The only exceptions are the six tilings the planners name above about 2.4 M pixels alone; they are compiled configurations, which
+    test_every_compiled_tiling runs.  A tuning row or a heuristic change that makes another instance reachable fails here until it
+    has a case."""
+    from squeezedet_pytorch_amd import ops, plan
+    names = set()
+    for arch in ('squeezedet', 'squeezedetplus'):
+        for batch in GRID_BATCHES:
+            for size in GRID_SIZES:
+                for planner in (plan.inference_launch_plan, plan.training_launch_plan):
+                    names |= {kernel for kernel, _tag in planner(arch, batch, size)}
+    covered = {c[2] for c in L.CASES} | {c[3] for c in OB.OFFBENCH} | set(ALLOWED)
+    large = ['conv_dma<1,16,2,4,4>', 'conv_dma<1,32,2,1,4>', 'conv_dma<1,32,2,2,4>', 'conv_dma<9,16,2,2,4>', 'conv_dma<9,16,2,3,4>',
+             'conv_dma<9,16,2,4,4>']
+    assert OB.LARGE_PIXEL_TILINGS == large
+    assert not set(large) & covered, 'a large-pixel tiling has a case now: take it off the exception list'
+    missing = sorted(names - covered - set(large))
+    assert not missing, f'kernel instances the planners can name without a float64 case: {missing}'
+    compiled = {ops.cfg_kernel_name(cid) for cid, (taps, _kc, _px, _bn) in ops.cfg_table().items()
+                if ops.conv_cfg_ok(cid, OB.TILING_SHAPES[taps][0])}
+    assert set(large) <= compiled, sorted(set(large) - compiled)
+
+
+def test_wgrad_blocking_restates_the_launchers():
+    """L.wgrad_blocking against the host's own split rule: the launchers refuse S above their number of pixel blocks, so the blocks of the
+    restatement must be at least as many as the S ``tiles.wgrad_split`` hands out; and the tile forms at the widths of both models."""
+    from squeezedet_pytorch_amd import ops
+    assert L.wgrad_blocking('squeeze_bwd', 64, 16, 1) == (('px', 32), 1)
+    assert L.wgrad_blocking('conv_wgrad_group', 64, 16, 1) == (('px', 64), 1)           # tc 1: launch_wgrad_group<4, 1, 4>
+    assert L.wgrad_blocking('conv_wgrad_group', 192, 48, 1) == (('px', 32), 1)          # tc 3
+    assert L.wgrad_blocking('conv_wgrad_group', 256, 384, 1) == (('px', 32), 1)         # tc 8
+    assert L.wgrad_blocking('conv_wgrad', 384, 512, 1) == (('px', 32), 1)               # launch_wgrad<1, 4, 8, 2>
+    assert L.wgrad_blocking('conv_wgrad', 16, 16, 1) == (('px', 128), 1)                # launch_wgrad<1, 1, 1, 8>
+    assert L.wgrad_blocking('conv_wgrad', 32, 32, 1) == (('px', 64), 1)                 # launch_wgrad<1, 2, 2, 4>
+    assert L.wgrad_blocking('conv_wgrad_wino', 72, 768, 9) == ('tile', 16)
+    assert L.wgrad_blocking('conv_wgrad_wino_group', 64, 16, 9) == ('tile', 16)
+    for B, H, W in ((1, 3, 3), (3, 4, 6), (2, 11, 19), (1, 12, 39), (20, 24, 78)):
+        for N, C in ((192, 128), (384, 512), (288, 256), (16, 16), (96, 64)):
+            S, _ = ops.wgrad_split(N, C, 1, B, H, W)
+            (_px, P), _step = L.wgrad_blocking('conv_wgrad', N, C, 1)
+            assert S <= -(-(B * H * W) // P), (B, H, W, N, C, S, P)
+
+
 def _rand(*shape, seed, relu=False):
     g = torch.Generator().manual_seed(seed)
     t = torch.randn(*shape, generator=g, dtype=torch.float64)
@@ -78,6 +183,52 @@ def test_reference_conv_dgrad_wgrad(k):
     assert torch.allclose(R.conv(_nhwc(dy), R.dgrad_weight(w)).ref64, _nhwc(xg.grad), atol=1e-12)
     dW, db = R.wgrad(_nhwc(dy), _nhwc(x), k * k)
     assert torch.allclose(dW.ref64, wg.grad, atol=1e-12) and torch.allclose(db.ref64, bg.grad, atol=1e-12)
+
+
+def test_reference_fire_expand():
+    """R.fire_expand (the reference of the ``ops.fire_expand`` wrapper) against torch's own conv2d in float64: relu(expand1x1) next to
+    relu(expand3x3) in the channel window, magnitude above |ref64|, the float32 chain inside bar L."""
+    x = _rand(2, 6, 5, 7, seed=41, relu=True)
+    w1, b1 = _rand(8, 6, 1, 1, seed=42), _rand(8, seed=43)
+    w3, b3 = _rand(8, 6, 3, 3, seed=44), _rand(8, seed=45)
+    want = torch.cat([F.relu(F.conv2d(x, w1, b1)), F.relu(F.conv2d(x, w3, b3, padding=1))], 1)
+    r = R.fire_expand(_nhwc(x), w1, b1, w3, b3)
+    assert tuple(r.ref64.shape) == (2, 5, 7, 16)
+    assert torch.allclose(r.ref64, _nhwc(want), atol=1e-12)
+    assert (r.M >= r.ref64.abs() - 1e-12).all()
+    assert ((r.b32.double() - r.ref64).abs() <= R.BAR_L * r.M).all()
+    assert R.bars(r.b32, r, 'act', 2)['p_ok']
+    for emu in ('bf16', 'split3'):
+        assert not R.bars(R.fire_expand(_nhwc(x), w1, b1, w3, b3, emu=emu).b32, r, 'act', 2)['p_ok'], emu
+
+
+def test_reference_direct3x3_chain():
+    """The restated float32 chain of the direct kernels (one accumulator over chunk x tap x 4-channel step) is the same
+    convolution: inside bar L of float64 and bar P of itself; ref64 and M are those of the plain reference; and the plain per-tap chain
+    is the more accurate one on a long reduction (why the restatement exists), so a kernel of that structure cannot be held to it."""
+    x = _rand(1, 5, 7, 200, seed=61, relu=True).float()
+    w = (_rand(12, 200, 3, 3, seed=62) * (2.0 / 1800) ** 0.5).float()
+    b = _rand(12, seed=63).float()
+    plain, chain = R.conv(x, w, b, relu=True), R.conv(x, w, b, relu=True, chain_kc=16)
+    assert torch.equal(plain.ref64, chain.ref64) and torch.equal(plain.M, chain.M)
+    assert ((chain.b32.double() - chain.ref64).abs() <= R.BAR_L * chain.M).all()
+    assert R.bars(chain.b32, chain, 'act', 2)['p_ok']
+    e_plain = (plain.b32.double() - plain.ref64).pow(2).mean().sqrt()
+    e_chain = (chain.b32.double() - chain.ref64).pow(2).mean().sqrt()
+    assert e_chain > e_plain
+    for emu in ('bf16', 'split3'):
+        assert not R.bars(R.conv(x, w, b, relu=True, emu=emu, chain_kc=16).b32, chain, 'act', 2)['p_ok'], emu
+    # a 1x1 layer has one tap: the chain is the plain one up to what the matmul does inside a step
+    w1 = w[:, :, 1:2, 1:2].contiguous()
+    assert R.bars(R.conv(x, w1, b, chain_kc=16).b32, R.conv(x, w1, b), 'act', 2)['p_ok']
+
+
+@pytest.mark.parametrize('H,W', [(35, 50), (50, 35), (12, 12), (11, 19)])
+def test_reference_pool_at_mixed_parity(H, W):
+    """R.maxpool_exact against torch's ceil-mode pool where rows and columns differ in parity (the padding of each axis is its own)."""
+    x = _rand(2, 3, H, W, seed=64)
+    want = F.max_pool2d(x, 3, 2, ceil_mode=True)
+    assert torch.equal(R.maxpool_exact(_nhwc(x)), _nhwc(want))
 
 
 @pytest.mark.parametrize('k,H,W', [(3, 13, 18), (7, 14, 17)])

@@ -1,5 +1,6 @@
 """GPU tier: every GEMM-type launch of the four benchmarked steps (inference and training of SqueezeDet at bs=20 and SqueezeDet+ at
-bs=16, 384x1248, shipped tuning table) held to fp32 accuracy against a float64 reference, element by element.
+bs=16, 384x1248, shipped tuning table) held to fp32 accuracy against a float64 reference, element by element.  (The harness takes any
+batch and input size: tests/test_fp64_offbench_gpu.py runs it away from the benchmark.)
 
 Each case is one distinct (arch, batch, kernel, shape tag) entry of ``plan.inference_launch_plan`` / ``plan.training_launch_plan``
 (``CASES``; tests/test_fp64_coverage.py keeps the list equal to the plans).  The cases run inside the real step: the model is built
@@ -13,6 +14,9 @@ Two bars per output (fp64_ref.bars):
 * L: |got - ref64| <= 2^-18 * M for every element (exact where M = 0): no dropped, duplicated or misplaced term anywhere;
 * P: per 64-channel block rms(err) <= k * max(rms(err32), 2^-24 rms(ref64)), per tensor max|err| <= 2k * max(max|err32|, ...), with
   err32 the plain fp32 chain's error: k = 2 for the direct-GEMM families, 4 for the Winograd ones (bridges included).
+  The direct kernels (conv_igemm, conv_dma, conv_ws, fire_expand) keep ONE accumulator per output over chunk x tap x 4-channel step: their
+  plain chain is restated that way (fp64_ref._conv_chain), as the weight gradients' is.  A library matmul per tap, summed afterwards,
+  is 2-5x more accurate than that on a 3x3 layer, and picks other algorithms for a few pixels (3x3 grids, batch 1).
   Weight and bias gradients sum 37k-599k pixels: there the plain chain is restated as the kernels' own algorithm
   (fp64_ref.wgrad_split_k: the kernel's pixel blocks, its S slabs accumulated in order, the shipped
   slab reduction) -- a whole-axis fp32 GEMM is 2-20x less accurate than the kernels and could not tell a 3-product bf16 split from
@@ -170,11 +174,27 @@ FAMILIES = ['conv_ws', 'conv_dma', 'conv_wino', 'conv_wino_us', 'conv_wino_sk', 
 LOSS_FAMILIES = ['loss_fwd', 'loss_bwd']
 
 
-# how each weight-gradient kernel cuts the pixel axis into the blocks its split-K slabs take in turn (csrc/wgrad.hip, wino_wgrad.hip), and
-# the pixels per fp32 accumulation: 1 for the direct form (its 16x16x4 matrix-core steps are not taken as one exact 4-product sum),
-# 4 output tiles (16 pixels) for the Winograd form
-WGRAD_BLOCKING = {'conv_wgrad': (('px', 128), 1), 'conv_wgrad_group': (('px', 128), 1), 'squeeze_bwd': (('px', 32), 1),
-                  'conv_wgrad_wino': ('tile', 16), 'conv_wgrad_wino_group': ('tile', 16)}
+def wgrad_blocking(fam, N, C, taps):
+    """How the weight-gradient kernel that ran a (N, C, taps) layer cuts the pixel axis into the blocks its split-K slabs take in turn, and the
+    pixels per fp32 accumulation -> (fp64_ref blocking, step).  Restated from the launchers (csrc/wgrad.hip sqd_conv_wgrad,
+    sqd_conv_wgrad_group, sqd_squeeze_bwd; csrc/wino_wgrad.hip): the direct forms take runs of 16 * TH consecutive pixels, TH chosen
+    from the out- / in-channel tiles (TN, TC) of the layer; the Winograd forms take 4x16-pixel groups whatever their channel tile
+    (tc 1 or 2).  Step: 1 for the direct forms (their 16x16x4 matrix-core steps are not taken as one exact 4-product sum), 4 output
+    tiles (16 pixels) for the Winograd form."""
+    if 'wino' in fam:
+        return 'tile', 16
+    if fam == 'squeeze_bwd':                                    # launch_wgrad<1, TN, TC, 2, true>
+        return ('px', 32), 1
+    if fam == 'conv_wgrad_group':                               # launch_wgrad_group<4, tc, tc == 1 ? 4 : 2>
+        tc = 8 if C >= 256 else (4 if C >= 64 else -(-C // 16))
+        return ('px', 64 if tc == 1 else 32), 1
+    assert fam == 'conv_wgrad', fam
+    if taps == 9:                                               # launch_wgrad<9, ., ., 4>: 4x16-pixel tiles, image-major
+        return 'tile', 1
+    tn = 6 if 64 < N <= 96 else (4 if N >= 64 else -(-N // 16))
+    tc = 8 if C >= 256 else (4 if C >= 64 else -(-C // 16))
+    th = 2 if tn + tc >= 6 else (4 if tn + tc >= 3 else 8)
+    return ('px', 16 * th), 1
 
 
 def family(kernel):
@@ -190,8 +210,9 @@ def k_of(kernel):
 class _Harness:
     """Wraps the ``ops`` entry points (and the slab reduction) for one step; collects per-(kernel, tag) output checks."""
 
-    def __init__(self, base, arch, batch, timer):
+    def __init__(self, base, arch, batch, timer, teeth_for=None):
         self.base, self.arch, self.batch, self.timer = base, arch, batch, timer
+        self.teeth_for = teeth_for     # the families whose first launch also runs the degraded emulations (None: every family)
         self.rows = {}                 # (arch, batch, kernel, tag) -> [(output, bars dict)]
         self.teeth = {}                # family -> {emu: bars dict}
         self.pending = {}              # slab data_ptr -> (entry, dy, x, taps) until the slab reduction
@@ -212,6 +233,9 @@ class _Harness:
         for key, val in self.base._fused_plans.items():
             if key[0] == 'firebridge':
                 m[id(val[1])] = ('bridge',) + tuple(val[2])
+            elif key[0] == 'fused':
+                fire = self.base.features[key[1]]
+                m[id(val[1])] = ('expand', fire.expand1x1, fire.expand3x3)
         return m
 
     def _weights(self, plan):
@@ -236,9 +260,12 @@ class _Harness:
         for j, (name, got, ref_fn, kind) in enumerate(outs):
             r = ref_fn(None)
             rows.append((name, R.bars(got, r, kind, k)))
-            if j == 0 and fam not in self.teeth:
+            if j == 0 and fam not in self.teeth and self._wants_teeth(fam):
                 self.teeth[fam] = {emu: R.bars(ref_fn(emu).b32, r, kind, k) for emu in ('bf16', 'split3')}
             del r
+
+    def _wants_teeth(self, fam):
+        return self.teeth_for is None or fam in self.teeth_for
 
     def _wgrad_pending(self, entry, slab, dy, x, taps):
         """A weight-gradient launch wrote its slabs: keep its operands; the check runs after the reduction (``reduce``)."""
@@ -261,7 +288,8 @@ class _Harness:
         out = orig(x, x_coff, plan, y, y_coff, relu=relu, accumulate=accumulate, xmask=xmask, xmask_coff=xmask_coff, ymask=ymask,
                    ymask_coff=ymask_coff, ymul=ymul, ymul_coff=ymul_coff, drop=drop)
         got = y[..., y_coff:y_coff + plan.N]
-        self._check(self._entry(n0), [('y', got, lambda e: R.epilogue(R.conv(xw, w, b, emu=e), prev, yl, 1.0, ym, relu), 'act')])
+        kc = plan.kc                                      # b32 restates the direct kernels' single accumulator (fp64_ref._conv_chain)
+        self._check(self._entry(n0), [('y', got, lambda e: R.epilogue(R.conv(xw, w, b, emu=e, chain_kc=kc), prev, yl, 1.0, ym, relu), 'act')])
         return out
 
     def conv_wino(self, orig, x, x_coff, plan, y, y_coff, relu=False, accumulate=False, ymask=None, ymul=None, yscale=1.0, drop=None,
@@ -278,6 +306,16 @@ class _Harness:
                    drop_advance=drop_advance)
         got = y[..., y_coff:y_coff + plan.N]
         self._check(self._entry(n0), [('y', got, lambda e: R.epilogue(R.conv(xw, w, b, emu=e), prev, yl, yscale, ym, relu), 'act')])
+        return out
+
+    def fire_expand(self, orig, x, x_coff, fplan, y, y_coff):
+        kind, e1, e3 = self.plan_map[id(fplan)]
+        assert kind == 'expand'
+        ws = tuple(t.detach() for t in (e1.weight, e1.bias, e3.weight, e3.bias))
+        xw = x[..., x_coff:x_coff + fplan.C].clone()
+        n0 = len(self.timer.records)
+        out = orig(x, x_coff, fplan, y, y_coff)
+        self._check(self._entry(n0), [('y', y[..., y_coff:y_coff + 2 * fplan.E], lambda e: R.fire_expand(xw, *ws, emu=e, chain_kc=fplan.plan.kc), 'act')])
         return out
 
     def _bridge_weights(self, plan):
@@ -405,7 +443,7 @@ class _Harness:
         self._loss_rows(entry, outs)
         self.rows[entry].append(('nobj', dict(exact=nobj_exact, l_ok=nobj_exact, p_ok=nobj_exact, l_ratio=0.0, p_block=0.0,
                                                p_tensor=0.0, k=0)))
-        if 'loss_fwd' not in self.teeth:
+        if 'loss_fwd' not in self.teeth and self._wants_teeth('loss_fwd'):
             l16 = R.loss_bf16(p, g, a, input_size, num_classes, weights)[0]
             self.teeth['loss_fwd'] = {'bf16': R.bars(l16, ref['losses'], 'vec', 2)}
         return res
@@ -429,7 +467,7 @@ class _Harness:
         print(f'{entry[2]} {entry[3]}: {flips} anchors where float64 and float32 take different branches')
         self.rows[entry].append(('flips', dict(exact=flips <= 4, l_ok=flips <= 4, p_ok=True, l_ratio=0.0, p_block=0.0, p_tensor=0.0,
                                                 k=0, flips=flips)))
-        if 'loss_bwd' not in self.teeth:
+        if 'loss_bwd' not in self.teeth and self._wants_teeth('loss_bwd'):
             d16 = R.loss_bf16(p, g, a, input_size, num_classes, weights, gmean=gmean, coef=coef)[1 if gmean is not None else 2]
             self.teeth['loss_bwd'] = {'bf16': R.bars(d16, ref[name], 'dpred', 2)}
         return dpred
@@ -454,7 +492,7 @@ class _Harness:
             src, dy, x, taps_ = self.pending.pop(base_ptr + 4 * slab_off)
             assert taps_ == taps and tuple(dy.shape[3:]) == (N,) and x.shape[3] == C
             fam = family(src[2])
-            blocking, step = WGRAD_BLOCKING[fam]
+            blocking, step = wgrad_blocking(fam, N, C, taps)
             kk = k_of(src[2])
             dW, db = R.wgrad(dy, x, taps)
             w32, b32 = R.wgrad_split_k(dy, x, taps, S, blocking, step)
@@ -473,34 +511,35 @@ class _Harness:
             checks = [(f'dW C{C} N{N} S{S}', bw), (f'db N{N} S{S}', R.bars(gb, db, 'vec', kk))]
             for e in (src, entry):
                 self.rows.setdefault(e, []).extend(checks)
-            if fam not in self.teeth:
+            if fam not in self.teeth and self._wants_teeth(fam):
                 self.teeth[fam] = {emu: R.bars(R.wgrad_split_k(dy, x, taps, S, blocking, step, emu)[0], dW, 'wgrad', kk)
                                    for emu in ('bf16', 'split3')}
             del dy, x, dW, db
         return res
 
 
-_NAMES = ('conv', 'conv_wino', 'fire_bridge', 'fire_pool_bridge', 'stem_pool', 'stem_pool_squeeze', 'maxpool', 'maxpool_bwd',
+_NAMES = ('conv', 'conv_wino', 'fire_expand', 'fire_bridge', 'fire_pool_bridge', 'stem_pool', 'stem_pool_squeeze', 'maxpool', 'maxpool_bwd',
           'conv_wgrad', 'conv_wgrad_group', 'conv_wgrad_wino_group', 'squeeze_bwd', 'stem_wgrad_pooled',
           'loss_fwd', 'loss_mean_fwd', 'loss_bwd', 'loss_mean_bwd')
 
 
-def _run_step(arch, batch, mode):
-    """One benchmarked step (the same seeds as bench.py) with every GEMM-type launch checked.  -> (harness, [(kernel, tag)] recorded)."""
+def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None):
+    """One step at ``size`` (the benchmarked one by default; the same seeds as bench.py) with every GEMM-type launch checked.
+    -> (harness, [(kernel, tag)] recorded)."""
     from squeezedet_pytorch_amd import ops, plans as plans_mod
     from squeezedet_pytorch_amd.detector import Detector
     from squeezedet_pytorch_amd.model import SqueezeDet, SqueezeDetWithLoss
     torch.manual_seed(0)
-    cfg = sqd.make_cfg(arch=arch, device='cuda')
+    cfg = sqd.make_cfg(arch=arch, input_size=size, device='cuda')
     sd = synthetic.make_state_dict(arch, seed=1234)
-    x = synthetic.make_images(batch, INPUT, seed=0).cuda()
+    x = synthetic.make_images(batch, size, seed=0).cuda()
     if mode == 'train':
         m = SqueezeDetWithLoss(cfg)
         m.load_state_dict(sd)
         m = m.cuda().train()
         base = m.base
         base.dropout_prob = 0.0          # the planned dropout epilogues with an all-keep mask
-        batch_d = {'image': x, 'gt': synthetic.make_gt(batch, cfg.anchors, INPUT, seed=1).cuda()}
+        batch_d = {'image': x, 'gt': synthetic.make_gt(batch, cfg.anchors, size, seed=gt_seed).cuda()}
 
         def step():                      # bench.py's form (trainer.make_train_step): the mean and its backward in the loss launches
             loss, _ = m.forward_mean(batch_d)
@@ -517,7 +556,7 @@ def _run_step(arch, batch, mode):
     step()                                # plans are packed here, outside the checked pass
     torch.cuda.synchronize()
     timer = ops.KernelTimer()
-    h = _Harness(base, arch, batch, timer)
+    h = _Harness(base, arch, batch, timer, teeth_for)
     saved = {n: getattr(ops, n) for n in _NAMES}
     red = plans_mod.WgradBatch.reduce
     for n in _NAMES:
@@ -539,13 +578,15 @@ def _run_step(arch, batch, mode):
 _STATE = {}
 
 
-def _step_results(arch, batch):
-    """{(arch, batch, kernel, tag): rows} of the inference and the training step of ``arch`` (run once per module; a failure is kept and
-    raised again for every case of that arch instead of re-running the steps)."""
-    key = (arch, batch)
+def _step_results(arch, batch, size=INPUT, swap=None, gt_seed=1, teeth_for=None):
+    """{(arch, batch, kernel, tag): rows} of the inference and the training step of ``arch`` at ``size`` (run once per process; a failure
+    is kept and raised again for every case of that point instead of re-running the steps).  ``swap``: a context manager factory that
+    replaces look-ups of ``ops`` for the two steps and the plans they are compared with (forced kernel forms); ``gt_seed``: the
+    ground-truth seed of the training step; ``teeth_for``: the families that also run the degraded emulations (None: all)."""
+    key = (arch, batch, tuple(size)) if swap is None else (arch, batch, tuple(size), swap.__name__)
     if key not in _STATE:
         try:
-            _STATE[key] = _run_both(arch, batch)
+            _STATE[key] = _run_both(arch, batch, tuple(size), swap, gt_seed, teeth_for)
         except Exception as exc:            # noqa: BLE001 -- re-raised below, and by every later case of this arch
             _STATE[key] = exc
     res = _STATE[key]
@@ -554,12 +595,15 @@ def _step_results(arch, batch):
     return res
 
 
-def _run_both(arch, batch):
+def _run_both(arch, batch, size=INPUT, swap=None, gt_seed=1, teeth_for=None):
+    if swap is not None:
+        with swap():
+            return _run_both(arch, batch, size, None, gt_seed, teeth_for)
     from squeezedet_pytorch_amd import plan
     rows, teeth = {}, {}
     for mode, planner in (('infer', plan.inference_launch_plan), ('train', plan.training_launch_plan)):
-        h, got = _run_step(arch, batch, mode)
-        want = planner(arch, batch, INPUT)
+        h, got = _run_step(arch, batch, mode, size, gt_seed, teeth_for)
+        want = planner(arch, batch, size)
         assert got == want, [(i, a, b) for i, (a, b) in enumerate(zip(got, want)) if a != b][:4] + [len(got), len(want)]
         for e, r in h.rows.items():
             rows.setdefault(e, []).extend(r)
