@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from . import ops
 from .plan import conv3x3_cfg
+from .plans import PlanCache, version
 from .synthetic import layer_table, convdet_in_channels
 
 
@@ -58,7 +59,7 @@ class _ConvParams(nn.Module):
         k = self.kernel_size[0]
         wc = ops.choose_wino_cfg(self.in_channels, self.out_channels, npix) if k == 3 else None
         cfg_id = ('w', wc) if wc is not None else ('d', ops.choose_cfg(k * k, self.in_channels, self.out_channels, npix))
-        ver = (cfg_id, self.weight._version, self.weight.data_ptr(), self.bias._version, self.bias.data_ptr())
+        ver = (cfg_id,) + version((self,))
         if self._own_plan is None or self._own_plan[0] != ver:
             plan = ops.WinoPlan(self.weight, self.bias, wc) if wc is not None else ops.ConvPlan(self.weight, self.bias, cfg_id[1])
             self._own_plan = (ver, plan)
@@ -107,7 +108,7 @@ class _PaddedConvDet:
 
     def sync(self):
         m, N = self.src, self.true_channels
-        ver = (m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr())
+        ver = version((m,))
         if ver != self._ver:
             self.weight[:N].copy_(m.weight.detach())
             self.bias[:N].copy_(m.bias.detach())
@@ -174,9 +175,7 @@ class SqueezeDetBase(nn.Module):
         self.convdet = _ConvParams(convdet_in_channels(cfg.arch), cfg.anchors_per_grid * (cfg.num_classes + 5), 3, padding=1)
         self._convdet_pad = None                  # _PaddedConvDet when the width is padded (convdet_exec)
         self._convdet_slab = None                 # its weight-gradient slab workspace
-        self._plans = {}
-        self._fused_plans = {}
-        self._wino_plans = {}
+        self.plan_cache = PlanCache()             # every packed / transformed weight copy the executors launch with
         self._wgrad_batches = {}
         self.last_grad_flat = None                # flat gradient buffer of the latest backward (every .grad is a view of it)
         self.grad_sync = None                     # trainer.GradientExchange when data parallel (attach_data_parallel)
@@ -189,7 +188,6 @@ class SqueezeDetBase(nn.Module):
         # to the two separate kernels (0.174 vs 0.18 ms) -- both are bound by the 9x L2 read amplification of the window gather
         self.fuse_pool_squeeze = False
         self.fuse_stem_squeeze = True             # inference forward: the first Fire's squeeze inside the stem launch (ops.stem_pool_squeeze)
-        self._pack_table_keepalive = None
         self._forced_drop_mask = None       # tests: NCHW mask (already scaled by 1/(1-p)) instead of RNG
         # counter-based dropout (ops.DropState): applied in the last Fire's expand epilogues, its step advanced by ConvDet's launch,
         # no mask tensor and no torch RNG kernel in the step.  fused_dropout = False draws the mask as a tensor (stand-alone kernel)
@@ -227,96 +225,54 @@ class SqueezeDetBase(nn.Module):
             ws = self._convdet_slab = torch.empty(numel, device=self.convdet.weight.device, dtype=torch.float32)
         return ws
 
-    # ---- packed-weight cache ----
+    # ---- packed-weight cache (plans.PlanCache: the entry keeps the modules, staleness and refresh are decided there) ----
     def plan(self, name, mod, cfg_id, direction='fwd'):
-        key = (name, cfg_id, direction)
-        ver = (mod.weight._version, mod.weight.data_ptr(), mod.bias._version, mod.bias.data_ptr())
-        hit = self._plans.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        p = ops.ConvPlan(mod.weight, mod.bias, cfg_id, dgrad=(direction != 'fwd'))
-        self._plans[key] = (ver, p)
-        return p
+        return self.plan_cache.get('conv', (name, cfg_id), (mod,),
+                                   lambda: ops.ConvPlan(mod.weight, mod.bias, cfg_id, dgrad=(direction != 'fwd')), direction)
+
+    def wino_plan(self, name, mod, cfg_id, direction='fwd'):
+        """Transformed-weight cache of the Winograd 3x3 kernel (ops.WinoPlan), re-transformed in place when the parameter
+        changed."""
+        return self.plan_cache.get('wino', (name, cfg_id), (mod,),
+                                   lambda: ops.WinoPlan(mod.weight, mod.bias, cfg_id, dgrad=(direction != 'fwd')), direction)
 
     def fused_expand_plan(self, idx, fire, cfg_id):
         """Packed weights of ``fire``'s expand pair for the one-launch fused expand (inference forward).  Rebuilt when
         either module's parameters change; not part of ``refresh_plans`` (training keeps the two separate kernels, whose
         per-layer activations and packed weights the backward needs anyway)."""
-        key = ('fused', idx, cfg_id)
-        mods = (fire.expand1x1, fire.expand3x3)
-        ver = tuple(v for m in mods for v in (m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr()))
-        hit = self._fused_plans.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        p = ops.FusedExpandPlan(fire.expand1x1.weight, fire.expand1x1.bias, fire.expand3x3.weight, fire.expand3x3.bias, cfg_id)
-        self._fused_plans[key] = (ver, p)
-        return p
+        e1, e3 = fire.expand1x1, fire.expand3x3
+        return self.plan_cache.get('fused_expand', (idx, cfg_id), (e1, e3),
+                                   lambda: ops.FusedExpandPlan(e1.weight, e1.bias, e3.weight, e3.bias, cfg_id))
 
     def fire_wino_plan(self, idx, fire, cfg_id):
         """Packed weights of ``fire``'s expand pair for the one-launch Winograd form (inference forward); rebuilt when either
         module's parameters change."""
-        key = ('firewino', idx, cfg_id)
-        mods = (fire.expand1x1, fire.expand3x3)
-        ver = tuple(v for m in mods for v in (m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr()))
-        hit = self._fused_plans.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        p = ops.FireWinoPlan(fire.expand1x1.weight, fire.expand1x1.bias, fire.expand3x3.weight, fire.expand3x3.bias, cfg_id)
-        self._fused_plans[key] = (ver, p)
-        return p
+        e1, e3 = fire.expand1x1, fire.expand3x3
+        return self.plan_cache.get('fire_wino', (idx, cfg_id), (e1, e3),
+                                   lambda: ops.FireWinoPlan(e1.weight, e1.bias, e3.weight, e3.bias, cfg_id))
 
     def fire_bridge_plan(self, idx, fire, nxt, cfg_id, pooled=False):
         """Operands of the one-launch form of ``fire``'s expand pair + ``nxt``'s squeeze (ops.fire_bridge / ops.fire_pool_bridge);
         refreshed in place when any of the three modules' parameters change (``refresh_plans`` does all bridges with two launches)."""
-        key = ('firebridge', idx, cfg_id, pooled)
-        mods = (fire.expand1x1, fire.expand3x3, nxt.squeeze)
-        hit = self._fused_plans.get(key)
-        if hit is not None:
-            if hit[0] != self._bridge_version(mods):
-                self._refresh_bridge_plans([key])
-            return self._fused_plans[key][1]
-        p = ops.FireBridgePlan(fire.expand1x1.weight, fire.expand1x1.bias, fire.expand3x3.weight, fire.expand3x3.bias,
-                               nxt.squeeze.weight, nxt.squeeze.bias, cfg_id, pooled=pooled)
-        self._fused_plans[key] = (self._bridge_version(mods), p, mods)
-        return p
+        e1, e3, sq = fire.expand1x1, fire.expand3x3, nxt.squeeze
+        return self.plan_cache.get('bridge', (idx, cfg_id, pooled), (e1, e3, sq),
+                                   lambda: ops.FireBridgePlan(e1.weight, e1.bias, e3.weight, e3.bias, sq.weight, sq.bias, cfg_id, pooled=pooled))
 
-    @staticmethod
-    def _bridge_version(mods):
-        return tuple(v for m in mods for v in (m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr()))
+    # Read-only views of ``plan_cache`` in the shapes of the three dictionaries it replaced, for harnesses and tools written against
+    # those.  Derived on every read: they hold no state, and nothing in the package reads them.
+    @property
+    def _plans(self):                              # (name, cfg, direction) -> (version, plan)
+        return {e.key + (e.direction,): (e.version, e.plan) for e in self.plan_cache.entries() if e.kind == 'conv'}
 
-    def _refresh_bridge_plans(self, keys=None):
-        """Every cached Fire-bridge plan (or just ``keys``) whose parameters changed: operands rewritten in place, two launches."""
-        from . import plans as _plans
-        stale = []
-        for key, val in self._fused_plans.items():
-            if key[0] != 'firebridge' or (keys is not None and key not in keys):
-                continue
-            ver, plan, mods = val
-            now = self._bridge_version(mods)
-            if now != ver:
-                stale.append((key, now, plan, mods))
-        if not stale:
-            return
-        tables = _plans.refresh_bridge_plans([(plan, m[0].weight.detach(), m[0].bias.detach(), m[1].weight.detach(), m[1].bias.detach(),
-                                              m[2].weight.detach(), m[2].bias.detach()) for _k, _n, plan, m in stale])
-        self._pack_table_keepalive = (self._pack_table_keepalive or [])[-6:] + [tables]
-        for key, now, plan, mods in stale:
-            self._fused_plans[key] = (now, plan, mods)
+    @property
+    def _wino_plans(self):                         # the same, of the Winograd plans
+        return {e.key + (e.direction,): (e.version, e.plan) for e in self.plan_cache.entries() if e.kind == 'wino'}
 
-    def wino_plan(self, name, mod, cfg_id, direction='fwd'):
-        """Transformed-weight cache of the Winograd 3x3 kernel (ops.WinoPlan), re-transformed in place when the parameter
-        changed."""
-        key = (name, cfg_id, direction)
-        ver = (mod.weight._version, mod.weight.data_ptr(), mod.bias._version, mod.bias.data_ptr())
-        hit = self._wino_plans.get(key)
-        if hit is not None:
-            if hit[0] != ver:
-                hit[1].repack(mod.weight, mod.bias, dgrad=(direction != 'fwd'))
-                self._wino_plans[key] = (ver, hit[1])
-            return hit[1]
-        p = ops.WinoPlan(mod.weight, mod.bias, cfg_id, dgrad=(direction != 'fwd'))
-        self._wino_plans[key] = (ver, p)
-        return p
+    @property
+    def _fused_plans(self):     # ('fused' | 'firewino', idx, cfg) -> (version, plan);  ('firebridge', idx, cfg, pooled) -> (version, plan, mods)
+        tag = {'fused_expand': 'fused', 'fire_wino': 'firewino', 'bridge': 'firebridge'}
+        return {(tag[e.kind],) + e.key: (e.version, e.plan) + ((e.mods,) if e.kind == 'bridge' else ())
+                for e in self.plan_cache.entries() if e.kind in tag}
 
     def conv3x3(self, name, mod, x, x_coff, y, y_coff, relu, ymul=None):
         """Forward 3x3 convolution of ``mod``: the Winograd kernel where the measured table prefers it, else the direct
@@ -372,53 +328,16 @@ class SqueezeDetBase(nn.Module):
         """Drop every packed / transformed weight copy.  The caches notice optimizer steps, ``load_state_dict``, ``.to()``
         and any other in-place op on the parameters (version counter / data pointer); a write through ``param.data``
         (EMA, manual ``p.data.copy_``) moves neither -- call this after one."""
-        self._plans.clear(); self._fused_plans.clear(); self._wino_plans.clear()
+        self.plan_cache.clear()
         for m in self.modules():
             if isinstance(m, _ConvParams):
                 m._own_plan = m._own_pad = None
 
     def refresh_plans(self):
         """Re-pack every cached plan whose parameter changed since it was packed (after an optimizer step that
-        is all of them) with ONE batched kernel launch instead of one launch per plan."""
-        stale, dg, keys = [], [], []
-        for key, (ver, plan) in self._plans.items():
-            name, _cfg, direction = key
-            name = name.split('@')[0]                  # 'N.squeeze@pool': the same module packed for the fused pool+squeeze
-            mod = self.convdet_exec() if name == 'convdet' else getattr(self.features[int(name.split('.')[0])], name.split('.')[1]) \
-                if '.' in name else self.features[int(name)]
-            now = (mod.weight._version, mod.weight.data_ptr(), mod.bias._version, mod.bias.data_ptr())
-            if now != ver:
-                stale.append((plan, mod.weight)); dg.append(direction != 'fwd'); keys.append((key, now, mod))
-        self._refresh_wino_plans()
-        self._refresh_bridge_plans()
-        if not stale:
-            return
-        if self._pack_table_keepalive is not None and len(self._pack_table_keepalive) > 8:
-            self._pack_table_keepalive = self._pack_table_keepalive[-4:]
-        table = ops.repack_batched(stale, dg)
-        self._pack_table_keepalive = (self._pack_table_keepalive or []) + [table]     # keep the descriptor table alive until consumed
-        for (key, now, mod), (plan, _w) in zip(keys, stale):
-            if plan.bias is not None:
-                plan.bias = mod.bias.detach()
-            self._plans[key] = (now, plan)
-
-    def _refresh_wino_plans(self):
-        """The same for the Winograd plans: every transformed-weight copy whose parameter changed, one launch."""
-        stale, dg, keys = [], [], []
-        for key, (ver, plan) in self._wino_plans.items():
-            name, _cfg, direction = key
-            mod = self.convdet_exec() if name == 'convdet' else getattr(self.features[int(name.split('.')[0])], name.split('.')[1])
-            now = (mod.weight._version, mod.weight.data_ptr(), mod.bias._version, mod.bias.data_ptr())
-            if now != ver:
-                stale.append((plan, mod.weight)); dg.append(direction != 'fwd'); keys.append((key, now, mod))
-        if not stale:
-            return
-        table = ops.repack_wino_batched(stale, dg)
-        self._pack_table_keepalive = (self._pack_table_keepalive or [])[-6:] + [table]
-        for (key, now, mod), (plan, _w) in zip(keys, stale):
-            if plan.bias is not None:
-                plan.bias = mod.bias.detach()
-            self._wino_plans[key] = (now, plan)
+        is all of them) with ONE batched kernel launch per kind instead of one launch per plan."""
+        self.convdet_exec()                        # (a padded ConvDet's stand-in is brought up to date before versions are compared)
+        self.plan_cache.refresh()
 
     def wgrad_batch(self, entries_fn, key):
         """Cached ops.WgradBatch for one set of layer shapes (``entries_fn()`` builds the entry list on a miss)."""

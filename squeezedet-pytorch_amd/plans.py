@@ -1,7 +1,7 @@
 """Operand plans of the HIP kernels: packed / transformed weight copies (``ConvPlan``, ``WinoPlan``, ``FusedExpandPlan``,
-``FireWinoPlan``, ``FireBridgePlan``), their batched one-launch refresh after an optimizer step, and the split-K slab
-workspace of the weight gradients (``WgradBatch``).  Built once per (parameter, configuration), pointer-stable afterwards so
-hipGraph replays stay valid."""
+``FireWinoPlan``, ``FireBridgePlan``), their batched one-launch refresh after an optimizer step, the cache that decides when a copy
+is stale and how it is brought up to date (``PlanCache``), and the split-K slab workspace of the weight gradients (``WgradBatch``).
+Built once per (parameter, configuration), pointer-stable afterwards so hipGraph replays stay valid."""
 from __future__ import annotations
 
 import torch
@@ -44,6 +44,19 @@ class ConvPlan:
 _PACK_TABLES = {}
 
 
+def _pack_tables(what, dev, *rows):
+    """Device copies of the descriptor tables of one batched pack launch, cached by content.  A table only holds pointers and
+    shapes: after the first optimizer step it is the same every step, so repeated rows make no host-to-device copy (that is also
+    what keeps the training step hipGraph-capturable).  Bounded: the cache is emptied when it outgrows 16 launches' tables."""
+    key = (what, str(dev)) + tuple(tuple(tuple(r) for r in rs) for rs in rows)
+    tables = _PACK_TABLES.get(key)
+    if tables is None:
+        if len(_PACK_TABLES) > 16:
+            _PACK_TABLES.clear()
+        tables = _PACK_TABLES[key] = tuple(torch.tensor(rs, dtype=torch.int64).to(dev) for rs in rows)
+    return tables
+
+
 def repack_batched(plans_and_weights, is_dgrad):
     """Refresh many packed weight copies with ONE kernel launch.  plans_and_weights: [(ConvPlan, weight)],
     is_dgrad: parallel list of bools."""
@@ -56,15 +69,7 @@ def repack_batched(plans_and_weights, is_dgrad):
         rows.append([w.data_ptr(), plan.w.data_ptr(), w.shape[0], w.shape[1], plan.taps, plan.kc, plan.Npad, plan.w.shape[0],
                      int(dg), plan.w.numel()])
     dev = plans_and_weights[0][1].device
-    # the descriptor table only holds pointers and shapes: after the first optimizer step it is the same every step, so the
-    # device copy is cached (no host-to-device copy per step; also what makes the training step hipGraph-capturable)
-    key = (str(dev), tuple(tuple(r) for r in rows))
-    table = _PACK_TABLES.get(key)
-    if table is None:
-        if len(_PACK_TABLES) > 16:
-            _PACK_TABLES.clear()
-        table = torch.tensor(rows, dtype=torch.int64).to(dev)
-        _PACK_TABLES[key] = table
+    table, = _pack_tables('conv', dev, rows)
     rc = nat.lib().sqd_pack_conv_weights_batched(nat.ptr(table), len(rows), 96, nat.stream_handle(dev))
     nat.check(rc, 'sqd_pack_conv_weights_batched')
     return table
@@ -115,16 +120,6 @@ class WinoPlan:
         nat.check(nat.lib().sqd_pack_wino_weight(nat.ptr(src), nat.ptr(self.w), No, Ci, self.Npad, int(dgrad),
                                                  nat.stream_handle(src.device)), 'sqd_pack_wino_weight')
         self.bias = None if (bias is None or dgrad) else bias.detach().contiguous()
-
-    def repack(self, w_oihw, bias, dgrad=False):
-        """Re-transform into the same buffer after the parameter changed (pointer-stable: hipGraph replays stay valid)."""
-        src = w_oihw.detach()
-        if not src.is_contiguous():
-            raise ValueError('WinoPlan.repack: parameters must be contiguous')
-        nat.check(nat.lib().sqd_pack_wino_weight(nat.ptr(src), nat.ptr(self.w), src.shape[0], src.shape[1], self.Npad, int(dgrad),
-                                                 nat.stream_handle(src.device)), 'sqd_pack_wino_weight')
-        if self.bias is not None:
-            self.bias = bias.detach()
 
 
 _SK_SCHEDULES = {}
@@ -224,13 +219,7 @@ def repack_wino_batched(plans_and_weights, is_dgrad):
             raise ValueError('repack_wino_batched: parameters must be contiguous')
         rows.append([w.data_ptr(), plan.w.data_ptr(), w.shape[0], w.shape[1], plan.Npad, int(dg), (plan.C // 8) * plan.Npad * 8])
     dev = plans_and_weights[0][1].device
-    key = ('wino', str(dev), tuple(tuple(r) for r in rows))
-    table = _PACK_TABLES.get(key)
-    if table is None:
-        if len(_PACK_TABLES) > 16:
-            _PACK_TABLES.clear()
-        table = torch.tensor(rows, dtype=torch.int64).to(dev)
-        _PACK_TABLES[key] = table
+    table, = _pack_tables('wino', dev, rows)
     nat.check(nat.lib().sqd_pack_wino_weights_batched(nat.ptr(table), len(rows), 96, nat.stream_handle(dev)), 'sqd_pack_wino_weights_batched')
     return table
 
@@ -375,17 +364,92 @@ def refresh_bridge_plans(items):
         grows.append([plan.w.data_ptr(), plan.map_u.data_ptr(), plan.w.numel(), w1.data_ptr(), 0, 0, 0])
         grows.append([plan.aux.data_ptr(), plan.map_aux.data_ptr(), plan.aux.numel(), wsq.data_ptr(), b1.data_ptr(), b3.data_ptr(), bsq.data_ptr()])
     dev = items[0][0].w.device
-    key = ('bridge', str(dev), tuple(tuple(r) for r in wrows), tuple(tuple(r) for r in grows))
-    tables = _PACK_TABLES.get(key)
-    if tables is None:
-        if len(_PACK_TABLES) > 16:
-            _PACK_TABLES.clear()
-        tables = (torch.tensor(wrows, dtype=torch.int64).to(dev), torch.tensor(grows, dtype=torch.int64).to(dev))
-        _PACK_TABLES[key] = tables
+    tables = _pack_tables('bridge', dev, wrows, grows)
     s = nat.stream_handle(dev)
     nat.check(nat.lib().sqd_pack_wino_weights_batched(nat.ptr(tables[0]), len(wrows), 16, s), 'sqd_pack_wino_weights_batched')
     nat.check(nat.lib().sqd_gather_pack_batched(nat.ptr(tables[1]), len(grows), 16, s), 'sqd_gather_pack_batched')
     return tables
+
+
+def version(mods):
+    """The staleness rule of every cached operand copy: what the parameters of ``mods`` (holders of ``weight`` / ``bias``) looked
+    like when the copy was made.  Optimizer steps, ``load_state_dict`` and every other in-place op move the version counter, ``.to()``
+    and ``p.data = ...`` the data pointer; a write THROUGH ``p.data`` moves neither (``SqueezeDetBase.invalidate_plans``)."""
+    return tuple(v for m in mods for v in (m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr()))
+
+
+class PlanEntry:
+    """One cached plan and the parameter holders it was packed from (kept: a stale entry is brought up to date from them)."""
+    __slots__ = ('kind', 'key', 'plan', 'mods', 'direction', 'version')
+
+    def __init__(self, kind, key, plan, mods, direction, version):
+        self.kind, self.key, self.plan, self.mods, self.direction, self.version = kind, key, plan, mods, direction, version
+
+
+def _repack(refresher, entries):
+    table = refresher([(e.plan, e.mods[0].weight) for e in entries], [e.direction != 'fwd' for e in entries])
+    for e in entries:
+        if e.plan.bias is not None:                # (forward plans read the bias through the plan: point it at the current one)
+            e.plan.bias = e.mods[0].bias.detach()
+    return table
+
+
+# kind -> how its stale entries are brought up to date IN PLACE with one batched launch (two for the bridges), in the order
+# ``PlanCache.refresh`` launches them; None: the plan is rebuilt by the next ``get``.  (The refreshers are looked up when called.)
+_REFRESH = {
+    'wino': lambda entries: _repack(repack_wino_batched, entries),
+    'bridge': lambda entries: refresh_bridge_plans([(e.plan,) + tuple(t.detach() for m in e.mods for t in (m.weight, m.bias))
+                                                    for e in entries]),
+    'conv': lambda entries: _repack(repack_batched, entries),
+    'fused_expand': None,
+    'fire_wino': None,
+}
+
+
+class PlanCache:
+    """The operand plans of one model: (kind, key, direction) -> PlanEntry.  Nothing faults when a copy is stale -- the step would
+    compute with last step's weights -- so this class alone decides when a copy is stale (``version``) and how it is brought up to
+    date (``_REFRESH``).  In-place kinds keep their buffers for life: hipGraph replays read them."""
+
+    def __init__(self):
+        self._entries = {}
+        # descriptor table(s) of the latest refresh launch, kept alive until replaced: per kind for ``refresh`` (the launch a captured
+        # step replays) and, apart from it, for the one-entry launch of a stale ``get``
+        self._tables = {}
+
+    def get(self, kind, key, mods, build, direction='fwd'):
+        """The plan of ``key`` packed from ``mods`` as they are now; ``build()`` makes it on a miss."""
+        now = version(mods)
+        e = self._entries.get((kind, key, direction))
+        if e is None or (e.version != now and _REFRESH[kind] is None):
+            e = self._entries[kind, key, direction] = PlanEntry(kind, key, build(), tuple(mods), direction, now)
+        elif e.version != now:
+            e.mods = tuple(mods)
+            self._refresh(kind, [e], (kind, 'get'))
+        return e.plan
+
+    def _refresh(self, kind, entries, slot):
+        self._tables[slot] = _REFRESH[kind](entries)
+        for e in entries:
+            e.version = version(e.mods)
+
+    def refresh(self):
+        """Every stale entry of the in-place kinds, one batched launch per kind (after an optimizer step that is all of them);
+        nothing when nothing is stale."""
+        stale = {}
+        for e in self._entries.values():
+            if _REFRESH[e.kind] is not None and e.version != version(e.mods):
+                stale.setdefault(e.kind, []).append(e)
+        for kind in _REFRESH:
+            if kind in stale:
+                self._refresh(kind, stale[kind], kind)
+
+    def clear(self):
+        self._entries.clear()
+        self._tables.clear()
+
+    def entries(self):
+        return iter(self._entries.values())
 
 
 _WGR_OUT = 64               # outputs per workgroup of the slab-reduction kernels (csrc/wgrad.hip WGR_OUT)

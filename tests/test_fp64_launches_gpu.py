@@ -218,24 +218,16 @@ class _Harness:
         self.pending = {}              # slab data_ptr -> (entry, dy, x, taps) until the slab reduction
         self.plan_map = self._plan_map()
 
-    def _mod(self, name):
-        name = name.split('@')[0]
-        if name == 'convdet':
-            return self.base.convdet
-        i, sub = name.split('.')
-        return getattr(self.base.features[int(i)], sub)
-
     def _plan_map(self):
-        """id(plan) -> what it was packed from (the model's plan caches, filled by the warm-up step)."""
+        """id(plan) -> what it was packed from (the model's plan cache, filled by the warm-up step)."""
         m = {}
-        for (name, _cfg, direction), (_v, p) in list(self.base._plans.items()) + list(self.base._wino_plans.items()):
-            m[id(p)] = ('conv', self._mod(name), direction)
-        for key, val in self.base._fused_plans.items():
-            if key[0] == 'firebridge':
-                m[id(val[1])] = ('bridge',) + tuple(val[2])
-            elif key[0] == 'fused':
-                fire = self.base.features[key[1]]
-                m[id(val[1])] = ('expand', fire.expand1x1, fire.expand3x3)
+        for e in self.base.plan_cache.entries():
+            if e.kind in ('conv', 'wino'):
+                m[id(e.plan)] = ('conv', e.mods[0], e.direction)
+            elif e.kind == 'bridge':
+                m[id(e.plan)] = ('bridge',) + e.mods
+            elif e.kind == 'fused_expand':
+                m[id(e.plan)] = ('expand',) + e.mods
         return m
 
     def _weights(self, plan):

@@ -89,6 +89,84 @@ def test_plan_cache_contract_and_invalidate():
         np.testing.assert_allclose(m.base(x.cuda()).cpu().numpy(), oracle.backbone_forward(x, sd2).numpy(), atol=TOL)
 
 
+def test_plan_cache_refreshes_in_place_after_a_parameter_update(monkeypatch):
+    """At the forced-forms point of tests/test_fp64_offbench_gpu.py (squeezedet, batch 3, 70x100: bridges and Winograd plans off the
+    tuning table), one training step + one ``no_grad`` forward fill the cache with all five kinds; after every parameter changed in
+    place the next step brings the in-place kinds up to date with one call per refresher -- same plan objects, same buffers, bit-equal
+    to plans built afresh -- and the forward after it refreshes nothing.  (The point's own swaps leave the one-launch expand forms to
+    the table, which has no row here: this test also sends the Fires the bridges do not take to ``fire_wino`` / ``fire_expand``.)"""
+    import test_fp64_offbench_gpu as OB
+    from squeezedet_pytorch_amd import ops, plans
+    from squeezedet_pytorch_amd.model import SqueezeDetWithLoss
+    arch, batch, size = OB.FORCED_POINT
+    in_place = ('wino', 'bridge', 'conv')
+    monkeypatch.setattr(ops, 'choose_fire_wino_cfg', lambda C, E1, E3, npix: 10 if (C == 32 and ops.fire_wino_cfg_ok(10, C)) else None)
+    monkeypatch.setattr(ops, 'choose_fused_cfg', lambda C, E, npix: (ops.fused_expand_cfgs(E) or [None])[0])
+    torch.manual_seed(0)
+    cfg = sqd.make_cfg(arch=arch, input_size=size, device='cuda')
+    m = SqueezeDetWithLoss(cfg)
+    m.load_state_dict(synthetic.make_state_dict(arch, seed=1234))
+    m = m.cuda().train()
+    base = m.base
+    base.dropout_prob = 0.0                                  # (as the point's own harness runs it)
+    batch_d = {'image': synthetic.make_images(batch, size, seed=0).cuda(), 'gt': synthetic.make_gt(batch, cfg.anchors, size, seed=1).cuda()}
+
+    def train_step():
+        loss, _ = m.forward_mean(batch_d)
+        m.zero_grad()
+        loss.backward()
+
+    def infer():
+        m.eval()
+        with torch.no_grad():
+            base(batch_d['image'])
+        m.train()
+
+    def buffers(plan):
+        return [plan.w] + ([plan.aux] if isinstance(plan, plans.FireBridgePlan) else [])
+    with OB.forced_forms():
+        train_step(); infer()
+        entries = list(base.plan_cache.entries())
+        kinds = {e.kind for e in entries}
+        assert kinds == {'conv', 'wino', 'bridge', 'fused_expand', 'fire_wino'}, kinds
+        held = [e for e in entries if e.kind in in_place]
+        ptrs = [[t.data_ptr() for t in buffers(e.plan)] for e in held]
+        with torch.no_grad():
+            for p in m.parameters():
+                p.mul_(1.01)
+        count = {}
+
+        def counted(owner, name):
+            orig = getattr(owner, name)
+
+            def wrapper(*a, **kw):
+                count[name] = count.get(name, 0) + 1
+                return orig(*a, **kw)
+            monkeypatch.setattr(owner, name, wrapper)
+        for name in ('repack_wino_batched', 'refresh_bridge_plans', 'repack_batched'):
+            counted(plans, name)
+        for name in ('ConvPlan', 'WinoPlan', 'FireBridgePlan'):
+            counted(ops, name)
+        train_step()
+        first = dict(count)
+        infer()
+        torch.cuda.synchronize()
+        assert first == {'repack_wino_batched': 1, 'refresh_bridge_plans': 1, 'repack_batched': 1}, first
+        assert count == first, count                         # nothing refreshed by the second pass, no in-place-kind plan constructed
+    now = [e for e in base.plan_cache.entries() if e.kind in in_place]
+    assert [id(e.plan) for e in now] == [id(e.plan) for e in held]
+    assert [[t.data_ptr() for t in buffers(e.plan)] for e in now] == ptrs
+    build = {'conv': lambda e: plans.ConvPlan(e.mods[0].weight, e.mods[0].bias, e.plan.cfg_id, dgrad=(e.direction != 'fwd')),
+             'wino': lambda e: plans.WinoPlan(e.mods[0].weight, e.mods[0].bias, e.plan.cfg_id, dgrad=(e.direction != 'fwd')),
+             'bridge': lambda e: plans.FireBridgePlan(*(t for mod in e.mods for t in (mod.weight, mod.bias)), e.plan.cfg_id, pooled=e.plan.pooled)}
+    for e in now:
+        fresh = build[e.kind](e)
+        for got, want in zip(buffers(e.plan), buffers(fresh)):
+            assert torch.equal(got, want), (e.kind, e.key, e.direction)
+        if e.kind != 'bridge' and e.direction == 'fwd':
+            assert e.plan.bias.data_ptr() == e.mods[0].bias.data_ptr()
+
+
 def _run_bench(*args, timeout=900):
     env = dict(os.environ)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
