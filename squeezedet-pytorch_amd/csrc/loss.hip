@@ -33,7 +33,7 @@ struct AnchorGeom {           // the class-independent part: confidence, box dec
   float mask, conf, iou_raw, e;          // e = iou*mask - conf
   float bb;                              // sum_j (delta_j - gt_j)^2
   // box decode intermediates for the backward
-  float w, h, aw, ah;
+  float w, h, ax, ay, aw, ah;
   float x1u, y1u, x2u, y2u;              // unclamped
   float px1, py1, px2, py2;              // clamped
   float gx1, gy1, gx2, gy2;
@@ -56,7 +56,7 @@ __device__ __forceinline__ void anchor_geom(const LossArgs& a, const float* __re
   // box decode (deltas_to_boxes)
   const float* d = p + C + 1;
   const float ax = anc[0], ay = anc[1];
-  t.aw = anc[2]; t.ah = anc[3];
+  t.ax = ax; t.ay = ay; t.aw = anc[2]; t.ah = anc[3];
   const float cx = ax + t.aw * d[0], cy = ay + t.ah * d[1];
   t.w = t.aw * expf(d[2]); t.h = t.ah * expf(d[3]);
   t.x1u = cx - 0.5f * (t.w - 1.f); t.y1u = cy - 0.5f * (t.h - 1.f);
@@ -178,37 +178,53 @@ __device__ __forceinline__ void anchor_geom_grad(const LossArgs& a, const Anchor
   const float k = us * (a.w_pos * t.mask / n + a.w_neg * (1.f - t.mask) / ((float)a.A - n));
   const float dL_de = 2.f * k * t.e;
   out[0] = -dL_de * t.conf * (1.f - t.conf);
-  // IoU path: d e / d iou_raw = mask
+  // IoU path: d e / d iou_raw = mask.  Only the rows with a box take it (about 0.1 % of a batch), and there the gradient is a
+  // difference of two products of areas that cancel about 3:1 for a well-fitting box: every float32 evaluation of it lands a few ulp
+  // to either side.  Those rows redo the decode and the IoU in float64 from the row's own operands and round once at the end; the
+  // branch rules are the forward's (clamp passes inclusively, min / max ties split, clamp_min passes at 0).
   const float dL_dov = dL_de * t.mask;
-  float gd[4] = {0.f, 0.f, 0.f, 0.f};
   if (dL_dov != 0.f) {
-    const float den = t.uni + LOSS_EPS;
-    const float dov_dinter = 1.f / den + t.inter / (den * den);     // union contains -inter
-    const float dov_dap = -t.inter / (den * den);                   // pred-box area
-    const float lr = fmaxf(t.lr_raw, 0.f), tb = fmaxf(t.tb_raw, 0.f);
-    const float dlr = (t.lr_raw >= 0.f) ? dL_dov * dov_dinter * tb : 0.f;
-    const float dtb = (t.tb_raw >= 0.f) ? dL_dov * dov_dinter * lr : 0.f;
+    const double aw = t.aw, ah = t.ah, wmax = a.wmax, hmax = a.hmax;
+    const double cx = (double)t.ax + aw * (double)d[0], cy = (double)t.ay + ah * (double)d[1];
+    const double w = aw * exp((double)d[2]), h = ah * exp((double)d[3]);
+    const double x1u = cx - 0.5 * (w - 1.0), y1u = cy - 0.5 * (h - 1.0), x2u = cx + 0.5 * (w - 1.0), y2u = cy + 0.5 * (h - 1.0);
+    const double px1 = fmin(fmax(x1u, 0.0), wmax), py1 = fmin(fmax(y1u, 0.0), hmax);
+    const double px2 = fmin(fmax(x2u, 0.0), wmax), py2 = fmin(fmax(y2u, 0.0), hmax);
+    const double gx1 = t.gx1, gy1 = t.gy1, gx2 = t.gx2, gy2 = t.gy2;
+    const double lr_raw = fmin(gx2, px2) - fmax(gx1, px1), tb_raw = fmin(gy2, py2) - fmax(gy1, py1);
+    const double lr = fmax(lr_raw, 0.0), tb = fmax(tb_raw, 0.0);
+    const double inter = lr * tb;
+    const double den = (gx2 - gx1) * (gy2 - gy1) + (px2 - px1) * (py2 - py1) - inter + (double)LOSS_EPS;
+    const double e = inter / den * (double)t.mask - (double)t.conf;
+    const double dov = 2.0 * (double)k * e * (double)t.mask;
+    const double dov_dinter = 1.0 / den + inter / (den * den);      // union contains -inter
+    const double dov_dap = -inter / (den * den);                    // pred-box area
+    const double dlr = (lr_raw >= 0.0) ? dov * dov_dinter * tb : 0.0;
+    const double dtb = (tb_raw >= 0.0) ? dov * dov_dinter * lr : 0.0;
     // min/max sub-gradients: ties split evenly (torch.minimum/maximum backward)
-    auto wmin = [](float mine, float other) { return mine < other ? 1.f : (mine == other ? 0.5f : 0.f); };
-    auto wmax = [](float mine, float other) { return mine > other ? 1.f : (mine == other ? 0.5f : 0.f); };
-    const float pw = t.px2 - t.px1, ph = t.py2 - t.py1;
-    const float dap = dL_dov * dov_dap;
-    float dpx2 = dlr * wmin(t.px2, t.gx2) + dap * ph;
-    float dpx1 = -dlr * wmax(t.px1, t.gx1) - dap * ph;
-    float dpy2 = dtb * wmin(t.py2, t.gy2) + dap * pw;
-    float dpy1 = -dtb * wmax(t.py1, t.gy1) - dap * pw;
+    auto wmin = [](double mine, double other) { return mine < other ? 1.0 : (mine == other ? 0.5 : 0.0); };
+    auto wmaxf = [](double mine, double other) { return mine > other ? 1.0 : (mine == other ? 0.5 : 0.0); };
+    const double pw = px2 - px1, ph = py2 - py1;
+    const double dap = dov * dov_dap;
+    double dpx2 = dlr * wmin(px2, gx2) + dap * ph;
+    double dpx1 = -dlr * wmaxf(px1, gx1) - dap * ph;
+    double dpy2 = dtb * wmin(py2, gy2) + dap * pw;
+    double dpy1 = -dtb * wmaxf(py1, gy1) - dap * pw;
     // clamp backward: passes where the unclamped value is inside [0, max] (inclusive)
-    if (!(t.x1u >= 0.f && t.x1u <= a.wmax)) dpx1 = 0.f;
-    if (!(t.x2u >= 0.f && t.x2u <= a.wmax)) dpx2 = 0.f;
-    if (!(t.y1u >= 0.f && t.y1u <= a.hmax)) dpy1 = 0.f;
-    if (!(t.y2u >= 0.f && t.y2u <= a.hmax)) dpy2 = 0.f;
-    gd[0] = (dpx1 + dpx2) * t.aw;                    // d x{1,2}u / d dx = aw
-    gd[1] = (dpy1 + dpy2) * t.ah;
-    gd[2] = (dpx2 - dpx1) * 0.5f * t.w;              // d x2u/d dw = +w/2, d x1u/d dw = -w/2
-    gd[3] = (dpy2 - dpy1) * 0.5f * t.h;
+    if (!(x1u >= 0.0 && x1u <= wmax)) dpx1 = 0.0;
+    if (!(x2u >= 0.0 && x2u <= wmax)) dpx2 = 0.0;
+    if (!(y1u >= 0.0 && y1u <= hmax)) dpy1 = 0.0;
+    if (!(y2u >= 0.0 && y2u <= hmax)) dpy2 = 0.0;
+    const double gd[4] = {(dpx1 + dpx2) * aw,                    // d x{1,2}u / d dx = aw
+                          (dpy1 + dpy2) * ah,
+                          (dpx2 - dpx1) * 0.5 * w,               // d x2u/d dw = +w/2, d x1u/d dw = -w/2
+                          (dpy2 - dpy1) * 0.5 * h};
+    const double kb = (double)ub * (double)a.w_bbox * (double)t.mask / (double)n * 2.0;
+    for (int j = 0; j < 4; ++j) out[1 + j] = (float)(gd[j] + kb * ((double)d[j] - (double)g[5 + j]));
+    return;
   }
   const float kb = ub * a.w_bbox * t.mask / n * 2.f;
-  for (int j = 0; j < 4; ++j) out[1 + j] = gd[j] + kb * (d[j] - g[5 + j]);
+  for (int j = 0; j < 4; ++j) out[1 + j] = 0.f + kb * (d[j] - g[5 + j]);      // (0.f +: a row without a box never holds -0)
 }
 
 // dpred[b][a][:] = u_class[b]*d(class_b) + u_score[b]*d(score_b) + u_bbox[b]*d(bbox_b), coef[3][B]

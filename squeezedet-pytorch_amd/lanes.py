@@ -25,6 +25,7 @@ steps and the result buffers as well.
 from __future__ import annotations
 
 import ctypes
+import gc
 from collections import deque
 
 import numpy as np
@@ -487,8 +488,15 @@ class DetectStream:
     def _capture(self, lane, compute):
         """One hipGraph of the lane's step for this key, captured on the lane's stream (its eager run has already sized the pools);
         'eager' (and ``degraded``) if the capture fails."""
+        # A cyclic garbage collection that starts inside the capture runs the finalisers of whatever GPU objects are unreachable by then
+        # (dropped graphs of this lane's pool, events, staging buffers of a closed stream) between two captured launches, and the
+        # process aborts.  Python starts one whenever its allocation counters say so: collect now, with the device idle, and keep the
+        # collector off until the capture has ended.
+        gc_was_on = gc.isenabled()
         try:
             torch.cuda.synchronize(self.device)
+            gc.collect()
+            gc.disable()
             g = torch.cuda.CUDAGraph()
             # thread_local: loader threads, a collective library's watchdog ... may touch the runtime while this thread captures
             if lane.pool is None:
@@ -506,6 +514,9 @@ class DetectStream:
             torch.cuda.synchronize(self.device)
             self.degraded = True
             return 'eager'
+        finally:
+            if gc_was_on:
+                gc.enable()
 
     # ------------------------------------------------------------------------------------------------------------------
     # results

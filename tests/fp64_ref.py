@@ -231,10 +231,20 @@ def _reduce_slabs(slabs):
     return ((parts[0] + parts[1]) + parts[2]) + parts[3]
 
 
-def wgrad_split_k(dy, x, taps, S, blocking, step, emu=None):
+def _reduce_slabs_ascending(slabs):
+    """The row reduction of a padded ConvDet (wgrad_reduce_rows): one fp32 accumulator takes the slabs 0, 1, ... in ascending order."""
+    acc = torch.zeros_like(slabs[0])
+    for k in range(slabs.shape[0]):
+        acc += slabs[k]
+    return acc
+
+
+def wgrad_split_k(dy, x, taps, S, blocking, step, emu=None, order='batched'):
     """Float32 restatement of a split-K weight-gradient kernel with its own summation structure: the pixel axis cut into the kernel's
     blocks, slab s accumulating blocks s, s + S, ... in order, ``step`` pixels (one matrix-core K step) per fp32 accumulation, the S
-    slabs reduced in the shipped order.  -> (dW [N,C,k,k], db [N]) in float32 (``emu``: degraded products, as ``wgrad``)."""
+    slabs reduced in the shipped order (``order``: 'batched' = wgrad_reduce_batched's four partitions, 'ascending' = wgrad_reduce_rows').
+    -> (dW [N,C,k,k], db [N]) in float32 (``emu``: degraded products, as ``wgrad``)."""
+    red = {'batched': _reduce_slabs, 'ascending': _reduce_slabs_ascending}[order]
     assert_full_fp32()
     B, H, W, N = dy.shape
     C = x.shape[3]
@@ -257,7 +267,7 @@ def wgrad_split_k(dy, x, taps, S, blocking, step, emu=None):
             slabs_w[:, :, :, ky, kx] = acc
     dbb = _pixel_blocks(db_in, blocking).view(nb, PB // step, step, N).sum(2)
     slabs_b = _in_order(dbb, S, torch.zeros(S, N, dtype=F32, device=dy.device))
-    return _reduce_slabs(slabs_w), _reduce_slabs(slabs_b)
+    return red(slabs_w), red(slabs_b)
 
 
 def wgrad_wino_magnitude(dy, x):

@@ -6,7 +6,13 @@ float32 oracle chain (attainability), and each wrong branch convention against t
 against torch.optim.SGD + clip_grad_norm_, and the norm bar against a norm that drops the tail or a part.
 The off-benchmark sweep (tests/test_fp64_offbench_gpu.py) is held the same way: its two lists equal the planners' output at its points
 (the forced-forms point recomputed under the same swap of look-ups), and every kernel name the planners produce over a grid of batches
-and input sizes has a float64 case in one of the lists."""
+and input sizes has a float64 case in one of the lists.
+The sweep along the head axis (tests/test_fp64_widths_gpu.py: class counts, anchors per cell, sparse ground truth) likewise: ``WIDTHS``
+equals the planners' ConvDet-side rows at its points, the backbone rows of those points are the ones the off-benchmark sweep checks,
+every kernel name and every ConvDet signature the planners produce over 1..20 anchors x 1..256 classes x dense / sparse occurs at a
+point, and a numpy restatement of ``wgrad_reduce_rows`` with a wrong row stride, a wrong bias offset or a dropped slab fails bar L."""
+import contextlib
+import functools
 import os
 import sys
 
@@ -20,6 +26,7 @@ import test_fp64_launches_gpu as L  # noqa: E402
 import test_fp64_loss_gpu as LG  # noqa: E402
 import test_fp64_offbench_gpu as OB  # noqa: E402
 import test_fp64_optim_gpu as OG  # noqa: E402
+import test_fp64_widths_gpu as WD  # noqa: E402
 
 # launches outside the float64 sweep, each with the test that covers it
 ALLOWED = {
@@ -68,13 +75,14 @@ def offbench_entries(points):
     return out
 
 
-def _same_as_plans(cases, entries, what):
+def _same_as_plans(cases, entries, what, name_at=3):
+    """``name_at``: where a case holds its kernel name."""
     assert len(set(cases)) == len(cases), 'duplicate cases'
-    missing = [e for e in entries if e not in set(cases) and e[3] not in ALLOWED]
+    missing = [e for e in entries if e not in set(cases) and e[name_at] not in ALLOWED]
     assert not missing, f'launches of {what} without a float64 case: {missing}'
     stale = [c for c in cases if c not in entries]
     assert not stale, f'cases the plans of {what} no longer launch: {stale}'
-    assert all(c[3] not in ALLOWED for c in cases)
+    assert all(c[name_at] not in ALLOWED for c in cases)
 
 
 def test_every_offbench_plan_entry_has_a_case():
@@ -137,6 +145,183 @@ def test_every_reachable_kernel_has_a_case():
     assert set(large) <= compiled, sorted(set(large) - compiled)
 
 
+# ---- the head axis: class counts, anchors per cell, sparse ground truth (tests/test_fp64_widths_gpu.py) ----
+
+def _width_plans(arch, apg, C, sparse=False):
+    from squeezedet_pytorch_amd import plan
+    return (plan.inference_launch_plan(arch, WD.BATCH, WD.SIZE, anchors_per_grid=apg, num_classes=C),
+            plan.training_launch_plan(arch, WD.BATCH, WD.SIZE, anchors_per_grid=apg, num_classes=C, sparse_gt=sparse))
+
+
+def width_entries(points):
+    """The ConvDet-side rows of both plans of every point, as WIDTHS cases."""
+    out = []
+    for pt in points:
+        arch, apg, C, _sparse = pt
+        for rows, train in zip(_width_plans(*pt), (False, True)):
+            i0, i1 = WD.convdet_side(rows, arch, apg, C, train)
+            for e in rows[i0:i1]:
+                if pt + e not in out:
+                    out.append(pt + e)
+    return out
+
+
+def test_every_width_plan_entry_has_a_case():
+    """WIDTHS equals the planners' ConvDet-side rows at POINTS: nothing missing, nothing stale (``detect`` stays with its own sweep)."""
+    assert WD.POINTS == [('squeezedet', 9, 7, False), ('squeezedet', 9, 255, True), ('squeezedet', 20, 7, False),
+                         ('squeezedet', 4, 6, False), ('squeezedet', 3, 7, False), ('squeezedet', 4, 3, False),
+                         ('squeezedet', 1, 3, False), ('squeezedet', 16, 3, False), ('squeezedet', 9, 1, False),
+                         ('squeezedet', 9, 20, False), ('squeezedet', 9, 256, True), ('squeezedetplus', 9, 20, True)]
+    assert (WD.BATCH, WD.SIZE) == (3, (70, 100))
+    _same_as_plans(WD.WIDTHS, width_entries(WD.POINTS), 'the head-axis points', name_at=4)
+    assert set(WD.TEETH_POINTS) <= set(WD.POINTS) and all(pt in WD.POINTS for pt in WD.GT_SEED)
+    # every case family has a bar: a GEMM family of the older sweeps (k from ``L.k_of``), a loss launch, or one of the exact launches
+    known = set(L.FAMILIES) | set(L.LOSS_FAMILIES) | set(OB.NEW_FAMILIES) | {'loss_sparse_fwd', 'loss_sparse_bwd', 'convdet_pack',
+                                                                             'convdet_unpack', 'wgrad_reduce_rows'}
+    assert all(L.family(c[4]) in known for c in WD.WIDTHS)
+    # the teeth points launch what their teeth are taken from
+    for pt, fams in WD.TEETH_POINTS.items():
+        kernels = {c[4] for c in WD.WIDTHS if c[:4] == pt}
+        for f in fams:
+            if f == 'conv_wgrad':
+                assert 'conv_wgrad<9>' in kernels, pt
+            elif 'sparse' in f:
+                assert f in kernels and pt[3], (pt, f)
+            else:
+                from squeezedet_pytorch_amd import ops
+                assert ops.head_path(pt[2]) == 'many' and not pt[3] and f.replace('_many', '') in kernels, (pt, f)
+
+
+def test_width_points_run_a_checked_backbone():
+    """Why the head-axis sweep may pass the backbone through unchecked: outside the ConvDet side the launches of every point are, name and
+    tag, those of the off-benchmark sweep's point of the same architecture at batch 3, 70x100 (all of which have float64 cases there).
+    The one row that differs is the batched slab reduction of a padded point: ConvDet's slabs are reduced on their own
+    (``wgrad_reduce_rows``), which leaves it 30 layers instead of 31."""
+    from squeezedet_pytorch_amd import ops
+    for pt in WD.POINTS:
+        arch, apg, C, sparse = pt
+        assert (arch, WD.BATCH, WD.SIZE) in OB.POINTS
+        checked = {c[3:] for c in OB.OFFBENCH if c[:3] == (arch, WD.BATCH, WD.SIZE)} | {(k, None) for k in ALLOWED}
+        for rows, base, train in zip(_width_plans(*pt), _width_plans(arch, 9, 3), (False, True)):
+            i0, i1 = WD.convdet_side(rows, arch, apg, C, train)
+            j0, j1 = WD.convdet_side(base, arch, 9, 3, train)
+            assert rows[:i0] == base[:j0], pt
+            tail, want = rows[i1:], base[j1:]
+            if train and ops.convdet_padded(apg, C):
+                assert tail[-1] == ('wgrad_reduce_batched', '30 layers') and want[-1] == ('wgrad_reduce_batched', '31 layers'), pt
+                tail, want = tail[:-1], want[:-1]
+            if train:
+                assert tail == want, pt
+            assert all(e in checked or (e[0], None) in checked for e in rows[:i0] + tail), pt
+
+
+@contextlib.contextmanager
+def _memoized_lookups():
+    """The two table look-ups every 3x3 and 1x1 row goes through, memoized for the grid walk below (they are pure functions of their
+    arguments and the loaded table; the planners read them through ``ops``).  Restored afterwards, schedule memos cleared, as
+    ``OB.forced_forms`` does."""
+    from squeezedet_pytorch_amd import ops, plan
+    saved = {n: getattr(ops, n) for n in ('choose_cfg', 'choose_wino_cfg')}
+    plan.forward_schedule.cache_clear(); plan.backward_schedule.cache_clear()
+    for n, f in saved.items():
+        setattr(ops, n, functools.lru_cache(maxsize=None)(f))
+    try:
+        yield
+    finally:
+        for n, f in saved.items():
+            setattr(ops, n, f)
+        plan.forward_schedule.cache_clear(); plan.backward_schedule.cache_clear()
+
+
+HEAD_GRID_ANCHORS = range(1, 21)
+HEAD_GRID_CLASSES = range(1, 257)
+
+
+def convdet_signature(arch, apg, C):
+    """What decides ConvDet's launches at (anchors per cell, classes): (padded or not, the forward kernel family, the weight-gradient
+    kernel name, the data-gradient kernel family, the run width mod 16 if it is <= 80 else whether it is a multiple of 64, the run
+    width mod 16 where the data gradient is a direct kernel)."""
+    from squeezedet_pytorch_amd import ops
+    rows = _width_plans(arch, apg, C)[1]
+    i0, i1 = WD.convdet_side(rows, arch, apg, C, True)
+    side = rows[i0:i1]
+    n, nrun = ops.convdet_width(apg, C)
+    wg, = [k for k, t in side if t.startswith('wgrad ')]
+    dg = L.family(side[-1][0])
+    return (n != nrun, L.family(side[0][0]), wg, dg, nrun % 16 if nrun <= 80 else nrun % 64 == 0, None if 'wino' in dg else nrun % 16)
+
+
+def test_every_reachable_head_kernel_and_convdet_signature_has_a_case():
+    """Over 1..20 anchors per cell x 1..256 classes x dense / sparse ground truth at batch 3, 70x100, for both architectures: every
+    kernel name either planner produces has a float64 case (``CASES``, ``OFFBENCH`` or ``WIDTHS``), and every ConvDet signature
+    (``convdet_signature``) occurs at a point of the head-axis sweep.  Both head paths and both kinds of loss launch occur there too."""
+    from squeezedet_pytorch_amd import ops
+    covered = {c[2] for c in L.CASES} | {c[3] for c in OB.OFFBENCH} | {c[4] for c in WD.WIDTHS} | set(ALLOWED)
+    at_points = {convdet_signature(*pt[:3]) for pt in WD.POINTS}
+    with _memoized_lookups():
+        for arch in ('squeezedet', 'squeezedetplus'):
+            names, sigs = set(), {}
+            for apg in HEAD_GRID_ANCHORS:
+                for C in HEAD_GRID_CLASSES:
+                    for sparse in (False, True):
+                        for rows in _width_plans(arch, apg, C, sparse):
+                            names |= {kernel for kernel, _tag in rows}
+                    sigs.setdefault(convdet_signature(arch, apg, C), (apg, C))
+            missing = sorted(names - covered)
+            assert not missing, f'{arch}: kernel instances the planners can name along the head axis without a float64 case: {missing}'
+            new = {s: at for s, at in sigs.items() if s not in at_points}
+            assert not new, f'{arch}: ConvDet signatures (first at anchors, classes) that no point of the head-axis sweep runs: {new}'
+            print(f'{arch}: {len(names)} kernel names, {len(sigs)} ConvDet signatures over the head grid')
+    assert {ops.head_path(pt[2]) for pt in WD.POINTS} == {'narrow', 'many'}
+    kernels = {c[4] for c in WD.WIDTHS}
+    assert {'loss_fwd', 'loss_bwd', 'loss_sparse_fwd', 'loss_sparse_bwd'} <= kernels
+    # the many-class launches are bracketed under the dense names: a dense point past 16 classes runs them
+    assert any(ops.head_path(pt[2]) == 'many' and not pt[3] for pt in WD.POINTS)
+
+
+def _reduce_rows_numpy(slab, S, N, Npad, C, taps, stride_rows=None, bias_off=None, slabs=None):
+    """csrc/convdet_pad.hip's wgrad_reduce_rows restated in numpy (float32, the slabs added in ascending order): slab s starts at
+    s * (Npad * taps * C + Npad) and holds [Npad][taps][C] weight sums, then [Npad] bias sums.  -> (dw [N,C,k,k], db [N]).  The keyword
+    arguments are the wrong variants of the teeth: the slab stride from another row count, another bias offset, a subset of the slabs."""
+    import numpy as np
+    k = 3 if taps == 9 else 1
+    stride_rows = Npad if stride_rows is None else stride_rows
+    stride = stride_rows * taps * C + stride_rows
+    bias_off = Npad * taps * C if bias_off is None else bias_off
+    dw = np.zeros((N, taps, C), np.float32)
+    db = np.zeros(N, np.float32)
+    for s in (range(S) if slabs is None else slabs):
+        dw += slab[s * stride:s * stride + N * taps * C].reshape(N, taps, C)
+        db += slab[s * stride + bias_off:s * stride + bias_off + N]
+    return dw.transpose(0, 2, 1).reshape(N, C, k, k), db
+
+
+def test_reduce_rows_restatement_and_its_teeth():
+    """The numpy restatement of ``wgrad_reduce_rows`` holds bar L against the float64 sum of the true rows on the (54 of 64, C768) layout;
+    reading the slabs at the stride of N instead of Npad rows, taking the bias from offset N * taps * C, or dropping one slab fails it."""
+    import numpy as np
+    S, N, Npad, C, taps = 3, 54, 64, 768, 9
+    rs = np.random.RandomState(54)
+    stride = Npad * taps * C + Npad
+    slab = rs.standard_normal(S * stride).astype(np.float32)
+    s64 = slab.astype(np.float64).reshape(S, stride)
+    w64 = s64[:, :Npad * taps * C].reshape(S, Npad, taps, C)[:, :N]
+    b64 = s64[:, Npad * taps * C:][:, :N]
+    ref_w, M_w = w64.sum(0).transpose(0, 2, 1).reshape(N, C, 3, 3), np.abs(w64).sum(0).transpose(0, 2, 1).reshape(N, C, 3, 3)
+    ref_b, M_b = b64.sum(0), np.abs(b64).sum(0)
+
+    def holds(dw, db):
+        return bool((np.abs(dw - ref_w) <= R.BAR_L * M_w).all()), bool((np.abs(db - ref_b) <= R.BAR_L * M_b).all())
+    assert holds(*_reduce_rows_numpy(slab, S, N, Npad, C, taps)) == (True, True)
+    # rows at stride N: the slabs are taken N * taps * C + N floats apart (slab 0 still lines up, the later ones do not)
+    assert holds(*_reduce_rows_numpy(slab, S, N, Npad, C, taps, stride_rows=N)) == (False, False)
+    # the bias from offset N * taps * C: weight sums of row N land in db
+    assert holds(*_reduce_rows_numpy(slab, S, N, Npad, C, taps, bias_off=N * taps * C)) == (True, False)
+    # one slab dropped
+    for drop in range(S):
+        assert holds(*_reduce_rows_numpy(slab, S, N, Npad, C, taps, slabs=[s for s in range(S) if s != drop])) == (False, False), drop
+
+
 def test_wgrad_blocking_restates_the_launchers():
     """L.wgrad_blocking against the host's own split rule: the launchers refuse S above their number of pixel blocks, so the blocks of the
     restatement must be at least as many as the S ``tiles.wgrad_split`` hands out; and the tile forms at the widths of both models."""
@@ -150,6 +335,16 @@ def test_wgrad_blocking_restates_the_launchers():
     assert L.wgrad_blocking('conv_wgrad', 32, 32, 1) == (('px', 64), 1)                 # launch_wgrad<1, 2, 2, 4>
     assert L.wgrad_blocking('conv_wgrad_wino', 72, 768, 9) == ('tile', 16)
     assert L.wgrad_blocking('conv_wgrad_wino_group', 64, 16, 9) == ('tile', 16)
+    # the 9-tap rows of the head-axis sweep: the direct 3x3 form takes 4x16-pixel tiles one pixel per accumulation whatever its
+    # out-channel tiling (N 108: a partial tile; 2340: 147 tiles), the N <= 80 Winograd form 4x16 groups, 16 pixels per step
+    for N in (108, 240, 2340):
+        assert not ops.wgrad_uses_wino(N, 768, 9, 3, 4, 6)
+        assert L.wgrad_blocking('conv_wgrad', N, 768, 9) == ('tile', 1)
+    for N in (8, 36, 44):
+        assert ops.wgrad_uses_wino(N, 768, 9, 3, 4, 6)
+        assert L.wgrad_blocking('conv_wgrad_wino', N, 768, 9) == ('tile', 16)
+    for N in (108, 240, 2340, 8, 36, 44, 64, 256, 2368):                # S never exceeds the 4x16 tile groups of the 3 x 4x6 grid
+        assert ops.wgrad_split(N, 768, 9, 3, 4, 6)[0] <= 3
     for B, H, W in ((1, 3, 3), (3, 4, 6), (2, 11, 19), (1, 12, 39), (20, 24, 78)):
         for N, C in ((192, 128), (384, 512), (288, 256), (16, 16), (96, 64)):
             S, _ = ops.wgrad_split(N, C, 1, B, H, W)

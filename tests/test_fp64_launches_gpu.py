@@ -1,6 +1,7 @@
 """GPU tier: every GEMM-type launch of the four benchmarked steps (inference and training of SqueezeDet at bs=20 and SqueezeDet+ at
 bs=16, 384x1248, shipped tuning table) held to fp32 accuracy against a float64 reference, element by element.  (The harness takes any
-batch and input size: tests/test_fp64_offbench_gpu.py runs it away from the benchmark.)
+batch and input size: tests/test_fp64_offbench_gpu.py runs it away from the benchmark; and any class count, anchor seed and ground-truth
+form: tests/test_fp64_widths_gpu.py runs it over ConvDet's width classes and the head paths.)
 
 Each case is one distinct (arch, batch, kernel, shape tag) entry of ``plan.inference_launch_plan`` / ``plan.training_launch_plan``
 (``CASES``; tests/test_fp64_coverage.py keeps the list equal to the plans).  The cases run inside the real step: the model is built
@@ -28,6 +29,19 @@ Two bars per output (fp64_ref.bars):
 The loss launches (``loss_fwd`` / ``loss_bwd``: the mean forms that bench.py's step differentiates) are held to fp64_ref.loss: losses
 [4, B], mean4 and dpred at bars L (M: the chain's running error bound) and P (k = 2; dpred in class-logit / conf / delta blocks), nobj
 exact, and at most 4 anchors of a launch on a branch where float64 and float32 disagree (either branch's reference is accepted there).
+
+The head axis (``num_classes``, ``anchors_seed``, ``sparse_gt`` of ``_run_step`` / ``_run_both`` / ``_step_results``; the defaults give the
+benchmark's 3 classes, KITTI's nine anchors and a dense gt, with the keys, plans and rows of before).  ConvDet's width
+anchors_per_grid * (num_classes + 5) decides its launches; the entry points that only other widths and heads reach are wrapped too:
+* ``loss_*_many`` (17 .. 256 classes) and ``loss_sparse_*`` (``cfg.sparse_gt``): the same checks against the same reference, a sparse gt
+  through ``ops.sparse_gt_to_dense``;
+* a padded ConvDet (a width that is no multiple of 4 runs zero-padded to a multiple of 64): its forward and data gradient are held to
+  the MODULE's parameters, zero-extended here -- not to the stand-in's tensors, so a stand-in that did not follow the parameters fails;
+  ``convdet_pack`` is bit-equal to the first N channels of the scratch, which is exactly 0.0 past them; ``convdet_unpack`` bit-equal to
+  dpred and exactly 0.0 past N; ``wgrad_reduce_rows`` (its weight gradient's own slab reduction, the slabs added in ascending order) holds
+  dW / db to float64 on the true dpred[..., :N], restated at the launch's own S in the blocking of the kernel that wrote the slabs.
+``check_from='convdet'`` passes the backbone's launches through unchecked (the launches are still asserted equal to the plan): for
+points whose backbone rows another sweep already checks, which tests/test_fp64_coverage.py asserts on the host.
 """
 import re
 
@@ -210,9 +224,11 @@ def k_of(kernel):
 class _Harness:
     """Wraps the ``ops`` entry points (and the slab reduction) for one step; collects per-(kernel, tag) output checks."""
 
-    def __init__(self, base, arch, batch, timer, teeth_for=None):
+    def __init__(self, base, arch, batch, timer, teeth_for=None, check_from=None):
         self.base, self.arch, self.batch, self.timer = base, arch, batch, timer
         self.teeth_for = teeth_for     # the families whose first launch also runs the degraded emulations (None: every family)
+        assert check_from in (None, 'convdet')
+        self.check_from = check_from   # 'convdet': the backbone's launches run unchecked (``passes``); None: every launch is checked
         self.rows = {}                 # (arch, batch, kernel, tag) -> [(output, bars dict)]
         self.teeth = {}                # family -> {emu: bars dict}
         self.pending = {}              # slab data_ptr -> (entry, dy, x, taps) until the slab reduction
@@ -230,9 +246,41 @@ class _Harness:
                 m[id(e.plan)] = ('expand',) + e.mods
         return m
 
+    def _is_convdet(self, mod):
+        """``mod`` is the model's ConvDet or the zero-padded stand-in the executors launch in its place (model._PaddedConvDet)."""
+        return mod is self.base.convdet or getattr(mod, 'src', None) is self.base.convdet
+
+    def passes(self, name, args):
+        """With ``check_from='convdet'``: whether this call runs unchecked -- every launch of the backbone (the CPU tier asserts they
+        are, name and tag, those of a point the off-benchmark sweep checks).  ConvDet's own launches, the pack / unpack / row-reduction
+        launches and the loss launches are always checked."""
+        if self.check_from is None:
+            return False
+        if name in ('conv', 'conv_wino'):
+            return not self._is_convdet(self.plan_map[id(args[2])][1])
+        if name == 'conv_wgrad':
+            return not (args[6] == 9 and args[5] == self.base.convdet.in_channels)
+        return name in _BACKBONE_NAMES
+
+    def _padded_params(self, pad):
+        """The reference weights of a padded ConvDet: the module's own parameters, zero-extended here to the run width -- never the
+        stand-in's tensors (a stand-in that did not follow the parameters must fail)."""
+        src = pad.src
+        assert src is self.base.convdet
+        N, Npad = src.out_channels, pad.out_channels
+        w0, b0 = src.weight.detach(), src.bias.detach()
+        w = torch.zeros(Npad, *w0.shape[1:], device=w0.device, dtype=w0.dtype)
+        b = torch.zeros(Npad, device=b0.device, dtype=b0.dtype)
+        w[:N] = w0
+        b[:N] = b0
+        return w, b
+
     def _weights(self, plan):
         kind, mod, direction = self.plan_map[id(plan)]
         assert kind == 'conv'
+        if getattr(mod, 'src', None) is not None:           # (the plan-cache entry of the stand-in, mapped back to base.convdet)
+            w, b = self._padded_params(mod)
+            return (R.dgrad_weight(w), None) if direction != 'fwd' else (w, b)
         w = mod.weight.detach()
         if direction != 'fwd':
             return R.dgrad_weight(w), None
@@ -410,6 +458,69 @@ class _Harness:
         self._wgrad_pending(entry, slab, dyw, xc, 1)
         return res
 
+    @staticmethod
+    def _exact(ok):
+        return dict(exact=ok, l_ok=ok, p_ok=ok, l_ratio=0.0 if ok else float('inf'), p_block=0.0, p_tensor=0.0, k=0)
+
+    def convdet_pack(self, orig, y_pad, N, out=None):
+        """No arithmetic: the packed pred is bit-equal to the first N channels of the padded scratch, and the scratch is exactly 0.0
+        past them (a zero weight row with a zero bias is exact in every kernel form)."""
+        src = y_pad.clone()
+        n0 = len(self.timer.records)
+        res = orig(y_pad, N, out=out)
+        entry = self._entry(n0)
+        same = tuple(res.shape) == tuple(src.shape[:3]) + (N,) and res.is_contiguous() and bool(torch.equal(res, src[..., :N]))
+        zero = bool((src[..., N:] == 0).all()) and not bool(torch.signbit(src[..., N:]).any())
+        self.rows.setdefault(entry, []).extend([('pred', self._exact(same)), ('scratch past N', self._exact(zero))])
+        return res
+
+    def convdet_unpack(self, orig, dy, Npad):
+        src = dy.clone()
+        N = dy.shape[3]
+        n0 = len(self.timer.records)
+        res = orig(dy, Npad)
+        entry = self._entry(n0)
+        same = tuple(res.shape) == tuple(src.shape[:3]) + (Npad,) and bool(torch.equal(res[..., :N], src))
+        zero = bool((res[..., N:] == 0).all()) and not bool(torch.signbit(res[..., N:]).any())
+        self.rows.setdefault(entry, []).extend([('dpred', self._exact(same)), ('past N', self._exact(zero))])
+        return res
+
+    def wgrad_reduce_rows(self, orig, slab, S, N, Npad, C, taps, dw, db, scale=1.0):
+        """The padded ConvDet's own slab reduction: dw / db (the parameter-shaped views) against float64 on the TRUE dpred[..., :N],
+        b32 = the split-K restatement at the launch's own S, in the blocking of the kernel that wrote the slabs, the slabs added in
+        ascending order (csrc/convdet_pad.hip)."""
+        assert scale == 1.0
+        src, dy, x, taps_ = self.pending.pop(slab.data_ptr())
+        assert taps_ == taps and dy.shape[3] == Npad and x.shape[3] == C and tuple(dw.shape) == (N, C, 3 if taps == 9 else 1, 3 if taps == 9 else 1)
+        n0 = len(self.timer.records)
+        res = orig(slab, S, N, Npad, C, taps, dw, db, scale=scale)
+        entry = self._entry(n0)
+        checks = self._wgrad_checks(src, dy[..., :N].contiguous(), x, taps, S, N, C, Npad, dw, db, 'ascending')
+        for e in (src, entry):
+            self.rows.setdefault(e, []).extend(checks)
+        return res
+
+    def _wgrad_checks(self, src, dy, x, taps, S, N, C, Nrun, gw, gb, order):
+        """[(name, bars)] of one layer's reduced (dW, db) against float64 on (dy, x); ``Nrun``: the width the launch ran at (its tiles)."""
+        fam = family(src[2])
+        blocking, step = wgrad_blocking(fam, Nrun, C, taps)
+        kk = k_of(src[2])
+        dW, db = R.wgrad(dy, x, taps)
+        w32, b32 = R.wgrad_split_k(dy, x, taps, S, blocking, step, order=order)
+        dW, db = R.Ref(dW.ref64, dW.M, w32), R.Ref(db.ref64, db.M, b32)
+        if 'wino' in fam:
+            # bar L on the Winograd form's own magnitude (R.wgrad_wino_magnitude); the per-tap ratio is logged next to it
+            tap = R.bars(gw, dW, 'wgrad', kk)['l_ratio']
+            dW = R.Ref(dW.ref64, R.wgrad_wino_magnitude(dy, x), dW.b32)
+            bw = R.bars(gw, dW, 'wgrad', kk)
+            bw['l_ratio_tap'] = tap
+        else:
+            bw = R.bars(gw, dW, 'wgrad', kk)
+        if fam not in self.teeth and self._wants_teeth(fam):
+            self.teeth[fam] = {emu: R.bars(R.wgrad_split_k(dy, x, taps, S, blocking, step, emu, order=order)[0], dW, 'wgrad', kk)
+                               for emu in ('bf16', 'split3')}
+        return [(f'dW C{C} N{N} S{S}', bw), (f'db N{N} S{S}', R.bars(gb, db, 'vec', kk))]
+
     def stem_wgrad_pooled(self, orig, dpool, pooled, argmax, image, N, ksize, out=None):
         d, am, img = dpool.clone(), argmax.clone(), image.clone()
         n0 = len(self.timer.records)
@@ -424,8 +535,17 @@ class _Harness:
         for name, got, r, kind in outs:
             rows.append((name, R.bars_nan(got.cpu(), r, kind, 2)))
 
-    def _loss_fwd(self, orig, pred, gt, anchors, input_size, num_classes, weights, mean):
-        p, g, a = (t.detach().clone() for t in (pred, gt, anchors))
+    @staticmethod
+    def _dense_gt(gt, A, C):
+        """The launch's ground truth as the dense [B, A, C+9] tensor the reference reads (a sparse one: ``ops.sparse_gt_to_dense``)."""
+        from squeezedet_pytorch_amd import ops
+        if isinstance(gt, ops.SparseGT):
+            return ops.sparse_gt_to_dense(ops.SparseGT(*(t.detach().clone() for t in gt)), A, C)
+        return gt.detach().clone()
+
+    def _loss_fwd(self, orig, pred, gt, anchors, input_size, num_classes, weights, mean, teeth='loss_fwd'):
+        p, a = pred.detach().clone(), anchors.detach().clone()
+        g = self._dense_gt(gt, p.shape[1], num_classes)
         n0 = len(self.timer.records)
         res = orig(pred, gt, anchors, input_size, num_classes, weights)
         entry = self._entry(n0)
@@ -435,9 +555,9 @@ class _Harness:
         self._loss_rows(entry, outs)
         self.rows[entry].append(('nobj', dict(exact=nobj_exact, l_ok=nobj_exact, p_ok=nobj_exact, l_ratio=0.0, p_block=0.0,
                                                p_tensor=0.0, k=0)))
-        if 'loss_fwd' not in self.teeth and self._wants_teeth('loss_fwd'):
+        if teeth not in self.teeth and self._wants_teeth(teeth):
             l16 = R.loss_bf16(p, g, a, input_size, num_classes, weights)[0]
-            self.teeth['loss_fwd'] = {'bf16': R.bars(l16, ref['losses'], 'vec', 2)}
+            self.teeth[teeth] = {'bf16': R.bars(l16, ref['losses'], 'vec', 2)}
         return res
 
     def loss_fwd(self, orig, pred, gt, anchors, input_size, num_classes, weights):
@@ -446,8 +566,9 @@ class _Harness:
     def loss_mean_fwd(self, orig, pred, gt, anchors, input_size, num_classes, weights):
         return self._loss_fwd(orig, pred, gt, anchors, input_size, num_classes, weights, True)
 
-    def _loss_bwd(self, orig, args, input_size, num_classes, weights, gmean=None, coef=None):
-        p, g, a = (t.detach().clone() for t in args[:3])
+    def _loss_bwd(self, orig, args, input_size, num_classes, weights, gmean=None, coef=None, teeth='loss_bwd'):
+        p, a = args[0].detach().clone(), args[2].detach().clone()
+        g = self._dense_gt(args[1], p.shape[1], num_classes)
         n0 = len(self.timer.records)
         dpred = orig(*args, input_size, num_classes, weights)
         entry = self._entry(n0)
@@ -459,9 +580,9 @@ class _Harness:
         print(f'{entry[2]} {entry[3]}: {flips} anchors where float64 and float32 take different branches')
         self.rows[entry].append(('flips', dict(exact=flips <= 4, l_ok=flips <= 4, p_ok=True, l_ratio=0.0, p_block=0.0, p_tensor=0.0,
                                                 k=0, flips=flips)))
-        if 'loss_bwd' not in self.teeth and self._wants_teeth('loss_bwd'):
+        if teeth not in self.teeth and self._wants_teeth(teeth):
             d16 = R.loss_bf16(p, g, a, input_size, num_classes, weights, gmean=gmean, coef=coef)[1 if gmean is not None else 2]
-            self.teeth['loss_bwd'] = {'bf16': R.bars(d16, ref[name], 'dpred', 2)}
+            self.teeth[teeth] = {'bf16': R.bars(d16, ref[name], 'dpred', 2)}
         return dpred
 
     def loss_mean_bwd(self, orig, pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
@@ -469,6 +590,36 @@ class _Harness:
 
     def loss_bwd(self, orig, pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
         return self._loss_bwd(orig, (pred, gt, anchors, nobj, coef), input_size, num_classes, weights, coef=coef.detach().cpu())
+
+    # the many-class (17 .. 256 classes: ``ops.loss_fns``) and the sparse-ground-truth launches: the same checks on the same reference
+    # (a sparse gt through ``ops.sparse_gt_to_dense``); their teeth are kept under their own names
+    def loss_fwd_many(self, orig, pred, gt, anchors, input_size, num_classes, weights):
+        return self._loss_fwd(orig, pred, gt, anchors, input_size, num_classes, weights, False, 'loss_fwd_many')
+
+    def loss_mean_fwd_many(self, orig, pred, gt, anchors, input_size, num_classes, weights):
+        return self._loss_fwd(orig, pred, gt, anchors, input_size, num_classes, weights, True, 'loss_fwd_many')
+
+    def loss_mean_bwd_many(self, orig, pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
+        return self._loss_bwd(orig, (pred, gt, anchors, nobj, gmean), input_size, num_classes, weights, gmean=float(gmean.reshape(-1)[0]),
+                              teeth='loss_bwd_many')
+
+    def loss_bwd_many(self, orig, pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
+        return self._loss_bwd(orig, (pred, gt, anchors, nobj, coef), input_size, num_classes, weights, coef=coef.detach().cpu(),
+                              teeth='loss_bwd_many')
+
+    def loss_sparse_fwd(self, orig, pred, sgt, anchors, input_size, num_classes, weights):
+        return self._loss_fwd(orig, pred, sgt, anchors, input_size, num_classes, weights, False, 'loss_sparse_fwd')
+
+    def loss_sparse_mean_fwd(self, orig, pred, sgt, anchors, input_size, num_classes, weights):
+        return self._loss_fwd(orig, pred, sgt, anchors, input_size, num_classes, weights, True, 'loss_sparse_fwd')
+
+    def loss_sparse_mean_bwd(self, orig, pred, sgt, anchors, nobj, gmean, input_size, num_classes, weights):
+        return self._loss_bwd(orig, (pred, sgt, anchors, nobj, gmean), input_size, num_classes, weights, gmean=float(gmean.reshape(-1)[0]),
+                              teeth='loss_sparse_bwd')
+
+    def loss_sparse_bwd(self, orig, pred, sgt, anchors, nobj, coef, input_size, num_classes, weights):
+        return self._loss_bwd(orig, (pred, sgt, anchors, nobj, coef), input_size, num_classes, weights, coef=coef.detach().cpu(),
+                              teeth='loss_sparse_bwd')
 
     def reduce(self, orig, wb, grad_flat, row_lo=0, row_hi=None, scale=1.0):
         """After the slab reduction: every layer's (dW, db) against float64, b32 = the split-K restatement with the layer's own S."""
@@ -481,49 +632,64 @@ class _Harness:
         base_ptr = wb.workspace.data_ptr()
         for slab_off, dw_off, db_off, S, _stride, N, C, taps, _blk in rows[row_lo:row_hi]:
             k = 3 if taps == 9 else 1
+            if self.check_from is not None and base_ptr + 4 * slab_off not in self.pending:
+                continue                                     # (a backbone layer, passed through unchecked)
             src, dy, x, taps_ = self.pending.pop(base_ptr + 4 * slab_off)
             assert taps_ == taps and tuple(dy.shape[3:]) == (N,) and x.shape[3] == C
-            fam = family(src[2])
-            blocking, step = wgrad_blocking(fam, N, C, taps)
-            kk = k_of(src[2])
-            dW, db = R.wgrad(dy, x, taps)
-            w32, b32 = R.wgrad_split_k(dy, x, taps, S, blocking, step)
-            dW, db = R.Ref(dW.ref64, dW.M, w32), R.Ref(db.ref64, db.M, b32)
             gw = grad_flat[dw_off:dw_off + N * C * taps].view(N, C, k, k)
             gb = grad_flat[db_off:db_off + N]
-            checks = []
-            if 'wino' in fam:
-                # bar L on the Winograd form's own magnitude (R.wgrad_wino_magnitude); the per-tap ratio is logged next to it
-                tap = R.bars(gw, dW, 'wgrad', kk)['l_ratio']
-                dW = R.Ref(dW.ref64, R.wgrad_wino_magnitude(dy, x), dW.b32)
-                bw = R.bars(gw, dW, 'wgrad', kk)
-                bw['l_ratio_tap'] = tap
-            else:
-                bw = R.bars(gw, dW, 'wgrad', kk)
-            checks = [(f'dW C{C} N{N} S{S}', bw), (f'db N{N} S{S}', R.bars(gb, db, 'vec', kk))]
+            checks = self._wgrad_checks(src, dy, x, taps, S, N, C, N, gw, gb, 'batched')
             for e in (src, entry):
                 self.rows.setdefault(e, []).extend(checks)
-            if fam not in self.teeth and self._wants_teeth(fam):
-                self.teeth[fam] = {emu: R.bars(R.wgrad_split_k(dy, x, taps, S, blocking, step, emu)[0], dW, 'wgrad', kk)
-                                   for emu in ('bf16', 'split3')}
-            del dy, x, dW, db
+            del dy, x
         return res
 
 
 _NAMES = ('conv', 'conv_wino', 'fire_expand', 'fire_bridge', 'fire_pool_bridge', 'stem_pool', 'stem_pool_squeeze', 'maxpool', 'maxpool_bwd',
           'conv_wgrad', 'conv_wgrad_group', 'conv_wgrad_wino_group', 'squeeze_bwd', 'stem_wgrad_pooled',
-          'loss_fwd', 'loss_mean_fwd', 'loss_bwd', 'loss_mean_bwd')
+          'loss_fwd', 'loss_mean_fwd', 'loss_bwd', 'loss_mean_bwd',
+          'convdet_pack', 'convdet_unpack', 'wgrad_reduce_rows', 'loss_fwd_many', 'loss_mean_fwd_many', 'loss_bwd_many', 'loss_mean_bwd_many',
+          'loss_sparse_fwd', 'loss_sparse_mean_fwd', 'loss_sparse_bwd', 'loss_sparse_mean_bwd')
+# what ``check_from='convdet'`` passes through unchecked whatever its operands (``_Harness.passes``): the backbone alone calls these
+_BACKBONE_NAMES = ('fire_expand', 'fire_bridge', 'fire_pool_bridge', 'stem_pool', 'stem_pool_squeeze', 'maxpool', 'maxpool_bwd',
+                   'conv_wgrad_group', 'conv_wgrad_wino_group', 'squeeze_bwd', 'stem_wgrad_pooled')
 
 
-def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None):
+def anchors_seed(k):
+    """An anchor seed of k shapes: the first k rows of the KITTI nine; past nine, the nine again times 2, 3, ... (distinct shapes)."""
+    import numpy as np
+    from squeezedet_pytorch_amd.boxes import KITTI_ANCHORS_SEED
+    base = np.asarray(KITTI_ANCHORS_SEED)
+    return np.concatenate([base * (1 + j) for j in range(-(-k // len(base)))])[:k]
+
+
+def _head_kwargs(num_classes, seed, sparse_gt):
+    """The keyword arguments of the class / anchor / gt axis for ``make_cfg``, ``make_state_dict``, ``make_gt`` and the planners: all
+    empty at the defaults (3 classes, the KITTI nine, dense gt), so that a default point calls everything exactly as before."""
+    import numpy as np
+    cfg_kw, sd_kw, gt_kw, plan_kw = {}, {}, {}, {}
+    if num_classes != 3:
+        cfg_kw['num_classes'] = sd_kw['num_classes'] = gt_kw['num_classes'] = plan_kw['num_classes'] = int(num_classes)
+    if seed is not None:
+        cfg_kw['anchors_seed'] = np.asarray(seed)
+        sd_kw['anchors_per_grid'] = plan_kw['anchors_per_grid'] = int(np.asarray(seed).shape[0])
+    if sparse_gt:
+        cfg_kw['sparse_gt'] = True
+    return cfg_kw, sd_kw, gt_kw, plan_kw
+
+
+def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None, num_classes=3, anchors_seed=None, sparse_gt=False, check_from=None):
     """One step at ``size`` (the benchmarked one by default; the same seeds as bench.py) with every GEMM-type launch checked.
+    ``num_classes`` / ``anchors_seed`` (None: the KITTI nine) / ``sparse_gt``: the head axis, which decides ConvDet's width
+    anchors_per_grid * (num_classes + 5) and the loss launches; ``check_from``: ``_Harness.passes``.
     -> (harness, [(kernel, tag)] recorded)."""
     from squeezedet_pytorch_amd import ops, plans as plans_mod
     from squeezedet_pytorch_amd.detector import Detector
     from squeezedet_pytorch_amd.model import SqueezeDet, SqueezeDetWithLoss
     torch.manual_seed(0)
-    cfg = sqd.make_cfg(arch=arch, input_size=size, device='cuda')
-    sd = synthetic.make_state_dict(arch, seed=1234)
+    cfg_kw, sd_kw, gt_kw, _ = _head_kwargs(num_classes, anchors_seed, sparse_gt)
+    cfg = sqd.make_cfg(arch=arch, input_size=size, device='cuda', **cfg_kw)
+    sd = synthetic.make_state_dict(arch, seed=1234, **sd_kw)
     x = synthetic.make_images(batch, size, seed=0).cuda()
     if mode == 'train':
         m = SqueezeDetWithLoss(cfg)
@@ -531,7 +697,9 @@ def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None):
         m = m.cuda().train()
         base = m.base
         base.dropout_prob = 0.0          # the planned dropout epilogues with an all-keep mask
-        batch_d = {'image': x, 'gt': synthetic.make_gt(batch, cfg.anchors, size, seed=gt_seed).cuda()}
+        batch_d = {'image': x, 'gt': synthetic.make_gt(batch, cfg.anchors, size, seed=gt_seed, **gt_kw).cuda()}
+        if sparse_gt:                    # the positives as a list: the sparse loss launches, no dense gt in the step
+            batch_d = {'image': x, 'gt_sparse': ops.sparse_gt_from_dense(batch_d['gt'])}
 
         def step():                      # bench.py's form (trainer.make_train_step): the mean and its backward in the loss launches
             loss, _ = m.forward_mean(batch_d)
@@ -548,11 +716,11 @@ def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None):
     step()                                # plans are packed here, outside the checked pass
     torch.cuda.synchronize()
     timer = ops.KernelTimer()
-    h = _Harness(base, arch, batch, timer, teeth_for)
+    h = _Harness(base, arch, batch, timer, teeth_for, check_from)
     saved = {n: getattr(ops, n) for n in _NAMES}
     red = plans_mod.WgradBatch.reduce
     for n in _NAMES:
-        setattr(ops, n, (lambda meth, orig: lambda *a, **kw: meth(orig, *a, **kw))(getattr(h, n), saved[n]))
+        setattr(ops, n, (lambda n, meth, orig: lambda *a, **kw: orig(*a, **kw) if h.passes(n, a) else meth(orig, *a, **kw))(n, getattr(h, n), saved[n]))
     plans_mod.WgradBatch.reduce = lambda wb, *a, **kw: h.reduce(red, wb, *a, **kw)
     ops.set_timer(timer)
     try:
@@ -570,15 +738,20 @@ def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None):
 _STATE = {}
 
 
-def _step_results(arch, batch, size=INPUT, swap=None, gt_seed=1, teeth_for=None):
+def _step_results(arch, batch, size=INPUT, swap=None, gt_seed=1, teeth_for=None, num_classes=3, anchors_seed=None, sparse_gt=False,
+                  check_from=None):
     """{(arch, batch, kernel, tag): rows} of the inference and the training step of ``arch`` at ``size`` (run once per process; a failure
     is kept and raised again for every case of that point instead of re-running the steps).  ``swap``: a context manager factory that
     replaces look-ups of ``ops`` for the two steps and the plans they are compared with (forced kernel forms); ``gt_seed``: the
-    ground-truth seed of the training step; ``teeth_for``: the families that also run the degraded emulations (None: all)."""
+    ground-truth seed of the training step; ``teeth_for``: the families that also run the degraded emulations (None: all);
+    ``num_classes`` / ``anchors_seed`` / ``sparse_gt`` / ``check_from``: ``_run_step`` (a default point keeps its key)."""
     key = (arch, batch, tuple(size)) if swap is None else (arch, batch, tuple(size), swap.__name__)
+    if (num_classes, anchors_seed is None, bool(sparse_gt), check_from) != (3, True, False, None):
+        seed_key = None if anchors_seed is None else tuple(map(tuple, anchors_seed))
+        key += (int(num_classes), seed_key, bool(sparse_gt), check_from)
     if key not in _STATE:
         try:
-            _STATE[key] = _run_both(arch, batch, tuple(size), swap, gt_seed, teeth_for)
+            _STATE[key] = _run_both(arch, batch, tuple(size), swap, gt_seed, teeth_for, num_classes, anchors_seed, sparse_gt, check_from)
         except Exception as exc:            # noqa: BLE001 -- re-raised below, and by every later case of this arch
             _STATE[key] = exc
     res = _STATE[key]
@@ -587,15 +760,17 @@ def _step_results(arch, batch, size=INPUT, swap=None, gt_seed=1, teeth_for=None)
     return res
 
 
-def _run_both(arch, batch, size=INPUT, swap=None, gt_seed=1, teeth_for=None):
+def _run_both(arch, batch, size=INPUT, swap=None, gt_seed=1, teeth_for=None, num_classes=3, anchors_seed=None, sparse_gt=False,
+              check_from=None):
     if swap is not None:
         with swap():
-            return _run_both(arch, batch, size, None, gt_seed, teeth_for)
+            return _run_both(arch, batch, size, None, gt_seed, teeth_for, num_classes, anchors_seed, sparse_gt, check_from)
     from squeezedet_pytorch_amd import plan
     rows, teeth = {}, {}
+    plan_kw = _head_kwargs(num_classes, anchors_seed, sparse_gt)[3]
     for mode, planner in (('infer', plan.inference_launch_plan), ('train', plan.training_launch_plan)):
-        h, got = _run_step(arch, batch, mode, size, gt_seed, teeth_for)
-        want = planner(arch, batch, size)
+        h, got = _run_step(arch, batch, mode, size, gt_seed, teeth_for, num_classes, anchors_seed, sparse_gt, check_from)
+        want = planner(arch, batch, size, **plan_kw, **({'sparse_gt': True} if (sparse_gt and mode == 'train') else {}))
         assert got == want, [(i, a, b) for i, (a, b) in enumerate(zip(got, want)) if a != b][:4] + [len(got), len(want)]
         for e, r in h.rows.items():
             rows.setdefault(e, []).extend(r)

@@ -31,6 +31,10 @@ read the same look-ups, so the launches still equal the plan.  What the swap can
 * ``conv_wino_us`` on layers with more than 128 input channels: the U-stationary LDS plan (``wino_cfg_ok``) does not fit; they run
   ``conv_wino<2,4>`` there.  ``conv_wino_vs`` has the plain bias / ReLU epilogue and N <= 80: ConvDet's forward only.
 
+Every point here runs 3 classes on KITTI's nine anchors with a dense ground truth, so ConvDet is 72 channels wide throughout: the class /
+anchor-count / sparse-gt axis, which decides ConvDet's own launches and the loss kernels, is tests/test_fp64_widths_gpu.py's, on the
+backbone of the two 70x100 points here.
+
 ``test_every_compiled_tiling``: every configuration id the library compiles (``ops.cfg_table()`` / ``ops.wino_cfgs()``), whether or not a
 plan names it, through ``ops.conv`` / ``ops.conv_wino`` on one small ragged shape per tap count, with and without a workgroup cap, into
 a channel window of a NaN-filled buffer, against ``fp64_ref.conv`` under the same bars.
