@@ -542,6 +542,33 @@ int sqd_sgd_clip_step_chunked(const void* descs_dev, const void* chunks_dev, int
                               const float* sumsq_parts, float* norm_out, float max_norm, float lr, float momentum, float weight_decay,
                               void* stream);
 
+/* Detection AP on the device (VOC / COCO style, any class count; DESIGN.md "Detection AP on the device").
+ * sqd_det_match_fwd labels every slot of the packed detect output of a batch -- count [B] int32, class_ids [B][K] int64, scores [B][K],
+ * boxes [B][K][4] fp32 xyxy (16-byte aligned), 1 <= K <= 1024 -- against the ground truth gt_boxes [total][4] fp32 xyxy (16-byte
+ * aligned), gt_class_ids [total] int32, gt_offsets [B+1] int32 (image b owns gt_offsets[b] .. gt_offsets[b+1], at most 65 535 entries;
+ * values are clamped to [0, total]), gt_ignore [total] uint8 or NULL (VOC "difficult", COCO "crowd"), at thresholds [T] float64 in
+ * DEVICE memory, 1 <= T <= 16, for 1 <= num_classes <= 256.  flags uint8 [B][K][T]: 0 false positive, 1 true positive, 2 ignored,
+ * 3 empty slot (k >= count[b]); matched_gt int32 [B][K][T]: global GT index or -1; npos int32 [num_classes]: the non-ignored GT
+ * per class are ADDED (integer atomics).  Rule, per image, class and threshold: detections in descending score (equal scores: lower
+ * slot first; the input need not be sorted) each take the unclaimed, non-ignored GT of their class with the highest float64 IoU (equal
+ * IoU: lowest index): IoU >= t -> true positive, the GT is claimed; else an ignored GT with IoU >= t -> ignored (never claimed);
+ * else false positive.  A detection class outside [0, num_classes) is a false positive, a GT class outside it is skipped.
+ * total = 0 allows NULL gt_boxes / gt_class_ids.
+ * sqd_det_ap_fwd: class_ids int32 [N] (num_classes = empty slot), flags uint8 [N][T] of the accumulated detections ordered by (class
+ * ascending, score descending, insertion order ascending), seg_offsets int32 [num_classes+1] (class c owns seg_offsets[c] ..
+ * seg_offsets[c+1]), npos int32 [num_classes]; mode 0 = area under the monotone precision envelope, 1 = 11-point, 2 = 101-point.
+ * ap float64 [num_classes][T] (NaN where npos <= 0); tp_cum / fp_cum int32 [N][T]: running counts within a class's segment (ignored
+ * and empty entries count as neither; entries outside every segment are not written); prec101 float64 [num_classes][T][101] or
+ * NULL: the sampled precisions, written in mode 2.  N = 0 allows NULL class_ids / flags / tp_cum / fp_cum.
+ * Status 1 for a NULL or misaligned pointer, T outside 1..16, num_classes outside 1..256, K outside 1..1024, B < 1, a negative size or a
+ * mode outside 0..2, before any launch. */
+int sqd_det_match_fwd(const int* count, const long long* class_ids, const float* scores, const float* boxes, const float* gt_boxes,
+                      const int* gt_class_ids, const int* gt_offsets, const unsigned char* gt_ignore, const double* thresholds,
+                      unsigned char* flags, int* matched_gt, int* npos, int B, int K, int total, int T, int num_classes,
+                      void* stream);
+int sqd_det_ap_fwd(const int* class_ids, const unsigned char* flags, const int* seg_offsets, const int* npos, double* ap, int* tp_cum,
+                   int* fp_cum, double* prec101, int N, int T, int num_classes, int mode, void* stream);
+
 
 #ifdef __cplusplus
 }

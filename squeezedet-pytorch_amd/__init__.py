@@ -8,5 +8,6 @@ CPU fallback in the product path.
 from . import boxes, config, synthetic  # noqa: F401
 from .config import make_cfg  # noqa: F401
 from .dataset_stats import compute_dataset_anchors_seed, compute_dataset_mean_and_std  # noqa: F401
+from .metrics import DetectionAP, evaluate_results  # noqa: F401
 
 __version__ = "0.1.0"

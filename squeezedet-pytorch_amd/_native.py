@@ -110,6 +110,8 @@ _SIGNATURES = {
     'sqd_loss_sparse_bwd': [c_p] * 10 + [c_i] * 6 + [c_f] * 4 + [c_p],
     'sqd_loss_sparse_mean_fwd': [c_p] * 11 + [c_i] * 6 + [c_f] * 4 + [c_p],
     'sqd_loss_sparse_mean_bwd': [c_p] * 10 + [c_i] * 6 + [c_f] * 4 + [c_p],
+    'sqd_det_match_fwd': [c_p] * 12 + [c_i] * 5 + [c_p],
+    'sqd_det_ap_fwd': [c_p] * 8 + [c_i] * 4 + [c_p],
 }
 # symbols added by later build stages; bound when present in the library
 _OPTIONAL = {}

@@ -1503,3 +1503,139 @@ def image_stats_u8(dev_buf, B, hdr, out=None):
     if br is not None:
         br.done()
     return out
+
+
+DET_EVAL_MAX_T = 16            # det_match / det_ap: one lane per IoU threshold, a uint16 claim per (detection, threshold)
+DET_EVAL_MAX_CLASSES = 256
+DET_EVAL_MAX_K = 1024
+DET_EVAL_MAX_GT = 65535        # per image: claims are uint16 indices within the image
+AP_MODES = {'area': 0, '11point': 1, '101point': 2}
+
+
+def _check_det_eval_sizes(name, T, num_classes):
+    if not 1 <= int(T) <= DET_EVAL_MAX_T:
+        raise ValueError(f'{name}: {T} IoU thresholds, the limit is 1..{DET_EVAL_MAX_T}')
+    if not 1 <= int(num_classes) <= DET_EVAL_MAX_CLASSES:
+        raise ValueError(f'{name}: num_classes {num_classes} outside 1..{DET_EVAL_MAX_CLASSES}')
+
+
+def det_thresholds(iou_thresholds, device):
+    """The IoU thresholds as the float64 [T] device tensor ``det_match`` reads (a tensor of that kind passes through)."""
+    if isinstance(iou_thresholds, torch.Tensor):
+        thr = iou_thresholds
+    else:
+        thr = torch.tensor([float(t) for t in iou_thresholds], dtype=torch.float64)
+        if torch.device(device).type == 'cuda':
+            thr = thr.pin_memory()                         # (an upload nothing waits for)
+    if thr.dim() != 1 or thr.dtype != torch.float64:
+        raise ValueError('det_match: iou_thresholds must be a sequence of floats or a float64 [T] tensor')
+    return thr.to(device, non_blocking=True).contiguous()
+
+
+def det_match(det, gt_boxes, gt_class_ids, gt_offsets, iou_thresholds, num_classes, gt_ignore=None, npos=None):
+    """Label the packed detect output of a batch against its ground truth (csrc/det_eval.hip; rule: DESIGN.md "Detection AP on the
+    device").  ``det``: the tuple of ``detect`` / ``Detector.detect_device`` (count int32 [B], class_ids int64 [B,K], scores [B,K],
+    boxes [B,K,4]; further members are not read), K <= 1024.  gt_boxes fp32 [total,4] xyxy, gt_class_ids int32 [total], gt_offsets
+    int32 [B+1] (at most 65 535 GT per image), gt_ignore uint8 / bool [total] or None, iou_thresholds: 1..16 floats (or a float64
+    device tensor), num_classes 1..256.  -> (flags uint8 [B,K,T]: 0 FP, 1 TP, 2 ignored, 3 empty slot; matched_gt int32 [B,K,T];
+    npos int32 [num_classes]).  ``npos``: an int32 [num_classes] device tensor the counts are ADDED to (default: fresh zeros).
+    One launch, nothing waits."""
+    if len(det) < 4:
+        raise ValueError('det_match: det must be (count, class_ids, scores, boxes, ...)')
+    cnt, cls, sc, bx = det[:4]
+    for t, nm, dt in ((cnt, 'count', torch.int32), (cls, 'class_ids', torch.int64), (sc, 'scores', torch.float32), (bx, 'boxes', torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f'det_match: det {nm} must be a {dt} tensor')
+    if sc.dim() != 2 or tuple(cls.shape) != tuple(sc.shape) or tuple(bx.shape) != tuple(sc.shape) + (4,) or tuple(cnt.shape) != (sc.shape[0],):
+        raise ValueError(f'det_match: det must be count [B], class_ids [B,K], scores [B,K], boxes [B,K,4], got {tuple(cnt.shape)} '
+                         f'{tuple(cls.shape)} {tuple(sc.shape)} {tuple(bx.shape)}')
+    B, K = sc.shape
+    if B < 1 or not 1 <= K <= DET_EVAL_MAX_K:
+        raise ValueError(f'det_match: B = {B}, K = {K}: need B >= 1 and 1 <= K <= {DET_EVAL_MAX_K}')
+    for t, nm, dt in ((gt_boxes, 'gt_boxes', torch.float32), (gt_class_ids, 'gt_class_ids', torch.int32), (gt_offsets, 'gt_offsets', torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f'det_match: {nm} must be a {dt} tensor')
+    total = gt_class_ids.shape[0] if gt_class_ids.dim() == 1 else -1
+    if total < 0 or tuple(gt_boxes.shape) != (total, 4) or tuple(gt_offsets.shape) != (B + 1,):
+        raise ValueError(f'det_match: gt_boxes [total,4], gt_class_ids [total], gt_offsets [B+1] = [{B + 1}], got {tuple(gt_boxes.shape)} '
+                         f'{tuple(gt_class_ids.shape)} {tuple(gt_offsets.shape)}')
+    if gt_ignore is not None:
+        if not isinstance(gt_ignore, torch.Tensor) or gt_ignore.dtype not in (torch.uint8, torch.bool) or tuple(gt_ignore.shape) != (total,):
+            raise ValueError('det_match: gt_ignore must be a uint8 or bool [total] tensor')
+        gt_ignore = gt_ignore.view(torch.uint8) if gt_ignore.dtype == torch.bool else gt_ignore
+    if not sc.is_cuda:
+        raise ValueError(f'det_match: det must be on the GPU, got {sc.device}')
+    dev = sc.device
+    thr = det_thresholds(iou_thresholds, dev)
+    T = thr.shape[0]
+    _check_det_eval_sizes('det_match', T, num_classes)
+    num_classes = int(num_classes)
+    if npos is None:
+        npos = torch.zeros(num_classes, device=dev, dtype=torch.int32)
+    elif not isinstance(npos, torch.Tensor) or npos.dtype != torch.int32 or tuple(npos.shape) != (num_classes,) or not npos.is_contiguous():
+        raise ValueError('det_match: npos must be a contiguous int32 [num_classes] tensor')
+    for t, nm in ((cnt, 'count'), (cls, 'class_ids'), (bx, 'boxes'), (gt_boxes, 'gt_boxes'), (gt_class_ids, 'gt_class_ids'),
+                  (gt_offsets, 'gt_offsets'), (gt_ignore, 'gt_ignore'), (npos, 'npos')):
+        if t is not None and t.device != dev:
+            raise ValueError(f'det_match: {nm} is on {t.device}, the detections on {dev}')
+    cnt, cls, sc, bx, gt_boxes, gt_class_ids, gt_offsets = (t.contiguous() for t in (cnt, cls, sc, bx, gt_boxes, gt_class_ids, gt_offsets))
+    if bx.data_ptr() % 16:
+        bx = bx.clone()
+    if gt_boxes.data_ptr() % 16:
+        gt_boxes = gt_boxes.clone()
+    if gt_ignore is not None:
+        gt_ignore = gt_ignore.contiguous()
+    flags = torch.empty(B, K, T, device=dev, dtype=torch.uint8)
+    matched = torch.empty(B, K, T, device=dev, dtype=torch.int32)
+    br = _Bracket('det_match', f'match K{K} T{T}', 0.0, 24.0 * B * K + 21.0 * total + 5.0 * B * K * T) if timing._timer is not None else None
+    rc = nat.lib().sqd_det_match_fwd(nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(gt_boxes) if total else None,
+                                     nat.ptr(gt_class_ids) if total else None, nat.ptr(gt_offsets),
+                                     nat.ptr(gt_ignore) if total else None, nat.ptr(thr), nat.ptr(flags), nat.ptr(matched), nat.ptr(npos),
+                                     B, K, int(total), T, num_classes, nat.stream_handle(dev))
+    nat.check(rc, 'sqd_det_match_fwd')
+    if br is not None:
+        br.done()
+    return flags, matched, npos
+
+
+def det_ap(class_ids, flags, seg_offsets, npos, mode, want_prec101=False):
+    """Average precision per class and threshold from the accumulated, ORDERED labels (csrc/det_eval.hip): class_ids int32 [N]
+    (``num_classes`` = empty slot), flags uint8 [N,T], ordered by (class ascending, score descending, insertion order); seg_offsets
+    int32 [num_classes+1]; npos int32 [num_classes]; mode 'area' / 0 (area under the monotone precision envelope), '11point' / 1,
+    '101point' / 2.  -> (ap float64 [num_classes,T], NaN where npos == 0; tp_cum, fp_cum int32 [N,T], zero outside the segments;
+    prec101 float64 [num_classes,T,101] in mode 2 with ``want_prec101``, else None).  1 <= T <= 16, num_classes <= 256.  One launch."""
+    mode = AP_MODES.get(mode, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError(f"det_ap: mode must be one of {sorted(AP_MODES)} or 0 / 1 / 2, got {mode!r}")
+    for t, nm, dt in ((class_ids, 'class_ids', torch.int32), (flags, 'flags', torch.uint8), (seg_offsets, 'seg_offsets', torch.int32),
+                      (npos, 'npos', torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f'det_ap: {nm} must be a {dt} tensor')
+    if class_ids.dim() != 1 or flags.dim() != 2 or flags.shape[0] != class_ids.shape[0] or npos.dim() != 1:
+        raise ValueError(f'det_ap: class_ids [N], flags [N,T], npos [num_classes], got {tuple(class_ids.shape)} {tuple(flags.shape)} {tuple(npos.shape)}')
+    N, T = flags.shape
+    C = npos.shape[0]
+    _check_det_eval_sizes('det_ap', T, C)
+    if tuple(seg_offsets.shape) != (C + 1,):
+        raise ValueError(f'det_ap: seg_offsets must be [num_classes+1] = [{C + 1}], got {tuple(seg_offsets.shape)}')
+    if N * T >= 2 ** 31:
+        raise ValueError(f'det_ap: N * T = {N * T} exceeds 2^31 - 1')
+    if not flags.is_cuda:
+        raise ValueError(f'det_ap: flags must be on the GPU, got {flags.device}')
+    dev = flags.device
+    for t, nm in ((class_ids, 'class_ids'), (seg_offsets, 'seg_offsets'), (npos, 'npos')):
+        if t.device != dev:
+            raise ValueError(f'det_ap: {nm} is on {t.device}, flags on {dev}')
+    class_ids, flags, seg_offsets, npos = class_ids.contiguous(), flags.contiguous(), seg_offsets.contiguous(), npos.contiguous()
+    ap = torch.empty(C, T, device=dev, dtype=torch.float64)
+    tp_cum = torch.zeros(N, T, device=dev, dtype=torch.int32)
+    fp_cum = torch.zeros(N, T, device=dev, dtype=torch.int32)
+    prec = torch.empty(C, T, 101, device=dev, dtype=torch.float64) if (want_prec101 and mode == 2) else None
+    br = _Bracket('det_ap', f'ap N{N} T{T}', 0.0, 4.0 * N + 21.0 * N * T) if timing._timer is not None else None
+    rc = nat.lib().sqd_det_ap_fwd(nat.ptr(class_ids) if N else None, nat.ptr(flags) if N else None, nat.ptr(seg_offsets), nat.ptr(npos),
+                                  nat.ptr(ap), nat.ptr(tp_cum) if N else None, nat.ptr(fp_cum) if N else None, nat.ptr(prec),
+                                  N, T, C, mode, nat.stream_handle(dev))
+    nat.check(rc, 'sqd_det_ap_fwd')
+    if br is not None:
+        br.done()
+    return ap, tp_cum, fp_cum, prec
