@@ -281,6 +281,21 @@ int sqd_preprocess_u8_padcrop_aug_fwd(const unsigned char* src, const long long*
                                       float* shifts, int* padcrop, const float* mean3, const float* std3, int B, int H, int W,
                                       void* stream);
 
+/* Colour forms of the two training entry points: per-image brightness / contrast / saturation jitter on the SOURCE pixels, inside the
+ * same launch ("Colour jitter").  color: DEVICE fp32 [B][3] = (fb, fc, fs); sums: DEVICE uint64 [B][3][2] exactly as
+ * sqd_image_stats_u8 writes it for the same src / offsets / sizes, enqueued before this call on the same stream (8-byte aligned).  With
+ * g = (0.299 Sr + 0.587 Sg + 0.114 Sb) / (H0 W0) (float64 from the exact sums, rounded to float32 once) and p = min(fb g, 255), in float32:
+ * t(v) = clamp(fc min(fb v, 255) + (1 - fc) p, 0, 255) per source byte, y = 0.299 t(r) + 0.587 t(g) + 0.114 t(b) per tap,
+ * c' = clamp(fs t(c) + (1 - fs) y, 0, 255), then (c' - mean) / std.  Fill taps stay 0.0f; geometry, scales, padding / crops / shifts are
+ * those of the _aug_ entry points.  Both pointers are required (NULL: bad argument, nothing is launched).  color = (1, 1, 1) everywhere
+ * gives the results of sqd_preprocess_u8_aug_fwd / sqd_preprocess_u8_padcrop_aug_fwd bit for bit. */
+int sqd_preprocess_u8_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                    const float* color, const unsigned long long* sums, float* out, float* scales, const float* mean3,
+                                    const float* std3, int B, int H, int W, void* stream);
+int sqd_preprocess_u8_padcrop_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                            const float* color, const unsigned long long* sums, float* out, float* shifts, int* padcrop,
+                                            const float* mean3, const float* std3, int B, int H, int W, void* stream);
+
 /* Dataset statistics (src/utils/compute_dataset_mean_and_std.py:35-41 computes torch.mean / torch.std per image in float32; here
  * the exact integer sums they follow from): for a packed batch of uint8 HWC RGB images -- src, offsets [B] (bytes from src, no
  * alignment required), sizes [B][2] = (H, W), exactly as sqd_preprocess_u8_fwd takes them -- sums [B][3][2] uint64 = per image and

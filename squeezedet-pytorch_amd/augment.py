@@ -10,6 +10,11 @@ whitens, drifts, flips, resizes (or pads / crops) and transposes the whole batch
 Two departures, both where the reference raises instead: an image without boxes draws its drift with the reference's
 ``boxes is None`` bound (``max_boxes = max_drift``); an axis whose ``randint`` range is empty (an image under 4 rows or 8 columns)
 gets drift 0 on that axis and consumes no draw for it.
+
+Colour jitter (this project's own rule, DESIGN.md 6b "Colour jitter"; off by default): per-image brightness / contrast / saturation
+factors (``draw_color``) ride in the header of the same upload; ``launch`` then sums the image's channels on the device
+(``sqd_image_stats_u8``, the contrast pivot) and calls the colour entry points (``sqd_preprocess_u8_aug_color_fwd`` /
+``sqd_preprocess_u8_padcrop_aug_color_fwd``) on the same stream.  The boxes and the geometric draws do not depend on it.
 """
 from __future__ import annotations
 
@@ -52,6 +57,28 @@ def draw_augmentation(rng, orig_sizes, boxes_list, drift_prob, flip_prob):
                     aug[i, k] = rng.randint(lo, hi)
         aug[i, 2] = rng.uniform() < flip_prob
     return aug
+
+
+def draw_color(rng, n, brightness, contrast, saturation):
+    """Colour factors of ``n`` images, float32 [n, 3] = (brightness, contrast, saturation).  Per image, in that order, one
+    ``rng.uniform(max(0, 1 - d), 1 + d)`` for each axis whose jitter ``d`` is > 0; an axis with ``d == 0`` is 1.0 and draws nothing."""
+    ds = [float(brightness), float(contrast), float(saturation)]
+    if any(not np.isfinite(d) or d < 0 for d in ds):
+        raise ValueError(f'draw_color: jitter amounts must be finite and >= 0, got {ds}')
+    color = np.ones((int(n), 3), dtype=np.float32)
+    for i in range(int(n)):
+        for k, d in enumerate(ds):
+            if d > 0:
+                color[i, k] = rng.uniform(max(0., 1. - d), 1. + d)
+    return color
+
+
+def check_color(color, B):
+    """``color`` as float32 [B, 3]; the factors must be finite and >= 0."""
+    color = np.ascontiguousarray(np.asarray(color, np.float32)).reshape(-1)
+    if color.size != 3 * B or not np.all(np.isfinite(color)) or np.any(color < 0):
+        raise ValueError(f'colour factors must be {B} finite (brightness, contrast, saturation) triples >= 0')
+    return color.reshape(B, 3)
 
 
 def _pad_crop(size, target):
@@ -128,11 +155,11 @@ def as_u8_image(im, what):
     return u8
 
 
-def pack_layout(sizes):
-    """Byte layout of one upload: int64 offsets [B], int32 sizes [B, 2], int32 aug [B, 3], then (at HDR_ALIGN) the pixels.
-    Returns (header bytes, pixel offsets int64 [B] relative to the pixel base, total bytes)."""
+def pack_layout(sizes, color=False):
+    """Byte layout of one upload: int64 offsets [B], int32 sizes [B, 2], int32 aug [B, 3], (``color``: float32 color [B, 3],) then
+    (at HDR_ALIGN) the pixels.  Returns (header bytes, pixel offsets int64 [B] relative to the pixel base, total bytes)."""
     B = len(sizes)
-    hdr = -(-(8 * B + 20 * B) // HDR_ALIGN) * HDR_ALIGN
+    hdr = -(-(8 * B + 20 * B + (12 * B if color else 0)) // HDR_ALIGN) * HDR_ALIGN
     offsets = np.zeros(B, np.int64)
     total = 0
     for i, (h, w) in enumerate(sizes):
@@ -141,23 +168,47 @@ def pack_layout(sizes):
     return hdr, offsets, hdr + total
 
 
-def write_header(buf_np, offsets, sizes, aug):
-    """Fill the int header of a packed upload (``buf_np``: the uint8 numpy view of the whole pinned buffer)."""
+def write_header(buf_np, offsets, sizes, aug, color=None):
+    """Fill the header of a packed upload (``buf_np``: the uint8 numpy view of the whole pinned buffer).  ``color``: float32 [B, 3]
+    factors for a ``pack_layout(sizes, color=True)`` layout."""
     B = len(offsets)
     buf_np[:8 * B].view(np.int64)[:] = offsets
     buf_np[8 * B:16 * B].view(np.int32)[:] = np.asarray(sizes, np.int32).reshape(-1)
     buf_np[16 * B:28 * B].view(np.int32)[:] = np.asarray(aug, np.int32).reshape(-1)
+    if color is not None:
+        buf_np[28 * B:40 * B].view(np.float32)[:] = check_color(color, B).reshape(-1)
 
 
-def launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std):
+def launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std, color=False, sums=None):
     """One augmented preprocessing launch on the device copy ``dev_buf`` of a packed upload.  Returns the device tensor the kernel
-    writes next to ``out``: scales fp32 [B, 2], or (forbid_resize) padcrop int32 [B, 8]."""
+    writes next to ``out``: scales fp32 [B, 2], or (forbid_resize) padcrop int32 [B, 8].
+
+    ``color``: true when the upload has the colour header (``pack_layout(sizes, color=True)``, factors written by ``write_header``).
+    The per-image channel sums the contrast pivot needs are then taken on the device first (``sqd_image_stats_u8`` into ``sums``,
+    int64 [B, 3, 2] on the device, allocated when not given) and the colour entry point follows on the same stream: no host
+    synchronisation, nothing is copied back."""
     H, W = int(input_size[0]), int(input_size[1])
     base = dev_buf.data_ptr()
     p = lambda off: ctypes.c_void_p(base + off)      # noqa: E731
     mean = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_mean).reshape(-1)])
     std = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_std).reshape(-1)])
     stream = nat.stream_handle(dev_buf.device)
+    if color:
+        if hdr < 40 * B:
+            raise ValueError(f'launch: a header of {hdr} bytes has no room for the colour factors of {B} images')
+        from .ops import image_stats_u8
+        sums = image_stats_u8(dev_buf, B, hdr, out=sums)
+        if forbid_resize:
+            side = torch.empty(B, 8, device=dev_buf.device, dtype=torch.int32)
+            rc = nat.lib().sqd_preprocess_u8_padcrop_aug_color_fwd(p(hdr), p(0), p(8 * B), p(16 * B), p(28 * B), nat.ptr(sums), nat.ptr(out),
+                                                                   None, nat.ptr(side), mean, std, B, H, W, stream)
+            nat.check(rc, 'sqd_preprocess_u8_padcrop_aug_color_fwd')
+        else:
+            side = torch.empty(B, 2, device=dev_buf.device, dtype=torch.float32)
+            rc = nat.lib().sqd_preprocess_u8_aug_color_fwd(p(hdr), p(0), p(8 * B), p(16 * B), p(28 * B), nat.ptr(sums), nat.ptr(out),
+                                                           nat.ptr(side), mean, std, B, H, W, stream)
+            nat.check(rc, 'sqd_preprocess_u8_aug_color_fwd')
+        return side
     if forbid_resize:
         side = torch.empty(B, 8, device=dev_buf.device, dtype=torch.int32)
         rc = nat.lib().sqd_preprocess_u8_padcrop_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), nat.ptr(out), None, nat.ptr(side),
@@ -185,12 +236,14 @@ def _default_anchors(input_size):
 
 def preprocess_train_batch(images, class_ids_list, boxes_list, input_size, rng, drift_prob=1.0, flip_prob=0.5,
                            rgb_mean=KITTI_RGB_MEAN, rgb_std=KITTI_RGB_STD, forbid_resize=False, device='cuda', out=None,
-                           anchors=None, num_classes=3, aug=None):
+                           anchors=None, num_classes=3, aug=None, color_jitter=(0., 0., 0.), color=None):
     """A training batch the reference's way (``BaseDataset.__getitem__`` in the train phase + default collate), built on the GPU.
 
     images: list of uint8 (or uint8-representable float) [H0, W0, 3] RGB arrays; class_ids_list / boxes_list: per image [n] and
     xyxy [n, 4] in original-image coordinates; rng: ``np.random.RandomState`` the draws come from (``aug``: int32 [B, 3] to use
-    instead of drawing); anchors: ``cfg.anchors`` (default: the KITTI anchors of ``input_size``).  Returns (image fp32 NCHW on
+    instead of drawing); color_jitter: (brightness, contrast, saturation) amounts, any > 0 draws the colour factors from ``rng`` after
+    the geometric draws of the whole batch (``draw_color``); color: float32 [B, 3] factors to use instead of drawing (``image_meta``
+    then carries them as ``'color'``); anchors: ``cfg.anchors`` (default: the KITTI anchors of ``input_size``).  Returns (image fp32 NCHW on
     ``device`` -- ``out`` when given --, image_meta with the reference's keys, dense gt [B, A, num_classes + 9] on ``device``).
     Uploads: one packed uint8 buffer (int header included) and the boxes of ``encode_annotations``; nothing waits on the device."""
     B = len(images)
@@ -202,11 +255,15 @@ def preprocess_train_batch(images, class_ids_list, boxes_list, input_size, rng, 
     if aug is None:
         aug = draw_augmentation(rng, sizes, boxes_list, drift_prob, flip_prob)
     aug = np.asarray(aug, np.int32).reshape(B, 3)
+    if color is not None:
+        color = check_color(color, B)
+    elif any(float(d) > 0 for d in color_jitter):
+        color = draw_color(rng, B, *color_jitter)
     tb, metas = zip(*[transform_boxes(bx, (h, w), a, input_size, forbid_resize) for bx, (h, w), a in zip(boxes_list, sizes, aug)])
-    hdr, offsets, total = pack_layout(sizes)
+    hdr, offsets, total = pack_layout(sizes, color is not None)
     packed = _staging(total)
     pk = packed.numpy()
-    write_header(pk, offsets, sizes, aug)
+    write_header(pk, offsets, sizes, aug, color)
     for im, off in zip(ims, offsets):
         pk[hdr + off:hdr + off + im.size] = np.ascontiguousarray(im).reshape(-1)
     dev = torch.device(device)
@@ -214,7 +271,10 @@ def preprocess_train_batch(images, class_ids_list, boxes_list, input_size, rng, 
         dev = torch.device('cuda', torch.cuda.current_device())
     dev_buf = packed.to(dev, non_blocking=True)
     out = check_out(out, B, H, W, dev)
-    launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std)
+    launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std, color=color is not None)
     from .annotations import encode_annotations
     gt = encode_annotations(class_ids_list, list(tb), _default_anchors(input_size) if anchors is None else anchors, num_classes, device=dev)
-    return out, batch_meta(metas, sizes, rgb_mean, rgb_std), gt
+    meta = batch_meta(metas, sizes, rgb_mean, rgb_std)
+    if color is not None:
+        meta['color'] = color
+    return out, meta, gt

@@ -61,6 +61,58 @@ __device__ __forceinline__ int pre_stage(unsigned* dst, const unsigned char* img
   return shift;
 }
 
+// Photometric jitter ("Colour jitter"): per image color[b] = (fb, fc, fs) -- brightness, contrast, saturation -- applied
+// to the SOURCE pixels in float32, before whitening and interpolation.  g = (0.299 Sr + 0.587 Sg + 0.114 Sb) / (H0 W0) is the mean luma
+// of the untouched image, formed in float64 from the exact channel sums sqd_image_stats_u8 wrote and rounded to float32 once;
+// p = min(fb g, 255) the contrast pivot;  t(v) = clamp(fc min(fb v, 255) + (1 - fc) p, 0, 255) per byte;  y = 0.299 t(r) + 0.587 t(g) +
+// 0.114 t(b) per tap;  c' = clamp(fs t(c) + (1 - fs) y, 0, 255) per channel, then whiten(c') = (c' - mean) / std as above.
+// Uniform per workgroup (one image each): with fs == 1 the whole chain is per channel (c' = t(c) exactly: t is already inside
+// [0, 255], 1 * t + 0 * y = t), so the 768-entry table holds whiten(t(v)) and the per-pixel loop is the plain one; otherwise the
+// first 256 entries hold t(v) and the saturation blend and the whitening run per tap.  (1, 1, 1) reproduces the plain table bit
+// for bit: min(1 * v, 255) = v and 1 * v + 0 * p = v.
+struct PreColor {
+  float fb, fc, fs;
+  float cp;                      // (1 - fc) * p
+  bool per_tap;                  // fs != 1: the table holds t(v), not whiten(t(v))
+};
+
+__device__ __forceinline__ PreColor pre_color_of(const float* color, const unsigned long long* sums, int b, int H0, int W0) {
+  PreColor k;
+  k.fb = color[3 * b]; k.fc = color[3 * b + 1]; k.fs = color[3 * b + 2];
+  const unsigned long long* s = sums + 6ll * b;     // [3][2] = (sum x, sum x*x) per channel
+  const double g64 = (0.299 * (double)s[0] + 0.587 * (double)s[2] + 0.114 * (double)s[4]) / ((double)H0 * (double)W0);
+  const float p = fminf(k.fb * (float)g64, 255.f);
+  k.cp = (1.f - k.fc) * p;
+  k.per_tap = k.fs != 1.f;
+  return k;
+}
+
+__device__ __forceinline__ float pre_color_t(const PreColor& k, float v) {
+  return fminf(fmaxf(k.fc * fminf(k.fb * v, 255.f) + k.cp, 0.f), 255.f);
+}
+
+__device__ __forceinline__ void pre_build_lut_color(float* lut, const PreColor& k, float m0, float m1, float m2, float s0, float s1, float s2) {
+  if (k.per_tap) {
+    lut[threadIdx.x] = pre_color_t(k, (float)threadIdx.x);     // (256 threads)
+    return;
+  }
+  for (int i = threadIdx.x; i < 768; i += 256) {
+    const int c = i >> 8, v = i & 255;
+    const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+    lut[i] = (pre_color_t(k, (float)v) - m) / sd;
+  }
+}
+
+// one tap of the per-tap form: the three bytes at p through the t table, the saturation blend, then whiten
+__device__ __forceinline__ void pre_color_tap(const float* lut, const PreColor& k, const unsigned char* p, const float* mean, const float* stdv,
+                                              float (&o)[3]) {
+  const float t0 = lut[p[0]], t1 = lut[p[1]], t2 = lut[p[2]];
+  const float q = (1.f - k.fs) * (0.299f * t0 + 0.587f * t1 + 0.114f * t2);
+  o[0] = (fminf(fmaxf(k.fs * t0 + q, 0.f), 255.f) - mean[0]) / stdv[0];
+  o[1] = (fminf(fmaxf(k.fs * t1 + q, 0.f), 255.f) - mean[1]) / stdv[1];
+  o[2] = (fminf(fmaxf(k.fs * t2 + q, 0.f), 255.f) - mean[2]) / stdv[2];
+}
+
 // Training augmentation (reference train phase, src/datasets/base.py:43-59 with drift / flip active; src/utils/image.py:22-74): per image
 // aug[b] = (dy, dx, flipped).  The drifted image V is Hd x Wd = (H0 - dy) x (W0 - dx); before the flip V[y][x] = whiten(I[y+dy][x+dx])
 // where y + dy >= 0 and x + dx >= 0, else exactly 0.0f (the reference zero-fills AFTER whitening); the flip reads V[y][Wd-1-x].  Both
@@ -69,13 +121,14 @@ __device__ __forceinline__ int pre_stage(unsigned* dst, const unsigned char* img
 // never loaded; a workgroup's source segment is bounded by the mapped columns of its two end pixels (min / max: under a flip the
 // column falls as x rises), clamped to the image, and a row wholly in the fill region is not staged.  dy / dx are clamped to
 // [-2^20, H0-1] / [-2^20, W0-1] so that Hd, Wd >= 1 whatever the buffer holds.  AUG = false is the untouched eval-time kernel.
+// COLOR (with AUG only): the photometric jitter above; COLOR = false instantiates exactly the body without it.
 template <bool AUG>
 __device__ __forceinline__ int pre_drift(const int* aug, int k, int n0) {
   return AUG ? max(min(aug[k], n0 - 1), -(1 << 20)) : 0;
 }
 
-template <bool AUG>
-__device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug) {
+template <bool AUG, bool COLOR>
+__device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug, const float* color, const unsigned long long* sums) {
   __shared__ float lut[768];
   __shared__ unsigned rows[2][PRE_ROWB / 4];
   const int b = blockIdx.z;
@@ -119,7 +172,13 @@ __device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug
   const int ux0 = AUG ? max(cx0, 0) : cx0, ux1 = AUG ? max(cx1, 0) : cx1;     // (a fill tap's address: any in-range one)
   const float ax0 = 1.f - fx, ax1 = fx;
   const long long plane = (long long)a.H * a.W;
-  pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
+  PreColor kc = {};
+  if (COLOR) {
+    kc = pre_color_of(color, sums, b, H0, W0);
+    pre_build_lut_color(lut, kc, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
+  } else {
+    pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
+  }
   for (int r = 0; r < PRE_ROWS; ++r) {
     const int y = blockIdx.y * PRE_ROWS + r;
     if (y >= a.H) break;                             // (uniform)
@@ -152,6 +211,20 @@ __device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug
       p10 = img + ((long long)uy1 * W0 + ux0) * 3; p11 = img + ((long long)uy1 * W0 + ux1) * 3;
     }
     const bool t00 = vy0 && vx0, t01 = vy0 && vx1, t10 = vy1 && vx0, t11 = vy1 && vx1;
+    if (COLOR && kc.per_tap) {                       // (uniform) saturation mixes the channels of a tap: blend and whiten per tap
+      float v00[3] = {0.f, 0.f, 0.f}, v01[3] = {0.f, 0.f, 0.f}, v10[3] = {0.f, 0.f, 0.f}, v11[3] = {0.f, 0.f, 0.f};     // (fill: 0)
+      if (t00) pre_color_tap(lut, kc, p00, a.mean, a.stdv, v00);
+      if (t01) pre_color_tap(lut, kc, p01, a.mean, a.stdv, v01);
+      if (t10) pre_color_tap(lut, kc, p10, a.mean, a.stdv, v10);
+      if (t11) pre_color_tap(lut, kc, p11, a.mean, a.stdv, v11);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float r0 = v00[c] * ax0 + v01[c] * ax1;
+        const float r1 = v10[c] * ax0 + v11[c] * ax1;
+        o[c * plane] = r0 * ay0 + r1 * ay1;
+      }
+      continue;
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float* l = lut + 256 * c;                                    // whiten (image.py:17) in float32: the table holds (v - mean) / std
@@ -164,9 +237,13 @@ __device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug
   }
 }
 
-__global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) { preprocess_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) { preprocess_body<false, false>(a, nullptr, nullptr, nullptr); }
 
-__global__ __launch_bounds__(256) void preprocess_aug_kernel(PreArgs a, const int* aug) { preprocess_body<true>(a, aug); }
+__global__ __launch_bounds__(256) void preprocess_aug_kernel(PreArgs a, const int* aug) { preprocess_body<true, false>(a, aug, nullptr, nullptr); }
+
+__global__ __launch_bounds__(256) void preprocess_aug_color_kernel(PreArgs a, const int* aug, const float* color, const unsigned long long* sums) {
+  preprocess_body<true, true>(a, aug, color, sums);
+}
 
 // src: device buffer holding the B images back to back (HWC uint8 RGB); offsets [B] byte offsets; sizes [B][2] =
 // (H0, W0) int32; out: NCHW fp32 [B][3][H][W]; scales: [B][2] fp32 or NULL; mean/std: 3 floats each (host).
@@ -197,8 +274,8 @@ struct PadCropArgs {
 };
 
 // AUG: crop_or_pad of the drifted, flipped image V (Hd x Wd, see preprocess_body): padding / crops / shifts from (Hd, Wd).
-template <bool AUG>
-__device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, const int* aug) {
+template <bool AUG, bool COLOR>
+__device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, const int* aug, const float* color, const unsigned long long* sums) {
   __shared__ float lut[768];
   __shared__ unsigned row[PRE_ROWB / 4];
   const int b = blockIdx.z;
@@ -229,7 +306,13 @@ __device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, co
     lo = max(min(ca, cb), 0); hi = min(max(ca, cb), W0 - 1);
   }
   const long long plane = (long long)a.H * a.W;
-  pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
+  PreColor kc = {};
+  if (COLOR) {
+    kc = pre_color_of(color, sums, b, H0, W0);
+    pre_build_lut_color(lut, kc, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
+  } else {
+    pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
+  }
   for (int r = 0; r < PRE_ROWS; ++r) {
     const int y = blockIdx.y * PRE_ROWS + r;
     if (y >= a.H) break;                             // (uniform)
@@ -244,14 +327,26 @@ __device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, co
     const bool inside = row_in && sx >= 0 && sx < Wd && (!AUG || cx >= 0);
     float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
     const unsigned char* p = (const unsigned char*)row + sh + (inside ? (cx - lo) * 3 : 0);
+    if (COLOR && kc.per_tap) {                       // (uniform)
+      float v[3] = {0.f, 0.f, 0.f};
+      if (inside) pre_color_tap(lut, kc, p, a.mean, a.stdv, v);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c * plane] = v[c];
+      continue;
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c * plane] = inside ? lut[256 * c + p[c]] : 0.f;
   }
 }
 
-__global__ __launch_bounds__(256) void preprocess_padcrop_kernel(PadCropArgs a) { preprocess_padcrop_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void preprocess_padcrop_kernel(PadCropArgs a) { preprocess_padcrop_body<false, false>(a, nullptr, nullptr, nullptr); }
 
-__global__ __launch_bounds__(256) void preprocess_padcrop_aug_kernel(PadCropArgs a, const int* aug) { preprocess_padcrop_body<true>(a, aug); }
+__global__ __launch_bounds__(256) void preprocess_padcrop_aug_kernel(PadCropArgs a, const int* aug) { preprocess_padcrop_body<true, false>(a, aug, nullptr, nullptr); }
+
+__global__ __launch_bounds__(256) void preprocess_padcrop_aug_color_kernel(PadCropArgs a, const int* aug, const float* color,
+                                                                           const unsigned long long* sums) {
+  preprocess_padcrop_body<true, true>(a, aug, color, sums);
+}
 
 // Arguments as sqd_preprocess_u8_fwd; shifts: [B][2] fp32 (dy, dx) or NULL; padcrop: [B][8] int32 = padding (top, bottom, left,
 // right) then crops (top, bottom, left, right), or NULL.
@@ -287,5 +382,32 @@ extern "C" int sqd_preprocess_u8_padcrop_aug_fwd(const unsigned char* src, const
   a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.shifts = shifts; a.padcrop = padcrop; a.B = B; a.H = H; a.W = W;
   for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
   hipLaunchKernelGGL(preprocess_padcrop_aug_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug);
+  return sqd_launch_status();
+}
+
+// Colour forms of the two above (the photometric jitter of pre_color_of): color: device fp32 [B][3] = (brightness, contrast, saturation)
+// factors per image; sums: device uint64 [B][3][2] as sqd_image_stats_u8 writes it for the same src / offsets / sizes (launched before this
+// call on the same stream).  Both are required.  color = (1, 1, 1) everywhere gives the results of the _aug_ entry points bit for bit.
+extern "C" int sqd_preprocess_u8_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                               const float* color, const unsigned long long* sums, float* out, float* scales,
+                                               const float* mean3, const float* std3, int B, int H, int W, void* stream) {
+  SQD_CHECK_ARG(src && offsets && sizes && aug && color && sums && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
+  SQD_CHECK_ARG(((uintptr_t)sums & 7) == 0 && ((uintptr_t)color & 3) == 0);
+  PreArgs a;
+  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.scales = scales; a.B = B; a.H = H; a.W = W;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
+  hipLaunchKernelGGL(preprocess_aug_color_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug, color, sums);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_preprocess_u8_padcrop_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                                       const float* color, const unsigned long long* sums, float* out, float* shifts,
+                                                       int* padcrop, const float* mean3, const float* std3, int B, int H, int W, void* stream) {
+  SQD_CHECK_ARG(src && offsets && sizes && aug && color && sums && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
+  SQD_CHECK_ARG(((uintptr_t)sums & 7) == 0 && ((uintptr_t)color & 3) == 0);
+  PadCropArgs a;
+  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.shifts = shifts; a.padcrop = padcrop; a.B = B; a.H = H; a.W = W;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
+  hipLaunchKernelGGL(preprocess_padcrop_aug_color_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug, color, sums);
   return sqd_launch_status();
 }

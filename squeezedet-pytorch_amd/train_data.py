@@ -26,6 +26,9 @@ from .annotations import encode_annotations
 from .trainer import shard_sizes
 
 
+COLOR_STREAM = 0xC0105EED      # second word of the colour RandomState's seed key
+
+
 class _Stage:
     """One pinned upload buffer and the event of its latest host-to-device copy."""
 
@@ -48,7 +51,8 @@ class TrainLoader:
     """Iterable of device-resident training batches over ``dataset`` (see the module docstring).
 
     cfg fields read: batch_size (global), input_size, num_workers, device, drift_prob, flip_prob, seed, forbid_resize, anchors,
-    num_classes.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState once; each epoch (``iter``) continues it."""
+    num_classes, brightness_jitter, contrast_jitter, saturation_jitter.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState
+    once (and, as ``[seed mod 2^32, COLOR_STREAM]``, the colour one); each epoch (``iter``) continues them."""
 
     def __init__(self, dataset, cfg, seed=None, shuffle=True, drop_last=True, rank=0, world=1):
         self.dataset, self.cfg = dataset, cfg
@@ -57,7 +61,13 @@ class TrainLoader:
         if not 0 <= self.rank < self.world:
             raise ValueError(f'TrainLoader: rank {rank} outside world {world}')
         self.batch_size = int(cfg.batch_size)
-        self.rng = np.random.RandomState(getattr(cfg, 'seed', 42) if seed is None else seed)
+        seed = getattr(cfg, 'seed', 42) if seed is None else seed
+        self.rng = np.random.RandomState(seed)
+        self.color_rng = np.random.RandomState(None if seed is None else np.append(np.asarray(seed, np.int64).reshape(-1) & 0xFFFFFFFF, COLOR_STREAM))
+        self.color_jitter = tuple(float(getattr(cfg, k, 0.)) for k in ('brightness_jitter', 'contrast_jitter', 'saturation_jitter'))
+        if any(not np.isfinite(d) or d < 0 for d in self.color_jitter):
+            raise ValueError(f'TrainLoader: colour jitter amounts must be finite and >= 0, got {self.color_jitter}')
+        self.color_on = any(d > 0 for d in self.color_jitter)
         self.drift_prob = float(getattr(cfg, 'drift_prob', 1.0))
         self.flip_prob = float(getattr(cfg, 'flip_prob', 0.5))
         self.forbid_resize = bool(getattr(cfg, 'forbid_resize', False))
@@ -117,7 +127,7 @@ class TrainLoader:
 
         def pack(ims, parallel):
             sizes = [im.shape[:2] for im in ims]
-            hdr, offsets, total = augment.pack_layout(sizes)
+            hdr, offsets, total = augment.pack_layout(sizes, self.color_on)
             pk = stage.acquire(total)
 
             def put(k):                               # (numpy releases the GIL while copying)
@@ -149,18 +159,21 @@ class TrainLoader:
 
     def _plan_batch(self, idxs, gsizes, ann):
         """The host half of a batch: draws for the whole global batch (main thread, batch order), then this rank's slice of the
-        draws, transformed boxes, per-image metas and class ids."""
+        draws, transformed boxes, per-image metas and class ids (jitter on: ``'color'``, this rank's slice of the colour factors)."""
         lo, hi = self._local(idxs)
         box_all = [np.asarray(b, np.float32).reshape(-1, 4) for _, b in ann]
         aug = augment.draw_augmentation(self.rng, gsizes, box_all, self.drift_prob, self.flip_prob)[lo:hi]
         tb, metas = zip(*[augment.transform_boxes(b, s, a, self.cfg.input_size, self.forbid_resize)
                           for b, s, a in zip(box_all[lo:hi], gsizes[lo:hi], aug)])
-        return {'index': np.asarray(idxs[lo:hi], np.int64), 'aug': aug, 'boxes': list(tb), 'metas': list(metas),
-                'class_ids': [np.asarray(c) for c, _ in ann[lo:hi]]}
+        p = {'index': np.asarray(idxs[lo:hi], np.int64), 'aug': aug, 'boxes': list(tb), 'metas': list(metas),
+             'class_ids': [np.asarray(c) for c, _ in ann[lo:hi]]}
+        if self.color_on:
+            p['color'] = augment.draw_color(self.color_rng, len(idxs), *self.color_jitter)[lo:hi]
+        return p
 
     def plan(self):
-        """One epoch's host side only (no pixels, no device): per batch this rank's dataset indices, draws, transformed boxes.
-        Consumes the loader's RandomState exactly as iterating the epoch does."""
+        """One epoch's host side only (no pixels, no device): per batch this rank's dataset indices, draws, transformed boxes (jitter
+        on: the colour factors under ``'color'``).  Consumes the loader's RandomStates exactly as iterating the epoch does."""
         for idxs in self._global_batches():
             yield self._plan_batch(idxs, [self._size_of(int(i)) for i in idxs], [self.dataset.load_annotations(int(i)) for i in idxs])
 
@@ -169,7 +182,8 @@ class TrainLoader:
         lo, hi = self._local(idxs)
         p = self._plan_batch(idxs, gsizes, ann)
         aug, tb, metas = p['aug'], p['boxes'], p['metas']
-        augment.write_header(stage.np, offsets, sizes, aug)
+        color = p.get('color')
+        augment.write_header(stage.np, offsets, sizes, aug, color)
         B = hi - lo
         H, W = int(self.cfg.input_size[0]), int(self.cfg.input_size[1])
         dev_buf = torch.empty(total, dtype=torch.uint8, device=self.device)
@@ -177,11 +191,13 @@ class TrainLoader:
         stage.copied = torch.cuda.Event()
         stage.copied.record(torch.cuda.current_stream(self.device))
         out = torch.empty(B, 3, H, W, device=self.device, dtype=torch.float32)
-        augment.launch(dev_buf, B, hdr, self.cfg.input_size, out, self.forbid_resize, self.rgb_mean, self.rgb_std)
+        augment.launch(dev_buf, B, hdr, self.cfg.input_size, out, self.forbid_resize, self.rgb_mean, self.rgb_std, color=color is not None)
         sparse = bool(getattr(self.cfg, 'sparse_gt', False))      # the positives as a list (ops.SparseGT): no dense tensor is built
         gt = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device, dense=not sparse)
         meta = augment.batch_meta(metas, sizes, self.rgb_mean, self.rgb_std)
         meta['index'] = p['index']
+        if color is not None:
+            meta['color'] = color
         return {'image': out, 'image_meta': meta, 'gt_sparse' if sparse else 'gt': gt}
 
     def __iter__(self):

@@ -2,9 +2,11 @@
 """Training input pipeline measurements ("Training input on the GPU"), one JSON line on stdout:
 
   kernel  : the augmented preprocessing launch against the plain one on the same 20-image KITTI-sized uint8 batch (device events
-            after warm-up, the two alternating in one process), both branches;
+            after warm-up, the two alternating in one process), both branches; and the colour-jitter call (statistics launches +
+            colour launch) in its table form (saturation factor 1) and its per-tap form, against the augmented launch;
   loader  : TrainLoader throughput (img/s) over an in-memory uint8 dataset, num_workers 4 and 8;
-  trainer : Trainer.run_epoch img/s fed by TrainLoader (8 workers) against the same Trainer over device-resident synthetic batches.
+  trainer : Trainer.run_epoch img/s fed by TrainLoader (8 workers) against the same Trainer over device-resident synthetic batches,
+            and fed by the same loader with colour jitter on.
 
     python tools/augment_bench.py [--reps 200] [--iters 30] [--out FILE]
 """
@@ -58,6 +60,29 @@ def bench_kernels(reps):
     std = (ctypes.c_float * 3)(*[float(v) for v in KITTI_RGB_STD])
     st = nat.stream_handle()
     lib = nat.lib()
+    # the same batch and draws with the colour header: factors with saturation 1 (table form) and with all three drawn (per-tap form)
+    hdr_c, offsets_c, total_c = augment.pack_layout(sizes, color=True)
+    crng = np.random.RandomState(43)
+    dev_c = {}
+    for name, jit in (('table', (0.4, 0.4, 0.)), ('pertap', (0.4, 0.4, 0.4))):
+        pkc = np.zeros(total_c, np.uint8)
+        augment.write_header(pkc, offsets_c, sizes, aug, augment.draw_color(crng, B, *jit))
+        pkc[hdr_c:] = pk[hdr:]
+        dev_c[name] = torch.from_numpy(pkc).cuda()
+    sums = torch.empty(B, 3, 2, device='cuda', dtype=torch.int64)
+
+    def color_call(name, forbid):                     # the statistics call (zeroing + sums launches), then the colour launch
+        base_c = dev_c[name].data_ptr()
+        q = lambda off: ctypes.c_void_p(base_c + off)      # noqa: E731
+
+        def f():
+            rc = lib.sqd_image_stats_u8(q(hdr_c), q(0), q(8 * B), nat.ptr(sums), B, st)
+            if forbid:
+                return rc or lib.sqd_preprocess_u8_padcrop_aug_color_fwd(q(hdr_c), q(0), q(8 * B), q(16 * B), q(28 * B), nat.ptr(sums), nat.ptr(out),
+                                                                         None, nat.ptr(side), mean, std, B, SIZE[0], SIZE[1], st)
+            return rc or lib.sqd_preprocess_u8_aug_color_fwd(q(hdr_c), q(0), q(8 * B), q(16 * B), q(28 * B), nat.ptr(sums), nat.ptr(out),
+                                                             nat.ptr(side), mean, std, B, SIZE[0], SIZE[1], st)
+        return f
     launches = {
         'plain_resize': lambda: lib.sqd_preprocess_u8_fwd(p(hdr), p(0), p(8 * B), nat.ptr(out), nat.ptr(side), mean, std, B, SIZE[0], SIZE[1], st),
         'aug_resize': lambda: lib.sqd_preprocess_u8_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), nat.ptr(out), nat.ptr(side), mean, std, B,
@@ -66,6 +91,11 @@ def bench_kernels(reps):
                                                                    SIZE[0], SIZE[1], st),
         'aug_padcrop': lambda: lib.sqd_preprocess_u8_padcrop_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), nat.ptr(out), None, nat.ptr(side),
                                                                      mean, std, B, SIZE[0], SIZE[1], st),
+        'stats': lambda: lib.sqd_image_stats_u8(p(hdr), p(0), p(8 * B), nat.ptr(sums), B, st),
+        'color_table_resize': color_call('table', False),
+        'color_pertap_resize': color_call('pertap', False),
+        'color_table_padcrop': color_call('table', True),
+        'color_pertap_padcrop': color_call('pertap', True),
     }
     for f in launches.values():
         for _ in range(20):
@@ -83,7 +113,12 @@ def bench_kernels(reps):
             j += 1
     torch.cuda.synchronize()
     us = {k: float(np.median([a.elapsed_time(b) * 1e3 for a, b in v])) for k, v in times.items()}
-    return {'median_us': us, 'aug_over_plain_resize': us['aug_resize'] / us['plain_resize'],
+    pct = {k: [float(np.percentile([a.elapsed_time(b) * 1e3 for a, b in v], q)) for q in (10, 90)] for k, v in times.items()}
+    return {'median_us': us, 'p10_p90_us': pct,
+            'color_table_over_aug_resize': us['color_table_resize'] / us['aug_resize'],
+            'color_pertap_over_aug_resize': us['color_pertap_resize'] / us['aug_resize'],
+            'color_table_over_aug_padcrop': us['color_table_padcrop'] / us['aug_padcrop'],
+            'color_pertap_over_aug_padcrop': us['color_pertap_padcrop'] / us['aug_padcrop'], 'aug_over_plain_resize': us['aug_resize'] / us['plain_resize'],
             'aug_over_plain_padcrop': us['aug_padcrop'] / us['plain_padcrop'], 'reps': reps, 'batch': B,
             'target_ratio': 1.15}
 
@@ -144,16 +179,22 @@ def bench_trainer(iters, workers=8):
     synth = [{'image': x, 'gt': gt, 'image_meta': {}}] * iters
     ds = MemKitti(B * iters)
     out = {}
-    for rnd in range(2):                                   # round 0 warms both paths up
-        for name, make in (('synthetic', lambda: synth), ('loader', lambda: TrainLoader(ds, cfg, seed=rnd))):
+    cfg_c = sqd.make_cfg(input_size=SIZE, device='cuda', batch_size=B, num_workers=workers, brightness_jitter=0.4, contrast_jitter=0.4,
+                         saturation_jitter=0.4)
+    runs = {}
+    for rnd in range(4):                                   # round 0 warms the paths up; rounds 1-3 are measured, interleaved
+        for name, make in (('synthetic', lambda: synth), ('loader', lambda: TrainLoader(ds, cfg, seed=rnd)),
+                           ('loader_color', lambda: TrainLoader(ds, cfg_c, seed=rnd))):
             loader = make()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             tr.run_epoch('train', 1, loader)
             torch.cuda.synchronize()
-            out[name] = B * iters / (time.perf_counter() - t0)
-    return {'img_per_s': out, 'loader_over_synthetic': out['loader'] / out['synthetic'], 'workers': workers, 'iters': iters,
-            'target_ratio': 0.90}
+            if rnd:
+                runs.setdefault(name, []).append(B * iters / (time.perf_counter() - t0))
+    out = {k: float(np.median(v)) for k, v in runs.items()}
+    return {'img_per_s': out, 'img_per_s_runs': runs, 'loader_over_synthetic': out['loader'] / out['synthetic'],
+            'loader_color_over_loader': out['loader_color'] / out['loader'], 'workers': workers, 'iters': iters, 'target_ratio': 0.90}
 
 
 def main():
