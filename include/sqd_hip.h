@@ -472,6 +472,47 @@ int sqd_loss_sparse_mean_bwd(const float* pred, const int* anchor_idx, const flo
                              const float* gmean, float* dpred, int total, int B, int A, int num_classes, int input_h,
                              int input_w, float w_class, float w_pos, float w_neg, float w_bbox, void* stream);
 
+/* Anchor ignore bitmap: which anchors lie on an ignore region of their image (KITTI DontCare, VOC difficult, COCO crowd).
+ * ign_boxes [total][4] fp32 xyxy (network-input coordinates), ign_offsets [B+1] int32 (image b owns boxes ign_offsets[b] ..
+ * ign_offsets[b+1]-1), anchors [A][4] FLOAT64 (cx,cy,w,h), mask uint32 [B][ceil(A/32)]: device pointers.  overlap: HOST pointer to
+ * one double in (0, 1] (read before the launch).  Rule, all float64 and without a division (a numpy float64 restatement gives the
+ * same bits): with the encoder's anchor corners x0 = cx - 0.5 (w - 1), x1 = cx + 0.5 (w - 1) (y likewise), inter =
+ * max(min(x1,bx2) - max(x0,bx1), 0) * max(min(y1,by2) - max(y0,by1), 0) and area = (x1 - x0) (y1 - y0), bit a of image b is set
+ * iff area > 0 and inter >= overlap * area for SOME box of the image: intersection over ANCHOR area, the per-box maximum.
+ * Anchor a is bit a & 31 of word a >> 5; bits at and past A are 0; every word is written (no memset needed).  total = 0
+ * (ign_boxes may be NULL) and images without boxes are legal: zero words.  Status 1 for anything malformed (an overlap outside
+ * (0, 1] included), 2 for A > 2^20, B > 65535 or total > 65535 B (at most 65535 ignore boxes per image). */
+int sqd_anchor_ignore_fwd(const float* ign_boxes, const int* ign_offsets, const double* anchors, unsigned* mask,
+                          const double* overlap, int total, int B, int A, void* stream);
+
+/* The sparse loss launches with an ignore bitmap (sqd_anchor_ignore_fwd's layout): ignore uint32 [B][ceil(A/32)].  Per image:
+ * pos = the list's valid entries; ign = the anchors whose bit is set and that are not in pos (a positive wins over its own bit);
+ * n_obj = |pos|, n_ign = |ign|, n_neg = A - n_obj - n_ign.  class, pos-score and bbox are sqd_loss_sparse_*'s sums / n_obj, each
+ * 0 where n_obj = 0; neg = w_neg * sum over the anchors outside pos and ign of sigmoid(conf)^2 / n_neg, 0 where n_neg = 0.
+ * dpred: a positive row is what sqd_loss_sparse_bwd writes, a row of ign is all zeros, any other row is zeros and the confidence
+ * gradient with 1 / n_neg; every element is written and no count of 0 gives a NaN.  workspace: float[B * 16 * 6]; counts
+ * float[2][B] = (n_obj, n_neg), written by the forward and read by the backward where the unmasked launches have nobj.  Other
+ * arguments, status codes and determinism as for sqd_loss_sparse_*.  With an all-zero bitmap on images that all have positives
+ * the four launches give the bits of their unmasked siblings. */
+int sqd_loss_masked_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                        const int* offsets, const unsigned* ignore, const float* anchors, float* workspace, float* losses,
+                        float* counts, int total, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                        float w_pos, float w_neg, float w_bbox, void* stream);
+int sqd_loss_masked_mean_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                             const int* class_ids, const int* offsets, const unsigned* ignore, const float* anchors,
+                             float* workspace, float* losses, float* counts, float* mean4, int total, int B, int A,
+                             int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                             float w_bbox, void* stream);
+int sqd_loss_masked_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                        const int* offsets, const unsigned* ignore, const float* anchors, const float* counts,
+                        const float* coef, float* dpred, int total, int B, int A, int num_classes, int input_h, int input_w,
+                        float w_class, float w_pos, float w_neg, float w_bbox, void* stream);
+int sqd_loss_masked_mean_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                             const int* class_ids, const int* offsets, const unsigned* ignore, const float* anchors,
+                             const float* counts, const float* gmean, float* dpred, int total, int B, int A,
+                             int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                             float w_bbox, void* stream);
+
 
 /* Fire.forward's two expand convolutions + torch.cat (src/model/squeezedet.py:18-22) in ONE Winograd launch (inference):
  * y[..., y_coff3 : +N3] = ReLU(conv3x3(x, w3) + b3), y[..., y_coff1 : +N1] = ReLU(conv1x1(x, w1) + b1).  A 1x1 convolution only

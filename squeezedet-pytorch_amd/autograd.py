@@ -185,10 +185,14 @@ def backbone_apply(base, image):
     return out
 
 
-def loss_apply(loss_mod, pred, gt):
-    from .backward import LossFn, LossSparseFn
+def loss_apply(loss_mod, pred, gt, ignore=None):
+    from .backward import LossFn, LossMaskedFn, LossSparseFn
     anchors = loss_mod.resolver.anchors_on(pred.device)
-    if isinstance(gt, ops.SparseGT):
+    if ignore is not None:
+        if not isinstance(gt, ops.SparseGT):
+            raise ValueError('Loss: an ignore bitmap needs a sparse ground truth (ops.SparseGT, cfg.sparse_gt); the dense loss has no masked form')
+        vec = LossMaskedFn.apply(pred, anchors, loss_mod, ignore, *gt)
+    elif isinstance(gt, ops.SparseGT):
         vec = LossSparseFn.apply(pred, anchors, loss_mod, *gt)
     else:
         vec = LossFn.apply(pred, gt, anchors, loss_mod)

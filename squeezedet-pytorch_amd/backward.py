@@ -281,3 +281,50 @@ class LossSparseMeanFn(torch.autograd.Function):
         input_size, num_classes, weights = ctx.meta
         dpred = ops.loss_sparse_mean_bwd(pred, ops.SparseGT(*sgt), anchors, nobj, g.reshape(1), input_size, num_classes, weights)
         return (dpred, None, None) + (None,) * len(sgt)
+
+
+class LossMaskedFn(torch.autograd.Function):
+    """``LossSparseFn`` with an anchor ignore bitmap (ops.anchor_ignore_mask): ignored anchors are neither positives nor negatives, and
+    an object-free image gives finite losses and gradients (ops.loss_masked_*)."""
+
+    @staticmethod
+    def forward(ctx, pred, anchors, loss_mod, ignore, *sgt):
+        res = loss_mod.resolver
+        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
+                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
+        losses, counts = ops.loss_masked_fwd(pred.detach(), ops.SparseGT(*sgt), ignore, anchors, res.input_size, res.num_classes, weights)
+        ctx.save_for_backward(pred.detach(), anchors, counts, ignore, *sgt)
+        ctx.meta = (res.input_size, res.num_classes, weights)
+        return losses                      # [4,B] = (class, score, bbox, total)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, anchors, counts, ignore, *sgt = ctx.saved_tensors
+        input_size, num_classes, weights = ctx.meta
+        coef = (g[:3] + g[3:4]).contiguous()       # gradient of `total` reaches all three components
+        dpred = ops.loss_masked_bwd(pred, ops.SparseGT(*sgt), ignore, anchors, counts, coef, input_size, num_classes, weights)
+        return (dpred, None, None, None) + (None,) * len(sgt)
+
+
+class LossMaskedMeanFn(torch.autograd.Function):
+    """``LossSparseMeanFn`` with an anchor ignore bitmap: mean(total) and its backward inside the masked loss launches."""
+
+    @staticmethod
+    def forward(ctx, pred, anchors, loss_mod, ignore, *sgt):
+        res = loss_mod.resolver
+        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
+                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
+        losses, counts, mean4 = ops.loss_masked_mean_fwd(pred.detach(), ops.SparseGT(*sgt), ignore, anchors, res.input_size,
+                                                         res.num_classes, weights)
+        ctx.save_for_backward(pred.detach(), anchors, counts, ignore, *sgt)
+        ctx.meta = (res.input_size, res.num_classes, weights)
+        ctx.mark_non_differentiable(losses)
+        ctx.set_materialize_grads(False)
+        return mean4[3], losses
+
+    @staticmethod
+    def backward(ctx, g, _gl):
+        pred, anchors, counts, ignore, *sgt = ctx.saved_tensors
+        input_size, num_classes, weights = ctx.meta
+        dpred = ops.loss_masked_mean_bwd(pred, ops.SparseGT(*sgt), ignore, anchors, counts, g.reshape(1), input_size, num_classes, weights)
+        return (dpred, None, None, None) + (None,) * len(sgt)

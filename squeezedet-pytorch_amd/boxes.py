@@ -136,3 +136,45 @@ def boxes_postprocess(boxes, image_meta):
         xs += dx
         ys += dy
     return boxes
+
+
+def anchor_ignore_mask(anchors, ign_boxes, overlap):
+    """Which anchors of one image lie on an ignore region (KITTI ``DontCare``, VOC ``difficult``, COCO ``crowd``): anchors [A,4]
+    (cx,cy,w,h), ign_boxes [n,4] xyxy float32 in network-input coordinates, overlap in (0, 1] -> bool [A].
+
+    Anchor a is ignored iff ``area > 0`` and ``inter >= overlap * area`` for SOME box, with the corners ``compute_deltas`` uses
+    (``x0 = cx - 0.5 (w - 1)``, ``x1 = cx + 0.5 (w - 1)``), ``inter`` the intersection with the box and ``area = (x1 - x0) (y1 - y0)``
+    the ANCHOR's area: intersection over anchor area, the per-box maximum, not a sum.  (An IoU would never fire for a small anchor
+    inside a large region.)  All float64 and no division: ``ops.anchor_ignore_mask`` gives the same bits."""
+    overlap = float(overlap)
+    if not (overlap > 0.0 and overlap <= 1.0):
+        raise ValueError(f'anchor_ignore_mask: overlap must be in (0, 1], got {overlap!r}')
+    a = np.asarray(anchors, dtype=np.float64).reshape(-1, 4)
+    b = np.asarray(ign_boxes, dtype=np.float32).reshape(-1, 4).astype(np.float64)
+    x0, y0 = a[:, 0] - 0.5 * (a[:, 2] - 1.0), a[:, 1] - 0.5 * (a[:, 3] - 1.0)
+    x1, y1 = a[:, 0] + 0.5 * (a[:, 2] - 1.0), a[:, 1] + 0.5 * (a[:, 3] - 1.0)
+    area = (x1 - x0) * (y1 - y0)
+    need = overlap * area
+    hit = np.zeros(a.shape[0], dtype=bool)
+    for bx in b:
+        lr = np.maximum(np.minimum(x1, bx[2]) - np.maximum(x0, bx[0]), 0.0)
+        tb = np.maximum(np.minimum(y1, bx[3]) - np.maximum(y0, bx[1]), 0.0)
+        hit |= lr * tb >= need
+    return hit & (area > 0.0)
+
+
+def pack_ignore_bits(mask):
+    """bool [..., A] -> int32 [..., ceil(A/32)]: anchor a in bit ``a & 31`` of word ``a >> 5`` (the layout of
+    ``ops.anchor_ignore_mask``); the bits at and past A are 0."""
+    mask = np.asarray(mask, dtype=bool)
+    A = mask.shape[-1]
+    pad = -A % 32
+    m = np.concatenate([mask, np.zeros(mask.shape[:-1] + (pad,), dtype=bool)], -1) if pad else mask
+    by = np.packbits(m, axis=-1, bitorder='little')
+    return np.ascontiguousarray(by).view('<u4').view(np.int32) if by.size else np.zeros(mask.shape[:-1] + (0,), np.int32)
+
+
+def unpack_ignore_bits(words, A):
+    """int32 [..., ceil(A/32)] -> bool [..., A] (the inverse of ``pack_ignore_bits``)."""
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.int32)).view(np.uint8)
+    return np.unpackbits(w, axis=-1, bitorder='little')[..., :A].astype(bool)

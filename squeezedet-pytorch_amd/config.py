@@ -41,6 +41,8 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         flip_prob=0.5, drift_prob=1., seed=42,      # training augmentation (train_data.TrainLoader), src/utils/config.py:53-56
         brightness_jitter=0., contrast_jitter=0., saturation_jitter=0.,      # colour jitter amounts (augment.draw_color); 0 = off
         sparse_gt=False,             # training ground truth as the list of positives (ops.SparseGT in batch['gt_sparse']) instead of dense
+        ignore_overlap=None,         # None: off.  A float in (0, 1] (0.5 is the documented value; needs sparse_gt): anchors covered to that share
+                                     # by a flagged box (DontCare / difficult / crowd) leave the loss (batch['gt_ignore'], ops.loss_masked_*)
         inflight=2,                  # batches in flight on the device in Detector.stream / detect_dataset (lanes.DetectStream)
         input_size=tuple(input_size), num_classes=num_classes, class_names=tuple(class_names),
         anchors=anchors, anchors_per_grid=int(np.asarray(anchors_seed).shape[0]),

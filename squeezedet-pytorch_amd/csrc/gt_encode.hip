@@ -217,3 +217,67 @@ extern "C" int sqd_encode_gt_fwd(const float* boxes, const int* class_ids, const
   hipLaunchKernelGGL(encode_gt_kernel, dim3((unsigned)B), dim3(GT_THREADS), lds, (hipStream_t)stream, a);
   return sqd_launch_status();
 }
+
+// ---- anchor ignore bitmap: which anchors lie on an ignore region (KITTI DontCare, VOC difficult, COCO crowd) ---------------------------
+// Bit a of image b is set iff area > 0 and inter >= overlap * area for SOME ignore box of the image, with the anchor corners the
+// encoder above uses, inter the intersection with the box and area the ANCHOR's area: intersection over anchor area, the per-box
+// maximum.  (An IoU would never fire for a small anchor inside a large region.)  All float64 and no division, so a numpy float64
+// restatement gives the same bits (boxes.anchor_ignore_mask).  One thread per anchor, grid (ceil(A / 256), B); the image's boxes pass
+// through LDS in chunks of IGN_THREADS; a wave's 64 results leave as two ballot words, so every word of mask [B][ceil(A / 32)] is
+// written (bits at and past A are 0) and the caller needs no memset.
+constexpr int IGN_THREADS = 256;
+constexpr int IGN_MAX_BOXES = 65535;                   // ignore boxes per image
+
+__global__ __launch_bounds__(IGN_THREADS) void anchor_ignore_kernel(const float* __restrict__ boxes, const int* __restrict__ offsets,
+                                                                    const double* __restrict__ anchors, unsigned* __restrict__ mask,
+                                                                    double overlap, int total, int A) {
+  __shared__ float s_box[IGN_THREADS][4];
+  const int b = blockIdx.y, tid = threadIdx.x, i = blockIdx.x * IGN_THREADS + tid;
+  const int beg = max(0, offsets[b]), end = min(total, offsets[b + 1]);      // (a malformed table reads nothing out of bounds)
+  double x0 = 0.0, y0 = 0.0, x1 = 0.0, y1 = 0.0, area = 0.0;
+  if (i < A) {
+    const double ax = anchors[4 * i], ay = anchors[4 * i + 1], aw = anchors[4 * i + 2], ah = anchors[4 * i + 3];
+    x0 = ax - 0.5 * (aw - 1.0); y0 = ay - 0.5 * (ah - 1.0);
+    x1 = ax + 0.5 * (aw - 1.0); y1 = ay + 0.5 * (ah - 1.0);
+    area = (x1 - x0) * (y1 - y0);
+  }
+  const bool live = i < A && area > 0.0;
+  bool hit = false;
+  for (int c = beg; c < end; c += IGN_THREADS) {        // (block-uniform)
+    const int n = min(IGN_THREADS, end - c);
+    __syncthreads();
+    if (tid < n) {
+      const float* bx = boxes + 4 * (long long)(c + tid);
+      s_box[tid][0] = bx[0]; s_box[tid][1] = bx[1]; s_box[tid][2] = bx[2]; s_box[tid][3] = bx[3];
+    }
+    __syncthreads();
+    if (live && !hit) {
+      for (int k = 0; k < n; ++k) {
+        const double lr = fmax(fmin(x1, (double)s_box[k][2]) - fmax(x0, (double)s_box[k][0]), 0.0);
+        const double tb = fmax(fmin(y1, (double)s_box[k][3]) - fmax(y0, (double)s_box[k][1]), 0.0);
+        if (lr * tb >= overlap * area) hit = true;
+      }
+    }
+  }
+  const unsigned long long bal = __ballot(hit);
+  const int lane = tid & 63, nwords = (A + 31) >> 5;
+  const int w0 = (blockIdx.x * IGN_THREADS + (tid & ~63)) >> 5;
+  unsigned* row = mask + (long long)b * nwords;
+  if (lane == 0 && w0 < nwords) row[w0] = (unsigned)(bal & 0xffffffffull);
+  if (lane == 32 && w0 + 1 < nwords) row[w0 + 1] = (unsigned)(bal >> 32);
+}
+
+// ign_boxes [total][4] xyxy fp32 (network-input coordinates), ign_offsets [B+1] int32, anchors [A][4] float64 (cx,cy,w,h), mask
+// uint32 [B][ceil(A/32)] (anchor a: word a >> 5, bit a & 31) -- device pointers; overlap: HOST pointer to one double in (0, 1].
+// total = 0 (ign_boxes may then be NULL) and images without boxes are legal and give zero words.  Status 1 for anything malformed, 2
+// for A > 2^20, B > 65535 or more boxes than 65535 per image can hold.
+extern "C" int sqd_anchor_ignore_fwd(const float* ign_boxes, const int* ign_offsets, const double* anchors, unsigned* mask,
+                                     const double* overlap, int total, int B, int A, void* stream) {
+  SQD_CHECK_ARG(ign_offsets && anchors && mask && overlap && B > 0 && A > 0 && total >= 0);
+  SQD_CHECK_ARG(total == 0 || ign_boxes);
+  SQD_CHECK_ARG(*overlap > 0.0 && *overlap <= 1.0);
+  if (A > (1 << 20) || B > 65535 || (long long)total > (long long)IGN_MAX_BOXES * B) return SQD_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(anchor_ignore_kernel, dim3((unsigned)sqd_cdiv(A, IGN_THREADS), (unsigned)B), dim3(IGN_THREADS), 0,
+                     (hipStream_t)stream, ign_boxes, ign_offsets, anchors, mask, *overlap, total, A);
+  return sqd_launch_status();
+}

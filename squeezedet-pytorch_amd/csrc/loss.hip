@@ -172,10 +172,12 @@ __global__ void loss_finalize_kernel(const float* __restrict__ partial, float* _
 
 // d loss / d (conf logit, 4 deltas) of one anchor: the score terms incl. the un-detached IoU path, and the delta regression.
 // us / ub: upstream gradients of the image's score and bbox components; n = n_obj.  Shared by both backward kernels.
-__device__ __forceinline__ void anchor_geom_grad(const LossArgs& a, const AnchorGeom& t, const float* __restrict__ d,
-                                                 const float* __restrict__ g, float n, float us, float ub, float (&out)[5]) {
+// nneg: the denominator of the negative score term, A - n_obj (the masked launches: a count that left the ignored anchors out).
+__device__ __forceinline__ void anchor_geom_grad_nneg(const LossArgs& a, const AnchorGeom& t, const float* __restrict__ d,
+                                                      const float* __restrict__ g, float n, float nneg, float us, float ub,
+                                                      float (&out)[5]) {
   // score terms: k*(iou*mask - conf)^2, k = w_p*mask/n + w_n*(1-mask)/(A-n)
-  const float k = us * (a.w_pos * t.mask / n + a.w_neg * (1.f - t.mask) / ((float)a.A - n));
+  const float k = us * (a.w_pos * t.mask / n + a.w_neg * (1.f - t.mask) / nneg);
   const float dL_de = 2.f * k * t.e;
   out[0] = -dL_de * t.conf * (1.f - t.conf);
   // IoU path: d e / d iou_raw = mask.  Only the rows with a box take it (about 0.1 % of a batch), and there the gradient is a
@@ -225,6 +227,11 @@ __device__ __forceinline__ void anchor_geom_grad(const LossArgs& a, const Anchor
   }
   const float kb = ub * a.w_bbox * t.mask / n * 2.f;
   for (int j = 0; j < 4; ++j) out[1 + j] = 0.f + kb * (d[j] - g[5 + j]);      // (0.f +: a row without a box never holds -0)
+}
+
+__device__ __forceinline__ void anchor_geom_grad(const LossArgs& a, const AnchorGeom& t, const float* __restrict__ d,
+                                                 const float* __restrict__ g, float n, float us, float ub, float (&out)[5]) {
+  anchor_geom_grad_nneg(a, t, d, g, n, (float)a.A - n, us, ub, out);
 }
 
 // dpred[b][a][:] = u_class[b]*d(class_b) + u_score[b]*d(score_b) + u_bbox[b]*d(bbox_b), coef[3][B]
@@ -504,6 +511,21 @@ struct SparseGT {
   int total;
 };
 
+// What a sparse kernel takes: the list, and in the MASKED form the ignore bitmap [B][ceil(A / 32)] (anchor a of image b: word a >> 5,
+// bit a & 31).  SparseArgs<false> is SparseGT itself, so the unmasked kernels keep their arguments.
+template <bool MASKED> struct SparseArgs : SparseGT {
+  SparseArgs(const SparseGT& s, const unsigned*) : SparseGT(s) {}
+};
+template <> struct SparseArgs<true> : SparseGT {
+  const unsigned* ignore;
+  SparseArgs(const SparseGT& s, const unsigned* ig) : SparseGT(s), ignore(ig) {}
+};
+
+__device__ __forceinline__ bool ignore_bit(const SparseArgs<true>& sg, int b, int A, int i) {
+  return (sg.ignore[(long long)b * ((A + 31) >> 5) + (i >> 5)] >> (i & 31)) & 1u;
+}
+__device__ __forceinline__ bool ignore_bit(const SparseArgs<false>&, int, int, int) { return false; }
+
 // image b's entries [beg, end), cut to the list (a malformed offsets table reads nothing out of bounds)
 __device__ __forceinline__ void sparse_range(const SparseGT& sg, int b, int& beg, int& end) {
   beg = max(0, sg.offsets[b]);
@@ -517,10 +539,13 @@ __device__ __forceinline__ void sparse_gt_row(const SparseGT& sg, int e, float (
   for (int k = 0; k < 4; ++k) { g[1 + k] = sg.boxes[4 * (long long)e + k]; g[5 + k] = sg.deltas[4 * (long long)e + k]; }
 }
 
-template <int R>
-__global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArgs a, SparseGT sg, float* __restrict__ partial) {
+// MASKED: a row that is no positive and whose ignore bit is set adds nothing but a count, the sixth partial sum n_ign
+// (partial [B][LOSS_NPART][6]); the words are read from global memory by the global anchor index (a slice's lo is no multiple of 32).
+template <int R, bool MASKED = false>
+__global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArgs a, SparseArgs<MASKED> sg, float* __restrict__ partial) {
+  constexpr int NS = MASKED ? 6 : 5;
   __shared__ unsigned bitmap[LS_BITMAP_WORDS];
-  __shared__ float red[5][MC_THREADS / 64];
+  __shared__ float red[NS][MC_THREADS / 64];
   const int b = blockIdx.y, blk = blockIdx.x, C = a.C, tid = threadIdx.x;
   const int per = (a.A + LOSS_NPART - 1) / LOSS_NPART;
   const int lo = blk * per, hi = min(a.A, lo + per);
@@ -534,11 +559,13 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArg
     if (i >= lo && i < hi) atomicOr(&bitmap[(i - lo) >> 5], 1u << ((i - lo) & 31));
   }
   __syncthreads();
-  float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  float s[NS] = {};
   // 2. every row of the slice: a marked row counts toward n_obj, any other adds sigmoid(conf)^2 (the dense e * e at mask = 0)
   for (int i = lo + tid; i < hi; i += MC_THREADS) {
     if ((bitmap[(i - lo) >> 5] >> ((i - lo) & 31)) & 1u) {
       s[0] += 1.f;
+    } else if (MASKED && ignore_bit(sg, b, a.A, i)) {
+      s[NS - 1] += 1.f;
     } else {
       const float conf = 1.f / (1.f + expf(-a.pred[((long long)b * a.A + i) * (C + 5) + C]));
       const float e = 0.f - conf;
@@ -572,29 +599,73 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArg
   }
   const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
-  for (int k = 0; k < 5; ++k) {
+  for (int k = 0; k < NS; ++k) {
     float v = s[k];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
     if (lane == 0) red[k][wave] = v;
   }
   __syncthreads();
-  if (tid < 5) {
+  if (tid < NS) {
     float v = 0.f;
     for (int w = 0; w < MC_THREADS / 64; ++w) v += red[tid][w];
-    partial[((long long)b * LOSS_NPART + blk) * 5 + tid] = v;
+    partial[((long long)b * LOSS_NPART + blk) * NS + tid] = v;
   }
+}
+
+// The masked forward's second stage: loss_finalize_kernel on partial [B][LOSS_NPART][6] with n_neg = A - n_obj - n_ign and the
+// zero-denominator conventions: class, pos and bbox are 0 where n_obj = 0, neg is 0 where n_neg = 0.  counts [2][B] = (n_obj, n_neg).
+// With n_ign = 0 and n_obj > 0 every operation is loss_finalize_kernel's, in its order: the same bits.
+__device__ __forceinline__ void masked_image_losses(const float* __restrict__ partial, int b, int A, float w_class, float w_pos,
+                                                    float w_neg, float w_bbox, float (&v)[4], float& n, float& nneg) {
+  float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int k = 0; k < LOSS_NPART; ++k)
+    for (int j = 0; j < 6; ++j) s[j] += partial[((long long)b * LOSS_NPART + k) * 6 + j];
+  n = s[0];
+  nneg = (float)A - n - s[5];
+  const float cls = n > 0.f ? w_class * s[1] / n : 0.f, pos = n > 0.f ? w_pos * s[2] / n : 0.f;
+  const float neg = nneg > 0.f ? w_neg * s[3] / nneg : 0.f, bbx = n > 0.f ? w_bbox * s[4] / n : 0.f;
+  v[0] = cls; v[1] = pos + neg; v[2] = bbx; v[3] = cls + pos + neg + bbx;
+}
+
+__global__ void loss_masked_finalize_kernel(const float* __restrict__ partial, float* __restrict__ losses, float* __restrict__ counts,
+                                            int B, int A, float w_class, float w_pos, float w_neg, float w_bbox, float* __restrict__ mean4) {
+  if (mean4) {                                          // ONE block walks the images in loss_finalize_kernel's fixed order
+    float m[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int b = threadIdx.x; b < B; b += 64) {
+      float v[4], n, nneg;
+      masked_image_losses(partial, b, A, w_class, w_pos, w_neg, w_bbox, v, n, nneg);
+      for (int j = 0; j < 4; ++j) { losses[j * B + b] = v[j]; m[j] += v[j]; }
+      counts[b] = n; counts[B + b] = nneg;
+    }
+    for (int j = 0; j < 4; ++j) {
+      float v = m[j];
+      for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+      if (threadIdx.x == 0) mean4[j] = v / (float)B;
+    }
+    return;
+  }
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float v[4], n, nneg;
+  masked_image_losses(partial, b, A, w_class, w_pos, w_neg, w_bbox, v, n, nneg);
+  for (int j = 0; j < 4; ++j) losses[j * B + b] = v[j];
+  counts[b] = n; counts[B + b] = nneg;
 }
 
 // One launch writes all of dpred.  Workgroup (x, b) owns rows x * LS_ROWS .. of image b: it looks its rows up in the image's list
 // (slot[row] = entry + 1), writes every negative row as zeros with the confidence gradient in column C (anchor_geom_grad at mask = 0),
 // consecutive lanes storing consecutive 16-byte pieces, and hands each positive row to a lane group as loss_many_bwd_kernel does.
-template <int R>
-__global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a, SparseGT sg, const float* __restrict__ nobj,
+// MASKED: ``nobj`` is counts [2][B] = (n_obj, n_neg) of the masked forward.  A positive row is what the unmasked kernel writes (the
+// negative denominator reaches it only as w_neg * 0 / n_neg); a row that is no positive and whose ignore bit is set is all +0; every
+// other row carries the confidence gradient with 1 / n_neg, and nothing is NaN because a count is 0.
+template <int R, bool MASKED = false>
+__global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a, SparseArgs<MASKED> sg, const float* __restrict__ nobj,
                                                                      const float* __restrict__ coef, float* __restrict__ dpred,
                                                                      const float* __restrict__ gmean) {
   __shared__ int slot[LS_ROWS];
   __shared__ float cgrad[LS_ROWS];
+  __shared__ unsigned char ign[MASKED ? LS_ROWS : 1];
   const int b = blockIdx.y, row0 = blockIdx.x * LS_ROWS, C = a.C, W = C + 5, tid = threadIdx.x;
   const int nrows = min(LS_ROWS, a.A - row0);
   slot[tid] = 0;
@@ -609,23 +680,46 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a,
   const float gm = gmean ? gmean[0] / (float)a.B : 0.f;
   const float uc = gmean ? gm : coef[0 * a.B + b], us = gmean ? gm : coef[1 * a.B + b], ub = gmean ? gm : coef[2 * a.B + b];
   // mask = 0 in the dense formulas: the score coefficient, and what the class / delta columns hold (0, or NaN where n_obj = 0)
-  const float kneg = us * (a.w_pos * 0.f / n + a.w_neg * (1.f - 0.f) / ((float)a.A - n));
-  const float zc = (uc * a.w_class * 0.f / n) * 0.f;
-  const float zd = kneg * 0.f + (ub * a.w_bbox * 0.f / n * 2.f) * 0.f;
+  // MASKED: the same expressions where their denominator is a count > 0 (so a zero keeps the sign it has there), else 0; for
+  // n > 0 the dropped w_pos * 0 / n is an exact zero added in front
+  float nneg = 0.f, kneg, zc, zd;
+  if constexpr (MASKED) {
+    nneg = nobj[a.B + b];
+    kneg = nneg > 0.f ? us * (0.f + a.w_neg * (1.f - 0.f) / nneg) : 0.f;
+    zc = n > 0.f ? (uc * a.w_class * 0.f / n) * 0.f : 0.f;
+    zd = n > 0.f ? kneg * 0.f + (ub * a.w_bbox * 0.f / n * 2.f) * 0.f : 0.f;
+  } else {
+    kneg = us * (a.w_pos * 0.f / n + a.w_neg * (1.f - 0.f) / ((float)a.A - n));
+    zc = (uc * a.w_class * 0.f / n) * 0.f;
+    zd = kneg * 0.f + (ub * a.w_bbox * 0.f / n * 2.f) * 0.f;
+  }
   __syncthreads();
   const long long base = (long long)b * a.A + row0;
+  if (MASKED && tid < nrows) ign[tid] = slot[tid] == 0 && ignore_bit(sg, b, a.A, row0 + tid);
   if (tid < nrows && slot[tid] == 0) {
     const float conf = 1.f / (1.f + expf(-a.pred[(base + tid) * W + C]));
     const float dL_de = 2.f * kneg * (0.f - conf);
     cgrad[tid] = -dL_de * conf * (1.f - conf);
+    if (MASKED && ign[tid]) cgrad[tid] = 0.f;                                     // (ign[tid]: this thread's own write)
   }
+  // an ignored row differs from a negative one outside column C only where zc / zd are not +0 (a negative upstream gradient gives
+  // -0): only then does a store have to look the row up
+  const bool zplain = MASKED && __float_as_uint(zc) == 0u && __float_as_uint(zd) == 0u;
   __syncthreads();
   float* __restrict__ o = dpred + base * W;
   {
     // the workgroup's nrows * W floats are contiguous: up to three floats to the first 16-byte boundary, 16-byte stores, a tail.  A
     // vector covers at most two rows (W >= 6); one that touches a positive row stores its other floats one by one.
     const int nfl = nrows * W;
-    const auto val = [&](int r, int col) { return col < C ? zc : (col == C ? cgrad[r] : zd); };
+    const auto val = [&](int r, int col) {
+      if constexpr (MASKED) {
+        if (col == C) return cgrad[r];
+        if (!zplain && ign[r]) return 0.f;
+        return col < C ? zc : zd;
+      } else {
+        return col < C ? zc : (col == C ? cgrad[r] : zd);
+      }
+    };
     int head = (int)((4 - ((base * W) & 3)) & 3);
     if ((reinterpret_cast<uintptr_t>(dpred) & 15) != 0 || head > nfl) head = nfl;          // (an unaligned dpred: all of it one by one)
     const int nv = (nfl - head) / 4;
@@ -680,7 +774,8 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a,
       if (c < C) orow[c] = kc * (ohs * (ex[k] / sum) - (c == cls ? 1.f : 0.f));
     }
     float og[5];
-    anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
+    if (MASKED) anchor_geom_grad_nneg(a, t, p + C + 1, g, n, nneg > 0.f ? nneg : 1.f, us, ub, og);      // (mask = 1: w_neg * 0 / n_neg)
+    else anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
     if (j < 5) orow[C + j] = (j == 0) ? og[0] : (j == 1) ? og[1] : (j == 2) ? og[2] : (j == 3) ? og[3] : og[4];
   }
 }
@@ -698,16 +793,20 @@ static int fill_args_sparse(LossArgs& a, SparseGT& sg, const float* pred, const 
   return SQD_OK;
 }
 
-static void launch_loss_sparse_partial(const LossArgs& a, const SparseGT& sg, float* workspace, hipStream_t s) {
-#define CALL(R) hipLaunchKernelGGL(loss_sparse_partial_kernel<R>, dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), 0, s, a, sg, workspace)
+template <bool MASKED = false>
+static void launch_loss_sparse_partial(const LossArgs& a, const SparseGT& sg, float* workspace, hipStream_t s, const unsigned* ignore = nullptr) {
+  const SparseArgs<MASKED> sa(sg, ignore);
+#define CALL(R) hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_sparse_partial_kernel<R, MASKED>), dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), 0, s, a, sa, workspace)
   MC_DISPATCH(a.C, CALL);
 #undef CALL
 }
 
+template <bool MASKED = false>
 static void launch_loss_sparse_bwd(const LossArgs& a, const SparseGT& sg, const float* nobj, const float* coef, float* dpred,
-                                   const float* gmean, hipStream_t s) {
+                                   const float* gmean, hipStream_t s, const unsigned* ignore = nullptr) {
   const dim3 grid((unsigned)sqd_cdiv(a.A, LS_ROWS), (unsigned)a.B);
-#define CALL(R) hipLaunchKernelGGL(loss_sparse_bwd_kernel<R>, grid, dim3(MC_THREADS), 0, s, a, sg, nobj, coef, dpred, gmean)
+  const SparseArgs<MASKED> sa(sg, ignore);
+#define CALL(R) hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_sparse_bwd_kernel<R, MASKED>), grid, dim3(MC_THREADS), 0, s, a, sa, nobj, coef, dpred, gmean)
   MC_DISPATCH(a.C, CALL);
 #undef CALL
 }
@@ -765,5 +864,69 @@ extern "C" int sqd_loss_sparse_mean_bwd(const float* pred, const int* anchor_idx
                                 input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
   SQD_CHECK_ARG(nobj && gmean && dpred);
   launch_loss_sparse_bwd(a, sg, nobj, nullptr, dpred, gmean, (hipStream_t)stream);
+  return sqd_launch_status();
+}
+
+// ---- masked sparse loss: ignore regions and object-free images ---------------------------------------------------------------------------
+// The sparse launches + ignore [B][ceil(A / 32)] uint32 (sqd_anchor_ignore_fwd's bitmap).  Per image: pos = the list's valid entries,
+// ign = the anchors whose bit is set and that are no positives (a positive wins over its own bit), n_obj = |pos|, n_ign = |ign|,
+// n_neg = A - n_obj - n_ign.  class, pos-score and bbox are the sparse launches' sums / n_obj, each 0 where n_obj = 0; neg =
+// w_neg * sum over the rows outside pos and ign of sigmoid(conf)^2 / n_neg, 0 where n_neg = 0.  dpred: a positive row as the
+// unmasked launch writes it, a row of ign all zeros, any other row zeros and the confidence gradient with 1 / n_neg.  workspace:
+// float[B * 16 * 6]; counts: float[2][B] = (n_obj, n_neg), what the backward takes where the unmasked one takes nobj.  An all-zero
+// bitmap on images that all have positives gives the unmasked launches' bits.
+extern "C" int sqd_loss_masked_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                                   const int* offsets, const unsigned* ignore, const float* anchors, float* workspace, float* losses,
+                                   float* counts, int total, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                                   float w_pos, float w_neg, float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
+                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(ignore && workspace && losses && counts);
+  hipStream_t s = (hipStream_t)stream;
+  launch_loss_sparse_partial<true>(a, sg, workspace, s, ignore);
+  hipLaunchKernelGGL(loss_masked_finalize_kernel, dim3((unsigned)sqd_cdiv(B, 64)), dim3(64), 0, s, workspace, losses, counts, B, A,
+                     w_class, w_pos, w_neg, w_bbox, (float*)nullptr);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_loss_masked_mean_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                        const int* class_ids, const int* offsets, const unsigned* ignore, const float* anchors,
+                                        float* workspace, float* losses, float* counts, float* mean4, int total, int B, int A,
+                                        int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                                        float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
+                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(ignore && workspace && losses && counts && mean4);
+  hipStream_t s = (hipStream_t)stream;
+  launch_loss_sparse_partial<true>(a, sg, workspace, s, ignore);
+  hipLaunchKernelGGL(loss_masked_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, losses, counts, B, A, w_class, w_pos, w_neg,
+                     w_bbox, mean4);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_loss_masked_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                                   const int* offsets, const unsigned* ignore, const float* anchors, const float* counts,
+                                   const float* coef, float* dpred, int total, int B, int A, int num_classes, int input_h, int input_w,
+                                   float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
+                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(ignore && counts && coef && dpred);
+  launch_loss_sparse_bwd<true>(a, sg, counts, coef, dpred, nullptr, (hipStream_t)stream, ignore);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_loss_masked_mean_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                        const int* class_ids, const int* offsets, const unsigned* ignore, const float* anchors,
+                                        const float* counts, const float* gmean, float* dpred, int total, int B, int A,
+                                        int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                                        float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
+                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(ignore && counts && gmean && dpred);
+  launch_loss_sparse_bwd<true>(a, sg, counts, nullptr, dpred, gmean, (hipStream_t)stream, ignore);
   return sqd_launch_status();
 }

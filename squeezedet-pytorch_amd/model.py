@@ -410,17 +410,23 @@ class Loss(nn.Module):
         self.negative_score_loss_weight = cfg.negative_score_loss_weight
         self.bbox_loss_weight = cfg.bbox_loss_weight
 
-    def forward(self, pred, gt):
-        """``gt``: the dense tensor [B,A,C+9] or an ``ops.SparseGT`` (the positives as a list: the sparse loss launches)."""
+    def forward(self, pred, gt, ignore=None):
+        """``gt``: the dense tensor [B,A,C+9] or an ``ops.SparseGT`` (the positives as a list: the sparse loss launches).  ``ignore``:
+        an anchor ignore bitmap int32 [B, ceil(A/32)] (``ops.anchor_ignore_mask``; sparse ``gt`` only): the masked launches, which
+        leave ignored anchors out of the loss and give finite values on an object-free image."""
         from .autograd import loss_apply
-        return loss_apply(self, pred, gt)
+        return loss_apply(self, pred, gt, ignore)
 
-    def mean_loss(self, pred, gt):
-        """``forward(pred, gt)[0].mean()`` and the (detached) statistics as one autograd node whose forward and backward are the loss
-        kernels alone (backward.LossMeanFn; LossSparseMeanFn for an ``ops.SparseGT``): -> (mean total loss, 0-dim; stats dict of
-        per-image vectors)."""
-        from .backward import LossMeanFn, LossSparseMeanFn
-        if isinstance(gt, ops.SparseGT):
+    def mean_loss(self, pred, gt, ignore=None):
+        """``forward(pred, gt, ignore)[0].mean()`` and the (detached) statistics as one autograd node whose forward and backward are the
+        loss kernels alone (backward.LossMeanFn; LossSparseMeanFn for an ``ops.SparseGT``; LossMaskedMeanFn with ``ignore``): -> (mean
+        total loss, 0-dim; stats dict of per-image vectors)."""
+        from .backward import LossMeanFn, LossMaskedMeanFn, LossSparseMeanFn
+        if ignore is not None:
+            if not isinstance(gt, ops.SparseGT):
+                raise ValueError('Loss: an ignore bitmap needs a sparse ground truth (ops.SparseGT, cfg.sparse_gt); the dense loss has no masked form')
+            mean, vec = LossMaskedMeanFn.apply(pred, self.resolver.anchors_on(pred.device), self, ignore, *gt)
+        elif isinstance(gt, ops.SparseGT):
             mean, vec = LossSparseMeanFn.apply(pred, self.resolver.anchors_on(pred.device), self, *gt)
         else:
             mean, vec = LossMeanFn.apply(pred, gt, self.resolver.anchors_on(pred.device), self)
@@ -437,11 +443,12 @@ class SqueezeDetWithLoss(nn.Module):
 
     def forward(self, batch):
         pred = self.base(batch['image'])
-        loss, loss_stats = self.loss(pred, batch['gt'] if 'gt' in batch else batch['gt_sparse'])
+        loss, loss_stats = self.loss(pred, batch['gt'] if 'gt' in batch else batch['gt_sparse'], batch.get('gt_ignore'))
         return loss, loss_stats
 
     def forward_mean(self, batch):
         """``forward(batch)[0].mean()`` (the scalar the reference's trainer differentiates, src/engine/trainer.py:43) + the per-image
-        statistics, with the mean and its backward inside the loss kernels (no torch kernel between loss and backbone)."""
+        statistics, with the mean and its backward inside the loss kernels (no torch kernel between loss and backbone).
+        ``batch['gt_ignore']`` (optional, with ``'gt_sparse'``): the anchor ignore bitmap."""
         pred = self.base(batch['image'])
-        return self.loss.mean_loss(pred, batch['gt'] if 'gt' in batch else batch['gt_sparse'])
+        return self.loss.mean_loss(pred, batch['gt'] if 'gt' in batch else batch['gt_sparse'], batch.get('gt_ignore'))

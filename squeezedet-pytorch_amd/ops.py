@@ -1450,6 +1450,164 @@ def loss_sparse_mean_bwd(pred, sgt, anchors, nobj, gmean, input_size, num_classe
     return dpred
 
 
+def ignore_words(A):
+    """Words per image of an anchor ignore bitmap: anchor a is bit ``a & 31`` of word ``a >> 5``."""
+    return (int(A) + 31) // 32
+
+
+def check_ignore_overlap(name, overlap):
+    """``overlap`` as a float in (0, 1] (``cfg.ignore_overlap`` when it is set)."""
+    try:
+        v = float(overlap)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name}: ignore overlap must be a number in (0, 1], got {overlap!r}') from None
+    if not (v > 0.0 and v <= 1.0):              # (NaN fails both)
+        raise ValueError(f'{name}: ignore overlap must be in (0, 1], got {overlap!r}')
+    return v
+
+
+def anchor_ignore_mask(ign_boxes, ign_offsets, anchors64, overlap, out=None):
+    """The anchors that lie on an ignore region (KITTI ``DontCare``, VOC ``difficult``, COCO ``crowd``): ign_boxes fp32 [total,4] xyxy in
+    network-input coordinates, ign_offsets int32 [B+1], anchors64 float64 [A,4] (cx,cy,w,h), all on the GPU -> int32 [B, ceil(A/32)],
+    bit ``a & 31`` of word ``a >> 5`` set iff ``inter >= overlap * area(anchor) > 0`` for some box of the image (float64, the rule of
+    ``boxes.anchor_ignore_mask``, bit for bit).  ``total = 0`` and images without boxes give zero words.  One launch, every word
+    written (``out``: a contiguous int32 [B, ceil(A/32)] device tensor to write instead; it needs no clearing), nothing waits."""
+    overlap = check_ignore_overlap('anchor_ignore_mask', overlap)
+    if not isinstance(ign_boxes, torch.Tensor) or ign_boxes.dtype != torch.float32 or ign_boxes.dim() != 2 or ign_boxes.shape[1] != 4:
+        raise ValueError('anchor_ignore_mask: ign_boxes must be fp32 [total,4]')
+    if not isinstance(ign_offsets, torch.Tensor) or ign_offsets.dtype != torch.int32 or ign_offsets.dim() != 1 or ign_offsets.shape[0] < 2:
+        raise ValueError('anchor_ignore_mask: ign_offsets must be int32 [B+1], B >= 1')
+    if not isinstance(anchors64, torch.Tensor) or anchors64.dtype != torch.float64 or anchors64.dim() != 2 or anchors64.shape[1] != 4 \
+            or anchors64.shape[0] < 1:
+        raise ValueError('anchor_ignore_mask: anchors must be float64 [A,4]')
+    B, A, total = ign_offsets.shape[0] - 1, anchors64.shape[0], ign_boxes.shape[0]
+    if A > 2 ** 20 or B > 65535 or total > 65535 * B:
+        raise ValueError(f'anchor_ignore_mask: at most 2^20 anchors, 65535 images and 65535 ignore boxes per image, got A={A} B={B} total={total}')
+    if not anchors64.is_cuda:
+        raise ValueError(f'anchor_ignore_mask: anchors must be on the GPU, got {anchors64.device}')
+    for t, nm in ((ign_boxes, 'ign_boxes'), (ign_offsets, 'ign_offsets')):
+        if t.device != anchors64.device:
+            raise ValueError(f'anchor_ignore_mask: {nm} is on {t.device}, anchors on {anchors64.device}')
+    ign_boxes, ign_offsets, anchors64 = ign_boxes.contiguous(), ign_offsets.contiguous(), anchors64.contiguous()
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (B, ignore_words(A))
+                            or out.device != anchors64.device or not out.is_contiguous()):
+        raise ValueError(f'anchor_ignore_mask: out must be a contiguous int32 [{B}, {ignore_words(A)}] tensor on the device of the anchors')
+    mask = torch.empty(B, ignore_words(A), device=anchors64.device, dtype=torch.int32) if out is None else out
+    br = _Bracket('anchor_ignore', f'ignore A{A}', 0.0, 32.0 * A + 16.0 * total + 4.0 * mask.numel()) if timing._timer is not None else None
+    rc = nat.lib().sqd_anchor_ignore_fwd(nat.ptr(ign_boxes) if total else None, nat.ptr(ign_offsets), nat.ptr(anchors64), nat.ptr(mask),
+                                         ctypes.byref(ctypes.c_double(overlap)), int(total), B, A, nat.stream_handle(anchors64.device))
+    nat.check(rc, 'sqd_anchor_ignore_fwd')
+    if br is not None:
+        br.done()
+    return mask
+
+
+def _check_masked_loss_args(name, pred, sgt, ignore, anchors, num_classes):
+    """``_check_sparse_loss_args`` + the bitmap: int32 [B, ceil(A/32)] on the device of pred.  -> (B, A, total, sgt, ignore)."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 3:
+        raise ValueError(f'{name}: pred must be fp32 [B,A,C+5]')
+    B, A = pred.shape[:2]                               # (kinds and shapes first, devices last: the bitmap before the list's devices)
+    if not isinstance(ignore, torch.Tensor) or ignore.dtype != torch.int32 or tuple(ignore.shape) != (B, ignore_words(A)):
+        raise ValueError(f'{name}: ignore must be int32 [B, ceil(A/32)] = [{B}, {ignore_words(A)}] (ops.anchor_ignore_mask), got '
+                         f'{getattr(ignore, "dtype", type(ignore))} {tuple(getattr(ignore, "shape", ()))}')
+    B, A, total, sgt = _check_sparse_loss_args(name, pred, sgt, anchors, num_classes)
+    if ignore.device != pred.device:
+        raise ValueError(f'{name}: ignore is on {ignore.device}, pred on {pred.device}')
+    return B, A, total, sgt, ignore.contiguous()
+
+
+def _check_counts(name, counts, B, pred):
+    if not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (2, B) or counts.dtype != torch.float32 or counts.device != pred.device:
+        raise ValueError(f'{name}: counts must be fp32 [2,B] = (n_obj, n_neg) on the device of pred')
+    return counts.contiguous()
+
+
+def loss_masked_fwd(pred, sgt, ignore, anchors, input_size, num_classes, weights):
+    """``loss_sparse_fwd`` with an anchor ignore bitmap (``anchor_ignore_mask``): -> (losses [4,B], counts [2,B] = (n_obj, n_neg)).
+    An anchor whose bit is set and that is no positive is neither a positive nor a negative; class / pos / bbox are 0 where
+    n_obj = 0 and neg is 0 where n_neg = 0, so an object-free image gives finite values."""
+    B, A, total, sgt, ignore = _check_masked_loss_args('loss_masked_fwd', pred, sgt, ignore, anchors, num_classes)
+    pred, anchors = pred.contiguous(), anchors.contiguous()
+    ws = torch.empty(B * 16 * 6, device=pred.device, dtype=torch.float32)
+    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
+    counts = torch.empty(2, B, device=pred.device, dtype=torch.float32)
+    br = _Bracket('loss_masked_fwd', f'loss A{A}', 0.0, _sparse_fwd_bytes(B, A, total, num_classes) + B * A / 8.0) if timing._timer is not None else None
+    rc = nat.lib().sqd_loss_masked_fwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(ignore), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses),
+                                       nat.ptr(counts), total, B, A, num_classes, int(input_size[0]), int(input_size[1]),
+                                       *[float(w) for w in weights], nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_loss_masked_fwd')
+    if br is not None:
+        br.done()
+    return losses, counts
+
+
+def loss_masked_mean_fwd(pred, sgt, ignore, anchors, input_size, num_classes, weights):
+    """``loss_masked_fwd`` + the batch means: -> (losses [4,B], counts [2,B], mean4 [4]); the per-image values equal
+    ``loss_masked_fwd``'s bit for bit."""
+    B, A, total, sgt, ignore = _check_masked_loss_args('loss_masked_mean_fwd', pred, sgt, ignore, anchors, num_classes)
+    pred, anchors = pred.contiguous(), anchors.contiguous()
+    ws = torch.empty(B * 16 * 6, device=pred.device, dtype=torch.float32)
+    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
+    counts = torch.empty(2, B, device=pred.device, dtype=torch.float32)
+    mean4 = torch.empty(4, device=pred.device, dtype=torch.float32)
+    br = _Bracket('loss_masked_fwd', f'loss A{A}', 0.0, _sparse_fwd_bytes(B, A, total, num_classes) + B * A / 8.0) if timing._timer is not None else None
+    rc = nat.lib().sqd_loss_masked_mean_fwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(ignore), nat.ptr(anchors), nat.ptr(ws),
+                                            nat.ptr(losses), nat.ptr(counts), nat.ptr(mean4), total, B, A, num_classes,
+                                            int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
+                                            nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_loss_masked_mean_fwd')
+    if br is not None:
+        br.done()
+    return losses, counts, mean4
+
+
+def loss_masked_bwd(pred, sgt, ignore, anchors, counts, coef, input_size, num_classes, weights, out=None):
+    """``loss_sparse_bwd`` with the bitmap: coef [3,B], counts [2,B] of the masked forward -> dpred [B,A,C+5], every element written
+    (an ignored row that is no positive: zeros).  ``out``: a fp32 [B,A,C+5] device tensor with contiguous strides to write instead
+    (any storage offset)."""
+    B, A, total, sgt, ignore = _check_masked_loss_args('loss_masked_bwd', pred, sgt, ignore, anchors, num_classes)
+    counts = _check_counts('loss_masked_bwd', counts, B, pred)
+    if not isinstance(coef, torch.Tensor) or tuple(coef.shape) != (3, B) or coef.device != pred.device:
+        raise ValueError('loss_masked_bwd: coef must be [3,B] on the device of pred')
+    pred, anchors, coef = pred.contiguous(), anchors.contiguous(), coef.contiguous().float()
+    dpred = _masked_dpred('loss_masked_bwd', pred, out)
+    br = _Bracket('loss_masked_bwd', f'lossbwd A{A}', 0.0, _sparse_bwd_bytes(B, A, total, num_classes) + B * A / 8.0) if timing._timer is not None else None
+    rc = nat.lib().sqd_loss_masked_bwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(ignore), nat.ptr(anchors), nat.ptr(counts), nat.ptr(coef),
+                                       nat.ptr(dpred), total, B, A, num_classes, int(input_size[0]), int(input_size[1]),
+                                       *[float(w) for w in weights], nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_loss_masked_bwd')
+    if br is not None:
+        br.done()
+    return dpred
+
+
+def loss_masked_mean_bwd(pred, sgt, ignore, anchors, counts, gmean, input_size, num_classes, weights, out=None):
+    """``loss_sparse_mean_bwd`` with the bitmap: gmean, a device scalar (the gradient arriving at mean(total)) -> dpred [B,A,C+5]."""
+    B, A, total, sgt, ignore = _check_masked_loss_args('loss_masked_mean_bwd', pred, sgt, ignore, anchors, num_classes)
+    counts = _check_counts('loss_masked_mean_bwd', counts, B, pred)
+    if not isinstance(gmean, torch.Tensor) or gmean.numel() != 1 or gmean.dtype != torch.float32 or gmean.device != pred.device:
+        raise ValueError('loss_masked_mean_bwd: gmean must be one fp32 value on the same device')
+    pred, anchors = pred.contiguous(), anchors.contiguous()
+    dpred = _masked_dpred('loss_masked_mean_bwd', pred, out)
+    br = _Bracket('loss_masked_bwd', f'lossbwd A{A}', 0.0, _sparse_bwd_bytes(B, A, total, num_classes) + B * A / 8.0) if timing._timer is not None else None
+    rc = nat.lib().sqd_loss_masked_mean_bwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(ignore), nat.ptr(anchors), nat.ptr(counts),
+                                            nat.ptr(gmean.contiguous()), nat.ptr(dpred), total, B, A, num_classes, int(input_size[0]),
+                                            int(input_size[1]), *[float(w) for w in weights], nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_loss_masked_mean_bwd')
+    if br is not None:
+        br.done()
+    return dpred
+
+
+def _masked_dpred(name, pred, out):
+    if out is None:
+        return torch.empty_like(pred)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != pred.shape or out.device != pred.device \
+            or not out.is_contiguous():
+        raise ValueError(f'{name}: out must be a contiguous fp32 {tuple(pred.shape)} tensor on the device of pred')
+    return out
+
+
 def encode_gt(boxes, class_ids, box_offsets, anchors64, num_classes, dense=True, parallel=True):
     """On-device GT encoding (compute_deltas + prepare_annotations, src/utils/boxes.py:84-135,
     src/datasets/base.py:61-76).  boxes [total,4] fp32 xyxy, class_ids [total] i32, box_offsets [B+1] i32,
@@ -1466,6 +1624,8 @@ def encode_gt(boxes, class_ids, box_offsets, anchors64, num_classes, dense=True,
     boxes, class_ids, box_offsets, anchors64 = boxes.contiguous(), class_ids.contiguous(), box_offsets.contiguous(), anchors64.contiguous()
     dev = boxes.device
     gt = torch.empty(B, A, num_classes + 9, device=dev, dtype=torch.float32) if dense else None
+    if total == 0 and not dense:                   # nothing to assign and nothing to zero: no launch
+        return None, torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, 4, device=dev, dtype=torch.float32)
     idx = torch.empty(max(total, 1), device=dev, dtype=torch.int32)
     deltas = torch.empty(max(total, 1), 4, device=dev, dtype=torch.float32)
     br = _Bracket('encode_gt', f'gt A{A}', 0.0, 4.0 * B * A * (num_classes + 9)) if timing._timer is not None else None

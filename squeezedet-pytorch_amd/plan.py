@@ -245,7 +245,7 @@ def _wgrad(batch, H, W, N, C, taps):
 def training_launch_plan(arch='squeezedet', batch=20, input_size=(384, 1248), anchors_per_grid=9, num_classes=3,
                          use_winograd=True, data_parallel_stages=False, fuse_squeeze_bwd=True, dropout=True,
                          fused_dropout=True, fuse_train_forward=True, fuse_fire_bridge=True, fuse_stem_squeeze=True, group_wgrad=None,
-                         sparse_gt=False):
+                         sparse_gt=False, ignore_regions=False):
     """Launches of one training iteration's forward (activations saved; ``fuse_train_forward``: the stem + squeeze launch and the
     two small-C bridges run in their STORING forms -- what the backward reads is written by the fused launch -- where the table has
     their rows; the other inference-only fusions stay off), multi-task loss forward / backward and the backbone backward, as
@@ -256,7 +256,11 @@ def training_launch_plan(arch='squeezedet', batch=20, input_size=(384, 1248), an
     in the last Fire's expand launches (a weight-stationary 1x1 configuration + the balanced Winograd kernel) and ConvDet's data
     gradient runs on the balanced Winograd kernel (mask = its own input, constant scale); where that form does not apply
     (``fused_dropout`` off, squeeze width not a multiple of 8) the mask is drawn by the stand-alone ``dropout_mask`` launch.
-    ``sparse_gt`` (``cfg.sparse_gt``): the two loss rows are the sparse launches' (``ops.loss_sparse_*``); everything else is the same."""
+    ``sparse_gt`` (``cfg.sparse_gt``): the two loss rows are the sparse launches' (``ops.loss_sparse_*``); everything else is the same.
+    ``ignore_regions`` (a batch with ``'gt_ignore'``, ``cfg.ignore_overlap``; needs ``sparse_gt``): the two loss rows are the masked
+    launches' (``ops.loss_masked_*``)."""
+    if ignore_regions and not sparse_gt:
+        raise ValueError('training_launch_plan: ignore_regions needs sparse_gt (the dense loss has no masked form)')
     flags = Flags(use_winograd, True, True, fuse_fire_bridge, False, fuse_stem_squeeze, fuse_train_forward, fused_dropout)
     steps = forward_schedule(arch, batch, input_size, flags, True, 'stream' if dropout else None)
     plan = _render_forward(steps, batch, input_size, use_winograd)
@@ -268,8 +272,9 @@ def training_launch_plan(arch='squeezedet', batch=20, input_size=(384, 1248), an
     if padded:
         plan.append(('convdet_pack', f'pack N{ntrue} <- {ncd} {H}x{W}'))
     A = H * W * anchors_per_grid
-    plan.append(('loss_sparse_fwd' if sparse_gt else 'loss_fwd', f'loss A{A}'))
-    plan.append(('loss_sparse_bwd' if sparse_gt else 'loss_bwd', f'lossbwd A{A}'))
+    kind = 'loss_masked' if ignore_regions else ('loss_sparse' if sparse_gt else 'loss')
+    plan.append((kind + '_fwd', f'loss A{A}'))
+    plan.append((kind + '_bwd', f'lossbwd A{A}'))
     # ---- backward ----
     wgrad, convdet_sk = backward_schedule(arch, [(batch, st.H, st.W) for st in steps if type(st) is FireStep], ncd, fuse_squeeze_bwd,
                                           group_wgrad, steps[-1].fused_rng)

@@ -3,6 +3,13 @@
 device as ``{'image', 'image_meta', 'gt'}`` (with ``cfg.sparse_gt``: ``'gt_sparse'``, an ``ops.SparseGT``, in place of the dense ``'gt'``),
 augmented the reference's train-phase way (``augment``), ready for ``Trainer.run_epoch``.
 
+``load_annotations(i)`` may return a third element, per-box flags (bool / uint8 [n], nonzero = ignore: KITTI ``DontCare``, VOC
+``difficult``, COCO ``crowd``).  A flagged box never becomes a positive and never bounds the drift, so the draws of a dataset are the
+same with and without its flagged boxes.  With ``cfg.ignore_overlap`` unset the flagged boxes are dropped (what the reference's KITTI
+loader does to ``DontCare``); with it set (``cfg.sparse_gt`` only) they follow the image's draw, are clipped to the network input and
+become ``'gt_ignore'``, the anchor ignore bitmap of ``ops.anchor_ignore_mask`` that the masked loss reads.  An image without an
+unflagged box is a legal, object-free image.
+
 ``cfg.num_workers`` threads load the next batch and pack its raw pixels into a pinned staging buffer owned by the loader (two,
 used alternately; one is refilled only after an event shows its previous host-to-device copy has finished).  The main thread
 draws the epoch permutation and every augmentation parameter from ONE ``np.random.RandomState``, in dataset order, so the batches
@@ -22,7 +29,7 @@ import numpy as np
 import torch
 
 from . import augment
-from .annotations import encode_annotations
+from .annotations import clip_ignore_boxes, encode_annotations, ignore_overlap_of, split_flagged
 from .trainer import shard_sizes
 
 
@@ -51,7 +58,7 @@ class TrainLoader:
     """Iterable of device-resident training batches over ``dataset`` (see the module docstring).
 
     cfg fields read: batch_size (global), input_size, num_workers, device, drift_prob, flip_prob, seed, forbid_resize, anchors,
-    num_classes, brightness_jitter, contrast_jitter, saturation_jitter.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState
+    num_classes, brightness_jitter, contrast_jitter, saturation_jitter, sparse_gt, ignore_overlap.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState
     once (and, as ``[seed mod 2^32, COLOR_STREAM]``, the colour one); each epoch (``iter``) continues them."""
 
     def __init__(self, dataset, cfg, seed=None, shuffle=True, drop_last=True, rank=0, world=1):
@@ -61,6 +68,7 @@ class TrainLoader:
         if not 0 <= self.rank < self.world:
             raise ValueError(f'TrainLoader: rank {rank} outside world {world}')
         self.batch_size = int(cfg.batch_size)
+        self.ignore_overlap = ignore_overlap_of(cfg, 'TrainLoader')
         seed = getattr(cfg, 'seed', 42) if seed is None else seed
         self.rng = np.random.RandomState(seed)
         self.color_rng = np.random.RandomState(None if seed is None else np.append(np.asarray(seed, np.int64).reshape(-1) & 0xFFFFFFFF, COLOR_STREAM))
@@ -161,19 +169,23 @@ class TrainLoader:
         """The host half of a batch: draws for the whole global batch (main thread, batch order), then this rank's slice of the
         draws, transformed boxes, per-image metas and class ids (jitter on: ``'color'``, this rank's slice of the colour factors)."""
         lo, hi = self._local(idxs)
-        box_all = [np.asarray(b, np.float32).reshape(-1, 4) for _, b in ann]
+        ann = [split_flagged(a) for a in ann]             # (class ids, boxes, flagged boxes): the draws see the unflagged boxes only
+        box_all = [b for _, b, _ in ann]
         aug = augment.draw_augmentation(self.rng, gsizes, box_all, self.drift_prob, self.flip_prob)[lo:hi]
         tb, metas = zip(*[augment.transform_boxes(b, s, a, self.cfg.input_size, self.forbid_resize)
                           for b, s, a in zip(box_all[lo:hi], gsizes[lo:hi], aug)])
         p = {'index': np.asarray(idxs[lo:hi], np.int64), 'aug': aug, 'boxes': list(tb), 'metas': list(metas),
-             'class_ids': [np.asarray(c) for c, _ in ann[lo:hi]]}
+             'class_ids': [np.asarray(c) for c, _, _ in ann[lo:hi]]}
+        if self.ignore_overlap is not None:
+            p['ignore_boxes'] = [clip_ignore_boxes(augment.transform_boxes(f, s, a, self.cfg.input_size, self.forbid_resize)[0], self.cfg.input_size)
+                                 for (_, _, f), s, a in zip(ann[lo:hi], gsizes[lo:hi], aug)]
         if self.color_on:
             p['color'] = augment.draw_color(self.color_rng, len(idxs), *self.color_jitter)[lo:hi]
         return p
 
     def plan(self):
         """One epoch's host side only (no pixels, no device): per batch this rank's dataset indices, draws, transformed boxes (jitter
-        on: the colour factors under ``'color'``).  Consumes the loader's RandomStates exactly as iterating the epoch does."""
+        on: the colour factors under ``'color'``; ``cfg.ignore_overlap`` set: the transformed, clipped flagged boxes under ``'ignore_boxes'``).  Consumes the loader's RandomStates exactly as iterating the epoch does."""
         for idxs in self._global_batches():
             yield self._plan_batch(idxs, [self._size_of(int(i)) for i in idxs], [self.dataset.load_annotations(int(i)) for i in idxs])
 
@@ -193,12 +205,20 @@ class TrainLoader:
         out = torch.empty(B, 3, H, W, device=self.device, dtype=torch.float32)
         augment.launch(dev_buf, B, hdr, self.cfg.input_size, out, self.forbid_resize, self.rgb_mean, self.rgb_std, color=color is not None)
         sparse = bool(getattr(self.cfg, 'sparse_gt', False))      # the positives as a list (ops.SparseGT): no dense tensor is built
-        gt = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device, dense=not sparse)
+        ignore = None
+        if self.ignore_overlap is not None:
+            gt, ignore = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device, dense=False,
+                                            ignore_boxes_list=p['ignore_boxes'], ignore_overlap=self.ignore_overlap)
+        else:
+            gt = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device, dense=not sparse)
         meta = augment.batch_meta(metas, sizes, self.rgb_mean, self.rgb_std)
         meta['index'] = p['index']
         if color is not None:
             meta['color'] = color
-        return {'image': out, 'image_meta': meta, 'gt_sparse' if sparse else 'gt': gt}
+        batch = {'image': out, 'image_meta': meta, 'gt_sparse' if sparse else 'gt': gt}
+        if ignore is not None:
+            batch['gt_ignore'] = ignore
+        return batch
 
     def __iter__(self):
         batches = self._global_batches()

@@ -274,12 +274,22 @@ def encode_sparse_batch(batch, cfg):
     coordinates) instead of the dense ``gt`` gets the dense tensor built ON THE GPU (``annotations.encode_annotations``;
     the reference does it per image in DataLoader workers, src/datasets/base.py:61-76).  With ``cfg.sparse_gt`` the batch gets
     ``'gt_sparse'`` (an ``ops.SparseGT``: the positives as a list, read by the sparse loss launches) instead and no dense tensor is
-    built.  Dense batches pass through, whatever the flag."""
+    built.  Dense batches pass through, whatever the flag.  ``cfg.ignore_overlap`` (needs ``cfg.sparse_gt``): ``batch['gt_ignore_boxes']``,
+    a per-image list of ignore boxes (xyxy, network-input coordinates; absent: none), becomes ``'gt_ignore'``, the anchor ignore
+    bitmap the masked loss reads; with the field unset the ignore boxes are dropped."""
+    from .annotations import encode_annotations, ignore_overlap_of
+    overlap = ignore_overlap_of(cfg, 'encode_sparse_batch')
     if 'gt' in batch or 'gt_sparse' in batch or 'gt_boxes' not in batch:
         return batch
-    from .annotations import encode_annotations
-    out = {k: v for k, v in batch.items() if k not in ('gt_boxes', 'gt_class_ids')}
+    out = {k: v for k, v in batch.items() if k not in ('gt_boxes', 'gt_class_ids', 'gt_ignore_boxes')}
     sparse = bool(getattr(cfg, 'sparse_gt', False))
+    if overlap is not None:
+        ign = batch.get('gt_ignore_boxes')
+        ign = [[] for _ in batch['gt_boxes']] if ign is None else ign
+        out['gt_sparse'], out['gt_ignore'] = encode_annotations(batch['gt_class_ids'], batch['gt_boxes'], cfg.anchors, cfg.num_classes,
+                                                                device=cfg.device, dense=False, ignore_boxes_list=ign,
+                                                                ignore_overlap=overlap)
+        return out
     out['gt_sparse' if sparse else 'gt'] = encode_annotations(batch['gt_class_ids'], batch['gt_boxes'], cfg.anchors, cfg.num_classes,
                                                                device=cfg.device, dense=not sparse)
     return out
