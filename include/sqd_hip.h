@@ -296,6 +296,24 @@ int sqd_preprocess_u8_padcrop_aug_color_fwd(const unsigned char* src, const long
                                             const float* color, const unsigned long long* sums, float* out, float* shifts, int* padcrop,
                                             const float* mean3, const float* std3, int B, int H, int W, void* stream);
 
+/* The third input geometry, cfg.letterbox (no reference counterpart; DESIGN.md 6b, "Letterbox and zoom-out"): the image -- for the
+ * training forms the drifted, flipped image (Hd, Wd) of the _aug_ entry points -- is resized with its aspect ratio kept into a window
+ * (top, left, h1, w1) of the H x W canvas by the rule of sqd_preprocess_u8_fwd with destination (h1, w1); every pixel outside the window
+ * is exactly +0.0f (the whitened mean).  win: DEVICE int32 [B][4] = (top, left, h1, w1) per image (clamped into the canvas), or NULL:
+ * H * Wd <= W * Hd ? (h1 = H, w1 = max(1, (Wd * H + Hd / 2) / Hd)) : (w1 = W, h1 = max(1, (Hd * W + Wd / 2) / Wd)), integer divisions in 64
+ * bits, top = (H - h1) / 2, left = (W - w1) / 2.  scales [B][2] = (h1 / Hd, w1 / Wd) (float64 division, cast to float32) and shifts [B][2] =
+ * (-(float)top / sy, -(float)left / sx) for sqd_detect_shift_fwd, either may be NULL: box / scales + shifts is boxes_postprocess with
+ * padding = (top / sy, ., left / sx, .).  A window equal to the canvas gives the results of sqd_preprocess_u8_fwd / _aug_fwd bit for bit;
+ * the colour form is that of sqd_preprocess_u8_aug_color_fwd (color and sums required). */
+int sqd_preprocess_u8_letterbox_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* win, float* out,
+                                    float* scales, float* shifts, const float* mean3, const float* std3, int B, int H, int W, void* stream);
+int sqd_preprocess_u8_letterbox_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug, const int* win,
+                                        float* out, float* scales, float* shifts, const float* mean3, const float* std3, int B, int H, int W,
+                                        void* stream);
+int sqd_preprocess_u8_letterbox_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                              const int* win, const float* color, const unsigned long long* sums, float* out, float* scales,
+                                              float* shifts, const float* mean3, const float* std3, int B, int H, int W, void* stream);
+
 /* Dataset statistics (src/utils/compute_dataset_mean_and_std.py:35-41 computes torch.mean / torch.std per image in float32; here
  * the exact integer sums they follow from): for a packed batch of uint8 HWC RGB images -- src, offsets [B] (bytes from src, no
  * alignment required), sizes [B][2] = (H, W), exactly as sqd_preprocess_u8_fwd takes them -- sums [B][3][2] uint64 = per image and

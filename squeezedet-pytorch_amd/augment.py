@@ -15,6 +15,11 @@ Colour jitter (this project's own rule, DESIGN.md 6b "Colour jitter"; off by def
 factors (``draw_color``) ride in the header of the same upload; ``launch`` then sums the image's channels on the device
 (``sqd_image_stats_u8``, the contrast pivot) and calls the colour entry points (``sqd_preprocess_u8_aug_color_fwd`` /
 ``sqd_preprocess_u8_padcrop_aug_color_fwd``) on the same stream.  The boxes and the geometric draws do not depend on it.
+
+Letterbox and zoom-out (this project's own rule, DESIGN.md 6b "Letterbox and zoom-out"; off by default): the drifted, flipped image
+is resized with its aspect ratio kept into a window of the canvas (``boxes.letterbox_window``) and the rest is the whitened mean, 0.
+Zoom-out (``draw_zoom``) shrinks that window and places it at random; the window rides in the header of the same upload and the
+``sqd_preprocess_u8_letterbox_aug_fwd`` / ``_aug_color_fwd`` launch reads it there.  No box is ever lost.
 """
 from __future__ import annotations
 
@@ -24,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .boxes import letterbox_meta, letterbox_window
 from .preprocess import KITTI_RGB_MEAN, KITTI_RGB_STD, _staging
 
 HDR_ALIGN = 256          # the packed pixels start this many bytes into the upload, after the int header
@@ -73,6 +79,37 @@ def draw_color(rng, n, brightness, contrast, saturation):
     return color
 
 
+def draw_zoom(rng, windows, canvas, zoom_out):
+    """Zoom-out (the SSD "expand" step) of letterbox ``windows`` int32 [n, 4] = (top, left, h1, w1) on ``canvas`` = (H, W).  Per image, in
+    this order: ``z = rng.uniform(1 - zoom_out, 1)``, then ``h1 <- max(1, floor(h1 * z + 0.5))`` and ``w1`` likewise (float64),
+    ``top = rng.randint(0, H - h1 + 1)``, ``left = rng.randint(0, W - w1 + 1)``: three draws per image, always.  Returns int32 [n, 4]."""
+    d = float(zoom_out)
+    if not (np.isfinite(d) and 0. < d < 1.):
+        raise ValueError(f'draw_zoom: zoom_out must be finite and in (0, 1), got {zoom_out!r}')
+    H, W = int(canvas[0]), int(canvas[1])
+    out = np.array(windows, dtype=np.int32).reshape(-1, 4)
+    for i in range(out.shape[0]):
+        z = rng.uniform(1. - d, 1.)
+        h1 = max(1, int(np.floor(np.float64(out[i, 2]) * z + 0.5)))
+        w1 = max(1, int(np.floor(np.float64(out[i, 3]) * z + 0.5)))
+        if h1 > H or w1 > W:
+            raise ValueError(f'draw_zoom: window {out[i].tolist()} is larger than the canvas {(H, W)}')
+        out[i] = (rng.randint(0, H - h1 + 1), rng.randint(0, W - w1 + 1), h1, w1)
+    return out
+
+
+def check_window(window, B, canvas):
+    """``window`` as int32 [B, 4] = (top, left, h1, w1); every window must lie inside ``canvas``."""
+    w = np.ascontiguousarray(np.asarray(window, np.int32)).reshape(-1)
+    H, W = int(canvas[0]), int(canvas[1])
+    if w.size != 4 * B:
+        raise ValueError(f'letterbox windows must be {B} (top, left, h1, w1) rows')
+    w = w.reshape(B, 4)
+    if np.any(w[:, 2] < 1) or np.any(w[:, 3] < 1) or np.any(w[:, :2] < 0) or np.any(w[:, 0] + w[:, 2] > H) or np.any(w[:, 1] + w[:, 3] > W):
+        raise ValueError(f'letterbox windows must lie inside the canvas {(H, W)}')
+    return w
+
+
 def check_color(color, B):
     """``color`` as float32 [B, 3]; the factors must be finite and >= 0."""
     color = np.ascontiguousarray(np.asarray(color, np.float32)).reshape(-1)
@@ -90,10 +127,13 @@ def _pad_crop(size, target):
     return 0, 0, 0, 0
 
 
-def transform_boxes(boxes, orig_size, aug, input_size, forbid_resize=False):
+def transform_boxes(boxes, orig_size, aug, input_size, forbid_resize=False, letterbox=False, window=None):
     """The box half of the train-phase ``preprocess`` for one image, in float32 and in the reference's order: clip to the original
     image, subtract the drift, flip with the drifted width, then scale by ``scales`` (or shift by padding / crops).
-    Returns (boxes float32 [n, 4], meta dict of that image: drifts, drifted_size, flipped, scales or padding / crops)."""
+    ``letterbox``: scale by the window's ``scales`` = (h1 / Hd, w1 / Wd) and move to the window, ``x <- x * sx + left``, ``y <- y * sy + top``;
+    ``window`` = (top, left, h1, w1), default the centred ``letterbox_window`` of the drifted size.
+    Returns (boxes float32 [n, 4], meta dict of that image: drifts, drifted_size, flipped, scales or padding / crops; letterbox:
+    ``letterbox_meta``'s scales, padding, letterbox)."""
     orig = np.asarray(orig_size, dtype=np.int32)
     H0, W0 = int(orig[0]), int(orig[1])
     dy, dx, flipped = int(aug[0]), int(aug[1]), bool(aug[2])
@@ -107,6 +147,16 @@ def transform_boxes(boxes, orig_size, aug, input_size, forbid_resize=False):
         b[:, 2] = b[:, 0] + widths
     meta = {'drifts': np.array([dy, dx], np.int32), 'drifted_size': np.array([Hd, Wd, 3], np.int32), 'flipped': flipped}
     H, W = int(input_size[0]), int(input_size[1])
+    if letterbox:
+        if forbid_resize:
+            raise ValueError('transform_boxes: letterbox and forbid_resize are two different input geometries')
+        win = letterbox_window((Hd, Wd), (H, W)) if window is None else tuple(int(v) for v in window)
+        meta.update(letterbox_meta((Hd, Wd), win, (H, W)))
+        b[:, [0, 2]] *= meta['scales'][1]
+        b[:, [1, 3]] *= meta['scales'][0]
+        b[:, [0, 2]] += np.float32(win[1])
+        b[:, [1, 3]] += np.float32(win[0])
+        return b, meta
     if not forbid_resize:
         scales = np.array([H / Hd, W / Wd], dtype=np.float32)
         b[:, [0, 2]] *= scales[1]
@@ -136,7 +186,7 @@ def batch_meta(metas, sizes, rgb_mean, rgb_std):
            'rgb_mean': np.tile(np.asarray(rgb_mean, np.float32).reshape(1, 1, 1, 3), (B, 1, 1, 1)),
            'rgb_std': np.tile(np.asarray(rgb_std, np.float32).reshape(1, 1, 1, 3), (B, 1, 1, 1)),
            'flipped': [m['flipped'] for m in metas]}
-    for k in ('drifts', 'drifted_size', 'scales', 'padding', 'crops'):
+    for k in ('drifts', 'drifted_size', 'scales', 'padding', 'crops', 'letterbox'):
         if k in metas[0]:
             out[k] = np.stack([m[k] for m in metas])
     return out
@@ -155,11 +205,17 @@ def as_u8_image(im, what):
     return u8
 
 
-def pack_layout(sizes, color=False):
-    """Byte layout of one upload: int64 offsets [B], int32 sizes [B, 2], int32 aug [B, 3], (``color``: float32 color [B, 3],) then
-    (at HDR_ALIGN) the pixels.  Returns (header bytes, pixel offsets int64 [B] relative to the pixel base, total bytes)."""
+def window_offset(B, color=False):
+    """Byte offset of the int32 [B, 4] window block in a ``pack_layout(sizes, color, window=True)`` header."""
+    return 28 * B + (12 * B if color else 0)
+
+
+def pack_layout(sizes, color=False, window=False):
+    """Byte layout of one upload: int64 offsets [B], int32 sizes [B, 2], int32 aug [B, 3], (``color``: float32 color [B, 3],)
+    (``window``: int32 letterbox windows [B, 4],) then (at HDR_ALIGN) the pixels.  Returns (header bytes, pixel offsets int64 [B]
+    relative to the pixel base, total bytes)."""
     B = len(sizes)
-    hdr = -(-(8 * B + 20 * B + (12 * B if color else 0)) // HDR_ALIGN) * HDR_ALIGN
+    hdr = -(-(8 * B + 20 * B + (12 * B if color else 0) + (16 * B if window else 0)) // HDR_ALIGN) * HDR_ALIGN
     offsets = np.zeros(B, np.int64)
     total = 0
     for i, (h, w) in enumerate(sizes):
@@ -168,20 +224,26 @@ def pack_layout(sizes, color=False):
     return hdr, offsets, hdr + total
 
 
-def write_header(buf_np, offsets, sizes, aug, color=None):
+def write_header(buf_np, offsets, sizes, aug, color=None, window=None):
     """Fill the header of a packed upload (``buf_np``: the uint8 numpy view of the whole pinned buffer).  ``color``: float32 [B, 3]
-    factors for a ``pack_layout(sizes, color=True)`` layout."""
+    factors for a ``pack_layout(sizes, color=True)`` layout; ``window``: int32 [B, 4] letterbox windows for a ``window=True`` layout."""
     B = len(offsets)
     buf_np[:8 * B].view(np.int64)[:] = offsets
     buf_np[8 * B:16 * B].view(np.int32)[:] = np.asarray(sizes, np.int32).reshape(-1)
     buf_np[16 * B:28 * B].view(np.int32)[:] = np.asarray(aug, np.int32).reshape(-1)
     if color is not None:
         buf_np[28 * B:40 * B].view(np.float32)[:] = check_color(color, B).reshape(-1)
+    if window is not None:
+        off = window_offset(B, color is not None)
+        buf_np[off:off + 16 * B].view(np.int32)[:] = np.asarray(window, np.int32).reshape(-1)
 
 
-def launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std, color=False, sums=None):
+def launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std, color=False, sums=None, letterbox=False, window=False):
     """One augmented preprocessing launch on the device copy ``dev_buf`` of a packed upload.  Returns the device tensor the kernel
-    writes next to ``out``: scales fp32 [B, 2], or (forbid_resize) padcrop int32 [B, 8].
+    writes next to ``out``: scales fp32 [B, 2], or (forbid_resize) padcrop int32 [B, 8], or (letterbox) fp32 [2, B, 2] = (scales, shifts).
+
+    ``letterbox``: the letterbox entry points; ``window``: true when the upload carries the window block (``pack_layout(...,
+    window=True)``, written by ``write_header``), false for the kernel's own centred window.
 
     ``color``: true when the upload has the colour header (``pack_layout(sizes, color=True)``, factors written by ``write_header``).
     The per-image channel sums the contrast pivot needs are then taken on the device first (``sqd_image_stats_u8`` into ``sums``,
@@ -193,9 +255,27 @@ def launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std, c
     mean = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_mean).reshape(-1)])
     std = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_std).reshape(-1)])
     stream = nat.stream_handle(dev_buf.device)
+    if letterbox and forbid_resize:
+        raise ValueError('launch: letterbox and forbid_resize are two different input geometries')
+    if color and hdr < 40 * B:
+        raise ValueError(f'launch: a header of {hdr} bytes has no room for the colour factors of {B} images')
+    if window and (not letterbox or hdr < window_offset(B, color) + 16 * B):
+        raise ValueError(f'launch: a header of {hdr} bytes has no room for the letterbox windows of {B} images (or letterbox is off)')
+    if letterbox:
+        side = torch.empty(2, B, 2, device=dev_buf.device, dtype=torch.float32)
+        win = p(window_offset(B, color)) if window else None
+        if color:
+            from .ops import image_stats_u8
+            sums = image_stats_u8(dev_buf, B, hdr, out=sums)
+            rc = nat.lib().sqd_preprocess_u8_letterbox_aug_color_fwd(p(hdr), p(0), p(8 * B), p(16 * B), win, p(28 * B), nat.ptr(sums), nat.ptr(out),
+                                                                     nat.ptr(side[0]), nat.ptr(side[1]), mean, std, B, H, W, stream)
+            nat.check(rc, 'sqd_preprocess_u8_letterbox_aug_color_fwd')
+        else:
+            rc = nat.lib().sqd_preprocess_u8_letterbox_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), win, nat.ptr(out), nat.ptr(side[0]),
+                                                               nat.ptr(side[1]), mean, std, B, H, W, stream)
+            nat.check(rc, 'sqd_preprocess_u8_letterbox_aug_fwd')
+        return side
     if color:
-        if hdr < 40 * B:
-            raise ValueError(f'launch: a header of {hdr} bytes has no room for the colour factors of {B} images')
         from .ops import image_stats_u8
         sums = image_stats_u8(dev_buf, B, hdr, out=sums)
         if forbid_resize:
@@ -236,14 +316,15 @@ def _default_anchors(input_size):
 
 def preprocess_train_batch(images, class_ids_list, boxes_list, input_size, rng, drift_prob=1.0, flip_prob=0.5,
                            rgb_mean=KITTI_RGB_MEAN, rgb_std=KITTI_RGB_STD, forbid_resize=False, device='cuda', out=None,
-                           anchors=None, num_classes=3, aug=None, color_jitter=(0., 0., 0.), color=None):
+                           anchors=None, num_classes=3, aug=None, color_jitter=(0., 0., 0.), color=None, letterbox=False, window=None):
     """A training batch the reference's way (``BaseDataset.__getitem__`` in the train phase + default collate), built on the GPU.
 
     images: list of uint8 (or uint8-representable float) [H0, W0, 3] RGB arrays; class_ids_list / boxes_list: per image [n] and
     xyxy [n, 4] in original-image coordinates; rng: ``np.random.RandomState`` the draws come from (``aug``: int32 [B, 3] to use
     instead of drawing); color_jitter: (brightness, contrast, saturation) amounts, any > 0 draws the colour factors from ``rng`` after
     the geometric draws of the whole batch (``draw_color``); color: float32 [B, 3] factors to use instead of drawing (``image_meta``
-    then carries them as ``'color'``); anchors: ``cfg.anchors`` (default: the KITTI anchors of ``input_size``).  Returns (image fp32 NCHW on
+    then carries them as ``'color'``); letterbox: the letterbox geometry (``image_meta`` then carries ``letterbox_meta``'s keys), with
+    ``window``: int32 [B, 4] windows to use (default: the centred ones; ``draw_zoom`` makes zoomed-out ones); anchors: ``cfg.anchors`` (default: the KITTI anchors of ``input_size``).  Returns (image fp32 NCHW on
     ``device`` -- ``out`` when given --, image_meta with the reference's keys, dense gt [B, A, num_classes + 9] on ``device``).
     Uploads: one packed uint8 buffer (int header included) and the boxes of ``encode_annotations``; nothing waits on the device."""
     B = len(images)
@@ -259,11 +340,20 @@ def preprocess_train_batch(images, class_ids_list, boxes_list, input_size, rng, 
         color = check_color(color, B)
     elif any(float(d) > 0 for d in color_jitter):
         color = draw_color(rng, B, *color_jitter)
-    tb, metas = zip(*[transform_boxes(bx, (h, w), a, input_size, forbid_resize) for bx, (h, w), a in zip(boxes_list, sizes, aug)])
-    hdr, offsets, total = pack_layout(sizes, color is not None)
+    if letterbox:
+        if window is not None:
+            window = check_window(window, B, (H, W))
+        else:
+            window = np.array([letterbox_window((h - int(a[0]), w - int(a[1])), (H, W)) for (h, w), a in zip(sizes, aug)], np.int32)
+    elif window is not None:
+        raise ValueError('preprocess_train_batch: window needs letterbox=True')
+    wins = window if letterbox else [None] * B
+    tb, metas = zip(*[transform_boxes(bx, (h, w), a, input_size, forbid_resize, letterbox, wn)
+                      for bx, (h, w), a, wn in zip(boxes_list, sizes, aug, wins)])
+    hdr, offsets, total = pack_layout(sizes, color is not None, letterbox)
     packed = _staging(total)
     pk = packed.numpy()
-    write_header(pk, offsets, sizes, aug, color)
+    write_header(pk, offsets, sizes, aug, color, window)
     for im, off in zip(ims, offsets):
         pk[hdr + off:hdr + off + im.size] = np.ascontiguousarray(im).reshape(-1)
     dev = torch.device(device)
@@ -271,7 +361,7 @@ def preprocess_train_batch(images, class_ids_list, boxes_list, input_size, rng, 
         dev = torch.device('cuda', torch.cuda.current_device())
     dev_buf = packed.to(dev, non_blocking=True)
     out = check_out(out, B, H, W, dev)
-    launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std, color=color is not None)
+    launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std, color=color is not None, letterbox=letterbox, window=letterbox)
     from .annotations import encode_annotations
     gt = encode_annotations(class_ids_list, list(tb), _default_anchors(input_size) if anchors is None else anchors, num_classes, device=dev)
     meta = batch_meta(metas, sizes, rgb_mean, rgb_std)

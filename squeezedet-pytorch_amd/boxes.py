@@ -138,6 +138,36 @@ def boxes_postprocess(boxes, image_meta):
     return boxes
 
 
+def letterbox_window(size, canvas):
+    """The centred letterbox window of an image of ``size`` = (Hd, Wd) on a ``canvas`` = (H, W): (top, left, h1, w1), the image
+    scaled with its aspect ratio kept so that it just fits.  Integers only, the expressions ``preprocess_letterbox_body``
+    (csrc/preproc.hip) evaluates in 64 bits: height-limited (``H * Wd <= W * Hd``) ``h1 = H, w1 = max(1, (Wd * H + Hd // 2) // Hd)``,
+    else ``w1 = W, h1 = max(1, (Hd * W + Wd // 2) // Wd)``; ``top = (H - h1) // 2``, ``left = (W - w1) // 2``."""
+    Hd, Wd = int(size[0]), int(size[1])
+    H, W = int(canvas[0]), int(canvas[1])
+    if Hd < 1 or Wd < 1 or H < 1 or W < 1:
+        raise ValueError(f'letterbox_window: empty image {size} or canvas {canvas}')
+    if H * Wd <= W * Hd:
+        h1, w1 = H, max(1, (Wd * H + Hd // 2) // Hd)
+    else:
+        h1, w1 = max(1, (Hd * W + Wd // 2) // Wd), W
+    return (H - h1) // 2, (W - w1) // 2, h1, w1
+
+
+def letterbox_meta(size, window, canvas):
+    """The ``image_meta`` entries of an image of ``size`` = (Hd, Wd) letterboxed into ``window`` = (top, left, h1, w1) of ``canvas``:
+    ``scales`` float32 [2] = (h1 / Hd, w1 / Wd) (float64 division, then cast), ``padding`` float32 [4] = (top / sy, bottom / sy, left / sx,
+    right / sx) -- the padding in original-image pixels, float32 divisions --, ``letterbox`` int32 [4] = the window.  With them
+    ``boxes_postprocess`` (divide by ``scales``, then subtract ``padding``) undoes the transform unchanged."""
+    top, left, h1, w1 = (int(v) for v in window)
+    H, W = int(canvas[0]), int(canvas[1])
+    if not (1 <= h1 <= H and 1 <= w1 <= W and 0 <= top <= H - h1 and 0 <= left <= W - w1):
+        raise ValueError(f'letterbox_meta: window {(top, left, h1, w1)} outside the canvas {(H, W)}')
+    scales = np.array([h1 / int(size[0]), w1 / int(size[1])], dtype=np.float32)
+    pads = np.array([top, H - h1 - top, left, W - w1 - left], dtype=np.float32)
+    return {'scales': scales, 'padding': pads / scales[[0, 0, 1, 1]], 'letterbox': np.array([top, left, h1, w1], np.int32)}
+
+
 def anchor_ignore_mask(anchors, ign_boxes, overlap):
     """Which anchors of one image lie on an ignore region (KITTI ``DontCare``, VOC ``difficult``, COCO ``crowd``): anchors [A,4]
     (cx,cy,w,h), ign_boxes [n,4] xyxy float32 in network-input coordinates, overlap in (0, 1] -> bool [A].

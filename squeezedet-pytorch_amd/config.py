@@ -14,6 +14,23 @@ import numpy as np
 from .boxes import KITTI_ANCHORS_SEED, KITTI_INPUT_SIZE, generate_anchors
 
 MAX_CLASSES = 256                # ops.HEAD_MANY_MAX_CLASSES (this module imports no kernels)
+
+
+def check_geometry(cfg, who):
+    """The input geometry of ``cfg``: (letterbox, zoom_out).  ``letterbox`` excludes ``forbid_resize``; ``zoom_out`` is a finite
+    amount in [0, 1) and needs ``letterbox``."""
+    letterbox = bool(getattr(cfg, 'letterbox', False))
+    if letterbox and bool(getattr(cfg, 'forbid_resize', False)):
+        raise ValueError(f'{who}: letterbox and forbid_resize are two different input geometries, set one')
+    try:
+        zoom = float(getattr(cfg, 'zoom_out', 0.))
+    except (TypeError, ValueError):
+        raise ValueError(f'{who}: zoom_out must be a number in [0, 1), got {getattr(cfg, "zoom_out")!r}') from None
+    if not (np.isfinite(zoom) and 0. <= zoom < 1.):
+        raise ValueError(f'{who}: zoom_out must be finite and in [0, 1), got {zoom!r}')
+    if zoom > 0 and not letterbox:
+        raise ValueError(f'{who}: zoom_out shrinks the letterbox window, it needs letterbox=True')
+    return letterbox, zoom
 KITTI_CLASS_NAMES = ('Car', 'Pedestrian', 'Cyclist')
 
 
@@ -40,6 +57,8 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         gpus=[0], chunk_sizes=[20], num_iters=-1, print_interval=10, debug=0, num_workers=4, forbid_resize=False,
         flip_prob=0.5, drift_prob=1., seed=42,      # training augmentation (train_data.TrainLoader), src/utils/config.py:53-56
         brightness_jitter=0., contrast_jitter=0., saturation_jitter=0.,      # colour jitter amounts (augment.draw_color); 0 = off
+        letterbox=False,             # input geometry: resize with the aspect ratio kept, pad the rest with the whitened mean (excludes forbid_resize)
+        zoom_out=0.,                 # training, with letterbox: shrink the window by uniform(1 - zoom_out, 1) and place it at random; 0 = off
         sparse_gt=False,             # training ground truth as the list of positives (ops.SparseGT in batch['gt_sparse']) instead of dense
         ignore_overlap=None,         # None: off.  A float in (0, 1] (0.5 is the documented value; needs sparse_gt): anchors covered to that share
                                      # by a flagged box (DontCare / difficult / crowd) leave the loss (batch['gt_ignore'], ops.loss_masked_*)
@@ -50,4 +69,5 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
     )
     for k, v in overrides.items():
         setattr(cfg, k, v)
+    check_geometry(cfg, 'make_cfg')
     return cfg

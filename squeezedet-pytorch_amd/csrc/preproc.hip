@@ -411,3 +411,220 @@ extern "C" int sqd_preprocess_u8_padcrop_aug_color_fwd(const unsigned char* src,
   hipLaunchKernelGGL(preprocess_padcrop_aug_color_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug, color, sums);
   return sqd_launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The third geometry, cfg.letterbox (no reference counterpart; DESIGN.md 6b, "Letterbox and zoom-out"): the drifted, flipped image
+// V (Hd x Wd, see preprocess_body; eval: the image itself) is resized with its aspect ratio kept into a window (top, left, h1, w1)
+// of the H x W canvas, and everything outside the window is exactly +0.0f -- the whitened mean, as the reference's zero fill after
+// whitening.  Inside the window the value at (y, x) is preprocess_body's resize rule with destination size (h1, w1) evaluated at
+// (y - top, x - left): the same expressions, so a window that is the whole canvas gives preprocess_body's bits.
+// The window comes from win[B][4] int32 (zoom-out: the host shrinks and places it) or, win == null, from the integer rule
+//   H * Wd <= W * Hd (height-limited):  h1 = H, w1 = max(1, (Wd * H + Hd / 2) / Hd);  else  w1 = W, h1 = max(1, (Hd * W + Wd / 2) / Wd);
+//   top = (H - h1) / 2, left = (W - w1) / 2     (64-bit, integer divisions: augment.letterbox_window evaluates the same)
+// A given window is clamped into the canvas (h1 to 1..H, w1 to 1..W, then top to 0..H-h1, left to 0..W-w1), in the spirit of pre_drift: no
+// buffer content makes the kernel read or write out of range.  scales = (h1 / Hd, w1 / Wd) (float64 division, cast to float32) and
+// shifts = (-(float)top / sy, -(float)left / sx): box / scales + shifts in the detect kernels is boxes_postprocess with
+// padding = (top / sy, ., left / sx, .), i.e. the padding in original-image pixels.
+// Workgroup shape as above.  The staged segment is bounded by the workgroup's columns INSIDE the window; a workgroup with no column
+// or no row in the window stores zeros and returns before the table is built; one cut by a window edge takes both cases per thread
+// (the barriers run for every row, window or not).
+// ---------------------------------------------------------------------------------------------------------------------
+struct LetterboxArgs {
+  const unsigned char* src; const long long* offsets; const int* sizes;
+  const int* win;                // [B][4] = (top, left, h1, w1), or null: the centred window of the integer rule
+  float* out; float* scales; float* shifts;
+  float mean[3], stdv[3];
+  int B, H, W;
+};
+
+template <bool AUG, bool COLOR>
+__device__ __forceinline__ void preprocess_letterbox_body(const LetterboxArgs& a, const int* aug, const float* color, const unsigned long long* sums) {
+  __shared__ float lut[768];
+  __shared__ unsigned rows[2][PRE_ROWB / 4];
+  const int b = blockIdx.z;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int H0 = a.sizes[2 * b], W0 = a.sizes[2 * b + 1];
+  const int dy = pre_drift<AUG>(aug, 3 * b, H0), dx = pre_drift<AUG>(aug, 3 * b + 1, W0);
+  const bool flip = AUG && aug[3 * b + 2] != 0;
+  const int Hd = AUG ? H0 - dy : H0, Wd = AUG ? W0 - dx : W0;     // the (drifted) image the resize rule sees
+  int top, left, h1, w1;
+  if (a.win) {
+    const int* w = a.win + 4 * b;
+    h1 = max(min(w[2], a.H), 1); w1 = max(min(w[3], a.W), 1);
+    top = max(min(w[0], a.H - h1), 0); left = max(min(w[1], a.W - w1), 0);
+  } else {
+    const long long H = a.H, W = a.W, hd = Hd, wd = Wd;
+    if (H * wd <= W * hd) { h1 = a.H; w1 = (int)min(max((wd * H + hd / 2) / hd, 1ll), W); }
+    else { w1 = a.W; h1 = (int)min(max((hd * W + wd / 2) / wd, 1ll), H); }
+    top = (a.H - h1) / 2; left = (a.W - w1) / 2;
+  }
+  if (x == 0 && blockIdx.y == 0 && (a.scales || a.shifts)) {
+    const float sy = (float)((double)h1 / (double)Hd), sx = (float)((double)w1 / (double)Wd);
+    if (a.scales) { a.scales[2 * b] = sy; a.scales[2 * b + 1] = sx; }
+    if (a.shifts) { a.shifts[2 * b] = -(float)top / sy; a.shifts[2 * b + 1] = -(float)left / sx; }
+  }
+  const long long plane = (long long)a.H * a.W;
+  // the workgroup's columns and rows inside the window (all uniform)
+  const int xa = blockIdx.x * 256, xb = min(a.W, xa + 256) - 1;
+  const int ia = max(xa, left), ib = min(xb, left + w1 - 1);
+  const int ya = blockIdx.y * PRE_ROWS, yb = min(a.H, ya + PRE_ROWS) - 1;
+  if (ia > ib || yb < top || ya >= top + h1) {       // wholly in the fill region: zeros, nothing staged
+    if (x < a.W)
+      for (int y = ya; y <= yb; ++y) {
+        float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
+        o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
+      }
+    return;
+  }
+  const unsigned char* img = a.src + a.offsets[b];
+  const unsigned char* img_end = img + (long long)H0 * W0 * 3;
+  // source coordinates of a window pixel (double scale like OpenCV, then float weights): the resize rule with destination (h1, w1)
+  const double sclx = (double)Wd / (double)w1, scly = (double)Hd / (double)h1;
+  auto src_x = [&](int xx, float& f) {
+    f = (float)((xx + 0.5) * sclx - 0.5);
+    int sx = (int)floorf(f); f -= (float)sx;
+    if (sx < 0) { sx = 0; f = 0.f; }
+    if (sx >= Wd - 1) { sx = Wd - 1; f = 0.f; }
+    return sx;
+  };
+  auto col = [&](int v) { return AUG ? (flip ? Wd - 1 - v : v) + dx : v; };     // V column -> image column
+  // the source column range [lo, hi] of the workgroup's window columns (sx is monotone in x): one segment per source row
+  float fdummy;
+  int lo = src_x(ia - left, fdummy), hi = min(src_x(ib - left, fdummy) + 1, Wd - 1);
+  if (AUG) {
+    const int ca = col(lo), cb = col(hi);
+    lo = max(min(ca, cb), 0); hi = min(max(ca, cb), W0 - 1);
+  }
+  const bool seg = !AUG || hi >= lo;                 // (AUG) false: every window column of the workgroup lies in the drift fill
+  const int len = (hi - lo + 1) * 3;
+  const bool staged = len + 8 <= PRE_ROWB;
+  const int xc = min(x, a.W - 1);
+  const bool xin = xc >= left && xc < left + w1;
+  float fx;
+  const int sx = src_x(min(max(xc - left, 0), w1 - 1), fx);     // (a thread outside the window: the nearest window column, never read)
+  const int sx1 = min(sx + 1, Wd - 1);
+  const int cx0 = col(sx), cx1 = col(sx1);
+  const bool vx0 = !AUG || cx0 >= 0, vx1 = !AUG || cx1 >= 0;
+  const int ux0 = AUG ? max(cx0, 0) : cx0, ux1 = AUG ? max(cx1, 0) : cx1;     // (a fill tap's address: any in-range one)
+  const float ax0 = 1.f - fx, ax1 = fx;
+  PreColor kc = {};
+  if (COLOR) {
+    kc = pre_color_of(color, sums, b, H0, W0);
+    pre_build_lut_color(lut, kc, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
+  } else {
+    pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
+  }
+  for (int r = 0; r < PRE_ROWS; ++r) {
+    const int y = ya + r;
+    if (y >= a.H) break;                             // (uniform)
+    const bool yin = y >= top && y < top + h1;       // (uniform)
+    float fy = (float)((min(max(y - top, 0), h1 - 1) + 0.5) * scly - 0.5);
+    int sy = (int)floorf(fy); fy -= (float)sy;
+    if (sy < 0) { sy = 0; fy = 0.f; }
+    if (sy >= Hd - 1) { sy = Hd - 1; fy = 0.f; }
+    const int sy1 = min(sy + 1, Hd - 1);
+    const int ry0 = sy + dy, ry1 = sy1 + dy;         // image rows (AUG: negative = fill)
+    const bool vy0 = !AUG || ry0 >= 0, vy1 = !AUG || ry1 >= 0;
+    const int uy0 = AUG ? max(ry0, 0) : ry0, uy1 = AUG ? max(ry1, 0) : ry1;
+    int sh0 = 0, sh1 = 0;
+    if (r) __syncthreads();                          // the previous row's readers are done with the segments
+    if (staged && seg && yin) {
+      if (vy0) sh0 = pre_stage(rows[0], img, img_end, ((long long)uy0 * W0 + lo) * 3, len);
+      if (vy1) sh1 = pre_stage(rows[1], img, img_end, ((long long)uy1 * W0 + lo) * 3, len);
+    }
+    __syncthreads();
+    if (x >= a.W) continue;
+    float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
+    if (!(yin && xin)) {                             // outside the window: the whitened mean
+      o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
+      continue;
+    }
+    const float ay0 = 1.f - fy, ay1 = fy;
+    const unsigned char *p00, *p01, *p10, *p11;
+    if (staged) {
+      const unsigned char* r0 = (const unsigned char*)rows[0] + sh0;
+      const unsigned char* r1 = (const unsigned char*)rows[1] + sh1;
+      const int ox0 = AUG ? (vx0 ? ux0 - lo : 0) : sx - lo, ox1 = AUG ? (vx1 ? ux1 - lo : 0) : sx1 - lo;
+      p00 = r0 + ox0 * 3; p01 = r0 + ox1 * 3; p10 = r1 + ox0 * 3; p11 = r1 + ox1 * 3;
+    } else {
+      p00 = img + ((long long)uy0 * W0 + ux0) * 3; p01 = img + ((long long)uy0 * W0 + ux1) * 3;
+      p10 = img + ((long long)uy1 * W0 + ux0) * 3; p11 = img + ((long long)uy1 * W0 + ux1) * 3;
+    }
+    const bool t00 = vy0 && vx0, t01 = vy0 && vx1, t10 = vy1 && vx0, t11 = vy1 && vx1;
+    if (COLOR && kc.per_tap) {                       // (uniform) saturation mixes the channels of a tap: blend and whiten per tap
+      float v00[3] = {0.f, 0.f, 0.f}, v01[3] = {0.f, 0.f, 0.f}, v10[3] = {0.f, 0.f, 0.f}, v11[3] = {0.f, 0.f, 0.f};     // (fill: 0)
+      if (t00) pre_color_tap(lut, kc, p00, a.mean, a.stdv, v00);
+      if (t01) pre_color_tap(lut, kc, p01, a.mean, a.stdv, v01);
+      if (t10) pre_color_tap(lut, kc, p10, a.mean, a.stdv, v10);
+      if (t11) pre_color_tap(lut, kc, p11, a.mean, a.stdv, v11);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float r0 = v00[c] * ax0 + v01[c] * ax1;
+        const float r1 = v10[c] * ax0 + v11[c] * ax1;
+        o[c * plane] = r0 * ay0 + r1 * ay1;
+      }
+      continue;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float* l = lut + 256 * c;
+      const float v00 = t00 ? l[p00[c]] : 0.f, v01 = t01 ? l[p01[c]] : 0.f;
+      const float v10 = t10 ? l[p10[c]] : 0.f, v11 = t11 ? l[p11[c]] : 0.f;
+      const float r0 = v00 * ax0 + v01 * ax1;
+      const float r1 = v10 * ax0 + v11 * ax1;
+      o[c * plane] = r0 * ay0 + r1 * ay1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void preprocess_letterbox_kernel(LetterboxArgs a) { preprocess_letterbox_body<false, false>(a, nullptr, nullptr, nullptr); }
+
+__global__ __launch_bounds__(256) void preprocess_letterbox_aug_kernel(LetterboxArgs a, const int* aug) {
+  preprocess_letterbox_body<true, false>(a, aug, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void preprocess_letterbox_aug_color_kernel(LetterboxArgs a, const int* aug, const float* color,
+                                                                             const unsigned long long* sums) {
+  preprocess_letterbox_body<true, true>(a, aug, color, sums);
+}
+
+static inline bool letterbox_args(LetterboxArgs& a, const unsigned char* src, const long long* offsets, const int* sizes, const int* win, float* out,
+                                  float* scales, float* shifts, const float* mean3, const float* std3, int B, int H, int W) {
+  if (!(src && offsets && sizes && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535)) return false;
+  if (((uintptr_t)win & 3) != 0) return false;
+  a.src = src; a.offsets = offsets; a.sizes = sizes; a.win = win; a.out = out; a.scales = scales; a.shifts = shifts; a.B = B; a.H = H; a.W = W;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; if (std3[c] == 0.f) return false; }
+  return true;
+}
+
+// Arguments as sqd_preprocess_u8_fwd / _aug_fwd / _aug_color_fwd; win: device int32 [B][4] = (top, left, h1, w1) per image or NULL
+// (the centred window of the integer rule above); scales [B][2] = (h1 / Hd, w1 / Wd) and shifts [B][2] = (-top / sy, -left / sx), either
+// may be NULL.
+extern "C" int sqd_preprocess_u8_letterbox_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* win, float* out,
+                                               float* scales, float* shifts, const float* mean3, const float* std3, int B, int H, int W,
+                                               void* stream) {
+  LetterboxArgs a;
+  SQD_CHECK_ARG(letterbox_args(a, src, offsets, sizes, win, out, scales, shifts, mean3, std3, B, H, W));
+  hipLaunchKernelGGL(preprocess_letterbox_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_preprocess_u8_letterbox_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                                   const int* win, float* out, float* scales, float* shifts, const float* mean3,
+                                                   const float* std3, int B, int H, int W, void* stream) {
+  LetterboxArgs a;
+  SQD_CHECK_ARG(aug && letterbox_args(a, src, offsets, sizes, win, out, scales, shifts, mean3, std3, B, H, W));
+  hipLaunchKernelGGL(preprocess_letterbox_aug_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug);
+  return sqd_launch_status();
+}
+
+extern "C" int sqd_preprocess_u8_letterbox_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                                         const int* win, const float* color, const unsigned long long* sums, float* out,
+                                                         float* scales, float* shifts, const float* mean3, const float* std3, int B, int H,
+                                                         int W, void* stream) {
+  LetterboxArgs a;
+  SQD_CHECK_ARG(aug && color && sums && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)color & 3) == 0);
+  SQD_CHECK_ARG(letterbox_args(a, src, offsets, sizes, win, out, scales, shifts, mean3, std3, B, H, W));
+  hipLaunchKernelGGL(preprocess_letterbox_aug_color_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug, color, sums);
+  return sqd_launch_status();
+}

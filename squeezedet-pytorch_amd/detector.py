@@ -82,8 +82,9 @@ class Detector(object):
     @torch.no_grad()
     def detect_images(self, images, image_ids=None, rgb_mean=None, rgb_std=None):
         """Raw path: list of uint8 HWC RGB images (any sizes) -> detections in original-image coordinates.
-        Upload of the uint8 pixels, GPU pre-processing (whiten + resize -- or, with ``cfg.forbid_resize``, whiten + crop_or_pad --
-        + CHW), backbone, fused detection with the per-image scale division (or un-pad / un-crop shift), one compact D2H copy.
+        Upload of the uint8 pixels, GPU pre-processing (whiten + resize -- or, with ``cfg.forbid_resize``, whiten + crop_or_pad; with
+        ``cfg.letterbox``, whiten + aspect-preserving resize into a zero canvas -- + CHW), backbone, fused detection with the per-image
+        scale division (or un-pad / un-crop shift; letterbox: both), one compact D2H copy.  Boxes are not clamped to the original image.
         ``rgb_mean`` / ``rgb_std``: the dataset's whitening statistics (default: ``cfg.rgb_mean`` / ``cfg.rgb_std``, else KITTI's)."""
         from .preprocess import preprocess_batch
         cfg = self.cfg
@@ -91,14 +92,21 @@ class Detector(object):
         std = rgb_std if rgb_std is not None else getattr(cfg, 'rgb_std', None)
         kw = {} if mean is None or std is None else {'rgb_mean': np.asarray(mean).reshape(-1), 'rgb_std': np.asarray(std).reshape(-1)}
         forbid = bool(getattr(cfg, 'forbid_resize', False))
-        image, aux, meta = preprocess_batch(images, cfg.input_size, device=cfg.device, forbid_resize=forbid, **kw)
-        dets = self.detect_device(image, shifts=aux) if forbid else self.detect_device(image, scales=aux)
+        letterbox = bool(getattr(cfg, 'letterbox', False))
+        image, aux, meta = preprocess_batch(images, cfg.input_size, device=cfg.device, forbid_resize=forbid, letterbox=letterbox, **kw)
+        if letterbox:
+            dets = self.detect_device(image, scales=aux[0], shifts=aux[1])
+        else:
+            dets = self.detect_device(image, shifts=aux) if forbid else self.detect_device(image, scales=aux)
         cnt, cls, sc, bx, idx = (t.cpu().numpy() for t in dets)
         results = []
         for b in range(len(images)):
             n = int(cnt[b])
             m = {'orig_size': meta['orig_size'][b], 'index': b, 'image_id': image_ids[b] if image_ids is not None else str(b)}
-            m.update({'padding': meta['padding'][b], 'crops': meta['crops'][b]} if forbid else {'scales': meta['scales'][b]})
+            if letterbox:
+                m.update({k: meta[k][b] for k in ('scales', 'padding', 'letterbox')})
+            else:
+                m.update({'padding': meta['padding'][b], 'crops': meta['crops'][b]} if forbid else {'scales': meta['scales'][b]})
             if n == 0:
                 results.append({'image_meta': m})
                 continue
@@ -115,7 +123,8 @@ class Detector(object):
         lanes = int(lanes if lanes is not None else getattr(self.cfg, 'inflight', 2))
         key = (lanes, bool(graph), None if rgb_mean is None else tuple(np.asarray(rgb_mean, np.float32).reshape(-1).tolist()),
                None if rgb_std is None else tuple(np.asarray(rgb_std, np.float32).reshape(-1).tolist()),
-               bool(getattr(self.cfg, 'forbid_resize', False)), int(getattr(self.cfg, 'batch_size', 20)))
+               bool(getattr(self.cfg, 'forbid_resize', False)), int(getattr(self.cfg, 'batch_size', 20)),
+               bool(getattr(self.cfg, 'letterbox', False)))
         cache = self.__dict__.setdefault('_streams', {})
         ex = cache.get(key)
         if ex is None:

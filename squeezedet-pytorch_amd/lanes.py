@@ -33,6 +33,7 @@ import torch
 
 from . import _native as nat
 from . import ops
+from .boxes import letterbox_meta, letterbox_window
 from .preprocess import KITTI_RGB_MEAN, KITTI_RGB_STD
 
 _HDR_ALIGN = 256
@@ -193,6 +194,9 @@ class DetectStream:
         self.eager_batches = 0
         self.replayed_batches = 0
         self.forbid = bool(getattr(cfg, 'forbid_resize', False))
+        self.letterbox = bool(getattr(cfg, 'letterbox', False))          # the third geometry (preprocess.preprocess_batch)
+        if self.forbid and self.letterbox:
+            raise ValueError('DetectStream: letterbox and forbid_resize are two different input geometries')
         mean = rgb_mean if rgb_mean is not None else getattr(cfg, 'rgb_mean', None)
         std = rgb_std if rgb_std is not None else getattr(cfg, 'rgb_std', None)
         mean = KITTI_RGB_MEAN if mean is None else np.asarray(mean, np.float32).reshape(-1)
@@ -294,7 +298,7 @@ class DetectStream:
             uploaded = hb['uploaded']
         self._open.discard(st.index)
         nb = self._bufs(lane, n)
-        key = ('u8', n, self.forbid)
+        key = ('u8', n, self.forbid, self.letterbox)
         lane.comp.wait_event(uploaded)
         # the pre-processing kernel is launched eagerly in front of the captured step: the lane's raw-pixel buffer is free again as
         # soon as THAT kernel is through (``lane.consumed``), so the next upload into it overlaps the whole network
@@ -303,7 +307,12 @@ class DetectStream:
             d_off = nat.c_p(src.data_ptr())
             d_sizes = nat.c_p(src.data_ptr() + 8 * cap)
             H, W = int(self.cfg.input_size[0]), int(self.cfg.input_size[1])
-            if self.forbid:
+            if self.letterbox:
+                rc = nat.lib().sqd_preprocess_u8_letterbox_fwd(nat.ptr(src), d_off, d_sizes, None, nat.ptr(nb['img']), nat.ptr(nb['aux']),
+                                                               nat.ptr(nb['aux2']), self._mean_c, self._std_c, n, H, W,
+                                                               nat.stream_handle(self.device))
+                nat.check(rc, 'sqd_preprocess_u8_letterbox_fwd')
+            elif self.forbid:
                 rc = nat.lib().sqd_preprocess_u8_padcrop_fwd(nat.ptr(src), d_off, d_sizes, nat.ptr(nb['img']), nat.ptr(nb['aux']), None,
                                                              self._mean_c, self._std_c, n, H, W, nat.stream_handle(self.device))
                 nat.check(rc, 'sqd_preprocess_u8_padcrop_fwd')
@@ -314,7 +323,9 @@ class DetectStream:
             lane.consumed.record(lane.comp)
 
         def compute():
-            if self.forbid:
+            if self.letterbox:
+                self.det.detect_device(nb['img'], scales=nb['aux'], shifts=nb['aux2'], out=nb['out'])
+            elif self.forbid:
                 self.det.detect_device(nb['img'], shifts=nb['aux'], out=nb['out'])
             else:
                 self.det.detect_device(nb['img'], scales=nb['aux'], out=nb['out'])
@@ -339,7 +350,9 @@ class DetectStream:
         for b, (h0, w0) in enumerate(sizes):
             m = {'orig_size': np.array([int(h0), int(w0), 3], dtype=np.int32), 'index': b,
                  'image_id': image_ids[b] if image_ids is not None else str(b)}
-            if self.forbid:
+            if getattr(self, 'letterbox', False):
+                m.update(letterbox_meta((h0, w0), letterbox_window((h0, w0), (H, W)), (H, W)))      # the same integers as the kernel
+            elif self.forbid:
                 pad, crop = np.zeros(4, np.int16), np.zeros(4, np.int16)       # the same integers as the kernel (image.py:99-115)
                 for size, target, k in ((int(h0), H, 0), (int(w0), W, 2)):
                     if size < target:
@@ -403,7 +416,7 @@ class DetectStream:
             with torch.cuda.stream(lane.comp):
                 out, flat = ops.det_buffers_packed(n, K, self.device, int(self.cfg.num_anchors), int(self.cfg.num_classes))
             secs, total = ops.det_packed_layout(n, K)
-            nb = {'out': out, 'flat': flat, 'secs': secs, 'img': None, 'aux': None,
+            nb = {'out': out, 'flat': flat, 'secs': secs, 'img': None, 'aux': None, 'aux2': None,
                   'res': [torch.empty(total, dtype=torch.uint8, pin_memory=True) for _ in range(2)],
                   'copied': [torch.cuda.Event(), torch.cuda.Event()], 'uses': 0}
             lane.bufs[n] = nb
@@ -412,6 +425,7 @@ class DetectStream:
             with torch.cuda.stream(lane.comp):
                 nb['img'] = torch.empty(n, 3, H, W, device=self.device, dtype=torch.float32)
                 nb['aux'] = torch.empty(n, 2, device=self.device, dtype=torch.float32)
+                nb['aux2'] = torch.empty(n, 2, device=self.device, dtype=torch.float32)       # (letterbox: scales in aux, shifts here)
         return nb
 
     def _launch(self, lane, nb, key, compute, meta, tag):

@@ -44,13 +44,20 @@ def _pack_pool():
     return _POOL
 
 
-def preprocess_batch(images, input_size, device='cuda', rgb_mean=KITTI_RGB_MEAN, rgb_std=KITTI_RGB_STD, out=None, forbid_resize=False):
+def preprocess_batch(images, input_size, device='cuda', rgb_mean=KITTI_RGB_MEAN, rgb_std=KITTI_RGB_STD, out=None, forbid_resize=False,
+                     letterbox=False):
     """images: list of uint8 numpy arrays [H0, W0, 3] (RGB, any sizes).  Returns (image fp32 NCHW [B,3,H,W] on
     ``device``, scales fp32 [B,2] = (H/H0, W/W0) on ``device``, image_meta dict of per-image lists/arrays).
     ``forbid_resize`` (``cfg.forbid_resize``, src/datasets/base.py:53-54): whiten + ``crop_or_pad`` instead of whiten + resize --
     the second return value is then the box shift fp32 [B,2] = (dy, dx) = (crops - padding)(top, left) that ``ops.detect(...,
     shifts=)`` adds (``boxes_postprocess``' padding / crops terms), and ``image_meta`` carries ``padding`` / ``crops`` (int16 [B,4],
-    (top, bottom, left, right)) instead of ``scales``.  Bit-exact against the reference (tests/golden/padcrop.npz)."""
+    (top, bottom, left, right)) instead of ``scales``.  Bit-exact against the reference (tests/golden/padcrop.npz).
+    ``letterbox`` (``cfg.letterbox``, DESIGN.md 6b "Letterbox and zoom-out"): whiten + resize with the aspect ratio kept into the centred
+    window of ``boxes.letterbox_window``, zeros around it -- the second return value is then the pair (scales, shifts), fp32 [B,2] each,
+    that ``ops.detect(..., scales=, shifts=)`` takes, and ``image_meta`` carries ``boxes.letterbox_meta``'s ``scales``, ``padding`` (float32,
+    in original-image pixels) and ``letterbox`` (the window)."""
+    if letterbox and forbid_resize:
+        raise ValueError('preprocess_batch: letterbox and forbid_resize are two different input geometries')
     if len(images) == 0:
         raise ValueError('preprocess_batch: empty batch')
     H, W = int(input_size[0]), int(input_size[1])
@@ -93,6 +100,15 @@ def preprocess_batch(images, input_size, device='cuda', rgb_mean=KITTI_RGB_MEAN,
                  'drifts': np.zeros((B, 2), np.int32), 'flipped': [False] * B,
                  'rgb_mean': np.tile(np.asarray(rgb_mean, np.float32).reshape(1, 1, 1, 3), (B, 1, 1, 1)),
                  'rgb_std': np.tile(np.asarray(rgb_std, np.float32).reshape(1, 1, 1, 3), (B, 1, 1, 1))}
+    if letterbox:
+        from .boxes import letterbox_meta, letterbox_window
+        shifts = torch.empty(B, 2, device=dev, dtype=torch.float32)
+        rc = nat.lib().sqd_preprocess_u8_letterbox_fwd(nat.ptr(src), nat.ptr(d_off), nat.ptr(d_sizes), None, nat.ptr(out), nat.ptr(scales),
+                                                       nat.ptr(shifts), mean, std, B, H, W, nat.stream_handle(dev))
+        nat.check(rc, 'sqd_preprocess_u8_letterbox_fwd')
+        metas = [letterbox_meta(s, letterbox_window(s, (H, W)), (H, W)) for s in sizes]      # the same integers on the host
+        base_meta.update({k: np.stack([m[k] for m in metas]) for k in ('scales', 'padding', 'letterbox')})
+        return out, (scales, shifts), base_meta
     if forbid_resize:
         rc = nat.lib().sqd_preprocess_u8_padcrop_fwd(nat.ptr(src), nat.ptr(d_off), nat.ptr(d_sizes), nat.ptr(out), nat.ptr(scales), None,
                                                      mean, std, B, H, W, nat.stream_handle(dev))

@@ -29,11 +29,13 @@ import numpy as np
 import torch
 
 from . import augment
+from .config import check_geometry
 from .annotations import clip_ignore_boxes, encode_annotations, ignore_overlap_of, split_flagged
 from .trainer import shard_sizes
 
 
 COLOR_STREAM = 0xC0105EED      # second word of the colour RandomState's seed key
+ZOOM_STREAM = 0x200D0075       # ... and of the zoom-out one
 
 
 class _Stage:
@@ -58,8 +60,12 @@ class TrainLoader:
     """Iterable of device-resident training batches over ``dataset`` (see the module docstring).
 
     cfg fields read: batch_size (global), input_size, num_workers, device, drift_prob, flip_prob, seed, forbid_resize, anchors,
-    num_classes, brightness_jitter, contrast_jitter, saturation_jitter, sparse_gt, ignore_overlap.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState
-    once (and, as ``[seed mod 2^32, COLOR_STREAM]``, the colour one); each epoch (``iter``) continues them."""
+    num_classes, brightness_jitter, contrast_jitter, saturation_jitter, sparse_gt, ignore_overlap, letterbox, zoom_out.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState
+    once (and, as ``[seed mod 2^32, COLOR_STREAM]``, the colour one; as ``[seed mod 2^32, ZOOM_STREAM]``, the zoom-out one); each epoch
+    (``iter``) continues them.  ``cfg.letterbox``: the letterbox geometry (DESIGN.md 6b "Letterbox and zoom-out"), the window of every
+    image in ``plan()``'s ``'window'`` and ``image_meta['letterbox']``; ``cfg.zoom_out`` = d in (0, 1) shrinks and places it
+    (``augment.draw_zoom``, three draws per image of the global batch from the zoom-out RandomState: the drift / flip / colour draws of a
+    dataset are the same with and without it)."""
 
     def __init__(self, dataset, cfg, seed=None, shuffle=True, drop_last=True, rank=0, world=1):
         self.dataset, self.cfg = dataset, cfg
@@ -76,6 +82,8 @@ class TrainLoader:
         if any(not np.isfinite(d) or d < 0 for d in self.color_jitter):
             raise ValueError(f'TrainLoader: colour jitter amounts must be finite and >= 0, got {self.color_jitter}')
         self.color_on = any(d > 0 for d in self.color_jitter)
+        self.letterbox, self.zoom_out = check_geometry(cfg, 'TrainLoader')
+        self.zoom_rng = np.random.RandomState(None if seed is None else np.append(np.asarray(seed, np.int64).reshape(-1) & 0xFFFFFFFF, ZOOM_STREAM))
         self.drift_prob = float(getattr(cfg, 'drift_prob', 1.0))
         self.flip_prob = float(getattr(cfg, 'flip_prob', 0.5))
         self.forbid_resize = bool(getattr(cfg, 'forbid_resize', False))
@@ -135,7 +143,7 @@ class TrainLoader:
 
         def pack(ims, parallel):
             sizes = [im.shape[:2] for im in ims]
-            hdr, offsets, total = augment.pack_layout(sizes, self.color_on)
+            hdr, offsets, total = augment.pack_layout(sizes, self.color_on, self.letterbox)
             pk = stage.acquire(total)
 
             def put(k):                               # (numpy releases the GIL while copying)
@@ -171,21 +179,32 @@ class TrainLoader:
         lo, hi = self._local(idxs)
         ann = [split_flagged(a) for a in ann]             # (class ids, boxes, flagged boxes): the draws see the unflagged boxes only
         box_all = [b for _, b, _ in ann]
-        aug = augment.draw_augmentation(self.rng, gsizes, box_all, self.drift_prob, self.flip_prob)[lo:hi]
-        tb, metas = zip(*[augment.transform_boxes(b, s, a, self.cfg.input_size, self.forbid_resize)
-                          for b, s, a in zip(box_all[lo:hi], gsizes[lo:hi], aug)])
+        aug_all = augment.draw_augmentation(self.rng, gsizes, box_all, self.drift_prob, self.flip_prob)
+        aug = aug_all[lo:hi]
+        wins = [None] * (hi - lo)
+        if self.letterbox:
+            # the windows of the whole global batch (the zoom draws depend on them), then this rank's slice
+            win_all = np.array([augment.letterbox_window((h - int(a[0]), w - int(a[1])), self.cfg.input_size)
+                                for (h, w), a in zip(gsizes, aug_all)], np.int32).reshape(-1, 4)
+            if self.zoom_out > 0:
+                win_all = augment.draw_zoom(self.zoom_rng, win_all, self.cfg.input_size, self.zoom_out)
+            wins = win_all[lo:hi]
+        geo = (self.cfg.input_size, self.forbid_resize, self.letterbox)
+        tb, metas = zip(*[augment.transform_boxes(b, s, a, *geo, w) for b, s, a, w in zip(box_all[lo:hi], gsizes[lo:hi], aug, wins)])
         p = {'index': np.asarray(idxs[lo:hi], np.int64), 'aug': aug, 'boxes': list(tb), 'metas': list(metas),
              'class_ids': [np.asarray(c) for c, _, _ in ann[lo:hi]]}
+        if self.letterbox:
+            p['window'] = wins
         if self.ignore_overlap is not None:
-            p['ignore_boxes'] = [clip_ignore_boxes(augment.transform_boxes(f, s, a, self.cfg.input_size, self.forbid_resize)[0], self.cfg.input_size)
-                                 for (_, _, f), s, a in zip(ann[lo:hi], gsizes[lo:hi], aug)]
+            p['ignore_boxes'] = [clip_ignore_boxes(augment.transform_boxes(f, s, a, *geo, w)[0], self.cfg.input_size)
+                                 for (_, _, f), s, a, w in zip(ann[lo:hi], gsizes[lo:hi], aug, wins)]
         if self.color_on:
             p['color'] = augment.draw_color(self.color_rng, len(idxs), *self.color_jitter)[lo:hi]
         return p
 
     def plan(self):
         """One epoch's host side only (no pixels, no device): per batch this rank's dataset indices, draws, transformed boxes (jitter
-        on: the colour factors under ``'color'``; ``cfg.ignore_overlap`` set: the transformed, clipped flagged boxes under ``'ignore_boxes'``).  Consumes the loader's RandomStates exactly as iterating the epoch does."""
+        on: the colour factors under ``'color'``; ``cfg.letterbox``: the int32 [n, 4] windows under ``'window'``; ``cfg.ignore_overlap`` set: the transformed, clipped flagged boxes under ``'ignore_boxes'``).  Consumes the loader's RandomStates exactly as iterating the epoch does."""
         for idxs in self._global_batches():
             yield self._plan_batch(idxs, [self._size_of(int(i)) for i in idxs], [self.dataset.load_annotations(int(i)) for i in idxs])
 
@@ -195,7 +214,7 @@ class TrainLoader:
         p = self._plan_batch(idxs, gsizes, ann)
         aug, tb, metas = p['aug'], p['boxes'], p['metas']
         color = p.get('color')
-        augment.write_header(stage.np, offsets, sizes, aug, color)
+        augment.write_header(stage.np, offsets, sizes, aug, color, p.get('window'))
         B = hi - lo
         H, W = int(self.cfg.input_size[0]), int(self.cfg.input_size[1])
         dev_buf = torch.empty(total, dtype=torch.uint8, device=self.device)
@@ -203,7 +222,8 @@ class TrainLoader:
         stage.copied = torch.cuda.Event()
         stage.copied.record(torch.cuda.current_stream(self.device))
         out = torch.empty(B, 3, H, W, device=self.device, dtype=torch.float32)
-        augment.launch(dev_buf, B, hdr, self.cfg.input_size, out, self.forbid_resize, self.rgb_mean, self.rgb_std, color=color is not None)
+        augment.launch(dev_buf, B, hdr, self.cfg.input_size, out, self.forbid_resize, self.rgb_mean, self.rgb_std, color=color is not None,
+                       letterbox=self.letterbox, window=self.letterbox)
         sparse = bool(getattr(self.cfg, 'sparse_gt', False))      # the positives as a list (ops.SparseGT): no dense tensor is built
         ignore = None
         if self.ignore_overlap is not None:
