@@ -338,7 +338,8 @@ int sqd_fire_expand_fwd(const float* x, const float* w_packed, const float* bias
  * (C/8 * 16 * Npad * 8 floats, Npad = N rounded up to the configuration's slice width); C % 8 == 0.  Epilogue options as
  * in sqd_conv_fwd, for the data-gradient use: accumulate != 0 adds to y; ymul / ymask (NULL or NHWC tensors with the SAME
  * pixel pitch and channel offset as y) multiply the result (dropout) / zero it where ymask <= 0 (ReLU backward).  cfg_id in
- * [0, sqd_wino_num_cfgs()) (+ 1000 * k = workgroups-per-CU cap); sqd_wino_cfg_info reports slice width and waves. */
+ * [0, sqd_wino_num_cfgs()) (+ 1000 * k = workgroups-per-CU cap); sqd_wino_cfg_info reports slice width and waves, and
+ * SQD_ERR_UNSUPPORTED for the retired ids 4..7, which sqd_conv_wino_fwd does not dispatch either. */
 int sqd_wino_num_cfgs(void);
 int sqd_wino_cfg_info(int cfg_id, int* bn, int* waves);
 int sqd_conv_wino_fwd(const float* x, const float* u_packed, const float* bias, float* y, const float* ymask, const float* ymul,
@@ -537,8 +538,8 @@ int sqd_loss_masked_mean_bwd(const float* pred, const int* anchor_idx, const flo
  * occupies the four inner Winograd positions, so expand1x1 rides along as extra workgroup slices (128 channels x 4 positions
  * each) that reuse the squeeze tile's staging instead of a second launch re-reading it.
  * sqd_pack_wino_fire: w3 OIHW [N3][C][3][3] + w1 OIHW [N1][C][1][1] -> u_packed of (C/8)*16*Npad_total*8 floats,
- * Npad_total = ceil32(N3) + 32*ceil(N1/128).  cfg_id of sqd_fire_wino_fwd: 4 / 6 (streamed U, 8 / 4 waves), 8 / 10
- * (U-stationary: whole U in LDS, needs (C/8)*16 KB + patch ring <= 160 KB), 12 (C <= 16: one workgroup stream runs ALL channel
+ * Npad_total = ceil32(N3) + 32*ceil(N1/128).  cfg_id of sqd_fire_wino_fwd: 8 / 10 (8 / 4 waves;
+ * U-stationary: whole U in LDS, needs (C/8)*16 KB + patch ring <= 160 KB), 12 (C <= 16: one workgroup stream runs ALL channel
  * passes of a pixel group from a transformed input held in registers; whole U in LDS), + 1000*k = workgroups-per-CU cap. */
 int sqd_pack_wino_fire(const float* w3_oihw, const float* w1_oihw, float* u_packed, int N3, int N1, int C, int Npad_total, void* stream);
 int sqd_fire_wino_fwd(const float* x, const float* u_packed, const float* bias3, const float* bias1, float* y, int B, int H, int W,
@@ -552,7 +553,7 @@ int sqd_fire_wino_fwd(const float* x, const float* u_packed, const float* bias3,
  * its 16-channel blocks (expand3x3 slice s: blocks 0, 1 = b3[32 s + 16 j + n]; expand1x1 slice s: 8 blocks = b1[128 s + 16 blk + n];
  * 0 where padded).  sq_ops [blocks][4][ceil(Nsq/16)][64] floats, blocks in the same order (2 per expand3x3 slice, then 8 per
  * expand1x1 slice): value at (block, t, q, lane = 16 g + lr) = Wsq[16 q + lr][cat channel of (block, 4 g + t)], 0 where padded.
- * sq_bias [Nsq].  Nsq <= 32.  cfg_id 10: U resident in LDS (needs (Npad_total/32)*(C/8)*16 KB + 32 KB + operands <= 160 KB), 6: streamed;
+ * sq_bias [Nsq].  Nsq <= 32.  cfg_id 10: U resident in LDS (needs (Npad_total/32)*(C/8)*16 KB + 32 KB + operands <= 160 KB);
  * + 1000*k = workgroups-per-CU cap.  cfg_id 12 (C <= 16; the transformed input of a group stays in registers, 16-wide passes):
  * bias_tab [passes][4][16], passes = 2*ceil(N3/32) expand3x3 passes (block 0 = b3[16 p + n]) then 2*ceil(N1/128) expand1x1 passes s1
  * (block r = b1[128 (s1 >> 1) + (2 r + (s1 & 1)) 16 + n]); sq_ops blocks in that order (1 per expand3x3 pass, 4 per expand1x1 pass). */

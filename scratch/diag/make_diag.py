@@ -10,7 +10,7 @@ csrc = os.path.join(here, '..', '..', 'squeezedet-pytorch_amd', 'csrc')
 
 src = open(os.path.join(csrc, 'conv_igemm.hip')).read()
 a = src.index("__global__ __launch_bounds__(WM * 64, MINW) void conv_dma_kernel")
-b = src.index("static int sqd_num_cus()")
+b = src.index("template <int NT, int WV>\nstatic int launch_conv_ws")     # (first host code behind the kernels)
 k = src[a:b]
 st = "          *(f32x4*)(ybase + off) = v;\n"
 assert st in k

@@ -126,7 +126,9 @@ _SIGNATURES = {
 # symbols added by later build stages; bound when present in the library
 _OPTIONAL = {}
 
-_ERRORS = {1: 'bad argument', 2: 'unsupported configuration', 3: 'kernel launch failed'}
+# status codes of the C ABI (csrc/sqd_common.h: SQD_ERR_BAD_ARG, SQD_ERR_UNSUPPORTED, SQD_ERR_LAUNCH)
+ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = 1, 2, 3
+_ERRORS = {ERR_BAD_ARG: 'bad argument', ERR_UNSUPPORTED: 'unsupported configuration', ERR_LAUNCH: 'kernel launch failed'}
 
 
 class NativeLibraryError(RuntimeError):

@@ -790,16 +790,6 @@ __global__ __launch_bounds__(WV * 64) void conv_ws_kernel(ConvArgs a) {
 #endif
 }
 
-static int sqd_num_cus() {
-  static int cus = 0;                        // immutable per-process cache
-  if (cus == 0) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 template <int NT, int WV>
 static int launch_conv_ws(ConvArgs a, hipStream_t stream) {
   constexpr int BN = 16 * NT, NTHR = WV * 64, KC = 32;

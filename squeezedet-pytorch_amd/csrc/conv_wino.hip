@@ -27,11 +27,8 @@
 // Packed weights: U[C/8][8 position pairs][Npad/16][4 channel pairs][16 n][position parity][2 channels] -- the LDS image
 // of a slice is a set of contiguous runs (sqd_pack_wino_weight; host: ops.WinoPlan).
 #include "sqd_common.h"
+#include "wino_tile.h"
 #include <type_traits>
-#ifndef SQD_WINO_DIAG
-#define SQD_WINO_DIAG 0           /* ablation builds only (scratch/diag/build_wino_diag.sh): bit 0 = no MFMA, 1 = no input transform,
-                                     2 = no DMA inside the chunk loop, 3 = no output stores.  0 in the product library. */
-#endif
 
 struct WinoArgs {
   const float* x; const float* u; const float* bias; float* y;
@@ -41,9 +38,7 @@ struct WinoArgs {
   int relu, accumulate;         // epilogue: y += result
   const float* ymask; const float* ymul;   // epilogue (same pitch / channel offset as y): multiply by ymul (dropout), zero where ymask <= 0
   int gxn, gyn;                 // column / row groups per image
-  unsigned gxn_m, gyn_m;        // ceil(2^32 / gxn), ceil(2^32 / gyn): the group index is split with two scalar multiply-highs
-                                // (a division of wave-uniform integers otherwise goes through ~10 vector instructions + readfirstlane,
-                                // twice per tile, and every vector instruction delays the SIMD's MFMA stream)
+  unsigned gxn_m, gyn_m;        // ceil(2^32 / gxn), ceil(2^32 / gyn) (wino_group_pos, wino_tile.h)
   int ngroups, ntiles;          // B*gyn*gxn groups; ntiles = super-groups of WV groups
   int nslices, gx;              // persistent grid: gx tile streams x nslices channel slices
   int wg_cap;
@@ -66,21 +61,6 @@ struct WinoArgs {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_w_t;
 
-// Diagnostic build only (-DSQD_WINO_STAMP, scratch/diag/wino_stamp.sh; never in libsqdhip.so): every workgroup of conv_wino_kernel
-// records {HW_ID, XCC_ID, start, end (100 MHz clock), tiles done} -- which workgroups of a two-per-CU launch finish early.
-#ifdef SQD_WINO_STAMP
-__device__ long long* sqd_wino_dbg = nullptr;
-extern "C" int sqd_wino_set_debug(long long* p) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(sqd_wino_dbg), &p, sizeof(p)) == hipSuccess ? SQD_OK : SQD_ERR_LAUNCH;
-}
-#endif
-
-__device__ __forceinline__ f32x4 wino_relu4(f32x4 v, float lo) {
-  asm volatile("v_max_f32 %0, %4, %0\n\tv_max_f32 %1, %4, %1\n\tv_max_f32 %2, %4, %2\n\tv_max_f32 %3, %4, %3"
-               : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w) : "s"(lo));
-  return v;
-}
-
 // Residency: 4 waves x 32-channel slices = 80 KB of LDS and 253 VGPRs -> two workgroups per CU (two waves per SIMD).  The
 // 16-channel slice (NT = 1) needs half the accumulators and half the parking area: 48 KB and <= 168 VGPRs -> THREE workgroups per
 // CU, three waves per SIMD.  That is the ConvDet configuration of round 3: N = 72 runs as 5 slices of 16 (80 channels) instead of
@@ -91,8 +71,6 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
 #if defined(__HIP_DEVICE_COMPILE__)    // the host pass only needs the launch stub (the buffer-resource builtins are device-only)
   constexpr int NTHR = WV * 64;
   constexpr int BN = 16 * NT;
-  constexpr int RP = 113;                     // slots per k-quad plane of the raw patch (108 used): 113*16 B = 16 mod 256, so the
-                                              // two planes interleave in the LDS bank row and the transform's reads do not collide
   constexpr int RAW_IT = 4;                   // 256 slots per wave (226 used)
   constexpr int USLOTS = 32 * BN;             // 16 pos x BN channels x 2 halves of 16 B
   static_assert(USLOTS % NTHR == 0, "U slice must be whole workgroup passes");
@@ -118,28 +96,14 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
   int tile = ((int)blockIdx.x & 7) * (a.gx >> 3) + wgq / a.nslices;
   if (tile >= ntiles) return;
   const int wv_s = __builtin_amdgcn_readfirstlane(wv);
-#ifdef SQD_WINO_STAMP
-  const long long stamp_t0 = wall_clock64();
-  long long stamp_tiles = 0;
-#endif
 
   // ---- per-lane DMA slots ----
   // Both DMA streams go through buffer resources: address = resource base + wave-uniform SGPR offset (group origin /
   // K chunk) + per-lane 32-bit offset, so a stage's DMA issue costs no vector instruction at all, and a lane whose slot
-  // lies outside the image carries an offset beyond the resource's range -- the hardware range check then returns zeros
-  // (the zero padding of the convolution) without touching memory.  Only the per-lane offset is range-checked, the SGPR
-  // offset is not (MI355X_MICROARCH.md buffer addressing), so the range only has to exceed any in-patch offset.
-  constexpr unsigned OOB = 0x80000000u;
-  int r_offB[RAW_IT], r_key[RAW_IT];                        // byte offset inside the patch (padding slots: 0), row << 8 | col (-1 = padding)
+  // lies outside the image carries WINO_OOB: zero-filled by the hardware range check.
+  int r_offB[RAW_IT], r_key[RAW_IT];
 #pragma unroll
-  for (int it = 0; it < RAW_IT; ++it) {
-    const int slot = it * 64 + lane;
-    const int kq = slot / RP, pix = slot - kq * RP;
-    const bool real = kq < 2 && pix < 108;
-    const int r = pix / 18, c = pix - r * 18;
-    r_key[it] = real ? (r << 8 | c) : -1;
-    r_offB[it] = real ? ((r * a.W + c) * a.x_pitch + 4 * kq) * 4 : 0;
-  }
+  for (int it = 0; it < RAW_IT; ++it) wino_patch_slot(it * 64 + lane, a.W, a.x_pitch, r_offB[it], r_key[it]);
   int u_offB[U_IT];
 #pragma unroll
   for (int it = 0; it < U_IT; ++it) {
@@ -154,40 +118,13 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
       (void*)(a.x + a.x_coff - (long long)(a.W + 1) * a.x_pitch), 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t ures = __builtin_amdgcn_make_buffer_rsrc((void*)a.u, 0, 0x7ffffff0, 0x00020000);
 
-  struct GPos { int y0, x0, inner, valid; long long p0; unsigned soff; };
-  auto group_pos = [&](int t) {                              // this wave's group of super-group t (all wave-uniform)
-    GPos gp;
-    int q = t * WV + wv_s;
-    gp.valid = (int)((unsigned)(q - a.ngroups) >> 31);       // q < ngroups
-    q = gp.valid ? q : a.ngroups - 1;                        // idle waves of the last super-group redo the last group (not stored)
-    const int q1 = a.gxn_m ? (int)__umulhi((unsigned)q, a.gxn_m) : q;        // q / gxn (exact: q * gxn < 2^32, host-checked; magic 0 = divisor 1)
-    const int gxi = q - q1 * a.gxn;
-    const int b = a.gyn_m ? (int)__umulhi((unsigned)q1, a.gyn_m) : q1;       // q1 / gyn
-    const int gyi = q1 - b * a.gyn;
-    gp.y0 = gyi * 4; gp.x0 = gxi * 16;
-    gp.p0 = ((long long)b * a.H + gp.y0) * a.W + gp.x0;
-    gp.soff = (unsigned)(gp.p0 * a.x_pitch * 4);             // byte offset of the patch origin from the resource base
-    gp.inner = (int)(((unsigned)(-gp.y0) & (unsigned)(gp.y0 + 4 - a.H) & (unsigned)(-gp.x0) & (unsigned)(gp.x0 + 16 - a.W)) >> 31);
-    return gp;
-  };
-  // per-lane patch offsets of the group whose stages are being fetched: evaluated once per group (interior groups: the
-  // plain offsets), out-of-image slots -> OOB
-  int r_offG[RAW_IT];
-  auto group_offsets = [&](const GPos gp) {
-    if (gp.inner) {
-#pragma unroll
-      for (int it = 0; it < RAW_IT; ++it) r_offG[it] = r_offB[it];
-      return;
-    }
-#pragma unroll
-    for (int it = 0; it < RAW_IT; ++it) {
-      const int key = r_key[it];
-      const bool ok = key >= 0 && (unsigned)(gp.y0 + (key >> 8) - 1) < (unsigned)a.H && (unsigned)(gp.x0 + (key & 255) - 1) < (unsigned)a.W;
-      r_offG[it] = ok ? r_offB[it] : (int)OOB;
-    }
-  };
+  typedef WinoGPos GPos;
+  auto group_pos = [&](int t) { return wino_group_pos(a, t * WV + wv_s); };      // this wave's group of super-group t
+  int r_offG[RAW_IT];                                        // per-lane patch offsets of the group whose stages are being fetched
+  auto group_offsets = [&](const GPos gp) { wino_group_offsets<RAW_IT>(gp.y0, gp.x0, gp.inner, a.H, a.W, r_offB, r_key, r_offG); };
   float* const rawW = rawB + wv_s * 256 * 4;                 // this wave's raw patch / V image
   float* const VW = VB + wv_s * 1024 * NT;
+  // (single patch buffer: the other kernels of the family ring two)
   auto dma_raw_one = [&](int it, unsigned soff) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_ptr_w_t)(rawW + it * 64 * 4), 16, r_offG[it], (int)soff, 0, 0);
   };
@@ -215,14 +152,8 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
   for (int px = 0; px < 4; ++px) o_off[px] = ((2 * ty + (px >> 1)) * a.W + 2 * tx + (px & 1)) * a.y_pitch + 4 * g;
   const float relu_lo = a.relu ? 0.f : -__builtin_inff();
 
-  // transform unit of this lane: tile tt, channel pair cp of the chunk
-  // (lanes 0-31 = tile row 0, lanes 32-63 = tile row 1; within a half: 8 tiles x (k-quad, channel half) -- the 32 lanes of
-  // a ds_read_b64 half then cover 32 distinct 8-byte units of one 256-byte bank row: conflict-free)
-  // = the lane's role as MFMA B operand (column = tile lr, k = channel pair g): the transformed values V[pos][tile][2 ch]
-  // are consumed by the lane that computed them and never leave its registers (the patch reads are 2-way bank
-  // conflicted in this order: 16 ds_read_b64 per chunk, cheap next to a V round trip through LDS)
-  const int tt = lr, cp = g;
-  const float* const rawL = rawW + (((cp >> 1) * RP + (2 * (tt >> 3)) * 18 + 2 * (tt & 7)) * 4 + 2 * (cp & 1));
+  // transform unit of this lane: tile lr, channel pair g of the chunk
+  const float* const rawL = rawW + (((g >> 1) * WINO_RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
   // U image per 16 channels: [8 position pairs][4 channel pairs][16 n][pos parity][2 channels] (k-quad-major: conflict-free)
   const float* const uR0 = UB + g * 64 + lr * 4;
   // the former V image now parks a finished tile's outputs until the next barrier: [4 px][NT][64 lanes] f32x4
@@ -246,11 +177,9 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
       const f32x4 m = *(const f32x4*)mask;
       v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
     }
-#if SQD_WINO_DIAG & 8
-    if (v.x == 123.456f)
-#endif
     *(f32x4*)dst = wino_relu4(v, relu_lo);
   };
+  // (parked outputs through flat pointers: the other kernels store straight from registers through wino_store16)
   auto flush = [&](const GPos gp) {
     float* ybase = a.y + gp.p0 * a.y_pitch + a.y_coff + n0;
     const float* mulbase = a.ymul + gp.p0 * a.y_pitch + a.y_coff + n0;     // dereferenced only when present
@@ -300,25 +229,7 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
 
       // ---- input transform: V = B^T d B for (tile tt, channels 2cp, 2cp+1) ----
       f32x2 vv[16];                          // V[pos] for (tile lr, channels 2g, 2g+1): this lane's B operands of the chunk
-#if SQD_WINO_DIAG & 2
-#pragma unroll
-      for (int i = 0; i < 16; ++i) vv[i] = (f32x2){(float)(lane + i + cc), 1.f};
-#else
-      {
-        f32x2 t[4][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f32x2 d0 = *(const f32x2*)(rawL + (0 * 18 + j) * 4), d1 = *(const f32x2*)(rawL + (1 * 18 + j) * 4);
-          const f32x2 d2 = *(const f32x2*)(rawL + (2 * 18 + j) * 4), d3 = *(const f32x2*)(rawL + (3 * 18 + j) * 4);
-          t[0][j] = d0 - d2; t[1][j] = d1 + d2; t[2][j] = d2 - d1; t[3][j] = d1 - d3;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          vv[i * 4 + 0] = t[i][0] - t[i][2]; vv[i * 4 + 1] = t[i][1] + t[i][2];
-          vv[i * 4 + 2] = t[i][2] - t[i][1]; vv[i * 4 + 3] = t[i][1] - t[i][3];
-        }
-      }
-#endif
+      wino_input_transform(rawL, vv);
       // The patch buffer is refilled (LDS-DMA, below) for the next chunk: its reads above must have returned, and neither
       // the compiler nor the machine scheduler may move a DMA issue across this point (the DMA's LDS side is invisible to
       // them).
@@ -343,12 +254,7 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
 #pragma unroll
           for (int j = 0; j < NT; ++j) {
             const f32x4 c0v = (FIRST && t == 0) ? ((p == 5) ? biasv[j] : (f32x4){0.f, 0.f, 0.f, 0.f}) : acc[p][j];
-#if SQD_WINO_DIAG & 1
-            asm volatile("" ::"v"(afr[j][2 * h + t]), "v"(vv[p][t]));      // operands materialised, no matrix instruction
-            acc[p][j] = c0v;
-#else
             acc[p][j] = mfma16(afr[j][2 * h + t], vv[p][t], c0v);
-#endif
           }
       };
       f32x4 af0[NT], af1[NT];
@@ -358,7 +264,6 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
 #pragma unroll
         for (int q = 0; q < NDMA; ++q) {
           if (q * NSTEP / NDMA != step) continue;      // the next stage's DMA instructions are spread over the 8 MFMA steps
-          if (SQD_WINO_DIAG & 4) continue;
           if (q < RAW_IT) dma_raw_one(q < RAW_IT ? q : 0, nsoff);
           else dma_u_one(q - RAW_IT, ncc, ubuf ^ 1);
         }
@@ -382,26 +287,8 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
       if (last) {                            // inverse transform Y = A^T M A in registers; stored after the next barrier
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          // on register pairs (f32x2): adds AND subtracts then compile to one v_pk_add_f32 per pair (a 4-wide subtract
-          // would be four scalar v_sub_f32)
-          auto inv = [&](auto half, auto put) {             // half(v): the register pair to work on; put(px, y): store it
-            f32x2 s[4][2];
-#pragma unroll
-            for (int xi = 0; xi < 4; ++xi) {
-              const f32x2 m0 = half(acc[xi * 4 + 0][j]), m1 = half(acc[xi * 4 + 1][j]);
-              const f32x2 m2 = half(acc[xi * 4 + 2][j]), m3 = half(acc[xi * 4 + 3][j]);
-              s[xi][0] = m0 + m1 + m2;
-              s[xi][1] = m1 - (m2 + m3);
-            }
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-              put(0 * 2 + b, s[0][b] + s[1][b] + s[2][b]);
-              put(1 * 2 + b, s[1][b] - (s[2][b] + s[3][b]));
-            }
-          };
           f32x4 ov[4];
-          inv([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 y) { ov[px].lo = y; });
-          inv([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 y) { ov[px].hi = y; });
+          wino_inverse(acc, j, ov);
 #pragma unroll
           for (int px = 0; px < 4; ++px) parkW[(px * NT + j) * 64] = ov[px];     // lane-contiguous 16-byte slots: conflict-free
         }
@@ -409,56 +296,35 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT == 2) ? 2 : ((WV == 4 && NT
       }
       ubuf ^= 1;
     }
-#ifdef SQD_WINO_STAMP
-    stamp_tiles += 1;
-#endif
     if (!more) break;
     tile += tstride;
     cur = nxt;
   }
   if (pending) flush(ptp);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef SQD_WINO_STAMP
-  if (sqd_wino_dbg && tid == 0) {
-    unsigned hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    long long* d = sqd_wino_dbg + (long long)blockIdx.x * 8;
-    d[0] = hw; d[1] = xcc; d[2] = stamp_t0; d[3] = wall_clock64(); d[4] = stamp_tiles; d[5] = n0;
-  }
 #endif
-#endif
-}
-
-static int wino_num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Deep-prefetch variant (cfg ids 4..7): the same decomposition and arithmetic (bit-identical results), but the staging
-// runs TWO K chunks ahead of the matrix work instead of one.  Measured on the kernel above (scratch/diag/run_wino_diag.py,
-// profiles/r02c_wino_ablation.log): with the MFMAs compiled out a chunk still takes 1.3-2.2 us -- one memory round trip
-// of the LDS-DMA under load -- against 0.85-1.7 us of matrix work per chunk, so with a prefetch distance of one chunk
-// every stage barrier waits for memory.  Here:
-//   * U lives in a ring of THREE buffers, the wave-private raw patch in a ring of TWO; chunk k+2 is requested while
-//     chunk k is multiplied: its U slice right behind the stage barrier (U[(k+2)%3] = U[(k-1)%3] is free from there on),
-//     its patch as soon as the transform has read chunk k's (same buffer);
+// U-stationary deep-prefetch form (cfg ids 8..11, layers with C <= 64): the same decomposition and arithmetic as the kernel
+// above (bit-identical results), but the staging runs TWO K chunks ahead of the matrix work instead of one and no wave waits
+// for another.  Measured on the kernel above (profiles/r02c_wino_ablation.log): with the MFMAs compiled out a chunk still
+// takes 1.3-2.2 us -- one memory round trip of the LDS-DMA under load -- against 0.85-1.7 us of matrix work per chunk, so with
+// a prefetch distance of one chunk every stage barrier waits for memory.  Here:
+//   * the slice's WHOLE transformed weight set (C/8 chunks of U) is fetched into LDS once per workgroup and stays there; ONE
+//     barrier publishes it.  The chunk loop needs neither U requests nor a workgroup barrier, and the waves of a workgroup run
+//     free of each other: the transform of one overlaps the matrix work of its SIMD neighbour instead of all waves meeting
+//     at a barrier 2..8 times per tile;
+//   * the raw patch lives in a wave-private ring of TWO buffers; chunk k+2's patch is requested while chunk k is multiplied,
+//     as soon as the transform has read chunk k's (same buffer);
 //   * the stage wait is a COUNTED s_waitcnt vmcnt(N) that leaves the younger chunk's DMA (and a finished tile's stores)
-//     in flight -- vector-memory operations retire in issue order (MI355X_MICROARCH.md) -- and the stage barrier is a raw
-//     s_barrier (a __syncthreads() would drain the DMA queue with vmcnt(0));
-//   * the LDS for the extra buffers comes from dropping the output parking area: a finished tile is inverse-transformed
-//     and stored straight from registers behind its last chunk; with counted waits those stores never block a stage.
-// 4 waves x (2 x 4 KB patch) + 3 x 16 KB U = 80 KB: still two workgroups per CU.
-// USTAT = true (cfg ids 8..11, layers with C <= 64): the slice's WHOLE transformed weight set (C/8 chunks) is fetched into LDS
-// once per workgroup and stays there, so the chunk loop needs neither U requests nor a workgroup barrier -- the patch ring
-// is wave-private -- and the waves of a workgroup run free of each other: the transform of one overlaps the matrix work
-// of its SIMD neighbour instead of all waves meeting at a barrier 2..8 times per tile.
+//     in flight -- vector-memory operations retire in issue order (MI355X_MICROARCH.md);
+//   * there is no output parking area: a finished tile is inverse-transformed and stored straight from registers behind its
+//     last chunk; with counted waits those stores never block a stage.
+// LDS at 32-channel slices: WV x (2 x 4 KB patch) + C/8 x 16 KB of U (the launcher asks the occupancy per launch).
+// USTAT is kept in the kernels' template lists (their symbols are cited by the committed profiles); the streamed-U form it
+// once selected (ids 4..7, U through a ring of three buffers behind a stage barrier) is retired: no measured row ever selected it
+// (profiles/r02d, r02f).
 // E1 = true: the workgroup is an expand1x1 slice of the fused Fire launch (sqd_fire_wino_fwd).  A 1x1 convolution in the
 // Winograd domain only touches the four inner positions (1,1), (1,2), (2,1), (2,2) (U = +-0.25 w there, 0 elsewhere), so such a
 // slice carries 128 channels x 4 positions instead of 32 channels x 16 positions: the same 32 accumulators, the same 64
@@ -466,21 +332,21 @@ static int wino_num_cus() {
 // 2 r + j -- and only the operand selection, the bias injection and the inverse transform differ.
 template <int NT, int WV, bool USTAT, bool E1>
 __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
+  static_assert(USTAT, "streamed-U form retired");
   static_assert(!E1 || NT == 2, "expand1x1 slices are built on the 32-channel tiling");
   constexpr int NTHR = WV * 64;
   constexpr int BN = 16 * NT;
-  constexpr int RP = 113;
   constexpr int RAW_IT = 4;
   constexpr int USLOTS = 32 * BN;
   static_assert(USLOTS % NTHR == 0, "U slice must be whole workgroup passes");
   constexpr int U_IT = USLOTS / NTHR;
-  constexpr int NDMA = RAW_IT + (USTAT ? 0 : U_IT);      // DMA instructions per wave and chunk
+  constexpr int NDMA = RAW_IT;                // DMA instructions per wave and chunk
   constexpr int NST = 4 * NT;                 // store instructions of a whole tile's plain epilogue
   constexpr int NSTEP = 8;
   constexpr int RAW_STEPS = 4;                // the patch refill is spread over the first MFMA steps
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* const rawB = smem;                                 // [2][WV][256][4]
-  float* const UB = rawB + 2 * WV * 256 * 4;                // [3][USLOTS][4] ring, or (USTAT) [C/8][USLOTS][4] resident
+  float* const UB = rawB + 2 * WV * 256 * 4;                // [C/8][USLOTS][4] resident
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int lr = lane & 15, g = lane >> 4;
@@ -497,17 +363,9 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
   if (tile >= ntiles) return;
   const int wv_s = __builtin_amdgcn_readfirstlane(wv);
 
-  constexpr unsigned OOB = 0x80000000u;
   int r_offB[RAW_IT], r_key[RAW_IT];
 #pragma unroll
-  for (int it = 0; it < RAW_IT; ++it) {
-    const int slot = it * 64 + lane;
-    const int kq = slot / RP, pix = slot - kq * RP;
-    const bool real = kq < 2 && pix < 108;
-    const int r = pix / 18, c = pix - r * 18;
-    r_key[it] = real ? (r << 8 | c) : -1;
-    r_offB[it] = real ? ((r * a.W + c) * a.x_pitch + 4 * kq) * 4 : 0;
-  }
+  for (int it = 0; it < RAW_IT; ++it) wino_patch_slot(it * 64 + lane, a.W, a.x_pitch, r_offB[it], r_key[it]);
   int u_offB[U_IT];
 #pragma unroll
   for (int it = 0; it < U_IT; ++it) {
@@ -520,42 +378,16 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
       (void*)(a.x + a.x_coff - (long long)(a.W + 1) * a.x_pitch), 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t ures = __builtin_amdgcn_make_buffer_rsrc((void*)a.u, 0, 0x7ffffff0, 0x00020000);
 
-  struct GPos { int y0, x0, inner, valid; long long p0; unsigned soff; };
-  auto group_pos = [&](int t) {
-    GPos gp;
-    int q = t * WV + wv_s;
-    gp.valid = (int)((unsigned)(q - a.ngroups) >> 31);
-    q = gp.valid ? q : a.ngroups - 1;
-    const int q1 = a.gxn_m ? (int)__umulhi((unsigned)q, a.gxn_m) : q;        // q / gxn (exact: q * gxn < 2^32, host-checked; magic 0 = divisor 1)
-    const int gxi = q - q1 * a.gxn;
-    const int b = a.gyn_m ? (int)__umulhi((unsigned)q1, a.gyn_m) : q1;       // q1 / gyn
-    const int gyi = q1 - b * a.gyn;
-    gp.y0 = gyi * 4; gp.x0 = gxi * 16;
-    gp.p0 = ((long long)b * a.H + gp.y0) * a.W + gp.x0;
-    gp.soff = (unsigned)(gp.p0 * a.x_pitch * 4);
-    gp.inner = (int)(((unsigned)(-gp.y0) & (unsigned)(gp.y0 + 4 - a.H) & (unsigned)(-gp.x0) & (unsigned)(gp.x0 + 16 - a.W)) >> 31);
-    return gp;
-  };
+  typedef WinoGPos GPos;
+  auto group_pos = [&](int t) { return wino_group_pos(a, t * WV + wv_s); };
   int r_offG[RAW_IT];                                        // per-lane patch offsets of the group at the PREFETCH cursor
-  auto group_offsets = [&](int y0, int x0, int inner) {
-    if (inner) {
-#pragma unroll
-      for (int it = 0; it < RAW_IT; ++it) r_offG[it] = r_offB[it];
-      return;
-    }
-#pragma unroll
-    for (int it = 0; it < RAW_IT; ++it) {
-      const int key = r_key[it];
-      const bool ok = key >= 0 && (unsigned)(y0 + (key >> 8) - 1) < (unsigned)a.H && (unsigned)(x0 + (key & 255) - 1) < (unsigned)a.W;
-      r_offG[it] = ok ? r_offB[it] : (int)OOB;
-    }
-  };
+  auto group_offsets = [&](int y0, int x0, int inner) { wino_group_offsets<RAW_IT>(y0, x0, inner, a.H, a.W, r_offB, r_key, r_offG); };
   float* const rawW = rawB + wv_s * 256 * 4;                 // this wave's patch buffer 0 (buffer 1: + WV*256*4 floats)
   auto dma_raw_one = [&](int it, unsigned soff, int rb) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_ptr_w_t)(rawW + (rb * WV * 256 + it * 64) * 4), 16, r_offG[it], (int)soff, 0, 0);
   };
-  auto dma_u_one = [&](int it, int cc, int ub) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(ures, (lds_ptr_w_t)(UB + (ub * USLOTS + it * NTHR + wv_s * 64) * 4), 16, u_offB[it],
+  auto dma_u_one = [&](int it, int cc, int slot) {           // chunk cc of the slice's U into resident slot `slot` (= cc)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(ures, (lds_ptr_w_t)(UB + (slot * USLOTS + it * NTHR + wv_s * 64) * 4), 16, u_offB[it],
                                              (int)(cc * u_chunkB), 0, 0);
   };
 
@@ -593,20 +425,8 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
   const __amdgpu_buffer_rsrc_t yres = __builtin_amdgcn_make_buffer_rsrc((void*)(E1 ? a.y + a.y_coff1 + e1_c0 : a.y + a.y_coff + n0), 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t mulres = __builtin_amdgcn_make_buffer_rsrc((void*)(a.ymul ? a.ymul + a.y_coff + n0 : a.y), 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t maskres = __builtin_amdgcn_make_buffer_rsrc((void*)(a.ymask ? a.ymask + a.y_coff + n0 : a.y), 0, 0x7ffffff0, 0x00020000);
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-  // A 16-byte MUBUF store whose soffset is an SGPR, directly followed by a VALU write of its first data register, stored
-  // the NEW value in the last four lanes of every 16-lane row on this chip (found as rare wrong outputs, always component
-  // 0 of tile columns 12..15; the compiler only pads this write-after-read hazard when soffset is NOT a register): two
-  // wait states behind every such store, pinned in place.
-  auto store16 = [&](f32x4 v, __amdgpu_buffer_rsrc_t res, int voff, int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), res, voff, soff, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
   const float relu_lo = a.relu ? 0.f : -__builtin_inff();
-  const int tt = lr, cp = g;
-  const int rawL_off = (((cp >> 1) * RP + (2 * (tt >> 3)) * 18 + 2 * (tt & 7)) * 4 + 2 * (cp & 1));
+  const int rawL_off = (((g >> 1) * WINO_RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
   const float* const uR0 = UB + g * 64 + lr * 4;
   const int acc_i = a.accumulate, has_mul = a.ymul != nullptr, has_mask = a.ymask != nullptr;
   const bool plain_epi = !acc_i && !has_mul && !has_mask;
@@ -627,25 +447,20 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
       group_offsets(pf.y0, pf.x0, pf.inner);
     }
   };
-  if (USTAT) {                            // the whole slice of U, once; published by the only barrier of the kernel
-    for (int c = 0; c < nchunks; ++c)
+  // the whole slice of U, once; published by the only barrier of the kernel
+  for (int c = 0; c < nchunks; ++c)
 #pragma unroll
-      for (int it = 0; it < U_IT; ++it) dma_u_one(it, c, c);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  // prologue: chunks 0 and 1
+    for (int it = 0; it < U_IT; ++it) dma_u_one(it, c, c);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  // prologue: the patches of chunks 0 and 1
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    if (!USTAT) {
-#pragma unroll
-      for (int it = 0; it < U_IT; ++it) dma_u_one(it, pcc, s);
-    }
 #pragma unroll
     for (int it = 0; it < RAW_IT; ++it) dma_raw_one(it, psoff + (unsigned)pcc * 32u, s);
     advance();
   }
-  int ub = 0, rb = 0;                    // ring slots of the chunk about to be computed
+  int rb = 0;                            // patch ring slot of the chunk about to be computed
   int stores_behind = 0;                 // store instructions the previous chunk issued behind its DMA requests (0 = unknown)
 
   for (;;) {
@@ -663,46 +478,20 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
         else if (E1 && sb == 16) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA + 16) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");      // unknown / other counts: the smaller N is merely conservative
       }
-      if (!USTAT) __builtin_amdgcn_s_barrier();      // every wave's share of U[ub] is in LDS; every wave has left U[(ub+2)%3]
       asm volatile("" ::: "memory");
       stores_behind = 0;
       const int last_i = 1 - (int)((unsigned)(cc + 1 - nchunks) >> 31);
       const bool last = last_i != 0;
-      const int ub2 = (ub >= 1) ? ub - 1 : 2;                   // (ub + 2) % 3
-      // U slice of chunk k+2: its ring slot is free from the barrier on
-      if (!USTAT) {
-#pragma unroll
-        for (int it = 0; it < U_IT; ++it) dma_u_one(it, pcc, ub2);
-      }
       const unsigned nsoff = psoff + (unsigned)pcc * 32u;
 
       // ---- input transform of chunk k from patch buffer rb ----
       f32x2 vv[16];
-      if constexpr (E1) {
-        // only the four inner positions are needed: rows 1, 2 x columns 1, 2 of the tile's 4x4 patch
-        const float* const rawL = rawW + rb * WV * 256 * 4 + rawL_off;
-        const f32x2 d11 = *(const f32x2*)(rawL + (1 * 18 + 1) * 4), d12 = *(const f32x2*)(rawL + (1 * 18 + 2) * 4);
-        const f32x2 d21 = *(const f32x2*)(rawL + (2 * 18 + 1) * 4), d22 = *(const f32x2*)(rawL + (2 * 18 + 2) * 4);
-        const f32x2 t11 = d11 + d21, t12 = d12 + d22, t21 = d21 - d11, t22 = d22 - d12;      // column transform rows 1, 2
-        vv[5] = t11 + t12; vv[6] = t12 - t11; vv[9] = t21 + t22; vv[10] = t22 - t21;
-      } else {
-        const float* const rawL = rawW + rb * WV * 256 * 4 + rawL_off;
-        f32x2 t[4][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f32x2 d0 = *(const f32x2*)(rawL + (0 * 18 + j) * 4), d1 = *(const f32x2*)(rawL + (1 * 18 + j) * 4);
-          const f32x2 d2 = *(const f32x2*)(rawL + (2 * 18 + j) * 4), d3 = *(const f32x2*)(rawL + (3 * 18 + j) * 4);
-          t[0][j] = d0 - d2; t[1][j] = d1 + d2; t[2][j] = d2 - d1; t[3][j] = d1 - d3;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          vv[i * 4 + 0] = t[i][0] - t[i][2]; vv[i * 4 + 1] = t[i][1] + t[i][2];
-          vv[i * 4 + 2] = t[i][2] - t[i][1]; vv[i * 4 + 3] = t[i][1] - t[i][3];
-        }
-      }
+      const float* const rawL = rawW + rb * WV * 256 * 4 + rawL_off;
+      if constexpr (E1) wino_input_transform_inner(rawL, vv);
+      else wino_input_transform(rawL, vv);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the patch reads have returned: buffer rb may be refilled
       __builtin_amdgcn_sched_barrier(0);
-      const float* const uR = uR0 + (USTAT ? cc : ub) * USLOTS * 4;
+      const float* const uR = uR0 + cc * USLOTS * 4;
 
       auto load_ops = [&](int step, f32x4 (&afr)[NT]) {
 #pragma unroll
@@ -762,6 +551,7 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
         if constexpr (E1) {
           // M is non-zero only at the inner 2x2: y00 = m11+m12+m21+m22, y01 = m11-m12+m21-m22, y10 = m11+m12-m21-m22,
           // y11 = m11-m12-m21+m22; block blk = 2 r + j lives in accumulators [4 q + r][j], q = 0..3
+          // (4-wide arithmetic on [16][2] accumulators: not wino_inverse_inner's register pairs)
           const bool wholexy = cur.y0 + 4 <= a.H && cur.x0 + 16 <= a.W;
           int nst = 0;
 #pragma unroll
@@ -775,7 +565,7 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
             for (int px = 0; px < 4; ++px) {
               const bool valid = wholexy || (cur.y0 + 2 * ty + (px >> 1) < a.H && cur.x0 + 2 * tx + (px & 1) < a.W);
               if (!valid || e1_c0 + blk * 16 + 4 * g >= a.N1) continue;
-              store16(wino_relu4(ov[px], relu_lo), yres, o_offB[px] + blk * 64, ysoff);
+              wino_store16(wino_relu4(ov[px], relu_lo), yres, o_offB[px] + blk * 64, ysoff);
             }
             nst += 4;
           }
@@ -784,28 +574,12 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
         const bool whole = cur.y0 + 4 <= a.H && cur.x0 + 16 <= a.W && n0 + BN <= a.N;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          auto inv = [&](auto half, auto put) {
-            f32x2 sx[4][2];
-#pragma unroll
-            for (int xi = 0; xi < 4; ++xi) {
-              const f32x2 m0 = half(acc[xi * 4 + 0][j]), m1 = half(acc[xi * 4 + 1][j]);
-              const f32x2 m2 = half(acc[xi * 4 + 2][j]), m3 = half(acc[xi * 4 + 3][j]);
-              sx[xi][0] = m0 + m1 + m2;
-              sx[xi][1] = m1 - (m2 + m3);
-            }
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-              put(0 * 2 + b, sx[0][b] + sx[1][b] + sx[2][b]);
-              put(1 * 2 + b, sx[1][b] - (sx[2][b] + sx[3][b]));
-            }
-          };
           f32x4 ov[4];
-          inv([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 y) { ov[px].lo = y; });
-          inv([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 y) { ov[px].hi = y; });
+          wino_inverse(acc, j, ov);
           if (whole && plain_epi) {
 #pragma unroll
             for (int px = 0; px < 4; ++px)
-              store16(wino_relu4(ov[px], relu_lo), yres, o_offB[px] + j * 64, ysoff);
+              wino_store16(wino_relu4(ov[px], relu_lo), yres, o_offB[px] + j * 64, ysoff);
           } else {
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
@@ -819,14 +593,13 @@ __device__ __forceinline__ void wino_pipe_body(const WinoArgs& a) {
                 const f32x4 m = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(maskres, off, ysoff, 0));
                 v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
               }
-              store16(wino_relu4(v, relu_lo), yres, off, ysoff);
+              wino_store16(wino_relu4(v, relu_lo), yres, off, ysoff);
             }
           }
         }
         stores_behind = (whole && plain_epi) ? NST : 0;
         }
       }
-      ub = (ub == 2) ? 0 : ub + 1;
       rb ^= 1;
     }
     if (!more) break;
@@ -846,13 +619,11 @@ __global__ __launch_bounds__(WV * 64, (WV == 4 && NT <= 2) ? 2 : 1) void conv_wi
 #endif
 }
 
-template <int NT, int WV, bool USTAT = false, bool FIRE = false>
+template <int NT, int WV, bool USTAT, bool FIRE = false>
 static int launch_wino_pipe(WinoArgs a, hipStream_t stream) {
   constexpr int BN = 16 * NT, NTHR = WV * 64;
-  constexpr size_t lds_ring = (size_t)(2 * WV * 256 * 4 + 3 * 32 * BN * 4) * sizeof(float);
-  static_assert(lds_ring <= 160 * 1024, "LDS budget");
-  // U-stationary: the patch ring + C/8 chunks of the slice's U
-  const size_t lds = USTAT ? (size_t)(2 * WV * 256 * 4 + (a.C >> 3) * 32 * BN * 4) * sizeof(float) : lds_ring;
+  // the patch ring + C/8 chunks of the slice's U
+  const size_t lds = (size_t)(2 * WV * 256 * 4 + (a.C >> 3) * 32 * BN * 4) * sizeof(float);
   if (lds > 160 * 1024) return SQD_ERR_UNSUPPORTED;
   auto kern = conv_wino_pipe_kernel<NT, WV, USTAT, FIRE>;
   // 32-bit SGPR byte offset of a tile's output origin / per-lane byte offsets inside a group (buffer-resource stores)
@@ -862,22 +633,14 @@ static int launch_wino_pipe(WinoArgs a, hipStream_t stream) {
   int nb = 0;              // occupancy depends on the (C-dependent) LDS size of the stationary variant: ask per launch
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, NTHR, lds) != hipSuccess || nb < 1) nb = 1;
   const int wgs_per_cu = nb > 4 ? 4 : nb;
-  a.gxn = sqd_cdiv(a.W, 16); a.gyn = sqd_cdiv(a.H, 4);
-  a.ngroups = a.B * a.gxn * a.gyn;
-  if ((long long)(a.ngroups + 8) * (a.gxn > a.gyn ? a.gxn : a.gyn) >= (1ll << 32)) return SQD_ERR_UNSUPPORTED;
-  a.gxn_m = a.gxn > 1 ? (unsigned)(((1ull << 32) + a.gxn - 1) / a.gxn) : 0u; a.gyn_m = a.gyn > 1 ? (unsigned)(((1ull << 32) + a.gyn - 1) / a.gyn) : 0u;
-  a.ntiles = sqd_cdiv(a.ngroups, WV);
+  if (int rc = wino_launch_geometry(a, WV)) return rc;
   // fused Fire launch: every 32-wide slice of the packed (virtual) channel axis is a workgroup stream -- first the
   // expand3x3 slices, then the expand1x1 slices (128 real channels each)
   const int nslices = FIRE ? a.Npad / BN : sqd_cdiv(a.N, BN);
   if (nslices * BN > a.Npad) return SQD_ERR_BAD_ARG;
   if (!FIRE) a.nslices3 = nslices;
-  const int slots = wino_num_cus() * ((a.wg_cap > 0 && a.wg_cap < wgs_per_cu) ? a.wg_cap : wgs_per_cu);
-  int gx_max = slots / nslices; if (gx_max < 1) gx_max = 1;
-  const int per_wg = sqd_cdiv(a.ntiles, gx_max);
-  const int gx = (sqd_cdiv(a.ntiles, per_wg) + 7) & ~7;
-  a.nslices = nslices; a.gx = gx;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(gx * nslices)), dim3(NTHR), lds, stream, a);
+  a.nslices = nslices; a.gx = wino_grid(a, nslices, wgs_per_cu);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.gx * nslices)), dim3(NTHR), lds, stream, a);
   return sqd_launch_status();
 }
 
@@ -898,19 +661,11 @@ static int launch_wino(WinoArgs a, hipStream_t stream) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, NTHR, lds) != hipSuccess || nb < 1) nb = 1;
     wgs_per_cu = nb > 4 ? 4 : nb;
   }
-  a.gxn = sqd_cdiv(a.W, 16); a.gyn = sqd_cdiv(a.H, 4);
-  a.ngroups = a.B * a.gxn * a.gyn;
-  if ((long long)(a.ngroups + 8) * (a.gxn > a.gyn ? a.gxn : a.gyn) >= (1ll << 32)) return SQD_ERR_UNSUPPORTED;
-  a.gxn_m = a.gxn > 1 ? (unsigned)(((1ull << 32) + a.gxn - 1) / a.gxn) : 0u; a.gyn_m = a.gyn > 1 ? (unsigned)(((1ull << 32) + a.gyn - 1) / a.gyn) : 0u;
-  a.ntiles = sqd_cdiv(a.ngroups, WV);
+  if (int rc = wino_launch_geometry(a, WV)) return rc;
   const int nslices = sqd_cdiv(a.N, BN);
   if (nslices * BN > a.Npad) return SQD_ERR_BAD_ARG;
-  const int slots = wino_num_cus() * ((a.wg_cap > 0 && a.wg_cap < wgs_per_cu) ? a.wg_cap : wgs_per_cu);
-  int gx_max = slots / nslices; if (gx_max < 1) gx_max = 1;
-  const int per_wg = sqd_cdiv(a.ntiles, gx_max);
-  const int gx = (sqd_cdiv(a.ntiles, per_wg) + 7) & ~7;
-  a.nslices = nslices; a.gx = gx;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(gx * nslices)), dim3(NTHR), lds, stream, a);
+  a.nslices = nslices; a.gx = wino_grid(a, nslices, wgs_per_cu);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.gx * nslices)), dim3(NTHR), lds, stream, a);
   return sqd_launch_status();
 }
 
@@ -1054,18 +809,18 @@ extern "C" int sqd_gather_pack_batched(const void* descs_dev, int n, int blocks_
 }
 
 // Winograd configurations: cfg_id -> (channel blocks per slice NT, waves per workgroup WV)
-struct WinoCfg { int nt, wv; };
-// ids 4..7: the same tilings on the deep-prefetch kernel (conv_wino_pipe_kernel); 8..11: its U-stationary, barrier-free
-// form (the slice's whole U must fit the LDS next to the patch ring: C <= 64 at 32-channel slices, else "unsupported")
-static const WinoCfg kWinoCfgs[] = {{2, 8}, {1, 8}, {2, 4}, {1, 4}, {2, 8}, {1, 8}, {2, 4}, {1, 4}, {2, 8}, {1, 8}, {2, 4}, {1, 4}};
-static const int kNumWinoCfgs = (int)(sizeof(kWinoCfgs) / sizeof(kWinoCfgs[0]));
+// cfg_id & 3 = {0: (2, 8), 1: (1, 8), 2: (2, 4), 3: (1, 4)}.  Ids 0..3: conv_wino_kernel; 8..11: the same tilings on
+// conv_wino_pipe_kernel (U-stationary: the slice's whole U must fit the LDS next to the patch ring: C <= 64 at 32-channel
+// slices, else "unsupported"); 4..7 (its streamed-U form) are retired and answer "unsupported".
+static const int kNumWinoCfgs = 12;
 
 extern "C" int sqd_wino_num_cfgs() { return kNumWinoCfgs; }
 
 extern "C" int sqd_wino_cfg_info(int cfg_id, int* bn, int* waves) {
   if (cfg_id < 0 || cfg_id >= kNumWinoCfgs) return SQD_ERR_BAD_ARG;
-  if (bn) *bn = 16 * kWinoCfgs[cfg_id].nt;
-  if (waves) *waves = kWinoCfgs[cfg_id].wv;
+  if (cfg_id >= 4 && cfg_id <= 7) return SQD_ERR_UNSUPPORTED;
+  if (bn) *bn = (cfg_id & 1) ? 16 : 32;
+  if (waves) *waves = (cfg_id & 2) ? 4 : 8;
   return SQD_OK;
 }
 
@@ -1075,17 +830,12 @@ extern "C" int sqd_conv_wino_fwd(const float* x, const float* u_packed, const fl
   SQD_CHECK_ARG(x && u_packed && y);
   SQD_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && N > 0);
   SQD_CHECK_ARG(C % 8 == 0 && N % 4 == 0 && Npad >= N);
-  SQD_CHECK_ARG(x_pitch % 4 == 0 && x_coff % 4 == 0 && y_pitch % 4 == 0 && y_coff % 4 == 0);
-  SQD_CHECK_ARG(x_coff >= 0 && x_coff + C <= x_pitch && y_coff >= 0 && y_coff + N <= y_pitch);
-  SQD_CHECK_ARG((long long)W * 6 * (x_pitch > y_pitch ? x_pitch : y_pitch) * 4 < (1ll << 30));   // per-lane byte offsets inside a group
-  SQD_CHECK_ARG((long long)B * H * W * x_pitch * 4 < (1ll << 32) - (1ll << 30));                   // 32-bit SGPR byte offset of a group origin
-  SQD_CHECK_ARG((long long)(C >> 3) * 16 * Npad * 8 * 4 < (1ll << 32));
+  if (int rc = wino_check_common(B, H, W, C, x_pitch, x_coff, N, Npad, y_pitch, y_coff, x_pitch > y_pitch ? x_pitch : y_pitch)) return rc;
   const int cap = cfg_id / 1000; cfg_id %= 1000;
   SQD_CHECK_ARG(cfg_id >= 0 && cfg_id < kNumWinoCfgs);
   WinoArgs a{};
-  a.x = x; a.u = u_packed; a.bias = bias; a.y = y;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.N = N; a.Npad = Npad; a.y_pitch = y_pitch; a.y_coff = y_coff; a.relu = relu; a.wg_cap = cap;
+  wino_fill_args(a, x, u_packed, y, B, H, W, C, x_pitch, x_coff, N, Npad, y_pitch, y_coff, relu);
+  a.bias = bias; a.wg_cap = cap;
   a.accumulate = accumulate; a.ymask = ymask; a.ymul = ymul;
   hipStream_t s = (hipStream_t)stream;
   switch (cfg_id) {
@@ -1093,7 +843,7 @@ extern "C" int sqd_conv_wino_fwd(const float* x, const float* u_packed, const fl
     case 1: return launch_wino<1, 8>(a, s);
     case 2: return launch_wino<2, 4>(a, s);
     case 3: return launch_wino<1, 4>(a, s);
-    // (ids 4..7, the deep-prefetch streamed-U forms, are retired: no measured row ever selected them -- profiles/r02d, r02f)
+    // (ids 4..7, the streamed-U forms, are retired: no measured row ever selected them -- profiles/r02d, r02f)
     case 8: return launch_wino_pipe<2, 8, true>(a, s);
     case 9: return launch_wino_pipe<1, 8, true>(a, s);
     case 10: return launch_wino_pipe<2, 4, true>(a, s);
@@ -1104,25 +854,21 @@ extern "C" int sqd_conv_wino_fwd(const float* x, const float* u_packed, const fl
 
 // Fire.forward's two expand convolutions + torch.cat (src/model/squeezedet.py:18-22) in ONE Winograd launch: y[..., y_coff3 :
 // y_coff3 + N3] = ReLU(conv3x3(x) + b3), y[..., y_coff1 : y_coff1 + N1] = ReLU(conv1x1(x) + b1).  u_packed from
-// sqd_pack_wino_fire; cfg_id: a 32-channel-slice id of the deep-prefetch family (4, 6: streamed U; 8, 10: U-stationary, C <= 64
-// at 4 waves / C <= 32 at 8; 12: C <= 16, the group's transformed input stays in registers, U resident, eight waves),
-// + 1000 k = workgroups-per-CU cap.  Plain epilogue: bias + ReLU.
+// sqd_pack_wino_fire; cfg_id: 8, 10: the U-stationary 32-channel-slice forms (C <= 64 at 4 waves / C <= 32 at 8); 12: C <= 16,
+// the group's transformed input stays in registers, U resident, eight waves; + 1000 k = workgroups-per-CU cap.  Plain
+// epilogue: bias + ReLU.
 extern "C" int sqd_fire_wino_fwd(const float* x, const float* u_packed, const float* bias3, const float* bias1, float* y, int B, int H,
                                  int W, int C, int x_pitch, int x_coff, int N3, int y_coff3, int N1, int y_coff1, int Npad_total,
                                  int y_pitch, int cfg_id, void* stream) {
   SQD_CHECK_ARG(x && u_packed && y && B > 0 && H > 0 && W > 0 && C > 0 && N3 > 0 && N1 > 0);
   SQD_CHECK_ARG(C % 8 == 0 && N3 % 4 == 0 && N1 % 16 == 0);
-  SQD_CHECK_ARG(x_pitch % 4 == 0 && x_coff % 4 == 0 && y_pitch % 4 == 0 && y_coff3 % 4 == 0 && y_coff1 % 4 == 0);
-  SQD_CHECK_ARG(x_coff >= 0 && x_coff + C <= x_pitch && y_coff3 >= 0 && y_coff3 + N3 <= y_pitch && y_coff1 >= 0 && y_coff1 + N1 <= y_pitch);
+  if (int rc = wino_check_common(B, H, W, C, x_pitch, x_coff, N3, Npad_total, y_pitch, y_coff3, x_pitch > y_pitch ? x_pitch : y_pitch)) return rc;
+  SQD_CHECK_ARG(y_coff1 % 4 == 0 && y_coff1 >= 0 && y_coff1 + N1 <= y_pitch);
   SQD_CHECK_ARG(Npad_total == sqd_cdiv(N3, 32) * 32 + sqd_cdiv(N1, 128) * 32);
-  SQD_CHECK_ARG((long long)W * 6 * (x_pitch > y_pitch ? x_pitch : y_pitch) * 4 < (1ll << 30));
-  SQD_CHECK_ARG((long long)B * H * W * x_pitch * 4 < (1ll << 32) - (1ll << 30));
-  SQD_CHECK_ARG((long long)(C >> 3) * 16 * Npad_total * 8 * 4 < (1ll << 32));
   const int cap = cfg_id / 1000; cfg_id %= 1000;
   WinoArgs a{};
-  a.x = x; a.u = u_packed; a.bias = bias3; a.bias1 = bias1; a.y = y;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.N = N3; a.Npad = Npad_total; a.y_pitch = y_pitch; a.y_coff = y_coff3; a.relu = 1; a.wg_cap = cap;
+  wino_fill_args(a, x, u_packed, y, B, H, W, C, x_pitch, x_coff, N3, Npad_total, y_pitch, y_coff3, 1);
+  a.bias = bias3; a.bias1 = bias1; a.wg_cap = cap;
   a.N1 = N1; a.y_coff1 = y_coff1; a.nslices3 = sqd_cdiv(N3, 32);
   hipStream_t s = (hipStream_t)stream;
   switch (cfg_id) {
@@ -1139,8 +885,8 @@ extern "C" int sqd_fire_wino_fwd(const float* x, const float* u_packed, const fl
 // bias_tab [Npad_total/32][8][16]: per pass (32-wide slice of the packed axis) the biases of its channel blocks (expand3x3
 // slice: blocks 0, 1; expand1x1 slice: 8 blocks of its 128 channels; 0 where padded); sq_ops [blocks][4][ceil(Nsq/16)][64]:
 // the squeeze weights as MFMA A operands, blocks in pass order, value for lane (lr, g) at (block, t, q) =
-// Wsq[16 q + lr][channel(block) + 4 g + t] (0 where padded).  cfg_id 10: U resident in LDS (small C), 6: streamed through the
-// ring; four waves per workgroup, one workgroup per CU (the wave owns 512 registers: 128 + 16..32 accumulators).
+// Wsq[16 q + lr][channel(block) + 4 g + t] (0 where padded).  cfg_id 10: U resident in LDS (small C); four waves per
+// workgroup, one workgroup per CU (the wave owns 512 registers: 128 + 16..32 accumulators).
 // cfg_id 12 (C <= 16): 16-wide passes, the group's transformed input stays in registers, eight waves; its bias_tab is
 // [passes][4][16] and its sq_ops blocks follow ITS pass order: one block per expand3x3 pass (2 ceil(N3/32) passes of 16
 // channels), then four per expand1x1 pass s1 (channels 128 (s1 >> 1) + (2 r + (s1 & 1)) 16 + n, r = 0..3).
@@ -1149,17 +895,12 @@ extern "C" int sqd_fire_bridge_fwd(const float* x, const float* u_packed, const 
                                    int Nsq, int y_pitch, int y_coff, int cfg_id, void* stream) {
   SQD_CHECK_ARG(x && u_packed && bias_tab && sq_ops && y && B > 0 && H > 0 && W > 0 && C > 0 && N3 > 0 && N1 > 0 && Nsq > 0);
   SQD_CHECK_ARG(C % 8 == 0 && N3 % 4 == 0 && N1 % 16 == 0 && Nsq % 4 == 0 && Nsq <= 32);
-  SQD_CHECK_ARG(x_pitch % 4 == 0 && x_coff % 4 == 0 && y_pitch % 4 == 0 && y_coff % 4 == 0);
-  SQD_CHECK_ARG(x_coff >= 0 && x_coff + C <= x_pitch && y_coff >= 0 && y_coff + Nsq <= y_pitch);
+  if (int rc = wino_check_common(B, H, W, C, x_pitch, x_coff, Nsq, Npad_total, y_pitch, y_coff, x_pitch > y_pitch ? x_pitch : y_pitch)) return rc;
   SQD_CHECK_ARG(Npad_total == sqd_cdiv(N3, 32) * 32 + sqd_cdiv(N1, 128) * 32);
-  SQD_CHECK_ARG((long long)W * 6 * (x_pitch > y_pitch ? x_pitch : y_pitch) * 4 < (1ll << 30));
-  SQD_CHECK_ARG((long long)B * H * W * x_pitch * 4 < (1ll << 32) - (1ll << 30));
-  SQD_CHECK_ARG((long long)(C >> 3) * 16 * Npad_total * 8 * 4 < (1ll << 32));
   const int cap = cfg_id / 1000; cfg_id %= 1000;
   WinoArgs a{};
-  a.x = x; a.u = u_packed; a.y = y;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.N = N3; a.Npad = Npad_total; a.y_pitch = y_pitch; a.y_coff = y_coff; a.relu = 1; a.wg_cap = cap;
+  wino_fill_args(a, x, u_packed, y, B, H, W, C, x_pitch, x_coff, N3, Npad_total, y_pitch, y_coff, 1);
+  a.wg_cap = cap;
   a.N1 = N1; a.nslices3 = sqd_cdiv(N3, 32);
   a.br_w = sq_ops; a.br_bias = bias_tab; a.br_sqb = sq_bias; a.br_nsq = Nsq;
   hipStream_t s = (hipStream_t)stream;
@@ -1180,20 +921,14 @@ extern "C" int sqd_fire_bridge_save_fwd(const float* x, const float* u_packed, c
                                         void* stream) {
   SQD_CHECK_ARG(x && u_packed && bias_tab && sq_ops && y && save && B > 0 && H > 0 && W > 0 && C > 0 && N3 > 0 && N1 > 0 && Nsq > 0);
   SQD_CHECK_ARG(C % 8 == 0 && C <= 16 && N3 % 4 == 0 && N1 % 16 == 0 && Nsq % 4 == 0 && Nsq <= 32);
-  SQD_CHECK_ARG(x_pitch % 4 == 0 && x_coff % 4 == 0 && y_pitch % 4 == 0 && y_coff % 4 == 0);
+  const int widest = x_pitch > y_pitch ? (x_pitch > save_pitch ? x_pitch : save_pitch) : (y_pitch > save_pitch ? y_pitch : save_pitch);
+  if (int rc = wino_check_common(B, H, W, C, x_pitch, x_coff, Nsq, Npad_total, y_pitch, y_coff, widest)) return rc;
   SQD_CHECK_ARG(save_pitch % 4 == 0 && save_coff3 % 4 == 0 && save_coff1 % 4 == 0);
-  SQD_CHECK_ARG(x_coff >= 0 && x_coff + C <= x_pitch && y_coff >= 0 && y_coff + Nsq <= y_pitch);
   SQD_CHECK_ARG(save_coff3 >= 0 && save_coff3 + N3 <= save_pitch && save_coff1 >= 0 && save_coff1 + N1 <= save_pitch);
   SQD_CHECK_ARG(save_coff3 + N3 <= save_coff1 || save_coff1 + N1 <= save_coff3);
   SQD_CHECK_ARG(Npad_total == sqd_cdiv(N3, 32) * 32 + sqd_cdiv(N1, 128) * 32);
-  const int widest = x_pitch > y_pitch ? (x_pitch > save_pitch ? x_pitch : save_pitch) : (y_pitch > save_pitch ? y_pitch : save_pitch);
-  SQD_CHECK_ARG((long long)W * 6 * widest * 4 < (1ll << 30));
-  SQD_CHECK_ARG((long long)B * H * W * x_pitch * 4 < (1ll << 32) - (1ll << 30));
-  SQD_CHECK_ARG((long long)(C >> 3) * 16 * Npad_total * 8 * 4 < (1ll << 32));
   WinoArgs a{};
-  a.x = x; a.u = u_packed; a.y = y;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.N = N3; a.Npad = Npad_total; a.y_pitch = y_pitch; a.y_coff = y_coff; a.relu = 1;
+  wino_fill_args(a, x, u_packed, y, B, H, W, C, x_pitch, x_coff, N3, Npad_total, y_pitch, y_coff, 1);
   a.N1 = N1; a.nslices3 = sqd_cdiv(N3, 32);
   a.br_w = sq_ops; a.br_bias = bias_tab; a.br_sqb = sq_bias; a.br_nsq = Nsq;
   a.sv = save; a.sv_pitch = save_pitch; a.sv_coff = save_coff3; a.sv_coff1 = save_coff1;
@@ -1211,21 +946,18 @@ static int fire_pool_bridge_impl(const float* x, const float* u_packed, const fl
                                         int Nsq, int Hp, int Wp, int y_pitch, int y_coff, int nseg, void* stream) {
   SQD_CHECK_ARG(x && u_packed && bias_tab && sq_ops && y && B > 0 && H >= 3 && W >= 3 && C > 0 && N3 > 0 && N1 > 0 && Nsq > 0);
   SQD_CHECK_ARG(C % 8 == 0 && N3 % 4 == 0 && N1 % 16 == 0 && Nsq % 4 == 0 && Nsq <= 32);
-  SQD_CHECK_ARG(x_pitch % 4 == 0 && x_coff % 4 == 0 && y_pitch % 4 == 0 && y_coff % 4 == 0);
-  SQD_CHECK_ARG(x_coff >= 0 && x_coff + C <= x_pitch && y_coff >= 0 && y_coff + Nsq <= y_pitch);
+  // (only x is addressed per group; y is the pooled geometry and the walk runs past the image: its own bounds below)
+  if (int rc = wino_check_common(B, H, W, C, x_pitch, x_coff, Nsq, Npad_total, y_pitch, y_coff, x_pitch)) return rc;
   SQD_CHECK_ARG(Npad_total == sqd_cdiv(N3, 32) * 32 + sqd_cdiv(N1, 128) * 32);
   int hp = (H - 2) / 2 + 1, wp = (W - 2) / 2 + 1;            // ceil((n - 3) / 2) + 1, last window must start inside the map
   if ((hp - 1) * 2 >= H) --hp;
   if ((wp - 1) * 2 >= W) --wp;
   SQD_CHECK_ARG(Hp == hp && Wp == wp);
-  SQD_CHECK_ARG((long long)W * 6 * x_pitch * 4 < (1ll << 30) && (long long)(Wp + 8) * 2 * y_pitch * 4 < (1ll << 30));
+  SQD_CHECK_ARG((long long)(Wp + 8) * 2 * y_pitch * 4 < (1ll << 30));
   SQD_CHECK_ARG((long long)B * (H + 8) * W * x_pitch * 4 < (1ll << 32) - (1ll << 30));
   SQD_CHECK_ARG((long long)B * (Hp + 2) * Wp * y_pitch * 4 < (1ll << 32) - (1ll << 30));
-  SQD_CHECK_ARG((long long)(C >> 3) * 16 * Npad_total * 8 * 4 < (1ll << 32));
   WinoArgs a{};
-  a.x = x; a.u = u_packed; a.y = y;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.N = N3; a.Npad = Npad_total; a.y_pitch = y_pitch; a.y_coff = y_coff; a.relu = 1;
+  wino_fill_args(a, x, u_packed, y, B, H, W, C, x_pitch, x_coff, N3, Npad_total, y_pitch, y_coff, 1);
   a.N1 = N1;
   a.br_w = sq_ops; a.br_bias = bias_tab; a.br_sqb = sq_bias; a.br_nsq = Nsq;
   a.pb_hp = Hp; a.pb_wp = Wp;

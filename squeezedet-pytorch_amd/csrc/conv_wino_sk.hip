@@ -21,6 +21,7 @@
 //     (cdna_hip_programming.md section 5 "in-launch split-K reduction" / Guideline 16; no wave ever waits for another workgroup,
 //     so the kernel cannot deadlock whatever the residency).  The last arriver returns the counter to zero.
 #include "sqd_common.h"
+#include "wino_tile.h"
 #include <type_traits>
 #include <algorithm>
 #include <stdlib.h>
@@ -62,12 +63,6 @@ __device__ __forceinline__ SkSeg sk_load_seg(const SkSeg* p) {
   return s;
 }
 
-__device__ __forceinline__ f32x4 sk_relu4(f32x4 v, float lo) {
-  asm volatile("v_max_f32 %0, %4, %0\n\tv_max_f32 %1, %4, %1\n\tv_max_f32 %2, %4, %2\n\tv_max_f32 %3, %4, %3"
-               : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w) : "s"(lo));
-  return v;
-}
-
 // NT 16-channel blocks per slice, GW groups per wave (NT * GW == 2).  FULL: the epilogue options of the backward and of training
 // (accumulate, ymul, yscale, dropout, ymask); the plain instantiation (bias + optional ReLU: every inference launch) keeps them out
 // of its register budget.
@@ -77,7 +72,6 @@ __device__ __forceinline__ void wino_sk_body(const WinoSkArgs& a, int sidx, cons
   constexpr int WV = 4;
   constexpr int NTHR = WV * 64;
   constexpr int BN = 16 * NT;
-  constexpr int RP = 113;                     // slots per k-quad plane of a raw patch (108 used)
   constexpr int RAW_IT = 4;                   // 256 slots per patch
   constexpr int USLOTS = 32 * BN;
   constexpr int U_IT = USLOTS / NTHR;         // 4 (F) / 2 (H)
@@ -92,18 +86,10 @@ __device__ __forceinline__ void wino_sk_body(const WinoSkArgs& a, int sidx, cons
   const int lr = lane & 15, g = lane >> 4;
   const int wv_s = __builtin_amdgcn_readfirstlane(wv);
 
-  constexpr unsigned OOB = 0x80000000u;
   int r_offB[RAW_IT], r_key[RAW_IT];
 #pragma unroll
-  for (int it = 0; it < RAW_IT; ++it) {
-    const int slot = it * 64 + lane;
-    const int kq = slot / RP, pix = slot - kq * RP;
-    const bool real = kq < 2 && pix < 108;
-    const int r = pix / 18, c = pix - r * 18;
-    r_key[it] = real ? (r << 8 | c) : -1;
-    r_offB[it] = real ? ((r * a.W + c) * a.x_pitch + 4 * kq) * 4 : 0;
-  }
-  int u_offB[U_IT];                                           // (slice origin n0 and K chunk ride in the SGPR offset)
+  for (int it = 0; it < RAW_IT; ++it) wino_patch_slot(it * 64 + lane, a.W, a.x_pitch, r_offB[it], r_key[it]);
+  int u_offB[U_IT];                                          // (slice origin n0 and K chunk ride in the SGPR offset)
 #pragma unroll
   for (int it = 0; it < U_IT; ++it) {
     const int slot = it * NTHR + tid;
@@ -115,36 +101,11 @@ __device__ __forceinline__ void wino_sk_body(const WinoSkArgs& a, int sidx, cons
       (void*)(a.x + a.x_coff - (long long)(a.W + 1) * a.x_pitch), 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t ures = __builtin_amdgcn_make_buffer_rsrc((void*)a.u, 0, 0x7ffffff0, 0x00020000);
 
-  struct GPos { int y0, x0, inner, valid; long long p0; unsigned soff; };
-  auto group_pos = [&](int t, int gw) {                      // group gw of this wave in super-group t (all wave-uniform)
-    GPos gp;
-    int q = (t * WV + wv_s) * GW + gw;
-    gp.valid = (int)((unsigned)(q - a.ngroups) >> 31);
-    q = gp.valid ? q : a.ngroups - 1;                        // idle slots of the last super-group redo the last group (never stored)
-    const int q1 = a.gxn_m ? (int)__umulhi((unsigned)q, a.gxn_m) : q;
-    const int gxi = q - q1 * a.gxn;
-    const int b = a.gyn_m ? (int)__umulhi((unsigned)q1, a.gyn_m) : q1;
-    const int gyi = q1 - b * a.gyn;
-    gp.y0 = gyi * 4; gp.x0 = gxi * 16;
-    gp.p0 = ((long long)b * a.H + gp.y0) * a.W + gp.x0;
-    gp.soff = (unsigned)(gp.p0 * a.x_pitch * 4);
-    gp.inner = (int)(((unsigned)(-gp.y0) & (unsigned)(gp.y0 + 4 - a.H) & (unsigned)(-gp.x0) & (unsigned)(gp.x0 + 16 - a.W)) >> 31);
-    return gp;
-  };
+  typedef WinoGPos GPos;
+  // group gw of this wave in super-group t (GW groups per wave: every per-group array below has a gw axis)
+  auto group_pos = [&](int t, int gw) { return wino_group_pos(a, (t * WV + wv_s) * GW + gw); };
   int r_offG[GW][RAW_IT];                                     // per-lane patch offsets of the groups whose stages are being fetched
-  auto group_offsets = [&](int gw, const GPos gp) {
-    if (gp.inner) {
-#pragma unroll
-      for (int it = 0; it < RAW_IT; ++it) r_offG[gw][it] = r_offB[it];
-      return;
-    }
-#pragma unroll
-    for (int it = 0; it < RAW_IT; ++it) {
-      const int key = r_key[it];
-      const bool ok = key >= 0 && (unsigned)(gp.y0 + (key >> 8) - 1) < (unsigned)a.H && (unsigned)(gp.x0 + (key & 255) - 1) < (unsigned)a.W;
-      r_offG[gw][it] = ok ? r_offB[it] : (int)OOB;
-    }
-  };
+  auto group_offsets = [&](int gw, const GPos gp) { wino_group_offsets<RAW_IT>(gp.y0, gp.x0, gp.inner, a.H, a.W, r_offB, r_key, r_offG[gw]); };
   float* const rawW = rawB + wv_s * GW * 256 * 4;            // this wave's raw patches
   auto dma_raw_one = [&](int gw, int it, unsigned soff) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_ptr_sk_t)(rawW + (gw * 256 + it * 64) * 4), 16, r_offG[gw][it], (int)soff, 0, 0);
@@ -164,8 +125,7 @@ __device__ __forceinline__ void wino_sk_body(const WinoSkArgs& a, int sidx, cons
 
   const int ty = lr >> 3, tx = lr & 7;
   const float relu_lo = a.relu ? 0.f : -__builtin_inff();
-  const int tt = lr, cp = g;
-  const float* const rawL = rawW + (((cp >> 1) * RP + (2 * (tt >> 3)) * 18 + 2 * (tt & 7)) * 4 + 2 * (cp & 1));
+  const float* const rawL = rawW + (((g >> 1) * WINO_RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
   const float* const uR0 = UB + g * 64 + lr * 4;
   f32x4* const parkW = (f32x4*)(VB + wv_s * 2048) + lane;    // slot k = (gw * 4 + px) * NT + j
 
@@ -185,7 +145,7 @@ __device__ __forceinline__ void wino_sk_body(const WinoSkArgs& a, int sidx, cons
         v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
       }
     }
-    *(f32x4*)dst = sk_relu4(v, relu_lo);
+    *(f32x4*)dst = wino_relu4(v, relu_lo);
   };
   // partial slabs: buffer resource; stores and loads carry sc1 (aux 16): write-through, L1-bypassing
   const __amdgpu_buffer_rsrc_t wsres = __builtin_amdgcn_make_buffer_rsrc((void*)a.ws, 0, 0x7ffffff0, 0x00020000);
@@ -224,7 +184,7 @@ __device__ __forceinline__ void wino_sk_body(const WinoSkArgs& a, int sidx, cons
     for (int k = 0; k < 8; ++k) {
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_sk, parkW[k * 64]), wsres, lane * 16 + k * 1024, (int)slabB, 16);
       __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_nop 1" ::: "memory");                  // (SGPR-soffset 16-byte store followed by a write of its data register: conv_wino.hip)
+      asm volatile("s_nop 1" ::: "memory");                  // (wino_store16's hazard; this store carries sc1, so it is written out here)
       __builtin_amdgcn_sched_barrier(0);
     }
     return true;
@@ -312,21 +272,7 @@ __device__ __forceinline__ void wino_sk_body(const WinoSkArgs& a, int sidx, cons
       for (int gw = 0; gw < GW; ++gw) {
         // ---- input transform: V = B^T d B for (tile tt, channels 2cp, 2cp+1) of group gw ----
         f32x2 vv[16];
-        {
-          const float* const rl = rawL + gw * 256 * 4;
-          f32x2 t[4][4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const f32x2 d0 = *(const f32x2*)(rl + (0 * 18 + j) * 4), d1 = *(const f32x2*)(rl + (1 * 18 + j) * 4);
-            const f32x2 d2 = *(const f32x2*)(rl + (2 * 18 + j) * 4), d3 = *(const f32x2*)(rl + (3 * 18 + j) * 4);
-            t[0][j] = d0 - d2; t[1][j] = d1 + d2; t[2][j] = d2 - d1; t[3][j] = d1 - d3;
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            vv[i * 4 + 0] = t[i][0] - t[i][2]; vv[i * 4 + 1] = t[i][1] + t[i][2];
-            vv[i * 4 + 2] = t[i][2] - t[i][1]; vv[i * 4 + 3] = t[i][1] - t[i][3];
-          }
-        }
+        wino_input_transform(rawL + gw * 256 * 4, vv);
         // The patch buffer is refilled (LDS-DMA, below) for the next stage: its reads above must have returned, and neither
         // the compiler nor the machine scheduler may move a DMA issue across this point.
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -396,24 +342,8 @@ __device__ __forceinline__ void wino_sk_body(const WinoSkArgs& a, int sidx, cons
         for (int gw = 0; gw < GW; ++gw)
 #pragma unroll
           for (int j = 0; j < NT; ++j) {
-            auto inv = [&](auto half, auto put) {             // on register pairs: packed adds
-              f32x2 s[4][2];
-#pragma unroll
-              for (int xi = 0; xi < 4; ++xi) {
-                const f32x2 m0 = half(acc[gw][xi * 4 + 0][j]), m1 = half(acc[gw][xi * 4 + 1][j]);
-                const f32x2 m2 = half(acc[gw][xi * 4 + 2][j]), m3 = half(acc[gw][xi * 4 + 3][j]);
-                s[xi][0] = m0 + m1 + m2;
-                s[xi][1] = m1 - (m2 + m3);
-              }
-#pragma unroll
-              for (int b = 0; b < 2; ++b) {
-                put(0 * 2 + b, s[0][b] + s[1][b] + s[2][b]);
-                put(1 * 2 + b, s[1][b] - (s[2][b] + s[3][b]));
-              }
-            };
             f32x4 ov[4];
-            inv([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 y) { ov[px].lo = y; });
-            inv([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 y) { ov[px].hi = y; });
+            wino_inverse(acc[gw], j, ov);
 #pragma unroll
             for (int px = 0; px < 4; ++px) parkW[((gw * 4 + px) * NT + j) * 64] = ov[px];     // lane-contiguous 16-byte slots: conflict-free
           }
@@ -553,18 +483,8 @@ extern "C" int sqd_wino_sk_schedule(int ngroups, int N, int C, int G, int minseg
   return SQD_OK;
 }
 
-static int sk_num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 // Workgroups of one launch: every resident slot of the device (two 80 KB workgroups per CU); the schedule is built for it.
-extern "C" int sqd_wino_sk_grid(void) { return 2 * sk_num_cus(); }
+extern "C" int sqd_wino_sk_grid(void) { return 2 * sqd_num_cus(); }
 
 // y[..., y_coff : y_coff + N] (=|+=) conv3x3(x[..., x_coff : x_coff + C]) (+ bias) (* ymul) (* yscale) (zero where ymask <= 0) (ReLU).
 // u_packed / Npad: sqd_pack_wino_weight with 32-channel padding.  seg_off [G + 1] / segs [nsegs][8]: device copies of what
@@ -580,11 +500,7 @@ extern "C" int sqd_conv_wino_sk_fwd(const float* x, const float* u_packed, const
   SQD_CHECK_ARG(x && u_packed && y && seg_off && segs && G > 0 && nslabs >= 0 && (nslabs == 0 || (ws && cnt)));
   SQD_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && N > 0);
   SQD_CHECK_ARG(C % 8 == 0 && N % 4 == 0 && Npad >= N && Npad % 32 == 0);
-  SQD_CHECK_ARG(x_pitch % 4 == 0 && x_coff % 4 == 0 && y_pitch % 4 == 0 && y_coff % 4 == 0);
-  SQD_CHECK_ARG(x_coff >= 0 && x_coff + C <= x_pitch && y_coff >= 0 && y_coff + N <= y_pitch);
-  SQD_CHECK_ARG((long long)W * 6 * (x_pitch > y_pitch ? x_pitch : y_pitch) * 4 < (1ll << 30));
-  SQD_CHECK_ARG((long long)B * H * W * x_pitch * 4 < (1ll << 32) - (1ll << 30));
-  SQD_CHECK_ARG((long long)(C >> 3) * 16 * Npad * 8 * 4 < (1ll << 32));
+  if (int rc = wino_check_common(B, H, W, C, x_pitch, x_coff, N, Npad, y_pitch, y_coff, x_pitch > y_pitch ? x_pitch : y_pitch)) return rc;
   SQD_CHECK_ARG((long long)nslabs * 4 * 8192 < (1ll << 32) - (1ll << 30));
   WinoSkArgs a{};
   a.x = x; a.u = u_packed; a.bias = bias; a.y = y;
@@ -593,6 +509,7 @@ extern "C" int sqd_conv_wino_sk_fwd(const float* x, const float* u_packed, const
   a.ymask = ymask; a.ymul = ymul; a.yscale = yscale;
   SQD_CHECK_ARG(!drop_state || (drop_keep16 >= 0 && drop_keep16 <= 65536));
   a.drop_state = drop_state; a.drop_keep = drop_keep16; a.drop_scale = drop_scale; a.drop_advance = drop_advance;
+  // (idle slots reach ngroups + 16 with two groups per wave, and there is no super-group count: not wino_launch_geometry)
   a.gxn = sqd_cdiv(W, 16); a.gyn = sqd_cdiv(H, 4);
   a.ngroups = B * a.gxn * a.gyn;
   if ((long long)(a.ngroups + 16) * (a.gxn > a.gyn ? a.gxn : a.gyn) >= (1ll << 32)) return SQD_ERR_UNSUPPORTED;

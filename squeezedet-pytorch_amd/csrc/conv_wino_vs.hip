@@ -24,15 +24,9 @@
 //     the transform of chunk c + 1.
 // Arithmetic per output element is that of conv_wino_kernel (same transforms, same k order): bit-identical results.
 #include "sqd_common.h"
+#include "wino_tile.h"
 #include <type_traits>
-#ifndef SQD_VS_DIAG
-#define SQD_VS_DIAG 0             /* ablation builds only (scratch/diag/vs_diag.sh; never in libsqdhip.so): bit 0 = no input transform,
-                                     1 = no patch DMA inside the chunk loop, 2 = no stage barrier, 3 = U operands not loaded in the loop */
-#endif
 /* (s_setprio for the duty wave behind its transform measured slower, 186 vs 174 us, and is gone.) */
-#ifndef SQD_VS_ENTRY
-#define SQD_VS_ENTRY sqd_conv_wino_vs_fwd
-#endif
 
 struct WinoVsArgs {
   const float* x; const float* u; const float* bias; float* y;
@@ -57,7 +51,6 @@ static_assert(VS_LDS == 112 * 1024, "64 KB of V + 48 KB of wave-private patches:
 
 __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int RP = 113;                     // slots per k-quad plane of the raw patch (as conv_wino_kernel: planes interleave in the bank row)
   constexpr int RAW_IT = 4;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* const VB = smem;                                   // [VS_SLOTS][2][VS_VFL]
@@ -81,20 +74,21 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
   int w_hi = (grp == a.ngroups - 1) ? VS_WV : (grp + 1) * VS_NB - u0; w_hi = w_hi > VS_WV ? VS_WV : w_hi;
   const int nw = w_hi - w_lo, rank = wv - w_lo;
 
-  // ---- group geometry (wave-uniform, once) ----
+  // ---- group geometry (wave-uniform, once per kernel: plain divisions, not wino_group_pos's multiply-highs) ----
   const int q1 = grp / a.gxn, gxi = grp - q1 * a.gxn;
   const int b = q1 / a.gyn, gyi = q1 - b * a.gyn;
   const int y0 = gyi * 4, x0 = gxi * 16;
   const long long p0 = ((long long)b * a.H + y0) * a.W + x0;
   const unsigned soff0 = (unsigned)(p0 * a.x_pitch * 4);    // byte offset of the patch origin from the resource base (host-checked < 3 GiB)
 
-  // ---- per-lane DMA slots of the patch (fixed for the kernel: the wave's group never changes) ----
-  constexpr unsigned OOB = 0x80000000u;
+  // ---- per-lane DMA slots of the patch (fixed for the kernel: the wave's group never changes, so the slot and its range
+  // check are one step: not wino_patch_slot + wino_group_offsets) ----
+  constexpr unsigned OOB = WINO_OOB;
   int r_off[RAW_IT];
 #pragma unroll
   for (int it = 0; it < RAW_IT; ++it) {
     const int s = it * 64 + lane;
-    const int kq = s / RP, pix = s - kq * RP;
+    const int kq = s / WINO_RP, pix = s - kq * WINO_RP;
     const bool real = kq < 2 && pix < 108;
     const int r = pix / 18, c = pix - r * 18;
     const bool ok = real && (unsigned)(y0 + r - 1) < (unsigned)a.H && (unsigned)(x0 + c - 1) < (unsigned)a.W;
@@ -106,7 +100,6 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
   float* const rawS = RB + wv * VS_RFL;                     // this wave's own patch image
   float* const vS = VB + slot * 2 * VS_VFL;
   auto dma_raw = [&](int cc) {                               // the patch of chunk cc -> this wave's raw image
-    if ((SQD_VS_DIAG & 2) && cc >= 2 * nw) return;
 #pragma unroll
     for (int it = 0; it < RAW_IT; ++it)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_ptr_vs_t)(rawS + it * 64 * 4), 16, r_off[it], (int)(soff0 + (unsigned)cc * 32u), 0, 0);
@@ -119,8 +112,9 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
   };
 
   // ---- transform unit of a lane = its MFMA B-operand role: tile lr, channel pair g of the chunk ----
-  const float* const rawL = rawS + (((g >> 1) * RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
+  const float* const rawL = rawS + (((g >> 1) * WINO_RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
   // raw image -> V[vbuf] of this group (whole wave); the image is re-requested for chunk `next_cc` (< 0: not) as soon as it has been read
+  // (the DMA re-request sits between the column and the row transform, and V goes to LDS: not wino_input_transform)
   auto transform = [&](int vbuf, int next_cc) {
     f32x2 t[4][4];
 #pragma unroll
@@ -134,7 +128,6 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
     __builtin_amdgcn_sched_barrier(0);
     if (next_cc >= 0) dma_raw(next_cc);
     __builtin_amdgcn_sched_barrier(0);
-    if (SQD_VS_DIAG & 1) return;
     f32x4* const vdst = (f32x4*)(vS + vbuf * VS_VFL) + lane;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -204,13 +197,13 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
       __builtin_amdgcn_sched_barrier(0);
       // the same position pair of the next chunk: one interval of latency budget.  Issued UNCONDITIONALLY (the last interval re-reads
       // its own chunk): behind a branch the compiler's wait-count bookkeeping assumes the loads absent and drains them at every step
-      if (!(SQD_VS_DIAG & 8)) uq[pp] = load_u(nc, pp);
+      uq[pp] = load_u(nc, pp);
       __builtin_amdgcn_sched_barrier(0);
     }
     // V(cc + 1) written (duty wave) and V(cc) read (everyone) before the barrier publishes one and frees the other; the U loads and
     // patch requests in flight stay in flight (a raw s_barrier: __syncthreads() would drain the vector memory queue)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!(SQD_VS_DIAG & 4)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
   };
   interval(0, std::true_type{});
   for (int cc = 1; cc < nchunks; ++cc) interval(cc, std::false_type{});
@@ -220,22 +213,7 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
   const int ty = lr >> 3, tx = lr & 7;
   const float relu_lo = a.relu ? 0.f : -__builtin_inff();
   f32x4 ov[4];
-  auto inv = [&](auto half, auto put) {
-    f32x2 s[4][2];
-#pragma unroll
-    for (int xi = 0; xi < 4; ++xi) {
-      const f32x2 m0 = half(acc[xi * 4 + 0]), m1 = half(acc[xi * 4 + 1]), m2 = half(acc[xi * 4 + 2]), m3 = half(acc[xi * 4 + 3]);
-      s[xi][0] = m0 + m1 + m2;
-      s[xi][1] = m1 - (m2 + m3);
-    }
-#pragma unroll
-    for (int bb = 0; bb < 2; ++bb) {
-      put(0 * 2 + bb, s[0][bb] + s[1][bb] + s[2][bb]);
-      put(1 * 2 + bb, s[1][bb] - (s[2][bb] + s[3][bb]));
-    }
-  };
-  inv([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 yv) { ov[px].lo = yv; });
-  inv([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 yv) { ov[px].hi = yv; });
+  wino_inverse(acc, ov);
   const int n = blk * 16 + 4 * g;
   if (n >= a.N) return;
   float* const ybase = a.y + p0 * a.y_pitch + a.y_coff + n;
@@ -252,15 +230,12 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
 
 // y[..., y_coff : y_coff + N] = (ReLU)(conv3x3(x[..., x_coff : x_coff + C]) + bias), N <= 80, u_packed = sqd_pack_wino_weight output with
 // Npad = 80 (C/8 * 16 * 80 * 8 floats).  Same results, bit for bit, as sqd_conv_wino_fwd.
-extern "C" int SQD_VS_ENTRY(const float* x, const float* u_packed, const float* bias, float* y, int B, int H, int W, int C,
+extern "C" int sqd_conv_wino_vs_fwd(const float* x, const float* u_packed, const float* bias, float* y, int B, int H, int W, int C,
                                     int x_pitch, int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu, void* stream) {
   SQD_CHECK_ARG(x && u_packed && y && B > 0 && H > 0 && W > 0 && C > 0 && N > 0);
   SQD_CHECK_ARG(C % 8 == 0 && N % 4 == 0 && N <= 16 * VS_NB && Npad == 16 * VS_NB);
-  SQD_CHECK_ARG(x_pitch % 4 == 0 && x_coff % 4 == 0 && y_pitch % 4 == 0 && y_coff % 4 == 0);
-  SQD_CHECK_ARG(x_coff >= 0 && x_coff + C <= x_pitch && y_coff >= 0 && y_coff + N <= y_pitch);
-  SQD_CHECK_ARG((long long)W * 6 * x_pitch * 4 < (1ll << 30));                                    // per-lane byte offsets inside a patch
-  SQD_CHECK_ARG((long long)B * H * W * x_pitch * 4 < (1ll << 32) - (1ll << 30));                  // 32-bit SGPR byte offset of a group origin
-  SQD_CHECK_ARG((long long)(C >> 3) * VS_UFL * 4 < (1ll << 32));
+  // (y is stored through flat pointers: only x is addressed per lane; Npad = 80, so the U bound is (C/8) * VS_UFL * 4)
+  if (int rc = wino_check_common(B, H, W, C, x_pitch, x_coff, N, Npad, y_pitch, y_coff, x_pitch)) return rc;
   WinoVsArgs a{};
   a.x = x; a.u = u_packed; a.bias = bias; a.y = y;
   a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;

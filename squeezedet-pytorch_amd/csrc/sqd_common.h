@@ -21,6 +21,17 @@ static inline int sqd_launch_status() {
 
 static inline int sqd_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Compute units of the current device (asked once; 256 where the query fails): persistent kernels size their grids by it.
+static inline int sqd_num_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0; hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+    if (cus <= 0) cus = 256;
+  }
+  return cus;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the device that is current at the call: kernels that need more than 64 KB of
 // LDS set it once PER DEVICE (a process may launch on several: reference-style DataParallel, tests that switch devices).  Idempotent,
 // so two threads racing through the first launch on a device is harmless.

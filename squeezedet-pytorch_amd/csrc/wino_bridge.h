@@ -3,8 +3,9 @@
 // written and read again at 1248x384 bs=20 -- never exists (reference: src/model/squeezedet.py:18-22, Fire.forward twice:
 // cat(relu(e1(s)), relu(e3(s))) -> relu(squeeze'(.)); inference only, the training forward keeps every activation).
 //
-// Built on the deep-prefetch Winograd machinery above (wave-private patch ring filled by LDS-DMA, counted vmcnt waits,
-// 16 tiles x 32 channels x 16 positions per wave in 32 accumulators).  One wave takes a 4x16-pixel group through P
+// Built on the U-stationary Winograd machinery above (U resident in LDS behind one barrier, wave-private two-deep patch ring
+// filled by LDS-DMA, counted vmcnt waits, stores straight from registers; 16 tiles x 32 channels x 16 positions per wave in
+// 32 accumulators).  One wave takes a 4x16-pixel group through P
 // "passes": the expand3x3 slices (32 channels each), then the expand1x1 slices in Winograd form (128 channels x the four
 // inner positions, see wino_pipe_body).  Behind the last chunk of a pass the accumulators are inverse-transformed, get
 // their ReLU and -- instead of being stored -- are multiplied into the next squeeze: the inverse transform leaves lane
@@ -12,17 +13,17 @@
 // (k = g, column = tile) of v_mfma_f32_16x16x4_f32 for input channel 4g + t, t = 0..3; the A operand is the matching
 // column of the squeeze weights, pre-arranged by the host (sq_ops[block][t][q][lane]).  Four more accumulators per 16
 // squeeze channels collect the result over all passes; bias + ReLU + one 16-byte store per pixel finish the group.
-// The patch of a chunk is re-requested for every pass (L2 hits); U is resident (USTAT) or streamed through the ring.
+// The patch of a chunk is re-requested for every pass (L2 hits); the U of every pass is resident (USTAT: see wino_pipe_body).
 template <int WV, bool USTAT, int NSQ>
 __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
+  static_assert(USTAT, "streamed-U form retired");
   constexpr int NT = 2;
   constexpr int NTHR = WV * 64;
   constexpr int BN = 16 * NT;
-  constexpr int RP = 113;
   constexpr int RAW_IT = 4;
   constexpr int USLOTS = 32 * BN;
   constexpr int U_IT = USLOTS / NTHR;
-  constexpr int NDMA = RAW_IT + (USTAT ? 0 : U_IT);
+  constexpr int NDMA = RAW_IT;
   constexpr int NSTB = 4 * NSQ;                // store instructions of a whole group
   constexpr int NSTEP = 8;
   constexpr int RAW_STEPS = 4;
@@ -30,8 +31,8 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
   const int P = a.nslices, P3 = a.nslices3;
   const int nchunks = a.C >> 3;
   float* const rawB = smem;                                         // [2][WV][256][4]
-  float* const UB = rawB + 2 * WV * 256 * 4;                        // [3 | P * C/8][USLOTS][4]
-  float* const sqAL = UB + (USTAT ? P * nchunks : 3) * USLOTS * 4;  // [blocks][4 t][NSQ][64 lanes]
+  float* const UB = rawB + 2 * WV * 256 * 4;                        // [P * C/8][USLOTS][4]
+  float* const sqAL = UB + P * nchunks * USLOTS * 4;                // [blocks][4 t][NSQ][64 lanes]
   const int nblk = 2 * P3 + 8 * (P - P3);
   float* const biasL = sqAL + nblk * 4 * NSQ * 64;                  // [P][8 blocks][16]
 
@@ -43,17 +44,9 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
   if (tile >= ntiles) return;
   const int wv_s = __builtin_amdgcn_readfirstlane(wv);
 
-  constexpr unsigned OOB = 0x80000000u;
   int r_offB[RAW_IT], r_key[RAW_IT];
 #pragma unroll
-  for (int it = 0; it < RAW_IT; ++it) {
-    const int slot = it * 64 + lane;
-    const int kq = slot / RP, pix = slot - kq * RP;
-    const bool real = kq < 2 && pix < 108;
-    const int r = pix / 18, c = pix - r * 18;
-    r_key[it] = real ? (r << 8 | c) : -1;
-    r_offB[it] = real ? ((r * a.W + c) * a.x_pitch + 4 * kq) * 4 : 0;
-  }
+  for (int it = 0; it < RAW_IT; ++it) wino_patch_slot(it * 64 + lane, a.W, a.x_pitch, r_offB[it], r_key[it]);
   int u_offB[U_IT];
 #pragma unroll
   for (int it = 0; it < U_IT; ++it) {
@@ -66,41 +59,15 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
       (void*)(a.x + a.x_coff - (long long)(a.W + 1) * a.x_pitch), 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t ures = __builtin_amdgcn_make_buffer_rsrc((void*)a.u, 0, 0x7ffffff0, 0x00020000);
 
-  struct GPos { int y0, x0, inner, valid; long long p0; unsigned soff; };
-  auto group_pos = [&](int t) {
-    GPos gp;
-    int q = t * WV + wv_s;
-    gp.valid = (int)((unsigned)(q - a.ngroups) >> 31);
-    q = gp.valid ? q : a.ngroups - 1;
-    const int q1 = a.gxn_m ? (int)__umulhi((unsigned)q, a.gxn_m) : q;
-    const int gxi = q - q1 * a.gxn;
-    const int b = a.gyn_m ? (int)__umulhi((unsigned)q1, a.gyn_m) : q1;
-    const int gyi = q1 - b * a.gyn;
-    gp.y0 = gyi * 4; gp.x0 = gxi * 16;
-    gp.p0 = ((long long)b * a.H + gp.y0) * a.W + gp.x0;
-    gp.soff = (unsigned)(gp.p0 * a.x_pitch * 4);
-    gp.inner = (int)(((unsigned)(-gp.y0) & (unsigned)(gp.y0 + 4 - a.H) & (unsigned)(-gp.x0) & (unsigned)(gp.x0 + 16 - a.W)) >> 31);
-    return gp;
-  };
+  typedef WinoGPos GPos;
+  auto group_pos = [&](int t) { return wino_group_pos(a, t * WV + wv_s); };
   int r_offG[RAW_IT];
-  auto group_offsets = [&](int y0, int x0, int inner) {
-    if (inner) {
-#pragma unroll
-      for (int it = 0; it < RAW_IT; ++it) r_offG[it] = r_offB[it];
-      return;
-    }
-#pragma unroll
-    for (int it = 0; it < RAW_IT; ++it) {
-      const int key = r_key[it];
-      const bool ok = key >= 0 && (unsigned)(y0 + (key >> 8) - 1) < (unsigned)a.H && (unsigned)(x0 + (key & 255) - 1) < (unsigned)a.W;
-      r_offG[it] = ok ? r_offB[it] : (int)OOB;
-    }
-  };
+  auto group_offsets = [&](int y0, int x0, int inner) { wino_group_offsets<RAW_IT>(y0, x0, inner, a.H, a.W, r_offB, r_key, r_offG); };
   float* const rawW = rawB + wv_s * 256 * 4;
   auto dma_raw_one = [&](int it, unsigned soff, int rb) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_ptr_w_t)(rawW + (rb * WV * 256 + it * 64) * 4), 16, r_offG[it], (int)soff, 0, 0);
   };
-  // U of (pass, chunk) into ring / resident slot `slot`; a pass is a 32-wide slice of the packed virtual channel axis
+  // U of (pass, chunk) into resident slot `slot`; a pass is a 32-wide slice of the packed virtual channel axis
   auto dma_u_one = [&](int it, int pass, int cc, int slot) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(ures, (lds_ptr_w_t)(UB + (slot * USLOTS + it * NTHR + wv_s * 64) * 4), 16, u_offB[it],
                                              (int)(cc * u_chunkB + (unsigned)pass * (BN * 64u)), 0, 0);
@@ -125,15 +92,7 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
 #pragma unroll
   for (int px = 0; px < 4; ++px) o_offB[px] = (((2 * ty + (px >> 1)) * a.W + 2 * tx + (px & 1)) * a.y_pitch + 4 * g) * 4;
   const __amdgpu_buffer_rsrc_t yres = __builtin_amdgcn_make_buffer_rsrc((void*)(a.y + a.y_coff), 0, 0x7ffffff0, 0x00020000);
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-  auto store16 = [&](f32x4 v, __amdgpu_buffer_rsrc_t res, int voff, int soff) {      // (hazard: see wino_pipe_body)
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), res, voff, soff, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  const int tt = lr, cp = g;
-  const int rawL_off = (((cp >> 1) * RP + (2 * (tt >> 3)) * 18 + 2 * (tt & 7)) * 4 + 2 * (cp & 1));
+  const int rawL_off = (((g >> 1) * WINO_RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
   const float* const uR0 = UB + g * 64 + lr * 4;
 
   // ---- prefetch cursor: two stages ahead of the compute cursor; a stage = (pass, chunk) of a tile ----
@@ -158,25 +117,19 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
   // squeeze operands + bias table into LDS (plain loads), the resident U by DMA; one barrier publishes all of it
   for (int i = tid; i < nblk * 4 * NSQ * 64; i += NTHR) sqAL[i] = a.br_w[i];
   for (int i = tid; i < P * 8 * 16; i += NTHR) biasL[i] = a.br_bias[i];
-  if (USTAT) {
-    for (int ps = 0; ps < P; ++ps)
-      for (int c = 0; c < nchunks; ++c)
+  for (int ps = 0; ps < P; ++ps)
+    for (int c = 0; c < nchunks; ++c)
 #pragma unroll
-        for (int it = 0; it < U_IT; ++it) dma_u_one(it, ps, c, ps * nchunks + c);
-  }
+      for (int it = 0; it < U_IT; ++it) dma_u_one(it, ps, c, ps * nchunks + c);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    if (!USTAT) {
-#pragma unroll
-      for (int it = 0; it < U_IT; ++it) dma_u_one(it, ppass, pcc, s);
-    }
 #pragma unroll
     for (int it = 0; it < RAW_IT; ++it) dma_raw_one(it, psoff + (unsigned)pcc * 32u, s);
     advance();
   }
-  int ub = 0, rb = 0;
+  int rb = 0;
   int stores_behind = 0;
 
   for (;;) {
@@ -191,17 +144,11 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
           if (sb == NSTB) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA + NSTB) : "memory");
           else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
         }
-        if (!USTAT) __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         stores_behind = 0;
         const bool last = cc + 1 == nchunks;
-        const int ub2 = (ub >= 1) ? ub - 1 : 2;
-        if (!USTAT) {
-#pragma unroll
-          for (int it = 0; it < U_IT; ++it) dma_u_one(it, ppass, pcc, ub2);
-        }
         const unsigned nsoff = psoff + (unsigned)pcc * 32u;
-        const float* const uR = uR0 + (USTAT ? pass * nchunks + cc : ub) * USLOTS * 4;
+        const float* const uR = uR0 + (pass * nchunks + cc) * USLOTS * 4;
         const float* const rawL = rawW + rb * WV * 256 * 4 + rawL_off;
         const float* const bL = biasL + pass * 128 + lr;
 
@@ -216,25 +163,8 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
 #pragma unroll
             for (int k = 0; k < (E1 ? (KIND == 2 ? 4 : 8) : 2); ++k) bA[k] = bL[k * 16];
           }
-          if constexpr (E1) {
-            const f32x2 d11 = *(const f32x2*)(rawL + (1 * 18 + 1) * 4), d12 = *(const f32x2*)(rawL + (1 * 18 + 2) * 4);
-            const f32x2 d21 = *(const f32x2*)(rawL + (2 * 18 + 1) * 4), d22 = *(const f32x2*)(rawL + (2 * 18 + 2) * 4);
-            const f32x2 t11 = d11 + d21, t12 = d12 + d22, t21 = d21 - d11, t22 = d22 - d12;
-            vv[5] = t11 + t12; vv[6] = t12 - t11; vv[9] = t21 + t22; vv[10] = t22 - t21;
-          } else {
-            f32x2 t[4][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const f32x2 d0 = *(const f32x2*)(rawL + (0 * 18 + j) * 4), d1 = *(const f32x2*)(rawL + (1 * 18 + j) * 4);
-              const f32x2 d2 = *(const f32x2*)(rawL + (2 * 18 + j) * 4), d3 = *(const f32x2*)(rawL + (3 * 18 + j) * 4);
-              t[0][j] = d0 - d2; t[1][j] = d1 + d2; t[2][j] = d2 - d1; t[3][j] = d1 - d3;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              vv[i * 4 + 0] = t[i][0] - t[i][2]; vv[i * 4 + 1] = t[i][1] + t[i][2];
-              vv[i * 4 + 2] = t[i][2] - t[i][1]; vv[i * 4 + 3] = t[i][1] - t[i][3];
-            }
-          }
+          if constexpr (E1) wino_input_transform_inner(rawL, vv);
+          else wino_input_transform(rawL, vv);
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_sched_barrier(0);
 
@@ -305,6 +235,7 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
           };
           if (is_e1) {
             const int bi0 = 2 * P3 + 8 * (pass - P3);
+            // (4-wide arithmetic on [16][2] accumulators, as wino_pipe_body's: not wino_inverse_inner's register pairs)
 #pragma unroll
             for (int blk = 0; blk < 8; ++blk) {
               if (e1_c0 + blk * 16 >= a.N1) continue;
@@ -317,24 +248,8 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
           } else {
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-              auto inv = [&](auto half, auto put) {
-                f32x2 sx[4][2];
-#pragma unroll
-                for (int xi = 0; xi < 4; ++xi) {
-                  const f32x2 m0 = half(acc[xi * 4 + 0][j]), m1 = half(acc[xi * 4 + 1][j]);
-                  const f32x2 m2 = half(acc[xi * 4 + 2][j]), m3 = half(acc[xi * 4 + 3][j]);
-                  sx[xi][0] = m0 + m1 + m2;
-                  sx[xi][1] = m1 - (m2 + m3);
-                }
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                  put(0 * 2 + b, sx[0][b] + sx[1][b] + sx[2][b]);
-                  put(1 * 2 + b, sx[1][b] - (sx[2][b] + sx[3][b]));
-                }
-              };
               f32x4 ov[4];
-              inv([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 y) { ov[px].lo = y; });
-              inv([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 y) { ov[px].hi = y; });
+              wino_inverse(acc, j, ov);
 #pragma unroll
               for (int px = 0; px < 4; ++px) ov[px] = wino_relu4(ov[px], 0.f);
               squeeze_in(2 * pass + j, ov);
@@ -351,7 +266,7 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
 #pragma unroll
                 for (int q = 0; q < NSQ; ++q) {
                   if (!valid || q * 16 + 4 * g >= a.br_nsq) continue;
-                  store16(wino_relu4(acc_sq[px][q], 0.f), yres, o_offB[px] + q * 64, ysoff);
+                  wino_store16(wino_relu4(acc_sq[px][q], 0.f), yres, o_offB[px] + q * 64, ysoff);
                 }
               }
               stores_behind = whole ? NSTB : 0;
@@ -362,7 +277,6 @@ __device__ __forceinline__ void wino_bridge_body(const WinoArgs& a) {
               for (int q = 0; q < NSQ; ++q) acc_sq[px][q] = sqb[q];
           }
         }
-        ub = (ub == 2) ? 0 : ub + 1;
         rb ^= 1;
       }
     }
@@ -385,7 +299,7 @@ static int launch_wino_bridge(WinoArgs a, hipStream_t stream) {
   constexpr int NTHR = WV * 64, USLOTS = 32 * 32;
   const int P = a.Npad / 32, nchunks = a.C >> 3;
   const int nblk = 2 * a.nslices3 + 8 * (P - a.nslices3);
-  const size_t lds = (size_t)(2 * WV * 256 * 4 + (USTAT ? P * nchunks : 3) * USLOTS * 4 + nblk * 4 * NSQ * 64 + P * 128) * sizeof(float);
+  const size_t lds = (size_t)(2 * WV * 256 * 4 + P * nchunks * USLOTS * 4 + nblk * 4 * NSQ * 64 + P * 128) * sizeof(float);
   if (lds > 160 * 1024) return SQD_ERR_UNSUPPORTED;
   auto kern = fire_bridge_kernel<WV, USTAT, NSQ>;
   if ((long long)a.B * a.H * a.W * a.y_pitch * 4 >= (1ll << 32) - (1ll << 30)) return SQD_ERR_UNSUPPORTED;
@@ -394,12 +308,9 @@ static int launch_wino_bridge(WinoArgs a, hipStream_t stream) {
   int nb = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, NTHR, lds) != hipSuccess || nb < 1) nb = 1;
   const int wgs_per_cu = nb > 4 ? 4 : nb;
-  a.gxn = sqd_cdiv(a.W, 16); a.gyn = sqd_cdiv(a.H, 4);
-  a.ngroups = a.B * a.gxn * a.gyn;
-  if ((long long)(a.ngroups + 8) * (a.gxn > a.gyn ? a.gxn : a.gyn) >= (1ll << 32)) return SQD_ERR_UNSUPPORTED;
-  a.gxn_m = a.gxn > 1 ? (unsigned)(((1ull << 32) + a.gxn - 1) / a.gxn) : 0u; a.gyn_m = a.gyn > 1 ? (unsigned)(((1ull << 32) + a.gyn - 1) / a.gyn) : 0u;
-  a.ntiles = sqd_cdiv(a.ngroups, WV);
-  const int slots = wino_num_cus() * ((a.wg_cap > 0 && a.wg_cap < wgs_per_cu) ? a.wg_cap : wgs_per_cu);
+  if (int rc = wino_launch_geometry(a, WV)) return rc;
+  // (one workgroup walks every pass of its groups: no slice axis and no rounding of the grid to 8, unlike wino_grid)
+  const int slots = sqd_num_cus() * ((a.wg_cap > 0 && a.wg_cap < wgs_per_cu) ? a.wg_cap : wgs_per_cu);
   const int per_wg = sqd_cdiv(a.ntiles, slots);
   const int gx = sqd_cdiv(a.ntiles, per_wg);
   a.nslices = P; a.gx = gx;
@@ -424,7 +335,7 @@ static int launch_wino_bridge(WinoArgs a, hipStream_t stream) {
 template <int NSQ, int MODE, int NCH>
 __device__ __forceinline__ void wino_bridge16_body(const WinoArgs& a) {
   constexpr bool SQZ = MODE != 0, STO = MODE != 1;
-  constexpr int WV = 8, NTHR = WV * 64, RP = 113, RAW_IT = 4, NSTB = 4 * NSQ;
+  constexpr int WV = 8, NTHR = WV * 64, RAW_IT = 4, NSTB = 4 * NSQ;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int P3 = a.nslices3, P = a.nslices;            // 16-wide passes: expand3x3, then expand1x1
   constexpr int nchunks = NCH;                         // C / 8
@@ -445,12 +356,12 @@ __device__ __forceinline__ void wino_bridge16_body(const WinoArgs& a) {
   if (tile >= ntiles) return;
   const int wv_s = __builtin_amdgcn_readfirstlane(wv);
 
-  constexpr unsigned OOB = 0x80000000u;
+  // (private copy of wino_patch_slot: with the helper the plain fused-expand instances were scheduled differently)
   int r_offB[RAW_IT], r_key[RAW_IT];
 #pragma unroll
   for (int it = 0; it < RAW_IT; ++it) {
     const int slot = it * 64 + lane;
-    const int kq = slot / RP, pix = slot - kq * RP;
+    const int kq = slot / WINO_RP, pix = slot - kq * WINO_RP;
     const bool real = kq < 2 && pix < 108;
     const int r = pix / 18, c = pix - r * 18;
     r_key[it] = real ? (r << 8 | c) : -1;
@@ -460,29 +371,16 @@ __device__ __forceinline__ void wino_bridge16_body(const WinoArgs& a) {
       (void*)(a.x + a.x_coff - (long long)(a.W + 1) * a.x_pitch), 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t ures = __builtin_amdgcn_make_buffer_rsrc((void*)a.u, 0, 0x7ffffff0, 0x00020000);
 
-  struct GPos { int y0, x0, inner, valid; long long p0; unsigned soff; };
-  auto group_pos = [&](int t) {
-    GPos gp;
-    int q = t * WV + wv_s;
-    gp.valid = (int)((unsigned)(q - a.ngroups) >> 31);
-    q = gp.valid ? q : a.ngroups - 1;
-    const int q1 = a.gxn_m ? (int)__umulhi((unsigned)q, a.gxn_m) : q;
-    const int gxi = q - q1 * a.gxn;
-    const int b = a.gyn_m ? (int)__umulhi((unsigned)q1, a.gyn_m) : q1;
-    const int gyi = q1 - b * a.gyn;
-    gp.y0 = gyi * 4; gp.x0 = gxi * 16;
-    gp.p0 = ((long long)b * a.H + gp.y0) * a.W + gp.x0;
-    gp.soff = (unsigned)(gp.p0 * a.x_pitch * 4);
-    gp.inner = (int)(((unsigned)(-gp.y0) & (unsigned)(gp.y0 + 4 - a.H) & (unsigned)(-gp.x0) & (unsigned)(gp.x0 + 16 - a.W)) >> 31);
-    return gp;
-  };
+  typedef WinoGPos GPos;
+  auto group_pos = [&](int t) { return wino_group_pos(a, t * WV + wv_s); };
   float* const rawW = rawB + wv_s * 256 * 4;
+  // (the offsets are evaluated where they are used, once per group, not kept: no wino_group_offsets)
   auto dma_group = [&](const GPos& gp) {               // both chunks of a group's patch into this wave's two buffers
 #pragma unroll
     for (int it = 0; it < RAW_IT; ++it) {
       const int key = r_key[it];
       const bool ok = gp.inner ? true : (key >= 0 && (unsigned)(gp.y0 + (key >> 8) - 1) < (unsigned)a.H && (unsigned)(gp.x0 + (key & 255) - 1) < (unsigned)a.W);
-      const int off = ok ? r_offB[it] : (int)OOB;
+      const int off = ok ? r_offB[it] : (int)WINO_OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_ptr_w_t)(rawW + (it * 64) * 4), 16, off, (int)gp.soff, 0, 0);
       if (nchunks > 1)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_ptr_w_t)(rawW + (WV * 256 + it * 64) * 4), 16, off, (int)(gp.soff + 32u), 0, 0);
@@ -548,14 +446,7 @@ __device__ __forceinline__ void wino_bridge16_body(const WinoArgs& a) {
   for (int px = 0; px < 4; ++px) s_offB[px] = (((2 * ty + (px >> 1)) * a.W + 2 * tx + (px & 1)) * sto_pitch + 4 * g) * 4;
   // plain fused expand: store instructions of a whole group with every channel block present
   const int nst_full = ((a.N & 15) == 0 && (a.N1 & 31) == 0) ? 4 * ((a.N >> 4) + (a.N1 >> 4)) : -1;
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-  auto store16 = [&](f32x4 v, __amdgpu_buffer_rsrc_t res, int voff, int soff) {      // (hazard: see wino_pipe_body)
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), res, voff, soff, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  const int rawL_off = (((g >> 1) * RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
+  const int rawL_off = (((g >> 1) * WINO_RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
   const int u_ln = g * 64 + lr * 4;
   int stores_behind = 0;
 
@@ -574,6 +465,7 @@ __device__ __forceinline__ void wino_bridge16_body(const WinoArgs& a) {
     asm volatile("" ::: "memory");
     stores_behind = 0;
     // ---- input transform of the whole group (both chunks), kept in registers for every pass ----
+    // (private copy of wino_input_transform: with the helper the one-chunk training bridge measured 2.6 % slower)
     f32x2 vv[NCH][16];
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -606,7 +498,7 @@ __device__ __forceinline__ void wino_bridge16_body(const WinoArgs& a) {
 #pragma unroll
       for (int px = 0; px < 4; ++px) {
         if (!wholexy && !(cur.y0 + 2 * ty + (px >> 1) < a.H && cur.x0 + 2 * tx + (px & 1) < a.W)) continue;
-        store16(ov[px], res, s_offB[px] + c0 * 4, ysoff_g);
+        wino_store16(ov[px], res, s_offB[px] + c0 * 4, ysoff_g);
       }
     };
     auto squeeze_in = [&](int bi, const f32x4 (&ov)[4]) {
@@ -673,37 +565,15 @@ __device__ __forceinline__ void wino_bridge16_body(const WinoArgs& a) {
 #pragma unroll
           for (int r = 0; r < (KIND == 2 ? 2 : 4); ++r) {
             f32x4 ov[4];
-            auto inv1 = [&](auto half, auto put) {          // (register pairs: packed adds)
-              const f32x2 m0 = half(acc[0 + r]), m1 = half(acc[4 + r]), m2 = half(acc[8 + r]), m3 = half(acc[12 + r]);
-              const f32x2 s01 = m0 + m1, d01 = m0 - m1, s23 = m2 + m3, d23 = m2 - m3;
-              put(0, s01 + s23); put(1, d01 + d23); put(2, s01 - s23); put(3, d01 - d23);
-            };
-            inv1([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 y) { ov[px].lo = y; });
-            inv1([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 y) { ov[px].hi = y; });
+            wino_inverse_inner(acc, r, ov);
 #pragma unroll
             for (int px = 0; px < 4; ++px) ov[px] = wino_relu4(ov[px], 0.f);
             if constexpr (STO) { const int s1 = pass - P3; store_out(sres1, 128 * (s1 >> 1) + (2 * r + (s1 & 1)) * 16, a.N1, ov); }
             if constexpr (SQZ) squeeze_in(bi0 + r, ov);
           }
         } else {
-          auto inv = [&](auto half, auto put) {
-            f32x2 sx[4][2];
-#pragma unroll
-            for (int xi = 0; xi < 4; ++xi) {
-              const f32x2 m0 = half(acc[xi * 4 + 0]), m1 = half(acc[xi * 4 + 1]);
-              const f32x2 m2 = half(acc[xi * 4 + 2]), m3 = half(acc[xi * 4 + 3]);
-              sx[xi][0] = m0 + m1 + m2;
-              sx[xi][1] = m1 - (m2 + m3);
-            }
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-              put(0 * 2 + b, sx[0][b] + sx[1][b] + sx[2][b]);
-              put(1 * 2 + b, sx[1][b] - (sx[2][b] + sx[3][b]));
-            }
-          };
           f32x4 ov[4];
-          inv([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 y) { ov[px].lo = y; });
-          inv([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 y) { ov[px].hi = y; });
+          wino_inverse(acc, ov);
 #pragma unroll
           for (int px = 0; px < 4; ++px) ov[px] = wino_relu4(ov[px], 0.f);
           if constexpr (STO) store_out(sres3, pass * 16, a.N, ov);
@@ -736,7 +606,7 @@ __device__ __forceinline__ void wino_bridge16_body(const WinoArgs& a) {
 #pragma unroll
         for (int q = 0; q < NSQ; ++q) {
           if (!valid || q * 16 + 4 * g >= a.br_nsq) continue;
-          store16(wino_relu4(acc_sq[px][q], 0.f), yres, o_offB[px] + q * 64, ysoff);
+          wino_store16(wino_relu4(acc_sq[px][q], 0.f), yres, o_offB[px] + q * 64, ysoff);
         }
       }
       // (MODE 2: the counted wait needs BOTH store runs at their full count)
@@ -782,12 +652,8 @@ static int launch_wino_bridge16_t(WinoArgs a, hipStream_t stream) {
   if (MODE == 2 && (!a.sv || (long long)a.B * a.H * a.W * a.sv_pitch * 4 >= (1ll << 32) - (1ll << 30))) return SQD_ERR_UNSUPPORTED;
   static SqdDevOnce attr_once;                 // (per device: ADVICE round 4)
   if (int rc_attr = sqd_max_lds_once(attr_once, (const void*)kern, 160 * 1024)) return rc_attr;
-  a.gxn = sqd_cdiv(a.W, 16); a.gyn = sqd_cdiv(a.H, 4);
-  a.ngroups = a.B * a.gxn * a.gyn;
-  if ((long long)(a.ngroups + 8) * (a.gxn > a.gyn ? a.gxn : a.gyn) >= (1ll << 32)) return SQD_ERR_UNSUPPORTED;
-  a.gxn_m = a.gxn > 1 ? (unsigned)(((1ull << 32) + a.gxn - 1) / a.gxn) : 0u; a.gyn_m = a.gyn > 1 ? (unsigned)(((1ull << 32) + a.gyn - 1) / a.gyn) : 0u;
-  a.ntiles = sqd_cdiv(a.ngroups, WV);
-  const int slots = wino_num_cus();
+  if (int rc = wino_launch_geometry(a, WV)) return rc;
+  const int slots = sqd_num_cus();
   const int per_wg = sqd_cdiv(a.ntiles, slots);
   const int gx = sqd_cdiv(a.ntiles, per_wg);
   a.nslices3 = first1; a.nslices = first1 + P1; a.gx = gx;

@@ -28,7 +28,7 @@
 // partial maximum (four codes packed in one register per channel block).
 template <int NSQ, int NCH, bool SAVE = false>
 __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
-  constexpr int WV = 8, NTHR = WV * 64, RP = 113, RAW_IT = 4, RSLOTS = 224;
+  constexpr int WV = 8, NTHR = WV * 64, RAW_IT = 4, RSLOTS = 224;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int P3 = a.nslices3, P = a.nslices;            // 16-wide passes: expand3x3, then expand1x1
   constexpr int nchunks = NCH;                         // C / 8 (1 or 2)
@@ -50,17 +50,9 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
   int task = (int)blockIdx.x * WV + wv_s;
   const int tstride = a.gx * WV;
 
-  constexpr unsigned OOB = 0x80000000u;
   int r_offB[RAW_IT], r_key[RAW_IT];
 #pragma unroll
-  for (int it = 0; it < RAW_IT; ++it) {
-    const int slot = it * 64 + lane;
-    const int kq = slot / RP, pix = slot - kq * RP;
-    const bool real = kq < 2 && pix < 108;
-    const int r = pix / 18, c = pix - r * 18;
-    r_key[it] = real ? (r << 8 | c) : -1;
-    r_offB[it] = real ? ((r * a.W + c) * a.x_pitch + 4 * kq) * 4 : 0;
-  }
+  for (int it = 0; it < RAW_IT; ++it) wino_patch_slot(it * 64 + lane, a.W, a.x_pitch, r_offB[it], r_key[it]);
   const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(a.x + a.x_coff - (long long)(a.W + 1) * a.x_pitch), 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t ures = __builtin_amdgcn_make_buffer_rsrc((void*)a.u, 0, 0x7ffffff0, 0x00020000);
@@ -96,6 +88,7 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
 
   struct IterPos { int b, s, r, y0, x0, inner; unsigned soff; };
   // iteration `r` (group row) of task (b, s, .): the 4x16-pixel group at rows 4 r, columns 14 s
+  // (groups step 14 columns and walk down a strip: not wino_group_pos's flat list of 16-column groups)
   auto iter_pos = [&](int b, int s, int r) {
     IterPos ip;
     ip.b = b; ip.s = s; ip.r = r;
@@ -106,12 +99,13 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
     return ip;
   };
   float* const rawW = rawB + wv_s * RSLOTS * 4;
+  // (as wino_bridge16_body's: offsets evaluated where they are used, and a 224-slot ring: no wino_group_offsets)
   auto dma_group = [&](const IterPos& ip) {
 #pragma unroll
     for (int it = 0; it < RAW_IT; ++it) {
       const int key = r_key[it];
       const bool ok = ip.inner ? true : (key >= 0 && (unsigned)(ip.y0 + (key >> 8) - 1) < (unsigned)a.H && (unsigned)(ip.x0 + (key & 255) - 1) < (unsigned)a.W);
-      const int off = ok ? r_offB[it] : (int)OOB;
+      const int off = ok ? r_offB[it] : (int)WINO_OOB;
       // the ring slot holds 224 positions: the last request only has 32 lanes (positions 192..223; 221.. are padding)
       if (it < RAW_IT - 1 || lane < RSLOTS - (RAW_IT - 1) * 64) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (lds_ptr_w_t)(rawW + (it * 64) * 4), 16, off, (int)ip.soff, 0, 0);
@@ -139,8 +133,7 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
   // this lane's pooled pixel: row (2 r - 1) + (1 - ty) ... i.e. ty = 0 -> pooled row 2 r, ty = 1 -> the carried row 2 r - 1
   const int o_off = (((1 - ty) * a.pb_wp + tx) * a.y_pitch + 4 * g) * 4;
   const int p_off = SAVE ? (((1 - ty) * a.pb_wp + tx) * a.sv_pitch + 4 * g) * 4 : 0;       // pooled tensor (bytes); codes: a quarter
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-  const int rawL_off = (((g >> 1) * RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
+  const int rawL_off = (((g >> 1) * WINO_RP + (2 * (lr >> 3)) * 18 + 2 * (lr & 7)) * 4 + 2 * (g & 1));
   const int u_ln = g * 64 + lr * 4;
   auto max4 = [](f32x4 p, f32x4 q) {
     f32x4 r;
@@ -184,21 +177,7 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
     // ---- input transform of the whole group (both chunks) ----
     f32x2 vv[NCH][16];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const float* const rawL = rawW + c * WV * RSLOTS * 4 + rawL_off;
-      f32x2 t[4][4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x2 d0 = *(const f32x2*)(rawL + (0 * 18 + j) * 4), d1 = *(const f32x2*)(rawL + (1 * 18 + j) * 4);
-        const f32x2 d2 = *(const f32x2*)(rawL + (2 * 18 + j) * 4), d3 = *(const f32x2*)(rawL + (3 * 18 + j) * 4);
-        t[0][j] = d0 - d2; t[1][j] = d1 + d2; t[2][j] = d2 - d1; t[3][j] = d1 - d3;
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        vv[c][i * 4 + 0] = t[i][0] - t[i][2]; vv[c][i * 4 + 1] = t[i][1] + t[i][2];
-        vv[c][i * 4 + 2] = t[i][2] - t[i][1]; vv[c][i * 4 + 3] = t[i][1] - t[i][3];
-      }
-    }
+    for (int c = 0; c < NCH; ++c) wino_input_transform(rawW + c * WV * RSLOTS * 4 + rawL_off, vv[c]);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     const IterPos nxt = iter_pos(nb, ns, nr);
@@ -282,12 +261,9 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
         pooled = wino_relu4(pooled, 0.f);
         // always issued (the counted wait relies on it): lanes without a pixel or beyond the channel count go out of range
         const bool st = emit_px && cbase + 4 * g < climit;
-        const int pv = st ? p_off + cbase * 4 : (int)OOB;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, pooled), pres, pv, (int)psoff, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 1" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_raw_buffer_store_b32(codes, cres, st ? (p_off >> 2) + cbase : (int)OOB, (int)(psoff >> 2), 0);
+        const int pv = st ? p_off + cbase * 4 : (int)WINO_OOB;
+        wino_store16(pooled, pres, pv, (int)psoff);
+        __builtin_amdgcn_raw_buffer_store_b32(codes, cres, st ? (p_off >> 2) + cbase : (int)WINO_OOB, (int)(psoff >> 2), 0);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_nop 1" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -351,13 +327,7 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
 #pragma unroll
           for (int rr = 0; rr < (KIND == 2 ? 2 : 4); ++rr) {
             f32x4 ov[4];
-            auto inv1 = [&](auto half, auto put) {
-              const f32x2 m0 = half(acc[0 + rr]), m1 = half(acc[4 + rr]), m2 = half(acc[8 + rr]), m3 = half(acc[12 + rr]);
-              const f32x2 s01 = m0 + m1, d01 = m0 - m1, s23 = m2 + m3, d23 = m2 - m3;
-              put(0, s01 + s23); put(1, d01 + d23); put(2, s01 - s23); put(3, d01 - d23);
-            };
-            inv1([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 y) { ov[px].lo = y; });
-            inv1([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 y) { ov[px].hi = y; });
+            wino_inverse_inner(acc, rr, ov);
             // (SAVE) channel of the block in the expand1x1 window of the saved tensor
             const int s1 = pass - P3, c1 = a.sv_coff1 + 128 * (s1 >> 1) + (2 * rr + (s1 & 1)) * 16, l1 = a.sv_coff1 + a.N1;
             if (rr == 0) pool_in(bi0 + rr, std::integral_constant<int, KS0>{}, ov, c1, l1);
@@ -366,24 +336,8 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
             else pool_in(bi0 + rr, std::integral_constant<int, (KS0 + 3) & 7>{}, ov, c1, l1);
           }
         } else {
-          auto inv = [&](auto half, auto put) {
-            f32x2 sx[4][2];
-#pragma unroll
-            for (int xi = 0; xi < 4; ++xi) {
-              const f32x2 m0 = half(acc[xi * 4 + 0]), m1 = half(acc[xi * 4 + 1]);
-              const f32x2 m2 = half(acc[xi * 4 + 2]), m3 = half(acc[xi * 4 + 3]);
-              sx[xi][0] = m0 + m1 + m2;
-              sx[xi][1] = m1 - (m2 + m3);
-            }
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-              put(0 * 2 + b, sx[0][b] + sx[1][b] + sx[2][b]);
-              put(1 * 2 + b, sx[1][b] - (sx[2][b] + sx[3][b]));
-            }
-          };
           f32x4 ov[4];
-          inv([](const f32x4& v) { return (f32x2)v.lo; }, [&](int px, f32x2 y) { ov[px].lo = y; });
-          inv([](const f32x4& v) { return (f32x2)v.hi; }, [&](int px, f32x2 y) { ov[px].hi = y; });
+          wino_inverse(acc, ov);
           pool_in(pass, std::integral_constant<int, KS0>{}, ov, a.sv_coff + 16 * pass, a.sv_coff + a.N);
         }
       };
@@ -409,11 +363,8 @@ __device__ __forceinline__ void wino_poolbridge16_body(const WinoArgs& a) {
         const f32x4 v = wino_relu4(acc_sq[q] + *(const f32x4*)(sqbL + q * 16 + 4 * g), 0.f);
         // every wave issues exactly NSQ stores per iteration (the counted wait above relies on it): lanes without a
         // pixel, or beyond the squeeze width, point outside the buffer and are dropped by the range check
-        const int voff = (emit && q * 16 + 4 * g < a.br_nsq) ? o_off + q * 64 : (int)OOB;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), yres, voff, (int)ysoff, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 1" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        const int voff = (emit && q * 16 + 4 * g < a.br_nsq) ? o_off + q * 64 : (int)WINO_OOB;
+        wino_store16(v, yres, voff, (int)ysoff);
       }
       stored = true;
     }
@@ -457,7 +408,7 @@ static int launch_wino_poolbridge16_t(WinoArgs a, int nseg, hipStream_t stream) 
   a.pb_nseg = sqd_cdiv(a.pb_ng, a.pb_gseg);
   a.ngroups = a.B * a.pb_ns * a.pb_nseg;              // tasks
   const int wgs = sqd_cdiv(a.ngroups, WV);
-  const int slots = wino_num_cus();
+  const int slots = sqd_num_cus();
   const int per_wg = sqd_cdiv(wgs, slots);
   const int gx = sqd_cdiv(wgs, per_wg);
   a.nslices3 = first1; a.nslices = first1 + P1; a.gx = gx;

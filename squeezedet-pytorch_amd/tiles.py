@@ -161,17 +161,19 @@ def wino_cfgs():
     import ctypes
     out = {WINO_SK_CFG: (32, 4), WINO_VS_CFG: (80, 12)}
     for i in range(nat.lib().sqd_wino_num_cfgs()):
-        if 4 <= i <= 7:             # retired ids (deep-prefetch, streamed U): the library answers "unsupported"
-            continue
         bn, wv = ctypes.c_int(), ctypes.c_int()
-        nat.check(nat.lib().sqd_wino_cfg_info(i, ctypes.byref(bn), ctypes.byref(wv)), 'sqd_wino_cfg_info')
+        rc = nat.lib().sqd_wino_cfg_info(i, ctypes.byref(bn), ctypes.byref(wv))
+        if rc == nat.ERR_UNSUPPORTED:       # a retired id
+            continue
+        nat.check(rc, 'sqd_wino_cfg_info')
         out[i] = (bn.value, wv.value)
     return out
 
 
 def wino_kernel_name(cfg_id):
     """Name of a Winograd configuration as bench.py / the profiles print it: conv_wino<NT,WAVES> (ids 0..3),
-    conv_wino_us<..> (8..11: U-stationary, barrier-free; ids 4..7, the deep-prefetch streamed-U forms, are retired)."""
+    conv_wino_us<..> (8..11: U-stationary, barrier-free).  Ids 4..7 are retired: the library reports them unsupported and
+    ``wino_cfgs`` leaves them out."""
     c = cfg_id % 1000
     if c == WINO_SK_CFG:
         return 'conv_wino_sk'

@@ -20,6 +20,11 @@ def table():
 def test_every_tuned_entry_names_a_compiled_configuration(table):
     tab = ops.cfg_table()
     assert len(tab) >= 70
+    # the Winograd family: twelve ids, 4..7 retired (the library reports them unsupported), plus the stream-K and V-shared kernels
+    from squeezedet_pytorch_amd import _native
+    assert _native.lib().sqd_wino_num_cfgs() == 12
+    assert ops.wino_cfgs() == {0: (32, 8), 1: (16, 8), 2: (32, 4), 3: (16, 4), 8: (32, 8), 9: (16, 8), 10: (32, 4), 11: (16, 4),
+                               16: (32, 4), 17: (80, 12)}
     for key, v in table.items():
         cid = int(v["cfg"])
         if key.startswith("W:"):                                                  # Winograd family: its own configuration list
