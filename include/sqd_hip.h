@@ -88,6 +88,11 @@ int sqd_conv_wgrad_wino_group(const long long* layers, int n, int B, int H, int 
  * S <= the number of its pixel blocks; SQD_ERR_UNSUPPORTED otherwise.  Bitwise the slabs of n sqd_conv_wgrad(dw = NULL, taps = 1) calls
  * with the same S. */
 int sqd_conv_wgrad_group(const long long* layers, int n, int B, int H, int W, int S, void* stream);
+/* The tile form the three direct weight-gradient entries run a (taps, N, C) layer in: kind 0 = sqd_conv_wgrad, 1 = sqd_conv_wgrad_group,
+ * 2 = sqd_squeeze_bwd.  tn / tc = out- / in-channel tiles of 16 per workgroup, px_per_block = pixels of one block of the split pixel
+ * axis (3x3: a (px_per_block / 16) x 16 window); any of the three may be NULL.  The host sizes slab splits from this instead of
+ * restating the rule.  Launches nothing and touches no device.  SQD_ERR_UNSUPPORTED where the entry would refuse the shape. */
+int sqd_wgrad_tile_form(int kind, int taps, int N, int C, int* tn, int* tc, int* px_per_block);
 
 /* dw == NULL in sqd_conv_wgrad: write the S partial slabs only; the caller then reduces many layers with ONE launch:
  * descs_dev = device array of n records of 9 int64 {slab offset, dw offset, db offset (floats from slab_base / grad_base;

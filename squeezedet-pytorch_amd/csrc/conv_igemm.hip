@@ -790,6 +790,18 @@ __global__ __launch_bounds__(WV * 64) void conv_ws_kernel(ConvArgs a) {
 #endif
 }
 
+// Pixel tiles of a launch: 16 x TH windows per image (3x3), runs of 16 * TH pixels of the flat pixel axis (1x1).
+template <int TAPS>
+static void conv_tiles(ConvArgs& a, int TH) {
+  if (TAPS == 9) {
+    a.tiles_x = sqd_cdiv(a.W, 16); a.tiles_y = sqd_cdiv(a.H, TH);
+    a.ntiles = a.B * a.tiles_x * a.tiles_y;
+  } else {
+    a.tiles_x = a.tiles_y = 0;
+    a.ntiles = (int)((a.total_px + TH * 16 - 1) / (TH * 16));
+  }
+}
+
 template <int NT, int WV>
 static int launch_conv_ws(ConvArgs a, hipStream_t stream) {
   constexpr int BN = 16 * NT, NTHR = WV * 64, KC = 32;
@@ -805,7 +817,7 @@ static int launch_conv_ws(ConvArgs a, hipStream_t stream) {
   for (int d : {8, 6, 4, 3}) if (wbytes + d * stage <= 160 * 1024 && (d <= 4 || wbytes + d * stage <= 80 * 1024)) { D = d; break; }
   if (D == 0) return SQD_ERR_UNSUPPORTED;
   const size_t lds = wbytes + D * stage;
-  a.ntiles = (int)((a.total_px + 15) / 16);
+  conv_tiles<1>(a, 1);
   const int nslices = sqd_cdiv(a.N, BN);
   if (nslices * BN > a.Npad) return SQD_ERR_BAD_ARG;
   auto go = [&](auto kern) {
@@ -813,15 +825,9 @@ static int launch_conv_ws(ConvArgs a, hipStream_t stream) {
     if (int rc_attr = sqd_max_lds_once(attr_once, (const void*)kern, 160 * 1024)) return (int)rc_attr;
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, NTHR, lds) != hipSuccess || nb < 1) nb = 1;
-    int wgs_per_cu = nb > 4 ? 4 : nb;
-    if (a.wg_cap > 0 && a.wg_cap < wgs_per_cu) wgs_per_cu = a.wg_cap;
-    const int slots = sqd_num_cus() * wgs_per_cu;
-    int gx_max = slots / nslices; if (gx_max < 1) gx_max = 1;
     const int wave_tiles = sqd_cdiv(a.ntiles, WV);            // tiles per wave stream if there were one stream
-    const int per_wg = sqd_cdiv(wave_tiles, gx_max);
-    const int gx = (sqd_cdiv(wave_tiles, per_wg) + 7) & ~7;
-    a.nslices = nslices; a.gx = gx;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(gx * nslices)), dim3(NTHR), lds, stream, a);
+    a.nslices = nslices; a.gx = sqd_persistent_grid(wave_tiles, nslices, nb > 4 ? 4 : nb, a.wg_cap);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a.gx * nslices)), dim3(NTHR), lds, stream, a);
     return sqd_launch_status();
   };
   switch (D) {
@@ -854,22 +860,11 @@ static int launch_conv(ConvArgs a, hipStream_t stream) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
     wgs_per_cu = nb > 4 ? 4 : nb;
   }
-  if (TAPS == 9) {
-    a.tiles_x = sqd_cdiv(a.W, 16); a.tiles_y = sqd_cdiv(a.H, TH);
-    a.ntiles = a.B * a.tiles_x * a.tiles_y;
-  } else {
-    a.tiles_x = a.tiles_y = 0;
-    a.ntiles = (int)((a.total_px + TH * 16 - 1) / (TH * 16));
-  }
+  conv_tiles<TAPS>(a, TH);
   const int nslices = sqd_cdiv(a.N, BN);
   if (nslices * BN > a.Npad) return SQD_ERR_BAD_ARG;     // packed weights too short for this slice width
-  // persistent grid: at most one resident wave of workgroups, pixel tiles dealt evenly
-  const int slots = sqd_num_cus() * ((a.wg_cap > 0 && a.wg_cap < wgs_per_cu) ? a.wg_cap : wgs_per_cu);
-  int gx_max = slots / nslices; if (gx_max < 1) gx_max = 1;
-  const int per_wg = sqd_cdiv(a.ntiles, gx_max);
-  const int gx = (sqd_cdiv(a.ntiles, per_wg) + 7) & ~7;        // tile streams, a multiple of 8 (one per XCD lane)
-  a.nslices = nslices; a.gx = gx;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(gx * nslices)), dim3(256), lds, stream, a);
+  a.nslices = nslices; a.gx = sqd_persistent_grid(a.ntiles, nslices, wgs_per_cu, a.wg_cap);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.gx * nslices)), dim3(256), lds, stream, a);
   return sqd_launch_status();
 }
 
@@ -902,119 +897,114 @@ static int launch_conv_dma(ConvArgs a, hipStream_t stream) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, NTHR, lds) != hipSuccess || nb < 1) nb = 1;
     wgs_per_cu[stationary] = nb > 6 ? 6 : nb;
   }
-  if (TAPS == 9) {
-    a.tiles_x = sqd_cdiv(a.W, 16); a.tiles_y = sqd_cdiv(a.H, TH);
-    a.ntiles = a.B * a.tiles_x * a.tiles_y;
-  } else {
-    a.tiles_x = a.tiles_y = 0;
-    a.ntiles = (int)((a.total_px + TH * 16 - 1) / (TH * 16));
-  }
+  conv_tiles<TAPS>(a, TH);
   const int nslices = sqd_cdiv(a.N, BN);
   if (nslices * BN > a.Npad) return SQD_ERR_BAD_ARG;
-  const int slots = sqd_num_cus() * ((a.wg_cap > 0 && a.wg_cap < wgs_per_cu[stationary]) ? a.wg_cap : wgs_per_cu[stationary]);
-  int gx_max = slots / nslices; if (gx_max < 1) gx_max = 1;
-  const int per_wg = sqd_cdiv(a.ntiles, gx_max);
-  const int gx = (sqd_cdiv(a.ntiles, per_wg) + 7) & ~7;        // tile streams, a multiple of 8 (one per XCD lane)
-  a.nslices = nslices; a.gx = gx;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(gx * nslices)), dim3(NTHR), lds, stream, a);
+  a.nslices = nslices; a.gx = sqd_persistent_grid(a.ntiles, nslices, wgs_per_cu[stationary], a.wg_cap);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.gx * nslices)), dim3(NTHR), lds, stream, a);
   return sqd_launch_status();
 }
 
 // Tile configurations (cfg_id) -> template instance.  The host picks per layer; any config is
 // correct for any shape (edges are masked, partial K chunks zero-filled).
-struct ConvCfg { int taps, kc, mt, nt, dma; };   // dma: 0 = register-staged 4 waves, 1 = LDS-DMA 4 waves, 2 = LDS-DMA 8 waves
-static const ConvCfg kConvCfgs[] = {
-    {1, 16, 2, 4, 0},  // 0  1x1, small C (expand1x1), 128 px x 64 ch
-    {1, 32, 2, 1, 0},  // 1  1x1 squeeze N<=16
-    {1, 32, 2, 2, 0},  // 2  N<=32
-    {1, 32, 2, 3, 0},  // 3  N<=48
-    {1, 32, 2, 4, 0},  // 4  N<=64
-    {1, 32, 2, 6, 0},  // 5  N<=96
-    {1, 32, 1, 3, 0},  // 6  64-px tiles (late, small layers)
-    {1, 32, 1, 4, 0},  // 7
-    {1, 32, 1, 6, 0},  // 8
-    {1, 16, 1, 4, 0},  // 9  1x1 small C, 64 px
-    {9, 16, 2, 4, 0},  // 10 3x3, 8x16 px x 64 ch
-    {9, 16, 2, 5, 0},  // 11 3x3, 8x16 px x 80 ch (ConvDet N=72)
-    {9, 16, 1, 4, 0},  // 12 3x3, 4x16 px x 64 ch
-    {9, 16, 1, 5, 0},  // 13 3x3, 4x16 px x 80 ch
-    {9, 16, 2, 2, 0},  // 14 3x3, 8x16 px x 32 ch
-    {9, 16, 2, 6, 0},  // 15 3x3, 8x16 px x 96 ch
-    {9, 16, 1, 6, 0},  // 16 3x3, 4x16 px x 96 ch
-    {9, 16, 2, 3, 0},  // 17 3x3, 8x16 px x 48 ch
-    {9, 16, 2, 1, 0},  // 18 3x3, 8x16 px x 16 ch (dgrad into a 16-channel squeeze)
-    {9, 16, 1, 1, 0},  // 19 3x3, 4x16 px x 16 ch
-    {9, 16, 1, 2, 0},  // 20 3x3, 4x16 px x 32 ch
-    {9, 16, 1, 3, 0},  // 21 3x3, 4x16 px x 48 ch
-    {9, 16, 4, 1, 0},  // 22 3x3, 16x16 px x 16 ch
-    {9, 16, 4, 2, 0},  // 23 3x3, 16x16 px x 32 ch
-    {1, 16, 1, 2, 0},  // 24 1x1 small C, 64 px x 32 ch
-    {1, 16, 2, 2, 0},  // 25 1x1 small C, 128 px x 32 ch
-    {1, 16, 4, 2, 0},  // 26 1x1 small C, 256 px x 32 ch
-    {1, 16, 4, 4, 0},  // 27 1x1 small C, 256 px x 64 ch
-    {1, 32, 1, 1, 0},  // 28 1x1, 64 px x 16 ch
-    {1, 32, 1, 2, 0},  // 29 1x1, 64 px x 32 ch
-    {1, 32, 4, 1, 0},  // 30 1x1, 256 px x 16 ch
-    {1, 32, 4, 2, 0},  // 31 1x1, 256 px x 32 ch
-    {1, 64, 1, 2, 0},  // 32 1x1, KC=64, 64 px x 32 ch
-    {1, 64, 1, 3, 0},  // 33 1x1, KC=64, 64 px x 48 ch
-    {1, 64, 1, 4, 0},  // 34 1x1, KC=64, 64 px x 64 ch
-    {1, 64, 2, 1, 0},  // 35 1x1, KC=64, 128 px x 16 ch
-    {1, 64, 2, 2, 0},  // 36 1x1, KC=64, 128 px x 32 ch
-    // ---- LDS-DMA double-buffered variants (dma = 1) ----
-    {9, 16, 1, 1, 1},  // 37
-    {9, 16, 1, 2, 1},  // 38
-    {9, 16, 1, 3, 1},  // 39
-    {9, 16, 1, 4, 1},  // 40
-    {9, 16, 2, 1, 1},  // 41
-    {9, 16, 2, 2, 1},  // 42
-    {9, 16, 2, 3, 1},  // 43
-    {9, 16, 2, 4, 1},  // 44
-    {9, 16, 4, 1, 1},  // 45
-    {9, 16, 4, 2, 1},  // 46
-    {1, 16, 1, 2, 1},  // 47
-    {1, 16, 1, 4, 1},  // 48
-    {1, 16, 2, 4, 1},  // 49
-    {1, 16, 4, 4, 1},  // 50
-    {1, 32, 1, 1, 1},  // 51
-    {1, 32, 1, 2, 1},  // 52
-    {1, 32, 1, 3, 1},  // 53
-    {1, 32, 1, 4, 1},  // 54
-    {1, 32, 1, 6, 1},  // 55
-    {1, 32, 2, 1, 1},  // 56
-    {1, 32, 2, 2, 1},  // 57
-    {1, 32, 4, 1, 1},  // 58
-    {1, 64, 1, 2, 1},  // 59
-    {1, 64, 1, 3, 1},  // 60
-    {1, 64, 1, 4, 1},  // 61
-    {1, 64, 1, 6, 1},  // 62
-    {1, 64, 2, 1, 1},  // 63
-    {1, 64, 2, 2, 1},  // 64
-    // ---- LDS-DMA, 8-wave workgroups (dma = 2): tile = mt*8 rows ----
-    {9, 16, 1, 2, 2},  // 65  8x16 px x 32 ch
-    {9, 16, 1, 3, 2},  // 66
-    {9, 16, 1, 4, 2},  // 67  8x16 px x 64 ch
-    {9, 16, 2, 1, 2},  // 68  16x16 px x 16 ch
-    {9, 16, 2, 2, 2},  // 69  16x16 px x 32 ch
-    {9, 16, 2, 3, 2},  // 70
-    {9, 16, 2, 4, 2},  // 71  16x16 px x 64 ch
-    {9, 16, 1, 5, 2},  // 72  8x16 px x 80 ch
-    {1, 32, 1, 2, 2},  // 73
-    {1, 32, 1, 4, 2},  // 74
-    {1, 32, 2, 2, 2},  // 75
-    {1, 16, 1, 4, 2},  // 76
-    {1, 16, 2, 4, 2},  // 77
-    // ---- weight-stationary, barrier-free 1x1 (dma = 3: 4 waves, dma = 4: 8 waves); KC = 32 packing, 16-pixel wave tiles ----
-    {1, 32, 1, 1, 3},  // 78
-    {1, 32, 1, 2, 3},  // 79
-    {1, 32, 1, 3, 3},  // 80
-    {1, 32, 1, 4, 3},  // 81
-    {1, 32, 1, 6, 3},  // 82
-    {1, 32, 1, 2, 4},  // 83
-    {1, 32, 1, 3, 4},  // 84
-    {1, 32, 1, 4, 4},  // 85
-    {1, 32, 1, 6, 4},  // 86
-};
+// X(taps, kc, mt, nt, dma), written ONCE: a line's position is its cfg id (tuning.json and the tests hold ids), and the table the host
+// reads (kConvCfgs) and the launch tables (kConvLaunch, kFuseLaunch) are generated from this list.
+// dma: 0 = register-staged 4 waves, 1 = LDS-DMA 4 waves, 2 = LDS-DMA 8 waves, 3 / 4 = weight-stationary 1x1 with 4 / 8 waves
+#define SQD_CONV_CFGS(X) \
+  X(1, 16, 2, 4, 0)  /* 0  1x1, small C (expand1x1), 128 px x 64 ch */ \
+  X(1, 32, 2, 1, 0)  /* 1  1x1 squeeze N<=16 */ \
+  X(1, 32, 2, 2, 0)  /* 2  N<=32 */ \
+  X(1, 32, 2, 3, 0)  /* 3  N<=48 */ \
+  X(1, 32, 2, 4, 0)  /* 4  N<=64 */ \
+  X(1, 32, 2, 6, 0)  /* 5  N<=96 */ \
+  X(1, 32, 1, 3, 0)  /* 6  64-px tiles (late, small layers) */ \
+  X(1, 32, 1, 4, 0)  /* 7 */ \
+  X(1, 32, 1, 6, 0)  /* 8 */ \
+  X(1, 16, 1, 4, 0)  /* 9  1x1 small C, 64 px */ \
+  X(9, 16, 2, 4, 0)  /* 10  3x3, 8x16 px x 64 ch */ \
+  X(9, 16, 2, 5, 0)  /* 11  3x3, 8x16 px x 80 ch (ConvDet N=72) */ \
+  X(9, 16, 1, 4, 0)  /* 12  3x3, 4x16 px x 64 ch */ \
+  X(9, 16, 1, 5, 0)  /* 13  3x3, 4x16 px x 80 ch */ \
+  X(9, 16, 2, 2, 0)  /* 14  3x3, 8x16 px x 32 ch */ \
+  X(9, 16, 2, 6, 0)  /* 15  3x3, 8x16 px x 96 ch */ \
+  X(9, 16, 1, 6, 0)  /* 16  3x3, 4x16 px x 96 ch */ \
+  X(9, 16, 2, 3, 0)  /* 17  3x3, 8x16 px x 48 ch */ \
+  X(9, 16, 2, 1, 0)  /* 18  3x3, 8x16 px x 16 ch (dgrad into a 16-channel squeeze) */ \
+  X(9, 16, 1, 1, 0)  /* 19  3x3, 4x16 px x 16 ch */ \
+  X(9, 16, 1, 2, 0)  /* 20  3x3, 4x16 px x 32 ch */ \
+  X(9, 16, 1, 3, 0)  /* 21  3x3, 4x16 px x 48 ch */ \
+  X(9, 16, 4, 1, 0)  /* 22  3x3, 16x16 px x 16 ch */ \
+  X(9, 16, 4, 2, 0)  /* 23  3x3, 16x16 px x 32 ch */ \
+  X(1, 16, 1, 2, 0)  /* 24  1x1 small C, 64 px x 32 ch */ \
+  X(1, 16, 2, 2, 0)  /* 25  1x1 small C, 128 px x 32 ch */ \
+  X(1, 16, 4, 2, 0)  /* 26  1x1 small C, 256 px x 32 ch */ \
+  X(1, 16, 4, 4, 0)  /* 27  1x1 small C, 256 px x 64 ch */ \
+  X(1, 32, 1, 1, 0)  /* 28  1x1, 64 px x 16 ch */ \
+  X(1, 32, 1, 2, 0)  /* 29  1x1, 64 px x 32 ch */ \
+  X(1, 32, 4, 1, 0)  /* 30  1x1, 256 px x 16 ch */ \
+  X(1, 32, 4, 2, 0)  /* 31  1x1, 256 px x 32 ch */ \
+  X(1, 64, 1, 2, 0)  /* 32  1x1, KC=64, 64 px x 32 ch */ \
+  X(1, 64, 1, 3, 0)  /* 33  1x1, KC=64, 64 px x 48 ch */ \
+  X(1, 64, 1, 4, 0)  /* 34  1x1, KC=64, 64 px x 64 ch */ \
+  X(1, 64, 2, 1, 0)  /* 35  1x1, KC=64, 128 px x 16 ch */ \
+  X(1, 64, 2, 2, 0)  /* 36  1x1, KC=64, 128 px x 32 ch */ \
+  /* ---- LDS-DMA double-buffered variants (dma = 1) ---- */ \
+  X(9, 16, 1, 1, 1)  /* 37 */ \
+  X(9, 16, 1, 2, 1)  /* 38 */ \
+  X(9, 16, 1, 3, 1)  /* 39 */ \
+  X(9, 16, 1, 4, 1)  /* 40 */ \
+  X(9, 16, 2, 1, 1)  /* 41 */ \
+  X(9, 16, 2, 2, 1)  /* 42 */ \
+  X(9, 16, 2, 3, 1)  /* 43 */ \
+  X(9, 16, 2, 4, 1)  /* 44 */ \
+  X(9, 16, 4, 1, 1)  /* 45 */ \
+  X(9, 16, 4, 2, 1)  /* 46 */ \
+  X(1, 16, 1, 2, 1)  /* 47 */ \
+  X(1, 16, 1, 4, 1)  /* 48 */ \
+  X(1, 16, 2, 4, 1)  /* 49 */ \
+  X(1, 16, 4, 4, 1)  /* 50 */ \
+  X(1, 32, 1, 1, 1)  /* 51 */ \
+  X(1, 32, 1, 2, 1)  /* 52 */ \
+  X(1, 32, 1, 3, 1)  /* 53 */ \
+  X(1, 32, 1, 4, 1)  /* 54 */ \
+  X(1, 32, 1, 6, 1)  /* 55 */ \
+  X(1, 32, 2, 1, 1)  /* 56 */ \
+  X(1, 32, 2, 2, 1)  /* 57 */ \
+  X(1, 32, 4, 1, 1)  /* 58 */ \
+  X(1, 64, 1, 2, 1)  /* 59 */ \
+  X(1, 64, 1, 3, 1)  /* 60 */ \
+  X(1, 64, 1, 4, 1)  /* 61 */ \
+  X(1, 64, 1, 6, 1)  /* 62 */ \
+  X(1, 64, 2, 1, 1)  /* 63 */ \
+  X(1, 64, 2, 2, 1)  /* 64 */ \
+  /* ---- LDS-DMA, 8-wave workgroups (dma = 2): tile = mt*8 rows ---- */ \
+  X(9, 16, 1, 2, 2)  /* 65  8x16 px x 32 ch */ \
+  X(9, 16, 1, 3, 2)  /* 66 */ \
+  X(9, 16, 1, 4, 2)  /* 67  8x16 px x 64 ch */ \
+  X(9, 16, 2, 1, 2)  /* 68  16x16 px x 16 ch */ \
+  X(9, 16, 2, 2, 2)  /* 69  16x16 px x 32 ch */ \
+  X(9, 16, 2, 3, 2)  /* 70 */ \
+  X(9, 16, 2, 4, 2)  /* 71  16x16 px x 64 ch */ \
+  X(9, 16, 1, 5, 2)  /* 72  8x16 px x 80 ch */ \
+  X(1, 32, 1, 2, 2)  /* 73 */ \
+  X(1, 32, 1, 4, 2)  /* 74 */ \
+  X(1, 32, 2, 2, 2)  /* 75 */ \
+  X(1, 16, 1, 4, 2)  /* 76 */ \
+  X(1, 16, 2, 4, 2)  /* 77 */ \
+  /* ---- weight-stationary, barrier-free 1x1 (dma = 3: 4 waves, dma = 4: 8 waves); KC = 32 packing, 16-pixel wave tiles ---- */ \
+  X(1, 32, 1, 1, 3)  /* 78 */ \
+  X(1, 32, 1, 2, 3)  /* 79 */ \
+  X(1, 32, 1, 3, 3)  /* 80 */ \
+  X(1, 32, 1, 4, 3)  /* 81 */ \
+  X(1, 32, 1, 6, 3)  /* 82 */ \
+  X(1, 32, 1, 2, 4)  /* 83 */ \
+  X(1, 32, 1, 3, 4)  /* 84 */ \
+  X(1, 32, 1, 4, 4)  /* 85 */ \
+  X(1, 32, 1, 6, 4)  /* 86 */
+struct ConvCfg { int taps, kc, mt, nt, dma; };
+#define SQD_CFG_ROW(T, K, M, Nn, D) {T, K, M, Nn, D},
+static const ConvCfg kConvCfgs[] = {SQD_CONV_CFGS(SQD_CFG_ROW)};
+#undef SQD_CFG_ROW
 static const int kNumConvCfgs = (int)(sizeof(kConvCfgs) / sizeof(kConvCfgs[0]));
 
 extern "C" int sqd_conv_num_cfgs() { return kNumConvCfgs; }
@@ -1036,16 +1026,34 @@ extern "C" int sqd_conv_cfg_info(int cfg_id, int* taps, int* kc, int* tile_px, i
   return SQD_OK;
 }
 
-static int conv_fwd_impl(const float* x, const float* w_packed, const float* bias, float* y,
-                         const float* xmask, const float* ymask, const float* ymul, int B, int H, int W, int C,
-                         int x_pitch, int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu,
-                         int accumulate, int xmask_pitch, int xmask_coff, int ymask_pitch, int ymask_coff,
-                         int ymul_pitch, int ymul_coff, int cfg_id, void* stream, const unsigned long long* drop_state, int drop_keep,
-                         float drop_scale) {
+// cfg id -> launcher, generated from the list: D selects the kernel family.  A configuration can run the fused Fire expand exactly
+// when it is a 3x3, KC = 16 LDS-DMA tiling with an even number of 16-channel groups per slice.
+typedef int (*ConvLaunch)(ConvArgs, hipStream_t);
+template <int T, int K, int M, int Nn, int D>
+static int launch_cfg(ConvArgs a, hipStream_t s) {
+  if constexpr (D == 0) return launch_conv<T, K, M, Nn>(a, s);
+  else if constexpr (D <= 2) return launch_conv_dma<T, K, M, Nn, 4 * D>(a, s);
+  else return launch_conv_ws<Nn, D == 4 ? 8 : 4>(a, s);
+}
+template <int T, int K, int M, int Nn, int D>
+static int launch_fuse_cfg(ConvArgs a, hipStream_t s) {
+  if constexpr (T == 9 && K == 16 && (D == 1 || D == 2) && Nn % 2 == 0) return launch_conv_dma<9, 16, M, Nn, 4 * D, true>(a, s);
+  else return SQD_ERR_UNSUPPORTED;
+}
+#define SQD_CFG_LAUNCH(T, K, M, Nn, D) launch_cfg<T, K, M, Nn, D>,
+#define SQD_CFG_FUSE(T, K, M, Nn, D) launch_fuse_cfg<T, K, M, Nn, D>,
+static const ConvLaunch kConvLaunch[] = {SQD_CONV_CFGS(SQD_CFG_LAUNCH)};
+static const ConvLaunch kFuseLaunch[] = {SQD_CONV_CFGS(SQD_CFG_FUSE)};
+#undef SQD_CFG_LAUNCH
+#undef SQD_CFG_FUSE
+
+// What every forward entry checks and fills: the tensors' windows and a ConvArgs without masks or dropout.  cfg_id comes in as
+// tile configuration + 1000 * k and leaves as the tile configuration: k > 0 caps the persistent grid at k workgroups per CU (fewer,
+// longer tile streams balance better on small layers; the tuner measures it), k = 0 fills the occupancy.
+static int conv_args(ConvArgs& a, const float* x, const float* w_packed, const float* bias, float* y, int B, int H, int W, int C,
+                     int x_pitch, int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu, int accumulate, int& cfg_id) {
   SQD_CHECK_ARG(x && w_packed && y);
   SQD_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && N > 0);
-  // cfg_id = tile configuration + 1000 * k: k > 0 caps the persistent grid at k workgroups per CU (fewer, longer tile
-  // streams balance better on small layers; the tuner measures it), k = 0 fills the occupancy
   const int wg_cap = cfg_id >= 0 ? cfg_id / 1000 : 0;
   if (cfg_id >= 0) cfg_id %= 1000;
   SQD_CHECK_ARG(cfg_id >= 0 && cfg_id < kNumConvCfgs && wg_cap <= 8);
@@ -1054,87 +1062,32 @@ static int conv_fwd_impl(const float* x, const float* w_packed, const float* bia
   SQD_CHECK_ARG(x_coff + C <= x_pitch && y_coff + N <= y_pitch);
   SQD_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)w_packed & 15) == 0);
   SQD_CHECK_ARG(!bias || ((uintptr_t)bias & 15) == 0);
+  a = {};
+  a.x = x; a.w = w_packed; a.bias = bias; a.y = y;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
+  a.N = N; a.Npad = Npad; a.y_pitch = y_pitch; a.y_coff = y_coff;
+  a.relu = relu; a.accumulate = accumulate; a.nslices = 1; a.gx = 8; a.wg_cap = wg_cap;
+  a.total_px = (long long)B * H * W;
+  return SQD_OK;
+}
+
+static int conv_fwd_impl(const float* x, const float* w_packed, const float* bias, float* y,
+                         const float* xmask, const float* ymask, const float* ymul, int B, int H, int W, int C,
+                         int x_pitch, int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu,
+                         int accumulate, int xmask_pitch, int xmask_coff, int ymask_pitch, int ymask_coff,
+                         int ymul_pitch, int ymul_coff, int cfg_id, void* stream, const unsigned long long* drop_state, int drop_keep,
+                         float drop_scale) {
+  ConvArgs a;
+  if (int rc = conv_args(a, x, w_packed, bias, y, B, H, W, C, x_pitch, x_coff, N, Npad, y_pitch, y_coff, relu, accumulate, cfg_id)) return rc;
   if (xmask) SQD_CHECK_ARG((xmask_pitch & 3) == 0 && (xmask_coff & 3) == 0 && xmask_coff + C <= xmask_pitch && ((uintptr_t)xmask & 15) == 0);
   if (ymask) SQD_CHECK_ARG((ymask_pitch & 3) == 0 && (ymask_coff & 3) == 0 && ymask_coff + N <= ymask_pitch && ((uintptr_t)ymask & 15) == 0);
   if (ymul) SQD_CHECK_ARG((ymul_pitch & 3) == 0 && (ymul_coff & 3) == 0 && ymul_coff + N <= ymul_pitch && ((uintptr_t)ymul & 15) == 0);
-  ConvArgs a = {};
-  a.ymask = ymask; a.ymul = ymul; a.ymask_pitch = ymask_pitch; a.ymask_coff = ymask_coff; a.ymul_pitch = ymul_pitch; a.ymul_coff = ymul_coff;
-  a.x = x; a.w = w_packed; a.bias = bias; a.y = y; a.xmask = xmask;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.N = N; a.Npad = Npad; a.y_pitch = y_pitch; a.y_coff = y_coff;
-  a.relu = relu; a.accumulate = accumulate; a.tiles_x = a.tiles_y = 0; a.ntiles = 0; a.nslices = 1; a.gx = 8; a.wg_cap = wg_cap; a.fuse_e = 0;
-  a.xmask_pitch = xmask_pitch; a.xmask_coff = xmask_coff;
-  a.total_px = (long long)B * H * W;
+  a.xmask = xmask; a.xmask_pitch = xmask_pitch; a.xmask_coff = xmask_coff;
+  a.ymask = ymask; a.ymask_pitch = ymask_pitch; a.ymask_coff = ymask_coff;
+  a.ymul = ymul; a.ymul_pitch = ymul_pitch; a.ymul_coff = ymul_coff;
   a.drop_state = drop_state; a.drop_keep = drop_keep; a.drop_scale = drop_scale;
-  hipStream_t s = (hipStream_t)stream;
-  const ConvCfg& c = kConvCfgs[cfg_id];
-  if (drop_state && c.dma < 3) return SQD_ERR_UNSUPPORTED;      // only the weight-stationary 1x1 family carries the dropout epilogue
-#define SQD_WS_CASE(Nn) \
-  if (c.dma >= 3 && c.nt == Nn) return (c.dma == 4) ? launch_conv_ws<Nn, 8>(a, s) : launch_conv_ws<Nn, 4>(a, s);
-  SQD_WS_CASE(1) SQD_WS_CASE(2) SQD_WS_CASE(3) SQD_WS_CASE(4) SQD_WS_CASE(6)
-#undef SQD_WS_CASE
-  if (c.dma >= 3) return SQD_ERR_UNSUPPORTED;
-#define SQD_DMA8_CASE(T, K, M, Nn) \
-  if (c.dma == 2 && c.taps == T && c.kc == K && c.mt == M && c.nt == Nn) return launch_conv_dma<T, K, M, Nn, 8>(a, s);
-  SQD_DMA8_CASE(9, 16, 1, 2) SQD_DMA8_CASE(9, 16, 1, 3) SQD_DMA8_CASE(9, 16, 1, 4) SQD_DMA8_CASE(9, 16, 2, 1)
-  SQD_DMA8_CASE(9, 16, 2, 2) SQD_DMA8_CASE(9, 16, 2, 3) SQD_DMA8_CASE(9, 16, 2, 4) SQD_DMA8_CASE(9, 16, 1, 5)
-  SQD_DMA8_CASE(1, 32, 1, 2) SQD_DMA8_CASE(1, 32, 1, 4) SQD_DMA8_CASE(1, 32, 2, 2) SQD_DMA8_CASE(1, 16, 1, 4)
-  SQD_DMA8_CASE(1, 16, 2, 4)
-#undef SQD_DMA8_CASE
-  if (c.dma == 2) return SQD_ERR_UNSUPPORTED;
-#define SQD_DMA_CASE(T, K, M, Nn) \
-  if (c.dma && c.taps == T && c.kc == K && c.mt == M && c.nt == Nn) return launch_conv_dma<T, K, M, Nn, 4>(a, s);
-  SQD_DMA_CASE(9, 16, 1, 1) SQD_DMA_CASE(9, 16, 1, 2) SQD_DMA_CASE(9, 16, 1, 3) SQD_DMA_CASE(9, 16, 1, 4)
-  SQD_DMA_CASE(9, 16, 2, 1) SQD_DMA_CASE(9, 16, 2, 2) SQD_DMA_CASE(9, 16, 2, 3) SQD_DMA_CASE(9, 16, 2, 4)
-  SQD_DMA_CASE(9, 16, 4, 1) SQD_DMA_CASE(9, 16, 4, 2)
-  SQD_DMA_CASE(1, 16, 1, 2) SQD_DMA_CASE(1, 16, 1, 4) SQD_DMA_CASE(1, 16, 2, 4) SQD_DMA_CASE(1, 16, 4, 4)
-  SQD_DMA_CASE(1, 32, 1, 1) SQD_DMA_CASE(1, 32, 1, 2) SQD_DMA_CASE(1, 32, 1, 3) SQD_DMA_CASE(1, 32, 1, 4)
-  SQD_DMA_CASE(1, 32, 1, 6) SQD_DMA_CASE(1, 32, 2, 1) SQD_DMA_CASE(1, 32, 2, 2) SQD_DMA_CASE(1, 32, 4, 1)
-  SQD_DMA_CASE(1, 64, 1, 2) SQD_DMA_CASE(1, 64, 1, 3) SQD_DMA_CASE(1, 64, 1, 4) SQD_DMA_CASE(1, 64, 1, 6)
-  SQD_DMA_CASE(1, 64, 2, 1) SQD_DMA_CASE(1, 64, 2, 2)
-#undef SQD_DMA_CASE
-  if (c.dma) return SQD_ERR_UNSUPPORTED;
-#define SQD_CONV_CASE(T, K, M, Nn) \
-  if (c.taps == T && c.kc == K && c.mt == M && c.nt == Nn) return launch_conv<T, K, M, Nn>(a, s);
-  SQD_CONV_CASE(1, 16, 2, 4)
-  SQD_CONV_CASE(1, 32, 2, 1)
-  SQD_CONV_CASE(1, 32, 2, 2)
-  SQD_CONV_CASE(1, 32, 2, 3)
-  SQD_CONV_CASE(1, 32, 2, 4)
-  SQD_CONV_CASE(1, 32, 2, 6)
-  SQD_CONV_CASE(1, 32, 1, 3)
-  SQD_CONV_CASE(1, 32, 1, 4)
-  SQD_CONV_CASE(1, 32, 1, 6)
-  SQD_CONV_CASE(1, 16, 1, 4)
-  SQD_CONV_CASE(9, 16, 2, 4)
-  SQD_CONV_CASE(9, 16, 2, 5)
-  SQD_CONV_CASE(9, 16, 1, 4)
-  SQD_CONV_CASE(9, 16, 1, 5)
-  SQD_CONV_CASE(9, 16, 2, 2)
-  SQD_CONV_CASE(9, 16, 2, 6)
-  SQD_CONV_CASE(9, 16, 1, 6)
-  SQD_CONV_CASE(9, 16, 2, 3)
-  SQD_CONV_CASE(9, 16, 2, 1)
-  SQD_CONV_CASE(9, 16, 1, 1)
-  SQD_CONV_CASE(9, 16, 1, 2)
-  SQD_CONV_CASE(9, 16, 1, 3)
-  SQD_CONV_CASE(9, 16, 4, 1)
-  SQD_CONV_CASE(9, 16, 4, 2)
-  SQD_CONV_CASE(1, 16, 1, 2)
-  SQD_CONV_CASE(1, 16, 2, 2)
-  SQD_CONV_CASE(1, 16, 4, 2)
-  SQD_CONV_CASE(1, 16, 4, 4)
-  SQD_CONV_CASE(1, 32, 1, 1)
-  SQD_CONV_CASE(1, 32, 1, 2)
-  SQD_CONV_CASE(1, 32, 4, 1)
-  SQD_CONV_CASE(1, 32, 4, 2)
-  SQD_CONV_CASE(1, 64, 1, 2)
-  SQD_CONV_CASE(1, 64, 1, 3)
-  SQD_CONV_CASE(1, 64, 1, 4)
-  SQD_CONV_CASE(1, 64, 2, 1)
-  SQD_CONV_CASE(1, 64, 2, 2)
-#undef SQD_CONV_CASE
-  return SQD_ERR_UNSUPPORTED;
+  if (drop_state && kConvCfgs[cfg_id].dma < 3) return SQD_ERR_UNSUPPORTED;      // only the weight-stationary 1x1 family carries the dropout epilogue
+  return kConvLaunch[cfg_id](a, (hipStream_t)stream);
 }
 
 extern "C" int sqd_conv_fwd(const float* x, const float* w_packed, const float* bias, float* y,
@@ -1167,32 +1120,12 @@ extern "C" int sqd_conv_drop_fwd(const float* x, const float* w_packed, const fl
 extern "C" int sqd_fire_expand_fwd(const float* x, const float* w_packed, const float* bias, float* y, int B, int H, int W,
                                    int C, int x_pitch, int x_coff, int E, int Npad, int y_pitch, int y_coff, int cfg_id,
                                    void* stream) {
-  SQD_CHECK_ARG(x && w_packed && y && B > 0 && H > 0 && W > 0 && C > 0 && E > 0);
-  const int wg_cap = cfg_id >= 0 ? cfg_id / 1000 : 0;
-  if (cfg_id >= 0) cfg_id %= 1000;
-  SQD_CHECK_ARG(cfg_id >= 0 && cfg_id < kNumConvCfgs && wg_cap <= 8);
-  SQD_CHECK_ARG((C & 3) == 0 && (E & 15) == 0);
-  SQD_CHECK_ARG((x_pitch & 3) == 0 && (x_coff & 3) == 0 && (y_pitch & 3) == 0 && (y_coff & 3) == 0);
-  SQD_CHECK_ARG(x_coff + C <= x_pitch && y_coff + 2 * E <= y_pitch);
-  SQD_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)w_packed & 15) == 0);
-  SQD_CHECK_ARG(!bias || ((uintptr_t)bias & 15) == 0);
+  SQD_CHECK_ARG(E > 0 && (E & 15) == 0);
+  ConvArgs a;
+  if (int rc = conv_args(a, x, w_packed, bias, y, B, H, W, C, x_pitch, x_coff, 2 * E, Npad, y_pitch, y_coff, 1, 0, cfg_id)) return rc;
   const ConvCfg& c = kConvCfgs[cfg_id];
   SQD_CHECK_ARG(c.taps == 9 && c.dma != 0 && (c.nt & 1) == 0);
   SQD_CHECK_ARG((2 * E) % (16 * c.nt) == 0);               // whole slices: every slice carries nt/2 groups of each half
-  ConvArgs a = {};
-  a.ymask = nullptr; a.ymul = nullptr; a.ymask_pitch = a.ymask_coff = a.ymul_pitch = a.ymul_coff = 0;
-  a.x = x; a.w = w_packed; a.bias = bias; a.y = y; a.xmask = nullptr;
-  a.B = B; a.H = H; a.W = W; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.N = 2 * E; a.Npad = Npad; a.y_pitch = y_pitch; a.y_coff = y_coff;
-  a.relu = 1; a.accumulate = 0; a.tiles_x = a.tiles_y = 0; a.ntiles = 0; a.nslices = 1; a.gx = 8; a.wg_cap = wg_cap;
   a.fuse_e = E;
-  a.xmask_pitch = a.xmask_coff = 0;
-  a.total_px = (long long)B * H * W;
-  hipStream_t s = (hipStream_t)stream;
-#define SQD_FUSE_CASE(M, Nn, Wv) \
-  if (c.dma == ((Wv) == 8 ? 2 : 1) && c.kc == 16 && c.mt == M && c.nt == Nn) return launch_conv_dma<9, 16, M, Nn, Wv, true>(a, s);
-  SQD_FUSE_CASE(1, 2, 4) SQD_FUSE_CASE(1, 4, 4) SQD_FUSE_CASE(2, 2, 4) SQD_FUSE_CASE(2, 4, 4) SQD_FUSE_CASE(4, 2, 4)
-  SQD_FUSE_CASE(1, 2, 8) SQD_FUSE_CASE(1, 4, 8) SQD_FUSE_CASE(2, 2, 8) SQD_FUSE_CASE(2, 4, 8)
-#undef SQD_FUSE_CASE
-  return SQD_ERR_UNSUPPORTED;
+  return kFuseLaunch[cfg_id](a, (hipStream_t)stream);
 }

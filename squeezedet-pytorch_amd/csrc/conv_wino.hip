@@ -639,7 +639,7 @@ static int launch_wino_pipe(WinoArgs a, hipStream_t stream) {
   const int nslices = FIRE ? a.Npad / BN : sqd_cdiv(a.N, BN);
   if (nslices * BN > a.Npad) return SQD_ERR_BAD_ARG;
   if (!FIRE) a.nslices3 = nslices;
-  a.nslices = nslices; a.gx = wino_grid(a, nslices, wgs_per_cu);
+  a.nslices = nslices; a.gx = sqd_persistent_grid(a.ntiles, nslices, wgs_per_cu, a.wg_cap);
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.gx * nslices)), dim3(NTHR), lds, stream, a);
   return sqd_launch_status();
 }
@@ -664,7 +664,7 @@ static int launch_wino(WinoArgs a, hipStream_t stream) {
   if (int rc = wino_launch_geometry(a, WV)) return rc;
   const int nslices = sqd_cdiv(a.N, BN);
   if (nslices * BN > a.Npad) return SQD_ERR_BAD_ARG;
-  a.nslices = nslices; a.gx = wino_grid(a, nslices, wgs_per_cu);
+  a.nslices = nslices; a.gx = sqd_persistent_grid(a.ntiles, nslices, wgs_per_cu, a.wg_cap);
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.gx * nslices)), dim3(NTHR), lds, stream, a);
   return sqd_launch_status();
 }

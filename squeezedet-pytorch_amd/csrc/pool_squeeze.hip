@@ -132,17 +132,12 @@ static int launch_pool_squeeze(PoolSqArgs a, hipStream_t s) {
   const size_t lds = (size_t)(32 * 65 * 4 + ((a.C + 3) / 4) * 16 * NT * 4) * sizeof(float);
   if (lds > 160 * 1024) return SQD_ERR_UNSUPPORTED;
   auto kern = pool_squeeze_kernel<NT>;
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return SQD_ERR_LAUNCH;
-  int nb = 0;
+  static SqdDevOnce lds_once;                  // (the weight tile grows with C: the attribute is raised to the budget, once per device)
+  if (lds > 64 * 1024 && sqd_max_lds_once(lds_once, (const void*)kern, 160 * 1024) != SQD_OK) return SQD_ERR_LAUNCH;
+  int nb = 0;                                  // (not cached: the LDS size depends on C)
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
   if (nb > 4) nb = 4;
-  int dev = 0, cus = 256; hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-    cus = prop.multiProcessorCount;
-  const int slots = cus * nb;
-  const int per_wg = sqd_cdiv(a.ntiles, slots);
-  const int gx = sqd_cdiv(a.ntiles, per_wg);
+  const int gx = sqd_even_grid(a.ntiles, sqd_num_cus() * nb);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, s, a);
   return sqd_launch_status();
 }

@@ -32,6 +32,18 @@ static inline int sqd_num_cus() {
   return cus;
 }
 
+// Grid of a persistent kernel: at most one resident round of workgroups, the tiles dealt evenly.  sqd_resident_slots: CUs x workgroups
+// per CU (wg_cap > 0 caps the latter).  sqd_even_grid: the workgroups for n tiles over `slots` resident ones.  sqd_persistent_grid: the
+// tile streams of a kernel whose workgroup ids also carry an output-channel slice axis -- a multiple of 8 (one stream per XCD lane).
+static inline int sqd_resident_slots(int wgs_per_cu, int wg_cap) {
+  return sqd_num_cus() * ((wg_cap > 0 && wg_cap < wgs_per_cu) ? wg_cap : wgs_per_cu);
+}
+static inline int sqd_even_grid(int n, int slots) { return sqd_cdiv(n, sqd_cdiv(n, slots)); }
+static inline int sqd_persistent_grid(int ntiles, int nslices, int wgs_per_cu, int wg_cap) {
+  int gx_max = sqd_resident_slots(wgs_per_cu, wg_cap) / nslices; if (gx_max < 1) gx_max = 1;
+  return (sqd_even_grid(ntiles, gx_max) + 7) & ~7;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the device that is current at the call: kernels that need more than 64 KB of
 // LDS set it once PER DEVICE (a process may launch on several: reference-style DataParallel, tests that switch devices).  Idempotent,
 // so two threads racing through the first launch on a device is harmless.

@@ -500,12 +500,7 @@ static int launch_stem_pool_t(StemPoolArgs a, hipStream_t s) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, NTHR, lds) != hipSuccess || nb < 1) nb = 1;
     wgs_per_cu = nb > 4 ? 4 : nb;
   }
-  int dev = 0, cus = 256; hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-    cus = prop.multiProcessorCount;
-  const int slots = cus * wgs_per_cu;
-  const int per_wg = sqd_cdiv(a.ntiles, slots);
-  const int gx = sqd_cdiv(a.ntiles, per_wg);
+  const int gx = sqd_even_grid(a.ntiles, sqd_num_cus() * wgs_per_cu);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(NTHR), lds, s, a);
   return sqd_launch_status();
 }
@@ -871,12 +866,7 @@ static int launch_stem_wave(StemWaveArgs a, hipStream_t s) {
   auto kern = stem_wave_kernel<PH, CB, ARGMAX, SQ>;
   static SqdDevOnce attr_once;                 // (per device: ADVICE round 4)
   if (int rc_attr = lds <= 64 * 1024 ? SQD_OK : sqd_max_lds_once(attr_once, (const void*)kern, (int)lds)) return rc_attr;
-  int dev = 0, cus = 256; hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-    cus = prop.multiProcessorCount;
-  const int wtiles = sqd_cdiv(a.ntiles, 4);                      // workgroup-sized runs of 4 tiles
-  const int per_wg = sqd_cdiv(wtiles, OCC * cus);
-  const int gx = sqd_cdiv(wtiles, per_wg);
+  const int gx = sqd_even_grid(sqd_cdiv(a.ntiles, 4), OCC * sqd_num_cus());      // over workgroup-sized runs of 4 tiles
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, s, a);
   return sqd_launch_status();
 }

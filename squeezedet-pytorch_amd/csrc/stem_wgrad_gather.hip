@@ -241,30 +241,19 @@ __global__ __launch_bounds__(256, OCC) void stem_wgrad_gather_kernel(StemWgradAr
 #endif
 }
 
-static int stem_wgrad_gather_occ() { return 2; }      // workgroups per CU the launch is sized for (3 measured no faster)
-
-static int stem_wgrad_gather_slabs(const StemWgradArgs& a, int S, int occ) {
-  int dev = 0, cus = 256; hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-    cus = prop.multiProcessorCount;
-  const int ntiles = a.B * sqd_cdiv(a.Hp, 2) * sqd_cdiv(a.Wp, 8);
-  int g = sqd_cdiv(ntiles, 4);
-  if (g > occ * cus) g = occ * cus;
-  return g < S ? g : S;
-}
-
 // returns the number of slabs written (= workgroups), or a negative status
 int launch_stem_wgrad_gather(StemWgradArgs a, int S, hipStream_t s) {
   constexpr int IH = 11, SL = 11, N_IT = (3 * IH * SL + 63) / 64;
   constexpr size_t lds_patch = (size_t)4 * 2 * N_IT * 64 * 16, lds_red = (size_t)4 * 56 * 32 * 4;
   constexpr size_t lds = lds_patch > lds_red ? lds_patch : lds_red;
+  constexpr int OCC = 2;                                 // workgroups per CU the launch is sized for (3 measured no faster)
   a.tiles_x = sqd_cdiv(a.Wp, 8); a.tiles_y = sqd_cdiv(a.Hp, 2);
   a.nblocks = a.B * a.tiles_x * a.tiles_y;
-  const int occ = stem_wgrad_gather_occ();
-  const int g = stem_wgrad_gather_slabs(a, S, occ);
-  if (a.pooled) hipLaunchKernelGGL((stem_wgrad_gather_kernel<true, 2>), dim3((unsigned)g), dim3(256), lds, s, a);
-  else if (occ == 3) hipLaunchKernelGGL((stem_wgrad_gather_kernel<false, 3>), dim3((unsigned)g), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((stem_wgrad_gather_kernel<false, 2>), dim3((unsigned)g), dim3(256), lds, s, a);
+  int g = sqd_cdiv(a.nblocks, 4);                        // slabs: one resident round at most, and no more than the caller's S
+  if (g > OCC * sqd_num_cus()) g = OCC * sqd_num_cus();
+  if (g > S) g = S;
+  if (a.pooled) hipLaunchKernelGGL((stem_wgrad_gather_kernel<true, OCC>), dim3((unsigned)g), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((stem_wgrad_gather_kernel<false, OCC>), dim3((unsigned)g), dim3(256), lds, s, a);
   return sqd_launch_status() == SQD_OK ? g : -1;
 }
 

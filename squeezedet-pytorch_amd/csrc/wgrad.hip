@@ -477,56 +477,95 @@ extern "C" int sqd_wgrad_reduce_launch(const float* slab, float* dw, float* db, 
   return sqd_launch_status();
 }
 
-// dy: [B][H][W][dy_pitch] window [dy_coff, dy_coff+N) (ReLU mask already applied); x: input window
-// [x_coff, x_coff+C); slab: workspace of S * (N*taps*C + N) floats; dw: [N][C][k][k]; db: [N] or NULL.
-extern "C" int sqd_conv_wgrad(const float* dy, const float* x, float* slab, float* dw, float* db, int B, int H, int W,
-                              int N, int dy_pitch, int dy_coff, int C, int x_pitch, int x_coff, int taps, int S,
-                              void* stream) {
-  SQD_CHECK_ARG(dy && x && slab && B > 0 && H > 0 && W > 0 && N > 0 && C > 0 && S > 0 && S <= 65535);
-  SQD_CHECK_ARG((N & 3) == 0 && (C & 3) == 0 && (dy_pitch & 3) == 0 && (dy_coff & 3) == 0 && (x_pitch & 3) == 0 && (x_coff & 3) == 0);
-  SQD_CHECK_ARG(dy_coff + N <= dy_pitch && x_coff + C <= x_pitch);
-  SQD_CHECK_ARG(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0);
-  SQD_CHECK_ARG(taps == 1 || taps == 9);
-  WgradArgs a;
-  a.dy = dy; a.x = x; a.slab = slab; a.B = B; a.H = H; a.W = W;
-  a.N = N; a.dy_pitch = dy_pitch; a.dy_coff = dy_coff; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.total_px = (long long)B * H * W;
-  a.slab_stride = (long long)N * taps * C + N;
-  a.w = nullptr; a.dx = nullptr; a.dx_pitch = a.dx_coff = a.dx_mask = 0;
-  hipStream_t s = (hipStream_t)stream;
-  const int tn = N >= 64 ? 4 : sqd_cdiv(N, 16);
-  int rc = SQD_ERR_UNSUPPORTED;
+// ---------------------------------------------------------------------------------------------
+// The tile form of a launch -- out-channel tiles tn, in-channel tiles tc (of 16), th * 16 pixels per block -- decided HERE and nowhere
+// else: the three entry points dispatch on it and the host sizes its slab workspaces and split counts from it (sqd_wgrad_tile_form).
+// kind: 0 = sqd_conv_wgrad, 1 = sqd_conv_wgrad_group (1x1, 64-out-channel forms only), 2 = sqd_squeeze_bwd (1x1, all N <= 128 in one
+// group).
+// ---------------------------------------------------------------------------------------------
+enum { WG_PLAIN = 0, WG_GROUP = 1, WG_FUSED = 2 };
+struct WgForm { int tn, tc, th; };
+// 1x1: pixels per block sized so the double-buffered LDS image stays <= 40 KB: 4-5 workgroups per CU instead of one
+// (the late 24x78 layers have only ~300 blocks of 128 pixels: with one resident workgroup per CU nothing overlapped)
+static constexpr int wg1_th(int tn, int tc) { return tn + tc >= 6 ? 2 : (tn + tc >= 3 ? 4 : 8); }
+static constexpr int wg9_th(int tn, int tc) { return (tn == 4 && tc == 2) ? SQD_WG9_TH : 4; }
+
+static int wgrad_form(int kind, int taps, int N, int C, WgForm& f) {
+  SQD_CHECK_ARG(kind >= WG_PLAIN && kind <= WG_FUSED && (taps == 1 || taps == 9) && N > 0 && C > 0);
+  if (kind != WG_PLAIN && taps != 1) return SQD_ERR_UNSUPPORTED;
+  if (kind == WG_FUSED) {
+    if (N > 128) return SQD_ERR_UNSUPPORTED;
+    f = {N > 96 ? 8 : (N > 64 ? 6 : sqd_cdiv(N, 16)), C >= 64 ? 4 : sqd_cdiv(C, 16), 2};
+    return SQD_OK;
+  }
+  if (kind == WG_GROUP && (N < 64 || (N > 64 && N <= 96))) return SQD_ERR_UNSUPPORTED;     // (those layers run other forms: their own launch)
+  f.tn = N >= 64 ? 4 : sqd_cdiv(N, 16);
   if (taps == 9) {
-    if (N > 64 && N <= 80) rc = launch_wgrad<9, 5, 1, 4>(a, S, s);      // ConvDet (N = 72)
-    else if (C % 32 == 0 && tn == 4) rc = launch_wgrad<9, 4, 2, SQD_WG9_TH>(a, S, s);
-    else if (tn == 4) rc = launch_wgrad<9, 4, 1, 4>(a, S, s);
-    else if (tn == 1) rc = launch_wgrad<9, 1, 2, 4>(a, S, s);
-    else if (tn == 2) rc = launch_wgrad<9, 2, 2, 4>(a, S, s);
-    else rc = launch_wgrad<9, 3, 1, 4>(a, S, s);
+    if (N > 64 && N <= 80) { f.tn = 5; f.tc = 1; }          // ConvDet (N = 72)
+    else if (f.tn == 4) f.tc = (C % 32 == 0) ? 2 : 1;
+    else f.tc = (f.tn == 3) ? 1 : 2;
+    f.th = wg9_th(f.tn, f.tc);
   } else {
     // Round 3: wider output tiles where the layer is wide enough.  A workgroup that owns TC = 8 in-channel tiles (128 channels)
     // re-reads dY half as often as with 4, and N = 96 (the squeeze of fire13 / fire14) runs as ONE 6-tile group instead of 64 + a
     // half-empty 64 (X streamed once instead of twice, no padded MFMAs): the 24x78 1x1 weight gradients were bound by L2 -> LDS
     // bytes per MFMA, not by HBM or the matrix pipe.
-    int tn1 = tn, tc = C >= 64 ? 4 : sqd_cdiv(C, 16);
-    if (N > 64 && N <= 96) tn1 = 6;
-    if (C >= 256) tc = 8;            // (C = 128 at 96x312 measured slower with the wide tile: 60.7 -> 74.2 us)
-    // pixels per block sized so the double-buffered LDS image stays <= 40 KB: 4-5 workgroups per CU instead of one
-    // (the late 24x78 layers have only ~300 blocks of 128 pixels: with one resident workgroup per CU nothing overlapped)
-#define SQD_WG_CASE(TNv, TCv) if (tn1 == TNv && tc == TCv) rc = launch_wgrad<1, TNv, TCv, ((TNv + TCv >= 6) ? 2 : ((TNv + TCv >= 3) ? 4 : 8))>(a, S, s);
-    SQD_WG_CASE(1, 1) SQD_WG_CASE(1, 2) SQD_WG_CASE(1, 3) SQD_WG_CASE(1, 4) SQD_WG_CASE(1, 8)
-    SQD_WG_CASE(2, 1) SQD_WG_CASE(2, 2) SQD_WG_CASE(2, 3) SQD_WG_CASE(2, 4) SQD_WG_CASE(2, 8)
-    SQD_WG_CASE(3, 1) SQD_WG_CASE(3, 2) SQD_WG_CASE(3, 3) SQD_WG_CASE(3, 4) SQD_WG_CASE(3, 8)
-    SQD_WG_CASE(4, 1) SQD_WG_CASE(4, 2) SQD_WG_CASE(4, 3) SQD_WG_CASE(4, 4) SQD_WG_CASE(4, 8)
-    SQD_WG_CASE(6, 1) SQD_WG_CASE(6, 2) SQD_WG_CASE(6, 3) SQD_WG_CASE(6, 4) SQD_WG_CASE(6, 8)
-#undef SQD_WG_CASE
+    if (N > 64 && N <= 96) f.tn = 6;
+    f.tc = C >= 256 ? 8 : (C >= 64 ? 4 : sqd_cdiv(C, 16));            // (C = 128 at 96x312 measured slower with the wide tile: 60.7 -> 74.2 us)
+    f.th = wg1_th(f.tn, f.tc);
   }
+  return SQD_OK;
+}
+
+// The host's view of the rule: launches nothing, touches no device.  px_per_block = th * 16 (3x3: a th x 16 window).
+extern "C" int sqd_wgrad_tile_form(int kind, int taps, int N, int C, int* tn, int* tc, int* px_per_block) {
+  WgForm f;
+  if (int rc = wgrad_form(kind, taps, N, C, f)) return rc;
+  if (tn) *tn = f.tn;
+  if (tc) *tc = f.tc;
+  if (px_per_block) *px_per_block = f.th * 16;
+  return SQD_OK;
+}
+
+// What the three entries check and fill for one layer (the fused entry adds w / dx).
+static int wgrad_args(WgradArgs& a, const float* dy, const float* x, float* slab, int B, int H, int W, int N, int dy_pitch, int dy_coff,
+                      int C, int x_pitch, int x_coff, int taps) {
+  SQD_CHECK_ARG(dy && x && slab && B > 0 && H > 0 && W > 0 && N > 0 && C > 0);
+  SQD_CHECK_ARG((N & 3) == 0 && (C & 3) == 0 && (dy_pitch & 3) == 0 && (dy_coff & 3) == 0 && (x_pitch & 3) == 0 && (x_coff & 3) == 0);
+  SQD_CHECK_ARG(dy_coff + N <= dy_pitch && x_coff + C <= x_pitch);
+  SQD_CHECK_ARG(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0);
+  SQD_CHECK_ARG(taps == 1 || taps == 9);
+  a.dy = dy; a.x = x; a.slab = slab; a.B = B; a.H = H; a.W = W;
+  a.N = N; a.dy_pitch = dy_pitch; a.dy_coff = dy_coff; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
+  a.total_px = (long long)B * H * W;
+  a.slab_stride = (long long)N * taps * C + N;
+  a.w = nullptr; a.dx = nullptr; a.dx_pitch = a.dx_coff = a.dx_mask = 0;
+  return SQD_OK;
+}
+
+// dy: [B][H][W][dy_pitch] window [dy_coff, dy_coff+N) (ReLU mask already applied); x: input window
+// [x_coff, x_coff+C); slab: workspace of S * (N*taps*C + N) floats; dw: [N][C][k][k]; db: [N] or NULL.
+extern "C" int sqd_conv_wgrad(const float* dy, const float* x, float* slab, float* dw, float* db, int B, int H, int W,
+                              int N, int dy_pitch, int dy_coff, int C, int x_pitch, int x_coff, int taps, int S,
+                              void* stream) {
+  SQD_CHECK_ARG(S > 0 && S <= 65535);
+  WgradArgs a; WgForm f;
+  if (int rc = wgrad_args(a, dy, x, slab, B, H, W, N, dy_pitch, dy_coff, C, x_pitch, x_coff, taps)) return rc;
+  if (int rc = wgrad_form(WG_PLAIN, taps, N, C, f)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = SQD_ERR_UNSUPPORTED;
+#define SQD_WG_CASE(TAPSv, TNv, TCv) \
+  if (taps == TAPSv && f.tn == TNv && f.tc == TCv) rc = launch_wgrad<TAPSv, TNv, TCv, (TAPSv == 9 ? wg9_th(TNv, TCv) : wg1_th(TNv, TCv))>(a, S, s);
+  SQD_WG_CASE(9, 5, 1) SQD_WG_CASE(9, 4, 2) SQD_WG_CASE(9, 4, 1) SQD_WG_CASE(9, 1, 2) SQD_WG_CASE(9, 2, 2) SQD_WG_CASE(9, 3, 1)
+  SQD_WG_CASE(1, 1, 1) SQD_WG_CASE(1, 1, 2) SQD_WG_CASE(1, 1, 3) SQD_WG_CASE(1, 1, 4) SQD_WG_CASE(1, 1, 8)
+  SQD_WG_CASE(1, 2, 1) SQD_WG_CASE(1, 2, 2) SQD_WG_CASE(1, 2, 3) SQD_WG_CASE(1, 2, 4) SQD_WG_CASE(1, 2, 8)
+  SQD_WG_CASE(1, 3, 1) SQD_WG_CASE(1, 3, 2) SQD_WG_CASE(1, 3, 3) SQD_WG_CASE(1, 3, 4) SQD_WG_CASE(1, 3, 8)
+  SQD_WG_CASE(1, 4, 1) SQD_WG_CASE(1, 4, 2) SQD_WG_CASE(1, 4, 3) SQD_WG_CASE(1, 4, 4) SQD_WG_CASE(1, 4, 8)
+  SQD_WG_CASE(1, 6, 1) SQD_WG_CASE(1, 6, 2) SQD_WG_CASE(1, 6, 3) SQD_WG_CASE(1, 6, 4) SQD_WG_CASE(1, 6, 8)
+#undef SQD_WG_CASE
   if (rc != SQD_OK) return rc;
   if (!dw) return sqd_launch_status();       // partial slabs only: the caller reduces many layers at once (sqd_wgrad_reduce_batched)
-  const long long outs = a.slab_stride;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((outs + WGR_OUT - 1) / WGR_OUT)), dim3(WGR_OUT * WGR_PARTS), 0, s, slab, dw, db, S,
-                     a.slab_stride, N, C, taps);
-  return sqd_launch_status();
+  return sqd_wgrad_reduce_launch(slab, dw, db, S, a.slab_stride, N, C, taps, stream);
 }
 
 template <int TN, int TC, int TH>
@@ -561,34 +600,21 @@ extern "C" int sqd_conv_wgrad_group(const long long* layers, int n, int B, int H
   SQD_CHECK_ARG(layers && n >= 1 && n <= WG_MAX_GROUP && B > 0 && H > 0 && W > 0 && S > 0 && S <= 65535);
   WgGroupArgs ga;
   ga.n = n; ga.S = S;
-  int tc0 = 0;
+  WgForm f0 = {0, 0, 0};
   for (int i = 0; i < n; ++i) {
     const long long* r = layers + 9 * i;
-    WgradArgs& a = ga.l[i];
-    a.dy = (const float*)(uintptr_t)r[0]; a.x = (const float*)(uintptr_t)r[1]; a.slab = (float*)(uintptr_t)r[2];
-    a.N = (int)r[3]; a.dy_pitch = (int)r[4]; a.dy_coff = (int)r[5]; a.C = (int)r[6]; a.x_pitch = (int)r[7]; a.x_coff = (int)r[8];
-    a.B = B; a.H = H; a.W = W;
-    SQD_CHECK_ARG(a.dy && a.x && a.slab && a.N > 0 && a.C > 0);
-    SQD_CHECK_ARG((a.N & 3) == 0 && (a.C & 3) == 0 && (a.dy_pitch & 3) == 0 && (a.dy_coff & 3) == 0 && (a.x_pitch & 3) == 0 && (a.x_coff & 3) == 0);
-    SQD_CHECK_ARG(a.dy_coff + a.N <= a.dy_pitch && a.x_coff + a.C <= a.x_pitch);
-    SQD_CHECK_ARG(((uintptr_t)a.dy & 15) == 0 && ((uintptr_t)a.x & 15) == 0);
-    a.total_px = (long long)B * H * W;
-    a.slab_stride = (long long)a.N * a.C + a.N;
-    a.w = nullptr; a.dx = nullptr; a.dx_pitch = a.dx_coff = a.dx_mask = 0;
-    if (a.N < 64 || (a.N > 64 && a.N <= 96)) return SQD_ERR_UNSUPPORTED;          // (those layers run other tile forms: their own launch)
-    const int tc = a.C >= 256 ? 8 : (a.C >= 64 ? 4 : sqd_cdiv(a.C, 16));
-    if (i == 0) tc0 = tc;
-    if (tc != tc0) return SQD_ERR_UNSUPPORTED;
+    WgForm f;
+    if (int rc = wgrad_args(ga.l[i], (const float*)(uintptr_t)r[0], (const float*)(uintptr_t)r[1], (float*)(uintptr_t)r[2], B, H, W, (int)r[3],
+                            (int)r[4], (int)r[5], (int)r[6], (int)r[7], (int)r[8], 1)) return rc;
+    if (int rc = wgrad_form(WG_GROUP, 1, ga.l[i].N, ga.l[i].C, f)) return rc;
+    if (i == 0) f0 = f;
+    if (f.tc != f0.tc) return SQD_ERR_UNSUPPORTED;
   }
   for (int i = n; i < WG_MAX_GROUP; ++i) ga.l[i] = ga.l[0];
   hipStream_t s = (hipStream_t)stream;
-  switch (tc0) {
-    case 1: return launch_wgrad_group<4, 1, 4>(ga, s);
-    case 2: return launch_wgrad_group<4, 2, 2>(ga, s);
-    case 3: return launch_wgrad_group<4, 3, 2>(ga, s);
-    case 4: return launch_wgrad_group<4, 4, 2>(ga, s);
-    case 8: return launch_wgrad_group<4, 8, 2>(ga, s);
-  }
+#define SQD_WGG_CASE(TCv) case TCv: return launch_wgrad_group<4, TCv, wg1_th(4, TCv)>(ga, s);
+  switch (f0.tc) { SQD_WGG_CASE(1) SQD_WGG_CASE(2) SQD_WGG_CASE(3) SQD_WGG_CASE(4) SQD_WGG_CASE(8) }
+#undef SQD_WGG_CASE
   return SQD_ERR_UNSUPPORTED;
 }
 
@@ -603,25 +629,18 @@ extern "C" int sqd_conv_wgrad_group(const long long* layers, int n, int B, int H
 extern "C" int sqd_squeeze_bwd(const float* dy, const float* x, const float* w_oihw, float* slab, float* dx, int B, int H, int W,
                                int N, int dy_pitch, int dy_coff, int C, int x_pitch, int x_coff, int dx_pitch, int dx_coff,
                                int relu_mask, int S, void* stream) {
-  SQD_CHECK_ARG(dy && x && w_oihw && slab && dx && B > 0 && H > 0 && W > 0 && N > 0 && C > 0 && S > 0 && S <= 65535);
-  SQD_CHECK_ARG((N & 3) == 0 && (C & 3) == 0 && (dy_pitch & 3) == 0 && (dy_coff & 3) == 0 && (x_pitch & 3) == 0 && (x_coff & 3) == 0);
+  SQD_CHECK_ARG(w_oihw && dx && S > 0 && S <= 65535);
+  WgradArgs a; WgForm f;
+  if (int rc = wgrad_args(a, dy, x, slab, B, H, W, N, dy_pitch, dy_coff, C, x_pitch, x_coff, 1)) return rc;
   SQD_CHECK_ARG((dx_pitch & 3) == 0 && (dx_coff & 3) == 0 && dx_coff >= 0 && dx_coff + C <= dx_pitch);
-  SQD_CHECK_ARG(dy_coff + N <= dy_pitch && x_coff + C <= x_pitch);
-  SQD_CHECK_ARG(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0);
+  SQD_CHECK_ARG(((uintptr_t)dx & 15) == 0);
   SQD_CHECK_ARG((long long)B * H * W * dx_pitch * 4 < (1ll << 32) - (1ll << 24));       // 32-bit SGPR byte offset of a pixel block
   SQD_CHECK_ARG((long long)32 * dx_pitch * 4 < (1ll << 30));                             // per-lane byte offsets inside a block
-  if (N > 128) return SQD_ERR_UNSUPPORTED;
-  WgradArgs a;
-  a.dy = dy; a.x = x; a.slab = slab; a.B = B; a.H = H; a.W = W;
-  a.N = N; a.dy_pitch = dy_pitch; a.dy_coff = dy_coff; a.C = C; a.x_pitch = x_pitch; a.x_coff = x_coff;
-  a.total_px = (long long)B * H * W;
-  a.slab_stride = (long long)N * C + N;
+  if (int rc = wgrad_form(WG_FUSED, 1, N, C, f)) return rc;
   a.w = w_oihw; a.dx = dx; a.dx_pitch = dx_pitch; a.dx_coff = dx_coff; a.dx_mask = relu_mask;
   hipStream_t s = (hipStream_t)stream;
-  const int tn = N > 96 ? 8 : (N > 64 ? 6 : sqd_cdiv(N, 16));
-  const int tc = C >= 64 ? 4 : sqd_cdiv(C, 16);
   int rc = SQD_ERR_UNSUPPORTED;
-#define SQD_SB_CASE(TNv, TCv) if (tn == TNv && tc == TCv) rc = launch_wgrad<1, TNv, TCv, 2, true>(a, S, s);
+#define SQD_SB_CASE(TNv, TCv) if (f.tn == TNv && f.tc == TCv) rc = launch_wgrad<1, TNv, TCv, 2, true>(a, S, s);
   SQD_SB_CASE(1, 1) SQD_SB_CASE(1, 2) SQD_SB_CASE(1, 3) SQD_SB_CASE(1, 4)
   SQD_SB_CASE(2, 1) SQD_SB_CASE(2, 2) SQD_SB_CASE(2, 3) SQD_SB_CASE(2, 4)
   SQD_SB_CASE(3, 1) SQD_SB_CASE(3, 2) SQD_SB_CASE(3, 3) SQD_SB_CASE(3, 4)
@@ -1127,9 +1146,7 @@ static int stem_wgrad_common(StemWgradArgs a, int ksize, int S, float* dw, float
   else if (ksize == 7 && a.N == 96) rc = pooled ? launch_stem_wgrad_pooled<7, 3, 6>(a, S, s) : launch_stem_wgrad<7, 3, 6, false>(a, S, s);
   if (rc != SQD_OK) return rc;
   // slab layout [n][K] is already OIHW-flat: reduce with C := K, TAPS := 1
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((a.slab_stride + WGR_OUT - 1) / WGR_OUT)), dim3(WGR_OUT * WGR_PARTS), 0, s, a.slab, dw, db, S,
-                     a.slab_stride, a.N, K, 1);
-  return sqd_launch_status();
+  return sqd_wgrad_reduce_launch(a.slab, dw, db, S, a.slab_stride, a.N, K, 1, s);
 }
 
 // dy: NHWC [B][Ho][Wo][N] (ReLU-masked); img: NCHW [B][3][Hin][Win]; slab: S*(N*3*k*k + N) floats;

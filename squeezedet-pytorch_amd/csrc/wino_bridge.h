@@ -309,10 +309,8 @@ static int launch_wino_bridge(WinoArgs a, hipStream_t stream) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, NTHR, lds) != hipSuccess || nb < 1) nb = 1;
   const int wgs_per_cu = nb > 4 ? 4 : nb;
   if (int rc = wino_launch_geometry(a, WV)) return rc;
-  // (one workgroup walks every pass of its groups: no slice axis and no rounding of the grid to 8, unlike wino_grid)
-  const int slots = sqd_num_cus() * ((a.wg_cap > 0 && a.wg_cap < wgs_per_cu) ? a.wg_cap : wgs_per_cu);
-  const int per_wg = sqd_cdiv(a.ntiles, slots);
-  const int gx = sqd_cdiv(a.ntiles, per_wg);
+  // (one workgroup walks every pass of its groups: no slice axis and no rounding of the grid to 8, unlike sqd_persistent_grid)
+  const int gx = sqd_even_grid(a.ntiles, sqd_resident_slots(wgs_per_cu, a.wg_cap));
   a.nslices = P; a.gx = gx;
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(NTHR), lds, stream, a);
   return sqd_launch_status();
@@ -653,9 +651,7 @@ static int launch_wino_bridge16_t(WinoArgs a, hipStream_t stream) {
   static SqdDevOnce attr_once;                 // (per device: ADVICE round 4)
   if (int rc_attr = sqd_max_lds_once(attr_once, (const void*)kern, 160 * 1024)) return rc_attr;
   if (int rc = wino_launch_geometry(a, WV)) return rc;
-  const int slots = sqd_num_cus();
-  const int per_wg = sqd_cdiv(a.ntiles, slots);
-  const int gx = sqd_cdiv(a.ntiles, per_wg);
+  const int gx = sqd_even_grid(a.ntiles, sqd_num_cus());
   a.nslices3 = first1; a.nslices = first1 + P1; a.gx = gx;
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(NTHR), lds, stream, a);
   return sqd_launch_status();

@@ -407,10 +407,7 @@ static int launch_wino_poolbridge16_t(WinoArgs a, int nseg, hipStream_t stream) 
   a.pb_gseg = sqd_cdiv(a.pb_ng, nseg);
   a.pb_nseg = sqd_cdiv(a.pb_ng, a.pb_gseg);
   a.ngroups = a.B * a.pb_ns * a.pb_nseg;              // tasks
-  const int wgs = sqd_cdiv(a.ngroups, WV);
-  const int slots = sqd_num_cus();
-  const int per_wg = sqd_cdiv(wgs, slots);
-  const int gx = sqd_cdiv(wgs, per_wg);
+  const int gx = sqd_even_grid(sqd_cdiv(a.ngroups, WV), sqd_num_cus());
   a.nslices3 = first1; a.nslices = first1 + P1; a.gx = gx;
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(NTHR), lds, stream, a);
   return sqd_launch_status();

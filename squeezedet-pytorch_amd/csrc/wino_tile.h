@@ -212,13 +212,3 @@ static inline int wino_launch_geometry(Args& a, int WV) {
   a.ntiles = sqd_cdiv(a.ngroups, WV);
   return SQD_OK;
 }
-
-// Persistent grid of a sliced launch: gx tile streams (a multiple of 8: one run of super-groups per XCD) x nslices channel
-// slices on the device's resident workgroup slots (wgs_per_cu, capped by a.wg_cap); every stream gets the same tile count.
-template <class Args>
-static inline int wino_grid(const Args& a, int nslices, int wgs_per_cu) {
-  const int slots = sqd_num_cus() * ((a.wg_cap > 0 && a.wg_cap < wgs_per_cu) ? a.wg_cap : wgs_per_cu);
-  int gx_max = slots / nslices; if (gx_max < 1) gx_max = 1;
-  const int per_wg = sqd_cdiv(a.ntiles, gx_max);
-  return (sqd_cdiv(a.ntiles, per_wg) + 7) & ~7;
-}

@@ -4,6 +4,7 @@ shapes, the feasibility predicates of every kernel family (LDS budgets, channel 
 weight-gradient kernels.  Pure host logic: nothing here launches a kernel."""
 from __future__ import annotations
 
+import functools
 import math  # noqa: F401
 
 from . import _native as nat
@@ -377,30 +378,42 @@ def wino_wgrad_groups(layers, wino=None, enabled=None):
     return out
 
 
-def _wgrad1x1_tc(C):
-    """In-channel tiles of 16 per workgroup of the direct 1x1 weight-gradient kernel for N >= 64 layers (csrc/wgrad.hip sqd_conv_wgrad)."""
-    return 8 if C >= 256 else (4 if C >= 64 else -(-C // 16))
+WGRAD_PLAIN, WGRAD_GROUP, WGRAD_FUSED = 0, 1, 2       # sqd_conv_wgrad, sqd_conv_wgrad_group, sqd_squeeze_bwd
+
+
+@functools.lru_cache(maxsize=None)
+def wgrad_tile_form(kind, taps, N, C):
+    """(tn, tc, pixels per block) of the direct weight-gradient launch of a layer, as the library decides it (``sqd_wgrad_tile_form``:
+    out- / in-channel tiles of 16 per workgroup, pixels per block of the split pixel axis); None where that entry refuses the shape."""
+    import ctypes
+    tn, tc, px = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = nat.lib().sqd_wgrad_tile_form(kind, taps, N, C, ctypes.byref(tn), ctypes.byref(tc), ctypes.byref(px))
+    if rc == nat.ERR_UNSUPPORTED:
+        return None
+    nat.check(rc, 'sqd_wgrad_tile_form')
+    return tn.value, tc.value, px.value
 
 
 def wgrad1x1_groups(layers, enabled=None):
     """Which 1x1 weight gradients that do NOT run in the fused squeeze backward share a launch (``ops.conv_wgrad_group``).  ``layers``:
-    [(key, N, C, B, H, W)] in launch (backward) order.  Returns {key: (group id, S, tc, member keys)}: same pixel grid, 64-out-channel
-    tile form (N >= 64, not 64 < N <= 96), same in-channel tile, at least two members (at most WINO_WGRAD_GROUP_MAX per launch).
+    [(key, N, C, B, H, W)] in launch (backward) order.  Returns {key: (group id, S, tc, member keys)}: same pixel grid, a tile form the
+    grouped entry accepts (``wgrad_tile_form``: 64 out-channels, i.e. N >= 64 and not 64 < N <= 96), same in-channel tile, at least two
+    members (at most WINO_WGRAD_GROUP_MAX per launch).
     S = the splits every member is cut into: one resident round of workgroups over the whole group ('G1:tc:groups:npix' overrides)."""
     if not (WINO_WGRAD_GROUP if enabled is None else enabled):
         return {}
     buckets = {}
     for key, N, C, B, H, W in layers:
-        if N >= 64 and not (64 < N <= 96) and N % 4 == 0 and C % 4 == 0:
-            buckets.setdefault((B, H, W, _wgrad1x1_tc(C)), []).append((key, N, C))
+        form = wgrad_tile_form(WGRAD_GROUP, 1, N, C) if (N % 4 == 0 and C % 4 == 0) else None
+        if form is not None:
+            buckets.setdefault((B, H, W) + form, []).append((key, N, C))
     out, gid = {}, 1000
-    for (B, H, W, tc), members in buckets.items():
+    for (B, H, W, tn, tc, pb), members in buckets.items():
         for lo in range(0, len(members), WINO_WGRAD_GROUP_MAX):
             part = members[lo:lo + WINO_WGRAD_GROUP_MAX]
             if len(part) < 2:
                 continue
-            groups = sum(-(-N // 64) * -(-C // (16 * tc)) for _k, N, C in part)
-            pb = 64 if tc == 1 else 32                     # pixels per block of the tile form (TH * 16)
+            groups = sum(-(-N // (16 * tn)) * -(-C // (16 * tc)) for _k, N, C in part)
             nblocks = -(-(B * H * W) // pb)
             S = max(1, min(nblocks, _TARGET_WGS_1X1 // groups if groups <= _TARGET_WGS_1X1 else 1))
             tuned = _tuning().get(f'G1:{tc}:{groups}:{B * H * W}')
@@ -434,33 +447,22 @@ def wgrad_split(N, C, taps, B, H, W, wino=None, fused_dgrad=False, group_S=None)
             S = max(1, min(ngroups, int(tuned)))
         return S, N * taps * C + N
     if fused_dgrad:
-        if taps != 1 or N > 128:
+        form = wgrad_tile_form(WGRAD_FUSED, taps, N, C) if taps == 1 else None
+        if form is None:
             raise ValueError('fused 1x1 backward: 1x1 layers with N <= 128')
-        nblocks = -(-(B * H * W) // 32)
-        groups = -(-C // 64)
+        _tn, tc, pb = form
+        nblocks = -(-(B * H * W) // pb)
+        groups = -(-C // (16 * tc))
         target = _TARGET_WGS_SQBWD
         S = max(1, min(nblocks, target // groups, 1024))
         if tuned is not None and tuned >= 1:
             S = max(1, min(nblocks, int(tuned), 1024))
         return S, N * C + N
-    tn = 4 if N >= 64 else -(-N // 16)
+    tn, tc, pb = wgrad_tile_form(WGRAD_PLAIN, taps, N, C)
     if taps == 9:
-        if 64 < N <= 80:
-            tn, tc = 5, 1
-        elif tn == 4:
-            tc = 2 if C % 32 == 0 else 1
-        elif tn in (1, 2):
-            tc = 2
-        else:
-            tc = 1
-        nblocks = B * -(-H // 4) * -(-W // 16)
+        nblocks = B * -(-H // (pb // 16)) * -(-W // 16)
     else:
-        tc = 4 if C >= 64 else -(-C // 16)
-        if 64 < N <= 96:                        # (mirrors csrc/wgrad.hip sqd_conv_wgrad: 128-channel in-tiles, N = 96 as one 6-tile group)
-            tn = 6
-        if C >= 256:
-            tc = 8
-        nblocks = -(-(B * H * W) // 128)
+        nblocks = -(-(B * H * W) // 128)        # (128 pixels = the largest block of any 1x1 form: S stays within the blocks of whichever runs)
     groups = -(-N // (tn * 16)) * -(-C // (tc * 16))
     S = max(1, min(nblocks, (_TARGET_WGS if taps == 9 else _TARGET_WGS_1X1) // groups, 256))
     if tuned is not None and tuned >= 1:

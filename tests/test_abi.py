@@ -78,6 +78,34 @@ def test_status_codes_without_gpu():
     assert lib.sqd_detect_fwd(null, null, null, null, null, null, null, null, null, 1, 1, 3, 1, 1, 64, 0.4, 0.3, null) == 1
 
 
+def test_wgrad_tile_form_without_gpu():
+    """sqd_wgrad_tile_form is declared, bound and answers on the host: a form for each entry point (kind 0 = sqd_conv_wgrad,
+    1 = sqd_conv_wgrad_group, 2 = sqd_squeeze_bwd), NULL outputs allowed, status codes for what the entries refuse."""
+    from squeezedet_pytorch_amd import _native as nat
+    assert 'sqd_wgrad_tile_form' in _header_protos() and 'sqd_wgrad_tile_form' in nat._SIGNATURES
+    lib = nat.lib()
+
+    def form(kind, taps, N, C):
+        tn, tc, px = (ctypes.c_int(-1) for _ in range(3))
+        rc = lib.sqd_wgrad_tile_form(kind, taps, N, C, ctypes.byref(tn), ctypes.byref(tc), ctypes.byref(px))
+        return rc, (tn.value, tc.value, px.value)
+    assert form(0, 1, 384, 512) == (0, (4, 8, 32))           # launch_wgrad<1, 4, 8, 2>
+    assert form(0, 1, 16, 16) == (0, (1, 1, 128))            # launch_wgrad<1, 1, 1, 8>
+    assert form(0, 1, 96, 64) == (0, (6, 4, 32))             # one 6-tile group
+    assert form(0, 9, 72, 768) == (0, (5, 1, 64))            # ConvDet
+    assert form(0, 9, 64, 64) == (0, (4, 2, 64))
+    assert form(0, 9, 64, 48) == (0, (4, 1, 64))
+    assert form(1, 1, 64, 16) == (0, (4, 1, 64))             # launch_wgrad_group<4, 1, 4>
+    assert form(1, 1, 256, 384) == (0, (4, 8, 32))
+    assert form(2, 1, 128, 64) == (0, (8, 4, 32))            # launch_wgrad<1, 8, 4, 2, true>
+    assert form(2, 1, 16, 96) == (0, (1, 4, 32))
+    assert lib.sqd_wgrad_tile_form(0, 1, 64, 64, None, None, None) == 0
+    for bad in ((3, 1, 64, 64), (-1, 1, 64, 64), (0, 3, 64, 64), (0, 1, 0, 64), (0, 1, 64, 0)):
+        assert form(*bad) == (nat.ERR_BAD_ARG, (-1, -1, -1)), bad
+    for refused in ((1, 1, 48, 64), (1, 1, 96, 64), (1, 9, 64, 64), (2, 1, 132, 64), (2, 9, 64, 64)):
+        assert form(*refused) == (nat.ERR_UNSUPPORTED, (-1, -1, -1)), refused
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from squeezedet_pytorch_amd import _native as nat
     monkeypatch.setattr(nat, "_lib", None)

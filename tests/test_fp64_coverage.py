@@ -352,6 +352,47 @@ def test_wgrad_blocking_restates_the_launchers():
             assert S <= -(-(B * H * W) // P), (B, H, W, N, C, S, P)
 
 
+def test_wgrad_tile_form_agrees_with_the_restatement():
+    """The library's own tile-form rule (``sqd_wgrad_tile_form``, the one the host sizes its splits from) against the independent
+    restatement ``L.wgrad_blocking`` on pixels per block, over every width the rule branches on (N up to 128 in steps of 4, the wide
+    and ConvDet widths; C likewise) for the plain entry at 1 and 9 taps and the grouped and fused entries where they accept the shape;
+    and ``tiles.wgrad_split``'s S within the library's own block count on the grids of the test above."""
+    from squeezedet_pytorch_amd import ops, tiles
+    Ns = list(range(4, 129, 4)) + [192, 256, 288, 384, 2340]
+    Cs = list(range(4, 65, 4)) + [96, 128, 256, 384, 512, 768]
+    grids = ((1, 3, 3), (3, 4, 6), (2, 11, 19), (1, 12, 39), (20, 24, 78))
+    seen = {tiles.WGRAD_GROUP: 0, tiles.WGRAD_FUSED: 0}
+    for N in Ns:
+        for C in Cs:
+            tn, tc, px = tiles.wgrad_tile_form(tiles.WGRAD_PLAIN, 1, N, C)
+            assert L.wgrad_blocking('conv_wgrad', N, C, 1) == (('px', px), 1), (N, C, px)
+            assert tn * 16 >= min(N, 64) and tc * 16 >= min(C, 64), (N, C, tn, tc)
+            tn9, tc9, px9 = tiles.wgrad_tile_form(tiles.WGRAD_PLAIN, 9, N, C)
+            assert L.wgrad_blocking('conv_wgrad', N, C, 9) == ('tile', 1) and px9 == 4 * 16, (N, C, px9)      # 'tile': 4x16-pixel windows
+            forms = {(1, False): (tn, tc, px), (9, False): (tn9, tc9, px9)}
+            grp = tiles.wgrad_tile_form(tiles.WGRAD_GROUP, 1, N, C)
+            assert (grp is not None) == (N >= 64 and not 64 < N <= 96), (N, C)
+            if grp is not None:
+                assert L.wgrad_blocking('conv_wgrad_group', N, C, 1) == (('px', grp[2]), 1), (N, C, grp)
+                assert grp == (tn, tc, px), (N, C, grp)                # bitwise the slabs of sqd_conv_wgrad: the same form
+                seen[tiles.WGRAD_GROUP] += 1
+            fus = tiles.wgrad_tile_form(tiles.WGRAD_FUSED, 1, N, C)
+            assert (fus is not None) == (N <= 128), (N, C)
+            if fus is not None:
+                assert L.wgrad_blocking('squeeze_bwd', N, C, 1) == (('px', fus[2]), 1), (N, C, fus)
+                assert fus[0] * 16 >= N, (N, C, fus)                   # all of N in one out-channel group
+                forms[(1, True)] = fus
+                seen[tiles.WGRAD_FUSED] += 1
+            for (taps, fused), (_tn, _tc, p) in forms.items():
+                for B, H, W in grids:
+                    S, stride = ops.wgrad_split(N, C, taps, B, H, W, wino=False, fused_dgrad=fused)
+                    blocks = B * -(-H // (p // 16)) * -(-W // 16) if taps == 9 else -(-(B * H * W) // p)
+                    assert 1 <= S <= blocks and stride == N * taps * C + N, (N, C, taps, fused, B, H, W, S, blocks)
+    assert seen[tiles.WGRAD_GROUP] == 14 * len(Cs) and seen[tiles.WGRAD_FUSED] == 32 * len(Cs)
+    for kind in (tiles.WGRAD_GROUP, tiles.WGRAD_FUSED):                # 1x1 entries only
+        assert tiles.wgrad_tile_form(kind, 9, 64, 64) is None
+
+
 def _rand(*shape, seed, relu=False):
     g = torch.Generator().manual_seed(seed)
     t = torch.randn(*shape, generator=g, dtype=torch.float64)

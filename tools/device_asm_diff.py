@@ -1,0 +1,133 @@
+"""Is the gfx950 device code of two source trees the same, kernel by kernel?  Needs no GPU.
+
+usage: python tools/device_asm_diff.py OLD_CSRC NEW_CSRC [--work DIR] [--jobs N]
+
+Every file of the Makefile's SRCS is compiled on both sides with the flags the Makefile gives that file, plus
+--cuda-device-only -S.  The listings are split by kernel symbol; basic-block label numbers (BB<n>_ -> BB_), comments and
+whitespace are normalised; then the kernel symbol sets, each kernel's instruction text and each kernel's .amdhsa_kernel
+descriptor (registers, LDS, scratch) are compared.  Prints one line per file and every difference; exit status 1 if any
+kernel differs or exists on one side only (a host-only refactor lists the instantiations it removed on purpose)."""
+import argparse
+import os
+import re
+import shlex
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+
+def srcs(csrc):
+    for line in open(os.path.join(csrc, 'Makefile')):
+        if line.startswith('SRCS'):
+            return line.split('=', 1)[1].split()
+    raise SystemExit(f'no SRCS in {csrc}/Makefile')
+
+
+def compile_cmd(csrc, src):
+    """the hipcc line `make` would run for src, up to its -c"""
+    obj = src.replace('.hip', '.o')
+    out = subprocess.run(['make', '-C', csrc, '-n', '-B', obj], capture_output=True, text=True, check=True).stdout
+    line = next(l for l in out.splitlines() if 'hipcc' in l and f' {src} ' in l)
+    toks = shlex.split(line.split(' 2>')[0])
+    return toks[:toks.index('-c')]
+
+
+def listing(csrc, src, work):
+    dst = os.path.join(work, src.replace('.hip', '.s'))
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(('.hip', '.h')) or f == 'Makefile']
+    if os.path.exists(dst) and os.path.getmtime(dst) > max(os.path.getmtime(d) for d in deps):
+        return dst
+    r = subprocess.run(compile_cmd(csrc, src) + ['--cuda-device-only', '-S', src, '-o', os.path.abspath(dst)], cwd=csrc, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise SystemExit(f'{csrc}/{src}: {r.stderr[-2000:]}')
+    return dst
+
+
+def norm(line):
+    line = line.split(';', 1)[0]
+    line = re.sub(r'BB\d+_', 'BB_', line)
+    return ' '.join(line.split())
+
+
+def kernels(path):
+    """{symbol: (instruction text, descriptor text)}"""
+    lines = open(path).read().splitlines()
+    desc, cur = {}, None
+    for l in lines:
+        s = l.strip()
+        if s.startswith('.amdhsa_kernel '):
+            cur = s.split()[1]
+            desc[cur] = []
+        elif s == '.end_amdhsa_kernel':
+            cur = None
+        elif cur is not None:
+            desc[cur].append(norm(s))
+    body, cur, in_desc = {}, None, False
+    for l in lines:
+        s = l.strip()
+        if s.startswith('.amdhsa_kernel ') or s == '.end_amdhsa_kernel':      # (the descriptor may sit before the function's end label)
+            in_desc = s != '.end_amdhsa_kernel'
+        elif in_desc:
+            pass
+        elif cur is None:
+            m = re.match(r'(\S+):', s)                 # "symbol:   ; @symbol"
+            if m and m.group(1) in desc:
+                cur = m.group(1)
+                body[cur] = []
+        elif re.match(r'\.Lfunc_end\d+:', s):
+            cur = None
+        else:
+            n = norm(s)
+            if n:
+                body[cur].append(n)
+    empty = [k for k in desc if not body.get(k)]
+    if empty:
+        raise SystemExit(f'{path}: no instructions found for {empty[:3]} ...: the listing format is not the one this script reads')
+    return {k: ('\n'.join(body[k]), '\n'.join(desc[k])) for k in desc}
+
+
+def demangle(names):
+    if not names:
+        return []
+    r = subprocess.run(['c++filt'], input='\n'.join(names), capture_output=True, text=True)
+    return r.stdout.splitlines() if r.returncode == 0 else list(names)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('old')
+    ap.add_argument('new')
+    ap.add_argument('--work', default=None, help='keeps the listings (old/ and new/) for reuse')
+    ap.add_argument('--jobs', type=int, default=4)
+    a = ap.parse_args()
+    work = a.work or tempfile.mkdtemp(prefix='device_asm_diff_')
+    files = srcs(a.old)
+    if files != srcs(a.new):
+        print(f'SRCS differ: {files} vs {srcs(a.new)}')
+        return 1
+    for side in ('old', 'new'):
+        os.makedirs(os.path.join(work, side), exist_ok=True)
+    jobs = [(side, csrc, f) for f in files for side, csrc in (('old', a.old), ('new', a.new))]
+    with ThreadPoolExecutor(a.jobs) as ex:
+        paths = dict(zip([(s, f) for s, _, f in jobs], ex.map(lambda j: listing(j[1], j[2], os.path.join(work, j[0])), jobs)))
+    bad = total = 0
+    for f in files:
+        ko, kn = kernels(paths[('old', f)]), kernels(paths[('new', f)])
+        gone, added = sorted(set(ko) - set(kn)), sorted(set(kn) - set(ko))
+        text = [k for k in sorted(set(ko) & set(kn)) if ko[k][0] != kn[k][0]]
+        dsc = [k for k in sorted(set(ko) & set(kn)) if ko[k][1] != kn[k][1]]
+        same = len(set(ko) & set(kn)) - len(set(text) | set(dsc))
+        print(f'{f}: {len(ko)} kernels before, {len(kn)} after, {same} identical (text and descriptor), '
+              f'{len(gone)} removed, {len(added)} added, {len(text)} text differs, {len(dsc)} descriptor differs')
+        for tag, ks in (('removed', gone), ('added', added), ('TEXT DIFFERS', text), ('DESCRIPTOR DIFFERS', dsc)):
+            for k in demangle(ks):
+                print(f'    {tag}: {k}')
+        bad += len(gone) + len(added) + len(set(text) | set(dsc))
+        total += len(ko)
+    print(f'total: {total} kernels before; {bad} removed, added or different')
+    return 1 if bad else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
