@@ -165,6 +165,10 @@ def _make_drop_mask(base, device):
 
 
 def backbone_apply(base, image):
+    if torch.is_grad_enabled() and isinstance(image, torch.Tensor) and image.requires_grad:
+        # (torch would hand back image.grad; the backward stops at the stem's weight gradient, so it would stay None without a word)
+        raise RuntimeError('SqueezeDetBase: the input image requires grad, but the HIP backward computes no gradient with respect to '
+                           'the image (it ends at the stem\'s weight gradient).  Pass image.detach(), or run under torch.no_grad().')
     train_drop = base.training and base.dropout is not None
     drop_mask = drop = None
     if train_drop:

@@ -178,20 +178,46 @@ def run_backbone_backward(base, saved, dpred):
     return {n: gview(n) for n in slots}
 
 
+def _param_state(params):
+    """What the backward's operands looked like at the forward: the staleness rule of the plan cache (plans.version), per parameter."""
+    return [(p._version, p.data_ptr()) for p in params]
+
+
 class BackboneFn(torch.autograd.Function):
+    """The autograd contract around the node ("autograd contract"): the backward reads the parameters LIVE (the plan
+    cache re-packs the data-gradient operands from them, ops.squeeze_bwd takes expand1x1 / squeeze weights as they are), so a parameter
+    changed since the forward is refused with torch's own error instead of mixing old activations with new weights; the saved
+    activations are freed by the first backward, a second one is refused (``retain_graph`` would keep them alive through the
+    optimizer step of every training loop)."""
+
     @staticmethod
     def forward(ctx, base, image, drop_mask, drop, *params):
         pred, saved = run_backbone_forward(base, image.detach(), save=True, drop_mask=drop_mask, drop=drop)
         ctx.base = base
         ctx.saved = saved
         ctx.names = [n for n, _ in base.named_parameters()]
+        ctx.params = params
+        ctx.param_state = _param_state(params)
         return pred
 
     @staticmethod
     def backward(ctx, dpred):
+        if ctx.saved is None:
+            raise RuntimeError('Trying to backward through the graph a second time: SqueezeDetBase frees its saved activations after '
+                               'the first backward, with or without retain_graph=True (keeping them would raise the peak memory of '
+                               'every training step).  Run the forward again for another backward.')
+        for n, p, was in zip(ctx.names, ctx.params, ctx.param_state):
+            now = (p._version, p.data_ptr())
+            if now != was:
+                raise RuntimeError(f'one of the variables needed for gradient computation has been modified by an inplace operation: '
+                                   f'parameter {n} of SqueezeDetBase is at version {now[0]}; expected version {was[0]} instead'
+                                   + ('' if now[1] == was[1] else ' (and its storage was replaced)')
+                                   + '.  The backward reads the parameters as they are now: run it before the optimizer step / EMA '
+                                   'update, or run the forward again.')
         grads = run_backbone_backward(ctx.base, ctx.saved, dpred)
         ctx.saved = None
-        return (None, None, None, None) + tuple(grads[n] for n in ctx.names)
+        ctx.params = None
+        return (None, None, None, None) + tuple(grads[n] if need else None for n, need in zip(ctx.names, ctx.needs_input_grad[4:]))
 
 
 class LossFn(torch.autograd.Function):
