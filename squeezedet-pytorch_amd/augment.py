@@ -3,7 +3,7 @@ flip active; src/utils/image.py:22-74 ``drift`` / ``flip``, then ``resize`` :77-
 
 The random parameters are drawn on the host, in the reference's order and with the reference's arguments
 (``draw_augmentation``); the boxes are transformed on the host in float32, op for op as the reference does (``transform_boxes``);
-the pixels go up as packed uint8 and ONE launch (``sqd_preprocess_u8_aug_fwd`` / ``sqd_preprocess_u8_padcrop_aug_fwd``)
+the pixels go up as packed uint8 and ONE launch (``preprocess.launch_u8``: the ``_aug_`` entry of the geometry)
 whitens, drifts, flips, resizes (or pads / crops) and transposes the whole batch.  The dense ``gt`` is then encoded on the device
 (``annotations.encode_annotations``).
 
@@ -13,13 +13,12 @@ gets drift 0 on that axis and consumes no draw for it.
 
 Colour jitter (this project's own rule, DESIGN.md 6b "Colour jitter"; off by default): per-image brightness / contrast / saturation
 factors (``draw_color``) ride in the header of the same upload; ``launch`` then sums the image's channels on the device
-(``sqd_image_stats_u8``, the contrast pivot) and calls the colour entry points (``sqd_preprocess_u8_aug_color_fwd`` /
-``sqd_preprocess_u8_padcrop_aug_color_fwd``) on the same stream.  The boxes and the geometric draws do not depend on it.
+(``sqd_image_stats_u8``, the contrast pivot) and calls the geometry's ``_aug_color_`` entry on the same stream.  The boxes and the geometric draws do not depend on it.
 
 Letterbox and zoom-out (this project's own rule, DESIGN.md 6b "Letterbox and zoom-out"; off by default): the drifted, flipped image
 is resized with its aspect ratio kept into a window of the canvas (``boxes.letterbox_window``) and the rest is the whitened mean, 0.
 Zoom-out (``draw_zoom``) shrinks that window and places it at random; the window rides in the header of the same upload and the
-``sqd_preprocess_u8_letterbox_aug_fwd`` / ``_aug_color_fwd`` launch reads it there.  No box is ever lost.
+letterbox launch reads it there.  No box is ever lost.
 """
 from __future__ import annotations
 
@@ -28,9 +27,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _native as nat
-from .boxes import letterbox_meta, letterbox_window
-from .preprocess import KITTI_RGB_MEAN, KITTI_RGB_STD, _staging
+from .boxes import letterbox_meta, letterbox_window, pad_crop
+from .preprocess import KITTI_RGB_MEAN, KITTI_RGB_STD, _staging, launch_u8
 
 HDR_ALIGN = 256          # the packed pixels start this many bytes into the upload, after the int header
 
@@ -118,15 +116,6 @@ def check_color(color, B):
     return color.reshape(B, 3)
 
 
-def _pad_crop(size, target):
-    """crop_or_pad's integers for one axis (image.py:99-115): (pad front, pad back, crop front, crop back)."""
-    if size < target:
-        return (target - size) // 2, (target - size) - (target - size) // 2, 0, 0
-    if size > target:
-        return 0, 0, (size - target) // 2, (size - target) - (size - target) // 2
-    return 0, 0, 0, 0
-
-
 def transform_boxes(boxes, orig_size, aug, input_size, forbid_resize=False, letterbox=False, window=None):
     """The box half of the train-phase ``preprocess`` for one image, in float32 and in the reference's order: clip to the original
     image, subtract the drift, flip with the drifted width, then scale by ``scales`` (or shift by padding / crops).
@@ -163,8 +152,8 @@ def transform_boxes(boxes, orig_size, aug, input_size, forbid_resize=False, lett
         b[:, [1, 3]] *= scales[0]
         meta['scales'] = scales
         return b, meta
-    pt, pb, ct, cb = _pad_crop(Hd, H)
-    pl, pr, cl, cr = _pad_crop(Wd, W)
+    pt, pb, ct, cb = pad_crop(Hd, H)
+    pl, pr, cl, cr = pad_crop(Wd, W)
     padding, crops = np.array([pt, pb, pl, pr], np.int16), np.array([ct, cb, cl, cr], np.int16)
     if not np.all(padding == 0):
         # as the reference's ``pad`` (image.py:133-137): it rebinds ``padding`` to np.pad's ((top, bottom), (left, right), (0, 0))
@@ -250,54 +239,29 @@ def launch(dev_buf, B, hdr, input_size, out, forbid_resize, rgb_mean, rgb_std, c
     int64 [B, 3, 2] on the device, allocated when not given) and the colour entry point follows on the same stream: no host
     synchronisation, nothing is copied back."""
     H, W = int(input_size[0]), int(input_size[1])
-    base = dev_buf.data_ptr()
+    base, dev = dev_buf.data_ptr(), dev_buf.device
     p = lambda off: ctypes.c_void_p(base + off)      # noqa: E731
-    mean = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_mean).reshape(-1)])
-    std = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_std).reshape(-1)])
-    stream = nat.stream_handle(dev_buf.device)
     if letterbox and forbid_resize:
         raise ValueError('launch: letterbox and forbid_resize are two different input geometries')
     if color and hdr < 40 * B:
         raise ValueError(f'launch: a header of {hdr} bytes has no room for the colour factors of {B} images')
     if window and (not letterbox or hdr < window_offset(B, color) + 16 * B):
         raise ValueError(f'launch: a header of {hdr} bytes has no room for the letterbox windows of {B} images (or letterbox is off)')
-    if letterbox:
-        side = torch.empty(2, B, 2, device=dev_buf.device, dtype=torch.float32)
-        win = p(window_offset(B, color)) if window else None
-        if color:
-            from .ops import image_stats_u8
-            sums = image_stats_u8(dev_buf, B, hdr, out=sums)
-            rc = nat.lib().sqd_preprocess_u8_letterbox_aug_color_fwd(p(hdr), p(0), p(8 * B), p(16 * B), win, p(28 * B), nat.ptr(sums), nat.ptr(out),
-                                                                     nat.ptr(side[0]), nat.ptr(side[1]), mean, std, B, H, W, stream)
-            nat.check(rc, 'sqd_preprocess_u8_letterbox_aug_color_fwd')
-        else:
-            rc = nat.lib().sqd_preprocess_u8_letterbox_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), win, nat.ptr(out), nat.ptr(side[0]),
-                                                               nat.ptr(side[1]), mean, std, B, H, W, stream)
-            nat.check(rc, 'sqd_preprocess_u8_letterbox_aug_fwd')
-        return side
+    blocks = {}
     if color:
         from .ops import image_stats_u8
-        sums = image_stats_u8(dev_buf, B, hdr, out=sums)
-        if forbid_resize:
-            side = torch.empty(B, 8, device=dev_buf.device, dtype=torch.int32)
-            rc = nat.lib().sqd_preprocess_u8_padcrop_aug_color_fwd(p(hdr), p(0), p(8 * B), p(16 * B), p(28 * B), nat.ptr(sums), nat.ptr(out),
-                                                                   None, nat.ptr(side), mean, std, B, H, W, stream)
-            nat.check(rc, 'sqd_preprocess_u8_padcrop_aug_color_fwd')
-        else:
-            side = torch.empty(B, 2, device=dev_buf.device, dtype=torch.float32)
-            rc = nat.lib().sqd_preprocess_u8_aug_color_fwd(p(hdr), p(0), p(8 * B), p(16 * B), p(28 * B), nat.ptr(sums), nat.ptr(out),
-                                                           nat.ptr(side), mean, std, B, H, W, stream)
-            nat.check(rc, 'sqd_preprocess_u8_aug_color_fwd')
-        return side
-    if forbid_resize:
-        side = torch.empty(B, 8, device=dev_buf.device, dtype=torch.int32)
-        rc = nat.lib().sqd_preprocess_u8_padcrop_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), nat.ptr(out), None, nat.ptr(side),
-                                                         mean, std, B, H, W, stream)
-        nat.check(rc, 'sqd_preprocess_u8_padcrop_aug_fwd')
+        blocks.update(color=p(28 * B), sums=image_stats_u8(dev_buf, B, hdr, out=sums))
+    if letterbox:
+        side = torch.empty(2, B, 2, device=dev, dtype=torch.float32)
+        blocks.update(win=p(window_offset(B, color)) if window else None, scales=side[0], shifts=side[1])
+    elif forbid_resize:
+        side = torch.empty(B, 8, device=dev, dtype=torch.int32)
+        blocks.update(padcrop=side)
     else:
-        side = torch.empty(B, 2, device=dev_buf.device, dtype=torch.float32)
-        rc = nat.lib().sqd_preprocess_u8_aug_fwd(p(hdr), p(0), p(8 * B), p(16 * B), nat.ptr(out), nat.ptr(side), mean, std, B, H, W, stream)
-        nat.check(rc, 'sqd_preprocess_u8_aug_fwd')
+        side = torch.empty(B, 2, device=dev, dtype=torch.float32)
+        blocks.update(scales=side)
+    launch_u8('letterbox' if letterbox else 'padcrop' if forbid_resize else 'resize', p(hdr), p(0), p(8 * B), out, B, H, W, rgb_mean, rgb_std,
+              dev, aug=p(16 * B), **blocks)
     return side
 
 

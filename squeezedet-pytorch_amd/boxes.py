@@ -138,9 +138,19 @@ def boxes_postprocess(boxes, image_meta):
     return boxes
 
 
+def pad_crop(size, target):
+    """``crop_or_pad``'s integers for one axis (src/utils/image.py:99-115; ``preprocess_padcrop_body`` in csrc/preproc.hip evaluates the
+    same): (pad front, pad back, crop front, crop back) -- a smaller image is padded, a larger one centre-cropped, floor half in front."""
+    if size < target:
+        return (target - size) // 2, (target - size) - (target - size) // 2, 0, 0
+    if size > target:
+        return 0, 0, (size - target) // 2, (size - target) - (size - target) // 2
+    return 0, 0, 0, 0
+
+
 def letterbox_window(size, canvas):
     """The centred letterbox window of an image of ``size`` = (Hd, Wd) on a ``canvas`` = (H, W): (top, left, h1, w1), the image
-    scaled with its aspect ratio kept so that it just fits.  Integers only, the expressions ``preprocess_letterbox_body``
+    scaled with its aspect ratio kept so that it just fits.  Integers only, the expressions ``preprocess_bilinear_body``
     (csrc/preproc.hip) evaluates in 64 bits: height-limited (``H * Wd <= W * Hd``) ``h1 = H, w1 = max(1, (Wd * H + Hd // 2) // Hd)``,
     else ``w1 = W, h1 = max(1, (Hd * W + Wd // 2) // Wd)``; ``top = (H - h1) // 2``, ``left = (W - w1) // 2``."""
     Hd, Wd = int(size[0]), int(size[1])

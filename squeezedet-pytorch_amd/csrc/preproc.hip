@@ -11,6 +11,10 @@
 // (0, 0); if sx >= W0 - 1 -> (sx, fx) = (W0 - 1, 0); likewise y; value = (1-fy) * ((1-fx) * s00 + fx * s01) +
 // fy * ((1-fx) * s10 + fx * s11), horizontal pass first, all in float32.  Uploading uint8 instead of the
 // reference's fp32 cuts host->device bytes 4x (5.75 MB -> ~1.4 MB per KITTI image).
+//
+// Three geometries (resize, crop_or_pad, letterbox) x three forms (eval, AUG, AUG + COLOR) = nine kernels and nine entry points, from
+// two device bodies (preprocess_bilinear_body: resize and letterbox; preprocess_padcrop_body) that share the per-image prologue
+// (pre_image), the whitening table (pre_build_table) and the staging (pre_stage), and one host-side check / fill / launch path.
 #include "sqd_common.h"
 
 struct PreArgs {
@@ -23,23 +27,14 @@ struct PreArgs {
   int B, H, W;
 };
 
-// Both kernels: a workgroup produces 256 consecutive pixels of one output row.  The source bytes it needs are one or two CONTIGUOUS
+// All kernels: a workgroup produces 256 consecutive pixels of one output row.  The source bytes it needs are one or two CONTIGUOUS
 // row segments, so they are fetched once as aligned dwords (coalesced) into LDS and the per-pixel 3-byte gathers read LDS -- a byte
 // gather from global memory is one texture-addresser instruction per byte and wave (12 per pixel for the bilinear taps: ~50 us of
 // address processing for a 20-image batch, against 25 us of HBM time for its 143 MB).  Whitening is a 256-entry table per channel,
 // ((float)v - mean) / std evaluated once per workgroup with the same float32 subtract and IEEE divide the per-pixel form used: bit for bit
 // the same values.  A segment that does not fit the LDS buffer (down-scaling by more than ~10x) takes the direct path.
 constexpr int PRE_ROWB = 8192;                       // bytes of LDS per staged row segment
-
 constexpr int PRE_ROWS = 4;                          // output rows per workgroup (the whitening table is built once for all of them)
-
-__device__ __forceinline__ void pre_build_lut(float* lut, float m0, float m1, float m2, float s0, float s1, float s2) {
-  for (int i = threadIdx.x; i < 768; i += 256) {
-    const int c = i >> 8, v = i & 255;
-    const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    lut[i] = ((float)v - m) / sd;
-  }
-}
 
 // bytes [begin, begin + len) of the image at ``img`` (``img_end`` = one past its last byte) -> dst[shift ...]; returns shift (0..3).
 // Aligned dword loads; a dword that would reach past the image's last byte is assembled from byte loads (the packed buffer may end there).
@@ -91,16 +86,25 @@ __device__ __forceinline__ float pre_color_t(const PreColor& k, float v) {
   return fminf(fmaxf(k.fc * fminf(k.fb * v, 255.f) + k.cp, 0.f), 255.f);
 }
 
-__device__ __forceinline__ void pre_build_lut_color(float* lut, const PreColor& k, float m0, float m1, float m2, float s0, float s1, float s2) {
-  if (k.per_tap) {
-    lut[threadIdx.x] = pre_color_t(k, (float)threadIdx.x);     // (256 threads)
-    return;
+// The workgroup's table (256 threads): whiten(v), or COLOR whiten(t(v)), per channel; COLOR with per_tap only t(v).
+template <bool COLOR>
+__device__ __forceinline__ PreColor pre_build_table(float* lut, const float* color, const unsigned long long* sums, int b, int H0, int W0,
+                                                    const float (&mean)[3], const float (&stdv)[3]) {
+  PreColor k = {};
+  if (COLOR) {
+    k = pre_color_of(color, sums, b, H0, W0);
+    if (k.per_tap) {
+      lut[threadIdx.x] = pre_color_t(k, (float)threadIdx.x);
+      return k;
+    }
   }
+  const float m0 = mean[0], m1 = mean[1], m2 = mean[2], s0 = stdv[0], s1 = stdv[1], s2 = stdv[2];
   for (int i = threadIdx.x; i < 768; i += 256) {
     const int c = i >> 8, v = i & 255;
     const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    lut[i] = (pre_color_t(k, (float)v) - m) / sd;
+    lut[i] = ((COLOR ? pre_color_t(k, (float)v) : (float)v) - m) / sd;
   }
+  return k;
 }
 
 // one tap of the per-tap form: the three bytes at p through the t table, the saturation blend, then whiten
@@ -115,9 +119,9 @@ __device__ __forceinline__ void pre_color_tap(const float* lut, const PreColor& 
 
 // Training augmentation (reference train phase, src/datasets/base.py:43-59 with drift / flip active; src/utils/image.py:22-74): per image
 // aug[b] = (dy, dx, flipped).  The drifted image V is Hd x Wd = (H0 - dy) x (W0 - dx); before the flip V[y][x] = whiten(I[y+dy][x+dx])
-// where y + dy >= 0 and x + dx >= 0, else exactly 0.0f (the reference zero-fills AFTER whitening); the flip reads V[y][Wd-1-x].  Both
-// kernels below are templates on AUG: the resize / crop_or_pad coordinate rule runs in V coordinates (Hd, Wd), and only then is a
-// V column mapped to a column of I, col(v) = (flipped ? Wd-1-v : v) + dx (a row: v + dy).  A tap in the fill region reads 0 and is
+// where y + dy >= 0 and x + dx >= 0, else exactly 0.0f (the reference zero-fills AFTER whitening); the flip reads V[y][Wd-1-x].  Every
+// kernel below is a template on AUG: the resize / crop_or_pad / letterbox coordinate rule runs in V coordinates (Hd, Wd), and only then
+// is a V column mapped to a column of I, col(v) = (flipped ? Wd-1-v : v) + dx (a row: v + dy).  A tap in the fill region reads 0 and is
 // never loaded; a workgroup's source segment is bounded by the mapped columns of its two end pixels (min / max: under a flip the
 // column falls as x rises), clamped to the image, and a row wholly in the fill region is not staged.  dy / dx are clamped to
 // [-2^20, H0-1] / [-2^20, W0-1] so that Hd, Wd >= 1 whatever the buffer holds.  AUG = false is the untouched eval-time kernel.
@@ -127,24 +131,101 @@ __device__ __forceinline__ int pre_drift(const int* aug, int k, int n0) {
   return AUG ? max(min(aug[k], n0 - 1), -(1 << 20)) : 0;
 }
 
-template <bool AUG, bool COLOR>
-__device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug, const float* color, const unsigned long long* sums) {
+// image b of size (H0, W0): (AUG) its clamped drift and flip, and the size (Hd, Wd) of the drifted image V the coordinate rule sees
+// (the bodies load H0 and W0 themselves: inside this struct the pair costs the letterbox kernels an SGPR and reorders pad / crop)
+struct PreView {
+  int dy, dx; bool flip;
+  int Hd, Wd;
+  template <bool AUG> __device__ __forceinline__ int col(int v) const { return AUG ? (flip ? Wd - 1 - v : v) + dx : v; }     // V column -> image column
+};
+
+template <bool AUG>
+__device__ __forceinline__ PreView pre_view(const int* aug, int b, int H0, int W0) {
+  PreView v;
+  v.dy = pre_drift<AUG>(aug, 3 * b, H0); v.dx = pre_drift<AUG>(aug, 3 * b + 1, W0);
+  v.flip = AUG && aug[3 * b + 2] != 0;
+  v.Hd = AUG ? H0 - v.dy : H0; v.Wd = AUG ? W0 - v.dx : W0;
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The third geometry, cfg.letterbox (no reference counterpart; DESIGN.md 6b, "Letterbox and zoom-out"): the drifted, flipped image
+// V (Hd x Wd; eval: the image itself) is resized with its aspect ratio kept into a window (top, left, h1, w1) of the H x W canvas,
+// and everything outside the window is exactly +0.0f -- the whitened mean, as the reference's zero fill after whitening.  Inside
+// the window the value at (y, x) is the resize rule with destination size (h1, w1) evaluated at (y - top, x - left): the same
+// expressions of the same body (LB), so a window that is the whole canvas gives the resize kernel's bits.
+// The window comes from win[B][4] int32 (zoom-out: the host shrinks and places it) or, win == null, from the integer rule
+//   H * Wd <= W * Hd (height-limited):  h1 = H, w1 = max(1, (Wd * H + Hd / 2) / Hd);  else  w1 = W, h1 = max(1, (Hd * W + Wd / 2) / Wd);
+//   top = (H - h1) / 2, left = (W - w1) / 2     (64-bit, integer divisions: boxes.letterbox_window evaluates the same)
+// A given window is clamped into the canvas (h1 to 1..H, w1 to 1..W, then top to 0..H-h1, left to 0..W-w1), in the spirit of pre_drift: no
+// buffer content makes the kernel read or write out of range.  scales = (h1 / Hd, w1 / Wd) (float64 division, cast to float32) and
+// shifts = (-(float)top / sy, -(float)left / sx): box / scales + shifts in the detect kernels is boxes_postprocess with
+// padding = (top / sy, ., left / sx, .), i.e. the padding in original-image pixels.
+// The staged segment is bounded by the workgroup's columns INSIDE the window; a workgroup with no column or no row in the window
+// stores zeros and returns before the table is built; one cut by a window edge takes both cases per thread (the barriers run for
+// every row, window or not).
+// ---------------------------------------------------------------------------------------------------------------------
+struct LetterboxArgs {
+  const unsigned char* src; const long long* offsets; const int* sizes;
+  const int* win;                // [B][4] = (top, left, h1, w1), or null: the centred window of the integer rule
+  float* out; float* scales; float* shifts;
+  float mean[3], stdv[3];
+  int B, H, W;
+};
+
+// The bilinear body of the resize (LB = false, Args = PreArgs) and letterbox (LB = true, Args = LetterboxArgs) geometries.  Everything
+// the window adds sits behind LB: with LB = false the destination is the canvas itself and the expressions are the resize rule's own.
+template <bool LB, bool AUG, bool COLOR, class Args>
+__device__ __forceinline__ void preprocess_bilinear_body(const Args& a, const int* aug, const float* color, const unsigned long long* sums) {
   __shared__ float lut[768];
   __shared__ unsigned rows[2][PRE_ROWB / 4];
   const int b = blockIdx.z;
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int H0 = a.sizes[2 * b], W0 = a.sizes[2 * b + 1];
-  const int dy = pre_drift<AUG>(aug, 3 * b, H0), dx = pre_drift<AUG>(aug, 3 * b + 1, W0);
-  const bool flip = AUG && aug[3 * b + 2] != 0;
-  const int Hd = AUG ? H0 - dy : H0, Wd = AUG ? W0 - dx : W0;     // the (drifted) image the resize rule sees
-  if (x == 0 && blockIdx.y == 0 && a.scales) {
-    a.scales[2 * b] = (float)a.H / (float)Hd;       // np.array([H/H0, W/W0], dtype=float32): float64 division then cast;
-    a.scales[2 * b + 1] = (float)a.W / (float)Wd;   // identical for these integer ratios up to float32 rounding
+  const PreView im = pre_view<AUG>(aug, b, H0, W0);
+  const int dy = im.dy, Hd = im.Hd, Wd = im.Wd;
+  int top = 0, left = 0, h1 = a.H, w1 = a.W;         // the destination window (!LB: the canvas)
+  if constexpr (LB) {
+    if (a.win) {
+      const int* w = a.win + 4 * b;
+      h1 = max(min(w[2], a.H), 1); w1 = max(min(w[3], a.W), 1);
+      top = max(min(w[0], a.H - h1), 0); left = max(min(w[1], a.W - w1), 0);
+    } else {
+      const long long H = a.H, W = a.W, hd = Hd, wd = Wd;
+      if (H * wd <= W * hd) { h1 = a.H; w1 = (int)min(max((wd * H + hd / 2) / hd, 1ll), W); }
+      else { w1 = a.W; h1 = (int)min(max((hd * W + wd / 2) / wd, 1ll), H); }
+      top = (a.H - h1) / 2; left = (a.W - w1) / 2;
+    }
+    if (x == 0 && blockIdx.y == 0 && (a.scales || a.shifts)) {
+      const float sy = (float)((double)h1 / (double)Hd), sx = (float)((double)w1 / (double)Wd);
+      if (a.scales) { a.scales[2 * b] = sy; a.scales[2 * b + 1] = sx; }
+      if (a.shifts) { a.shifts[2 * b] = -(float)top / sy; a.shifts[2 * b + 1] = -(float)left / sx; }
+    }
+  } else {
+    if (x == 0 && blockIdx.y == 0 && a.scales) {
+      a.scales[2 * b] = (float)a.H / (float)Hd;       // np.array([H/H0, W/W0], dtype=float32): float64 division then cast;
+      a.scales[2 * b + 1] = (float)a.W / (float)Wd;   // identical for these integer ratios up to float32 rounding
+    }
+  }
+  const long long plane = (long long)a.H * a.W;
+  // the workgroup's columns and rows, (LB) those inside the window (all uniform)
+  const int xa = blockIdx.x * 256, xb = min(a.W, xa + 256) - 1;
+  const int ia = LB ? max(xa, left) : xa, ib = LB ? min(xb, left + w1 - 1) : xb;
+  const int ya = blockIdx.y * PRE_ROWS, yb = min(a.H, ya + PRE_ROWS) - 1;
+  if constexpr (LB) {
+    if (ia > ib || yb < top || ya >= top + h1) {     // wholly in the fill region: zeros, nothing staged
+      if (x < a.W)
+        for (int y = ya; y <= yb; ++y) {
+          float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
+          o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
+        }
+      return;
+    }
   }
   const unsigned char* img = a.src + a.offsets[b];
   const unsigned char* img_end = img + (long long)H0 * W0 * 3;
-  // source coordinates (double scale like OpenCV, then float weights)
-  const double sclx = (double)Wd / (double)a.W, scly = (double)Hd / (double)a.H;
+  // source coordinates of a destination pixel (double scale like OpenCV, then float weights)
+  const double sclx = (double)Wd / (double)w1, scly = (double)Hd / (double)h1;
   auto src_x = [&](int xx, float& f) {
     f = (float)((xx + 0.5) * sclx - 0.5);
     int sx = (int)floorf(f); f -= (float)sx;
@@ -152,37 +233,31 @@ __device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug
     if (sx >= Wd - 1) { sx = Wd - 1; f = 0.f; }
     return sx;
   };
-  auto col = [&](int v) { return AUG ? (flip ? Wd - 1 - v : v) + dx : v; };     // V column -> image column
-  // the workgroup's source column range [lo, hi] (sx is monotone in x): one segment per source row
+  // the source column range [lo, hi] of the workgroup's (window) columns (sx is monotone in x): one segment per source row
   float fdummy;
-  const int xa = blockIdx.x * 256, xb = min(a.W, xa + 256) - 1;
-  int lo = src_x(xa, fdummy), hi = min(src_x(xb, fdummy) + 1, Wd - 1);
+  int lo = src_x(ia - left, fdummy), hi = min(src_x(ib - left, fdummy) + 1, Wd - 1);
   if (AUG) {
-    const int ca = col(lo), cb = col(hi);
+    const int ca = im.col<AUG>(lo), cb = im.col<AUG>(hi);
     lo = max(min(ca, cb), 0); hi = min(max(ca, cb), W0 - 1);
   }
-  const bool seg = !AUG || hi >= lo;                 // (AUG) false: every column of the workgroup lies in the fill region
+  const bool seg = !AUG || hi >= lo;                 // (AUG) false: every (window) column of the workgroup lies in the drift fill
   const int len = (hi - lo + 1) * 3;
   const bool staged = len + 8 <= PRE_ROWB;
+  const int xc = min(x, a.W - 1);
+  const bool xin = !LB || (xc >= left && xc < left + w1);
   float fx;
-  const int sx = src_x(min(x, a.W - 1), fx);
+  const int sx = src_x(LB ? min(max(xc - left, 0), w1 - 1) : xc, fx);     // (a thread outside the window: the nearest window column, never read)
   const int sx1 = min(sx + 1, Wd - 1);
-  const int cx0 = col(sx), cx1 = col(sx1);
+  const int cx0 = im.col<AUG>(sx), cx1 = im.col<AUG>(sx1);
   const bool vx0 = !AUG || cx0 >= 0, vx1 = !AUG || cx1 >= 0;
   const int ux0 = AUG ? max(cx0, 0) : cx0, ux1 = AUG ? max(cx1, 0) : cx1;     // (a fill tap's address: any in-range one)
   const float ax0 = 1.f - fx, ax1 = fx;
-  const long long plane = (long long)a.H * a.W;
-  PreColor kc = {};
-  if (COLOR) {
-    kc = pre_color_of(color, sums, b, H0, W0);
-    pre_build_lut_color(lut, kc, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
-  } else {
-    pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
-  }
+  const PreColor kc = pre_build_table<COLOR>(lut, color, sums, b, H0, W0, a.mean, a.stdv);
   for (int r = 0; r < PRE_ROWS; ++r) {
-    const int y = blockIdx.y * PRE_ROWS + r;
+    const int y = ya + r;
     if (y >= a.H) break;                             // (uniform)
-    float fy = (float)((y + 0.5) * scly - 0.5);
+    const bool yin = !LB || (y >= top && y < top + h1);       // (uniform)
+    float fy = (float)(((LB ? min(max(y - top, 0), h1 - 1) : y) + 0.5) * scly - 0.5);
     int sy = (int)floorf(fy); fy -= (float)sy;
     if (sy < 0) { sy = 0; fy = 0.f; }
     if (sy >= Hd - 1) { sy = Hd - 1; fy = 0.f; }
@@ -192,14 +267,18 @@ __device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug
     const int uy0 = AUG ? max(ry0, 0) : ry0, uy1 = AUG ? max(ry1, 0) : ry1;
     int sh0 = 0, sh1 = 0;
     if (r) __syncthreads();                          // the previous row's readers are done with the segments
-    if (staged && seg) {
+    if (staged && seg && yin) {
       if (vy0) sh0 = pre_stage(rows[0], img, img_end, ((long long)uy0 * W0 + lo) * 3, len);
       if (vy1) sh1 = pre_stage(rows[1], img, img_end, ((long long)uy1 * W0 + lo) * 3, len);
     }
     __syncthreads();
     if (x >= a.W) continue;
-    const float ay0 = 1.f - fy, ay1 = fy;
     float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
+    if (LB && !(yin && xin)) {                       // outside the window: the whitened mean
+      o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
+      continue;
+    }
+    const float ay0 = 1.f - fy, ay1 = fy;
     const unsigned char *p00, *p01, *p10, *p11;
     if (staged) {
       const unsigned char* r0 = (const unsigned char*)rows[0] + sh0;
@@ -237,27 +316,6 @@ __device__ __forceinline__ void preprocess_body(const PreArgs& a, const int* aug
   }
 }
 
-__global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) { preprocess_body<false, false>(a, nullptr, nullptr, nullptr); }
-
-__global__ __launch_bounds__(256) void preprocess_aug_kernel(PreArgs a, const int* aug) { preprocess_body<true, false>(a, aug, nullptr, nullptr); }
-
-__global__ __launch_bounds__(256) void preprocess_aug_color_kernel(PreArgs a, const int* aug, const float* color, const unsigned long long* sums) {
-  preprocess_body<true, true>(a, aug, color, sums);
-}
-
-// src: device buffer holding the B images back to back (HWC uint8 RGB); offsets [B] byte offsets; sizes [B][2] =
-// (H0, W0) int32; out: NCHW fp32 [B][3][H][W]; scales: [B][2] fp32 or NULL; mean/std: 3 floats each (host).
-extern "C" int sqd_preprocess_u8_fwd(const unsigned char* src, const long long* offsets, const int* sizes, float* out,
-                                     float* scales, const float* mean3, const float* std3, int B, int H, int W,
-                                     void* stream) {
-  SQD_CHECK_ARG(src && offsets && sizes && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
-  PreArgs a;
-  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.scales = scales; a.B = B; a.H = H; a.W = W;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
-  hipLaunchKernelGGL(preprocess_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
-  return sqd_launch_status();
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The reference's OTHER pre-processing branch, cfg.forbid_resize (src/datasets/base.py:53-54): whiten (src/utils/image.py:9-19),
 // then crop_or_pad (:91-124) -- per axis, a smaller image is zero-padded to the target (floor half in front, np.pad constant 0
@@ -265,6 +323,7 @@ extern "C" int sqd_preprocess_u8_fwd(const unsigned char* src, const long long* 
 // Pure index arithmetic plus the one float32 subtract and divide of whiten: bit-exact against the reference.
 // Also writes what boxes_postprocess (src/utils/boxes.py:149-155) needs to map detections back: padding / crops (top, bottom,
 // left, right) and the box shift (dy, dx) = (crops[0] - padding[0], crops[2] - padding[2]) the fused detect kernel adds.
+// AUG: crop_or_pad of the drifted, flipped image V: padding / crops / shifts from (Hd, Wd).
 // ---------------------------------------------------------------------------------------------------------------------
 struct PadCropArgs {
   const unsigned char* src; const long long* offsets; const int* sizes;
@@ -273,7 +332,6 @@ struct PadCropArgs {
   int B, H, W;
 };
 
-// AUG: crop_or_pad of the drifted, flipped image V (Hd x Wd, see preprocess_body): padding / crops / shifts from (Hd, Wd).
 template <bool AUG, bool COLOR>
 __device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, const int* aug, const float* color, const unsigned long long* sums) {
   __shared__ float lut[768];
@@ -281,9 +339,8 @@ __device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, co
   const int b = blockIdx.z;
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int H0 = a.sizes[2 * b], W0 = a.sizes[2 * b + 1];
-  const int dy = pre_drift<AUG>(aug, 3 * b, H0), dx = pre_drift<AUG>(aug, 3 * b + 1, W0);
-  const bool flip = AUG && aug[3 * b + 2] != 0;
-  const int Hd = AUG ? H0 - dy : H0, Wd = AUG ? W0 - dx : W0;
+  const PreView im = pre_view<AUG>(aug, b, H0, W0);
+  const int dy = im.dy, Hd = im.Hd, Wd = im.Wd;
   // (target - size) // 2 in front when padding, (size - target) // 2 cut in front when cropping
   const int pt = Hd < a.H ? (a.H - Hd) / 2 : 0, ct = Hd > a.H ? (Hd - a.H) / 2 : 0;
   const int pl = Wd < a.W ? (a.W - Wd) / 2 : 0, cl = Wd > a.W ? (Wd - a.W) / 2 : 0;
@@ -295,24 +352,17 @@ __device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, co
     }
     if (a.shifts) { a.shifts[2 * b] = (float)(ct - pt); a.shifts[2 * b + 1] = (float)(cl - pl); }
   }
-  auto col = [&](int v) { return AUG ? (flip ? Wd - 1 - v : v) + dx : v; };     // V column -> image column
   const int sx = x - pl + cl;
   const unsigned char* img = a.src + a.offsets[b];
   // the workgroup's source columns: [lo, hi] of the source row, clipped to the image (256 pixels = 768 bytes: always fits)
   const int xa = blockIdx.x * 256;
   int lo = max(xa - pl + cl, 0), hi = min(min(a.W, xa + 256) - 1 - pl + cl, Wd - 1);
   if (AUG && hi >= lo) {
-    const int ca = col(lo), cb = col(hi);
+    const int ca = im.col<AUG>(lo), cb = im.col<AUG>(hi);
     lo = max(min(ca, cb), 0); hi = min(max(ca, cb), W0 - 1);
   }
   const long long plane = (long long)a.H * a.W;
-  PreColor kc = {};
-  if (COLOR) {
-    kc = pre_color_of(color, sums, b, H0, W0);
-    pre_build_lut_color(lut, kc, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
-  } else {
-    pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
-  }
+  const PreColor kc = pre_build_table<COLOR>(lut, color, sums, b, H0, W0, a.mean, a.stdv);
   for (int r = 0; r < PRE_ROWS; ++r) {
     const int y = blockIdx.y * PRE_ROWS + r;
     if (y >= a.H) break;                             // (uniform)
@@ -323,7 +373,7 @@ __device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, co
     if (row_in) sh = pre_stage(row, img, img + (long long)H0 * W0 * 3, ((long long)(AUG ? sy + dy : sy) * W0 + lo) * 3, (hi - lo + 1) * 3);
     __syncthreads();
     if (x >= a.W) continue;
-    const int cx = col(sx);
+    const int cx = im.col<AUG>(sx);
     const bool inside = row_in && sx >= 0 && sx < Wd && (!AUG || cx >= 0);
     float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
     const unsigned char* p = (const unsigned char*)row + sh + (inside ? (cx - lo) * 3 : 0);
@@ -339,26 +389,70 @@ __device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, co
   }
 }
 
+// The nine kernels: geometry x (eval, AUG, AUG + COLOR).
+__global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) { preprocess_bilinear_body<false, false, false>(a, nullptr, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void preprocess_aug_kernel(PreArgs a, const int* aug) { preprocess_bilinear_body<false, true, false>(a, aug, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void preprocess_aug_color_kernel(PreArgs a, const int* aug, const float* color, const unsigned long long* sums) {
+  preprocess_bilinear_body<false, true, true>(a, aug, color, sums);
+}
 __global__ __launch_bounds__(256) void preprocess_padcrop_kernel(PadCropArgs a) { preprocess_padcrop_body<false, false>(a, nullptr, nullptr, nullptr); }
-
 __global__ __launch_bounds__(256) void preprocess_padcrop_aug_kernel(PadCropArgs a, const int* aug) { preprocess_padcrop_body<true, false>(a, aug, nullptr, nullptr); }
-
 __global__ __launch_bounds__(256) void preprocess_padcrop_aug_color_kernel(PadCropArgs a, const int* aug, const float* color,
                                                                            const unsigned long long* sums) {
   preprocess_padcrop_body<true, true>(a, aug, color, sums);
 }
+__global__ __launch_bounds__(256) void preprocess_letterbox_kernel(LetterboxArgs a) { preprocess_bilinear_body<true, false, false>(a, nullptr, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void preprocess_letterbox_aug_kernel(LetterboxArgs a, const int* aug) {
+  preprocess_bilinear_body<true, true, false>(a, aug, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void preprocess_letterbox_aug_color_kernel(LetterboxArgs a, const int* aug, const float* color,
+                                                                             const unsigned long long* sums) {
+  preprocess_bilinear_body<true, true, true>(a, aug, color, sums);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side.  Every entry: SQD_ERR_BAD_ARG before any launch unless pre_args and pre_blocks accept its arguments.
+// ---------------------------------------------------------------------------------------------------------------------
+// the part common to all nine entries: checks it and copies it into the kernel's argument struct
+template <class Args>
+static inline bool pre_args(Args& a, const unsigned char* src, const long long* offsets, const int* sizes, float* out, const float* mean3,
+                            const float* std3, int B, int H, int W) {
+  if (!(src && offsets && sizes && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535)) return false;
+  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.B = B; a.H = H; a.W = W;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; if (std3[c] == 0.f) return false; }
+  return true;
+}
+
+// the optional blocks: aug required by the AUG forms, color and sums (aligned) by the COLOR forms; win (letterbox) may be null
+enum { PRE_AUG = 1, PRE_COLOR = 2 };
+static inline bool pre_blocks(int need, const int* aug, const float* color, const unsigned long long* sums, const int* win) {
+  if ((need & PRE_AUG) && !aug) return false;
+  if ((need & PRE_COLOR) && !(color && sums && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)color & 3) == 0)) return false;
+  return ((uintptr_t)win & 3) == 0;
+}
+
+template <class... T>
+static inline int pre_launch(void (*kernel)(T...), int B, int H, int W, void* stream, T... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, args...);
+  return sqd_launch_status();
+}
+
+// src: device buffer holding the B images back to back (HWC uint8 RGB); offsets [B] byte offsets; sizes [B][2] =
+// (H0, W0) int32; out: NCHW fp32 [B][3][H][W]; scales: [B][2] fp32 or NULL; mean/std: 3 floats each (host).
+extern "C" int sqd_preprocess_u8_fwd(const unsigned char* src, const long long* offsets, const int* sizes, float* out, float* scales,
+                                     const float* mean3, const float* std3, int B, int H, int W, void* stream) {
+  PreArgs a; a.scales = scales;
+  SQD_CHECK_ARG(pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_kernel, B, H, W, stream, a);
+}
 
 // Arguments as sqd_preprocess_u8_fwd; shifts: [B][2] fp32 (dy, dx) or NULL; padcrop: [B][8] int32 = padding (top, bottom, left,
 // right) then crops (top, bottom, left, right), or NULL.
-extern "C" int sqd_preprocess_u8_padcrop_fwd(const unsigned char* src, const long long* offsets, const int* sizes, float* out,
-                                             float* shifts, int* padcrop, const float* mean3, const float* std3, int B, int H, int W,
-                                             void* stream) {
-  SQD_CHECK_ARG(src && offsets && sizes && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
-  PadCropArgs a;
-  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.shifts = shifts; a.padcrop = padcrop; a.B = B; a.H = H; a.W = W;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
-  hipLaunchKernelGGL(preprocess_padcrop_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
-  return sqd_launch_status();
+extern "C" int sqd_preprocess_u8_padcrop_fwd(const unsigned char* src, const long long* offsets, const int* sizes, float* out, float* shifts,
+                                             int* padcrop, const float* mean3, const float* std3, int B, int H, int W, void* stream) {
+  PadCropArgs a; a.shifts = shifts; a.padcrop = padcrop;
+  SQD_CHECK_ARG(pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_padcrop_kernel, B, H, W, stream, a);
 }
 
 // Training forms (reference train phase: drift + flip before the resize / crop_or_pad).  aug: device int32 [B][3] = (dy, dx, flipped)
@@ -366,265 +460,62 @@ extern "C" int sqd_preprocess_u8_padcrop_fwd(const unsigned char* src, const lon
 // Other arguments as sqd_preprocess_u8_fwd / sqd_preprocess_u8_padcrop_fwd.
 extern "C" int sqd_preprocess_u8_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug, float* out,
                                          float* scales, const float* mean3, const float* std3, int B, int H, int W, void* stream) {
-  SQD_CHECK_ARG(src && offsets && sizes && aug && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
-  PreArgs a;
-  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.scales = scales; a.B = B; a.H = H; a.W = W;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
-  hipLaunchKernelGGL(preprocess_aug_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug);
-  return sqd_launch_status();
+  PreArgs a; a.scales = scales;
+  SQD_CHECK_ARG(pre_blocks(PRE_AUG, aug, nullptr, nullptr, nullptr) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_aug_kernel, B, H, W, stream, a, aug);
 }
 
-extern "C" int sqd_preprocess_u8_padcrop_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
-                                                 float* out, float* shifts, int* padcrop, const float* mean3, const float* std3, int B, int H,
-                                                 int W, void* stream) {
-  SQD_CHECK_ARG(src && offsets && sizes && aug && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
-  PadCropArgs a;
-  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.shifts = shifts; a.padcrop = padcrop; a.B = B; a.H = H; a.W = W;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
-  hipLaunchKernelGGL(preprocess_padcrop_aug_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug);
-  return sqd_launch_status();
+extern "C" int sqd_preprocess_u8_padcrop_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug, float* out,
+                                                 float* shifts, int* padcrop, const float* mean3, const float* std3, int B, int H, int W,
+                                                 void* stream) {
+  PadCropArgs a; a.shifts = shifts; a.padcrop = padcrop;
+  SQD_CHECK_ARG(pre_blocks(PRE_AUG, aug, nullptr, nullptr, nullptr) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_padcrop_aug_kernel, B, H, W, stream, a, aug);
 }
 
 // Colour forms of the two above (the photometric jitter of pre_color_of): color: device fp32 [B][3] = (brightness, contrast, saturation)
 // factors per image; sums: device uint64 [B][3][2] as sqd_image_stats_u8 writes it for the same src / offsets / sizes (launched before this
 // call on the same stream).  Both are required.  color = (1, 1, 1) everywhere gives the results of the _aug_ entry points bit for bit.
 extern "C" int sqd_preprocess_u8_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
-                                               const float* color, const unsigned long long* sums, float* out, float* scales,
-                                               const float* mean3, const float* std3, int B, int H, int W, void* stream) {
-  SQD_CHECK_ARG(src && offsets && sizes && aug && color && sums && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
-  SQD_CHECK_ARG(((uintptr_t)sums & 7) == 0 && ((uintptr_t)color & 3) == 0);
-  PreArgs a;
-  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.scales = scales; a.B = B; a.H = H; a.W = W;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
-  hipLaunchKernelGGL(preprocess_aug_color_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug, color, sums);
-  return sqd_launch_status();
+                                               const float* color, const unsigned long long* sums, float* out, float* scales, const float* mean3,
+                                               const float* std3, int B, int H, int W, void* stream) {
+  PreArgs a; a.scales = scales;
+  SQD_CHECK_ARG(pre_blocks(PRE_AUG | PRE_COLOR, aug, color, sums, nullptr) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_aug_color_kernel, B, H, W, stream, a, aug, color, sums);
 }
 
 extern "C" int sqd_preprocess_u8_padcrop_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
-                                                       const float* color, const unsigned long long* sums, float* out, float* shifts,
-                                                       int* padcrop, const float* mean3, const float* std3, int B, int H, int W, void* stream) {
-  SQD_CHECK_ARG(src && offsets && sizes && aug && color && sums && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535);
-  SQD_CHECK_ARG(((uintptr_t)sums & 7) == 0 && ((uintptr_t)color & 3) == 0);
-  PadCropArgs a;
-  a.src = src; a.offsets = offsets; a.sizes = sizes; a.out = out; a.shifts = shifts; a.padcrop = padcrop; a.B = B; a.H = H; a.W = W;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; SQD_CHECK_ARG(std3[c] != 0.f); }
-  hipLaunchKernelGGL(preprocess_padcrop_aug_color_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug, color, sums);
-  return sqd_launch_status();
+                                                       const float* color, const unsigned long long* sums, float* out, float* shifts, int* padcrop,
+                                                       const float* mean3, const float* std3, int B, int H, int W, void* stream) {
+  PadCropArgs a; a.shifts = shifts; a.padcrop = padcrop;
+  SQD_CHECK_ARG(pre_blocks(PRE_AUG | PRE_COLOR, aug, color, sums, nullptr) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_padcrop_aug_color_kernel, B, H, W, stream, a, aug, color, sums);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The third geometry, cfg.letterbox (no reference counterpart; DESIGN.md 6b, "Letterbox and zoom-out"): the drifted, flipped image
-// V (Hd x Wd, see preprocess_body; eval: the image itself) is resized with its aspect ratio kept into a window (top, left, h1, w1)
-// of the H x W canvas, and everything outside the window is exactly +0.0f -- the whitened mean, as the reference's zero fill after
-// whitening.  Inside the window the value at (y, x) is preprocess_body's resize rule with destination size (h1, w1) evaluated at
-// (y - top, x - left): the same expressions, so a window that is the whole canvas gives preprocess_body's bits.
-// The window comes from win[B][4] int32 (zoom-out: the host shrinks and places it) or, win == null, from the integer rule
-//   H * Wd <= W * Hd (height-limited):  h1 = H, w1 = max(1, (Wd * H + Hd / 2) / Hd);  else  w1 = W, h1 = max(1, (Hd * W + Wd / 2) / Wd);
-//   top = (H - h1) / 2, left = (W - w1) / 2     (64-bit, integer divisions: augment.letterbox_window evaluates the same)
-// A given window is clamped into the canvas (h1 to 1..H, w1 to 1..W, then top to 0..H-h1, left to 0..W-w1), in the spirit of pre_drift: no
-// buffer content makes the kernel read or write out of range.  scales = (h1 / Hd, w1 / Wd) (float64 division, cast to float32) and
-// shifts = (-(float)top / sy, -(float)left / sx): box / scales + shifts in the detect kernels is boxes_postprocess with
-// padding = (top / sy, ., left / sx, .), i.e. the padding in original-image pixels.
-// Workgroup shape as above.  The staged segment is bounded by the workgroup's columns INSIDE the window; a workgroup with no column
-// or no row in the window stores zeros and returns before the table is built; one cut by a window edge takes both cases per thread
-// (the barriers run for every row, window or not).
-// ---------------------------------------------------------------------------------------------------------------------
-struct LetterboxArgs {
-  const unsigned char* src; const long long* offsets; const int* sizes;
-  const int* win;                // [B][4] = (top, left, h1, w1), or null: the centred window of the integer rule
-  float* out; float* scales; float* shifts;
-  float mean[3], stdv[3];
-  int B, H, W;
-};
-
-template <bool AUG, bool COLOR>
-__device__ __forceinline__ void preprocess_letterbox_body(const LetterboxArgs& a, const int* aug, const float* color, const unsigned long long* sums) {
-  __shared__ float lut[768];
-  __shared__ unsigned rows[2][PRE_ROWB / 4];
-  const int b = blockIdx.z;
-  const int x = blockIdx.x * blockDim.x + threadIdx.x;
-  const int H0 = a.sizes[2 * b], W0 = a.sizes[2 * b + 1];
-  const int dy = pre_drift<AUG>(aug, 3 * b, H0), dx = pre_drift<AUG>(aug, 3 * b + 1, W0);
-  const bool flip = AUG && aug[3 * b + 2] != 0;
-  const int Hd = AUG ? H0 - dy : H0, Wd = AUG ? W0 - dx : W0;     // the (drifted) image the resize rule sees
-  int top, left, h1, w1;
-  if (a.win) {
-    const int* w = a.win + 4 * b;
-    h1 = max(min(w[2], a.H), 1); w1 = max(min(w[3], a.W), 1);
-    top = max(min(w[0], a.H - h1), 0); left = max(min(w[1], a.W - w1), 0);
-  } else {
-    const long long H = a.H, W = a.W, hd = Hd, wd = Wd;
-    if (H * wd <= W * hd) { h1 = a.H; w1 = (int)min(max((wd * H + hd / 2) / hd, 1ll), W); }
-    else { w1 = a.W; h1 = (int)min(max((hd * W + wd / 2) / wd, 1ll), H); }
-    top = (a.H - h1) / 2; left = (a.W - w1) / 2;
-  }
-  if (x == 0 && blockIdx.y == 0 && (a.scales || a.shifts)) {
-    const float sy = (float)((double)h1 / (double)Hd), sx = (float)((double)w1 / (double)Wd);
-    if (a.scales) { a.scales[2 * b] = sy; a.scales[2 * b + 1] = sx; }
-    if (a.shifts) { a.shifts[2 * b] = -(float)top / sy; a.shifts[2 * b + 1] = -(float)left / sx; }
-  }
-  const long long plane = (long long)a.H * a.W;
-  // the workgroup's columns and rows inside the window (all uniform)
-  const int xa = blockIdx.x * 256, xb = min(a.W, xa + 256) - 1;
-  const int ia = max(xa, left), ib = min(xb, left + w1 - 1);
-  const int ya = blockIdx.y * PRE_ROWS, yb = min(a.H, ya + PRE_ROWS) - 1;
-  if (ia > ib || yb < top || ya >= top + h1) {       // wholly in the fill region: zeros, nothing staged
-    if (x < a.W)
-      for (int y = ya; y <= yb; ++y) {
-        float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
-        o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
-      }
-    return;
-  }
-  const unsigned char* img = a.src + a.offsets[b];
-  const unsigned char* img_end = img + (long long)H0 * W0 * 3;
-  // source coordinates of a window pixel (double scale like OpenCV, then float weights): the resize rule with destination (h1, w1)
-  const double sclx = (double)Wd / (double)w1, scly = (double)Hd / (double)h1;
-  auto src_x = [&](int xx, float& f) {
-    f = (float)((xx + 0.5) * sclx - 0.5);
-    int sx = (int)floorf(f); f -= (float)sx;
-    if (sx < 0) { sx = 0; f = 0.f; }
-    if (sx >= Wd - 1) { sx = Wd - 1; f = 0.f; }
-    return sx;
-  };
-  auto col = [&](int v) { return AUG ? (flip ? Wd - 1 - v : v) + dx : v; };     // V column -> image column
-  // the source column range [lo, hi] of the workgroup's window columns (sx is monotone in x): one segment per source row
-  float fdummy;
-  int lo = src_x(ia - left, fdummy), hi = min(src_x(ib - left, fdummy) + 1, Wd - 1);
-  if (AUG) {
-    const int ca = col(lo), cb = col(hi);
-    lo = max(min(ca, cb), 0); hi = min(max(ca, cb), W0 - 1);
-  }
-  const bool seg = !AUG || hi >= lo;                 // (AUG) false: every window column of the workgroup lies in the drift fill
-  const int len = (hi - lo + 1) * 3;
-  const bool staged = len + 8 <= PRE_ROWB;
-  const int xc = min(x, a.W - 1);
-  const bool xin = xc >= left && xc < left + w1;
-  float fx;
-  const int sx = src_x(min(max(xc - left, 0), w1 - 1), fx);     // (a thread outside the window: the nearest window column, never read)
-  const int sx1 = min(sx + 1, Wd - 1);
-  const int cx0 = col(sx), cx1 = col(sx1);
-  const bool vx0 = !AUG || cx0 >= 0, vx1 = !AUG || cx1 >= 0;
-  const int ux0 = AUG ? max(cx0, 0) : cx0, ux1 = AUG ? max(cx1, 0) : cx1;     // (a fill tap's address: any in-range one)
-  const float ax0 = 1.f - fx, ax1 = fx;
-  PreColor kc = {};
-  if (COLOR) {
-    kc = pre_color_of(color, sums, b, H0, W0);
-    pre_build_lut_color(lut, kc, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
-  } else {
-    pre_build_lut(lut, a.mean[0], a.mean[1], a.mean[2], a.stdv[0], a.stdv[1], a.stdv[2]);
-  }
-  for (int r = 0; r < PRE_ROWS; ++r) {
-    const int y = ya + r;
-    if (y >= a.H) break;                             // (uniform)
-    const bool yin = y >= top && y < top + h1;       // (uniform)
-    float fy = (float)((min(max(y - top, 0), h1 - 1) + 0.5) * scly - 0.5);
-    int sy = (int)floorf(fy); fy -= (float)sy;
-    if (sy < 0) { sy = 0; fy = 0.f; }
-    if (sy >= Hd - 1) { sy = Hd - 1; fy = 0.f; }
-    const int sy1 = min(sy + 1, Hd - 1);
-    const int ry0 = sy + dy, ry1 = sy1 + dy;         // image rows (AUG: negative = fill)
-    const bool vy0 = !AUG || ry0 >= 0, vy1 = !AUG || ry1 >= 0;
-    const int uy0 = AUG ? max(ry0, 0) : ry0, uy1 = AUG ? max(ry1, 0) : ry1;
-    int sh0 = 0, sh1 = 0;
-    if (r) __syncthreads();                          // the previous row's readers are done with the segments
-    if (staged && seg && yin) {
-      if (vy0) sh0 = pre_stage(rows[0], img, img_end, ((long long)uy0 * W0 + lo) * 3, len);
-      if (vy1) sh1 = pre_stage(rows[1], img, img_end, ((long long)uy1 * W0 + lo) * 3, len);
-    }
-    __syncthreads();
-    if (x >= a.W) continue;
-    float* o = a.out + (long long)b * 3 * plane + (long long)y * a.W + x;
-    if (!(yin && xin)) {                             // outside the window: the whitened mean
-      o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
-      continue;
-    }
-    const float ay0 = 1.f - fy, ay1 = fy;
-    const unsigned char *p00, *p01, *p10, *p11;
-    if (staged) {
-      const unsigned char* r0 = (const unsigned char*)rows[0] + sh0;
-      const unsigned char* r1 = (const unsigned char*)rows[1] + sh1;
-      const int ox0 = AUG ? (vx0 ? ux0 - lo : 0) : sx - lo, ox1 = AUG ? (vx1 ? ux1 - lo : 0) : sx1 - lo;
-      p00 = r0 + ox0 * 3; p01 = r0 + ox1 * 3; p10 = r1 + ox0 * 3; p11 = r1 + ox1 * 3;
-    } else {
-      p00 = img + ((long long)uy0 * W0 + ux0) * 3; p01 = img + ((long long)uy0 * W0 + ux1) * 3;
-      p10 = img + ((long long)uy1 * W0 + ux0) * 3; p11 = img + ((long long)uy1 * W0 + ux1) * 3;
-    }
-    const bool t00 = vy0 && vx0, t01 = vy0 && vx1, t10 = vy1 && vx0, t11 = vy1 && vx1;
-    if (COLOR && kc.per_tap) {                       // (uniform) saturation mixes the channels of a tap: blend and whiten per tap
-      float v00[3] = {0.f, 0.f, 0.f}, v01[3] = {0.f, 0.f, 0.f}, v10[3] = {0.f, 0.f, 0.f}, v11[3] = {0.f, 0.f, 0.f};     // (fill: 0)
-      if (t00) pre_color_tap(lut, kc, p00, a.mean, a.stdv, v00);
-      if (t01) pre_color_tap(lut, kc, p01, a.mean, a.stdv, v01);
-      if (t10) pre_color_tap(lut, kc, p10, a.mean, a.stdv, v10);
-      if (t11) pre_color_tap(lut, kc, p11, a.mean, a.stdv, v11);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float r0 = v00[c] * ax0 + v01[c] * ax1;
-        const float r1 = v10[c] * ax0 + v11[c] * ax1;
-        o[c * plane] = r0 * ay0 + r1 * ay1;
-      }
-      continue;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* l = lut + 256 * c;
-      const float v00 = t00 ? l[p00[c]] : 0.f, v01 = t01 ? l[p01[c]] : 0.f;
-      const float v10 = t10 ? l[p10[c]] : 0.f, v11 = t11 ? l[p11[c]] : 0.f;
-      const float r0 = v00 * ax0 + v01 * ax1;
-      const float r1 = v10 * ax0 + v11 * ax1;
-      o[c * plane] = r0 * ay0 + r1 * ay1;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void preprocess_letterbox_kernel(LetterboxArgs a) { preprocess_letterbox_body<false, false>(a, nullptr, nullptr, nullptr); }
-
-__global__ __launch_bounds__(256) void preprocess_letterbox_aug_kernel(LetterboxArgs a, const int* aug) {
-  preprocess_letterbox_body<true, false>(a, aug, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(256) void preprocess_letterbox_aug_color_kernel(LetterboxArgs a, const int* aug, const float* color,
-                                                                             const unsigned long long* sums) {
-  preprocess_letterbox_body<true, true>(a, aug, color, sums);
-}
-
-static inline bool letterbox_args(LetterboxArgs& a, const unsigned char* src, const long long* offsets, const int* sizes, const int* win, float* out,
-                                  float* scales, float* shifts, const float* mean3, const float* std3, int B, int H, int W) {
-  if (!(src && offsets && sizes && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && B <= 65535 && H <= 65535)) return false;
-  if (((uintptr_t)win & 3) != 0) return false;
-  a.src = src; a.offsets = offsets; a.sizes = sizes; a.win = win; a.out = out; a.scales = scales; a.shifts = shifts; a.B = B; a.H = H; a.W = W;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; if (std3[c] == 0.f) return false; }
-  return true;
-}
-
-// Arguments as sqd_preprocess_u8_fwd / _aug_fwd / _aug_color_fwd; win: device int32 [B][4] = (top, left, h1, w1) per image or NULL
-// (the centred window of the integer rule above); scales [B][2] = (h1 / Hd, w1 / Wd) and shifts [B][2] = (-top / sy, -left / sx), either
-// may be NULL.
+// Letterbox forms.  Arguments as sqd_preprocess_u8_fwd / _aug_fwd / _aug_color_fwd; win: device int32 [B][4] = (top, left, h1, w1) per
+// image or NULL (the centred window of the integer rule above); scales [B][2] = (h1 / Hd, w1 / Wd) and shifts [B][2] = (-top / sy,
+// -left / sx), either may be NULL.
 extern "C" int sqd_preprocess_u8_letterbox_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* win, float* out,
                                                float* scales, float* shifts, const float* mean3, const float* std3, int B, int H, int W,
                                                void* stream) {
-  LetterboxArgs a;
-  SQD_CHECK_ARG(letterbox_args(a, src, offsets, sizes, win, out, scales, shifts, mean3, std3, B, H, W));
-  hipLaunchKernelGGL(preprocess_letterbox_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
-  return sqd_launch_status();
+  LetterboxArgs a; a.win = win; a.scales = scales; a.shifts = shifts;
+  SQD_CHECK_ARG(pre_blocks(0, nullptr, nullptr, nullptr, win) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_letterbox_kernel, B, H, W, stream, a);
 }
 
 extern "C" int sqd_preprocess_u8_letterbox_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
-                                                   const int* win, float* out, float* scales, float* shifts, const float* mean3,
-                                                   const float* std3, int B, int H, int W, void* stream) {
-  LetterboxArgs a;
-  SQD_CHECK_ARG(aug && letterbox_args(a, src, offsets, sizes, win, out, scales, shifts, mean3, std3, B, H, W));
-  hipLaunchKernelGGL(preprocess_letterbox_aug_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug);
-  return sqd_launch_status();
+                                                   const int* win, float* out, float* scales, float* shifts, const float* mean3, const float* std3,
+                                                   int B, int H, int W, void* stream) {
+  LetterboxArgs a; a.win = win; a.scales = scales; a.shifts = shifts;
+  SQD_CHECK_ARG(pre_blocks(PRE_AUG, aug, nullptr, nullptr, win) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_letterbox_aug_kernel, B, H, W, stream, a, aug);
 }
 
 extern "C" int sqd_preprocess_u8_letterbox_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
                                                          const int* win, const float* color, const unsigned long long* sums, float* out,
-                                                         float* scales, float* shifts, const float* mean3, const float* std3, int B, int H,
-                                                         int W, void* stream) {
-  LetterboxArgs a;
-  SQD_CHECK_ARG(aug && color && sums && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)color & 3) == 0);
-  SQD_CHECK_ARG(letterbox_args(a, src, offsets, sizes, win, out, scales, shifts, mean3, std3, B, H, W));
-  hipLaunchKernelGGL(preprocess_letterbox_aug_color_kernel, dim3((unsigned)sqd_cdiv(W, 256), (unsigned)sqd_cdiv(H, PRE_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, aug, color, sums);
-  return sqd_launch_status();
+                                                         float* scales, float* shifts, const float* mean3, const float* std3, int B, int H, int W,
+                                                         void* stream) {
+  LetterboxArgs a; a.win = win; a.scales = scales; a.shifts = shifts;
+  SQD_CHECK_ARG(pre_blocks(PRE_AUG | PRE_COLOR, aug, color, sums, win) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
+  return pre_launch(preprocess_letterbox_aug_color_kernel, B, H, W, stream, a, aug, color, sums);
 }

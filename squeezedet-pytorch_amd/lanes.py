@@ -24,7 +24,6 @@ steps and the result buffers as well.
 """
 from __future__ import annotations
 
-import ctypes
 import gc
 from collections import deque
 
@@ -33,8 +32,8 @@ import torch
 
 from . import _native as nat
 from . import ops
-from .boxes import letterbox_meta, letterbox_window
-from .preprocess import KITTI_RGB_MEAN, KITTI_RGB_STD
+from .boxes import letterbox_meta, letterbox_window, pad_crop
+from .preprocess import KITTI_RGB_MEAN, KITTI_RGB_STD, c_float3, launch_u8
 
 _HDR_ALIGN = 256
 
@@ -202,8 +201,7 @@ class DetectStream:
         mean = KITTI_RGB_MEAN if mean is None else np.asarray(mean, np.float32).reshape(-1)
         std = KITTI_RGB_STD if std is None else np.asarray(std, np.float32).reshape(-1)
         self.rgb_mean, self.rgb_std = mean, std
-        self._mean_c = (ctypes.c_float * 3)(*[float(v) for v in mean])
-        self._std_c = (ctypes.c_float * 3)(*[float(v) for v in std])
+        self._mean_c, self._std_c = c_float3(mean), c_float3(std)
         self.cap = int(capacity if capacity is not None else max(1, int(getattr(cfg, 'batch_size', 20))))
         H, W = int(cfg.input_size[0]), int(cfg.input_size[1])
         self._slot = -(-(H * W * 3) // 4096) * 4096          # first guess: an original the size of the network input
@@ -308,18 +306,12 @@ class DetectStream:
             d_sizes = nat.c_p(src.data_ptr() + 8 * cap)
             H, W = int(self.cfg.input_size[0]), int(self.cfg.input_size[1])
             if self.letterbox:
-                rc = nat.lib().sqd_preprocess_u8_letterbox_fwd(nat.ptr(src), d_off, d_sizes, None, nat.ptr(nb['img']), nat.ptr(nb['aux']),
-                                                               nat.ptr(nb['aux2']), self._mean_c, self._std_c, n, H, W,
-                                                               nat.stream_handle(self.device))
-                nat.check(rc, 'sqd_preprocess_u8_letterbox_fwd')
+                geometry, side = 'letterbox', {'scales': nb['aux'], 'shifts': nb['aux2']}
             elif self.forbid:
-                rc = nat.lib().sqd_preprocess_u8_padcrop_fwd(nat.ptr(src), d_off, d_sizes, nat.ptr(nb['img']), nat.ptr(nb['aux']), None,
-                                                             self._mean_c, self._std_c, n, H, W, nat.stream_handle(self.device))
-                nat.check(rc, 'sqd_preprocess_u8_padcrop_fwd')
+                geometry, side = 'padcrop', {'shifts': nb['aux']}
             else:
-                rc = nat.lib().sqd_preprocess_u8_fwd(nat.ptr(src), d_off, d_sizes, nat.ptr(nb['img']), nat.ptr(nb['aux']),
-                                                     self._mean_c, self._std_c, n, H, W, nat.stream_handle(self.device))
-                nat.check(rc, 'sqd_preprocess_u8_fwd')
+                geometry, side = 'resize', {'scales': nb['aux']}
+            launch_u8(geometry, src, d_off, d_sizes, nb['img'], n, H, W, self._mean_c, self._std_c, self.device, **side)
             lane.consumed.record(lane.comp)
 
         def compute():
@@ -353,13 +345,9 @@ class DetectStream:
             if getattr(self, 'letterbox', False):
                 m.update(letterbox_meta((h0, w0), letterbox_window((h0, w0), (H, W)), (H, W)))      # the same integers as the kernel
             elif self.forbid:
-                pad, crop = np.zeros(4, np.int16), np.zeros(4, np.int16)       # the same integers as the kernel (image.py:99-115)
-                for size, target, k in ((int(h0), H, 0), (int(w0), W, 2)):
-                    if size < target:
-                        pad[k] = (target - size) // 2; pad[k + 1] = (target - size) - pad[k]
-                    elif size > target:
-                        crop[k] = (size - target) // 2; crop[k + 1] = (size - target) - crop[k]
-                m.update(padding=pad, crops=crop)
+                pt, pb, ct, cb = pad_crop(int(h0), H)                          # the same integers as the kernel
+                pl, pr, cl, cr = pad_crop(int(w0), W)
+                m.update(padding=np.array([pt, pb, pl, pr], np.int16), crops=np.array([ct, cb, cl, cr], np.int16))
             else:
                 m['scales'] = np.array([H / h0, W / w0], dtype=np.float32)
             metas.append(m)

@@ -15,9 +15,59 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .boxes import letterbox_meta, letterbox_window, pad_crop
 
 KITTI_RGB_MEAN = np.array([93.877, 98.801, 95.923], dtype=np.float32)      # src/datasets/kitti.py:17
 KITTI_RGB_STD = np.array([78.782, 80.130, 81.200], dtype=np.float32)       # src/datasets/kitti.py:18
+
+
+_ENTRY_STEM = {'resize': 'sqd_preprocess_u8', 'padcrop': 'sqd_preprocess_u8_padcrop', 'letterbox': 'sqd_preprocess_u8_letterbox'}
+_Float3 = ctypes.c_float * 3
+
+
+def c_float3(values):
+    """Three floats (a mean or a std) as the host ``const float*`` the input entry points take."""
+    return values if isinstance(values, _Float3) else _Float3(*[float(v) for v in np.asarray(values).reshape(-1)])
+
+
+def entry_name(geometry, aug=False, color=False):
+    """The C entry point of one of the nine input kernels (csrc/preproc.hip): geometry x (eval, aug, aug + colour)."""
+    if geometry not in _ENTRY_STEM:
+        raise ValueError(f"launch_u8: geometry must be 'resize', 'padcrop' or 'letterbox', got {geometry!r}")
+    if color and not aug:
+        raise ValueError('launch_u8: the colour forms exist only with aug (there is no eval-time colour entry)')
+    return _ENTRY_STEM[geometry] + ('_aug' if aug else '') + ('_color' if color else '') + '_fwd'
+
+
+def launch_u8(geometry, src, offsets, sizes, out, B, H, W, mean, std, device, *, aug=None, color=None, sums=None, win=None,
+              scales=None, shifts=None, padcrop=None, stream=None):
+    """The one launch of the uint8 input pipeline: picks the entry point from (``geometry``, ``aug`` given, ``color`` given), puts its
+    arguments in the entry's order (include/sqd_hip.h) and checks its status.  Pointer arguments are device tensors, ``ctypes.c_void_p``
+    addresses (blocks inside a packed upload) or None; ``mean`` / ``std`` anything ``c_float3`` takes.  Argument blocks per geometry:
+    ``aug`` int32 [B,3] (any geometry); ``color`` fp32 [B,3] with ``sums`` [B,3,2] of ``ops.image_stats_u8`` (only with ``aug``); ``win`` int32
+    [B,4] (letterbox only); outputs ``scales`` (resize, letterbox), ``shifts`` (padcrop, letterbox), ``padcrop`` int32 [B,8] (padcrop).
+    ``stream``: a raw stream handle instead of ``device``'s current stream.  A combination without an entry raises ValueError."""
+    name = entry_name(geometry, aug is not None, color is not None)
+    if (color is None) != (sums is None):
+        raise ValueError('launch_u8: color and sums go together')
+    if win is not None and geometry != 'letterbox':
+        raise ValueError('launch_u8: win belongs to the letterbox geometry')
+    if padcrop is not None and geometry != 'padcrop':
+        raise ValueError(f'launch_u8: padcrop is an output of the padcrop geometry, not of {geometry}')
+    if (scales is not None and geometry == 'padcrop') or (shifts is not None and geometry == 'resize'):
+        raise ValueError(f'launch_u8: {geometry} writes ' + ('shifts and padcrop, not scales' if geometry == 'padcrop' else 'scales, not shifts'))
+    p = lambda t: t if isinstance(t, ctypes.c_void_p) else nat.ptr(t)      # noqa: E731
+    args = [p(src), p(offsets), p(sizes)]
+    if aug is not None:
+        args.append(p(aug))
+    if geometry == 'letterbox':
+        args.append(p(win))
+    if color is not None:
+        args += [p(color), p(sums)]
+    args.append(p(out))
+    args += {'resize': [p(scales)], 'padcrop': [p(shifts), p(padcrop)], 'letterbox': [p(scales), p(shifts)]}[geometry]
+    rc = getattr(nat.lib(), name)(*args, c_float3(mean), c_float3(std), B, H, W, nat.stream_handle(device) if stream is None else stream)
+    nat.check(rc, name)
 
 
 _STAGE = [None, None]        # two pinned staging buffers used alternately: the H2D copy of the previous batch may still run
@@ -94,36 +144,21 @@ def preprocess_batch(images, input_size, device='cuda', rgb_mean=KITTI_RGB_MEAN,
     elif tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError('preprocess_batch: bad out tensor')
     scales = torch.empty(B, 2, device=dev, dtype=torch.float32)
-    mean = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_mean).reshape(-1)])
-    std = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(rgb_std).reshape(-1)])
     base_meta = {'orig_size': np.concatenate([sizes, np.full((B, 1), 3, np.int32)], 1),
                  'drifts': np.zeros((B, 2), np.int32), 'flipped': [False] * B,
                  'rgb_mean': np.tile(np.asarray(rgb_mean, np.float32).reshape(1, 1, 1, 3), (B, 1, 1, 1)),
                  'rgb_std': np.tile(np.asarray(rgb_std, np.float32).reshape(1, 1, 1, 3), (B, 1, 1, 1))}
     if letterbox:
-        from .boxes import letterbox_meta, letterbox_window
         shifts = torch.empty(B, 2, device=dev, dtype=torch.float32)
-        rc = nat.lib().sqd_preprocess_u8_letterbox_fwd(nat.ptr(src), nat.ptr(d_off), nat.ptr(d_sizes), None, nat.ptr(out), nat.ptr(scales),
-                                                       nat.ptr(shifts), mean, std, B, H, W, nat.stream_handle(dev))
-        nat.check(rc, 'sqd_preprocess_u8_letterbox_fwd')
+        launch_u8('letterbox', src, d_off, d_sizes, out, B, H, W, rgb_mean, rgb_std, dev, scales=scales, shifts=shifts)
         metas = [letterbox_meta(s, letterbox_window(s, (H, W)), (H, W)) for s in sizes]      # the same integers on the host
         base_meta.update({k: np.stack([m[k] for m in metas]) for k in ('scales', 'padding', 'letterbox')})
         return out, (scales, shifts), base_meta
     if forbid_resize:
-        rc = nat.lib().sqd_preprocess_u8_padcrop_fwd(nat.ptr(src), nat.ptr(d_off), nat.ptr(d_sizes), nat.ptr(out), nat.ptr(scales), None,
-                                                     mean, std, B, H, W, nat.stream_handle(dev))
-        nat.check(rc, 'sqd_preprocess_u8_padcrop_fwd')
-        padding, crops = np.zeros((B, 4), np.int16), np.zeros((B, 4), np.int16)      # the same integers on the host (image.py:99-115)
-        for i, (h0, w0) in enumerate(sizes):
-            for size, target, k in ((int(h0), H, 0), (int(w0), W, 2)):
-                if size < target:
-                    padding[i, k] = (target - size) // 2; padding[i, k + 1] = (target - size) - padding[i, k]
-                elif size > target:
-                    crops[i, k] = (size - target) // 2; crops[i, k + 1] = (size - target) - crops[i, k]
-        base_meta.update(padding=padding, crops=crops)
+        launch_u8('padcrop', src, d_off, d_sizes, out, B, H, W, rgb_mean, rgb_std, dev, shifts=scales)
+        rows = np.array([pad_crop(int(h0), H) + pad_crop(int(w0), W) for h0, w0 in sizes], np.int16)      # the same integers on the host
+        base_meta.update(padding=rows[:, [0, 1, 4, 5]], crops=rows[:, [2, 3, 6, 7]])
         return out, scales, base_meta
-    rc = nat.lib().sqd_preprocess_u8_fwd(nat.ptr(src), nat.ptr(d_off), nat.ptr(d_sizes), nat.ptr(out), nat.ptr(scales), mean, std,
-                                         B, H, W, nat.stream_handle(dev))
-    nat.check(rc, 'sqd_preprocess_u8_fwd')
+    launch_u8('resize', src, d_off, d_sizes, out, B, H, W, rgb_mean, rgb_std, dev, scales=scales)
     meta = dict(base_meta, scales=np.stack([np.array([H / s[0], W / s[1]], dtype=np.float32) for s in sizes]))
     return out, scales, meta

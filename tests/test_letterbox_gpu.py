@@ -393,3 +393,78 @@ def test_loader_with_zoom_out_feeds_trainer_run_epoch(sparse):
     for k in ("loss", "class_loss", "score_loss", "bbox_loss"):
         assert np.isfinite(stats[k]), (k, stats)
     assert stats["loss"] > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 7. the one Python dispatch puts every entry's arguments where the entry reads them
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_launch_u8_is_bitwise_a_direct_call_of_each_of_the_nine_entries():
+    """``preprocess.launch_u8`` for every (geometry, aug, colour) against a ctypes call of the same entry whose arguments are written out
+    here by hand, in include/sqd_hip.h's order: outputs and side outputs bit for bit (both start as NaN / -1, so an output the dispatch
+    left out or swapped differs).  The numbers themselves are held by the tests above and by the other input-kernel modules."""
+    from squeezedet_pytorch_amd import _native as nat
+    from squeezedet_pytorch_amd.preprocess import c_float3, launch_u8
+    H, W = 64, 96
+    images = _images([(9, 5), (50, 61), (123, 77)], 11)
+    B = len(images)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    src = t(np.concatenate([im.reshape(-1) for im in images]))
+    offsets = t(np.cumsum([0] + [im.size for im in images[:-1]]).astype(np.int64))
+    sizes = t(np.array([im.shape[:2] for im in images], np.int32))
+    aug = t(np.array([(0, 0, 0), (-7, 5, 1), (3, -11, 0)], np.int32))
+    color = t(np.array([(1., 1., 1.), (1.25, 0.75, 1.5), (0.5, 1.5, 0.25)], np.float32))
+    sums = t(np.array([[(int(im[..., c].astype(np.int64).sum()), int((im[..., c].astype(np.int64) ** 2).sum())) for c in range(3)]
+                       for im in images], np.int64))                     # as sqd_image_stats_u8 writes them
+    win = t(np.array([(5, 7, 40, 70)] * B, np.int32))                    # strictly inside the canvas
+    mean, std = c_float3(oracle.KITTI_RGB_MEAN), c_float3(oracle.KITTI_RGB_STD)
+    lib, p, st = nat.lib(), nat.ptr, nat.stream_handle(dev)
+
+    def fresh():
+        return {"out": torch.full((B, 3, H, W), float("nan"), device=dev), "scales": torch.full((B, 2), float("nan"), device=dev),
+                "shifts": torch.full((B, 2), float("nan"), device=dev), "padcrop": torch.full((B, 8), -1, dtype=torch.int32, device=dev)}
+
+    direct = {
+        "sqd_preprocess_u8_fwd": lambda o: lib.sqd_preprocess_u8_fwd(
+            p(src), p(offsets), p(sizes), p(o["out"]), p(o["scales"]), mean, std, B, H, W, st),
+        "sqd_preprocess_u8_aug_fwd": lambda o: lib.sqd_preprocess_u8_aug_fwd(
+            p(src), p(offsets), p(sizes), p(aug), p(o["out"]), p(o["scales"]), mean, std, B, H, W, st),
+        "sqd_preprocess_u8_aug_color_fwd": lambda o: lib.sqd_preprocess_u8_aug_color_fwd(
+            p(src), p(offsets), p(sizes), p(aug), p(color), p(sums), p(o["out"]), p(o["scales"]), mean, std, B, H, W, st),
+        "sqd_preprocess_u8_padcrop_fwd": lambda o: lib.sqd_preprocess_u8_padcrop_fwd(
+            p(src), p(offsets), p(sizes), p(o["out"]), p(o["shifts"]), p(o["padcrop"]), mean, std, B, H, W, st),
+        "sqd_preprocess_u8_padcrop_aug_fwd": lambda o: lib.sqd_preprocess_u8_padcrop_aug_fwd(
+            p(src), p(offsets), p(sizes), p(aug), p(o["out"]), p(o["shifts"]), p(o["padcrop"]), mean, std, B, H, W, st),
+        "sqd_preprocess_u8_padcrop_aug_color_fwd": lambda o: lib.sqd_preprocess_u8_padcrop_aug_color_fwd(
+            p(src), p(offsets), p(sizes), p(aug), p(color), p(sums), p(o["out"]), p(o["shifts"]), p(o["padcrop"]), mean, std, B, H, W, st),
+        "sqd_preprocess_u8_letterbox_fwd": lambda o: lib.sqd_preprocess_u8_letterbox_fwd(
+            p(src), p(offsets), p(sizes), p(win), p(o["out"]), p(o["scales"]), p(o["shifts"]), mean, std, B, H, W, st),
+        "sqd_preprocess_u8_letterbox_aug_fwd": lambda o: lib.sqd_preprocess_u8_letterbox_aug_fwd(
+            p(src), p(offsets), p(sizes), p(aug), p(win), p(o["out"]), p(o["scales"]), p(o["shifts"]), mean, std, B, H, W, st),
+        "sqd_preprocess_u8_letterbox_aug_color_fwd": lambda o: lib.sqd_preprocess_u8_letterbox_aug_color_fwd(
+            p(src), p(offsets), p(sizes), p(aug), p(win), p(color), p(sums), p(o["out"]), p(o["scales"]), p(o["shifts"]), mean, std,
+            B, H, W, st),
+    }
+    side_of = {"resize": ("scales",), "padcrop": ("shifts", "padcrop"), "letterbox": ("scales", "shifts")}
+    stem = {"resize": "sqd_preprocess_u8", "padcrop": "sqd_preprocess_u8_padcrop", "letterbox": "sqd_preprocess_u8_letterbox"}
+    seen = {}
+    for geometry, keys in side_of.items():
+        for suffix, blocks in (("_fwd", {}), ("_aug_fwd", {"aug": aug}), ("_aug_color_fwd", {"aug": aug, "color": color, "sums": sums})):
+            name = stem[geometry] + suffix
+            got, want = fresh(), fresh()
+            launch_u8(geometry, src, offsets, sizes, got["out"], B, H, W, oracle.KITTI_RGB_MEAN, oracle.KITTI_RGB_STD, dev,
+                      **blocks, **({"win": win} if geometry == "letterbox" else {}), **{k: got[k] for k in keys})
+            assert direct[name](want) == 0, name
+            torch.cuda.synchronize()
+            for k in ("out", "scales", "shifts", "padcrop"):
+                g, w = got[k].cpu().numpy(), want[k].cpu().numpy()
+                assert np.array_equal(g.view(np.int32), w.view(np.int32)), (name, k)
+                written = not (np.isnan(g).any() if g.dtype == np.float32 else (g == -1).any())
+                assert written == (k == "out" or k in keys), (name, k)           # every output of the entry, and no other
+            seen[name] = got["out"].cpu().numpy()
+    assert sorted(seen) == sorted(direct)
+    # the nine are nine different launches: no two combinations ran the same entry (the identity colour row aside, every image differs)
+    names = sorted(seen)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            assert not np.array_equal(seen[a], seen[b]), (a, b)

@@ -216,3 +216,108 @@ def test_detect_dataset_driver(capsys):
         if 'boxes' in r and 'boxes' in w:
             common = set(r['anchor_idx'].tolist()) & set(w['anchor_idx'].tolist())
             assert len(common) >= min(len(r['anchor_idx']), len(w['anchor_idx'])) - 3
+
+
+_GEOMETRY_STEM = {'resize': 'sqd_preprocess_u8', 'padcrop': 'sqd_preprocess_u8_padcrop', 'letterbox': 'sqd_preprocess_u8_letterbox'}
+_FORMS = [(False, False, '_fwd'), (True, False, '_aug_fwd'), (True, True, '_aug_color_fwd')]
+
+
+@pytest.mark.parametrize("geometry", list(_GEOMETRY_STEM))
+@pytest.mark.parametrize("aug,color,suffix", _FORMS)
+def test_launch_u8_selects_the_entry_and_assembles_its_arguments(geometry, aug, color, suffix):
+    """The one Python dispatch against ``_native._SIGNATURES``, without a launch: every argument a non-null host address that is never
+    dereferenced and ``B = 0``, so the entry that was selected answers status 1 itself -- a wrong argument count or type would be a ctypes
+    error instead, and the message names the entry that was called."""
+    import ctypes
+    import __graft_entry__ as ge
+    ge.build()
+    from squeezedet_pytorch_amd import _native as nat
+    from squeezedet_pytorch_amd import preprocess as pre
+    want = _GEOMETRY_STEM[geometry] + suffix
+    assert pre.entry_name(geometry, aug, color) == want and want in nat._SIGNATURES
+    keep = (ctypes.c_ulonglong * 8)()
+    p = ctypes.c_void_p(ctypes.addressof(keep))
+    blocks = {'resize': dict(scales=p), 'padcrop': dict(shifts=p, padcrop=p), 'letterbox': dict(win=p, scales=p, shifts=p)}[geometry]
+    if aug:
+        blocks.update(aug=p)
+    if color:
+        blocks.update(color=p, sums=p)
+    with pytest.raises(RuntimeError) as e:
+        pre.launch_u8(geometry, p, p, p, p, 0, 8, 8, (1., 2., 3.), (4., 5., 6.), None, stream=ctypes.c_void_p(0), **blocks)
+    assert str(e.value) == f'{want}: bad argument (status 1)'
+    # the optional outputs may be left out (NULL)
+    with pytest.raises(RuntimeError, match=want + ': bad argument'):
+        pre.launch_u8(geometry, p, p, p, p, 0, 8, 8, (1., 2., 3.), (4., 5., 6.), None, stream=ctypes.c_void_p(0),
+                      **{k: v for k, v in blocks.items() if k in ('aug', 'color', 'sums')})
+
+
+def test_launch_u8_refuses_combinations_without_an_entry():
+    import ctypes
+    from squeezedet_pytorch_amd import preprocess as pre
+    keep = (ctypes.c_ulonglong * 8)()
+    p = ctypes.c_void_p(ctypes.addressof(keep))
+
+    def call(geometry, **blocks):
+        pre.launch_u8(geometry, p, p, p, p, 0, 8, 8, (1., 2., 3.), (4., 5., 6.), None, stream=ctypes.c_void_p(0), **blocks)
+
+    for geometry in _GEOMETRY_STEM:
+        with pytest.raises(ValueError):
+            call(geometry, color=p, sums=p)                              # colour without aug
+        with pytest.raises(ValueError):
+            call(geometry, aug=p, color=p)                               # colour without the channel sums
+    for geometry in ('resize', 'padcrop'):
+        with pytest.raises(ValueError):
+            call(geometry, win=p)                                        # a window outside letterbox
+        with pytest.raises(ValueError):
+            call(geometry, aug=p, win=p)
+    with pytest.raises(ValueError):
+        call('letterbox', padcrop=p)                                     # letterbox with pad / crop outputs
+    with pytest.raises(ValueError):
+        call('resize', padcrop=p)
+    with pytest.raises(ValueError):
+        call('resize', shifts=p)
+    with pytest.raises(ValueError):
+        call('padcrop', scales=p)
+    with pytest.raises(ValueError):
+        call('stretch')
+    with pytest.raises(ValueError):
+        pre.entry_name('resize', aug=False, color=True)
+
+
+def test_pad_crop_equals_the_three_formulas_it_replaces():
+    """``boxes.pad_crop`` against the three earlier spellings of crop_or_pad's integers (image.py:99-115), each restated here as it stood:
+    the [B, 4] array loop of ``preprocess_batch``, the per-image array loop of ``DetectStream._image_meta`` and the tuple of
+    ``augment._pad_crop``; every (size, target) in 1..40 squared, size == target included."""
+    from squeezedet_pytorch_amd.boxes import pad_crop
+
+    def batch_form(size, target):
+        padding, crops = np.zeros((1, 4), np.int16), np.zeros((1, 4), np.int16)
+        for s, t, k in ((size, target, 0),):
+            if s < t:
+                padding[0, k] = (t - s) // 2; padding[0, k + 1] = (t - s) - padding[0, k]
+            elif s > t:
+                crops[0, k] = (s - t) // 2; crops[0, k + 1] = (s - t) - crops[0, k]
+        return int(padding[0, 0]), int(padding[0, 1]), int(crops[0, 0]), int(crops[0, 1])
+
+    def stream_form(size, target):
+        pad, crop = np.zeros(4, np.int16), np.zeros(4, np.int16)
+        for s, t, k in ((int(size), target, 2),):
+            if s < t:
+                pad[k] = (t - s) // 2; pad[k + 1] = (t - s) - pad[k]
+            elif s > t:
+                crop[k] = (s - t) // 2; crop[k + 1] = (s - t) - crop[k]
+        return int(pad[2]), int(pad[3]), int(crop[2]), int(crop[3])
+
+    def tuple_form(size, target):
+        if size < target:
+            return (target - size) // 2, (target - size) - (target - size) // 2, 0, 0
+        if size > target:
+            return 0, 0, (size - target) // 2, (size - target) - (size - target) // 2
+        return 0, 0, 0, 0
+
+    for size in range(1, 41):
+        for target in range(1, 41):
+            got = pad_crop(size, target)
+            assert all(isinstance(v, int) for v in got)
+            assert got == batch_form(size, target) == stream_form(size, target) == tuple_form(size, target), (size, target)
+            assert got[0] + got[1] + size - got[2] - got[3] == target
