@@ -621,6 +621,19 @@ int sqd_sgd_chunk_elems(void);
 int sqd_sgd_clip_step_chunked(const void* descs_dev, const void* chunks_dev, int nchunks, const float* grad_base,
                               const float* sumsq_parts, float* norm_out, float max_norm, float lr, float momentum, float weight_decay,
                               void* stream);
+/* The chunked step with the hyper-parameters in DEVICE memory: hyper = float[4] {lr, momentum, weight_decay, max_norm}, read by every
+ * workgroup, so a captured step (hipGraph) follows a learning-rate schedule without a re-capture.  Same per-element arithmetic as the
+ * launch-argument forms (equal values give equal bits).  hyper[3] <= 0 = a coefficient of 1; sumsq_parts NULL = the norm is not
+ * evaluated and the step does not clip, whatever hyper[3] holds (whether the norm launch exists is fixed when a step is captured).
+ * sqd_fill_f32x4 writes such a table: dst[0..4) = {a, b, c, d} by a one-thread launch, the values travelling as launch arguments. */
+int sqd_sgd_clip_step_chunked_dev(const void* descs_dev, const void* chunks_dev, int nchunks, const float* grad_base,
+                                  const float* sumsq_parts, float* norm_out, const float* hyper, void* stream);
+int sqd_fill_f32x4(float* dst, float a, float b, float c, float d, void* stream);
+/* The training log on the device (one small workgroup, no atomics): losses = float[4][B], the per-image values of a loss launch.  For
+ * each component k the B values are added in index order in float64: sums[k] += that sum, ring[cursor % cap][k] = (float)(sum / B);
+ * then sums[4] += B and cursor += 1.  sums: double[5], ring: float[cap][4], cursor: one unsigned, all on the device; the host reads
+ * them when it wants to print (one sync per print interval instead of one per iteration). */
+int sqd_train_log_push(const float* losses, int B, double* sums, float* ring, unsigned* cursor, int cap, void* stream);
 
 /* Detection AP on the device (VOC / COCO style, any class count; DESIGN.md "Detection AP on the device").
  * sqd_det_match_fwd labels every slot of the packed detect output of a batch -- count [B] int32, class_ids [B][K] int64, scores [B][K],

@@ -62,6 +62,7 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         sparse_gt=False,             # training ground truth as the list of positives (ops.SparseGT in batch['gt_sparse']) instead of dense
         ignore_overlap=None,         # None: off.  A float in (0, 1] (0.5 is the documented value; needs sparse_gt): anchors covered to that share
                                      # by a flagged box (DontCare / difficult / crowd) leave the loss (batch['gt_ignore'], ops.loss_masked_*)
+        graph_step=False,            # training: replay the step as one captured hipGraph (trainer.GraphedStep; needs a FusedClipSGD, one process)
         inflight=2,                  # batches in flight on the device in Detector.stream / detect_dataset (lanes.DetectStream)
         input_size=tuple(input_size), num_classes=num_classes, class_names=tuple(class_names),
         anchors=anchors, anchors_per_grid=int(np.asarray(anchors_seed).shape[0]),

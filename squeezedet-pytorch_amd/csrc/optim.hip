@@ -12,6 +12,14 @@
 
 struct SgdDesc { float* p; long long g; float* m; long long n; };      // g: element offset into g_base, or an address when g_base is null
 
+// One element of the step, torch's order.  The ONE source expression of every kernel below (-ffp-contract=off: equal values, equal bits).
+__device__ __forceinline__ void sgd_one(float p, float gr, float m, float coef, float wd, float momentum, float lr, float& pn, float& mn) {
+  float g = gr * coef;
+  g = g + wd * p;
+  mn = momentum * m + g;
+  pn = p - lr * mn;
+}
+
 __global__ __launch_bounds__(256) void sgd_clip_batched_kernel(const SgdDesc* __restrict__ descs, const float* __restrict__ g_base,
                                                                const float* __restrict__ total_norm, float max_norm, float lr, float momentum,
                                                                float wd, int norm_parts, float* __restrict__ norm_out) {
@@ -35,12 +43,6 @@ __global__ __launch_bounds__(256) void sgd_clip_batched_kernel(const SgdDesc* __
   }
   const long long stride = (long long)gridDim.x * blockDim.x;
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  auto one = [&](float p, float gr, float m, float& pn, float& mn) {
-    float g = gr * coef;
-    g = g + wd * p;
-    mn = momentum * m + g;
-    pn = p - lr * mn;
-  };
   // 16-byte accesses where the three pointers allow it (they do for every tensor of the model), scalar tail / fallback
   const bool vec = ((((uintptr_t)d.p) | ((uintptr_t)dg) | ((uintptr_t)d.m)) & 15) == 0;
   const long long n4 = vec ? d.n >> 2 : 0;
@@ -48,12 +50,12 @@ __global__ __launch_bounds__(256) void sgd_clip_batched_kernel(const SgdDesc* __
     const f32x4 p = ((const f32x4*)d.p)[i], gr = ((const f32x4*)dg)[i], m = ((const f32x4*)d.m)[i];
     float pn[4], mn[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) one(p[e], gr[e], m[e], pn[e], mn[e]);
+    for (int e = 0; e < 4; ++e) sgd_one(p[e], gr[e], m[e], coef, wd, momentum, lr, pn[e], mn[e]);
     ((f32x4*)d.m)[i] = (f32x4){mn[0], mn[1], mn[2], mn[3]}; ((f32x4*)d.p)[i] = (f32x4){pn[0], pn[1], pn[2], pn[3]};
   }
   for (long long i = 4 * n4 + tid; i < d.n; i += stride) {
     float pn, mn;
-    one(d.p[i], dg[i], d.m[i], pn, mn);
+    sgd_one(d.p[i], dg[i], d.m[i], coef, wd, momentum, lr, pn, mn);
     d.m[i] = mn; d.p[i] = pn;
   }
 }
@@ -62,9 +64,9 @@ __global__ __launch_bounds__(256) void sgd_clip_batched_kernel(const SgdDesc* __
 // 16 to 500 k elements: 64 workgroups each left the large ones 8 serial rounds and the small ones 63 idle workgroups -- 47 us for 42 MB).
 // chunks: device array of [nchunks][2] int64 = {tensor, first element}; a workgroup handles SQD_SGD_CHUNK elements of one tensor.
 #define SQD_SGD_CHUNK 4096
-__global__ __launch_bounds__(256) void sgd_clip_chunked_kernel(const SgdDesc* __restrict__ descs, const long long* __restrict__ chunks,
-                                                               const float* __restrict__ g_base, const float* __restrict__ parts, float max_norm,
-                                                               float lr, float momentum, float wd, float* __restrict__ norm_out) {
+__device__ __forceinline__ void sgd_clip_chunk(const SgdDesc* __restrict__ descs, const long long* __restrict__ chunks,
+                                               const float* __restrict__ g_base, const float* __restrict__ parts, float max_norm,
+                                               float lr, float momentum, float wd, float* __restrict__ norm_out) {
   const SgdDesc d = descs[chunks[2 * blockIdx.x]];
   const long long e0 = chunks[2 * blockIdx.x + 1];
   const float* __restrict__ dg = g_base ? g_base + d.g : (const float*)d.g;
@@ -79,12 +81,6 @@ __global__ __launch_bounds__(256) void sgd_clip_chunked_kernel(const SgdDesc* __
     coef = max_norm / (tn + 1e-6f);
     coef = coef < 1.f ? coef : 1.f;
   }
-  auto one = [&](float p, float gr, float m, float& pn, float& mn) {
-    float g = gr * coef;
-    g = g + wd * p;
-    mn = momentum * m + g;
-    pn = p - lr * mn;
-  };
   const long long e1 = (e0 + SQD_SGD_CHUNK < d.n) ? e0 + SQD_SGD_CHUNK : d.n;
   const bool vec = ((((uintptr_t)d.p) | ((uintptr_t)dg) | ((uintptr_t)d.m)) & 15) == 0;       // (chunk origins are multiples of 4 elements)
   const long long q0 = e0 >> 2, q1 = vec ? (e1 >> 2) : q0;
@@ -92,17 +88,55 @@ __global__ __launch_bounds__(256) void sgd_clip_chunked_kernel(const SgdDesc* __
     const f32x4 p = ((const f32x4*)d.p)[i], gr = ((const f32x4*)dg)[i], m = ((const f32x4*)d.m)[i];
     float pn[4], mn[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) one(p[e], gr[e], m[e], pn[e], mn[e]);
+    for (int e = 0; e < 4; ++e) sgd_one(p[e], gr[e], m[e], coef, wd, momentum, lr, pn[e], mn[e]);
     ((f32x4*)d.m)[i] = (f32x4){mn[0], mn[1], mn[2], mn[3]}; ((f32x4*)d.p)[i] = (f32x4){pn[0], pn[1], pn[2], pn[3]};
   }
   for (long long i = 4 * q1 + threadIdx.x; i < e1; i += 256) {
     float pn, mn;
-    one(d.p[i], dg[i], d.m[i], pn, mn);
+    sgd_one(d.p[i], dg[i], d.m[i], coef, wd, momentum, lr, pn, mn);
     d.m[i] = mn; d.p[i] = pn;
   }
 }
 
+__global__ __launch_bounds__(256) void sgd_clip_chunked_kernel(const SgdDesc* __restrict__ descs, const long long* __restrict__ chunks,
+                                                               const float* __restrict__ g_base, const float* __restrict__ parts, float max_norm,
+                                                               float lr, float momentum, float wd, float* __restrict__ norm_out) {
+  sgd_clip_chunk(descs, chunks, g_base, parts, max_norm, lr, momentum, wd, norm_out);
+}
+
+// The chunked step with the hyper-parameters read from DEVICE memory: hyper = {lr, momentum, weight_decay, max_norm}, read by every
+// workgroup.  A captured step (hipGraph) then follows a learning-rate schedule without a re-capture: the table is rewritten in front
+// of a replay (sqd_fill_f32x4).  Whether the norm is evaluated at all is structural (parts given or not): without parts the step does
+// not clip, whatever hyper[3] says.
+__global__ __launch_bounds__(256) void sgd_clip_chunked_dev_kernel(const SgdDesc* __restrict__ descs, const long long* __restrict__ chunks,
+                                                                   const float* __restrict__ g_base, const float* __restrict__ parts,
+                                                                   const float* __restrict__ hyper, float* __restrict__ norm_out) {
+  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2], max_norm = parts ? hyper[3] : 0.f;
+  sgd_clip_chunk(descs, chunks, g_base, parts, max_norm, lr, momentum, wd, norm_out);
+}
+
+// hyper[0..4) = {a, b, c, d}: one thread.  The values travel as launch arguments (no staging buffer that a later call could overwrite
+// while a copy is still in flight).
+__global__ void fill_f32x4_kernel(float* __restrict__ dst, float a, float b, float c, float d) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { dst[0] = a; dst[1] = b; dst[2] = c; dst[3] = d; }
+}
+
+extern "C" int sqd_fill_f32x4(float* dst, float a, float b, float c, float d, void* stream) {
+  SQD_CHECK_ARG(dst);
+  hipLaunchKernelGGL(fill_f32x4_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dst, a, b, c, d);
+  return sqd_launch_status();
+}
+
 extern "C" int sqd_sgd_chunk_elems(void) { return SQD_SGD_CHUNK; }
+
+// sqd_sgd_clip_step_chunked with hyper_dev = DEVICE float[4] {lr, momentum, weight_decay, max_norm}; sumsq_parts NULL = no clipping.
+extern "C" int sqd_sgd_clip_step_chunked_dev(const void* descs_dev, const void* chunks_dev, int nchunks, const float* grad_base,
+                                             const float* sumsq_parts, float* norm_out, const float* hyper_dev, void* stream) {
+  SQD_CHECK_ARG(descs_dev && chunks_dev && nchunks > 0 && hyper_dev);
+  hipLaunchKernelGGL(sgd_clip_chunked_dev_kernel, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, (const SgdDesc*)descs_dev,
+                     (const long long*)chunks_dev, grad_base, sumsq_parts, hyper_dev, norm_out);
+  return sqd_launch_status();
+}
 
 // descs_dev as for sqd_sgd_clip_step; chunks_dev: [nchunks][2] int64 {tensor index, first element (a multiple of sqd_sgd_chunk_elems())}
 // covering every tensor; sumsq_parts / norm_out as for sqd_sgd_clip_step_parts (sumsq_parts may be NULL when max_norm <= 0).
@@ -188,5 +222,36 @@ extern "C" int sqd_grad_scale(float* g, long long n, float mul, const float* div
   long long blocks = (n + 1023) / 1024;
   blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
   hipLaunchKernelGGL(grad_scale_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, mul, div_by, fill_ptr, fill_value);
+  return sqd_launch_status();
+}
+
+// ---- the training log on the device (trainer.GraphedStep): per-epoch sums and a ring of batch means, no host sync per iteration ----
+// losses: float[4][B], the loss launches' per-image values.  For each component k: s = the B values added in index order in float64;
+// sums[k] += s; ring[(cursor % cap)][k] = (float)(s / B).  sums[4] += B; cursor += 1.  ONE workgroup, so the read-modify-writes need no
+// atomics; thread k adds component k, thread 0 stores.
+__global__ __launch_bounds__(64) void train_log_push_kernel(const float* __restrict__ losses, int B, double* __restrict__ sums,
+                                                            float* __restrict__ ring, unsigned* __restrict__ cursor, int cap) {
+  __shared__ double s[4];
+  if (threadIdx.x < 4) {
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) acc += (double)losses[(long long)threadIdx.x * B + b];
+    s[threadIdx.x] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned c = *cursor;
+    float* slot = ring + 4ll * (c % (unsigned)cap);
+    for (int k = 0; k < 4; ++k) {
+      sums[k] += s[k];
+      slot[k] = (float)(s[k] / (double)B);
+    }
+    sums[4] += (double)B;
+    *cursor = c + 1u;
+  }
+}
+
+extern "C" int sqd_train_log_push(const float* losses, int B, double* sums, float* ring, unsigned* cursor, int cap, void* stream) {
+  SQD_CHECK_ARG(losses && sums && ring && cursor && B > 0 && cap > 0);
+  hipLaunchKernelGGL(train_log_push_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, losses, B, sums, ring, cursor, cap);
   return sqd_launch_status();
 }

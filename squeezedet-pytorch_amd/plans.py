@@ -47,13 +47,16 @@ _PACK_TABLES = {}
 def _pack_tables(what, dev, *rows):
     """Device copies of the descriptor tables of one batched pack launch, cached by content.  A table only holds pointers and
     shapes: after the first optimizer step it is the same every step, so repeated rows make no host-to-device copy (that is also
-    what keeps the training step hipGraph-capturable).  Bounded: the cache is emptied when it outgrows 16 launches' tables."""
+    what keeps the training step hipGraph-capturable).  Bounded: beyond 16 launches' tables the least recently used one goes -- never
+    one of the latest few, so the tables of a refresh that ran a moment ago (all kinds of one model) are still there when the same
+    refresh is captured."""
     key = (what, str(dev)) + tuple(tuple(tuple(r) for r in rs) for rs in rows)
-    tables = _PACK_TABLES.get(key)
+    tables = _PACK_TABLES.pop(key, None)
     if tables is None:
-        if len(_PACK_TABLES) > 16:
-            _PACK_TABLES.clear()
-        tables = _PACK_TABLES[key] = tuple(torch.tensor(rs, dtype=torch.int64).to(dev) for rs in rows)
+        while len(_PACK_TABLES) > 16:
+            del _PACK_TABLES[next(iter(_PACK_TABLES))]
+        tables = tuple(torch.tensor(rs, dtype=torch.int64).to(dev) for rs in rows)
+    _PACK_TABLES[key] = tables                   # (re-inserted on a hit: the dict's order is the order of use)
     return tables
 
 

@@ -325,6 +325,8 @@ class Trainer(object):
         self.model, self.optimizer, self.lr_scheduler, self.cfg = model, optimizer, lr_scheduler, cfg
         self.metrics = list(LOSS_KEYS)
         self.set_device(cfg.gpus, cfg.chunk_sizes, cfg.device)
+        if getattr(cfg, 'graph_step', False):
+            self.graphed_step()                    # (what the captured step refuses -- optimizer, process group, model -- is refused here)
 
     def set_device(self, gpus, chunk_sizes, device):
         """``gpus`` / ``chunk_sizes`` describe the global job as in the reference; this process only owns ``device``.
@@ -378,7 +380,51 @@ class Trainer(object):
         logged = logged.tolist()                   # the iteration's single host sync
         return [v / logged[-1] for v in logged[:-1]], n
 
+    def graphed_step(self):
+        """The ``GraphedStep`` of ``cfg.graph_step`` (made on first use; its refusals surface here)."""
+        gs = getattr(self, '_graphed', None)
+        if gs is None or gs.model is not self.model or gs.optimizer is not self.optimizer:
+            if isinstance(self.optimizer, FusedClipSGD) and not self.optimizer.max_norm > 0:
+                raise ValueError('Trainer: cfg.graph_step clips inside the optimizer launch: construct the FusedClipSGD with '
+                                 'max_norm=cfg.grad_norm (with max_norm=0 the eager loop clips with a torch call the captured step lacks)')
+            gs = self._graphed = GraphedStep(self.model, self.optimizer, self.cfg)
+        return gs
+
+    def _run_epoch_graphed(self, epoch, data_loader):
+        """The train phase with ``cfg.graph_step``: every iteration is one ``GraphedStep.step`` and no host sync; the losses come from
+        the device log, read at every ``print_interval`` and at the epoch's end.  The printed line has the eager loop's format with the
+        latest iteration's losses; ``data`` / ``net`` are averages over the iterations since the last print (a per-iteration host clock
+        without a sync would time the enqueue only)."""
+        t_epoch = time.time()
+        gs = self.graphed_step()
+        self.model.train(True)
+        gs.reset_log()
+        limit = len(data_loader) if self.cfg.num_iters < 0 else self.cfg.num_iters
+        t_mark = t_int = time.time()
+        t_data, n_int = 0.0, 0
+        for it, batch in enumerate(data_loader):
+            if it >= limit:
+                break
+            batch = self._to_device(batch)
+            t_data += time.time() - t_mark
+            gs.step(batch)
+            n_int += 1
+            if self.rank == 0 and it % self.cfg.print_interval == 0:
+                _, latest, _ = gs.read_log()                 # the interval's one host sync
+                t_all = time.time() - t_int
+                losses = ' '.join(f'| {k} {latest[k]:.3f}' for k in self.metrics)
+                print(f'epoch {epoch}: train [{it}/{limit}] {losses} | data {1e3 * t_data / n_int:.1f}ms | net {1e3 * (t_all - t_data) / n_int:.1f}ms')
+                t_int, t_data, n_int = time.time(), 0.0, 0
+            t_mark = time.time()
+        self.lr_scheduler.step()
+        sums, _, _ = gs.read_log()
+        out = {k: (sums[k] / sums['images'] if sums['images'] else 0.0) for k in self.metrics}
+        out['epoch_time'] = (time.time() - t_epoch) / 60.0
+        return out
+
     def run_epoch(self, phase, epoch, data_loader):
+        if phase == 'train' and getattr(self.cfg, 'graph_step', False):
+            return self._run_epoch_graphed(epoch, data_loader)
         t_epoch = time.time()
         train = phase == 'train'
         self.model.train(train)
@@ -412,6 +458,27 @@ class Trainer(object):
         return self.run_epoch('val', epoch, data_loader)
 
 
+class HyperTable:
+    """When the device copy of a few hyper-parameters is written: ``refresh(values)`` calls ``write(values)`` if they differ from what
+    was written last (or ``force``), never otherwise; while a stream capture is under way it writes nothing and raises if it would
+    have to -- the write would be recorded into the graph with the values of the capture."""
+
+    def __init__(self, write):
+        self.write = write
+        self.written = None
+
+    def refresh(self, values, capturing=False, force=False):
+        values = tuple(float(v) for v in values)
+        if values == self.written and not force:
+            return False
+        if capturing:
+            raise RuntimeError(f'the device hyper-parameter table is stale under stream capture (holds {self.written}, wanted {values}): '
+                               'call refresh_hyper() before the capture begins')
+        self.write(values)
+        self.written = values
+        return True
+
+
 class FusedClipSGD(torch.optim.Optimizer):
     """``torch.nn.utils.clip_grad_norm_(params, max_norm)`` + ``torch.optim.SGD(params, lr, momentum, weight_decay).step()``
     (src/engine/trainer.py:47-50) as ONE launch over all parameter tensors (csrc/optim.hip, sqd_sgd_clip_step): torch runs the pair
@@ -424,8 +491,12 @@ class FusedClipSGD(torch.optim.Optimizer):
     ``max_norm`` and is read at every ``step()``, so ``torch.optim.lr_scheduler.StepLR(opt, 60, 0.5)`` (the reference's schedule,
     src/train.py:36, stepped at src/engine/trainer.py:67) drives it like ``torch.optim.SGD``.  ``max_norm > 0`` clips INSIDE
     ``step()``: a caller that keeps the reference's explicit ``clip_grad_norm_`` line must construct it with ``max_norm=0`` (or
-    drop the line, as ``Trainer._iteration`` does) -- otherwise the gradient is clipped twice.  The hyper-parameters are launch
-    arguments: a hipGraph replay of a captured step keeps the values of the capture (re-capture after an LR change)."""
+    drop the line, as ``Trainer._iteration`` does) -- otherwise the gradient is clipped twice.  By default the hyper-parameters are
+    launch arguments: a hipGraph replay of a captured step keeps the values of the capture.  With ``hyper_on_device = True`` they live
+    in a device ``float[4]`` table that the kernel reads (``sqd_sgd_clip_step_chunked_dev``; flat-gradient layout only): ``step()``
+    rewrites the table -- one one-thread launch, only when a value of ``param_groups[0]`` changed -- and whoever replays a captured step
+    calls ``refresh_hyper()`` in front of the replay, so an LR schedule needs no re-capture.  Only whether the norm is evaluated at all
+    (``max_norm > 0``) is fixed by the capture: a caller that switches between zero and positive re-captures."""
 
     def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, max_norm=0.0, flat_grad=None):
         params = [p for p in params if p.requires_grad]
@@ -445,6 +516,9 @@ class FusedClipSGD(torch.optim.Optimizer):
         self._table = self._table_key = self._chunks = None
         self._norm_ws = None                           # partial sums of squares + the norm (device)
         self.last_norm = None
+        self.hyper_on_device = False                   # the kernel reads {lr, momentum, weight_decay, max_norm} from device memory
+        self._hyper_dev = None                         # that table (device float[4])
+        self._hyper_table = HyperTable(self._write_hyper)
 
     @property
     def params(self):
@@ -462,6 +536,24 @@ class FusedClipSGD(torch.optim.Optimizer):
         if getattr(self, 'param_groups', None):
             raise ValueError('FusedClipSGD: one parameter group only')
         super().add_param_group(param_group)
+
+    def _hyper_values(self):
+        return (self.lr, self.momentum, self.weight_decay, self.max_norm)
+
+    def _write_hyper(self, values):
+        from . import _native as nat
+        dev = self.params[0].device
+        if self._hyper_dev is None or self._hyper_dev.device != dev:
+            self._hyper_dev = torch.zeros(4, device=dev, dtype=torch.float32)
+        nat.check(nat.lib().sqd_fill_f32x4(nat.ptr(self._hyper_dev), *[float(v) for v in values], nat.stream_handle(dev)), 'sqd_fill_f32x4')
+
+    def refresh_hyper(self):
+        """Bring the device table of ``hyper_on_device`` up to date with ``param_groups[0]`` on the current stream (a one-thread launch,
+        only when a value changed since the last write): what a caller does in front of a replay of a captured step.  -> whether it
+        wrote.  Raises under stream capture if the table is stale (the write would become part of the graph with today's values)."""
+        dev = self.params[0].device
+        return self._hyper_table.refresh(self._hyper_values(), capturing=torch.cuda.is_current_stream_capturing(),
+                                   force=self._hyper_dev is None or self._hyper_dev.device != dev)
 
     def _flat_base(self, grads):
         """The flat gradient tensor if the gradients are consecutive views of it (the HIP backward's layout), else None."""
@@ -491,6 +583,9 @@ class FusedClipSGD(torch.optim.Optimizer):
         if any(g is None for g in grads):
             raise RuntimeError('FusedClipSGD.step: a parameter has no gradient')
         flat = self._flat_base(grads)
+        if self.hyper_on_device and flat is None:
+            raise RuntimeError('FusedClipSGD.step: hyper_on_device needs the flat-gradient layout (flat_grad given and every p.grad a '
+                               'consecutive view of that buffer, as the HIP backward leaves them); these gradients are separate tensors')
         if flat is None:
             grads = [g if g.is_contiguous() else g.contiguous() for g in grads]
         # the descriptor table holds the parameter and momentum addresses and, per tensor, its offset into the flat gradient
@@ -513,7 +608,18 @@ class FusedClipSGD(torch.optim.Optimizer):
             self._table_key = key
         norm = None
         max_norm = self.max_norm
-        if max_norm > 0 and flat is not None:
+        if self.hyper_on_device:
+            self.refresh_hyper()                       # (writes when a value changed; under capture: raises if it would have to)
+            parts = None
+            if max_norm > 0:                           # structural: a captured step keeps or lacks the norm launch
+                if self._norm_ws is None:
+                    self._norm_ws = torch.empty(int(nat.lib().sqd_grad_sumsq_parts()) + 1, device=flat.device, dtype=torch.float32)
+                parts, norm = self._norm_ws[:-1], self._norm_ws[-1]
+                nat.check(nat.lib().sqd_grad_sumsq(nat.ptr(flat), self.total, nat.ptr(parts), nat.stream_handle(flat.device)), 'sqd_grad_sumsq')
+            nat.check(nat.lib().sqd_sgd_clip_step_chunked_dev(nat.ptr(self._table), nat.ptr(self._chunks), self._chunks.shape[0], nat.ptr(flat),
+                                                              nat.ptr(parts), nat.ptr(norm), nat.ptr(self._hyper_dev),
+                                                              nat.stream_handle(params[0].device)), 'sqd_sgd_clip_step_chunked_dev')
+        elif max_norm > 0 and flat is not None:
             # the norm of the flat gradient buffer: partial sums of squares by one small launch, finished (fixed order) inside the step
             if self._norm_ws is None:
                 self._norm_ws = torch.empty(int(nat.lib().sqd_grad_sumsq_parts()) + 1, device=flat.device, dtype=torch.float32)
@@ -549,6 +655,300 @@ class FusedClipSGD(torch.optim.Optimizer):
                 g[k] = float(sd[k])
         if sd.get('initial_lr') is not None:
             g['initial_lr'] = float(sd['initial_lr'])
+
+
+SPARSE_CAP_MIN = 64
+LOG_RING = 64                                    # batch means the device log keeps (a print interval reads the latest)
+LOG_ROWS = ('class_loss', 'score_loss', 'bbox_loss', 'loss')      # row order of the loss launches' [4,B] output = of the device log
+
+
+def sparse_capacity(total, current=0):
+    """Entries the fixed sparse-gt buffers of a captured step hold: the next power of two at or above the largest ``total`` seen, at
+    least ``SPARSE_CAP_MIN``; never shrinks (``current``: the capacity so far)."""
+    cap = max(int(current), SPARSE_CAP_MIN)
+    while cap < int(total):
+        cap *= 2
+    return cap
+
+
+def gt_form(batch):
+    """'dense' | 'sparse' | 'masked': which loss launches a batch runs."""
+    if 'gt' in batch:
+        return 'dense'
+    if 'gt_sparse' not in batch:
+        raise ValueError('GraphedStep: the batch carries neither gt nor gt_sparse')
+    return 'masked' if batch.get('gt_ignore') is not None else 'sparse'
+
+
+def step_signature(image_shape, form, cap, training, trainable, clip_on, loss_weights):
+    """What a captured training step is valid for: a step whose signature differs runs other launches, other grids or other buffers.
+    ``image_shape``: (B, H, W); ``form``: ``gt_form``; ``cap``: the sparse capacity (0 for dense); ``trainable``: names of the
+    parameters that require grad; ``clip_on``: whether the gradient norm is evaluated; ``loss_weights``: launch arguments of the loss."""
+    B, H, W = (int(v) for v in image_shape)
+    return (B, H, W, str(form), int(cap), bool(training), tuple(trainable), bool(clip_on), tuple(float(w) for w in loss_weights))
+
+
+class GraphedStep:
+    """The training step -- ``forward_mean``, ``zero_grad``, ``backward``, ``optimizer.step`` and the device log -- replayed as ONE
+    captured hipGraph, the product form of what ``bench.py --mode train`` measures.
+
+    ``step(batch)`` -> (mean loss, 0-dim device tensor; stats dict of per-image device vectors).  The returned tensors (and the
+    optimizer's ``last_norm``) are static: the next step overwrites them.  The first call with a new signature (``step_signature``)
+    is a real eager step on this object's side stream and does every lazy initialisation; the second stages the batch into static
+    buffers, captures and replays; later calls stage, refresh the optimizer's device hyper-parameter table and replay.  Every call is
+    exactly one optimizer step of the all-eager loop, bit for bit.  The graphs are made for ONE batch size, the largest seen so far
+    (``batch_size``): a smaller batch -- a ragged last one -- and a signature beyond ``max_graphs`` run the eager step on the same
+    stream and objects; a larger one takes over and drops what was made for the smaller.
+
+    Construction changes the optimizer it is given, because the captured step needs both: ``optimizer.hyper_on_device`` becomes True
+    (``step()`` launches the device-table kernel from then on, inside and outside this object) and a missing ``flat_grad`` is pointed
+    at the model's flat gradient buffer.  ``release()`` drops the graphs and gives the optimizer its two attributes back.
+
+    After every replay the parameters' version counters are advanced, as the Python of ``FusedClipSGD.step`` that the replay skipped
+    would have: the packed-weight caches key on them, and an eval forward / a ``Detector`` on the same parameters re-packs instead of
+    computing with stale weights.  ``p.grad`` stays what the captured backward left: views of the graph pool's flat buffer, holding
+    the latest step's unclipped gradients.  One process only: a process group with more than one rank is refused."""
+
+    def __init__(self, model, optimizer, cfg=None, max_graphs=4):
+        if not isinstance(optimizer, FusedClipSGD):
+            raise ValueError(f'GraphedStep: the optimizer must be a FusedClipSGD (its step is capturable and reads its hyper-parameters '
+                             f'from device memory), got {type(optimizer).__name__}')
+        d = _dist()
+        if d is not None and d.get_world_size() > 1:
+            raise ValueError(f'GraphedStep: a process group with {d.get_world_size()} ranks -- the captured gradient exchange is not '
+                             'supported, train multi-GPU with graph_step off')
+        if not hasattr(model, 'forward_mean'):
+            raise ValueError(f'GraphedStep: the model must have forward_mean (SqueezeDetWithLoss), {type(model).__name__} has none')
+        self.model, self.optimizer, self.cfg = model, optimizer, cfg
+        self.base = find_base(model)
+        # the loss weights are launch arguments of the captured loss kernels: they are read where backward.py reads them, from the Loss
+        from .model import Loss
+        self._loss = next((m for m in model.modules() if isinstance(m, Loss)), None)
+        if self._loss is None:
+            raise ValueError(f'GraphedStep: no model.Loss module inside {type(model).__name__}: the loss weights a captured step holds '
+                             'cannot be watched for changes')
+        self._optimizer_was = (optimizer.hyper_on_device, optimizer.flat_grad)
+        if optimizer.flat_grad is None:
+            base = self.base
+            optimizer.flat_grad = lambda: base.last_grad_flat
+        optimizer.hyper_on_device = True
+        self.device = optimizer.params[0].device
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.pool = torch.cuda.graph_pool_handle()
+        self.max_graphs = int(max_graphs)
+        self.batch_size = None                   # the batch size the graphs are made for: the largest seen so far
+        self.captures = 0
+        self.replays = 0
+        self.eager_steps = 0
+        self._graphs = {}                        # signature -> (CUDAGraph, outputs, gradients, kept-alive operands)
+        self._seen = set()                       # signatures (capacity left out) that had their eager step
+        self._bufs = {}                          # (B, H, W, form) -> static batch
+        self._cap = {}                           # (B, H, W, form) -> sparse capacity
+        self._live = None                        # the signature whose gradients p.grad points at
+        self._one = torch.ones((), device=self.device)
+        # the device log in one buffer (one copy reads it): sums double[5] | ring float[LOG_RING][4] | cursor
+        self._log = torch.zeros(40 + 16 * LOG_RING + 8, device=self.device, dtype=torch.uint8)
+        self._log_sums, self._log_ring, self._log_cursor = self._log_views(self._log)
+
+    @staticmethod
+    def _log_views(buf):
+        return (buf[:40].view(torch.float64), buf[40:40 + 16 * LOG_RING].view(torch.float32).view(LOG_RING, 4),
+                buf[40 + 16 * LOG_RING:40 + 16 * LOG_RING + 4].view(torch.int32))
+
+    # ---- the log ----
+    def reset_log(self):
+        """Zero the sums (the start of an epoch); the ring and its cursor go on."""
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self._log_sums.zero_()
+        cur.wait_stream(self.stream)
+
+    def read_log(self):
+        """One copy and one host sync: -> (sums: {key: float64 sum of the per-image values since ``reset_log``} + 'images';
+        latest: {key: batch mean of the latest step} or None before the first step; steps pushed so far)."""
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(self.stream)
+        sums, ring, cursor = self._log_views(self._log.cpu())
+        n = int(cursor[0]) & 0xffffffff
+        out = {k: float(sums[i]) for i, k in enumerate(LOG_ROWS)}
+        out['images'] = float(sums[4])
+        latest = None if n == 0 else {k: float(ring[(n - 1) % LOG_RING, i]) for i, k in enumerate(LOG_ROWS)}
+        return out, latest, n
+
+    def _log_push(self, stats):
+        from . import _native as nat
+        rows = [stats[k] for k in LOG_ROWS]
+        B = rows[0].shape[0]
+        p0 = rows[0].data_ptr()
+        if any(r.dtype != torch.float32 or r.dim() != 1 or r.shape[0] != B or not r.is_contiguous() or r.data_ptr() != p0 + 4 * B * i
+               for i, r in enumerate(rows)):
+            raise RuntimeError('GraphedStep: the loss statistics are not the rows of one fp32 [4,B] tensor (class, score, bbox, total)')
+        nat.check(nat.lib().sqd_train_log_push(nat.c_p(p0), B, nat.ptr(self._log_sums), nat.ptr(self._log_ring), nat.ptr(self._log_cursor),
+                                               LOG_RING, nat.stream_handle(self.device)), 'sqd_train_log_push')
+
+    # ---- the step ----
+    def _sequence(self, batch):
+        """The step itself, on the current stream: eager, or recorded when that stream is capturing."""
+        mean, stats = self.model.forward_mean(batch)
+        self.optimizer.zero_grad()
+        mean.backward(self._one)
+        self.optimizer.step()
+        self._log_push(stats)
+        # detached: a loss kept with its autograd graph would keep this step's nodes alive into the next step
+        return mean.detach(), {k: v.detach() for k, v in stats.items()}
+
+    def signature(self, batch, cap=None):
+        B, _, H, W = batch['image'].shape
+        form = gt_form(batch)
+        loss = self._loss
+        weights = (loss.class_loss_weight, loss.positive_score_loss_weight, loss.negative_score_loss_weight, loss.bbox_loss_weight)
+        if cap is None:
+            cap = self._cap.get((B, H, W, form), 0)
+        return step_signature((B, H, W), form, cap, self.model.training,
+                              [n for n, p in self.model.named_parameters() if p.requires_grad], self.optimizer.max_norm > 0, weights)
+
+    def _stage(self, key, batch):
+        """Copy the batch into the static buffers of ``key`` (device to device, on the current stream) -> (the static batch, whether the
+        sparse capacity grew)."""
+        form = key[3]
+        image = batch['image']
+        bufs = self._bufs.get(key)
+        grew = False
+        if bufs is None:
+            bufs = self._bufs[key] = {'image': torch.empty_like(image, memory_format=torch.contiguous_format)}
+            if form == 'dense':
+                bufs['gt'] = torch.empty_like(batch['gt'], memory_format=torch.contiguous_format)
+        bufs['image'].copy_(image)
+        if form == 'dense':
+            bufs['gt'].copy_(batch['gt'])
+            return bufs, grew
+        from .ops import SparseGT
+        sgt = batch['gt_sparse']
+        total = int(sgt.anchor_idx.shape[0])
+        cap = sparse_capacity(total, self._cap.get(key, 0))
+        if cap != self._cap.get(key, 0):
+            grew = key in self._cap
+            self._cap[key] = cap
+            dev = image.device
+            bufs['gt_sparse'] = SparseGT(torch.zeros(cap, device=dev, dtype=torch.int32), torch.zeros(cap, 4, device=dev),
+                                         torch.zeros(cap, 4, device=dev), torch.zeros(cap, device=dev, dtype=torch.int32),
+                                         torch.zeros(image.shape[0] + 1, device=dev, dtype=torch.int32))
+        st = bufs['gt_sparse']
+        # offsets and the first `total` entries: the launches bound every image's list by offsets, entries past offsets[B] are never read
+        st.offsets.copy_(sgt.offsets)
+        if total:
+            st.anchor_idx[:total].copy_(sgt.anchor_idx)
+            st.boxes[:total].copy_(sgt.boxes)
+            st.deltas[:total].copy_(sgt.deltas)
+            st.class_ids[:total].copy_(sgt.class_ids)
+        if form == 'masked':
+            if 'gt_ignore' not in bufs:
+                bufs['gt_ignore'] = torch.empty_like(batch['gt_ignore'], memory_format=torch.contiguous_format)
+            bufs['gt_ignore'].copy_(batch['gt_ignore'])
+        return bufs, grew
+
+    def _capture(self, sbatch):
+        import gc
+        from . import timing
+        params = self.optimizer.params
+        torch.cuda.synchronize(self.device)
+        # The captured forward must hold the re-pack launches of every packed weight copy, whatever ran since the last optimizer step
+        # (an eval forward brings the caches up to date): make every copy stale.  One eager refresh first, so that the descriptor tables
+        # of those launches exist -- a table built during the capture would be a host-to-device copy inside it.
+        torch.autograd.graph.increment_version(params)
+        self.base.refresh_plans()
+        torch.autograd.graph.increment_version(params)
+        self.optimizer.refresh_hyper()
+        timer = timing._timer
+        timing.set_timer(None)                   # (event brackets do not belong into a captured step)
+        gc_was_on = gc.isenabled()
+        g = torch.cuda.CUDAGraph()
+        try:
+            gc.collect()
+            gc.disable()                         # (a collection inside the capture would run GPU finalisers between two captured launches)
+            # thread_local: loader threads touch the runtime while this thread captures
+            with torch.cuda.graph(g, stream=self.stream, pool=self.pool, capture_error_mode='thread_local'):
+                out = self._sequence(sbatch)
+        except Exception as e:
+            raise RuntimeError(f'GraphedStep: capturing the training step failed ({type(e).__name__}: {e})') from e
+        finally:
+            timing.set_timer(timer)
+            if gc_was_on:
+                gc.enable()
+        self.captures += 1
+        grads = [p.grad for p in params]
+        # what the graph reads and writes outside its pool stays alive with it (caches that are bounded would drop them otherwise)
+        keep = (list(self.base.plan_cache._tables.values()), list(self.base._wgrad_batches.values()), self.base.last_grad_flat)
+        return g, out, grads, keep
+
+    def _drop_graphs(self):
+        """Forget every graph and static buffer (nothing may still be replaying them)."""
+        torch.cuda.synchronize(self.device)
+        self._graphs.clear(); self._seen.clear(); self._bufs.clear(); self._cap.clear()
+        self._live = None
+        self.pool = torch.cuda.graph_pool_handle()
+
+    def release(self):
+        """Drop the graphs and give the optimizer back what construction changed (``hyper_on_device``, ``flat_grad``)."""
+        self._drop_graphs()
+        self.optimizer.hyper_on_device, self.optimizer.flat_grad = self._optimizer_was
+
+    def _eager(self, batch):
+        self.eager_steps += 1
+        self._live = None
+        return self._sequence(batch)
+
+    def _run(self, batch):
+        image = batch['image']
+        B, _, H, W = image.shape
+        if self.batch_size is None or B > self.batch_size:
+            if self.batch_size is not None:
+                self._drop_graphs()              # (the first batches were the odd ones: nothing made for them is used again)
+            self.batch_size = B
+        if B != self.batch_size:
+            return self._eager(batch)            # a ragged last batch: no buffers, no graph
+        form = gt_form(batch)
+        key = (B, H, W, form)
+        sbatch, grew = self._stage(key, batch)
+        if grew:
+            # the capacity doubled: the graphs of this shape hold the old buffers
+            torch.cuda.synchronize(self.device)
+            for s in [s for s in self._graphs if s[:4] == key]:
+                del self._graphs[s]
+            # later captures go to a pool of their own: the old one may have lost its last graph while p.grad still holds blocks of it
+            self.pool = torch.cuda.graph_pool_handle()
+        sig = self.signature(batch)
+        seen_key = sig[:4] + sig[5:]
+        entry = self._graphs.get(sig)
+        if entry is None:
+            if seen_key not in self._seen:
+                self._seen.add(seen_key)
+                return self._eager(sbatch)       # the first step of this signature: real, and every lazy initialisation
+            if len(self._graphs) >= self.max_graphs:
+                return self._eager(sbatch)
+            entry = self._graphs[sig] = self._capture(sbatch)
+        else:
+            self.optimizer.refresh_hyper()
+        g, out, grads, _keep = entry
+        g.replay()
+        self.replays += 1
+        params = self.optimizer.params
+        torch.autograd.graph.increment_version(params)        # the Python a replay skipped (FusedClipSGD.step)
+        if self._live != sig:
+            for p, gr in zip(params, grads):
+                p.grad = gr
+            self.base.last_grad_flat = _keep[2]
+            self._live = sig
+        return out
+
+    def step(self, batch):
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)             # the batch was produced on the caller's stream
+        with torch.cuda.stream(self.stream):
+            out = self._run(batch)
+        cur.wait_stream(self.stream)             # the caller reads the outputs (and frees the batch) on its own stream
+        return out
 
 
 def make_train_step(cfg, state_dict, image, rank, world, dist, gt_seed=1, force_exchange=False, fused_optimizer=True, parts=None):
