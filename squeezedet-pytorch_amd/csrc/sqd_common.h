@@ -79,7 +79,9 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 // element -- the last Fire's expand1x1 and expand3x3 launches, whatever their tiling -- or a stand-alone mask kernel evaluates
 // the same bits, and the host can reproduce them (ops.dropout_mask_reference).  One 64-bit hash per group of four consecutive
 // elements (an f32x4 of the NHWC tensor), four 16-bit fields, keep where field < keep16 = round((1 - p) * 65536); kept values
-// are scaled by 1 / (1 - p).  state = {seed, step} in device memory: `step` is advanced on the device once per forward (the
+// are scaled by 1 / (1 - p).  The hash is keyed by (k0, k1) = sqd_drop_key(seed, step): each of the two words mixes all 128 bits
+// of (seed, step), so all four fields change with any bit of either -- seeds that differ only above bit 31 (torch.seed() returns
+// 64-bit seeds) or steps 2^32 apart draw independent masks (tests/test_dropout_host.py).  state = {seed, step} in device memory: `step` is advanced on the device once per forward (the
 // captured training step draws a fresh mask every replay).  The backward needs no mask: an element of the dropped ReLU output
 // is > 0 exactly where it was kept AND the ReLU was active, so the ConvDet data gradient masks by it and scales by a constant.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -93,8 +95,10 @@ __host__ __device__ __forceinline__ unsigned sqd_mix32(unsigned x) {
 __host__ __device__ __forceinline__ SqdDrop sqd_drop_key(unsigned long long seed, unsigned long long step, int keep16, float scale) {
   SqdDrop d;
   const unsigned s0 = (unsigned)seed, s1 = (unsigned)(seed >> 32), t0 = (unsigned)step, t1 = (unsigned)(step >> 32);
-  d.k0 = sqd_mix32(s0 ^ sqd_mix32(t0 + 0x9e3779b9u));
-  d.k1 = sqd_mix32(s1 ^ sqd_mix32(t0 ^ 0x85ebca6bu) ^ (t1 * 0xc2b2ae35u));
+  // two absorption chains over the four words, in opposite orders and from different constants: k0 and k1 are each a 32-bit hash
+  // of all 128 bits, and a pair (seed, step) that collides in one of them is an ordinary pair for the other
+  d.k0 = sqd_mix32(s0 ^ sqd_mix32(t0 ^ sqd_mix32(s1 ^ sqd_mix32(t1 + 0x9e3779b9u))));
+  d.k1 = sqd_mix32(t1 ^ sqd_mix32(s1 ^ sqd_mix32(t0 ^ sqd_mix32(s0 + 0x85ebca6bu))));
   d.keep16 = (unsigned)keep16; d.scale = scale;
   return d;
 }

@@ -43,6 +43,9 @@ class DropState:
         self.p = float(p)
         self.keep16 = int(round((1.0 - self.p) * 65536))
         self.scale = 1.0 / (1.0 - self.p)
+        if self.keep16 == 0 or (self.p > 0.0 and self.keep16 == 65536):
+            # the 16-bit threshold cannot express the rate: nothing would ever be kept (at a finite scale), or everything kept but scaled
+            raise ValueError(f'dropout probability {p} is not representable: keep threshold round((1 - p) * 65536) = {self.keep16}')
         self.state = torch.tensor([int(seed) & 0x7fffffffffffffff, int(step)], dtype=torch.int64, device=device)
 
     def get(self):
@@ -88,8 +91,8 @@ def dropout_mask_reference(seed, step, keep16, scale, n):
     u = lambda v: np.array([v & 0xffffffff], dtype=np.uint32)
     with np.errstate(over='ignore'):
         s0, s1, t0, t1 = u(seed), u(seed >> 32), u(step), u(step >> 32)
-        k0 = mix(s0 ^ mix(t0 + np.uint32(0x9e3779b9)))
-        k1 = mix(s1 ^ mix(t0 ^ np.uint32(0x85ebca6b)) ^ (t1 * np.uint32(0xc2b2ae35)))
+        k0 = mix(s0 ^ mix(t0 ^ mix(s1 ^ mix(t1 + np.uint32(0x9e3779b9)))))      # sqd_drop_key: both words mix all 128 bits
+        k1 = mix(t1 ^ mix(s1 ^ mix(t0 ^ mix(s0 + np.uint32(0x85ebca6b)))))
         e4 = np.arange((n + 3) // 4, dtype=np.uint64)
         lo = (e4 & np.uint64(0xffffffff)).astype(np.uint32) ^ ((e4 >> np.uint64(32)).astype(np.uint32) * np.uint32(0x9e3779b9))
         h1 = mix(lo ^ k0)
@@ -193,7 +196,7 @@ def conv_wino(x, x_coff, plan, y, y_coff, relu=False, accumulate=False, ymask=No
     """y[..., y_coff:y_coff+N] (=|+=) conv3x3(x[..., x_coff:x_coff+C]) (+bias) (* ymul) (* yscale) (zero where ymask <= 0) (ReLU),
     Winograd F(2x2,3x3) kernel.  ``ymask`` / ``ymul`` are read through y's own channel window (same shape as y).  ``yscale``
     (a constant factor, e.g. the dropout scale), ``drop`` (a DropState: counter-based dropout of the output) and ``drop_advance`` (a
-    DropState whose step this launch advances) need the balanced kernel (``plan.cfg_id`` = tiles.WINO_SK_CFG)."""
+    DropState whose step this launch advances; never the one ``drop`` names) need the balanced kernel (``plan.cfg_id`` = tiles.WINO_SK_CFG)."""
     _check_nhwc(x, 'x'); _check_nhwc(y, 'y')
     B, H, W, xp = x.shape
     if tuple(y.shape[:3]) != (B, H, W):
@@ -215,6 +218,9 @@ def conv_wino(x, x_coff, plan, y, y_coff, relu=False, accumulate=False, ymask=No
             _check_nhwc(t, nm)
             if tuple(t.shape) != tuple(y.shape):
                 raise ValueError(f'conv_wino: {nm} must have the shape of y')
+    if drop is not None and drop_advance is not None and drop.state.data_ptr() == drop_advance.state.data_ptr():
+        # the advance is one lane's unordered write: the other workgroups of the same launch would key their masks with either step
+        raise ValueError('conv_wino: a launch cannot advance the dropout state it draws its own mask from')
     if plan.cfg_id % 1000 == tiles.WINO_SK_CFG:
         sk = wino_sk_schedule(B * -(-H // 4) * -(-W // 16), plan.N, plan.C, x.device)
         sk_ws, sk_cnt = sk.workspace()               # (per launch stream: concurrent lanes must not share slabs / tickets)

@@ -164,6 +164,39 @@ def next_stage(r, w, bias, relu_out=True, emu=None):
     return Ref(ref64, M, b32)
 
 
+# ---- ConvDet's data gradient behind a live dropout, end to end ----
+
+DROP_EXCLUDE_CAP = 0.005      # at most this fraction of the tensor may sit on the ReLU's edge (see ``dropped_dgrad``)
+
+
+def dropped_dgrad(dpred, w_convdet, mask, pre, scale):
+    """The gradient that leaves ConvDet towards the last Fire when the dropout in front of ConvDet is live, from first principles:
+    (plain float64 data gradient of ``dpred``) * ``mask`` (the scaled keep mask, as the stand-alone kernel draws it) * relu'(pre),
+    ``pre`` = Ref of the last Fire's PRE-activation expand output, recomputed in float64 -- not the dropped tensor the kernels use in
+    its place.  -> (Ref with M = the plain data gradient's magnitude times ``scale`` = 1 / (1 - p), b32 = the plain chain times mask
+    times relu'; exclude: the elements whose float64 pre-activation is within BAR_L * its own magnitude of zero, where a correct fp32
+    forward may land on either side of the ReLU)."""
+    r = conv(dpred, dgrad_weight(w_convdet))
+    act = pre.ref64 > 0
+    m64 = mask.to(F64)
+    ref64 = torch.where(act, r.ref64 * m64, 0.0)
+    b32 = torch.where(act, r.b32 * mask.to(F32), 0.0)
+    exclude = pre.ref64.abs() <= BAR_L * pre.M
+    return Ref(ref64, r.M * float(scale), b32), exclude
+
+
+def bar_l_excluding(got, r, exclude):
+    """Bar L of ``got`` against ``r`` on the elements outside ``exclude`` -> dict(l_ratio, l_ok, excluded, cap_ok): ``cap_ok`` = no more
+    than DROP_EXCLUDE_CAP of the tensor is excluded."""
+    err = (got.double() - r.ref64).abs()
+    keep = ~exclude
+    ok = bool((err[keep] <= BAR_L * r.M[keep]).all())
+    pos = keep & (r.M > 0)
+    ratio = float((err[pos] / r.M[pos]).max()) if bool(pos.any()) else 0.0
+    n = int(exclude.sum())
+    return dict(l_ratio=ratio, l_ok=ok, excluded=n, cap_ok=n <= DROP_EXCLUDE_CAP * exclude.numel())
+
+
 # ---- weight gradient ----
 
 def wgrad(dy, x, taps, emu=None):

@@ -68,6 +68,127 @@ def test_fused_epilogues_equal_the_mask(C, E1, E3, B, H, W):
         ops.conv_wino(x, 0, ops.WinoPlan(w3, b3, 2), dropped, E1, relu=True, drop=d)
 
 
+def _nan_like(shape):
+    return torch.full(shape, float('nan'), device='cuda')
+
+
+def _window_is_the_masked_plain(dropped, plain, mask, coff, N, what):
+    """``dropped`` = ``plain`` * ``mask`` bit for bit inside the channel window [coff, coff + N) -- the mask indexed by the BUFFER's
+    flat element --, NaN (the pre-fill) everywhere outside it, no NaN inside."""
+    win = slice(coff, coff + N)
+    assert bool(torch.isnan(dropped[..., :coff]).all()) and bool(torch.isnan(dropped[..., coff + N:]).all()), f'{what}: wrote outside the window'
+    assert not bool(torch.isnan(dropped[..., win]).any()), f'{what}: elements of the window were not written'
+    assert not bool(torch.isnan(plain[..., win]).any()), what
+    assert torch.equal(dropped[..., win], plain[..., win] * mask[..., win]), f'{what}: fused epilogue != plain * mask'
+
+
+@pytest.mark.parametrize('p', [0.5, 0.2, 0.75])
+def test_every_weight_stationary_configuration_drops_into_a_window(p):
+    """Every 1x1 configuration ``sqd_conv_drop_fwd`` accepts (each weight-stationary id the library compiled, not only
+    ``conv_drop_cfg``'s pick), on a ragged shape (a partial 16-pixel tile, a partial out-channel slice in every configuration), into
+    the window at channel 8 of a buffer N + 24 wide: the epilogue indexes the mask by (pixel * y_pitch + y_coff + channel).  The
+    other 1-tap ids are refused before any launch and leave the buffer alone."""
+    from test_fp64_offbench_gpu import TILING_SHAPES
+    ops = _ops()
+    tab = ops.cfg_table()
+    one_tap = sorted(cid for cid, (taps, _kc, _px, _bn) in tab.items() if taps == 1)
+    C, N, B, H, W = TILING_SHAPES[1]
+    ws = [cid for cid in one_tap if ops._CFG_DMA[cid] >= 3 and ops.conv_cfg_ok(cid, C)]
+    if (B * H * W) % 16 == 0 or any(N % tab[cid][3] == 0 for cid in ws):
+        C, N, B, H, W = 48, 80, 3, 5, 17
+        ws = [cid for cid in one_tap if ops._CFG_DMA[cid] >= 3 and ops.conv_cfg_ok(cid, C)]
+    assert (B * H * W) % 16 and all(N % tab[cid][3] for cid in ws) and len(ws) >= 2, (ws, N)
+    coff, wide = 8, N + 24
+    x = torch.relu(_rand(B, H, W, C, seed=1)).cuda()
+    w = (_rand(N, C, 1, 1, seed=2) * (2.0 / C) ** 0.5).cuda(); b = (_rand(N, seed=3) * 0.1).cuda()
+    d = ops.DropState(p, 777, 'cuda', step=11)
+    mask = ops.dropout_mask(d, (B, H, W, wide))
+    ref = ops.dropout_mask_reference(777, 11, d.keep16, d.scale, mask.numel())
+    assert np.array_equal(mask.cpu().numpy().reshape(-1), ref)
+    for cid in ws:
+        plan = ops.ConvPlan(w, b, cid)
+        plain, dropped = _nan_like((B, H, W, wide)), _nan_like((B, H, W, wide))
+        ops.conv(x, 0, plan, plain, coff, relu=True)
+        ops.conv(x, 0, plan, dropped, coff, relu=True, drop=d)
+        _window_is_the_masked_plain(dropped, plain, mask, coff, N, ops.cfg_kernel_name(cid))
+        kept = float((dropped[..., coff:coff + N] > 0).sum()) / max(1.0, float((plain[..., coff:coff + N] > 0).sum()))
+        assert abs(kept - (1.0 - p)) < 0.05, (cid, kept)            # (not all-keep, not all-drop: about 8000 active elements)
+    refused = [cid for cid in one_tap if ops._CFG_DMA[cid] < 3]
+    assert refused
+    for cid in refused:
+        plan = ops.ConvPlan(w, b, cid)
+        buf = _nan_like((B, H, W, wide))
+        with pytest.raises(RuntimeError):
+            ops.conv(x, 0, plan, buf, coff, relu=True, drop=d)
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(buf).all()), f'cfg {cid}: a refused call wrote'
+    assert d.get() == (777, 11)
+
+
+@pytest.mark.parametrize('p', [0.5, 0.2])
+@pytest.mark.parametrize('grid', [0, 2, 7, 61])
+@pytest.mark.parametrize('C,N,B,H,W', [(16, 80, 3, 5, 17), (48, 192, 2, 9, 33), (8, 16, 1, 3, 3)])
+def test_balanced_winograd_epilogue_drops_under_forced_grids(C, N, B, H, W, grid, p, monkeypatch):
+    """The dropout of the balanced Winograd kernel lives in its FULL epilogue, which also runs from the path that joins cut units: with
+    the grid forced (units in one piece, cut in 2..3, cut in many parts) the launch with ``drop`` equals the same launch without it
+    times the mask, in a window at channel 4 of a buffer N + 8 wide; the arrival counters are back at zero; a second launch gives
+    the same bits."""
+    ops = _ops()
+    if grid:
+        monkeypatch.setenv('SQD_SK_GRID', str(grid))
+    coff, wide = 4, N + 8
+    x = torch.relu(_rand(B, H, W, C, seed=1)).cuda()
+    w = (_rand(N, C, 3, 3, seed=4) * (2.0 / (9 * C)) ** 0.5).cuda(); b = (_rand(N, seed=5) * 0.1).cuda()
+    plan = ops.WinoPlan(w, b, ops.WINO_SK_CFG)
+    d = ops.DropState(p, 777, 'cuda', step=11)
+    plain, dropped, again = (_nan_like((B, H, W, wide)) for _ in range(3))
+    ops.conv_wino(x, 0, plan, plain, coff, relu=True)
+    ops.conv_wino(x, 0, plan, dropped, coff, relu=True, drop=d)
+    from test_conv_wino_sk_gpu import _counters_clean
+    ok, sk = _counters_clean(ops, B * -(-H // 4) * -(-W // 16), N, C)
+    assert ok, 'arrival counters must return to zero'
+    mask = ops.dropout_mask(d, (B, H, W, wide))
+    _window_is_the_masked_plain(dropped, plain, mask, coff, N, f'grid {sk.G}, {sk.nslabs} slabs')
+    ops.conv_wino(x, 0, plan, again, coff, relu=True, drop=d)
+    assert torch.equal(again[..., coff:coff + N], dropped[..., coff:coff + N]) and d.get() == (777, 11)
+    assert _counters_clean(ops, B * -(-H // 4) * -(-W // 16), N, C)[0]
+
+
+def test_drop_advance_moves_the_step_after_the_mask_was_drawn():
+    """``drop_advance`` (ConvDet's forward can carry it): the launch leaves (seed, step + 1) and its own output untouched by it; a
+    launch without it leaves the state alone; the mask an earlier launch applied is the one of the step before the advance.  One
+    launch cannot advance the state it keys its own mask with (one lane's unordered write): refused on the host."""
+    ops = _ops()
+    C, N, B, H, W = 16, 80, 3, 5, 17
+    coff, wide = 4, N + 8
+    x = torch.relu(_rand(B, H, W, C, seed=1)).cuda()
+    w = (_rand(N, C, 3, 3, seed=4) * (2.0 / (9 * C)) ** 0.5).cuda(); b = (_rand(N, seed=5) * 0.1).cuda()
+    plan = ops.WinoPlan(w, b, ops.WINO_SK_CFG)
+    d = ops.DropState(0.5, 777, 'cuda', step=11)
+    other = ops.DropState(0.5, 4242, 'cuda', step=5)
+    before = ops.dropout_mask(d, (B, H, W, wide))
+    plain, dropped, advancing, third = (_nan_like((B, H, W, wide)) for _ in range(4))
+    ops.conv_wino(x, 0, plan, plain, coff, relu=True)
+    ops.conv_wino(x, 0, plan, dropped, coff, relu=True, drop=d)
+    assert d.get() == (777, 11)
+    ops.conv_wino(x, 0, plan, advancing, coff, relu=True, drop_advance=d)
+    assert d.get() == (777, 12)
+    assert torch.equal(advancing[..., coff:coff + N], plain[..., coff:coff + N])
+    _window_is_the_masked_plain(dropped, plain, before, coff, N, 'mask of the step before the advance')
+    after = ops.dropout_mask(d, (B, H, W, wide))
+    assert not torch.equal(after, before)
+    assert np.array_equal(after.cpu().numpy().reshape(-1), ops.dropout_mask_reference(777, 12, d.keep16, d.scale, after.numel()))
+    # another stream's mask, this stream's advance, in one launch
+    ops.conv_wino(x, 0, plan, third, coff, relu=True, drop=other, drop_advance=d)
+    assert d.get() == (777, 13) and other.get() == (4242, 5)
+    _window_is_the_masked_plain(third, plain, ops.dropout_mask(other, (B, H, W, wide)), coff, N, 'mask of another stream')
+    buf = _nan_like((B, H, W, wide))
+    with pytest.raises(ValueError):
+        ops.conv_wino(x, 0, plan, buf, coff, relu=True, drop=d, drop_advance=d)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(buf).all()) and d.get() == (777, 13)
+
+
 def _model(size, p=0.5, arch='squeezedet'):
     from squeezedet_pytorch_amd.model import SqueezeDetWithLoss
     cfg = sqd.make_cfg(arch=arch, input_size=size, dropout_prob=p)

@@ -10,7 +10,9 @@ and input sizes has a float64 case in one of the lists.
 The sweep along the head axis (tests/test_fp64_widths_gpu.py: class counts, anchors per cell, sparse ground truth) likewise: ``WIDTHS``
 equals the planners' ConvDet-side rows at its points, the backbone rows of those points are the ones the off-benchmark sweep checks,
 every kernel name and every ConvDet signature the planners produce over 1..20 anchors x 1..256 classes x dense / sparse occurs at a
-point, and a numpy restatement of ``wgrad_reduce_rows`` with a wrong row stride, a wrong bias offset or a dropped slab fails bar L."""
+point, and a numpy restatement of ``wgrad_reduce_rows`` with a wrong row stride, a wrong bias offset or a dropped slab fails bar L.
+The sweep with a live dropout (tests/test_fp64_dropout_gpu.py): its cases equal the planners' rows from the last Fire's expand launches
+through ConvDet's data gradient, for the fused and the stand-alone form; ``dropout_mask`` itself is bit-exact elsewhere (``ALLOWED``)."""
 import contextlib
 import functools
 import os
@@ -27,10 +29,12 @@ import test_fp64_loss_gpu as LG  # noqa: E402
 import test_fp64_offbench_gpu as OB  # noqa: E402
 import test_fp64_optim_gpu as OG  # noqa: E402
 import test_fp64_widths_gpu as WD  # noqa: E402
+import test_fp64_dropout_gpu as DR  # noqa: E402
 
 # launches outside the float64 sweep, each with the test that covers it
 ALLOWED = {
     'detect': 'tests/test_detect_sweep_gpu.py (exact against oracle.filter_detections)',
+    'dropout_mask': 'bit-exact against `ops.dropout_mask_reference`, tests/test_dropout_gpu.py',
 }
 
 
@@ -213,6 +217,35 @@ def test_width_points_run_a_checked_backbone():
             if train:
                 assert tail == want, pt
             assert all(e in checked or (e[0], None) in checked for e in rows[:i0] + tail), pt
+
+
+# ---- the step with a live dropout (tests/test_fp64_dropout_gpu.py) ----
+
+def test_every_dropout_plan_entry_has_a_case():
+    """``DR.CASES`` equals the planners' rows from the last Fire's expand launches through ConvDet's data gradient at its points, for
+    both values of ``fused_dropout`` (the injected form runs the stand-alone form's launches without the ``dropout_mask`` row, which has
+    its own bit-exact test); the rest of those plans -- the backbone, passed through unchecked -- is, name and tag, what the
+    off-benchmark sweep checks at batch 3, 70x100."""
+    assert DR.POINTS == [('squeezedet', 0.5), ('squeezedetplus', 0.5), ('squeezedet', 0.2)]
+    assert (DR.BATCH, DR.SIZE) == (3, (70, 100)) and DR.FORMS == ('fused', 'standalone', 'injected')
+    entries = []
+    for arch, p in DR.POINTS:
+        assert (arch, DR.BATCH, DR.SIZE) in OB.POINTS
+        checked = {c[3:] for c in OB.OFFBENCH if c[:3] == (arch, DR.BATCH, DR.SIZE)}
+        for form in DR.FORMS:
+            rows = DR.planned(arch, form)
+            i0, i1 = DR.dropout_side(rows, arch)
+            masks = [r for r in rows[:i0] if r[0] == 'dropout_mask']
+            assert len(masks) == (1 if form == 'standalone' else 0), (arch, form, masks)
+            entries += [(arch, p, form) + e for e in masks + rows[i0:i1]]
+            assert all(e in checked or e[0] in ALLOWED for e in rows[:i0] + rows[i1:]), (arch, form)
+    _same_as_plans(DR.CASES, entries, 'the live-dropout points', name_at=3)
+    known = set(L.FAMILIES) | set(L.LOSS_FAMILIES) | set(OB.NEW_FAMILIES)
+    assert all(L.family(c[3]) in known for c in DR.CASES)
+    # the fused form is the one the planners choose by default, and it needs no mask launch
+    from squeezedet_pytorch_amd import plan
+    for arch, _p in DR.POINTS:
+        assert DR.planned(arch, 'fused') == plan.training_launch_plan(arch, DR.BATCH, DR.SIZE)
 
 
 @contextlib.contextmanager

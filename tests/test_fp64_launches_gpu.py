@@ -9,7 +9,9 @@ with the benchmark's synthetic weights, images and targets (fixed seeds), and ev
 wrapper copies the launch's operands, runs the kernel, reads the (kernel, tag) its KernelTimer bracket recorded and compares every
 output with tests/fp64_ref.py evaluated on those same operands -- so each launch is checked on its own inputs, at the plan's batch and
 shape, on the kernel the plan names.  Weight gradients are checked after the slab reduction the step ships (``wgrad_reduce_batched``).
-Dropout runs at p = 0: the planned epilogue kernels launch with an all-keep mask (mask values are tested elsewhere).
+Dropout runs at p = 0 here: the planned epilogue kernels launch with an all-keep mask.  tests/test_fp64_dropout_gpu.py runs the harness
+with a live rate (``_run_step(dropout_prob=...)``, ``check_from='dropout'``): a launch with ``drop`` is then held to its reference times
+the step's mask, read through the stand-alone kernel before the launch.
 
 Two bars per output (fp64_ref.bars):
 * L: |got - ref64| <= 2^-18 * M for every element (exact where M = 0): no dropped, duplicated or misplaced term anywhere;
@@ -42,6 +44,8 @@ anchors_per_grid * (num_classes + 5) decides its launches; the entry points that
   dW / db to float64 on the true dpred[..., :N], restated at the launch's own S in the blocking of the kernel that wrote the slabs.
 ``check_from='convdet'`` passes the backbone's launches through unchecked (the launches are still asserted equal to the plan): for
 points whose backbone rows another sweep already checks, which tests/test_fp64_coverage.py asserts on the host.
+``check_from='dropout'`` does the same but also checks the last Fire's two expand launches, which carry the dropout; with a live rate
+ConvDet's data gradient gets a second, end-to-end reference (``_Harness._dgrad_end_to_end``).
 """
 import re
 
@@ -224,11 +228,15 @@ def k_of(kernel):
 class _Harness:
     """Wraps the ``ops`` entry points (and the slab reduction) for one step; collects per-(kernel, tag) output checks."""
 
-    def __init__(self, base, arch, batch, timer, teeth_for=None, check_from=None):
+    def __init__(self, base, arch, batch, timer, teeth_for=None, check_from=None, dropout_prob=0.0):
         self.base, self.arch, self.batch, self.timer = base, arch, batch, timer
         self.teeth_for = teeth_for     # the families whose first launch also runs the degraded emulations (None: every family)
-        assert check_from in (None, 'convdet')
-        self.check_from = check_from   # 'convdet': the backbone's launches run unchecked (``passes``); None: every launch is checked
+        assert check_from in (None, 'convdet', 'dropout')
+        # 'convdet': the backbone's launches run unchecked (``passes``); 'dropout': the same, but the last Fire's two expand launches
+        # (which carry the dropout) are checked as well; None: every launch is checked
+        self.check_from = check_from
+        self.dropout_prob = float(dropout_prob)     # 0: the planned epilogues with an all-keep mask; > 0: a live mask (``_mask_of``)
+        self.drop_ctx = {}             # live dropout: the last Fire's squeeze output and the whole mask, for ConvDet's data gradient
         self.rows = {}                 # (arch, batch, kernel, tag) -> [(output, bars dict)]
         self.teeth = {}                # family -> {emu: bars dict}
         self.pending = {}              # slab data_ptr -> (entry, dy, x, taps) until the slab reduction
@@ -257,10 +265,73 @@ class _Harness:
         if self.check_from is None:
             return False
         if name in ('conv', 'conv_wino'):
-            return not self._is_convdet(self.plan_map[id(args[2])][1])
+            _kind, mod, direction = self.plan_map[id(args[2])]
+            if self.check_from == 'dropout' and direction == 'fwd' and self._last_expand(mod) is not None:
+                return False
+            return not self._is_convdet(mod)
         if name == 'conv_wgrad':
             return not (args[6] == 9 and args[5] == self.base.convdet.in_channels)
         return name in _BACKBONE_NAMES
+
+    def _last_expand(self, mod):
+        """0 / 1 if ``mod`` is the expand1x1 / expand3x3 of the last Fire (the two launches in front of ConvDet), else None."""
+        fire = self.base.features[-1]
+        return 0 if mod is fire.expand1x1 else 1 if mod is fire.expand3x3 else None
+
+    def _mask_of(self, drop, y, y_coff, N):
+        """The scaled keep mask a launch with ``drop`` applies to y[..., y_coff:y_coff + N]: this step's mask of the whole buffer, read
+        through the stand-alone kernel BEFORE the launch (the step advances only behind ConvDet's forward), outside the timer.  At
+        p = 0 the state must be the all-keep one, and there is no mask to apply."""
+        if drop is None:
+            return None
+        if self.dropout_prob == 0.0:
+            assert drop.keep16 == 65536 and drop.scale == 1.0
+            return None
+        assert drop.keep16 < 65536 and drop.p == self.dropout_prob
+        from squeezedet_pytorch_amd import ops
+        ops.set_timer(None)
+        try:
+            full = ops.dropout_mask(drop, tuple(y.shape))
+        finally:
+            ops.set_timer(self.timer)
+        self.drop_ctx['mask'] = full
+        return full[..., y_coff:y_coff + N].clone()
+
+    @staticmethod
+    def _dropped(r, mask):
+        """A launch's Ref behind the fused dropout: ref64, M and the plain chain times the (non-negative) mask."""
+        if mask is None:
+            return r
+        return R.Ref(r.ref64 * mask.double(), r.M * mask.double(), r.b32 * mask)
+
+    def _note_last_fire(self, plan, x, x_coff, ymul):
+        """Live dropout: keep what the end-to-end reference of ConvDet's data gradient needs -- the last Fire's squeeze output (the
+        input of its expand launches) and, in the forms that multiply a mask tensor in, that tensor."""
+        kind, mod, direction = self.plan_map[id(plan)]
+        if self.dropout_prob > 0.0 and direction == 'fwd' and self._last_expand(mod) is not None:
+            self.drop_ctx['sq'] = x[..., x_coff:x_coff + plan.C].clone()
+            if ymul is not None:
+                self.drop_ctx['mask'] = ymul.clone()
+
+    def _dgrad_end_to_end(self, entry, plan, dpred, got, yscale, ymul):
+        """Live dropout, ConvDet's data gradient: beside the per-launch check (on the launch's own operands, the dropped tensor as
+        ReLU mask), the launch's output against fp64_ref.dropped_dgrad -- plain float64 gradient of the true dpred * the mask of the
+        stand-alone kernel * (pre-dropout expand output > 0), the latter recomputed in float64 from the last Fire's squeeze output and
+        the module's parameters.  Bar L with M / (1 - p); elements on the ReLU's edge excluded, at most 0.5 % of the tensor."""
+        kind, mod, direction = self.plan_map[id(plan)]
+        if self.dropout_prob == 0.0 or direction == 'fwd' or not self._is_convdet(mod):
+            return
+        scale = 1.0 / (1.0 - self.dropout_prob)
+        assert ymul is not None or yscale == scale, 'the launch does not carry the dropout scale: its output is not the final gradient'
+        cd, fire = self.base.convdet, self.base.features[-1]
+        assert mod is cd, 'a padded ConvDet: dpred is not the true one here'
+        sq, mask = self.drop_ctx['sq'], self.drop_ctx['mask']
+        pre = R.cat([R.conv(sq, fire.expand1x1.weight.detach(), fire.expand1x1.bias.detach()),
+                     R.conv(sq, fire.expand3x3.weight.detach(), fire.expand3x3.bias.detach())])
+        r, exclude = R.dropped_dgrad(dpred, cd.weight.detach(), mask, pre, scale)
+        b = R.bar_l_excluding(got, r, exclude)
+        b.update(l_ok=b['l_ok'] and b['cap_ok'], p_ok=True, p_block=0.0, p_tensor=0.0, k=0, end_to_end=True)
+        self.rows.setdefault(entry, []).append(('dA end to end', b))
 
     def _padded_params(self, pad):
         """The reference weights of a padded ConvDet: the module's own parameters, zero-extended here to the run width -- never the
@@ -314,8 +385,8 @@ class _Harness:
     # ---- wrapped entry points ----
     def conv(self, orig, x, x_coff, plan, y, y_coff, relu=False, accumulate=False, xmask=None, xmask_coff=0, ymask=None, ymask_coff=0,
              ymul=None, ymul_coff=0, drop=None):
-        if drop is not None:
-            assert drop.keep16 == 65536 and drop.scale == 1.0
+        dm = self._mask_of(drop, y, y_coff, plan.N)
+        self._note_last_fire(plan, x, x_coff, ymul)
         w, b = self._weights(plan)
         xw = x[..., x_coff:x_coff + plan.C]
         if xmask is not None:
@@ -329,13 +400,15 @@ class _Harness:
                    ymask_coff=ymask_coff, ymul=ymul, ymul_coff=ymul_coff, drop=drop)
         got = y[..., y_coff:y_coff + plan.N]
         kc = plan.kc                                      # b32 restates the direct kernels' single accumulator (fp64_ref._conv_chain)
-        self._check(self._entry(n0), [('y', got, lambda e: R.epilogue(R.conv(xw, w, b, emu=e, chain_kc=kc), prev, yl, 1.0, ym, relu), 'act')])
+        entry = self._entry(n0)
+        self._check(entry, [('y', got, lambda e: self._dropped(R.epilogue(R.conv(xw, w, b, emu=e, chain_kc=kc), prev, yl, 1.0, ym, relu), dm), 'act')])
+        self._dgrad_end_to_end(entry, plan, xw, got, 1.0, yl)
         return out
 
     def conv_wino(self, orig, x, x_coff, plan, y, y_coff, relu=False, accumulate=False, ymask=None, ymul=None, yscale=1.0, drop=None,
                   drop_advance=None):
-        if drop is not None:
-            assert drop.keep16 == 65536 and drop.scale == 1.0
+        dm = self._mask_of(drop, y, y_coff, plan.N)
+        self._note_last_fire(plan, x, x_coff, ymul)
         w, b = self._weights(plan)
         xw = x[..., x_coff:x_coff + plan.C].clone()
         prev = y[..., y_coff:y_coff + plan.N].clone() if accumulate else None
@@ -345,7 +418,9 @@ class _Harness:
         out = orig(x, x_coff, plan, y, y_coff, relu=relu, accumulate=accumulate, ymask=ymask, ymul=ymul, yscale=yscale, drop=drop,
                    drop_advance=drop_advance)
         got = y[..., y_coff:y_coff + plan.N]
-        self._check(self._entry(n0), [('y', got, lambda e: R.epilogue(R.conv(xw, w, b, emu=e), prev, yl, yscale, ym, relu), 'act')])
+        entry = self._entry(n0)
+        self._check(entry, [('y', got, lambda e: self._dropped(R.epilogue(R.conv(xw, w, b, emu=e), prev, yl, yscale, ym, relu), dm), 'act')])
+        self._dgrad_end_to_end(entry, plan, xw, got, yscale, yl)
         return out
 
     def fire_expand(self, orig, x, x_coff, fplan, y, y_coff):
@@ -678,16 +753,27 @@ def _head_kwargs(num_classes, seed, sparse_gt):
     return cfg_kw, sd_kw, gt_kw, plan_kw
 
 
-def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None, num_classes=3, anchors_seed=None, sparse_gt=False, check_from=None):
+DROP_FORMS = ('fused', 'standalone', 'injected')
+
+
+def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None, num_classes=3, anchors_seed=None, sparse_gt=False, check_from=None,
+              dropout_prob=0.0, drop_form='fused'):
     """One step at ``size`` (the benchmarked one by default; the same seeds as bench.py) with every GEMM-type launch checked.
     ``num_classes`` / ``anchors_seed`` (None: the KITTI nine) / ``sparse_gt``: the head axis, which decides ConvDet's width
     anchors_per_grid * (num_classes + 5) and the loss launches; ``check_from``: ``_Harness.passes``.
+    ``dropout_prob``: 0 (default) runs the planned dropout epilogues with an all-keep mask, as every sweep did; > 0 (training) builds
+    the module with that rate and leaves it live, in one of ``DROP_FORMS``: the fused epilogues, ``base.fused_dropout = False`` (the
+    stand-alone ``dropout_mask`` launch, a mask tensor multiplied in), or ``base._forced_drop_mask`` set to the stream's current mask.
+    The harness then holds (seed, step) of the stream before and after the checked step in ``drop_rng``.
     -> (harness, [(kernel, tag)] recorded)."""
     from squeezedet_pytorch_amd import ops, plans as plans_mod
     from squeezedet_pytorch_amd.detector import Detector
     from squeezedet_pytorch_amd.model import SqueezeDet, SqueezeDetWithLoss
     torch.manual_seed(0)
     cfg_kw, sd_kw, gt_kw, _ = _head_kwargs(num_classes, anchors_seed, sparse_gt)
+    assert drop_form in DROP_FORMS and (dropout_prob == 0.0 or mode == 'train')
+    if dropout_prob > 0.0:
+        cfg_kw['dropout_prob'] = float(dropout_prob)
     cfg = sqd.make_cfg(arch=arch, input_size=size, device='cuda', **cfg_kw)
     sd = synthetic.make_state_dict(arch, seed=1234, **sd_kw)
     x = synthetic.make_images(batch, size, seed=0).cuda()
@@ -696,7 +782,19 @@ def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None, num_clas
         m.load_state_dict(sd)
         m = m.cuda().train()
         base = m.base
-        base.dropout_prob = 0.0          # the planned dropout epilogues with an all-keep mask
+        if dropout_prob == 0.0:
+            base.dropout_prob = 0.0      # the planned dropout epilogues with an all-keep mask
+        else:
+            assert base.dropout_prob == dropout_prob and base.dropout is not None
+            dev = torch.device('cuda', torch.cuda.current_device())
+            if drop_form == 'standalone':
+                base.fused_dropout = False
+            elif drop_form == 'injected':        # the mask the stream would draw now, as the NCHW tensor the tests inject
+                from squeezedet_pytorch_amd import autograd, plan
+                last = plan.forward_schedule(arch, batch, size, autograd._flags(base), True, 'mask')[-1]
+                fh, fw = last.H, last.W
+                full = ops.dropout_mask(base.drop_state(dev), (batch, fh, fw, base.convdet.in_channels))
+                base._forced_drop_mask = full.permute(0, 3, 1, 2).contiguous()
         batch_d = {'image': x, 'gt': synthetic.make_gt(batch, cfg.anchors, size, seed=gt_seed, **gt_kw).cuda()}
         if sparse_gt:                    # the positives as a list: the sparse loss launches, no dense gt in the step
             batch_d = {'image': x, 'gt_sparse': ops.sparse_gt_from_dense(batch_d['gt'])}
@@ -716,7 +814,8 @@ def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None, num_clas
     step()                                # plans are packed here, outside the checked pass
     torch.cuda.synchronize()
     timer = ops.KernelTimer()
-    h = _Harness(base, arch, batch, timer, teeth_for, check_from)
+    h = _Harness(base, arch, batch, timer, teeth_for, check_from, dropout_prob)
+    rng_before = base.get_dropout_rng() if mode == 'train' else None
     saved = {n: getattr(ops, n) for n in _NAMES}
     red = plans_mod.WgradBatch.reduce
     for n in _NAMES:
@@ -732,6 +831,8 @@ def _run_step(arch, batch, mode, size=INPUT, gt_seed=1, teeth_for=None, num_clas
             setattr(ops, n, saved[n])
         plans_mod.WgradBatch.reduce = red
     assert not h.pending, 'weight-gradient slabs that no reduction consumed'
+    h.drop_rng = (rng_before, base.get_dropout_rng() if mode == 'train' else None)
+    h.drop_ctx.clear()
     return h, [(r[0], r[1]) for r in timer.records]
 
 
