@@ -629,6 +629,26 @@ int sqd_sgd_clip_step_chunked(const void* descs_dev, const void* chunks_dev, int
 int sqd_sgd_clip_step_chunked_dev(const void* descs_dev, const void* chunks_dev, int nchunks, const float* grad_base,
                                   const float* sumsq_parts, float* norm_out, const float* hyper, void* stream);
 int sqd_fill_f32x4(float* dst, float a, float b, float c, float d, void* stream);
+/* AdamW (torch.optim.AdamW, non-amsgrad, decoupled decay) behind clip_grad_norm_, and an exponential moving average of the weights
+ * (torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(d))), in the chunked one-launch form.  Per element:
+ *   g = grad * coef; p -= (lr * wd) * p; m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g; p -= (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps));
+ *   e = (first averaged step) ? p : e + (1 - d_t) (p - e),  d_t = warm-up ? min(d, (1 + n) / (10 + n)) : d.
+ * descs_dev: n records of 6 int64 {param ptr, grad (as for sqd_sgd_clip_step), exp_avg / momentum ptr, elements, exp_avg_sq ptr, EMA ptr};
+ * hyper: DEVICE float[8], AdamW {lr, beta1, beta2, eps, weight_decay, max_norm, ema_decay, ema_warmup}, SGD {lr, momentum, weight_decay,
+ * max_norm, ema_decay, ema_warmup, -, -}.  The step count t and the count n of averaged steps live on the device (counters: int[2]
+ * {t, n}): sqd_optim_begin, a one-thread launch in front of EVERY step, increments them (t when adam, n when ema) and writes derived
+ * (float[4]) {lr / bc1, 1 / sqrt(bc2), 1 - d_t, first averaged step ? 1 : 0}, evaluated in double; the step launches only read it, so a
+ * replayed hipGraph advances the counts without a host write.  The clip of sqd_adamw_clip_step_chunked: sumsq_parts (sqd_grad_sumsq's
+ * partials; norm_out receives the norm), else total_norm (a device float), else none; max_norm <= 0: a coefficient of 1.
+ * sqd_sgd_clip_step_chunked_ema: sqd_sgd_clip_step_chunked_dev (same arithmetic, same bits) with the EMA behind it.
+ * sqd_param_swap exchanges p and e of every tensor, exactly. */
+int sqd_optim_begin(const float* hyper, int* counters, float* derived, int adam, int ema, void* stream);
+int sqd_adamw_clip_step_chunked(const void* descs_dev, const void* chunks_dev, int nchunks, const float* grad_base,
+                                const float* sumsq_parts, const float* total_norm, float* norm_out, const float* hyper,
+                                const float* derived, int ema, void* stream);
+int sqd_sgd_clip_step_chunked_ema(const void* descs_dev, const void* chunks_dev, int nchunks, const float* grad_base,
+                                  const float* sumsq_parts, float* norm_out, const float* hyper, const float* derived, void* stream);
+int sqd_param_swap(const void* descs_dev, const void* chunks_dev, int nchunks, void* stream);
 /* The training log on the device (one small workgroup, no atomics): losses = float[4][B], the per-image values of a loss launch.  For
  * each component k the B values are added in index order in float64: sums[k] += that sum, ring[cursor % cap][k] = (float)(sum / B);
  * then sums[4] += B and cursor += 1.  sums: double[5], ring: float[cap][4], cursor: one unsigned, all on the device; the host reads

@@ -11,3 +11,13 @@ from .dataset_stats import compute_dataset_anchors_seed, compute_dataset_mean_an
 from .metrics import DetectionAP, evaluate_results  # noqa: F401
 
 __version__ = "0.1.0"
+
+_TRAINER_NAMES = ('FusedClipSGD', 'FusedClipAdamW', 'GraphedStep', 'Trainer')
+
+
+def __getattr__(name):
+    """The training surface (``sqd.FusedClipAdamW`` ...), imported from ``trainer`` on first use."""
+    if name in _TRAINER_NAMES:
+        from . import trainer
+        return getattr(trainer, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -103,6 +103,10 @@ _SIGNATURES = {
     'sqd_sgd_clip_step_parts': [c_p, c_i, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_p],
     'sqd_sgd_clip_step_chunked_dev': [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
     'sqd_fill_f32x4': [c_p, c_f, c_f, c_f, c_f, c_p],
+    'sqd_optim_begin': [c_p, c_p, c_p, c_i, c_i, c_p],
+    'sqd_adamw_clip_step_chunked': [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p],
+    'sqd_sgd_clip_step_chunked_ema': [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    'sqd_param_swap': [c_p, c_p, c_i, c_p],
     'sqd_train_log_push': [c_p, c_i, c_p, c_p, c_p, c_i, c_p],
     'sqd_fire_pool_bridge_fwd': [c_p] * 6 + [c_i] * 15 + [c_p],
     'sqd_fire_pool_bridge_save_fwd': [c_p] * 8 + [c_i] * 18 + [c_p],

@@ -7,8 +7,10 @@ stripped, shape-mismatched / missing / unknown parameters are reported and skipp
 SqueezeNet weights map by ``'base.' + key``.  Files written here load in the reference and vice versa.
 
 ``save_checkpoint`` / ``load_checkpoint`` add what the reference lacks for restarting a (multi-GPU) run exactly:
-optimizer state (momentum buffers), LR-scheduler state and the RNG streams, under extra top-level keys that the
-reference's ``load_model`` simply ignores.  One process per GPU: rank 0 writes, every rank reads.
+optimizer state (momentum buffers; for ``trainer.FusedClipAdamW`` both moments and the device step count; with ``ema_decay > 0`` the
+averaged weights and the count of averaged steps), LR-scheduler state and the RNG streams, under extra top-level keys that the
+reference's ``load_model`` simply ignores.  One process per GPU: rank 0 writes, every rank reads.  The averaged weights as a model
+file of their own: ``torch.save({'epoch': e, 'state_dict': optimizer.ema_state_dict(model)}, path)`` loads with ``load_model``.
 """
 from __future__ import annotations
 

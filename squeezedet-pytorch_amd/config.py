@@ -62,7 +62,12 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         sparse_gt=False,             # training ground truth as the list of positives (ops.SparseGT in batch['gt_sparse']) instead of dense
         ignore_overlap=None,         # None: off.  A float in (0, 1] (0.5 is the documented value; needs sparse_gt): anchors covered to that share
                                      # by a flagged box (DontCare / difficult / crowd) leave the loss (batch['gt_ignore'], ops.loss_masked_*)
-        graph_step=False,            # training: replay the step as one captured hipGraph (trainer.GraphedStep; needs a FusedClipSGD, one process)
+        graph_step=False,            # training: replay the step as one captured hipGraph (trainer.GraphedStep; needs a FusedClipSGD or a
+                                     # FusedClipAdamW, one process)
+        optimizer='sgd',             # 'sgd' | 'adamw': which fused optimizer trainer.make_train_step builds (FusedClipSGD / FusedClipAdamW)
+        ema_decay=0.,                # > 0: the optimizer keeps an exponential moving average of the weights inside its step launch
+        ema_warmup=False,            # the EMA's decay starts at min(ema_decay, (1 + n) / (10 + n)) after n averaged steps
+        ema_eval=False,              # Trainer.val_epoch runs on the averaged weights (optimizer.averaged_weights())
         inflight=2,                  # batches in flight on the device in Detector.stream / detect_dataset (lanes.DetectStream)
         input_size=tuple(input_size), num_classes=num_classes, class_names=tuple(class_names),
         anchors=anchors, anchors_per_grid=int(np.asarray(anchors_seed).shape[0]),

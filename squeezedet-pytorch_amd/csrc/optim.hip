@@ -255,3 +255,201 @@ extern "C" int sqd_train_log_push(const float* losses, int B, double* sums, floa
   hipLaunchKernelGGL(train_log_push_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, losses, B, sums, ring, cursor, cap);
   return sqd_launch_status();
 }
+
+// ---- AdamW and a weight EMA in the same one-launch form (trainer.FusedClipAdamW, FusedClipSGD(ema_decay > 0)) ----
+// torch.optim.AdamW (non-amsgrad, decoupled decay) behind clip_grad_norm_, and the exponential moving average of
+// torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(d)), as ONE more instantiation of the chunked walk: the step
+// streams p, grad, m (and v), and the EMA adds one read and one write while the fresh parameter is still in a register.
+//   g = grad * coef;  p = p - (lr * wd) * p;  m = b1 * m + (1 - b1) * g;  v = b2 * v + (1 - b2) * (g * g)
+//   den = sqrt(v) * (1 / sqrt(bc2)) + eps;  p = p - (lr / bc1) * (m / den);  e = first averaged step ? p : e + (1 - d_t) * (p - e)
+// The step count t (bias corrections bc1 = 1 - b1^t, bc2 = 1 - b2^t) and the number of averaged steps n (warm-up:
+// d_t = min(d, (1 + n) / (10 + n))) live in DEVICE memory: a replayed hipGraph advances them without a host write.  A one-thread
+// launch in front of every step (optim_begin_kernel) increments them and leaves lr / bc1, 1 / sqrt(bc2), 1 - d_t (evaluated in
+// double from the float hyper table) and the copy flag in a derived table; the big launch only reads that table, so no workgroup
+// reads a counter that another workgroup of its launch writes.
+//   hyper (float[8], always on the device: one form, one set of bits):
+//     AdamW {lr, beta1, beta2, eps | weight_decay, max_norm, ema_decay, ema_warmup};  SGD {lr, momentum, weight_decay, max_norm |
+//     ema_decay, ema_warmup, -, -} (the first four as sgd_clip_chunked_dev_kernel reads them)
+//   counters (int[2]) {t, n};  derived (float[4]) {lr / bc1, 1 / sqrt(bc2), 1 - d_t, first averaged step ? 1 : 0}
+struct OptDesc { float* p; long long g; float* m; long long n; float* v; float* e; };      // SgdDesc widened by the second moment and the EMA
+
+__global__ void optim_begin_kernel(const float* __restrict__ hyper, int* __restrict__ counters, float* __restrict__ derived, int adam, int ema) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (adam) {
+    const int t = counters[0] + 1;
+    counters[0] = t;
+    const double bc1 = 1.0 - pow((double)hyper[1], (double)t), bc2 = 1.0 - pow((double)hyper[2], (double)t);
+    derived[0] = (float)((double)hyper[0] / bc1);
+    derived[1] = (float)(1.0 / sqrt(bc2));
+  }
+  if (ema) {
+    const int n = counters[1];
+    const float* eh = adam ? hyper + 6 : hyper + 4;
+    double d = (double)eh[0];
+    if (eh[1] != 0.f) { const double w = (1.0 + (double)n) / (10.0 + (double)n); d = d < w ? d : w; }
+    derived[2] = (float)(1.0 - d);
+    derived[3] = n == 0 ? 1.f : 0.f;
+    counters[1] = n + 1;
+  }
+}
+
+extern "C" int sqd_optim_begin(const float* hyper_dev, int* counters_dev, float* derived_dev, int adam, int ema, void* stream) {
+  SQD_CHECK_ARG(hyper_dev && counters_dev && derived_dev && (adam == 0 || adam == 1) && (ema == 0 || ema == 1) && (adam || ema));
+  hipLaunchKernelGGL(optim_begin_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, hyper_dev, counters_dev, derived_dev, adam, ema);
+  return sqd_launch_status();
+}
+
+// One element of the AdamW step, torch's order.  The ONE source expression of every instantiation (-ffp-contract=off).
+__device__ __forceinline__ void adamw_one(float p, float gr, float m, float v, float coef, float lrwd, float b1, float omb1, float b2,
+                                          float omb2, float eps, float step, float rbc2, float& pn, float& mn, float& vn) {
+  const float g = gr * coef;
+  const float pd = p - lrwd * p;
+  mn = b1 * m + omb1 * g;
+  vn = b2 * v + omb2 * (g * g);
+  const float den = sqrtf(vn) * rbc2 + eps;
+  pn = pd - step * (mn / den);
+}
+
+// One element of the EMA (the first averaged step copies, later ones lerp).  The ONE source expression, as above.
+__device__ __forceinline__ float ema_one(float e, float pn, float omd, bool copy) { return copy ? pn : e + omd * (pn - e); }
+
+// The clip coefficient from the partials of sqd_grad_sumsq (every wave for itself, as sgd_clip_chunk does) or from a device scalar
+// holding the norm (separate gradients); neither given: 1.
+__device__ __forceinline__ float clip_coef(const float* __restrict__ parts, const float* __restrict__ total_norm, float max_norm,
+                                           float* __restrict__ norm_out) {
+  if (!(max_norm > 0.f) || (!parts && !total_norm)) return 1.f;
+  float tn;
+  if (parts) {
+    const int lane = threadIdx.x & 63;
+    float ssum = 0.f;
+    for (int i = lane; i < SQD_NORM_PARTS; i += 64) ssum += parts[i];
+    for (int off = 32; off >= 1; off >>= 1) ssum += __shfl_xor(ssum, off);
+    tn = sqrtf(ssum);
+    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = tn;
+  } else {
+    tn = *total_norm;
+  }
+  const float coef = max_norm / (tn + 1e-6f);
+  return coef < 1.f ? coef : 1.f;
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_clip_chunked_kernel(const OptDesc* __restrict__ descs, const long long* __restrict__ chunks,
+                                                                 const float* __restrict__ g_base, const float* __restrict__ parts,
+                                                                 const float* __restrict__ total_norm, const float* __restrict__ hyper,
+                                                                 const float* __restrict__ derived, float* __restrict__ norm_out) {
+  const OptDesc d = descs[chunks[2 * blockIdx.x]];
+  const long long e0 = chunks[2 * blockIdx.x + 1];
+  const float* __restrict__ dg = g_base ? g_base + d.g : (const float*)d.g;
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
+  const float lrwd = lr * wd, omb1 = 1.f - b1, omb2 = 1.f - b2;
+  const float step = derived[0], rbc2 = derived[1];
+  const float omd = EMA ? derived[2] : 0.f;
+  const bool copy = EMA && derived[3] != 0.f;
+  const float coef = clip_coef(parts, total_norm, hyper[5], norm_out);
+  const long long e1 = (e0 + SQD_SGD_CHUNK < d.n) ? e0 + SQD_SGD_CHUNK : d.n;
+  const bool vec = ((((uintptr_t)d.p) | ((uintptr_t)dg) | ((uintptr_t)d.m) | ((uintptr_t)d.v) | (EMA ? (uintptr_t)d.e : 0)) & 15) == 0;
+  const long long q0 = e0 >> 2, q1 = vec ? (e1 >> 2) : q0;
+  for (long long i = q0 + threadIdx.x; i < q1; i += 256) {
+    const f32x4 p = ((const f32x4*)d.p)[i], gr = ((const f32x4*)dg)[i], m = ((const f32x4*)d.m)[i], v = ((const f32x4*)d.v)[i];
+    float pn[4], mn[4], vn[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) adamw_one(p[e], gr[e], m[e], v[e], coef, lrwd, b1, omb1, b2, omb2, eps, step, rbc2, pn[e], mn[e], vn[e]);
+    ((f32x4*)d.m)[i] = (f32x4){mn[0], mn[1], mn[2], mn[3]}; ((f32x4*)d.v)[i] = (f32x4){vn[0], vn[1], vn[2], vn[3]};
+    ((f32x4*)d.p)[i] = (f32x4){pn[0], pn[1], pn[2], pn[3]};
+    if (EMA) {
+      const f32x4 a = ((const f32x4*)d.e)[i];
+      ((f32x4*)d.e)[i] = (f32x4){ema_one(a[0], pn[0], omd, copy), ema_one(a[1], pn[1], omd, copy), ema_one(a[2], pn[2], omd, copy),
+                                 ema_one(a[3], pn[3], omd, copy)};
+    }
+  }
+  for (long long i = 4 * q1 + threadIdx.x; i < e1; i += 256) {
+    float pn, mn, vn;
+    adamw_one(d.p[i], dg[i], d.m[i], d.v[i], coef, lrwd, b1, omb1, b2, omb2, eps, step, rbc2, pn, mn, vn);
+    d.m[i] = mn; d.v[i] = vn; d.p[i] = pn;
+    if (EMA) d.e[i] = ema_one(d.e[i], pn, omd, copy);
+  }
+}
+
+// descs_dev: n records of 6 int64 {param ptr, grad (offset into grad_base, or an address when grad_base is NULL), exp_avg ptr, elements,
+// exp_avg_sq ptr, EMA ptr (read only when ema)}; chunks_dev as for sqd_sgd_clip_step_chunked.  The clip: sumsq_parts (the partials of
+// sqd_grad_sumsq), else total_norm (a device float holding the norm), else none -- structural, as in sqd_sgd_clip_step_chunked_dev.
+extern "C" int sqd_adamw_clip_step_chunked(const void* descs_dev, const void* chunks_dev, int nchunks, const float* grad_base,
+                                           const float* sumsq_parts, const float* total_norm, float* norm_out, const float* hyper_dev,
+                                           const float* derived_dev, int ema, void* stream) {
+  SQD_CHECK_ARG(descs_dev && chunks_dev && nchunks > 0 && hyper_dev && derived_dev && (ema == 0 || ema == 1));
+  if (ema)
+    hipLaunchKernelGGL(adamw_clip_chunked_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, (const OptDesc*)descs_dev,
+                       (const long long*)chunks_dev, grad_base, sumsq_parts, total_norm, hyper_dev, derived_dev, norm_out);
+  else
+    hipLaunchKernelGGL(adamw_clip_chunked_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, (const OptDesc*)descs_dev,
+                       (const long long*)chunks_dev, grad_base, sumsq_parts, total_norm, hyper_dev, derived_dev, norm_out);
+  return sqd_launch_status();
+}
+
+// The SGD chunk body (sgd_one, the expression of the kernels above: equal values, equal bits) with the EMA behind it.
+__global__ __launch_bounds__(256) void sgd_clip_chunked_ema_kernel(const OptDesc* __restrict__ descs, const long long* __restrict__ chunks,
+                                                                   const float* __restrict__ g_base, const float* __restrict__ parts,
+                                                                   const float* __restrict__ hyper, const float* __restrict__ derived,
+                                                                   float* __restrict__ norm_out) {
+  const OptDesc d = descs[chunks[2 * blockIdx.x]];
+  const long long e0 = chunks[2 * blockIdx.x + 1];
+  const float* __restrict__ dg = g_base ? g_base + d.g : (const float*)d.g;
+  const float lr = hyper[0], momentum = hyper[1], wd = hyper[2];
+  const float omd = derived[2];
+  const bool copy = derived[3] != 0.f;
+  const float coef = clip_coef(parts, nullptr, hyper[3], norm_out);
+  const long long e1 = (e0 + SQD_SGD_CHUNK < d.n) ? e0 + SQD_SGD_CHUNK : d.n;
+  const bool vec = ((((uintptr_t)d.p) | ((uintptr_t)dg) | ((uintptr_t)d.m) | ((uintptr_t)d.e)) & 15) == 0;
+  const long long q0 = e0 >> 2, q1 = vec ? (e1 >> 2) : q0;
+  for (long long i = q0 + threadIdx.x; i < q1; i += 256) {
+    const f32x4 p = ((const f32x4*)d.p)[i], gr = ((const f32x4*)dg)[i], m = ((const f32x4*)d.m)[i], a = ((const f32x4*)d.e)[i];
+    float pn[4], mn[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sgd_one(p[e], gr[e], m[e], coef, wd, momentum, lr, pn[e], mn[e]);
+    ((f32x4*)d.m)[i] = (f32x4){mn[0], mn[1], mn[2], mn[3]}; ((f32x4*)d.p)[i] = (f32x4){pn[0], pn[1], pn[2], pn[3]};
+    ((f32x4*)d.e)[i] = (f32x4){ema_one(a[0], pn[0], omd, copy), ema_one(a[1], pn[1], omd, copy), ema_one(a[2], pn[2], omd, copy),
+                               ema_one(a[3], pn[3], omd, copy)};
+  }
+  for (long long i = 4 * q1 + threadIdx.x; i < e1; i += 256) {
+    float pn, mn;
+    sgd_one(d.p[i], dg[i], d.m[i], coef, wd, momentum, lr, pn, mn);
+    d.m[i] = mn; d.p[i] = pn;
+    d.e[i] = ema_one(d.e[i], pn, omd, copy);
+  }
+}
+
+// sqd_sgd_clip_step_chunked_dev with the EMA: descs_dev in the 6-word form (exp_avg_sq unused), hyper_dev float[8], derived_dev as
+// written by sqd_optim_begin(adam = 0, ema = 1).
+extern "C" int sqd_sgd_clip_step_chunked_ema(const void* descs_dev, const void* chunks_dev, int nchunks, const float* grad_base,
+                                             const float* sumsq_parts, float* norm_out, const float* hyper_dev, const float* derived_dev,
+                                             void* stream) {
+  SQD_CHECK_ARG(descs_dev && chunks_dev && nchunks > 0 && hyper_dev && derived_dev);
+  hipLaunchKernelGGL(sgd_clip_chunked_ema_kernel, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, (const OptDesc*)descs_dev,
+                     (const long long*)chunks_dev, grad_base, sumsq_parts, hyper_dev, derived_dev, norm_out);
+  return sqd_launch_status();
+}
+
+// p <-> e over the same tables, exactly (optimizer.averaged_weights()).
+__global__ __launch_bounds__(256) void param_swap_kernel(const OptDesc* __restrict__ descs, const long long* __restrict__ chunks) {
+  const OptDesc d = descs[chunks[2 * blockIdx.x]];
+  const long long e0 = chunks[2 * blockIdx.x + 1];
+  const long long e1 = (e0 + SQD_SGD_CHUNK < d.n) ? e0 + SQD_SGD_CHUNK : d.n;
+  const bool vec = ((((uintptr_t)d.p) | ((uintptr_t)d.e)) & 15) == 0;
+  const long long q0 = e0 >> 2, q1 = vec ? (e1 >> 2) : q0;
+  for (long long i = q0 + threadIdx.x; i < q1; i += 256) {
+    const f32x4 p = ((const f32x4*)d.p)[i], a = ((const f32x4*)d.e)[i];
+    ((f32x4*)d.p)[i] = a; ((f32x4*)d.e)[i] = p;
+  }
+  for (long long i = 4 * q1 + threadIdx.x; i < e1; i += 256) {
+    const float p = d.p[i], a = d.e[i];
+    d.p[i] = a; d.e[i] = p;
+  }
+}
+
+extern "C" int sqd_param_swap(const void* descs_dev, const void* chunks_dev, int nchunks, void* stream) {
+  SQD_CHECK_ARG(descs_dev && chunks_dev && nchunks > 0);
+  hipLaunchKernelGGL(param_swap_kernel, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, (const OptDesc*)descs_dev,
+                     (const long long*)chunks_dev);
+  return sqd_launch_status();
+}

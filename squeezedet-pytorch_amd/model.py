@@ -327,7 +327,9 @@ class SqueezeDetBase(nn.Module):
     def invalidate_plans(self):
         """Drop every packed / transformed weight copy.  The caches notice optimizer steps, ``load_state_dict``, ``.to()``
         and any other in-place op on the parameters (version counter / data pointer); a write through ``param.data``
-        (EMA, manual ``p.data.copy_``) moves neither -- call this after one."""
+        (a hand-made EMA, manual ``p.data.copy_``) moves neither -- call this after one.  The EMA the fused optimizers keep
+        (``trainer.FusedClipSGD`` / ``FusedClipAdamW`` with ``ema_decay > 0``) needs no such call: ``optimizer.averaged_weights()``
+        advances the version counters when it swaps the averaged values in and out."""
         self.plan_cache.clear()
         for m in self.modules():
             if isinstance(m, _ConvParams):

@@ -370,7 +370,7 @@ class Trainer(object):
                 mean_loss.backward(self._one)      # local shard mean; the gradient exchange turns it into the global mean
             else:
                 per_image_loss.mean().backward()
-            if not (isinstance(self.optimizer, FusedClipSGD) and self.optimizer.max_norm > 0):      # (it clips inside its one launch)
+            if not (isinstance(self.optimizer, FusedClipBase) and self.optimizer.max_norm > 0):     # (it clips inside its one launch)
                 torch.nn.utils.clip_grad_norm_([p for p in self.model.parameters() if p.requires_grad], self.cfg.grad_norm)
             self.optimizer.step()
         n = per_image_loss.shape[0]
@@ -384,8 +384,8 @@ class Trainer(object):
         """The ``GraphedStep`` of ``cfg.graph_step`` (made on first use; its refusals surface here)."""
         gs = getattr(self, '_graphed', None)
         if gs is None or gs.model is not self.model or gs.optimizer is not self.optimizer:
-            if isinstance(self.optimizer, FusedClipSGD) and not self.optimizer.max_norm > 0:
-                raise ValueError('Trainer: cfg.graph_step clips inside the optimizer launch: construct the FusedClipSGD with '
+            if isinstance(self.optimizer, FusedClipBase) and not self.optimizer.max_norm > 0:
+                raise ValueError(f'Trainer: cfg.graph_step clips inside the optimizer launch: construct the {type(self.optimizer).__name__} with '
                                  'max_norm=cfg.grad_norm (with max_norm=0 the eager loop clips with a torch call the captured step lacks)')
             gs = self._graphed = GraphedStep(self.model, self.optimizer, self.cfg)
         return gs
@@ -455,6 +455,13 @@ class Trainer(object):
 
     @torch.no_grad()
     def val_epoch(self, epoch, data_loader):
+        """With ``cfg.ema_eval`` the epoch runs on the optimizer's averaged weights (``averaged_weights()``: swapped in, swapped back)."""
+        if getattr(self.cfg, 'ema_eval', False):
+            if not (isinstance(self.optimizer, FusedClipBase) and self.optimizer.ema_on):
+                raise ValueError('Trainer: cfg.ema_eval needs a FusedClipSGD or FusedClipAdamW constructed with ema_decay > 0, got '
+                                 f'{type(self.optimizer).__name__}')
+            with self.optimizer.averaged_weights():
+                return self.run_epoch('val', epoch, data_loader)
         return self.run_epoch('val', epoch, data_loader)
 
 
@@ -479,7 +486,267 @@ class HyperTable:
         return True
 
 
-class FusedClipSGD(torch.optim.Optimizer):
+class FusedClipBase(torch.optim.Optimizer):
+    """What the one-launch optimizers (``FusedClipSGD``, ``FusedClipAdamW``) share: ONE parameter group whose ``param_groups[0]`` is read
+    at every ``step()``; the detection of the backward's flat gradient buffer; the descriptor and chunk tables with their rebuild rule;
+    the device hyper-parameter table (``HyperTable``); ``norm_value``; and the exponential moving average of the weights.
+
+    The EMA (``ema_decay > 0``, fixed at construction) follows ``torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(d))``:
+    the first averaged step copies the new parameters, later ones ``e += (1 - d_t) (p - e)`` with ``d_t = d``, or with ``ema_warmup``
+    ``min(d, (1 + n) / (10 + n))`` after ``n`` averaged steps.  It is computed inside the step launch (one more read and write while
+    the fresh parameter is in a register), lives in ``ema_flat`` (views in ``state[p]['ema']``) and is part of ``state_dict()``.  The
+    counts -- ``t`` optimizer steps (AdamW's bias correction) and ``n`` averaged steps -- live on the DEVICE and are advanced by a
+    one-thread launch in front of every step (``sqd_optim_begin``), eager and captured alike: a replayed hipGraph needs no host write.
+    ``averaged_weights()`` swaps the averaged values into the parameters for an evaluation, ``ema_state_dict(model)`` returns them."""
+
+    def __init__(self, params, defaults, flat_grad=None):
+        who = type(self).__name__
+        params = [p for p in params if p.requires_grad]
+        if not params or any(p.dtype != torch.float32 or not p.is_cuda for p in params):
+            raise ValueError(f'{who}: fp32 parameters on the GPU only (the product path has no CPU fallback)')
+        if not 0.0 <= float(defaults['ema_decay']) < 1.0:
+            raise ValueError(f'{who}: ema_decay must be in [0, 1) (0 = no EMA), got {defaults["ema_decay"]!r}')
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError(f'{who}: one parameter group (the kernel applies one set of hyper-parameters to all tensors)')
+        self.flat_grad = flat_grad                     # callable -> the flat gradient tensor the .grad views live in (or None)
+        self.total = sum(p.numel() for p in self.params)
+        self._table = self._table_key = self._chunks = None
+        self._norm_ws = None                           # partial sums of squares + the norm (device)
+        self.last_norm = None
+        self._hyper_dev = None                         # the device hyper-parameter table
+        self._hyper_table = HyperTable(self._write_hyper)
+        self.ema_on = float(defaults['ema_decay']) > 0     # structural: the EMA launches and buffers exist or not
+        self.ema_flat = self._emas = None
+        self._steps_dev = None                         # int32 {t, n} | float32 derived {lr / bc1, 1 / sqrt(bc2), 1 - d_t, copy} (device)
+        self._swap_tables = self._swap_key = None
+        self._averaging = False
+        if self.ema_on:
+            self.ema_flat, self._emas = self._flat_state('ema')
+            with torch.no_grad():                      # (meaningful before the first step; the first averaged step copies anyway)
+                for e, p in zip(self._emas, self.params):
+                    e.copy_(p.detach().reshape(-1))
+
+    @property
+    def params(self):
+        return self.param_groups[0]['params']
+
+    def _hyper(self, name):
+        return float(self.param_groups[0][name])
+
+    lr = property(lambda self: self._hyper('lr'))
+    weight_decay = property(lambda self: self._hyper('weight_decay'))
+    max_norm = property(lambda self: self._hyper('max_norm'))
+    ema_decay = property(lambda self: self._hyper('ema_decay'))
+    ema_warmup = property(lambda self: bool(self.param_groups[0]['ema_warmup']))
+
+    def add_param_group(self, param_group):
+        if getattr(self, 'param_groups', None):
+            raise ValueError(f'{type(self).__name__}: one parameter group only')
+        super().add_param_group(param_group)
+
+    def _flat_state(self, name):
+        """A zero flat buffer of the parameters' total size and its per-parameter views, registered as ``state[p][name]`` (views:
+        ``attach_data_parallel`` broadcasts floating-point optimizer state tensors in place)."""
+        flat = torch.zeros(self.total, device=self.params[0].device, dtype=torch.float32)
+        views, off = [], 0
+        for p in self.params:
+            views.append(flat[off:off + p.numel()]); off += p.numel()
+            self.state[p][name] = views[-1]
+        return flat, views
+
+    def _write_hyper(self, values):
+        from . import _native as nat
+        dev = self.params[0].device
+        if self._hyper_dev is None or self._hyper_dev.device != dev or self._hyper_dev.numel() != len(values):
+            self._hyper_dev = torch.zeros(len(values), device=dev, dtype=torch.float32)
+        for i in range(0, len(values), 4):             # (one one-thread launch per four values: the SGD table without EMA is one launch)
+            nat.check(nat.lib().sqd_fill_f32x4(nat.c_p(self._hyper_dev.data_ptr() + 4 * i), *[float(v) for v in values[i:i + 4]],
+                                               nat.stream_handle(dev)), 'sqd_fill_f32x4')
+
+    def refresh_hyper(self):
+        """Bring the device hyper-parameter table up to date with ``param_groups[0]`` on the current stream (one-thread launches, only
+        when a value changed since the last write): what a caller does in front of a replay of a captured step.  -> whether it wrote.
+        Raises under stream capture if the table is stale (the write would become part of the graph with today's values)."""
+        dev = self.params[0].device
+        return self._hyper_table.refresh(self._hyper_values(), capturing=torch.cuda.is_current_stream_capturing(),
+                                         force=self._hyper_dev is None or self._hyper_dev.device != dev)
+
+    def _flat_base(self, grads):
+        """The flat gradient tensor if the gradients are consecutive views of it (the HIP backward's layout), else None."""
+        flat = self.flat_grad() if self.flat_grad is not None else None
+        if flat is None or not flat.is_contiguous() or flat.numel() < self.total:
+            return None
+        ptr = flat.data_ptr()
+        for g in grads:
+            if not g.is_contiguous() or g.data_ptr() != ptr:
+                return None
+            ptr += g.numel() * 4
+        return flat
+
+    def _gradients(self):
+        """-> (the flat gradient buffer or None, the gradients: contiguous when they are separate tensors)."""
+        grads = [p.grad for p in self.params]
+        if any(g is None for g in grads):
+            raise RuntimeError(f'{type(self).__name__}.step: a parameter has no gradient')
+        flat = self._flat_base(grads)
+        if flat is None:
+            grads = [g if g.is_contiguous() else g.contiguous() for g in grads]
+        return flat, grads
+
+    def _ensure_tables(self, flat, grads, firsts, seconds=None):
+        """The descriptor table holds the parameter and state addresses and, per tensor, its offset into the flat gradient buffer (whose
+        own address is a launch argument) or the gradient's address: rows of 4 words {p, grad, first state, elements}, or of 6 with
+        ``seconds`` or the EMA {.., second state, ema}.  Everything baked into it is part of the key: a parameter whose storage was
+        replaced after the first step (model.to() / p.data = ...) rebuilds the table instead of letting the kernel write through a
+        stale pointer."""
+        from . import _native as nat
+        params = self.params
+        wide = seconds is not None or self.ema_on
+        key = (('flat',) if flat is not None else tuple(g.data_ptr() for g in grads), tuple(p.data_ptr() for p in params),
+               firsts[0].data_ptr()) + ((seconds[0].data_ptr() if seconds is not None else 0,
+                                         self.ema_flat.data_ptr() if self.ema_on else 0) if wide else ())
+        if key == self._table_key:
+            return
+        off, rows = 0, []
+        for i, (p, g, b) in enumerate(zip(params, grads, firsts)):
+            if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
+                raise RuntimeError(f'{type(self).__name__}.step: parameters must stay contiguous fp32 GPU tensors')
+            row = [p.data_ptr(), off if flat is not None else g.data_ptr(), b.data_ptr(), p.numel()]
+            if wide:
+                row += [seconds[i].data_ptr() if seconds is not None else 0, self._emas[i].data_ptr() if self.ema_on else 0]
+            rows.append(row); off += p.numel()
+        self._table = torch.tensor(rows, dtype=torch.int64).to(params[0].device)
+        # equal chunks of the 64 tensors (16 .. 500 k elements): one workgroup per chunk
+        ce = int(nat.lib().sqd_sgd_chunk_elems())
+        chunks = [[i, e] for i, p in enumerate(params) for e in range(0, p.numel(), ce)]
+        self._chunks = torch.tensor(chunks, dtype=torch.int64).to(params[0].device)
+        self._table_key = key
+
+    def _sumsq(self, flat):
+        """The norm of the flat gradient buffer: partial sums of squares by one small launch, finished (fixed order) inside the step.
+        -> (parts, the 0-dim norm the step launch writes)."""
+        from . import _native as nat
+        if self._norm_ws is None:
+            self._norm_ws = torch.empty(int(nat.lib().sqd_grad_sumsq_parts()) + 1, device=flat.device, dtype=torch.float32)
+        parts, norm = self._norm_ws[:-1], self._norm_ws[-1]
+        nat.check(nat.lib().sqd_grad_sumsq(nat.ptr(flat), self.total, nat.ptr(parts), nat.stream_handle(flat.device)), 'sqd_grad_sumsq')
+        return parts, norm
+
+    def _begin(self, adam):
+        """The one-thread launch in front of a step: advances the device counts, writes the derived table -> (counters, derived)."""
+        from . import _native as nat
+        dev = self.params[0].device
+        if self._steps_dev is None or self._steps_dev.device != dev:
+            was = self._steps_dev
+            self._steps_dev = torch.zeros(8, device=dev, dtype=torch.int32)
+            if was is not None:
+                self._steps_dev.copy_(was)
+        counters, derived = self._steps_dev[:2], self._steps_dev[2:6].view(torch.float32)
+        nat.check(nat.lib().sqd_optim_begin(nat.ptr(self._hyper_dev), nat.ptr(counters), nat.ptr(derived), int(adam), int(self.ema_on),
+                                            nat.stream_handle(dev)), 'sqd_optim_begin')
+        return counters, derived
+
+    def step_counts(self):
+        """(t, n): optimizer steps counted for the bias correction (0 for SGD) and averaged steps, read from the device (one host sync)."""
+        if self._steps_dev is None:
+            return 0, 0
+        t, n = self._steps_dev[:2].tolist()
+        return int(t), int(n)
+
+    def _set_step_counts(self, t, n):
+        dev = self.params[0].device
+        if self._steps_dev is None or self._steps_dev.device != dev:
+            self._steps_dev = torch.zeros(8, device=dev, dtype=torch.int32)
+        self._steps_dev[:2].copy_(torch.tensor([int(t), int(n)], dtype=torch.int32))
+
+    def norm_value(self):
+        """The latest step's total gradient norm as a Python float (one host sync), or None before the first clipped step."""
+        return None if self.last_norm is None else float(self.last_norm)
+
+    # ---- the averaged weights ----
+    def _swap(self):
+        from . import _native as nat
+        params = self.params
+        key = (tuple(p.data_ptr() for p in params), self.ema_flat.data_ptr())
+        if key != self._swap_key:
+            if any(not p.is_contiguous() for p in params):
+                raise RuntimeError(f'{type(self).__name__}.averaged_weights: parameters must stay contiguous fp32 GPU tensors')
+            rows = [[p.data_ptr(), 0, 0, p.numel(), 0, e.data_ptr()] for p, e in zip(params, self._emas)]
+            ce = int(nat.lib().sqd_sgd_chunk_elems())
+            chunks = [[i, e] for i, p in enumerate(params) for e in range(0, p.numel(), ce)]
+            dev = params[0].device
+            self._swap_tables = (torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int64).to(dev))
+            self._swap_key = key
+        table, chunks = self._swap_tables
+        nat.check(nat.lib().sqd_param_swap(nat.ptr(table), nat.ptr(chunks), chunks.shape[0], nat.stream_handle(params[0].device)),
+                  'sqd_param_swap')
+        torch.autograd.graph.increment_version(params)        # (the packed-weight caches key on the version counters: PlanCache re-packs)
+
+    def averaged_weights(self):
+        """Context manager: inside, the parameters hold the EMA (one swap launch; the version counters advance, so the packed-weight
+        caches re-pack without a manual ``invalidate_plans``) -- evaluate or export there; leaving swaps back, and the parameters are
+        bit-identical to before.  Raises when the EMA is off, when nested and under stream capture."""
+        import contextlib
+        who = type(self).__name__
+
+        @contextlib.contextmanager
+        def ctx():
+            if not self.ema_on:
+                raise RuntimeError(f'{who}.averaged_weights: the EMA is off (construct the optimizer with ema_decay > 0)')
+            if self._averaging:
+                raise RuntimeError(f'{who}.averaged_weights: already inside averaged_weights() (nested: the inner block would swap the '
+                                   'training weights back in)')
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f'{who}.averaged_weights: not under stream capture (the swap is not part of a training step)')
+            self._averaging = True
+            self._swap()
+            try:
+                yield self
+            finally:
+                self._swap()
+                self._averaging = False
+        return ctx()
+
+    def ema_state_dict(self, model):
+        """``model.state_dict()`` (clones) with every parameter this optimizer averages replaced by its EMA: what ``Detector``,
+        ``save_model`` / ``load_model`` and ``load_state_dict`` take unchanged."""
+        if not self.ema_on:
+            raise RuntimeError(f'{type(self).__name__}.ema_state_dict: the EMA is off (construct the optimizer with ema_decay > 0)')
+        if self._averaging:
+            raise RuntimeError(f'{type(self).__name__}.ema_state_dict: inside averaged_weights() the parameters ARE the averaged values: '
+                               'take model.state_dict()')
+        sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+        ema = {id(p): e for p, e in zip(self.params, self._emas)}
+        for name, p in model.named_parameters():
+            if id(p) in ema:
+                if name not in sd:
+                    raise RuntimeError(f'ema_state_dict: parameter {name} is not a key of the state_dict')
+                sd[name] = ema[id(p)].detach().clone().view(p.shape)
+        return sd
+
+    def _check_step_allowed(self):
+        if self._averaging:
+            raise RuntimeError(f'{type(self).__name__}.step: inside averaged_weights() (the parameters hold the EMA)')
+
+    def _ema_state(self):
+        g = self.param_groups[0]
+        out = {'ema_decay': g['ema_decay'], 'ema_warmup': bool(g['ema_warmup'])}
+        if self.ema_on:
+            out['ema_flat'] = self.ema_flat.clone()
+        return out
+
+    def _load_ema_state(self, sd):
+        g = self.param_groups[0]
+        if self.ema_on and sd.get('ema_flat') is not None:
+            self.ema_flat.copy_(sd['ema_flat'].to(self.ema_flat.device))
+        if self.ema_on and sd.get('ema_decay'):
+            g['ema_decay'] = float(sd['ema_decay'])
+        if sd.get('ema_warmup') is not None:
+            g['ema_warmup'] = bool(sd['ema_warmup'])
+
+
+class FusedClipSGD(FusedClipBase):
     """``torch.nn.utils.clip_grad_norm_(params, max_norm)`` + ``torch.optim.SGD(params, lr, momentum, weight_decay).step()``
     (src/engine/trainer.py:47-50) as ONE launch over all parameter tensors (csrc/optim.hip, sqd_sgd_clip_step): torch runs the pair
     as ~10 foreach / elementwise launches over the 64 tensors (about 0.15 ms of a 6.3 ms training step).  Same arithmetic in the
@@ -496,76 +763,23 @@ class FusedClipSGD(torch.optim.Optimizer):
     in a device ``float[4]`` table that the kernel reads (``sqd_sgd_clip_step_chunked_dev``; flat-gradient layout only): ``step()``
     rewrites the table -- one one-thread launch, only when a value of ``param_groups[0]`` changed -- and whoever replays a captured step
     calls ``refresh_hyper()`` in front of the replay, so an LR schedule needs no re-capture.  Only whether the norm is evaluated at all
-    (``max_norm > 0``) is fixed by the capture: a caller that switches between zero and positive re-captures."""
+    (``max_norm > 0``) is fixed by the capture: a caller that switches between zero and positive re-captures.
 
-    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, max_norm=0.0, flat_grad=None):
-        params = [p for p in params if p.requires_grad]
-        if not params or any(p.dtype != torch.float32 or not p.is_cuda for p in params):
-            raise ValueError('FusedClipSGD: fp32 parameters on the GPU only (the product path has no CPU fallback)')
-        super().__init__(params, dict(lr=float(lr), momentum=float(momentum), weight_decay=float(weight_decay), max_norm=float(max_norm)))
-        if len(self.param_groups) != 1:
-            raise ValueError('FusedClipSGD: one parameter group (the kernel applies one set of hyper-parameters to all tensors)')
-        self.flat_grad = flat_grad                     # callable -> the flat gradient tensor the .grad views live in (or None)
-        dev = self.params[0].device
-        self.total = sum(p.numel() for p in self.params)
-        self.momentum_flat = torch.zeros(self.total, device=dev, dtype=torch.float32)
-        self._bufs, off = [], 0
-        for p in self.params:
-            self._bufs.append(self.momentum_flat[off:off + p.numel()]); off += p.numel()
-            self.state[p]['momentum_buffer'] = self._bufs[-1]       # views: attach_data_parallel broadcasts optimizer state tensors in place
-        self._table = self._table_key = self._chunks = None
-        self._norm_ws = None                           # partial sums of squares + the norm (device)
-        self.last_norm = None
-        self.hyper_on_device = False                   # the kernel reads {lr, momentum, weight_decay, max_norm} from device memory
-        self._hyper_dev = None                         # that table (device float[4])
-        self._hyper_table = HyperTable(self._write_hyper)
+    ``ema_decay > 0`` adds the weight EMA of ``FusedClipBase`` to the launch (``sqd_sgd_clip_step_chunked_ema``: the same arithmetic
+    and bits for the parameters and the momentum).  It needs the device hyper-parameter table (``hyper_on_device`` is switched on at
+    construction) and the flat-gradient layout; at 0 nothing changes: the launches, the bits and the keys of ``state_dict()``."""
 
-    @property
-    def params(self):
-        return self.param_groups[0]['params']
+    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, max_norm=0.0, flat_grad=None, ema_decay=0.0, ema_warmup=False):
+        super().__init__(params, dict(lr=float(lr), momentum=float(momentum), weight_decay=float(weight_decay), max_norm=float(max_norm),
+                                      ema_decay=float(ema_decay), ema_warmup=bool(ema_warmup)), flat_grad)
+        self.momentum_flat, self._bufs = self._flat_state('momentum_buffer')
+        self.hyper_on_device = self.ema_on             # the kernel reads {lr, momentum, weight_decay, max_norm} from device memory
 
-    def _hyper(self, name):
-        return float(self.param_groups[0][name])
-
-    lr = property(lambda self: self._hyper('lr'))
     momentum = property(lambda self: self._hyper('momentum'))
-    weight_decay = property(lambda self: self._hyper('weight_decay'))
-    max_norm = property(lambda self: self._hyper('max_norm'))
-
-    def add_param_group(self, param_group):
-        if getattr(self, 'param_groups', None):
-            raise ValueError('FusedClipSGD: one parameter group only')
-        super().add_param_group(param_group)
 
     def _hyper_values(self):
-        return (self.lr, self.momentum, self.weight_decay, self.max_norm)
-
-    def _write_hyper(self, values):
-        from . import _native as nat
-        dev = self.params[0].device
-        if self._hyper_dev is None or self._hyper_dev.device != dev:
-            self._hyper_dev = torch.zeros(4, device=dev, dtype=torch.float32)
-        nat.check(nat.lib().sqd_fill_f32x4(nat.ptr(self._hyper_dev), *[float(v) for v in values], nat.stream_handle(dev)), 'sqd_fill_f32x4')
-
-    def refresh_hyper(self):
-        """Bring the device table of ``hyper_on_device`` up to date with ``param_groups[0]`` on the current stream (a one-thread launch,
-        only when a value changed since the last write): what a caller does in front of a replay of a captured step.  -> whether it
-        wrote.  Raises under stream capture if the table is stale (the write would become part of the graph with today's values)."""
-        dev = self.params[0].device
-        return self._hyper_table.refresh(self._hyper_values(), capturing=torch.cuda.is_current_stream_capturing(),
-                                   force=self._hyper_dev is None or self._hyper_dev.device != dev)
-
-    def _flat_base(self, grads):
-        """The flat gradient tensor if the gradients are consecutive views of it (the HIP backward's layout), else None."""
-        flat = self.flat_grad() if self.flat_grad is not None else None
-        if flat is None or not flat.is_contiguous() or flat.numel() < self.total:
-            return None
-        ptr = flat.data_ptr()
-        for g in grads:
-            if not g.is_contiguous() or g.data_ptr() != ptr:
-                return None
-            ptr += g.numel() * 4
-        return flat
+        sgd = (self.lr, self.momentum, self.weight_decay, self.max_norm)
+        return sgd + (self.ema_decay, float(self.ema_warmup), 0.0, 0.0) if self.ema_on else sgd
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -578,53 +792,36 @@ class FusedClipSGD(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_step_allowed()
         params = self.params
-        grads = [p.grad for p in params]
-        if any(g is None for g in grads):
-            raise RuntimeError('FusedClipSGD.step: a parameter has no gradient')
-        flat = self._flat_base(grads)
+        flat, grads = self._gradients()
+        if self.ema_on and not (self.hyper_on_device and flat is not None):
+            raise RuntimeError('FusedClipSGD.step: ema_decay > 0 runs in the chunked launch that reads its hyper-parameters from device '
+                               'memory, not on the launch-argument path: it needs hyper_on_device = True and the flat-gradient layout '
+                               '(flat_grad given and every p.grad a consecutive view of that buffer, as the HIP backward leaves them)')
         if self.hyper_on_device and flat is None:
             raise RuntimeError('FusedClipSGD.step: hyper_on_device needs the flat-gradient layout (flat_grad given and every p.grad a '
                                'consecutive view of that buffer, as the HIP backward leaves them); these gradients are separate tensors')
-        if flat is None:
-            grads = [g if g.is_contiguous() else g.contiguous() for g in grads]
-        # the descriptor table holds the parameter and momentum addresses and, per tensor, its offset into the flat gradient
-        # buffer (whose own address is a launch argument) or the gradient's address.  Everything baked into it is part of the key:
-        # a parameter whose storage was replaced after the first step (model.to() / p.data = ...) rebuilds the table instead of
-        # letting the kernel write through a stale pointer
-        key = (('flat',) if flat is not None else tuple(g.data_ptr() for g in grads),
-               tuple(p.data_ptr() for p in params), self.momentum_flat.data_ptr())
-        if key != self._table_key:
-            off, rows = 0, []
-            for p, g, b in zip(params, grads, self._bufs):
-                if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
-                    raise RuntimeError('FusedClipSGD.step: parameters must stay contiguous fp32 GPU tensors')
-                rows.append([p.data_ptr(), off if flat is not None else g.data_ptr(), b.data_ptr(), p.numel()]); off += p.numel()
-            self._table = torch.tensor(rows, dtype=torch.int64).to(params[0].device)
-            # equal chunks of the 64 tensors (16 .. 500 k elements): one workgroup per chunk
-            ce = int(nat.lib().sqd_sgd_chunk_elems())
-            chunks = [[i, e] for i, p in enumerate(params) for e in range(0, p.numel(), ce)]
-            self._chunks = torch.tensor(chunks, dtype=torch.int64).to(params[0].device)
-            self._table_key = key
+        self._ensure_tables(flat, grads, self._bufs)
         norm = None
         max_norm = self.max_norm
         if self.hyper_on_device:
             self.refresh_hyper()                       # (writes when a value changed; under capture: raises if it would have to)
             parts = None
             if max_norm > 0:                           # structural: a captured step keeps or lacks the norm launch
-                if self._norm_ws is None:
-                    self._norm_ws = torch.empty(int(nat.lib().sqd_grad_sumsq_parts()) + 1, device=flat.device, dtype=torch.float32)
-                parts, norm = self._norm_ws[:-1], self._norm_ws[-1]
-                nat.check(nat.lib().sqd_grad_sumsq(nat.ptr(flat), self.total, nat.ptr(parts), nat.stream_handle(flat.device)), 'sqd_grad_sumsq')
-            nat.check(nat.lib().sqd_sgd_clip_step_chunked_dev(nat.ptr(self._table), nat.ptr(self._chunks), self._chunks.shape[0], nat.ptr(flat),
-                                                              nat.ptr(parts), nat.ptr(norm), nat.ptr(self._hyper_dev),
-                                                              nat.stream_handle(params[0].device)), 'sqd_sgd_clip_step_chunked_dev')
+                parts, norm = self._sumsq(flat)
+            if self.ema_on:
+                _, derived = self._begin(adam=False)
+                nat.check(nat.lib().sqd_sgd_clip_step_chunked_ema(nat.ptr(self._table), nat.ptr(self._chunks), self._chunks.shape[0],
+                                                                  nat.ptr(flat), nat.ptr(parts), nat.ptr(norm), nat.ptr(self._hyper_dev),
+                                                                  nat.ptr(derived), nat.stream_handle(params[0].device)),
+                          'sqd_sgd_clip_step_chunked_ema')
+            else:
+                nat.check(nat.lib().sqd_sgd_clip_step_chunked_dev(nat.ptr(self._table), nat.ptr(self._chunks), self._chunks.shape[0],
+                                                                  nat.ptr(flat), nat.ptr(parts), nat.ptr(norm), nat.ptr(self._hyper_dev),
+                                                                  nat.stream_handle(params[0].device)), 'sqd_sgd_clip_step_chunked_dev')
         elif max_norm > 0 and flat is not None:
-            # the norm of the flat gradient buffer: partial sums of squares by one small launch, finished (fixed order) inside the step
-            if self._norm_ws is None:
-                self._norm_ws = torch.empty(int(nat.lib().sqd_grad_sumsq_parts()) + 1, device=flat.device, dtype=torch.float32)
-            parts, norm = self._norm_ws[:-1], self._norm_ws[-1]
-            nat.check(nat.lib().sqd_grad_sumsq(nat.ptr(flat), self.total, nat.ptr(parts), nat.stream_handle(flat.device)), 'sqd_grad_sumsq')
+            parts, norm = self._sumsq(flat)
             nat.check(nat.lib().sqd_sgd_clip_step_chunked(nat.ptr(self._table), nat.ptr(self._chunks), self._chunks.shape[0], nat.ptr(flat),
                                                           nat.ptr(parts), nat.ptr(norm), max_norm, self.lr, self.momentum, self.weight_decay,
                                                           nat.stream_handle(params[0].device)), 'sqd_sgd_clip_step_chunked')
@@ -638,14 +835,14 @@ class FusedClipSGD(torch.optim.Optimizer):
         self.last_norm = norm
         return norm if closure is None else loss
 
-    def norm_value(self):
-        """The latest step's total gradient norm as a Python float (one host sync), or None before the first clipped step."""
-        return None if self.last_norm is None else float(self.last_norm)
-
     def state_dict(self):
+        """With the EMA on, also the averaged weights and the count of averaged steps (read from the device: one sync, at save time)."""
         g = self.param_groups[0]
-        return {'momentum_flat': self.momentum_flat.clone(), 'lr': g['lr'], 'momentum': g['momentum'], 'weight_decay': g['weight_decay'],
-                'max_norm': g['max_norm'], 'initial_lr': g.get('initial_lr')}
+        sd = {'momentum_flat': self.momentum_flat.clone(), 'lr': g['lr'], 'momentum': g['momentum'], 'weight_decay': g['weight_decay'],
+              'max_norm': g['max_norm'], 'initial_lr': g.get('initial_lr')}
+        if self.ema_on:
+            sd.update(self._ema_state(), n=self.step_counts()[1])
+        return sd
 
     def load_state_dict(self, sd):
         self.momentum_flat.copy_(sd['momentum_flat'].to(self.momentum_flat.device))
@@ -655,6 +852,126 @@ class FusedClipSGD(torch.optim.Optimizer):
                 g[k] = float(sd[k])
         if sd.get('initial_lr') is not None:
             g['initial_lr'] = float(sd['initial_lr'])
+        if self.ema_on:
+            self._load_ema_state(sd)
+            self._set_step_counts(0, sd.get('n', 0))
+
+
+class FusedClipAdamW(FusedClipBase):
+    """``torch.nn.utils.clip_grad_norm_(params, max_norm)`` + ``torch.optim.AdamW(params, lr, betas, eps, weight_decay).step()``
+    (non-amsgrad, decoupled decay) and, with ``ema_decay > 0``, the weight EMA of ``FusedClipBase``, as the launches of ``FusedClipSGD``:
+    the sum of squares of the flat gradient, a one-thread begin launch and ONE launch over all parameter tensors (csrc/optim.hip,
+    ``sqd_adamw_clip_step_chunked``).  Per element, in torch's order: ``g = grad * coef; p -= lr wd p; m = b1 m + (1 - b1) g;
+    v = b2 v + (1 - b2) g g; p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)``.
+
+    A ``torch.optim.Optimizer`` with ONE parameter group: ``param_groups[0]`` carries ``lr`` / ``betas`` / ``eps`` / ``weight_decay`` /
+    ``max_norm`` / ``ema_decay`` / ``ema_warmup`` and drives every step, so ``StepLR`` and warm-up schedules work.  The hyper-parameters are
+    ALWAYS read from a device table (there is no launch-argument form: one form, one set of bits), rewritten only when a value changed;
+    the step count of the bias correction lives on the device, so the step is capturable and ``GraphedStep`` / ``cfg.graph_step`` accept
+    it.  ``max_norm > 0`` clips INSIDE ``step()`` (see ``FusedClipSGD``).  Gradients that are separate tensors are taken by address,
+    their norm by torch's foreach norm.  State: ``state[p]['exp_avg']`` / ``['exp_avg_sq']`` / ``['ema']`` are views of flat buffers."""
+
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=0.0, ema_decay=0.0, ema_warmup=False,
+                 flat_grad=None):
+        betas = (float(betas[0]), float(betas[1]))
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0) or not float(eps) >= 0.0:
+            raise ValueError(f'FusedClipAdamW: betas in [0, 1) and eps >= 0, got {betas!r}, {eps!r}')
+        super().__init__(params, dict(lr=float(lr), betas=betas, eps=float(eps), weight_decay=float(weight_decay), max_norm=float(max_norm),
+                                      ema_decay=float(ema_decay), ema_warmup=bool(ema_warmup)), flat_grad)
+        self.exp_avg_flat, self._m = self._flat_state('exp_avg')
+        self.exp_avg_sq_flat, self._v = self._flat_state('exp_avg_sq')
+        self.hyper_on_device = True                    # (always: GraphedStep sets and restores the attribute, nothing reads it here)
+
+    betas = property(lambda self: tuple(float(b) for b in self.param_groups[0]['betas']))
+    eps = property(lambda self: self._hyper('eps'))
+
+    def _hyper_values(self):
+        b1, b2 = self.betas
+        return (self.lr, b1, b2, self.eps, self.weight_decay, self.max_norm, self.ema_decay, float(self.ema_warmup))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """One clip + AdamW (+ EMA) step.  Returns the total gradient norm as ``FusedClipSGD.step`` does: a 0-dim DEVICE tensor that the
+        next step overwrites (flat layout), or None without clipping."""
+        from . import _native as nat
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._check_step_allowed()
+        params = self.params
+        dev = params[0].device
+        flat, grads = self._gradients()
+        self._ensure_tables(flat, grads, self._m, self._v)
+        self.refresh_hyper()                           # (writes when a value changed; under capture: raises if it would have to)
+        parts = norm = total_norm = None
+        if self.max_norm > 0:                          # structural: a captured step keeps or lacks the norm launch
+            if flat is not None:
+                parts, norm = self._sumsq(flat)
+            else:
+                norm = total_norm = torch.linalg.vector_norm(torch.stack(torch._foreach_norm(grads)))
+        _, derived = self._begin(adam=True)
+        nat.check(nat.lib().sqd_adamw_clip_step_chunked(nat.ptr(self._table), nat.ptr(self._chunks), self._chunks.shape[0], nat.ptr(flat),
+                                                        nat.ptr(parts), nat.ptr(total_norm), nat.ptr(norm if parts is not None else None),
+                                                        nat.ptr(self._hyper_dev), nat.ptr(derived), int(self.ema_on),
+                                                        nat.stream_handle(dev)), 'sqd_adamw_clip_step_chunked')
+        torch.autograd.graph.increment_version(params)        # (the packed-weight caches key on the version counters)
+        self.last_norm = norm
+        return norm if closure is None else loss
+
+    def state_dict(self):
+        """The moments, the EMA, the hyper-parameters and the device counts ``t`` / ``n`` (one sync to read them, at save time only)."""
+        g = self.param_groups[0]
+        t, n = self.step_counts()
+        sd = {'exp_avg_flat': self.exp_avg_flat.clone(), 'exp_avg_sq_flat': self.exp_avg_sq_flat.clone(), 't': t, 'n': n,
+              'lr': g['lr'], 'betas': tuple(g['betas']), 'eps': g['eps'], 'weight_decay': g['weight_decay'], 'max_norm': g['max_norm'],
+              'initial_lr': g.get('initial_lr')}
+        sd.update(self._ema_state())
+        return sd
+
+    def load_state_dict(self, sd):
+        """``state_dict()`` of this class, or of a ``torch.optim.AdamW`` over the same parameter list (``exp_avg``, ``exp_avg_sq``, ``step``
+        per parameter; its group's lr / betas / eps / weight_decay are taken over, the EMA starts afresh)."""
+        g = self.param_groups[0]
+        if 'state' in sd and 'param_groups' in sd:
+            groups, state = sd['param_groups'], sd['state']
+            ids = [i for grp in groups for i in grp['params']]
+            if len(groups) != 1 or len(ids) != len(self.params):
+                raise ValueError(f'FusedClipAdamW.load_state_dict: a torch optimizer state with {len(groups)} group(s) over {len(ids)} '
+                                 f'parameters, this optimizer has one group over {len(self.params)}')
+            if groups[0].get('amsgrad'):
+                raise ValueError('FusedClipAdamW.load_state_dict: amsgrad state is not supported')
+            steps = set()
+            for i, m, v in zip(ids, self._m, self._v):
+                st = state.get(i)
+                if st is None:                         # (torch creates the state at a parameter's first step)
+                    m.zero_(); v.zero_(); steps.add(0)
+                    continue
+                if st['exp_avg'].numel() != m.numel():
+                    raise ValueError(f'FusedClipAdamW.load_state_dict: parameter {i} has {st["exp_avg"].numel()} elements in the state, '
+                                     f'{m.numel()} here')
+                m.copy_(st['exp_avg'].reshape(-1).to(m.device)); v.copy_(st['exp_avg_sq'].reshape(-1).to(v.device))
+                steps.add(int(float(st['step'])))
+            if len(steps) != 1:
+                raise ValueError(f'FusedClipAdamW.load_state_dict: the parameters are at different steps {sorted(steps)} (one count here)')
+            grp = groups[0]
+            g['lr'], g['betas'], g['eps'] = float(grp['lr']), tuple(float(b) for b in grp['betas']), float(grp['eps'])
+            g['weight_decay'] = float(grp['weight_decay'])
+            if grp.get('initial_lr') is not None:
+                g['initial_lr'] = float(grp['initial_lr'])
+            self._set_step_counts(steps.pop(), 0)
+            return
+        self.exp_avg_flat.copy_(sd['exp_avg_flat'].to(self.exp_avg_flat.device))
+        self.exp_avg_sq_flat.copy_(sd['exp_avg_sq_flat'].to(self.exp_avg_sq_flat.device))
+        for k in ('lr', 'eps', 'weight_decay', 'max_norm'):
+            if sd.get(k) is not None:
+                g[k] = float(sd[k])
+        if sd.get('betas') is not None:
+            g['betas'] = tuple(float(b) for b in sd['betas'])
+        if sd.get('initial_lr') is not None:
+            g['initial_lr'] = float(sd['initial_lr'])
+        self._load_ema_state(sd)
+        self._set_step_counts(sd.get('t', 0), sd.get('n', 0))
 
 
 SPARSE_CAP_MIN = 64
@@ -710,9 +1027,9 @@ class GraphedStep:
     the latest step's unclipped gradients.  One process only: a process group with more than one rank is refused."""
 
     def __init__(self, model, optimizer, cfg=None, max_graphs=4):
-        if not isinstance(optimizer, FusedClipSGD):
-            raise ValueError(f'GraphedStep: the optimizer must be a FusedClipSGD (its step is capturable and reads its hyper-parameters '
-                             f'from device memory), got {type(optimizer).__name__}')
+        if not isinstance(optimizer, FusedClipBase):
+            raise ValueError(f'GraphedStep: the optimizer must be a FusedClipSGD or a FusedClipAdamW (their steps are capturable and read '
+                             f'their hyper-parameters and step counts from device memory), got {type(optimizer).__name__}')
         d = _dist()
         if d is not None and d.get_world_size() > 1:
             raise ValueError(f'GraphedStep: a process group with {d.get_world_size()} ranks -- the captured gradient exchange is not '
@@ -934,7 +1251,7 @@ class GraphedStep:
         g.replay()
         self.replays += 1
         params = self.optimizer.params
-        torch.autograd.graph.increment_version(params)        # the Python a replay skipped (FusedClipSGD.step)
+        torch.autograd.graph.increment_version(params)        # the Python a replay skipped (the optimizer's step())
         if self._live != sig:
             for p, gr in zip(params, grads):
                 p.grad = gr
@@ -962,10 +1279,20 @@ def make_train_step(cfg, state_dict, image, rank, world, dist, gt_seed=1, force_
     model.load_state_dict(state_dict)
     model = model.to(image.device).train()
     params = [p for p in model.parameters() if p.requires_grad]
+    kind = str(getattr(cfg, 'optimizer', 'sgd')).lower()
+    if kind not in ('sgd', 'adamw'):
+        raise ValueError(f"make_train_step: cfg.optimizer must be 'sgd' or 'adamw', got {getattr(cfg, 'optimizer')!r}")
+    ema = dict(ema_decay=float(getattr(cfg, 'ema_decay', 0.0)), ema_warmup=bool(getattr(cfg, 'ema_warmup', False)))
     if fused_optimizer:
         base = find_base(model)
-        opt = FusedClipSGD(params, lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay, max_norm=cfg.grad_norm,
-                           flat_grad=lambda: base.last_grad_flat)
+        if kind == 'adamw':
+            opt = FusedClipAdamW(params, lr=cfg.lr, weight_decay=cfg.weight_decay, max_norm=cfg.grad_norm,
+                                 flat_grad=lambda: base.last_grad_flat, **ema)
+        else:
+            opt = FusedClipSGD(params, lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay, max_norm=cfg.grad_norm,
+                               flat_grad=lambda: base.last_grad_flat, **ema)
+    elif kind == 'adamw':
+        opt = torch.optim.AdamW(params, lr=cfg.lr, weight_decay=cfg.weight_decay)
     else:
         opt = torch.optim.SGD(params, lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay)
     gt_cpu = synthetic.make_gt(image.shape[0], cfg.anchors, cfg.input_size, cfg.num_classes, seed=gt_seed + rank)
@@ -996,8 +1323,11 @@ def make_train_step(cfg, state_dict, image, rank, world, dist, gt_seed=1, force_
         return gt_cpu, lv.detach().cpu()
 
     net = 'SqueezeDet' if cfg.arch == 'squeezedet' else 'SqueezeDet+'
-    desc = f'{net} KITTI 1248x384 bs={image.shape[0]}/GPU training: fwd + multi-task loss + bwd + clip(5.0) + SGD' + (
-        ' (clip + SGD: one fused launch)' if fused_optimizer else '')
+    oname = 'SGD' if kind == 'sgd' else 'AdamW'
+    if fused_optimizer and ema['ema_decay'] > 0:
+        oname += ' + EMA'
+    desc = f'{net} KITTI 1248x384 bs={image.shape[0]}/GPU training: fwd + multi-task loss + bwd + clip(5.0) + {oname}' + (
+        f' (clip + {oname}: one fused launch)' if fused_optimizer else '')
     if ex is not None:
         desc += f' + RCCL gradient all-reduce over {world} GPU(s) in 3 buckets overlapped with backward'
     return step, desc, probe
