@@ -5,7 +5,8 @@ usage: python tools/device_asm_diff.py OLD_CSRC NEW_CSRC [--work DIR] [--jobs N]
 Every file of the Makefile's SRCS is compiled on both sides with the flags the Makefile gives that file, plus
 --cuda-device-only -S.  The listings are split by kernel symbol; basic-block label numbers (BB<n>_ -> BB_), comments and
 whitespace are normalised; then the kernel symbol sets, each kernel's instruction text and each kernel's .amdhsa_kernel
-descriptor (registers, LDS, scratch) are compared.  Prints one line per file and every difference; exit status 1 if any
+descriptor (registers, LDS, scratch) are compared.  Prints one line per file and every difference -- for a kernel that differs also
+its instruction count, its 16-byte vector loads / stores and its VGPR / LDS / scratch figures, before -> after; exit status 1 if any
 kernel differs or exists on one side only (a host-only refactor lists the instantiations it removed on purpose)."""
 import argparse
 import os
@@ -87,6 +88,21 @@ def kernels(path):
     return {k: ('\n'.join(body[k]), '\n'.join(desc[k])) for k in desc}
 
 
+WATCHED = ('global_load_dwordx4', 'global_store_dwordx4', 'flat_load_dwordx4', 'flat_store_dwordx4')
+RESOURCES = ('.amdhsa_next_free_vgpr', '.amdhsa_accum_offset', '.amdhsa_group_segment_fixed_size', '.amdhsa_private_segment_fixed_size')
+
+
+def counts(text):
+    """instructions (labels and directives left out) and the 16-byte vector memory instructions of one kernel's text"""
+    ins = [l.split()[0] for l in text.splitlines() if not l.endswith(':') and not l.startswith('.')]
+    return [len(ins)] + [ins.count(w) for w in WATCHED]
+
+
+def resources(desc):
+    got = dict(l.split()[:2] for l in desc.splitlines() if l.split()[0] in RESOURCES)
+    return [got.get(r, '-') for r in RESOURCES]
+
+
 def demangle(names):
     if not names:
         return []
@@ -123,6 +139,10 @@ def main():
         for tag, ks in (('removed', gone), ('added', added), ('TEXT DIFFERS', text), ('DESCRIPTOR DIFFERS', dsc)):
             for k in demangle(ks):
                 print(f'    {tag}: {k}')
+        for k, name in zip(sorted(set(text) | set(dsc)), demangle(sorted(set(text) | set(dsc)))):
+            o, n = counts(ko[k][0]), counts(kn[k][0])
+            print(f'    counts: {name}: ' + ', '.join(f'{w} {a} -> {b}' for w, a, b in zip(('instructions',) + WATCHED, o, n)) + '; '
+                  + ', '.join(f'{r[8:]} {a} -> {b}' for r, a, b in zip(RESOURCES, resources(ko[k][1]), resources(kn[k][1]))))
         bad += len(gone) + len(added) + len(set(text) | set(dsc))
         total += len(ko)
     print(f'total: {total} kernels before; {bad} removed, added or different')
