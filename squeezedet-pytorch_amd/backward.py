@@ -220,24 +220,38 @@ class BackboneFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads[n] if need else None for n, need in zip(ctx.names, ctx.needs_input_grad[4:]))
 
 
+def _loss_meta(ctx, loss_mod):
+    """ctx.meta = (input_size, num_classes, weights) of the Loss module: what the six loss Functions hand to ops in both passes."""
+    res = loss_mod.resolver
+    ctx.meta = (res.input_size, res.num_classes, (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
+                                                  loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight))
+    return ctx.meta
+
+
+def _coef(g):
+    """g [4,B] arriving at (class, score, bbox, total) -> coef [3,B]: the gradient of `total` reaches all three components."""
+    return (g[:3] + g[3:4]).contiguous()
+
+
+def _mean_outputs(ctx, losses, mean4):
+    """What the three mean Functions return: the 0-dim view of the total's mean, and the per-image vectors for the statistics."""
+    ctx.mark_non_differentiable(losses)
+    ctx.set_materialize_grads(False)   # (no zero-filled gradient tensor for the statistics output: that is a fill launch per step)
+    return mean4[3], losses
+
+
 class LossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, gt, anchors, loss_mod):
-        res = loss_mod.resolver
-        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
-                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
-        losses, nobj = ops.loss_fns(res.num_classes)[0](pred.detach(), gt, anchors, res.input_size, res.num_classes, weights)
+        meta = _loss_meta(ctx, loss_mod)
+        losses, nobj = ops.loss_fns(meta[1])[0](pred.detach(), gt, anchors, *meta)
         ctx.save_for_backward(pred.detach(), gt, anchors, nobj)
-        ctx.meta = (res.input_size, res.num_classes, weights)
         return losses                      # [4,B] = (class, score, bbox, total)
 
     @staticmethod
     def backward(ctx, g):
         pred, gt, anchors, nobj = ctx.saved_tensors
-        input_size, num_classes, weights = ctx.meta
-        coef = (g[:3] + g[3:4]).contiguous()       # gradient of `total` reaches all three components
-        dpred = ops.loss_fns(num_classes)[2](pred, gt, anchors, nobj, coef, input_size, num_classes, weights)
-        return dpred, None, None, None
+        return ops.loss_fns(ctx.meta[1])[2](pred, gt, anchors, nobj, _coef(g), *ctx.meta), None, None, None
 
 
 class LossMeanFn(torch.autograd.Function):
@@ -247,21 +261,15 @@ class LossMeanFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, gt, anchors, loss_mod):
-        res = loss_mod.resolver
-        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
-                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
-        losses, nobj, mean4 = ops.loss_fns(res.num_classes)[1](pred.detach(), gt, anchors, res.input_size, res.num_classes, weights)
+        meta = _loss_meta(ctx, loss_mod)
+        losses, nobj, mean4 = ops.loss_fns(meta[1])[1](pred.detach(), gt, anchors, *meta)
         ctx.save_for_backward(pred.detach(), gt, anchors, nobj)
-        ctx.meta = (res.input_size, res.num_classes, weights)
-        ctx.mark_non_differentiable(losses)
-        ctx.set_materialize_grads(False)   # (no zero-filled gradient tensor for the statistics output: that is a fill launch per step)
-        return mean4[3], losses            # (0-dim view of the total's mean; the per-image vectors for the statistics)
+        return _mean_outputs(ctx, losses, mean4)
 
     @staticmethod
     def backward(ctx, g, _gl):
         pred, gt, anchors, nobj = ctx.saved_tensors
-        input_size, num_classes, weights = ctx.meta
-        return ops.loss_fns(num_classes)[3](pred, gt, anchors, nobj, g.reshape(1), input_size, num_classes, weights), None, None, None
+        return ops.loss_fns(ctx.meta[1])[3](pred, gt, anchors, nobj, g.reshape(1), *ctx.meta), None, None, None
 
 
 class LossSparseFn(torch.autograd.Function):
@@ -269,20 +277,14 @@ class LossSparseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, anchors, loss_mod, *sgt):
-        res = loss_mod.resolver
-        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
-                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
-        losses, nobj = ops.loss_sparse_fwd(pred.detach(), ops.SparseGT(*sgt), anchors, res.input_size, res.num_classes, weights)
+        losses, nobj = ops.loss_sparse_fwd(pred.detach(), ops.SparseGT(*sgt), anchors, *_loss_meta(ctx, loss_mod))
         ctx.save_for_backward(pred.detach(), anchors, nobj, *sgt)
-        ctx.meta = (res.input_size, res.num_classes, weights)
         return losses                      # [4,B] = (class, score, bbox, total)
 
     @staticmethod
     def backward(ctx, g):
         pred, anchors, nobj, *sgt = ctx.saved_tensors
-        input_size, num_classes, weights = ctx.meta
-        coef = (g[:3] + g[3:4]).contiguous()       # gradient of `total` reaches all three components
-        dpred = ops.loss_sparse_bwd(pred, ops.SparseGT(*sgt), anchors, nobj, coef, input_size, num_classes, weights)
+        dpred = ops.loss_sparse_bwd(pred, ops.SparseGT(*sgt), anchors, nobj, _coef(g), *ctx.meta)
         return (dpred, None, None) + (None,) * len(sgt)
 
 
@@ -291,21 +293,14 @@ class LossSparseMeanFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, anchors, loss_mod, *sgt):
-        res = loss_mod.resolver
-        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
-                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
-        losses, nobj, mean4 = ops.loss_sparse_mean_fwd(pred.detach(), ops.SparseGT(*sgt), anchors, res.input_size, res.num_classes, weights)
+        losses, nobj, mean4 = ops.loss_sparse_mean_fwd(pred.detach(), ops.SparseGT(*sgt), anchors, *_loss_meta(ctx, loss_mod))
         ctx.save_for_backward(pred.detach(), anchors, nobj, *sgt)
-        ctx.meta = (res.input_size, res.num_classes, weights)
-        ctx.mark_non_differentiable(losses)
-        ctx.set_materialize_grads(False)
-        return mean4[3], losses
+        return _mean_outputs(ctx, losses, mean4)
 
     @staticmethod
     def backward(ctx, g, _gl):
         pred, anchors, nobj, *sgt = ctx.saved_tensors
-        input_size, num_classes, weights = ctx.meta
-        dpred = ops.loss_sparse_mean_bwd(pred, ops.SparseGT(*sgt), anchors, nobj, g.reshape(1), input_size, num_classes, weights)
+        dpred = ops.loss_sparse_mean_bwd(pred, ops.SparseGT(*sgt), anchors, nobj, g.reshape(1), *ctx.meta)
         return (dpred, None, None) + (None,) * len(sgt)
 
 
@@ -315,20 +310,14 @@ class LossMaskedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, anchors, loss_mod, ignore, *sgt):
-        res = loss_mod.resolver
-        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
-                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
-        losses, counts = ops.loss_masked_fwd(pred.detach(), ops.SparseGT(*sgt), ignore, anchors, res.input_size, res.num_classes, weights)
+        losses, counts = ops.loss_masked_fwd(pred.detach(), ops.SparseGT(*sgt), ignore, anchors, *_loss_meta(ctx, loss_mod))
         ctx.save_for_backward(pred.detach(), anchors, counts, ignore, *sgt)
-        ctx.meta = (res.input_size, res.num_classes, weights)
         return losses                      # [4,B] = (class, score, bbox, total)
 
     @staticmethod
     def backward(ctx, g):
         pred, anchors, counts, ignore, *sgt = ctx.saved_tensors
-        input_size, num_classes, weights = ctx.meta
-        coef = (g[:3] + g[3:4]).contiguous()       # gradient of `total` reaches all three components
-        dpred = ops.loss_masked_bwd(pred, ops.SparseGT(*sgt), ignore, anchors, counts, coef, input_size, num_classes, weights)
+        dpred = ops.loss_masked_bwd(pred, ops.SparseGT(*sgt), ignore, anchors, counts, _coef(g), *ctx.meta)
         return (dpred, None, None, None) + (None,) * len(sgt)
 
 
@@ -337,20 +326,12 @@ class LossMaskedMeanFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, anchors, loss_mod, ignore, *sgt):
-        res = loss_mod.resolver
-        weights = (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
-                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight)
-        losses, counts, mean4 = ops.loss_masked_mean_fwd(pred.detach(), ops.SparseGT(*sgt), ignore, anchors, res.input_size,
-                                                         res.num_classes, weights)
+        losses, counts, mean4 = ops.loss_masked_mean_fwd(pred.detach(), ops.SparseGT(*sgt), ignore, anchors, *_loss_meta(ctx, loss_mod))
         ctx.save_for_backward(pred.detach(), anchors, counts, ignore, *sgt)
-        ctx.meta = (res.input_size, res.num_classes, weights)
-        ctx.mark_non_differentiable(losses)
-        ctx.set_materialize_grads(False)
-        return mean4[3], losses
+        return _mean_outputs(ctx, losses, mean4)
 
     @staticmethod
     def backward(ctx, g, _gl):
         pred, anchors, counts, ignore, *sgt = ctx.saved_tensors
-        input_size, num_classes, weights = ctx.meta
-        dpred = ops.loss_masked_mean_bwd(pred, ops.SparseGT(*sgt), ignore, anchors, counts, g.reshape(1), input_size, num_classes, weights)
+        dpred = ops.loss_masked_mean_bwd(pred, ops.SparseGT(*sgt), ignore, anchors, counts, g.reshape(1), *ctx.meta)
         return (dpred, None, None, None) + (None,) * len(sgt)

@@ -96,11 +96,39 @@ __device__ __forceinline__ void anchor_terms(const LossArgs& a, const float* __r
   anchor_geom(a, p, g, anc, t);
 }
 
+// The anchors [lo, hi) of an image that block blk of LOSS_NPART sums.
+__device__ __forceinline__ void loss_slice(int A, int blk, int& lo, int& hi) {
+  const int per = (A + LOSS_NPART - 1) / LOSS_NPART;
+  lo = blk * per;
+  hi = min(A, lo + per);
+}
+
+// The first stage of every forward: each thread's NS sums meet in a fixed order (wave shuffle tree, then the waves one after the
+// other), so the same operands give the same bits; partial[b][blk][NS] is what the finalize kernels add up.
+template <int NS, int THREADS>
+__device__ __forceinline__ void block_reduce_store(const float (&s)[NS], float* partial, int b, int blk) {
+  __shared__ float red[NS][THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    float v = s[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+    if (lane == 0) red[k][wave] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    float v = 0.f;
+    for (int w = 0; w < THREADS / 64; ++w) v += red[threadIdx.x][w];
+    partial[((long long)b * LOSS_NPART + blk) * NS + threadIdx.x] = v;
+  }
+}
+
 // partial[b][blk][5] = (n_obj, S_class, S_pos, S_neg, S_bbox) over the block's anchors
 __global__ __launch_bounds__(LOSS_THREADS) void loss_partial_kernel(LossArgs a, float* __restrict__ partial) {
   const int b = blockIdx.y, blk = blockIdx.x;
-  const int per = (a.A + LOSS_NPART - 1) / LOSS_NPART;
-  const int lo = blk * per, hi = min(a.A, lo + per);
+  int lo, hi;
+  loss_slice(a.A, blk, lo, hi);
   float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   for (int i = lo + threadIdx.x; i < hi; i += LOSS_THREADS) {
     const long long row = (long long)b * a.A + i;
@@ -112,39 +140,58 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_partial_kernel(LossArgs a, 
     s[3] += (1.f - t.mask) * (t.e * t.e);
     s[4] += t.mask * t.bb;
   }
-  __shared__ float red[5][LOSS_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    float v = s[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    if (lane == 0) red[k][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    float v = 0.f;
-    for (int w = 0; w < LOSS_THREADS / 64; ++w) v += red[threadIdx.x][w];
-    partial[((long long)b * LOSS_NPART + blk) * 5 + threadIdx.x] = v;
-  }
+  block_reduce_store<5, LOSS_THREADS>(s, partial, b, blk);
 }
 
-// losses[4][B] = (class, score = pos+neg, bbox, total); nobj[B].  mean4 (or null): the four batch means, loss.mean() of
-// src/engine/trainer.py:43 without a torch reduction kernel -- ONE block then walks the images (thread t takes b = t, t + 64, ...:
-// a fixed order) and the 64 partial sums meet in a fixed shuffle tree.
-__global__ void loss_finalize_kernel(const float* __restrict__ partial, float* __restrict__ losses, float* __restrict__ nobj,
-                                     int B, int A, float w_class, float w_pos, float w_neg, float w_bbox, float* __restrict__ mean4) {
+// The second stage, one image: its LOSS_NPART partials -> v = (class, score = pos+neg, bbox, total) and the counts the backward
+// takes.  PlainImage: n_obj = 0 gives NaN like the reference.
+struct PlainImage {
+  static __device__ __forceinline__ void losses(const float* partial, int b, int A, float w_class, float w_pos, float w_neg,
+                                                float w_bbox, float (&v)[4], float& n, float&) {
+    float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < LOSS_NPART; ++k)
+      for (int j = 0; j < 5; ++j) s[j] += partial[((long long)b * LOSS_NPART + k) * 5 + j];
+    n = s[0];
+    const float cls = w_class * s[1] / n, pos = w_pos * s[2] / n, neg = w_neg * s[3] / ((float)A - n), bbx = w_bbox * s[4] / n;
+    v[0] = cls; v[1] = pos + neg; v[2] = bbx; v[3] = cls + pos + neg + bbx;     // same association as the reference (:166)
+  }
+  static __device__ __forceinline__ void store_counts(float* nobj, int, int b, float n, float) { nobj[b] = n; }      // nobj [B]
+};
+
+// MaskedImage: partial [B][LOSS_NPART][6] with n_neg = A - n_obj - n_ign and the zero-denominator conventions: class, pos and bbox
+// are 0 where n_obj = 0, neg is 0 where n_neg = 0.  With n_ign = 0 and n_obj > 0 every operation is PlainImage's, in its order: the
+// same bits.
+struct MaskedImage {
+  static __device__ __forceinline__ void losses(const float* partial, int b, int A, float w_class, float w_pos, float w_neg,
+                                                float w_bbox, float (&v)[4], float& n, float& nneg) {
+    float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < LOSS_NPART; ++k)
+      for (int j = 0; j < 6; ++j) s[j] += partial[((long long)b * LOSS_NPART + k) * 6 + j];
+    n = s[0];
+    nneg = (float)A - n - s[5];
+    const float cls = n > 0.f ? w_class * s[1] / n : 0.f, pos = n > 0.f ? w_pos * s[2] / n : 0.f;
+    const float neg = nneg > 0.f ? w_neg * s[3] / nneg : 0.f, bbx = n > 0.f ? w_bbox * s[4] / n : 0.f;
+    v[0] = cls; v[1] = pos + neg; v[2] = bbx; v[3] = cls + pos + neg + bbx;
+  }
+  static __device__ __forceinline__ void store_counts(float* counts, int B, int b, float n, float nneg) {       // counts [2][B]
+    counts[b] = n; counts[B + b] = nneg;
+  }
+};
+
+// losses[4][B] and the image rule's counts.  mean4 (or null): the four batch means, loss.mean() of src/engine/trainer.py:43 without
+// a torch reduction kernel -- ONE block then walks the images (thread t takes b = t, t + 64, ...: a fixed order) and the 64 partial
+// sums meet in a fixed shuffle tree.  Without mean4: one thread per image.  Both forms run the same per-image body, so the plain and
+// the mean forward give the same per-image bits.
+template <class Image>
+__device__ __forceinline__ void finalize_walk(const float* partial, float* losses, float* counts, int B, int A, float w_class,
+                                              float w_pos, float w_neg, float w_bbox, float* mean4) {
   if (mean4) {
     float m[4] = {0.f, 0.f, 0.f, 0.f};
     for (int b = threadIdx.x; b < B; b += 64) {
-      float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int k = 0; k < LOSS_NPART; ++k)
-        for (int j = 0; j < 5; ++j) s[j] += partial[((long long)b * LOSS_NPART + k) * 5 + j];
-      const float n = s[0];
-      const float cls = w_class * s[1] / n, pos = w_pos * s[2] / n, neg = w_neg * s[3] / ((float)A - n), bbx = w_bbox * s[4] / n;
-      const float v[4] = {cls, pos + neg, bbx, cls + pos + neg + bbx};
+      float v[4], n, nneg;
+      Image::losses(partial, b, A, w_class, w_pos, w_neg, w_bbox, v, n, nneg);
       for (int j = 0; j < 4; ++j) { losses[j * B + b] = v[j]; m[j] += v[j]; }
-      nobj[b] = n;
+      Image::store_counts(counts, B, b, n, nneg);
     }
     for (int j = 0; j < 4; ++j) {
       float v = m[j];
@@ -155,19 +202,23 @@ __global__ void loss_finalize_kernel(const float* __restrict__ partial, float* _
   }
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int k = 0; k < LOSS_NPART; ++k)
-    for (int j = 0; j < 5; ++j) s[j] += partial[((long long)b * LOSS_NPART + k) * 5 + j];
-  const float n = s[0];
-  const float cls = w_class * s[1] / n;
-  const float pos = w_pos * s[2] / n;
-  const float neg = w_neg * s[3] / ((float)A - n);
-  const float bbx = w_bbox * s[4] / n;
-  losses[0 * B + b] = cls;
-  losses[1 * B + b] = pos + neg;
-  losses[2 * B + b] = bbx;
-  losses[3 * B + b] = cls + pos + neg + bbx;     // same association as the reference (:166)
-  nobj[b] = n;
+  float v[4], n, nneg;
+  Image::losses(partial, b, A, w_class, w_pos, w_neg, w_bbox, v, n, nneg);
+  for (int j = 0; j < 4; ++j) losses[j * B + b] = v[j];
+  Image::store_counts(counts, B, b, n, nneg);
+}
+
+__global__ void loss_finalize_kernel(const float* __restrict__ partial, float* __restrict__ losses, float* __restrict__ nobj,
+                                     int B, int A, float w_class, float w_pos, float w_neg, float w_bbox, float* __restrict__ mean4) {
+  finalize_walk<PlainImage>(partial, losses, nobj, B, A, w_class, w_pos, w_neg, w_bbox, mean4);
+}
+
+// upstream gradients of image b's (class, score, bbox): per image and component (coef [3][B]), or (gmean: d / d mean(total)) the
+// same gmean[0] / B for all
+struct Upstream { float uc, us, ub; };
+__device__ __forceinline__ Upstream upstream_grads(const LossArgs& a, const float* coef, const float* gmean, int b) {
+  const float gm = gmean ? gmean[0] / (float)a.B : 0.f;
+  return {gmean ? gm : coef[0 * a.B + b], gmean ? gm : coef[1 * a.B + b], gmean ? gm : coef[2 * a.B + b]};
 }
 
 // d loss / d (conf logit, 4 deltas) of one anchor: the score terms incl. the un-detached IoU path, and the delta regression.
@@ -247,9 +298,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, cons
     AnchorTerms t;
     anchor_terms(a, p, g, a.anchors + 4 * i, t);
     const float n = nobj[b];
-    // upstream gradients: per image and component (coef [3][B]), or (gmean: d / d mean(total)) the same gmean[0] / B for all
-    const float gm = gmean ? gmean[0] / (float)a.B : 0.f;
-    const float uc = gmean ? gm : coef[0 * a.B + b], us = gmean ? gm : coef[1 * a.B + b], ub = gmean ? gm : coef[2 * a.B + b];
+    const Upstream u = upstream_grads(a, coef, gmean, b);
+    const float uc = u.uc, us = u.us, ub = u.ub;
     float* o = dpred + row * (C + 5);
     // class logits: w_c*mask/n * (sum(onehot)*softmax_j - onehot_j)
     const float kc = uc * a.w_class * t.mask / n;
@@ -258,70 +308,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, cons
     anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
     for (int j = 0; j < 5; ++j) o[C + j] = og[j];
   }
-}
-
-static int fill_args(LossArgs& a, const float* pred, const float* gt, const float* anchors, int B, int A, int C,
-                     int input_h, int input_w, float w_class, float w_pos, float w_neg, float w_bbox) {
-  SQD_CHECK_ARG(pred && gt && anchors && B > 0 && A > 0 && C >= 1 && C <= LOSS_MAX_CLASSES);
-  a.pred = pred; a.gt = gt; a.anchors = anchors; a.B = B; a.A = A; a.C = C;
-  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
-  a.w_class = w_class; a.w_pos = w_pos; a.w_neg = w_neg; a.w_bbox = w_bbox;
-  return SQD_OK;
-}
-
-// workspace: float[B * 16 * 5]; losses: float[4][B] = (class, score, bbox, total); nobj: float[B]
-extern "C" int sqd_loss_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses,
-                            float* nobj, int B, int A, int num_classes, int input_h, int input_w, float w_class,
-                            float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a;
-  if (int rc = fill_args(a, pred, gt, anchors, B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(workspace && losses && nobj);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(loss_partial_kernel, dim3(LOSS_NPART, (unsigned)B), dim3(LOSS_THREADS), 0, s, a, workspace);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3((unsigned)sqd_cdiv(B, 64)), dim3(64), 0, s, workspace, losses, nobj, B, A,
-                     w_class, w_pos, w_neg, w_bbox, (float*)nullptr);
-  return sqd_launch_status();
-}
-
-// The same + mean4 [4] = the batch means of (class, score, bbox, total): `loss.mean()` of the training step
-// (src/engine/trainer.py:43) computed by the finalize launch itself.
-extern "C" int sqd_loss_mean_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses,
-                                 float* nobj, float* mean4, int B, int A, int num_classes, int input_h, int input_w, float w_class,
-                                 float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a;
-  if (int rc = fill_args(a, pred, gt, anchors, B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(workspace && losses && nobj && mean4);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(loss_partial_kernel, dim3(LOSS_NPART, (unsigned)B), dim3(LOSS_THREADS), 0, s, a, workspace);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, losses, nobj, B, A, w_class, w_pos, w_neg, w_bbox, mean4);
-  return sqd_launch_status();
-}
-
-// coef: float[3][B] upstream gradients of (class, score, bbox) per image (total's gradient already added to each)
-extern "C" int sqd_loss_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* coef,
-                            float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class,
-                            float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a;
-  if (int rc = fill_args(a, pred, gt, anchors, B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(nobj && coef && dpred);
-  const long long total = (long long)B * A;
-  const int blocks = (int)((total + LOSS_THREADS - 1) / LOSS_THREADS);
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, a, nobj, coef, dpred, (const float*)nullptr);
-  return sqd_launch_status();
-}
-
-// Backward of mean(total): gmean = DEVICE float, the gradient arriving at the mean (1 for `loss.mean().backward()`); every image's
-// three components get gmean / B.
-extern "C" int sqd_loss_mean_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* gmean,
-                                 float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class,
-                                 float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a;
-  if (int rc = fill_args(a, pred, gt, anchors, B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(nobj && gmean && dpred);
-  const long long total = (long long)B * A;
-  const int blocks = (int)((total + LOSS_THREADS - 1) / LOSS_THREADS);
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, a, nobj, (const float*)nullptr, dpred, gmean);
-  return sqd_launch_status();
 }
 
 // ---- many-class loss: 1 <= num_classes <= 256 = 16 lanes x 16 registers (many_class.h) ------------------------------------------------
@@ -333,8 +319,8 @@ extern "C" int sqd_loss_mean_bwd(const float* pred, const float* gt, const float
 template <int R>
 __global__ __launch_bounds__(MC_THREADS) void loss_many_partial_kernel(LossArgs a, float* __restrict__ partial) {
   const int b = blockIdx.y, blk = blockIdx.x, C = a.C;
-  const int per = (a.A + LOSS_NPART - 1) / LOSS_NPART;
-  const int lo = blk * per, hi = min(a.A, lo + per);
+  int lo, hi;
+  loss_slice(a.A, blk, lo, hi);
   const int j = threadIdx.x & (MC_LANES - 1), grp = threadIdx.x / MC_LANES;
   float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   for (int i = lo + grp; i < hi; i += MC_GROUPS) {            // (group-uniform)
@@ -361,24 +347,26 @@ __global__ __launch_bounds__(MC_THREADS) void loss_many_partial_kernel(LossArgs 
       s[4] += t.mask * t.bb;
     }
   }
-  __shared__ float red[5][MC_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    float v = s[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    if (lane == 0) red[k][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    float v = 0.f;
-    for (int w = 0; w < MC_THREADS / 64; ++w) v += red[threadIdx.x][w];
-    partial[((long long)b * LOSS_NPART + blk) * 5 + threadIdx.x] = v;
-  }
+  block_reduce_store<5, MC_THREADS>(s, partial, b, blk);
 }
 
-// the dpred row is written by its group: lane j stores classes j, j + 16, ...; lanes 0..4 store the confidence and the four deltas
+// A positive dpred row is written by its 16-lane group: lane j stores classes c = j, j + 16, ... as
+// kc * (sum(onehot) * softmax_c - onehot_c), onehot(r, c) being the row's one-hot at c = j + 16 r (a register of the dense gt row,
+// or a comparison with the sparse class id); lanes 0..4 store the confidence and the four deltas, geom_grad(og) being the kernel's
+// anchor_geom_grad call (every lane evaluates it, as it does anchor_geom).
+template <int R, class OneHot, class GeomGrad>
+__device__ __forceinline__ void store_positive_row(float* o, int C, int j, float kc, float ohs, const float (&e)[R], float sum,
+                                                   OneHot onehot, GeomGrad geom_grad) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int c = j + MC_LANES * r;
+    if (c < C) o[c] = kc * (ohs * (e[r] / sum) - onehot(r, c));
+  }
+  float og[5];
+  geom_grad(og);
+  if (j < 5) o[C + j] = (j == 0) ? og[0] : (j == 1) ? og[1] : (j == 2) ? og[2] : (j == 3) ? og[3] : og[4];
+}
+
 template <int R>
 __global__ __launch_bounds__(MC_THREADS) void loss_many_bwd_kernel(LossArgs a, const float* __restrict__ nobj,
                                                                    const float* __restrict__ coef, float* __restrict__ dpred,
@@ -402,91 +390,145 @@ __global__ __launch_bounds__(MC_THREADS) void loss_many_bwd_kernel(LossArgs a, c
     AnchorGeom t;
     anchor_geom(a, p, g, a.anchors + 4 * i, t);
     const float n = nobj[b];
-    const float gm = gmean ? gmean[0] / (float)a.B : 0.f;
-    const float uc = gmean ? gm : coef[0 * a.B + b], us = gmean ? gm : coef[1 * a.B + b], ub = gmean ? gm : coef[2 * a.B + b];
-    float* o = dpred + row * (C + 5);
+    const Upstream u = upstream_grads(a, coef, gmean, b);
+    const float uc = u.uc, us = u.us, ub = u.ub;
     // class logits: w_c*mask/n * (sum(onehot)*softmax_c - onehot_c)
-    const float kc = uc * a.w_class * t.mask / n;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int c = j + MC_LANES * r;
-      if (c < C) o[c] = kc * (ohs * (e[r] / sum) - oh[r]);
-    }
-    float og[5];
-    anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
-    if (j < 5) o[C + j] = (j == 0) ? og[0] : (j == 1) ? og[1] : (j == 2) ? og[2] : (j == 3) ? og[3] : og[4];
+    store_positive_row<R>(dpred + row * (C + 5), C, j, uc * a.w_class * t.mask / n, ohs, e, sum,
+                          [&](int r, int) { return oh[r]; },
+                          [&](float (&og)[5]) { anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og); });
   }
 }
 
+// ---- host side of the dense launches ---------------------------------------------------------------------------------------------------
+static void fill_common(LossArgs& a, const float* pred, const float* gt, const float* anchors, int B, int A, int C, int input_h,
+                        int input_w, float w_class, float w_pos, float w_neg, float w_bbox) {
+  a.pred = pred; a.gt = gt; a.anchors = anchors; a.B = B; a.A = A; a.C = C;
+  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
+  a.w_class = w_class; a.w_pos = w_pos; a.w_neg = w_neg; a.w_bbox = w_bbox;
+}
+
+// the <= 16-class kernels: status 1 for anything malformed, a class count past 16 included
+static int fill_args(LossArgs& a, const float* pred, const float* gt, const float* anchors, int B, int A, int C,
+                     int input_h, int input_w, float w_class, float w_pos, float w_neg, float w_bbox) {
+  SQD_CHECK_ARG(pred && gt && anchors && B > 0 && A > 0 && C >= 1 && C <= LOSS_MAX_CLASSES);
+  fill_common(a, pred, gt, anchors, B, A, C, input_h, input_w, w_class, w_pos, w_neg, w_bbox);
+  return SQD_OK;
+}
+
+// the many-class kernels: status 1 for anything malformed, 2 for num_classes > 256
 static int fill_args_many(LossArgs& a, const float* pred, const float* gt, const float* anchors, int B, int A, int C,
                           int input_h, int input_w, float w_class, float w_pos, float w_neg, float w_bbox) {
   SQD_CHECK_ARG(pred && gt && anchors && B > 0 && A > 0 && C >= 1);
   if (C > SQD_MANY_MAX_CLASSES) return SQD_ERR_UNSUPPORTED;
-  a.pred = pred; a.gt = gt; a.anchors = anchors; a.B = B; a.A = A; a.C = C;
-  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
-  a.w_class = w_class; a.w_pos = w_pos; a.w_neg = w_neg; a.w_bbox = w_bbox;
+  fill_common(a, pred, gt, anchors, B, A, C, input_h, input_w, w_class, w_pos, w_neg, w_bbox);
   return SQD_OK;
 }
 
-static void launch_loss_many_partial(const LossArgs& a, float* workspace, hipStream_t s) {
+// The second launch of every forward.  mean4 (or null) selects the grid: ONE block that also writes the batch means, or a thread per
+// image.
+template <class Kernel>
+static void launch_finalize(Kernel kernel, const LossArgs& a, const float* workspace, float* losses, float* counts, float* mean4,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(kernel, dim3(mean4 ? 1u : (unsigned)sqd_cdiv(a.B, 64)), dim3(64), 0, s, workspace, losses, counts, a.B, a.A,
+                     a.w_class, a.w_pos, a.w_neg, a.w_bbox, mean4);
+}
+
+// Forward on a dense gt; MANY: the 16-lane-group kernels (1 <= num_classes <= 256), else the <= 16-class ones.  workspace:
+// float[B * 16 * 5]; losses: float[4][B] = (class, score, bbox, total); nobj: float[B]; mean (the *_mean_fwd entries): mean4 [4] = the
+// batch means of the four, `loss.mean()` of the training step (src/engine/trainer.py:43) computed by the finalize launch itself.
+template <bool MANY>
+static int loss_dense_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses, float* nobj,
+                          float* mean4, bool mean, int B, int A, int C, int input_h, int input_w, float w_class, float w_pos,
+                          float w_neg, float w_bbox, void* stream) {
+  LossArgs a;
+  if (int rc = (MANY ? fill_args_many : fill_args)(a, pred, gt, anchors, B, A, C, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(workspace && losses && nobj && (mean4 || !mean));
+  hipStream_t s = (hipStream_t)stream;
+  if constexpr (MANY) {
 #define CALL(R) hipLaunchKernelGGL(loss_many_partial_kernel<R>, dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), 0, s, a, workspace)
-  MC_DISPATCH(a.C, CALL);
+    MC_DISPATCH(a.C, CALL);
 #undef CALL
+  } else {
+    hipLaunchKernelGGL(loss_partial_kernel, dim3(LOSS_NPART, (unsigned)B), dim3(LOSS_THREADS), 0, s, a, workspace);
+  }
+  launch_finalize(loss_finalize_kernel, a, workspace, losses, nobj, mean4, s);
+  return sqd_launch_status();
 }
 
-static void launch_loss_many_bwd(const LossArgs& a, const float* nobj, const float* coef, float* dpred, const float* gmean, hipStream_t s) {
-  const long long blocks64 = ((long long)a.B * a.A + MC_GROUPS - 1) / MC_GROUPS;
-  const unsigned blocks = (unsigned)(blocks64 < (1 << 20) ? blocks64 : (1 << 20));
+// Backward on a dense gt, exactly one of coef / gmean.  coef: float[3][B] upstream gradients of (class, score, bbox) per image
+// (total's gradient already added to each).  gmean (backward of mean(total)): a DEVICE float, the gradient arriving at the mean (1 for
+// `loss.mean().backward()`); every image's three components get gmean / B.
+template <bool MANY>
+static int loss_dense_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* coef,
+                          const float* gmean, float* dpred, int B, int A, int C, int input_h, int input_w, float w_class, float w_pos,
+                          float w_neg, float w_bbox, void* stream) {
+  LossArgs a;
+  if (int rc = (MANY ? fill_args_many : fill_args)(a, pred, gt, anchors, B, A, C, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG(nobj && (coef || gmean) && dpred);
+  hipStream_t s = (hipStream_t)stream;
+  const long long rows = (long long)B * A;
+  if constexpr (MANY) {
+    const long long blocks64 = (rows + MC_GROUPS - 1) / MC_GROUPS;
+    const unsigned blocks = (unsigned)(blocks64 < (1 << 20) ? blocks64 : (1 << 20));
 #define CALL(R) hipLaunchKernelGGL(loss_many_bwd_kernel<R>, dim3(blocks), dim3(MC_THREADS), 0, s, a, nobj, coef, dpred, gmean)
-  MC_DISPATCH(a.C, CALL);
+    MC_DISPATCH(a.C, CALL);
 #undef CALL
+  } else {
+    const int blocks = (int)((rows + LOSS_THREADS - 1) / LOSS_THREADS);
+    hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a, nobj, coef, dpred, gmean);
+  }
+  return sqd_launch_status();
 }
 
-// sqd_loss_fwd / sqd_loss_mean_fwd / sqd_loss_bwd / sqd_loss_mean_bwd for 1 <= num_classes <= 256: same arguments, same workspace
-// (float[B * 16 * 5]).  Status 1 for anything malformed, 2 for num_classes > 256.
+// The sixteen entries: each forwards to its pass and family; what all of them end in, and what the sparse ones begin with.
+#define LOSS_TAIL B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox, stream
+extern "C" int sqd_loss_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses,
+                            float* nobj, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                            float w_pos, float w_neg, float w_bbox, void* stream) {
+  return loss_dense_fwd<false>(pred, gt, anchors, workspace, losses, nobj, nullptr, false, LOSS_TAIL);
+}
+
+extern "C" int sqd_loss_mean_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses,
+                                 float* nobj, float* mean4, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                                 float w_pos, float w_neg, float w_bbox, void* stream) {
+  return loss_dense_fwd<false>(pred, gt, anchors, workspace, losses, nobj, mean4, true, LOSS_TAIL);
+}
+
+extern "C" int sqd_loss_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* coef,
+                            float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                            float w_pos, float w_neg, float w_bbox, void* stream) {
+  return loss_dense_bwd<false>(pred, gt, anchors, nobj, coef, nullptr, dpred, LOSS_TAIL);
+}
+
+extern "C" int sqd_loss_mean_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* gmean,
+                                 float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                                 float w_pos, float w_neg, float w_bbox, void* stream) {
+  return loss_dense_bwd<false>(pred, gt, anchors, nobj, nullptr, gmean, dpred, LOSS_TAIL);
+}
+
+// sqd_loss_fwd / sqd_loss_mean_fwd / sqd_loss_bwd / sqd_loss_mean_bwd for 1 <= num_classes <= 256: same arguments, same workspace.
 extern "C" int sqd_loss_many_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses,
                                  float* nobj, int B, int A, int num_classes, int input_h, int input_w, float w_class,
                                  float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a;
-  if (int rc = fill_args_many(a, pred, gt, anchors, B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(workspace && losses && nobj);
-  hipStream_t s = (hipStream_t)stream;
-  launch_loss_many_partial(a, workspace, s);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3((unsigned)sqd_cdiv(B, 64)), dim3(64), 0, s, workspace, losses, nobj, B, A,
-                     w_class, w_pos, w_neg, w_bbox, (float*)nullptr);
-  return sqd_launch_status();
+  return loss_dense_fwd<true>(pred, gt, anchors, workspace, losses, nobj, nullptr, false, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_many_mean_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses,
                                       float* nobj, float* mean4, int B, int A, int num_classes, int input_h, int input_w, float w_class,
                                       float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a;
-  if (int rc = fill_args_many(a, pred, gt, anchors, B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(workspace && losses && nobj && mean4);
-  hipStream_t s = (hipStream_t)stream;
-  launch_loss_many_partial(a, workspace, s);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, losses, nobj, B, A, w_class, w_pos, w_neg, w_bbox, mean4);
-  return sqd_launch_status();
+  return loss_dense_fwd<true>(pred, gt, anchors, workspace, losses, nobj, mean4, true, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_many_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* coef,
                                  float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class,
                                  float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a;
-  if (int rc = fill_args_many(a, pred, gt, anchors, B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(nobj && coef && dpred);
-  launch_loss_many_bwd(a, nobj, coef, dpred, nullptr, (hipStream_t)stream);
-  return sqd_launch_status();
+  return loss_dense_bwd<true>(pred, gt, anchors, nobj, coef, nullptr, dpred, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_many_mean_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* gmean,
                                       float* dpred, int B, int A, int num_classes, int input_h, int input_w, float w_class,
                                       float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a;
-  if (int rc = fill_args_many(a, pred, gt, anchors, B, A, num_classes, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(nobj && gmean && dpred);
-  launch_loss_many_bwd(a, nobj, nullptr, dpred, gmean, (hipStream_t)stream);
-  return sqd_launch_status();
+  return loss_dense_bwd<true>(pred, gt, anchors, nobj, nullptr, gmean, dpred, LOSS_TAIL);
 }
 
 // ---- sparse ground truth: the positives as a list, 1 <= num_classes <= 256 -----------------------------------------------------------
@@ -545,10 +587,9 @@ template <int R, bool MASKED = false>
 __global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArgs a, SparseArgs<MASKED> sg, float* __restrict__ partial) {
   constexpr int NS = MASKED ? 6 : 5;
   __shared__ unsigned bitmap[LS_BITMAP_WORDS];
-  __shared__ float red[NS][MC_THREADS / 64];
   const int b = blockIdx.y, blk = blockIdx.x, C = a.C, tid = threadIdx.x;
-  const int per = (a.A + LOSS_NPART - 1) / LOSS_NPART;
-  const int lo = blk * per, hi = min(a.A, lo + per);
+  int lo, hi;
+  loss_slice(a.A, blk, lo, hi);
   // 1. mark the slice's positives (integer atomic-or: the result does not depend on the list's order)
   for (int w = tid; w < (hi - lo + 31) / 32; w += MC_THREADS) bitmap[w] = 0u;
   __syncthreads();
@@ -597,60 +638,13 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArg
       s[4] += t.bb;
     }
   }
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    float v = s[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    if (lane == 0) red[k][wave] = v;
-  }
-  __syncthreads();
-  if (tid < NS) {
-    float v = 0.f;
-    for (int w = 0; w < MC_THREADS / 64; ++w) v += red[tid][w];
-    partial[((long long)b * LOSS_NPART + blk) * NS + tid] = v;
-  }
+  block_reduce_store<NS, MC_THREADS>(s, partial, b, blk);
 }
 
-// The masked forward's second stage: loss_finalize_kernel on partial [B][LOSS_NPART][6] with n_neg = A - n_obj - n_ign and the
-// zero-denominator conventions: class, pos and bbox are 0 where n_obj = 0, neg is 0 where n_neg = 0.  counts [2][B] = (n_obj, n_neg).
-// With n_ign = 0 and n_obj > 0 every operation is loss_finalize_kernel's, in its order: the same bits.
-__device__ __forceinline__ void masked_image_losses(const float* __restrict__ partial, int b, int A, float w_class, float w_pos,
-                                                    float w_neg, float w_bbox, float (&v)[4], float& n, float& nneg) {
-  float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int k = 0; k < LOSS_NPART; ++k)
-    for (int j = 0; j < 6; ++j) s[j] += partial[((long long)b * LOSS_NPART + k) * 6 + j];
-  n = s[0];
-  nneg = (float)A - n - s[5];
-  const float cls = n > 0.f ? w_class * s[1] / n : 0.f, pos = n > 0.f ? w_pos * s[2] / n : 0.f;
-  const float neg = nneg > 0.f ? w_neg * s[3] / nneg : 0.f, bbx = n > 0.f ? w_bbox * s[4] / n : 0.f;
-  v[0] = cls; v[1] = pos + neg; v[2] = bbx; v[3] = cls + pos + neg + bbx;
-}
-
+// The masked forward's second stage: counts [2][B] = (n_obj, n_neg).
 __global__ void loss_masked_finalize_kernel(const float* __restrict__ partial, float* __restrict__ losses, float* __restrict__ counts,
                                             int B, int A, float w_class, float w_pos, float w_neg, float w_bbox, float* __restrict__ mean4) {
-  if (mean4) {                                          // ONE block walks the images in loss_finalize_kernel's fixed order
-    float m[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int b = threadIdx.x; b < B; b += 64) {
-      float v[4], n, nneg;
-      masked_image_losses(partial, b, A, w_class, w_pos, w_neg, w_bbox, v, n, nneg);
-      for (int j = 0; j < 4; ++j) { losses[j * B + b] = v[j]; m[j] += v[j]; }
-      counts[b] = n; counts[B + b] = nneg;
-    }
-    for (int j = 0; j < 4; ++j) {
-      float v = m[j];
-      for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-      if (threadIdx.x == 0) mean4[j] = v / (float)B;
-    }
-    return;
-  }
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  float v[4], n, nneg;
-  masked_image_losses(partial, b, A, w_class, w_pos, w_neg, w_bbox, v, n, nneg);
-  for (int j = 0; j < 4; ++j) losses[j * B + b] = v[j];
-  counts[b] = n; counts[B + b] = nneg;
+  finalize_walk<MaskedImage>(partial, losses, counts, B, A, w_class, w_pos, w_neg, w_bbox, mean4);
 }
 
 // One launch writes all of dpred.  Workgroup (x, b) owns rows x * LS_ROWS .. of image b: it looks its rows up in the image's list
@@ -677,8 +671,8 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a,
     if (i >= row0 && i < row0 + nrows) atomicMax(&slot[i - row0], e - beg + 1);      // (distinct by contract; max: defined anyway)
   }
   const float n = nobj[b];
-  const float gm = gmean ? gmean[0] / (float)a.B : 0.f;
-  const float uc = gmean ? gm : coef[0 * a.B + b], us = gmean ? gm : coef[1 * a.B + b], ub = gmean ? gm : coef[2 * a.B + b];
+  const Upstream u = upstream_grads(a, coef, gmean, b);
+  const float uc = u.uc, us = u.us, ub = u.ub;
   // mask = 0 in the dense formulas: the score coefficient, and what the class / delta columns hold (0, or NaN where n_obj = 0)
   // MASKED: the same expressions where their denominator is a count > 0 (so a zero keeps the sign it has there), else 0; for
   // n > 0 the dropped w_pos * 0 / n is an exact zero added in front
@@ -766,105 +760,95 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a,
     const float sum = mc_exp_sum<R>(C, j, m, l, ex);
     AnchorGeom t;
     anchor_geom(a, p, g, a.anchors + 4 * (row0 + r), t);
-    float* orow = o + (long long)r * W;
-    const float kc = uc * a.w_class * t.mask / n;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int c = j + MC_LANES * k;
-      if (c < C) orow[c] = kc * (ohs * (ex[k] / sum) - (c == cls ? 1.f : 0.f));
-    }
-    float og[5];
-    if (MASKED) anchor_geom_grad_nneg(a, t, p + C + 1, g, n, nneg > 0.f ? nneg : 1.f, us, ub, og);      // (mask = 1: w_neg * 0 / n_neg)
-    else anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
-    if (j < 5) orow[C + j] = (j == 0) ? og[0] : (j == 1) ? og[1] : (j == 2) ? og[2] : (j == 3) ? og[3] : og[4];
+    store_positive_row<R>(o + (long long)r * W, C, j, uc * a.w_class * t.mask / n, ohs, ex, sum,
+                          [&](int, int c) { return c == cls ? 1.f : 0.f; },
+                          [&](float (&og)[5]) {
+                            if (MASKED) anchor_geom_grad_nneg(a, t, p + C + 1, g, n, nneg > 0.f ? nneg : 1.f, us, ub, og);      // (mask = 1: w_neg * 0 / n_neg)
+                            else anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
+                          });
   }
 }
 
+// ---- host side of the sparse and the masked launches -----------------------------------------------------------------------------------
+// status 1 for anything malformed (the list pointers may be null when total = 0), 2 for num_classes > 256 or A > 2^20
 static int fill_args_sparse(LossArgs& a, SparseGT& sg, const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
                             const int* class_ids, const int* offsets, const float* anchors, int total, int B, int A, int C,
                             int input_h, int input_w, float w_class, float w_pos, float w_neg, float w_bbox) {
   SQD_CHECK_ARG(pred && anchors && offsets && B > 0 && B <= 65535 && A > 0 && C >= 1 && total >= 0);
   SQD_CHECK_ARG(total == 0 || (anchor_idx && boxes && deltas && class_ids));
   if (C > SQD_MANY_MAX_CLASSES || A > LS_MAX_ANCHORS) return SQD_ERR_UNSUPPORTED;
-  a.pred = pred; a.gt = nullptr; a.anchors = anchors; a.B = B; a.A = A; a.C = C;
-  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
-  a.w_class = w_class; a.w_pos = w_pos; a.w_neg = w_neg; a.w_bbox = w_bbox;
+  fill_common(a, pred, nullptr, anchors, B, A, C, input_h, input_w, w_class, w_pos, w_neg, w_bbox);
   sg.anchor_idx = anchor_idx; sg.boxes = boxes; sg.deltas = deltas; sg.class_ids = class_ids; sg.offsets = offsets; sg.total = total;
   return SQD_OK;
 }
 
-template <bool MASKED = false>
-static void launch_loss_sparse_partial(const LossArgs& a, const SparseGT& sg, float* workspace, hipStream_t s, const unsigned* ignore = nullptr) {
+// Forward on the sparse ground truth (all device pointers).  Workspace (MASKED: float[B * 16 * 6]), losses, mean4 and mean as for
+// loss_dense_fwd; counts: nobj float[B], MASKED: float[2][B] = (n_obj, n_neg), what the backward takes in nobj's place.
+template <bool MASKED>
+static int loss_sparse_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                           const int* offsets, const unsigned* ignore, const float* anchors, float* workspace, float* losses,
+                           float* counts, float* mean4, bool mean, int total, int B, int A, int C, int input_h, int input_w,
+                           float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, C, input_h, input_w,
+                                w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG((ignore || !MASKED) && workspace && losses && counts && (mean4 || !mean));
+  hipStream_t s = (hipStream_t)stream;
   const SparseArgs<MASKED> sa(sg, ignore);
 #define CALL(R) hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_sparse_partial_kernel<R, MASKED>), dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), 0, s, a, sa, workspace)
   MC_DISPATCH(a.C, CALL);
 #undef CALL
+  if constexpr (MASKED) launch_finalize(loss_masked_finalize_kernel, a, workspace, losses, counts, mean4, s);
+  else launch_finalize(loss_finalize_kernel, a, workspace, losses, counts, mean4, s);
+  return sqd_launch_status();
 }
 
-template <bool MASKED = false>
-static void launch_loss_sparse_bwd(const LossArgs& a, const SparseGT& sg, const float* nobj, const float* coef, float* dpred,
-                                   const float* gmean, hipStream_t s, const unsigned* ignore = nullptr) {
+// Backward on the sparse ground truth, exactly one of coef / gmean (loss_dense_bwd); counts: the forward's.
+template <bool MASKED>
+static int loss_sparse_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
+                           const int* offsets, const unsigned* ignore, const float* anchors, const float* counts, const float* coef,
+                           const float* gmean, float* dpred, int total, int B, int A, int C, int input_h, int input_w, float w_class,
+                           float w_pos, float w_neg, float w_bbox, void* stream) {
+  LossArgs a; SparseGT sg;
+  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, C, input_h, input_w,
+                                w_class, w_pos, w_neg, w_bbox)) return rc;
+  SQD_CHECK_ARG((ignore || !MASKED) && counts && (coef || gmean) && dpred);
+  hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)sqd_cdiv(a.A, LS_ROWS), (unsigned)a.B);
   const SparseArgs<MASKED> sa(sg, ignore);
-#define CALL(R) hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_sparse_bwd_kernel<R, MASKED>), grid, dim3(MC_THREADS), 0, s, a, sa, nobj, coef, dpred, gmean)
+#define CALL(R) hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_sparse_bwd_kernel<R, MASKED>), grid, dim3(MC_THREADS), 0, s, a, sa, counts, coef, dpred, gmean)
   MC_DISPATCH(a.C, CALL);
 #undef CALL
+  return sqd_launch_status();
 }
 
-// The four loss launches on the sparse ground truth (all device pointers; the list pointers may be null when total = 0).  Workspace,
-// losses, nobj, mean4, coef, gmean, dpred as for sqd_loss_many_*.  Status 1 for anything malformed, 2 for num_classes > 256 or
-// A > 2^20.
+#define SPARSE_LIST pred, anchor_idx, boxes, deltas, class_ids, offsets
 extern "C" int sqd_loss_sparse_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
                                    const int* offsets, const float* anchors, float* workspace, float* losses, float* nobj, int total,
                                    int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
                                    float w_bbox, void* stream) {
-  LossArgs a; SparseGT sg;
-  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
-                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(workspace && losses && nobj);
-  hipStream_t s = (hipStream_t)stream;
-  launch_loss_sparse_partial(a, sg, workspace, s);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3((unsigned)sqd_cdiv(B, 64)), dim3(64), 0, s, workspace, losses, nobj, B, A,
-                     w_class, w_pos, w_neg, w_bbox, (float*)nullptr);
-  return sqd_launch_status();
+  return loss_sparse_fwd<false>(SPARSE_LIST, nullptr, anchors, workspace, losses, nobj, nullptr, false, total, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_sparse_mean_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
                                         const int* class_ids, const int* offsets, const float* anchors, float* workspace, float* losses,
                                         float* nobj, float* mean4, int total, int B, int A, int num_classes, int input_h, int input_w,
                                         float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a; SparseGT sg;
-  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
-                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(workspace && losses && nobj && mean4);
-  hipStream_t s = (hipStream_t)stream;
-  launch_loss_sparse_partial(a, sg, workspace, s);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, losses, nobj, B, A, w_class, w_pos, w_neg, w_bbox, mean4);
-  return sqd_launch_status();
+  return loss_sparse_fwd<false>(SPARSE_LIST, nullptr, anchors, workspace, losses, nobj, mean4, true, total, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_sparse_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
                                    const int* offsets, const float* anchors, const float* nobj, const float* coef, float* dpred, int total,
                                    int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
                                    float w_bbox, void* stream) {
-  LossArgs a; SparseGT sg;
-  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
-                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(nobj && coef && dpred);
-  launch_loss_sparse_bwd(a, sg, nobj, coef, dpred, nullptr, (hipStream_t)stream);
-  return sqd_launch_status();
+  return loss_sparse_bwd<false>(SPARSE_LIST, nullptr, anchors, nobj, coef, nullptr, dpred, total, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_sparse_mean_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
                                         const int* class_ids, const int* offsets, const float* anchors, const float* nobj,
                                         const float* gmean, float* dpred, int total, int B, int A, int num_classes, int input_h,
                                         int input_w, float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a; SparseGT sg;
-  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
-                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(nobj && gmean && dpred);
-  launch_loss_sparse_bwd(a, sg, nobj, nullptr, dpred, gmean, (hipStream_t)stream);
-  return sqd_launch_status();
+  return loss_sparse_bwd<false>(SPARSE_LIST, nullptr, anchors, nobj, nullptr, gmean, dpred, total, LOSS_TAIL);
 }
 
 // ---- masked sparse loss: ignore regions and object-free images ---------------------------------------------------------------------------
@@ -872,22 +856,13 @@ extern "C" int sqd_loss_sparse_mean_bwd(const float* pred, const int* anchor_idx
 // ign = the anchors whose bit is set and that are no positives (a positive wins over its own bit), n_obj = |pos|, n_ign = |ign|,
 // n_neg = A - n_obj - n_ign.  class, pos-score and bbox are the sparse launches' sums / n_obj, each 0 where n_obj = 0; neg =
 // w_neg * sum over the rows outside pos and ign of sigmoid(conf)^2 / n_neg, 0 where n_neg = 0.  dpred: a positive row as the
-// unmasked launch writes it, a row of ign all zeros, any other row zeros and the confidence gradient with 1 / n_neg.  workspace:
-// float[B * 16 * 6]; counts: float[2][B] = (n_obj, n_neg), what the backward takes where the unmasked one takes nobj.  An all-zero
+// unmasked launch writes it, a row of ign all zeros, any other row zeros and the confidence gradient with 1 / n_neg.  An all-zero
 // bitmap on images that all have positives gives the unmasked launches' bits.
 extern "C" int sqd_loss_masked_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
                                    const int* offsets, const unsigned* ignore, const float* anchors, float* workspace, float* losses,
                                    float* counts, int total, int B, int A, int num_classes, int input_h, int input_w, float w_class,
                                    float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a; SparseGT sg;
-  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
-                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(ignore && workspace && losses && counts);
-  hipStream_t s = (hipStream_t)stream;
-  launch_loss_sparse_partial<true>(a, sg, workspace, s, ignore);
-  hipLaunchKernelGGL(loss_masked_finalize_kernel, dim3((unsigned)sqd_cdiv(B, 64)), dim3(64), 0, s, workspace, losses, counts, B, A,
-                     w_class, w_pos, w_neg, w_bbox, (float*)nullptr);
-  return sqd_launch_status();
+  return loss_sparse_fwd<true>(SPARSE_LIST, ignore, anchors, workspace, losses, counts, nullptr, false, total, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_masked_mean_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
@@ -895,27 +870,14 @@ extern "C" int sqd_loss_masked_mean_fwd(const float* pred, const int* anchor_idx
                                         float* workspace, float* losses, float* counts, float* mean4, int total, int B, int A,
                                         int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
                                         float w_bbox, void* stream) {
-  LossArgs a; SparseGT sg;
-  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
-                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(ignore && workspace && losses && counts && mean4);
-  hipStream_t s = (hipStream_t)stream;
-  launch_loss_sparse_partial<true>(a, sg, workspace, s, ignore);
-  hipLaunchKernelGGL(loss_masked_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, losses, counts, B, A, w_class, w_pos, w_neg,
-                     w_bbox, mean4);
-  return sqd_launch_status();
+  return loss_sparse_fwd<true>(SPARSE_LIST, ignore, anchors, workspace, losses, counts, mean4, true, total, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_masked_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
                                    const int* offsets, const unsigned* ignore, const float* anchors, const float* counts,
                                    const float* coef, float* dpred, int total, int B, int A, int num_classes, int input_h, int input_w,
                                    float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
-  LossArgs a; SparseGT sg;
-  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
-                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(ignore && counts && coef && dpred);
-  launch_loss_sparse_bwd<true>(a, sg, counts, coef, dpred, nullptr, (hipStream_t)stream, ignore);
-  return sqd_launch_status();
+  return loss_sparse_bwd<true>(SPARSE_LIST, ignore, anchors, counts, coef, nullptr, dpred, total, LOSS_TAIL);
 }
 
 extern "C" int sqd_loss_masked_mean_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
@@ -923,10 +885,5 @@ extern "C" int sqd_loss_masked_mean_bwd(const float* pred, const int* anchor_idx
                                         const float* counts, const float* gmean, float* dpred, int total, int B, int A,
                                         int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
                                         float w_bbox, void* stream) {
-  LossArgs a; SparseGT sg;
-  if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, num_classes, input_h,
-                                input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
-  SQD_CHECK_ARG(ignore && counts && gmean && dpred);
-  launch_loss_sparse_bwd<true>(a, sg, counts, nullptr, dpred, gmean, (hipStream_t)stream, ignore);
-  return sqd_launch_status();
+  return loss_sparse_bwd<true>(SPARSE_LIST, ignore, anchors, counts, nullptr, gmean, dpred, total, LOSS_TAIL);
 }

@@ -1162,47 +1162,106 @@ def _check_loss_args(pred, gt, anchors, num_classes):
     return B, A
 
 
-def loss_fwd(pred, gt, anchors, input_size, num_classes, weights):
-    """-> (losses [4,B] = class, score, bbox, total; nobj [B])."""
-    return _loss_fwd('sqd_loss_fwd', pred, gt, anchors, input_size, num_classes, weights)
-
-
-def _loss_fwd(_entry, pred, gt, anchors, input_size, num_classes, weights):
-    B, A = _check_loss_args(pred, gt, anchors, num_classes)
-    pred, gt, anchors = pred.contiguous(), gt.contiguous(), anchors.contiguous()
-    ws = torch.empty(B * 16 * 5, device=pred.device, dtype=torch.float32)
-    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
-    nobj = torch.empty(B, device=pred.device, dtype=torch.float32)
-    br = _Bracket('loss_fwd', f'loss A{A}', 0.0, 4.0 * B * A * (2 * num_classes + 14)) if timing._timer is not None else None
-    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj), B, A,
-                                num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
-                                nat.stream_handle(pred.device))
-    nat.check(rc, _entry)
+def _run_loss_fwd(entry, pred, mid, anchors, lead, B, A, num_classes, input_size, weights, ws_width, count_rows, mean, kind, nbytes):
+    """What the eight forward wrappers do once their operands are checked.  ``mid``: the contiguous tensors between pred and anchors
+    in the entry's argument list (gt, or the five list members, then the bitmap); ``lead``: the integers in front of B (``total`` of
+    the sparse entries); ``ws_width``: partial sums per block (5, masked 6); ``count_rows``: () for nobj [B], (2,) for counts [2,B];
+    ``mean``: the entry also takes mean4 [4]; ``nbytes(B, A, *lead, num_classes)``: the bracket's bytes, asked only when a timer
+    runs.  -> (losses, nobj or counts[, mean4])."""
+    pred, anchors = pred.contiguous(), anchors.contiguous()
+    ws = torch.empty(B * 16 * ws_width, device=pred.device, dtype=torch.float32)
+    out = [torch.empty(4, B, device=pred.device, dtype=torch.float32), torch.empty(*count_rows, B, device=pred.device, dtype=torch.float32)]
+    if mean:
+        out.append(torch.empty(4, device=pred.device, dtype=torch.float32))
+    br = _Bracket(kind, f'loss A{A}', 0.0, nbytes(B, A, *lead, num_classes)) if timing._timer is not None else None
+    rc = getattr(nat.lib(), entry)(nat.ptr(pred), *[nat.ptr(t) for t in mid], nat.ptr(anchors), nat.ptr(ws), *[nat.ptr(t) for t in out],
+                                   *lead, B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
+                                   nat.stream_handle(pred.device))
+    nat.check(rc, entry)
     if br is not None:
         br.done()
-    return losses, nobj
+    return tuple(out)
+
+
+def _run_loss_bwd(entry, pred, mid, anchors, counts, upstream, out, lead, B, A, num_classes, input_size, weights, kind, nbytes):
+    """What the eight backward wrappers do once their operands are checked: ``mid`` / ``lead`` / ``nbytes`` as for ``_run_loss_fwd``; ``counts``:
+    the forward's nobj or counts; ``upstream``: coef or gmean, whichever the entry takes; ``out``: a checked tensor to write, or None
+    for a new one.  -> dpred."""
+    pred, anchors = pred.contiguous(), anchors.contiguous()
+    dpred = torch.empty_like(pred) if out is None else out
+    br = _Bracket(kind, f'lossbwd A{A}', 0.0, nbytes(B, A, *lead, num_classes)) if timing._timer is not None else None
+    rc = getattr(nat.lib(), entry)(nat.ptr(pred), *[nat.ptr(t) for t in mid], nat.ptr(anchors), nat.ptr(counts), nat.ptr(upstream),
+                                   nat.ptr(dpred), *lead, B, A, num_classes, int(input_size[0]), int(input_size[1]),
+                                   *[float(w) for w in weights], nat.stream_handle(pred.device))
+    nat.check(rc, entry)
+    if br is not None:
+        br.done()
+    return dpred
+
+
+# The upstream operands of the backward wrappers.  The three families grew their checks apart; each keeps what it accepts and the
+# words it raises (``name``: the wrapper, ``msg``: its text): the dense wrappers look at shapes only and take any object that has
+# one, the sparse ones add dtype and device, the masked ones also refuse what is no tensor.
+def _check_coef(name, coef, B, pred, msg, tensor=False, device=True):
+    """coef [3,B] -> contiguous fp32."""
+    if (tensor and not isinstance(coef, torch.Tensor)) or tuple(coef.shape) != (3, B) or (device and coef.device != pred.device):
+        raise ValueError(f'{name}: {msg}')
+    return coef.contiguous().float()
+
+
+def _check_gmean(name, gmean, pred, tensor=False):
+    """gmean: one fp32 value on the device of pred -> contiguous."""
+    if (tensor and not isinstance(gmean, torch.Tensor)) or gmean.numel() != 1 or gmean.dtype != torch.float32 or gmean.device != pred.device:
+        raise ValueError(f'{name}: gmean must be one fp32 value on the same device')
+    return gmean.contiguous()
+
+
+def _check_nobj(name, nobj, shape, pred, msg, tensor=False, kind=True):
+    """The forward's nobj [B] or counts [2,B] (``shape``); ``kind``: fp32 on the device of pred -> contiguous."""
+    if (tensor and not isinstance(nobj, torch.Tensor)) or tuple(nobj.shape) != shape \
+            or (kind and (nobj.dtype != torch.float32 or nobj.device != pred.device)):
+        raise ValueError(f'{name}: {msg}')
+    return nobj.contiguous() if kind else nobj
+
+
+def _dense_fwd_bytes(B, A, num_classes):
+    return 4.0 * B * A * (2 * num_classes + 14)
+
+
+def _dense_bwd_bytes(B, A, num_classes):
+    return 4.0 * B * A * (3 * num_classes + 19)
+
+
+def _loss_fwd(_entry, mean, pred, gt, anchors, input_size, num_classes, weights):
+    B, A = _check_loss_args(pred, gt, anchors, num_classes)
+    return _run_loss_fwd(_entry, pred, [gt.contiguous()], anchors, (), B, A, num_classes, input_size, weights, 5, (), mean,
+                         'loss_fwd', _dense_fwd_bytes)
+
+
+def _loss_bwd(_entry, pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
+    B, A = _check_loss_args(pred, gt, anchors, num_classes)
+    msg = 'coef must be [3,B], nobj [B]'
+    coef = _check_coef('loss_bwd', coef, B, pred, msg, device=False)
+    nobj = _check_nobj('loss_bwd', nobj, (B,), pred, msg, kind=False)
+    return _run_loss_bwd(_entry, pred, [gt.contiguous()], anchors, nobj, coef, None, (), B, A, num_classes, input_size, weights,
+                         'loss_bwd', _dense_bwd_bytes)
+
+
+def _loss_mean_bwd(_entry, pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
+    B, A = _check_loss_args(pred, gt, anchors, num_classes)
+    gmean = _check_gmean('loss_mean_bwd', gmean, pred)                 # (nobj goes to the entry as it came)
+    return _run_loss_bwd(_entry, pred, [gt.contiguous()], anchors, nobj, gmean, None, (), B, A, num_classes, input_size, weights,
+                         'loss_bwd', _dense_bwd_bytes)
+
+
+def loss_fwd(pred, gt, anchors, input_size, num_classes, weights):
+    """-> (losses [4,B] = class, score, bbox, total; nobj [B])."""
+    return _loss_fwd('sqd_loss_fwd', False, pred, gt, anchors, input_size, num_classes, weights)
 
 
 def loss_mean_fwd(pred, gt, anchors, input_size, num_classes, weights):
     """-> (losses [4,B], nobj [B], mean4 [4] = batch means of class / score / bbox / total): ``loss.mean()`` inside the loss launches."""
-    return _loss_mean_fwd('sqd_loss_mean_fwd', pred, gt, anchors, input_size, num_classes, weights)
-
-
-def _loss_mean_fwd(_entry, pred, gt, anchors, input_size, num_classes, weights):
-    B, A = _check_loss_args(pred, gt, anchors, num_classes)
-    pred, gt, anchors = pred.contiguous(), gt.contiguous(), anchors.contiguous()
-    ws = torch.empty(B * 16 * 5, device=pred.device, dtype=torch.float32)
-    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
-    nobj = torch.empty(B, device=pred.device, dtype=torch.float32)
-    mean4 = torch.empty(4, device=pred.device, dtype=torch.float32)
-    br = _Bracket('loss_fwd', f'loss A{A}', 0.0, 4.0 * B * A * (2 * num_classes + 14)) if timing._timer is not None else None
-    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj), nat.ptr(mean4),
-                                     B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
-                                     nat.stream_handle(pred.device))
-    nat.check(rc, _entry)
-    if br is not None:
-        br.done()
-    return losses, nobj, mean4
+    return _loss_fwd('sqd_loss_mean_fwd', True, pred, gt, anchors, input_size, num_classes, weights)
 
 
 def loss_mean_bwd(pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
@@ -1210,53 +1269,21 @@ def loss_mean_bwd(pred, gt, anchors, nobj, gmean, input_size, num_classes, weigh
     return _loss_mean_bwd('sqd_loss_mean_bwd', pred, gt, anchors, nobj, gmean, input_size, num_classes, weights)
 
 
-def _loss_mean_bwd(_entry, pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
-    B, A = _check_loss_args(pred, gt, anchors, num_classes)
-    if gmean.numel() != 1 or gmean.dtype != torch.float32 or gmean.device != pred.device:
-        raise ValueError('loss_mean_bwd: gmean must be one fp32 value on the same device')
-    pred, gt, anchors = pred.contiguous(), gt.contiguous(), anchors.contiguous()
-    dpred = torch.empty_like(pred)
-    br = _Bracket('loss_bwd', f'lossbwd A{A}', 0.0, 4.0 * B * A * (3 * num_classes + 19)) if timing._timer is not None else None
-    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(gmean.contiguous()), nat.ptr(dpred), B, A,
-                                     num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
-                                     nat.stream_handle(pred.device))
-    nat.check(rc, _entry)
-    if br is not None:
-        br.done()
-    return dpred
-
-
 def loss_bwd(pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
     """coef [3,B] -> dpred [B,A,C+5]."""
     return _loss_bwd('sqd_loss_bwd', pred, gt, anchors, nobj, coef, input_size, num_classes, weights)
 
 
-def _loss_bwd(_entry, pred, gt, anchors, nobj, coef, input_size, num_classes, weights):
-    B, A = _check_loss_args(pred, gt, anchors, num_classes)
-    if tuple(coef.shape) != (3, B) or tuple(nobj.shape) != (B,):
-        raise ValueError('loss_bwd: coef must be [3,B], nobj [B]')
-    pred, gt, anchors, coef = pred.contiguous(), gt.contiguous(), anchors.contiguous(), coef.contiguous().float()
-    dpred = torch.empty_like(pred)
-    br = _Bracket('loss_bwd', f'lossbwd A{A}', 0.0, 4.0 * B * A * (3 * num_classes + 19)) if timing._timer is not None else None
-    rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(gt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(coef), nat.ptr(dpred), B, A,
-                                num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
-                                nat.stream_handle(pred.device))
-    nat.check(rc, _entry)
-    if br is not None:
-        br.done()
-    return dpred
-
-
 def loss_fwd_many(pred, gt, anchors, input_size, num_classes, weights):
     """``loss_fwd`` for 1 <= num_classes <= 256 (a 16-lane group per anchor row)."""
     head_path(num_classes)
-    return _loss_fwd('sqd_loss_many_fwd', pred, gt, anchors, input_size, num_classes, weights)
+    return _loss_fwd('sqd_loss_many_fwd', False, pred, gt, anchors, input_size, num_classes, weights)
 
 
 def loss_mean_fwd_many(pred, gt, anchors, input_size, num_classes, weights):
     """``loss_mean_fwd`` for 1 <= num_classes <= 256; the per-image values equal ``loss_fwd_many``'s bit for bit."""
     head_path(num_classes)
-    return _loss_mean_fwd('sqd_loss_many_mean_fwd', pred, gt, anchors, input_size, num_classes, weights)
+    return _loss_fwd('sqd_loss_many_mean_fwd', True, pred, gt, anchors, input_size, num_classes, weights)
 
 
 def loss_mean_bwd_many(pred, gt, anchors, nobj, gmean, input_size, num_classes, weights):
@@ -1366,10 +1393,6 @@ def _check_sparse_loss_args(name, pred, sgt, anchors, num_classes):
     return B, A, total, SparseGT(*(t.contiguous() for t in sgt))
 
 
-def _sparse_ptrs(sgt):
-    return [nat.ptr(t) for t in sgt]
-
-
 def _sparse_fwd_bytes(B, A, total, num_classes):
     """Bytes the sparse forward reads: one confidence logit per row, the list once per slice of an image, a positive's pred row,
     box, deltas and anchor."""
@@ -1380,37 +1403,16 @@ def loss_sparse_fwd(pred, sgt, anchors, input_size, num_classes, weights):
     """``loss_fwd`` on a sparse ground truth (``SparseGT``), 1 <= num_classes <= 256: -> (losses [4,B], nobj [B]).  A negative row
     costs one float of ``pred``; the dense gt is never read or built."""
     B, A, total, sgt = _check_sparse_loss_args('loss_sparse_fwd', pred, sgt, anchors, num_classes)
-    pred, anchors = pred.contiguous(), anchors.contiguous()
-    ws = torch.empty(B * 16 * 5, device=pred.device, dtype=torch.float32)
-    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
-    nobj = torch.empty(B, device=pred.device, dtype=torch.float32)
-    br = _Bracket('loss_sparse_fwd', f'loss A{A}', 0.0, _sparse_fwd_bytes(B, A, total, num_classes)) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_sparse_fwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj),
-                                       total, B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
-                                       nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_sparse_fwd')
-    if br is not None:
-        br.done()
-    return losses, nobj
+    return _run_loss_fwd('sqd_loss_sparse_fwd', pred, sgt, anchors, (total,), B, A, num_classes, input_size, weights, 5, (), False,
+                         'loss_sparse_fwd', _sparse_fwd_bytes)
 
 
 def loss_sparse_mean_fwd(pred, sgt, anchors, input_size, num_classes, weights):
     """``loss_mean_fwd`` on a sparse ground truth: -> (losses [4,B], nobj [B], mean4 [4]); the per-image values equal
     ``loss_sparse_fwd``'s bit for bit."""
     B, A, total, sgt = _check_sparse_loss_args('loss_sparse_mean_fwd', pred, sgt, anchors, num_classes)
-    pred, anchors = pred.contiguous(), anchors.contiguous()
-    ws = torch.empty(B * 16 * 5, device=pred.device, dtype=torch.float32)
-    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
-    nobj = torch.empty(B, device=pred.device, dtype=torch.float32)
-    mean4 = torch.empty(4, device=pred.device, dtype=torch.float32)
-    br = _Bracket('loss_sparse_fwd', f'loss A{A}', 0.0, _sparse_fwd_bytes(B, A, total, num_classes)) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_sparse_mean_fwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses), nat.ptr(nobj),
-                                            nat.ptr(mean4), total, B, A, num_classes, int(input_size[0]), int(input_size[1]),
-                                            *[float(w) for w in weights], nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_sparse_mean_fwd')
-    if br is not None:
-        br.done()
-    return losses, nobj, mean4
+    return _run_loss_fwd('sqd_loss_sparse_mean_fwd', pred, sgt, anchors, (total,), B, A, num_classes, input_size, weights, 5, (), True,
+                         'loss_sparse_fwd', _sparse_fwd_bytes)
 
 
 def _sparse_bwd_bytes(B, A, total, num_classes):
@@ -1422,38 +1424,20 @@ def _sparse_bwd_bytes(B, A, total, num_classes):
 def loss_sparse_bwd(pred, sgt, anchors, nobj, coef, input_size, num_classes, weights):
     """``loss_bwd`` on a sparse ground truth: coef [3,B] -> dpred [B,A,C+5] (dense: ConvDet's backward reads it whole)."""
     B, A, total, sgt = _check_sparse_loss_args('loss_sparse_bwd', pred, sgt, anchors, num_classes)
-    if tuple(coef.shape) != (3, B) or tuple(nobj.shape) != (B,) or nobj.dtype != torch.float32 or nobj.device != pred.device \
-            or coef.device != pred.device:
-        raise ValueError('loss_sparse_bwd: coef must be [3,B], nobj fp32 [B], both on the device of pred')
-    pred, anchors, coef, nobj = pred.contiguous(), anchors.contiguous(), coef.contiguous().float(), nobj.contiguous()
-    dpred = torch.empty_like(pred)
-    br = _Bracket('loss_sparse_bwd', f'lossbwd A{A}', 0.0, _sparse_bwd_bytes(B, A, total, num_classes)) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_sparse_bwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(coef), nat.ptr(dpred),
-                                       total, B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
-                                       nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_sparse_bwd')
-    if br is not None:
-        br.done()
-    return dpred
+    msg = 'coef must be [3,B], nobj fp32 [B], both on the device of pred'
+    coef = _check_coef('loss_sparse_bwd', coef, B, pred, msg)
+    nobj = _check_nobj('loss_sparse_bwd', nobj, (B,), pred, msg)
+    return _run_loss_bwd('sqd_loss_sparse_bwd', pred, sgt, anchors, nobj, coef, None, (total,), B, A, num_classes, input_size, weights,
+                         'loss_sparse_bwd', _sparse_bwd_bytes)
 
 
 def loss_sparse_mean_bwd(pred, sgt, anchors, nobj, gmean, input_size, num_classes, weights):
     """``loss_mean_bwd`` on a sparse ground truth: gmean, a device scalar (the gradient arriving at mean(total)) -> dpred [B,A,C+5]."""
     B, A, total, sgt = _check_sparse_loss_args('loss_sparse_mean_bwd', pred, sgt, anchors, num_classes)
-    if gmean.numel() != 1 or gmean.dtype != torch.float32 or gmean.device != pred.device:
-        raise ValueError('loss_sparse_mean_bwd: gmean must be one fp32 value on the same device')
-    if tuple(nobj.shape) != (B,) or nobj.dtype != torch.float32 or nobj.device != pred.device:
-        raise ValueError('loss_sparse_mean_bwd: nobj must be fp32 [B] on the device of pred')
-    pred, anchors, nobj = pred.contiguous(), anchors.contiguous(), nobj.contiguous()
-    dpred = torch.empty_like(pred)
-    br = _Bracket('loss_sparse_bwd', f'lossbwd A{A}', 0.0, _sparse_bwd_bytes(B, A, total, num_classes)) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_sparse_mean_bwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(anchors), nat.ptr(nobj), nat.ptr(gmean.contiguous()),
-                                            nat.ptr(dpred), total, B, A, num_classes, int(input_size[0]), int(input_size[1]),
-                                            *[float(w) for w in weights], nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_sparse_mean_bwd')
-    if br is not None:
-        br.done()
-    return dpred
+    gmean = _check_gmean('loss_sparse_mean_bwd', gmean, pred)
+    nobj = _check_nobj('loss_sparse_mean_bwd', nobj, (B,), pred, 'nobj must be fp32 [B] on the device of pred')
+    return _run_loss_bwd('sqd_loss_sparse_mean_bwd', pred, sgt, anchors, nobj, gmean, None, (total,), B, A, num_classes, input_size,
+                         weights, 'loss_sparse_bwd', _sparse_bwd_bytes)
 
 
 def ignore_words(A):
@@ -1522,10 +1506,15 @@ def _check_masked_loss_args(name, pred, sgt, ignore, anchors, num_classes):
     return B, A, total, sgt, ignore.contiguous()
 
 
-def _check_counts(name, counts, B, pred):
-    if not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (2, B) or counts.dtype != torch.float32 or counts.device != pred.device:
-        raise ValueError(f'{name}: counts must be fp32 [2,B] = (n_obj, n_neg) on the device of pred')
-    return counts.contiguous()
+_COUNTS_MSG = 'counts must be fp32 [2,B] = (n_obj, n_neg) on the device of pred'
+
+
+def _masked_fwd_bytes(B, A, total, num_classes):
+    return _sparse_fwd_bytes(B, A, total, num_classes) + B * A / 8.0          # (+ the bitmap)
+
+
+def _masked_bwd_bytes(B, A, total, num_classes):
+    return _sparse_bwd_bytes(B, A, total, num_classes) + B * A / 8.0
 
 
 def loss_masked_fwd(pred, sgt, ignore, anchors, input_size, num_classes, weights):
@@ -1533,38 +1522,16 @@ def loss_masked_fwd(pred, sgt, ignore, anchors, input_size, num_classes, weights
     An anchor whose bit is set and that is no positive is neither a positive nor a negative; class / pos / bbox are 0 where
     n_obj = 0 and neg is 0 where n_neg = 0, so an object-free image gives finite values."""
     B, A, total, sgt, ignore = _check_masked_loss_args('loss_masked_fwd', pred, sgt, ignore, anchors, num_classes)
-    pred, anchors = pred.contiguous(), anchors.contiguous()
-    ws = torch.empty(B * 16 * 6, device=pred.device, dtype=torch.float32)
-    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
-    counts = torch.empty(2, B, device=pred.device, dtype=torch.float32)
-    br = _Bracket('loss_masked_fwd', f'loss A{A}', 0.0, _sparse_fwd_bytes(B, A, total, num_classes) + B * A / 8.0) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_masked_fwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(ignore), nat.ptr(anchors), nat.ptr(ws), nat.ptr(losses),
-                                       nat.ptr(counts), total, B, A, num_classes, int(input_size[0]), int(input_size[1]),
-                                       *[float(w) for w in weights], nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_masked_fwd')
-    if br is not None:
-        br.done()
-    return losses, counts
+    return _run_loss_fwd('sqd_loss_masked_fwd', pred, [*sgt, ignore], anchors, (total,), B, A, num_classes, input_size, weights, 6, (2,),
+                         False, 'loss_masked_fwd', _masked_fwd_bytes)
 
 
 def loss_masked_mean_fwd(pred, sgt, ignore, anchors, input_size, num_classes, weights):
     """``loss_masked_fwd`` + the batch means: -> (losses [4,B], counts [2,B], mean4 [4]); the per-image values equal
     ``loss_masked_fwd``'s bit for bit."""
     B, A, total, sgt, ignore = _check_masked_loss_args('loss_masked_mean_fwd', pred, sgt, ignore, anchors, num_classes)
-    pred, anchors = pred.contiguous(), anchors.contiguous()
-    ws = torch.empty(B * 16 * 6, device=pred.device, dtype=torch.float32)
-    losses = torch.empty(4, B, device=pred.device, dtype=torch.float32)
-    counts = torch.empty(2, B, device=pred.device, dtype=torch.float32)
-    mean4 = torch.empty(4, device=pred.device, dtype=torch.float32)
-    br = _Bracket('loss_masked_fwd', f'loss A{A}', 0.0, _sparse_fwd_bytes(B, A, total, num_classes) + B * A / 8.0) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_masked_mean_fwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(ignore), nat.ptr(anchors), nat.ptr(ws),
-                                            nat.ptr(losses), nat.ptr(counts), nat.ptr(mean4), total, B, A, num_classes,
-                                            int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
-                                            nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_masked_mean_fwd')
-    if br is not None:
-        br.done()
-    return losses, counts, mean4
+    return _run_loss_fwd('sqd_loss_masked_mean_fwd', pred, [*sgt, ignore], anchors, (total,), B, A, num_classes, input_size, weights, 6,
+                         (2,), True, 'loss_masked_fwd', _masked_fwd_bytes)
 
 
 def loss_masked_bwd(pred, sgt, ignore, anchors, counts, coef, input_size, num_classes, weights, out=None):
@@ -1572,44 +1539,27 @@ def loss_masked_bwd(pred, sgt, ignore, anchors, counts, coef, input_size, num_cl
     (an ignored row that is no positive: zeros).  ``out``: a fp32 [B,A,C+5] device tensor with contiguous strides to write instead
     (any storage offset)."""
     B, A, total, sgt, ignore = _check_masked_loss_args('loss_masked_bwd', pred, sgt, ignore, anchors, num_classes)
-    counts = _check_counts('loss_masked_bwd', counts, B, pred)
-    if not isinstance(coef, torch.Tensor) or tuple(coef.shape) != (3, B) or coef.device != pred.device:
-        raise ValueError('loss_masked_bwd: coef must be [3,B] on the device of pred')
-    pred, anchors, coef = pred.contiguous(), anchors.contiguous(), coef.contiguous().float()
-    dpred = _masked_dpred('loss_masked_bwd', pred, out)
-    br = _Bracket('loss_masked_bwd', f'lossbwd A{A}', 0.0, _sparse_bwd_bytes(B, A, total, num_classes) + B * A / 8.0) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_masked_bwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(ignore), nat.ptr(anchors), nat.ptr(counts), nat.ptr(coef),
-                                       nat.ptr(dpred), total, B, A, num_classes, int(input_size[0]), int(input_size[1]),
-                                       *[float(w) for w in weights], nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_masked_bwd')
-    if br is not None:
-        br.done()
-    return dpred
+    counts = _check_nobj('loss_masked_bwd', counts, (2, B), pred, _COUNTS_MSG, tensor=True)
+    coef = _check_coef('loss_masked_bwd', coef, B, pred, 'coef must be [3,B] on the device of pred', tensor=True)
+    out = _check_dpred_out('loss_masked_bwd', pred, out)
+    return _run_loss_bwd('sqd_loss_masked_bwd', pred, [*sgt, ignore], anchors, counts, coef, out, (total,), B, A, num_classes, input_size,
+                         weights, 'loss_masked_bwd', _masked_bwd_bytes)
 
 
 def loss_masked_mean_bwd(pred, sgt, ignore, anchors, counts, gmean, input_size, num_classes, weights, out=None):
     """``loss_sparse_mean_bwd`` with the bitmap: gmean, a device scalar (the gradient arriving at mean(total)) -> dpred [B,A,C+5]."""
     B, A, total, sgt, ignore = _check_masked_loss_args('loss_masked_mean_bwd', pred, sgt, ignore, anchors, num_classes)
-    counts = _check_counts('loss_masked_mean_bwd', counts, B, pred)
-    if not isinstance(gmean, torch.Tensor) or gmean.numel() != 1 or gmean.dtype != torch.float32 or gmean.device != pred.device:
-        raise ValueError('loss_masked_mean_bwd: gmean must be one fp32 value on the same device')
-    pred, anchors = pred.contiguous(), anchors.contiguous()
-    dpred = _masked_dpred('loss_masked_mean_bwd', pred, out)
-    br = _Bracket('loss_masked_bwd', f'lossbwd A{A}', 0.0, _sparse_bwd_bytes(B, A, total, num_classes) + B * A / 8.0) if timing._timer is not None else None
-    rc = nat.lib().sqd_loss_masked_mean_bwd(nat.ptr(pred), *_sparse_ptrs(sgt), nat.ptr(ignore), nat.ptr(anchors), nat.ptr(counts),
-                                            nat.ptr(gmean.contiguous()), nat.ptr(dpred), total, B, A, num_classes, int(input_size[0]),
-                                            int(input_size[1]), *[float(w) for w in weights], nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_loss_masked_mean_bwd')
-    if br is not None:
-        br.done()
-    return dpred
+    counts = _check_nobj('loss_masked_mean_bwd', counts, (2, B), pred, _COUNTS_MSG, tensor=True)
+    gmean = _check_gmean('loss_masked_mean_bwd', gmean, pred, tensor=True)
+    out = _check_dpred_out('loss_masked_mean_bwd', pred, out)
+    return _run_loss_bwd('sqd_loss_masked_mean_bwd', pred, [*sgt, ignore], anchors, counts, gmean, out, (total,), B, A, num_classes,
+                         input_size, weights, 'loss_masked_bwd', _masked_bwd_bytes)
 
 
-def _masked_dpred(name, pred, out):
-    if out is None:
-        return torch.empty_like(pred)
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != pred.shape or out.device != pred.device \
-            or not out.is_contiguous():
+def _check_dpred_out(name, pred, out):
+    """``out`` of the masked backward wrappers: None (a new tensor), or what the launch may write in its place."""
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != pred.shape
+                            or out.device != pred.device or not out.is_contiguous()):
         raise ValueError(f'{name}: out must be a contiguous fp32 {tuple(pred.shape)} tensor on the device of pred')
     return out
 

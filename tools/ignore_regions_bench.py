@@ -77,10 +77,54 @@ def case(C, n, A, anchors, anchors64, reps):
     return out
 
 
+def as_called(cfg, anchors, anchors64, reps, warmup=30):
+    """Host time of one eager ``Loss.mean_loss(pred, gt)`` + ``.backward()`` as a training step calls it (C = 3, sparse gt, without
+    and with an ignore bitmap): wall clock around the two calls, the device drained before each, so the figure is the Python
+    wrappers, the autograd node and the launches' enqueue, not device time; ``*_ops``: the same two launches through the
+    ``ops.loss_*_mean_fwd`` / ``_bwd`` wrappers alone.  -> {name: {median_us, p10_us, p90_us}}."""
+    import time
+    from squeezedet_pytorch_amd.model import Loss
+    C, A = 3, cfg.num_anchors
+    loss_mod = Loss(cfg)
+    pred, gt = make_inputs(A, C, anchors, seed=C)
+    pred.requires_grad_(True)
+    sgt = ops.sparse_gt_from_dense(gt)
+    bitmap = ops.anchor_ignore_mask(*ignore_boxes(8, 108), anchors64, 0.5)
+    def module_step(ignore):
+        pred.grad = None
+        mean, _ = loss_mod.mean_loss(pred, sgt, ignore)
+        mean.backward()
+
+    # the same two launches through the ops wrappers alone (no autograd node, no engine thread)
+    p, gmean = pred.detach(), torch.ones(1, device='cuda')
+
+    def sparse_ops():
+        _, nobj, _ = ops.loss_sparse_mean_fwd(p, sgt, anchors, SIZE, C, WEIGHTS)
+        ops.loss_sparse_mean_bwd(p, sgt, anchors, nobj, gmean, SIZE, C, WEIGHTS)
+
+    def masked_ops():
+        _, counts, _ = ops.loss_masked_mean_fwd(p, sgt, bitmap, anchors, SIZE, C, WEIGHTS)
+        ops.loss_masked_mean_bwd(p, sgt, bitmap, anchors, counts, gmean, SIZE, C, WEIGHTS)
+
+    out = {}
+    for name, step in (('sparse', lambda: module_step(None)), ('masked', lambda: module_step(bitmap)),
+                       ('sparse_ops', sparse_ops), ('masked_ops', masked_ops)):
+        ts = []
+        for i in range(warmup + reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            step()
+            ts.append((time.perf_counter() - t0) * 1e6)
+        ts = np.asarray(ts[warmup:])
+        out[name] = {'median_us': float(np.median(ts)), 'p10_us': float(np.percentile(ts, 10)), 'p90_us': float(np.percentile(ts, 90))}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=100)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ignore_regions_bench.json'))
+    ap.add_argument('--as-called', action='store_true', help='only the host time of Loss.mean_loss + backward as called (reps calls)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('ignore_regions_bench: needs a GPU')
@@ -88,6 +132,14 @@ def main():
     anchors = torch.from_numpy(cfg.anchors).float().cuda()
     anchors64 = torch.from_numpy(np.asarray(cfg.anchors, np.float64)).cuda()
     A = cfg.num_anchors
+    if args.as_called:
+        line = json.dumps({'batch': B, 'anchors': A, 'reps': args.reps, 'unit': 'us (host wall clock per forward + backward)',
+                           'as_called': as_called(cfg, anchors, anchors64, args.reps)})
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as fh:
+            fh.write(line + '\n')
+        print(line)
+        return
     res = {'batch': B, 'anchors': A, 'reps': args.reps, 'overlap': 0.5, 'unit': 'us (median, device events behind a spin kernel)'}
     for C in (3, 80):
         res[f'C{C}'] = {f'boxes{n}': case(C, n, A, anchors, anchors64, args.reps) for n in (0, 8, 300)}
