@@ -205,6 +205,15 @@ int sqd_detect_shift_fwd(const float* pred, const float* anchors, const float* s
                          int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
                          void* stream);
 
+/* sqd_detect_shift_fwd for a pred whose keys are already in keys_ws (required, 16-byte aligned, [B][ceil4(A)] uint32, written by
+ * sqd_conv_wino_vs_keys_fwd with the same score_thresh earlier on the same stream): one workgroup per image loads its keys, selects
+ * and suppresses -- nothing is scored, pred is read for the <= keep_top_k candidates only, words of keys_ws past an image's A keys
+ * are never looked at.  Same results bit for bit. */
+int sqd_detect_keys_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                        int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                        int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                        void* stream);
+
 /* Detector.filter on already decoded dense tensors (class_ids int64 [B][A], scores [B][A], boxes [B][A][4]). */
 int sqd_filter_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
                    long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
@@ -356,6 +365,15 @@ int sqd_conv_wino_fwd(const float* x, const float* u_packed, const float* bias, 
  * bias + optional ReLU epilogue only.  Results equal sqd_conv_wino_fwd's bit for bit. */
 int sqd_conv_wino_vs_fwd(const float* x, const float* u_packed, const float* bias, float* y, int B, int H, int W, int C, int x_pitch,
                          int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu, void* stream);
+/* The same launch for ConvDet of a THREE-class head writing `pred` itself (N = y_pitch = 8 * anchors_per_cell, y_coff = 0, relu = 0):
+ * y bit for bit as above, and the lane that stores an anchor's three class logits and confidence logit also stores the anchor's
+ * detection key -- the fp32 score bits if score > score_thresh (>= 0), else 0: the value the fused detect computes from the stored
+ * row -- into keys[b][(y * W + x) * anchors_per_cell + k]; keys = [B][ceil4(A)] uint32, A = H * W * anchors_per_cell.  The words
+ * A .. ceil4(A)-1 of an image and everything behind the keys are left untouched.  For sqd_detect_keys_fwd on the same stream.
+ * Status 2, nothing launched or written, for any other head shape (num_classes != 3, N != 8 * anchors_per_cell, a channel window, ReLU). */
+int sqd_conv_wino_vs_keys_fwd(const float* x, const float* u_packed, const float* bias, float* y, int B, int H, int W, int C, int x_pitch,
+                              int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu, unsigned* keys, float score_thresh,
+                              int anchors_per_cell, int num_classes, void* stream);
 /* Transformed weights U = G g G^T of an OIHW [No][Ci][3][3] parameter into the layout above; dgrad != 0 packs the
  * data-gradient orientation (in/out channels swapped, taps flipped). */
 int sqd_pack_wino_weight(const float* w_oihw, float* u_packed, int No, int Ci, int Npad, int dgrad, void* stream);

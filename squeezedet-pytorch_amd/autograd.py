@@ -25,10 +25,11 @@ def _flags(base):
     return plan.Flags(*(getattr(base, f) for f in plan.Flags._fields))
 
 
-def run_backbone_forward(base, image, save=False, drop_mask=None, drop=None):
+def run_backbone_forward(base, image, save=False, drop_mask=None, drop=None, det_keys=None):
     """Launch the forward schedule (plan.forward_schedule: every launch decision is taken there).  Returns (pred_nhwc
     [B,H,W,A_per_cell*(C+5)], saved dict | None).  Dropout in front of ConvDet (training): ``drop`` (an ops.DropState) applies it
-    inside the last Fire's expand launches, or ``drop_mask`` (a scaled keep mask, NHWC) multiplies it in."""
+    inside the last Fire's expand launches, or ``drop_mask`` (a scaled keep mask, NHWC) multiplies it in.  ``det_keys`` (an
+    ops.DetKeys, inference): ConvDet's launch also stores the detection keys where it can (``det_keys.written``)."""
     if not image.is_cuda:
         raise RuntimeError('SqueezeDetBase runs on the MI355X HIP kernels only: input must be a CUDA/HIP tensor')
     if image.dtype != torch.float32:
@@ -142,7 +143,9 @@ def run_backbone_forward(base, image, save=False, drop_mask=None, drop=None):
             saved[f'fire{i}'] = (a, sq, out)
         a = out
     pred = empty(steps[-1].H, steps[-1].W, cd.out_channels)
-    base.conv3x3('convdet', cd, a, 0, pred, 0, relu=False)
+    # (a padded ConvDet's scratch is not `pred`: no keys from it)
+    with ops.det_keys_request(det_keys if cd is base.convdet else None):
+        base.conv3x3('convdet', cd, a, 0, pred, 0, relu=False)
     if cd is not base.convdet:
         # a width the convolution forms do not take ran zero-padded into a scratch: pack it into the contiguous reference layout
         pred = ops.convdet_pack(pred, base.convdet.out_channels)
@@ -164,7 +167,7 @@ def _make_drop_mask(base, device):
     return base._forced_drop_mask.to(device).permute(0, 2, 3, 1).contiguous()
 
 
-def backbone_apply(base, image):
+def backbone_apply(base, image, det_keys=None):
     if torch.is_grad_enabled() and isinstance(image, torch.Tensor) and image.requires_grad:
         # (torch would hand back image.grad; the backward stops at the stem's weight gradient, so it would stay None without a word)
         raise RuntimeError('SqueezeDetBase: the input image requires grad, but the HIP backward computes no gradient with respect to '
@@ -181,7 +184,8 @@ def backbone_apply(base, image):
         params = [p for _, p in base.named_parameters()]
         pred = BackboneFn.apply(base, image, drop_mask, drop, *params)
     else:
-        pred, _ = run_backbone_forward(base, image, save=False, drop_mask=drop_mask, drop=drop)
+        pred, _ = run_backbone_forward(base, image, save=False, drop_mask=drop_mask, drop=drop,
+                                       det_keys=None if train_drop else det_keys)
     B = pred.shape[0]
     out = pred.view(B, -1, base.num_classes + 5)
     if out.shape[1] != base.num_anchors:

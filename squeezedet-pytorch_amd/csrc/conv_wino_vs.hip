@@ -23,8 +23,11 @@
 //   * one raw s_barrier per chunk publishes V (double-buffered per group slot, 64 KB): interval c runs the MFMAs of chunk c next to
 //     the transform of chunk c + 1.
 // Arithmetic per output element is that of conv_wino_kernel (same transforms, same k order): bit-identical results.
+// As ConvDet of a three-class head (sqd_conv_wino_vs_keys_fwd) the store loop also writes the detection key of every anchor: a lane
+// ends with four consecutive channels of a pixel, which for an even quad are one anchor's class and confidence logits.
 #include "sqd_common.h"
 #include "wino_tile.h"
+#include "anchor_score.h"
 #include <type_traits>
 /* (s_setprio for the duty wave behind its transform measured slower, 186 vs 174 us, and is gone.) */
 
@@ -35,6 +38,8 @@ struct WinoVsArgs {
   int N, y_pitch, y_coff;
   int relu;
   int gxn, gyn, ngroups, nunits, nwg;
+  // detection keys (sqd_conv_wino_vs_keys_fwd; null: none): y is the three-class `pred`, rows of 8 channels per anchor
+  unsigned* keys; float score_thresh; int apc, A4;          // [B][A4] keys, anchors per cell, A4 = ceil4(H * W * apc)
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr_vs_t;
@@ -217,6 +222,11 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
   const int n = blk * 16 + 4 * g;
   if (n >= a.N) return;
   float* const ybase = a.y + p0 * a.y_pitch + a.y_coff + n;
+  // detection keys: the four channels of an EVEN quad (blk * 4 + g) are the three class logits and the confidence logit of anchor
+  // (blk * 4 + g) / 2 of the pixel -- the lane that stores them scores the anchor (anchor_score.h: the bits detect_kernel would
+  // compute from the stored row) and stores its key, a plain 4-byte store that the kernel boundary hands to the detect launch
+  const int quad = blk * 4 + g;
+  unsigned* const kbase = (a.keys && !(quad & 1)) ? a.keys + (long long)b * a.A4 + (quad >> 1) : nullptr;
 #pragma unroll
   for (int px = 0; px < 4; ++px) {
     const int yy = 2 * ty + (px >> 1), xx = 2 * tx + (px & 1);
@@ -224,14 +234,16 @@ __global__ __launch_bounds__(VS_WV * 64, 3) void conv_wino_vs_kernel(WinoVsArgs 
     f32x4 v = ov[px];
     v.x = fmaxf(v.x, relu_lo); v.y = fmaxf(v.y, relu_lo); v.z = fmaxf(v.z, relu_lo); v.w = fmaxf(v.w, relu_lo);
     *(f32x4*)(ybase + ((long long)yy * a.W + xx) * a.y_pitch) = v;
+    if (kbase) kbase[((y0 + yy) * a.W + (x0 + xx)) * a.apc] = anchor_key3(v, a.score_thresh);
   }
 #endif
 }
 
 // y[..., y_coff : y_coff + N] = (ReLU)(conv3x3(x[..., x_coff : x_coff + C]) + bias), N <= 80, u_packed = sqd_pack_wino_weight output with
 // Npad = 80 (C/8 * 16 * 80 * 8 floats).  Same results, bit for bit, as sqd_conv_wino_fwd.
-extern "C" int sqd_conv_wino_vs_fwd(const float* x, const float* u_packed, const float* bias, float* y, int B, int H, int W, int C,
-                                    int x_pitch, int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu, void* stream) {
+static int launch_wino_vs(const float* x, const float* u_packed, const float* bias, float* y, int B, int H, int W, int C,
+                          int x_pitch, int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu, unsigned* keys, float score_thresh,
+                          int anchors_per_cell, void* stream) {
   SQD_CHECK_ARG(x && u_packed && y && B > 0 && H > 0 && W > 0 && C > 0 && N > 0);
   SQD_CHECK_ARG(C % 8 == 0 && N % 4 == 0 && N <= 16 * VS_NB && Npad == 16 * VS_NB);
   // (y is stored through flat pointers: only x is addressed per lane; Npad = 80, so the U bound is (C/8) * VS_UFL * 4)
@@ -244,8 +256,31 @@ extern "C" int sqd_conv_wino_vs_fwd(const float* x, const float* u_packed, const
   const long long ngroups = (long long)B * a.gxn * a.gyn;
   SQD_CHECK_ARG(ngroups * VS_NB < (1ll << 30));
   a.ngroups = (int)ngroups; a.nunits = a.ngroups * VS_NB; a.nwg = sqd_cdiv(a.nunits, VS_WV);
+  a.keys = keys; a.score_thresh = score_thresh; a.apc = anchors_per_cell;
+  a.A4 = keys ? (int)(((long long)H * W * anchors_per_cell + 3) & ~3ll) : 0;
   static SqdDevOnce once;
   if (int rc = sqd_max_lds_once(once, (const void*)conv_wino_vs_kernel, (int)VS_LDS)) return rc;
   hipLaunchKernelGGL(conv_wino_vs_kernel, dim3((unsigned)a.nwg), dim3(VS_WV * 64), VS_LDS, (hipStream_t)stream, a);
   return sqd_launch_status();
+}
+
+extern "C" int sqd_conv_wino_vs_fwd(const float* x, const float* u_packed, const float* bias, float* y, int B, int H, int W, int C,
+                                    int x_pitch, int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu, void* stream) {
+  return launch_wino_vs(x, u_packed, bias, y, B, H, W, C, x_pitch, x_coff, N, Npad, y_pitch, y_coff, relu, nullptr, 0.f, 0, stream);
+}
+
+// The same launch for ConvDet of a THREE-class head whose y is `pred` itself ([B][H*W*anchors_per_cell][8]: N = y_pitch =
+// 8 * anchors_per_cell, y_coff = 0, no ReLU): besides y, bit for bit as above, the lane that stores an anchor's (l0, l1, l2, conf)
+// also stores the anchor's detection key -- the fp32 score bits if score > score_thresh, else 0, the value detect_kernel computes from
+// the stored row -- into keys[b][(y * W + x) * anchors_per_cell + k], keys = [B][ceil4(A)] uint32, A = H * W * anchors_per_cell.
+// The words A .. ceil4(A)-1 of an image are NOT written (sqd_detect_keys_fwd never looks at them), nor anything behind the keys.
+// Every other head shape: SQD_ERR_UNSUPPORTED, nothing is launched (the caller keeps sqd_conv_wino_vs_fwd + sqd_detect_shift_fwd).
+extern "C" int sqd_conv_wino_vs_keys_fwd(const float* x, const float* u_packed, const float* bias, float* y, int B, int H, int W, int C,
+                                         int x_pitch, int x_coff, int N, int Npad, int y_pitch, int y_coff, int relu, unsigned* keys,
+                                         float score_thresh, int anchors_per_cell, int num_classes, void* stream) {
+  SQD_CHECK_ARG(keys && ((uintptr_t)keys & 3) == 0 && anchors_per_cell > 0 && num_classes > 0 && score_thresh >= 0.f);
+  if (num_classes != 3 || N != 8 * anchors_per_cell || y_pitch != N || y_coff != 0 || relu != 0) return SQD_ERR_UNSUPPORTED;
+  if ((long long)H * W * anchors_per_cell > 0x7ffffff0ll) return SQD_ERR_UNSUPPORTED;
+  return launch_wino_vs(x, u_packed, bias, y, B, H, W, C, x_pitch, x_coff, N, Npad, y_pitch, y_coff, relu, keys, score_thresh,
+                        anchors_per_cell, stream);
 }

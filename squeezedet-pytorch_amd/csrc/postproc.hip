@@ -10,7 +10,8 @@
 // [A][4] (cx,cy,w,h) fp32.  The reference runs ~15 elementwise launches plus a Python loop with
 // >=10 host syncs per image; here ONE launch (detect_kernel, one workgroup per image) does everything on the device:
 //   1. 16 waves score the image's anchors into LDS: score = max_c softmax_c * sigmoid(conf) per anchor; key = fp32 score
-//      bits (non-negative floats order like uint32) if score > score_thresh else 0; then 4 waves carry on:
+//      bits (non-negative floats order like uint32) if score > score_thresh else 0 (or, where ConvDet's launch already stored the
+//      keys -- sqd_detect_keys_fwd -- copy them into LDS); then:
 //   2. stable compaction of the non-zero keys into LDS, 4-pass 8-bit radix select of the K-th largest; ties at that
 //      key taken in ascending anchor order (the build's documented tie rule),
 //   3. one wave ranks the <=64 candidates (score desc, anchor index asc), decodes their boxes,
@@ -20,36 +21,11 @@
 // Arithmetic mirrors the oracle op for op in fp32 (built with -ffp-contract=off, IEEE division), so
 // that, given identical pred, the kept anchor indices are bit-exact.
 #include "sqd_common.h"
+#include "anchor_score.h"        // anchor_score: shared with ConvDet's key-writing epilogue (conv_wino_vs.hip)
 #include "many_class.h"
 #include <math.h>
 
-#define SQD_MAX_CLASSES 16
-
 struct BoxF { float x1, y1, x2, y2; };
-
-// score / class of one anchor row.  p points at C+5 floats.
-__device__ __forceinline__ void anchor_score(const float* __restrict__ p, int C, float& score, int& cls) {
-  float l[SQD_MAX_CLASSES];
-  float conf_logit;
-  if (C == 3) {
-    const f32x4 v = *(const f32x4*)p;
-    l[0] = v.x; l[1] = v.y; l[2] = v.z; conf_logit = v.w;
-  } else {
-    for (int c = 0; c < C; ++c) l[c] = p[c];
-    conf_logit = p[C];
-  }
-  float m = l[0];
-  for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
-  float sum = 0.f;
-  for (int c = 0; c < C; ++c) { l[c] = expf(l[c] - m); sum += l[c]; }
-  const float conf = 1.f / (1.f + expf(-conf_logit));
-  float best = -1.f; int bc = 0;
-  for (int c = 0; c < C; ++c) {
-    const float v = (l[c] / sum) * conf;
-    if (v > best) { best = v; bc = c; }
-  }
-  score = best; cls = bc;
-}
 
 __device__ __forceinline__ BoxF anchor_box(const float* __restrict__ d, const float* __restrict__ anc, float wmax, float hmax) {
   const float ax = anc[0], ay = anc[1], aw = anc[2], ah = anc[3];
@@ -138,10 +114,18 @@ extern "C" int sqd_resolve_fwd(const float* pred, const float* anchors, float* p
 // One launch, one workgroup per image of 1024 threads.  Phase 1 scores the anchors into LDS keys -- the fp32 score bits if
 // score > score_thresh, else 0; phase 2 compacts the non-zero keys (stable, ascending anchor index) and selects the top K
 // (radix select; the 256 histogram bins belong to the first 256 threads, the candidate sweeps run on all 1024), ranks them,
-// runs class-wise NMS on one wave and writes the compact result.  (Tried and dropped in
+// runs class-wise NMS on one wave and writes the compact result.  Three forms of phase 1, one kernel:
+//   * keys given (sqd_detect_keys_fwd): ConvDet's epilogue already stored every key of the batch (sqd_conv_wino_vs_keys_fwd: the
+//     lane that stores an anchor's logits scores it) -- phase 1 is a 16-byte copy of the image's keys into LDS, B workgroups, `pred`
+//     is read for the <= 64 candidates only.  The kernel boundary orders the key stores before the loads: no fence, no sc1.  The
+//     form of the benchmarked step (three classes, ConvDet on conv_wino_vs_kernel);
+//   * pred, split (sqd_detect_shift_fwd with a workspace): eight workgroups score an image from `pred` and hand their keys to the
+//     image's last arriver through the workspace (below);
+//   * pred or dense, one workgroup per image: every other caller.
+// (Tried and dropped in
 // round 2: spreading phase 1 over the whole chip and handing the keys to the last-arriving workgroup of each image
 // through global memory -- the device-scope release / acquire pair across the XCDs' L2s cost 12-100 us, more than the
-// 20 idle-chip microseconds it saved; profiles/r02_detect_variants.log.)
+// 20 idle-chip microseconds it saved; profiles/r02_detect_variants.log.  The split form above is its cheaper successor.)
 // Why pre-filtering by the threshold is exact: Detector.filter thresholds AFTER NMS, but a box at or below the
 // threshold can only suppress boxes with lower scores, which are dropped by the same threshold -- so the kept set
 // is that of NMS over the top-K of the above-threshold anchors.
@@ -153,6 +137,7 @@ struct DetArgs {
   const float* shifts;                                            // [B][2] = (dy, dx) added after the scale division, or null
   const long long* in_class; const float* in_score; const float* in_box;   // dense inputs (filter mode) or null
   unsigned* keys;                                                 // workspace [B][ceil4(A)] keys + [B] arrival counters, or null (one workgroup per image)
+  int keys_ready = 0;                                             // the workspace already holds every key of the batch (words A .. ceil4(A)-1 of an image: any)
   int S, per;
   int* det_count; long long* det_class; float* det_score; float* det_box; int* det_anchor;
   int B, A, C, K;
@@ -179,7 +164,8 @@ __global__ __launch_bounds__(DET_SCORE_THREADS) void detect_kernel(DetArgs a) {
   const int A = a.A, C = a.C, K = a.K;
   const float* pred = a.pred ? a.pred + (long long)b * A * (C + 5) : nullptr;
   const bool dense = a.in_score != nullptr;
-  const int lo_a = seg * a.per, hi_a = min(A, lo_a + a.per);  // this workgroup's anchors (a.per is a multiple of 4)
+  const bool given = a.keys_ready != 0;                       // the keys come from ConvDet's epilogue (S == 1): nothing to score
+  const int lo_a = given ? 0 : seg * a.per, hi_a = given ? 0 : min(A, lo_a + a.per);   // this workgroup's anchors (a.per is a multiple of 4)
 
   // 1. score the anchors straight into LDS.  Two passes keep the exp / divide work dense:
   //    1a. confidence only: score = max_c softmax_c * conf <= conf (softmax_c <= 1 and the products round monotonically), so
@@ -247,6 +233,15 @@ __global__ __launch_bounds__(DET_SCORE_THREADS) void detect_kernel(DetArgs a) {
     __syncthreads();
     for (int q = tid; q < A4 / 4; q += DET_SCORE_THREADS)
       *(u32x4_d*)(keysL + 4 * q) = __builtin_amdgcn_raw_buffer_load_b128(kres, q * 16, 0, 16);   // sc1 loads: every key of the image
+    __syncthreads();
+  }
+  if (given) {
+    // keys given: ConvDet's launch stored them, the kernel boundary made them visible -- plain 16-byte loads.  The words A .. A4-1 of
+    // the last quad are whatever the workspace held: nothing below reads keysL past A
+    typedef unsigned int u32x4_g __attribute__((ext_vector_type(4)));
+    const int A4 = (A + 3) & ~3;
+    const u32x4_g* __restrict__ src = (const u32x4_g*)(a.keys + (long long)b * A4);
+    for (int q = tid; q < A4 / 4; q += DET_SCORE_THREADS) *(u32x4_g*)(keysL + 4 * q) = src[q];
     __syncthreads();
   }
 
@@ -432,7 +427,8 @@ static int launch_detect(DetArgs a, hipStream_t stream) {
   if (lds > 48 * 1024 && sqd_max_lds_once(lds_once, (const void*)detect_kernel, 150 * 1024) != SQD_OK) return SQD_ERR_LAUNCH;
   // pred mode with a workspace: eight workgroups score an image, its last arriver selects and suppresses (the workspace holds B x
   // ceil4(A) keys + B counters that are zero between launches)
-  a.S = (a.pred && a.keys) ? DET_SPLIT : 1;
+  // keys given (keys_ready): one workgroup per image copies them, nothing is split and no counter is touched
+  a.S = (a.pred && a.keys && !a.keys_ready) ? DET_SPLIT : 1;
   a.per = (((a.A + 3) / 4 + a.S - 1) / a.S) * 4;
   hipLaunchKernelGGL(detect_kernel, dim3((unsigned)(a.B * a.S)), dim3(DET_SCORE_THREADS), lds, stream, a);
   return sqd_launch_status();
@@ -446,21 +442,41 @@ static int launch_detect(DetArgs a, hipStream_t stream) {
 // boxes_postprocess' padding / crops terms of the reference's forbid_resize branch (src/utils/boxes.py:149-155) -- and, when keys_ws
 // is given (B * ceil4(A) + B uint32, the last B zero before the first launch; every launch leaves them zero), the scoring of an
 // image spread over eight workgroups whose last arriver selects and suppresses.  keys_ws NULL: one workgroup per image.
-extern "C" int sqd_detect_shift_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
-                                    int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
-                                    int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh,
-                                    float score_thresh, void* stream) {
+// sqd_detect_keys_fwd: the same arguments, but keys_ws (required, 16-byte aligned) already HOLDS the keys of this pred -- [B][ceil4(A)],
+// written by sqd_conv_wino_vs_keys_fwd with the same score_thresh earlier on the same stream: one workgroup per image loads them,
+// selects and suppresses; nothing is scored, the arrival counters behind the keys are neither read nor written.
+static int detect_pred(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws, int keys_ready,
+                       int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                       int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh, void* stream) {
   SQD_CHECK_ARG(pred && anchors && det_count && det_class && det_score && det_box && det_anchor);
   SQD_CHECK_ARG(B > 0 && A > 0 && num_classes >= 1 && num_classes <= SQD_MAX_CLASSES);
   SQD_CHECK_ARG(((uintptr_t)pred & 15) == 0 && ((uintptr_t)det_box & 15) == 0);
+  SQD_CHECK_ARG(!keys_ready || (keys_ws && ((uintptr_t)keys_ws & 15) == 0));
   DetArgs a;
   a.shifts = shifts;
   a.pred = pred; a.anchors = anchors; a.scales = scales; a.in_class = nullptr; a.in_score = nullptr; a.in_box = nullptr; a.keys = keys_ws;
+  a.keys_ready = keys_ready;
   a.det_count = det_count; a.det_class = det_class; a.det_score = det_score; a.det_box = det_box; a.det_anchor = det_anchor;
   a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
   a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
   a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
   return launch_detect(a, (hipStream_t)stream);
+}
+
+extern "C" int sqd_detect_shift_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                                    int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                    int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh,
+                                    float score_thresh, void* stream) {
+  return detect_pred(pred, anchors, scales, shifts, keys_ws, 0, det_count, det_class, det_score, det_box, det_anchor, B, A, num_classes,
+                     input_h, input_w, keep_top_k, nms_thresh, score_thresh, stream);
+}
+
+extern "C" int sqd_detect_keys_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                                   int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                   int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh,
+                                   float score_thresh, void* stream) {
+  return detect_pred(pred, anchors, scales, shifts, keys_ws, 1, det_count, det_class, det_score, det_box, det_anchor, B, A, num_classes,
+                     input_h, input_w, keep_top_k, nms_thresh, score_thresh, stream);
 }
 
 extern "C" int sqd_detect_fwd(const float* pred, const float* anchors, const float* scales, unsigned* keys_ws, int* det_count,

@@ -35,11 +35,29 @@ class Detector(object):
         anchor_idx [B,K] i32), all on the GPU; rows >= count[b] are padding.  ``scales`` / ``shifts`` [B,2]: ``boxes_postprocess``'
         scale division and padding / crops terms, folded into the detect kernel."""
         cfg = self.cfg
-        pred = self.model.base(image)
+        base = self.model.base
+        B, A, K = int(image.shape[0]), int(cfg.num_anchors), int(cfg.keep_top_k)
+        fused = ops.detect_fn(cfg.num_classes, K, A)
+        if not (getattr(base, 'fuse_detect_keys', False) and fused is ops.detect and int(cfg.num_classes) == 3
+                and float(cfg.score_thresh) >= 0.0 and isinstance(image, torch.Tensor) and image.is_cuda):
+            pred = base(image)
+            anchors = self.model.resolver.anchors_on(pred.device)
+            return fused(pred, anchors, cfg.input_size, cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh,
+                         cfg.score_thresh, scales=scales, out=out, shifts=shifts)
+        # keys form: ConvDet's launch stores every anchor's score key into the detect workspace of this batch (the caller's -- a lane's,
+        # next to its result buffers -- or a fresh one), the detect launch loads them instead of scoring `pred` again.  Where ConvDet
+        # runs on another kernel (keys.written stays False) the same launch scores as before.
+        from .autograd import backbone_apply
+        if out is not None:
+            ops._check_det_out(out, B, K, image.device)
+        bufs = tuple(out) if out is not None else ops._det_buffers(B, K, image.device, A)
+        if len(bufs) == 5:
+            bufs = bufs + (ops._det_workspace(B, A, image.device),)
+        keys = ops.DetKeys(bufs[5], cfg.score_thresh, cfg.anchors_per_grid, cfg.num_classes)
+        pred = backbone_apply(base, image, det_keys=keys)
         anchors = self.model.resolver.anchors_on(pred.device)
-        fused = ops.detect_fn(cfg.num_classes, cfg.keep_top_k, pred.shape[1])
-        return fused(pred, anchors, cfg.input_size, cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh,
-                     cfg.score_thresh, scales=scales, out=out, shifts=shifts)
+        return ops.detect(pred, anchors, cfg.input_size, cfg.num_classes, K, cfg.nms_thresh, cfg.score_thresh, scales=scales,
+                          out=bufs, shifts=shifts, keys_ready=keys.written)
 
     @torch.no_grad()
     def detect(self, batch):

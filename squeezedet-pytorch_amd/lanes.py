@@ -5,8 +5,9 @@ Here a queue of batches runs over ``lanes`` (default 2) independent *lanes*.  A 
 buffer of the raw uint8 pixels, the network input, one packed result buffer and -- per batch size it has seen twice -- a captured
 hipGraph of its step (backbone -> fused detect; ``preprocess_kernel`` runs in front of it as the one eager launch, so that the
 raw-pixel buffer is released to the next upload the moment it has been read).  Consecutive batches go to consecutive lanes, so
-the serial tail of batch i (the last round of every persistent kernel, the 160-workgroup detect launch) overlaps the head of
-batch i + 1.  Around the lanes:
+the serial tail of batch i (the last round of every persistent kernel, the one-workgroup-per-image detect launch) overlaps the head
+of batch i + 1.  The detect workspace in a lane's result buffers also carries the score keys ConvDet's launch hands to the detect
+launch (``model.base.fuse_detect_keys``): per lane, so two steps in flight never share it.  Around the lanes:
 
   * raw pixels are packed by any thread (``Staging.put``) into one of ``lanes + 1`` pinned host buffers -- header (byte offsets +
     sizes of the images) and pixels in ONE allocation -- and leave with ONE host-to-device copy on a copy stream;
@@ -19,8 +20,8 @@ A batch shape a lane sees for the first time runs as eager launches on the lane'
 the second time it is captured; afterwards it replays.  The ragged last batch of a dataset therefore costs no capture.  Graph
 replay, eager launches and ``Detector.detect_images`` produce the same bits (tests/test_lanes_gpu.py).  A failed capture keeps
 that shape on eager launches and sets ``degraded`` (bench.py reports it next to ``value``).  New weights drop the captured steps;
-new detection parameters (``cfg.keep_top_k``, ``nms_thresh``, ``score_thresh``, ``input_size``, ``num_classes``) drop the captured
-steps and the result buffers as well.
+new detection parameters (``cfg.keep_top_k``, ``nms_thresh``, ``score_thresh``, ``input_size``, ``num_classes``, the model's
+``fuse_detect_keys``) drop the captured steps and the result buffers as well.
 """
 from __future__ import annotations
 
@@ -481,7 +482,7 @@ class DetectStream:
     def _params_signature(self):
         cfg = self.cfg
         return (int(cfg.keep_top_k), float(cfg.nms_thresh), float(cfg.score_thresh), tuple(int(v) for v in cfg.input_size),
-                int(cfg.num_classes), int(cfg.num_anchors))
+                int(cfg.num_classes), int(cfg.num_anchors), bool(getattr(self.det.model.base, 'fuse_detect_keys', False)))
 
     def discard(self, st):
         """Give an un-submitted ``Staging`` back (its batch takes another route)."""

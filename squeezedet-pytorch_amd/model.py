@@ -188,6 +188,9 @@ class SqueezeDetBase(nn.Module):
         # to the two separate kernels (0.174 vs 0.18 ms) -- both are bound by the 9x L2 read amplification of the window gather
         self.fuse_pool_squeeze = False
         self.fuse_stem_squeeze = True             # inference forward: the first Fire's squeeze inside the stem launch (ops.stem_pool_squeeze)
+        # detection (Detector.detect_device / lanes.DetectStream): ConvDet's epilogue stores the score keys, the fused detect skips its
+        # scoring pass (three classes, ConvDet on the V-shared Winograd kernel, narrow detect; same launches, same bits)
+        self.fuse_detect_keys = True
         self._forced_drop_mask = None       # tests: NCHW mask (already scaled by 1/(1-p)) instead of RNG
         # counter-based dropout (ops.DropState): applied in the last Fire's expand epilogues, its step advanced by ConvDet's launch,
         # no mask tensor and no torch RNG kernel in the step.  fused_dropout = False draws the mask as a tensor (stand-alone kernel)

@@ -12,6 +12,7 @@ writing ``ops.choose_cfg`` / ``ops.ConvPlan`` / ``ops.KernelTimer``.
 from __future__ import annotations
 
 import ctypes
+import threading
 from typing import NamedTuple
 
 import torch
@@ -192,11 +193,56 @@ def fire_expand(x, x_coff, fplan, y, y_coff):
     return y
 
 
+class DetKeys:
+    """A request to ConvDet's launch: also store the detection key of every anchor (``sqd_conv_wino_vs_keys_fwd``) into ``ws`` -- the
+    detect workspace of the batch (``det_workspace_words``; the keys occupy its first B x ceil4(A) words, the arrival counters behind
+    them are left alone).  ``written`` tells the caller whether the launch that ran could honour it (three classes, ConvDet on the
+    V-shared Winograd kernel writing ``pred`` itself): ``detect(..., keys_ready=True)`` then skips its scoring pass."""
+    __slots__ = ('ws', 'score_thresh', 'anchors_per_cell', 'num_classes', 'written')
+
+    def __init__(self, ws, score_thresh, anchors_per_cell, num_classes):
+        self.ws, self.score_thresh = ws, float(score_thresh)
+        self.anchors_per_cell, self.num_classes = int(anchors_per_cell), int(num_classes)
+        self.written = False
+
+    def fits(self, plan, y, y_coff, relu):
+        B, H, W, yp = y.shape
+        return (self.num_classes == 3 and plan.N == 8 * self.anchors_per_cell and yp == plan.N and y_coff == 0 and not relu
+                and self.score_thresh >= 0.0 and isinstance(self.ws, torch.Tensor) and self.ws.dtype == torch.int32
+                and self.ws.device == y.device and self.ws.is_contiguous() and self.ws.data_ptr() % 16 == 0
+                and self.ws.numel() >= det_workspace_words(B, H * W * self.anchors_per_cell))
+
+
+class det_keys_request:
+    """``with det_keys_request(keys): <ConvDet's launch>``: the ``DetKeys`` request of the calling thread for the ``conv_wino`` launches
+    inside the block (None: none).  Out of band on purpose: ConvDet reaches ``conv_wino`` through the same call, with the same
+    arguments, as every other 3x3 layer, and wrappers around ``conv_wino`` (checkers, tracers) need not know about the request."""
+    _tls = threading.local()
+
+    def __init__(self, keys):
+        self.keys = keys
+
+    def __enter__(self):
+        self.prev = getattr(self._tls, 'keys', None)
+        self._tls.keys = self.keys
+        return self.keys
+
+    def __exit__(self, *exc):
+        self._tls.keys = self.prev
+        return False
+
+    @classmethod
+    def current(cls):
+        return getattr(cls._tls, 'keys', None)
+
+
 def conv_wino(x, x_coff, plan, y, y_coff, relu=False, accumulate=False, ymask=None, ymul=None, yscale=1.0, drop=None, drop_advance=None):
     """y[..., y_coff:y_coff+N] (=|+=) conv3x3(x[..., x_coff:x_coff+C]) (+bias) (* ymul) (* yscale) (zero where ymask <= 0) (ReLU),
     Winograd F(2x2,3x3) kernel.  ``ymask`` / ``ymul`` are read through y's own channel window (same shape as y).  ``yscale``
     (a constant factor, e.g. the dropout scale), ``drop`` (a DropState: counter-based dropout of the output) and ``drop_advance`` (a
-    DropState whose step this launch advances; never the one ``drop`` names) need the balanced kernel (``plan.cfg_id`` = tiles.WINO_SK_CFG)."""
+    DropState whose step this launch advances; never the one ``drop`` names) need the balanced kernel (``plan.cfg_id`` = tiles.WINO_SK_CFG).
+    Inside ``det_keys_request(keys)`` the V-shared kernel (tiles.WINO_VS_CFG) also stores the detection keys where ``keys.fits``;
+    every other launch ignores the request and leaves ``keys.written`` False."""
     _check_nhwc(x, 'x'); _check_nhwc(y, 'y')
     B, H, W, xp = x.shape
     if tuple(y.shape[:3]) != (B, H, W):
@@ -236,9 +282,17 @@ def conv_wino(x, x_coff, plan, y, y_coff, relu=False, accumulate=False, ymask=No
             raise ValueError('conv_wino: the V-shared kernel (cfg tiles.WINO_VS_CFG) has the plain bias / ReLU epilogue only')
         if plan.N > 80 or plan.Npad != 80:
             raise ValueError('conv_wino: the V-shared kernel (cfg tiles.WINO_VS_CFG) runs N <= 80 packed 80 wide')
-        rc = nat.lib().sqd_conv_wino_vs_fwd(nat.ptr(x), nat.ptr(plan.w), nat.ptr(plan.bias), nat.ptr(y), B, H, W, plan.C, xp, x_coff,
-                                            plan.N, plan.Npad, yp, y_coff, int(relu), nat.stream_handle(x.device))
-        nat.check(rc, 'sqd_conv_wino_vs_fwd')
+        det_keys = det_keys_request.current()
+        if det_keys is not None and det_keys.fits(plan, y, y_coff, relu):
+            rc = nat.lib().sqd_conv_wino_vs_keys_fwd(nat.ptr(x), nat.ptr(plan.w), nat.ptr(plan.bias), nat.ptr(y), B, H, W, plan.C, xp, x_coff,
+                                                     plan.N, plan.Npad, yp, y_coff, int(relu), nat.ptr(det_keys.ws), det_keys.score_thresh,
+                                                     det_keys.anchors_per_cell, det_keys.num_classes, nat.stream_handle(x.device))
+            nat.check(rc, 'sqd_conv_wino_vs_keys_fwd')
+            det_keys.written = True
+        else:
+            rc = nat.lib().sqd_conv_wino_vs_fwd(nat.ptr(x), nat.ptr(plan.w), nat.ptr(plan.bias), nat.ptr(y), B, H, W, plan.C, xp, x_coff,
+                                                plan.N, plan.Npad, yp, y_coff, int(relu), nat.stream_handle(x.device))
+            nat.check(rc, 'sqd_conv_wino_vs_fwd')
     else:
         if yscale != 1.0 or drop is not None or drop_advance is not None:
             raise ValueError('conv_wino: yscale / drop / drop_advance need the balanced kernel (cfg tiles.WINO_SK_CFG)')
@@ -791,8 +845,10 @@ def _check_det_out(bufs, B, K, device):
         raise ValueError('detect: out[3] (boxes) must be 16-byte aligned')
 
 
-def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None):
-    """Fused decode + top-k + class-wise NMS + threshold for a batch.
+def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None,
+           keys_ready=False):
+    """Fused decode + top-k + class-wise NMS + threshold for a batch.  ``keys_ready``: the workspace in ``out`` already holds the keys
+    of this ``pred`` for this ``score_thresh`` (ConvDet's launch wrote them: ``DetKeys``) -- one workgroup per image, no scoring pass.
     Returns (count int32 [B], class_ids int64 [B,K], scores [B,K], boxes [B,K,4], anchor_idx int32 [B,K]).  ``scales`` [B,2] =
     (sy, sx): boxes are divided by them; ``shifts`` [B,2] = (dy, dx): added afterwards (the padding / crops terms of
     ``boxes_postprocess``, src/utils/boxes.py:149-155).  ``out``: the five result tensors (checked against B and ``keep_top_k``) and
@@ -819,12 +875,15 @@ def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4
         raise ValueError('detect: workspace must be an int32 tensor on the same device')
     if keys.numel() < det_workspace_words(B, A) or not keys.is_contiguous():
         keys = None                                  # (a caller-made placeholder: one workgroup per image)
+    if keys_ready and (keys is None or keys.data_ptr() % 16):
+        raise ValueError('detect: keys_ready needs the 16-byte aligned workspace the keys were written to')
+    entry = 'sqd_detect_keys_fwd' if keys_ready else 'sqd_detect_shift_fwd'
     br = _Bracket('detect', f'detect A{A}', 0.0, 4.0 * B * A * (num_classes + 5)) if timing._timer is not None else None
-    rc = nat.lib().sqd_detect_shift_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
-                                        nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
-                                        int(input_size[0]), int(input_size[1]), int(keep_top_k), float(nms_thresh), float(score_thresh),
-                                        nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_detect_shift_fwd')
+    rc = getattr(nat.lib(), entry)(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
+                                   nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                   int(input_size[0]), int(input_size[1]), int(keep_top_k), float(nms_thresh), float(score_thresh),
+                                   nat.stream_handle(pred.device))
+    nat.check(rc, entry)
     if br is not None:
         br.done()
     return bufs[:5]
