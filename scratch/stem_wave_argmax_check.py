@@ -1,4 +1,4 @@
-"""Training-forward stem: stem_wave_kernel<2,2,ARGMAX> (SQD_STEM_WAVE=2) vs the workgroup kernel (0): pooled values and codes equal; time."""
+"""Training-forward stem: stem_wave_kernel<1,ARGMAX> (the shipped kernel; SQD_STEM_WAVE=2 = any value but 0) vs the workgroup kernel (0): pooled values and codes equal; time."""
 import os, sys
 sys.path.insert(0, '.')
 import torch

@@ -9,9 +9,8 @@
 // weights ([N][K], the checkpoint's own OIHW order) sit in LDS with an odd row pitch.  MFMA operand
 // A = weights, operand B = pixels, so a lane ends with 4 consecutive output channels of one pixel
 // and stores 16 bytes (the stem output is the largest tensor of the network: 30.7 MB per image).
-#include "sqd_common.h"
+#include "stem.h"
 #include <type_traits>
-#include <stdlib.h>
 
 struct StemArgs {
   const float* x;     // [B][3][Hin][Win]
@@ -45,14 +44,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(StemArgs a) {
   const int ty = t % a.tiles_y; const int b = t / a.tiles_y;
   const int y0 = ty * TH, x0 = tx * 16;
 
-  for (int idx = tid; idx < 3 * IH * IW; idx += 256) {
-    const int c = idx % IW; int r = idx / IW; const int ci = r / IH; r -= ci * IH;
-    const int iy = 2 * y0 - PAD + r, ix = 2 * x0 - PAD + c;
-    float v = 0.f;
-    if (iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win)
-      v = a.x[(((long long)b * 3 + ci) * a.Hin + iy) * a.Win + ix];
-    inT[(ci * IH + r) * IWP + c] = v;
-  }
+  stem_stage_planar<PAD, IH, IW, IWP>(inT, a.x, b, y0, x0, a.Hin, a.Win, tid);
   if (tid == 0) inT[NIN] = 0.f;
   for (int idx = tid; idx < BN * (KW - 1); idx += 256) {
     const int n = idx / (KW - 1), k = idx - n * (KW - 1);
@@ -111,9 +103,8 @@ static int launch_stem(StemArgs a, hipStream_t s) {
   constexpr size_t lds = (size_t)(3 * IH * IWP + 1 + 16 * NT * KW) * sizeof(float);
   a.tiles_x = sqd_cdiv(a.Wo, 16); a.tiles_y = sqd_cdiv(a.Ho, 8);
   auto kern = stem_conv_kernel<KS, PAD, NT>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return SQD_ERR_LAUNCH;
+  static SqdDevOnce lds_once;
+  if (lds > 64 * 1024 && sqd_max_lds_once(lds_once, (const void*)kern, (int)lds) != SQD_OK) return SQD_ERR_LAUNCH;
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.B * a.tiles_x * a.tiles_y)), dim3(256), lds, s, a);
   return sqd_launch_status();
 }
@@ -123,18 +114,13 @@ extern "C" int sqd_stem_conv_fwd(const float* x, const float* w, const float* bi
                                  int B, int Hin, int Win, int N, int ksize, int relu, void* stream) {
   SQD_CHECK_ARG(x && w && y && B > 0 && Hin > 0 && Win > 0);
   SQD_CHECK_ARG(((uintptr_t)y & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0));
+  const StemGeom g = stem_geom(Hin, Win, ksize);
   StemArgs a;
-  a.x = x; a.w = w; a.bias = bias; a.y = y; a.B = B; a.Hin = Hin; a.Win = Win; a.N = N; a.relu = relu;
-  hipStream_t s = (hipStream_t)stream;
-  if (ksize == 3 && N == 64) {
-    a.Ho = (Hin + 2 - 3) / 2 + 1; a.Wo = (Win + 2 - 3) / 2 + 1;
-    return launch_stem<3, 1, 4>(a, s);
-  }
-  if (ksize == 7 && N == 96) {
-    a.Ho = (Hin + 6 - 7) / 2 + 1; a.Wo = (Win + 6 - 7) / 2 + 1;
-    return launch_stem<7, 3, 6>(a, s);
-  }
-  return SQD_ERR_UNSUPPORTED;
+  a.x = x; a.w = w; a.bias = bias; a.y = y; a.B = B; a.Hin = Hin; a.Win = Win; a.Ho = g.Ho; a.Wo = g.Wo; a.N = N; a.relu = relu;
+  return stem_dispatch(ksize, N, [&](auto sh) {
+    using S = decltype(sh);
+    return launch_stem<S::KS, S::PAD, S::NT>(a, (hipStream_t)stream);
+  });
 }
 
 extern "C" int sqd_stem_conv_relu_fwd(const float* x, const float* w, const float* bias, float* y,
@@ -153,13 +139,12 @@ extern "C" int sqd_stem_conv_relu_fwd(const float* x, const float* w, const floa
 // double buffer (no staging registers, no index arithmetic: uniform tile origin + a per-lane element
 // offset computed once; only border tiles redirect out-of-image taps to a zero page), the weights
 // stay in LDS, im2col happens in the LDS read addresses of the MFMA B operand.  PH = 3 makes the conv
-// patch 7 x 17 = 119 pixels = 8 MFMA row tiles, two per wave (balanced).  Two barriers per tile.
+// patch 7 x 17 = 119 pixels = 8 MFMA row tiles, one per wave of the 8 (two waves per SIMD work on one tile).  Two barriers per tile.
 // ARGMAX = false (inference): pooling is v_max3 over the window.  ARGMAX = true (training): uint8 argmax
 // 0..8, first maximum in window scan order, NaN taken like PyTorch's CPU kernel.
+// This is the kernel of the 7x7 / 96-channel stem, of 3x3 images the wave kernel below refuses, and the parity partner of that
+// kernel (SQD_STEM_WAVE=0, stem.h).
 // ---------------------------------------------------------------------------------------------
-#ifndef SQD_STEM_WAVES
-#define SQD_STEM_WAVES 8
-#endif
 struct StemPoolArgs {
   const float* x; const float* w; const float* bias; float* y; uint8_t* amax;
   int B, Hin, Win, Ho, Wo, Hp, Wp, N;
@@ -170,9 +155,9 @@ struct StemPoolArgs {
 __device__ __attribute__((aligned(16))) float sqd_stem_zero[4] = {0.f, 0.f, 0.f, 0.f};
 typedef __attribute__((address_space(3))) void* stem_lds_ptr_t;
 
-template <int KS, int PAD, int NT, bool ARGMAX, int WM>
-__global__ __launch_bounds__(WM * 64, (WM == 4 && KS == 3) ? 3 : ((WM == 8 && KS == 3) ? 4 : 1)) void stem_pool_kernel(StemPoolArgs a) {
-  constexpr int NTHR = WM * 64;                       // 4 or 8 waves; with 8, two waves per SIMD work on one tile
+template <int KS, int PAD, int NT, bool ARGMAX>
+__global__ __launch_bounds__(512, KS == 3 ? 4 : 1) void stem_pool_kernel(StemPoolArgs a) {
+  constexpr int WM = 8, NTHR = WM * 64;               // 8 waves: two per SIMD work on one tile
   constexpr int PH = 3, PW = 8;                       // pooled tile
   constexpr int CH = 2 * PH + 1, CW = 2 * PW + 1;     // conv patch 7 x 17
   constexpr int NCP = CH * CW;                        // 119 conv pixels
@@ -182,12 +167,12 @@ __global__ __launch_bounds__(WM * 64, (WM == 4 && KS == 3) ? 3 : ((WM == 8 && KS
   constexpr int K = 3 * KS * KS, KSTEPS = (K + 3) / 4, KW = KSTEPS * 4 + 1;
   constexpr int IH = 2 * (CH - 1) + KS, IW = 2 * (CW - 1) + KS;
   constexpr int NIN = 3 * IH * IW;
-  // Wave roles (WM = 8): waves 0..3 are the only ones that issue input DMA, waves 4..7 the only ones that issue global
+  // Wave roles: waves 0..3 are the only ones that issue input DMA, waves 4..7 the only ones that issue global
   // stores (they do the pooling).  A wave's vmcnt then counts one kind of operation: the DMA waves' vmcnt(0) at the
   // tile barrier waits for loads issued a whole tile earlier, and nobody ever waits for a store acknowledgement
   // (with mixed roles every tile barrier also waited out the HBM write latency of the previous tile's outputs).
-  constexpr int NPROD = (WM == 8) ? 256 : NTHR;       // DMA threads
-  constexpr int NPOOL = (WM == 8) ? 256 : NTHR;       // pooling / storing threads
+  constexpr int NPROD = 256;                          // DMA threads
+  constexpr int NPOOL = 256;                          // pooling / storing threads
   constexpr int IN_IT = (NIN + NPROD - 1) / NPROD, INSLOTS = IN_IT * NPROD;
   constexpr bool WREG = KSTEPS * NT <= 32;            // weights + im2col offsets live in registers (3x3 stem)
   constexpr int BN = 16 * NT;
@@ -305,8 +290,8 @@ __global__ __launch_bounds__(WM * 64, (WM == 4 && KS == 3) ? 3 : ((WM == 8 && KS
 #pragma unroll
       for (int s = 0; s < KSTEPS; ++s) bofs[i][s] = (const char*)(inB + pbase[i] + kreg[s]);
   }
-  const bool is_prod = (WM != 8) || wave_s < 4;       // uniform
-  const bool is_pool = (WM != 8) || wave_s >= 4;
+  const bool is_prod = wave_s < 4;                    // uniform
+  const bool is_pool = wave_s >= 4;
   // XCD-contiguous walk: horizontally adjacent tiles share two of the three 128-byte lines every 140-byte patch row touches and
   // vertically adjacent ones 3 of 15 rows; with the plain id walk the eight neighbours of a run sat on eight XCDs and every
   // L2 fetched its own copy (375 MB per batch of 20 for a 115 MB image, profiles/traffic.json of round 2)
@@ -321,12 +306,8 @@ __global__ __launch_bounds__(WM * 64, (WM == 4 && KS == 3) ? 3 : ((WM == 8 && KS
     const bool has_next = ntile < a.ntiles;
     const Tile nxt = tile_at(has_next ? ntile : tile);
     // tile barrier: this tile's input landed (DMA waves: vmcnt(0)); previous tile's pooling left convT (LDS reads done)
-    if (WM == 8) {
-      if (is_prod) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    } else {
-      __syncthreads();
-    }
+    if (is_prod) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (has_next && is_prod) dma_in(nxt, buf ^ 1);
     const float* inT = inB + buf * INSLOTS;
     const int cy0 = 2 * cur.ty * PH, cx0 = 2 * cur.tx * PW;       // conv coords of the patch origin
@@ -475,23 +456,19 @@ __global__ __launch_bounds__(WM * 64, (WM == 4 && KS == 3) ? 3 : ((WM == 8 && KS
   }
 }
 
-template <int KS, int PAD, int NT, bool ARGMAX, int WM>
+template <int KS, int PAD, int NT, bool ARGMAX>
 static int launch_stem_pool_t(StemPoolArgs a, hipStream_t s) {
   constexpr int PH = 3, PW = 8, CH = 2 * PH + 1, CW = 2 * PW + 1, NSUB = (CH * CW + 15) / 16;
-  constexpr int K = 3 * KS * KS, KSTEPS = (K + 3) / 4, KW = KSTEPS * 4 + 1, NTHR = WM * 64;
+  constexpr int K = 3 * KS * KS, KSTEPS = (K + 3) / 4, KW = KSTEPS * 4 + 1, NTHR = 512;
   constexpr int IH = 2 * (CH - 1) + KS, IW = 2 * (CW - 1) + KS;
-  constexpr int NPROD = (WM == 8) ? 256 : NTHR;
+  constexpr int NPROD = 256;
   constexpr int INSLOTS = (3 * IH * IW + NPROD - 1) / NPROD * NPROD;
   constexpr bool WREG = KSTEPS * NT <= 32;
   constexpr size_t lds = (size_t)(NSUB * 16 * (16 * NT + 4) + 2 * INSLOTS + 4 + (WREG ? 0 : 16 * NT * KW) + 16 * NT + KSTEPS * 4) * sizeof(float);
   static_assert(lds <= 160 * 1024, "stem_pool LDS budget");
   static_assert(IH < 256 && IW < 256, "slot keys pack row/col in 8 bits");
-  a.tiles_x = sqd_cdiv(a.Wp, PW); a.tiles_y = sqd_cdiv(a.Hp, PH);
-  a.ntiles = a.B * a.tiles_x * a.tiles_y;
-  if ((long long)a.ntiles * (a.tiles_x > a.tiles_y ? a.tiles_x : a.tiles_y) >= (1ll << 32)) return SQD_ERR_UNSUPPORTED;
-  a.tiles_x_m = a.tiles_x > 1 ? (unsigned)(((1ull << 32) + a.tiles_x - 1) / a.tiles_x) : 0u;
-  a.tiles_y_m = a.tiles_y > 1 ? (unsigned)(((1ull << 32) + a.tiles_y - 1) / a.tiles_y) : 0u;
-  auto kern = stem_pool_kernel<KS, PAD, NT, ARGMAX, WM>;
+  if (!stem_fill_tiles(a, PH, PW)) return SQD_ERR_UNSUPPORTED;
+  auto kern = stem_pool_kernel<KS, PAD, NT, ARGMAX>;
   static int wgs_per_cu = 0;
   static SqdDevOnce lds_once;
   if (lds > 64 * 1024 && sqd_max_lds_once(lds_once, (const void*)kern, (int)lds) != SQD_OK) return SQD_ERR_LAUNCH;
@@ -507,49 +484,34 @@ static int launch_stem_pool_t(StemPoolArgs a, hipStream_t s) {
 
 template <int KS, int PAD, int NT>
 static int launch_stem_pool(StemPoolArgs a, hipStream_t s) {
-  constexpr int WM = SQD_STEM_WAVES;
-  return a.amax ? launch_stem_pool_t<KS, PAD, NT, true, WM>(a, s) : launch_stem_pool_t<KS, PAD, NT, false, WM>(a, s);
+  return a.amax ? launch_stem_pool_t<KS, PAD, NT, true>(a, s) : launch_stem_pool_t<KS, PAD, NT, false>(a, s);
 }
 
 // ---------------------------------------------------------------------------------------------
-// Wave-autonomous fused stem (round 3, the 3x3 / 64-channel stem of src/model/squeezedet.py:34-36 at inference): same
-// arithmetic as stem_pool_kernel<3,1,4,false,8> -- a k-ordered fp32 MFMA chain from 0, max over the window, THEN bias and
-// ReLU -- so the two kernels agree bit for bit, but no workgroup-level cooperation at all:
-//   * a WAVE owns a pooled tile of PH rows x 7 columns = a conv patch of (2 PH + 1) rows x 15 columns: one MFMA column
-//     block (16 conv columns, the 16th unused) per conv row, 4 channel blocks -> 4 (2 PH + 1) accumulators;
-//   * its NCHW input patch ((4 PH + 3) rows x 36 floats x 3 planes, 16-byte slots: the patch starts 4 floats left of the
-//     first tap so that every row segment is 16-byte aligned in a 4-float-aligned image row) arrives by buffer-resource
-//     LDS-DMA in a wave-private double buffer, retired by a counted s_waitcnt vmcnt; slots outside the image carry an
-//     out-of-range offset and are zero-filled by the hardware (the convolution's padding);
+// Wave-autonomous fused stem (the 3x3 / 64-channel stem of src/model/squeezedet.py:34-36): same arithmetic as
+// stem_pool_kernel<3,1,4,..> -- a k-ordered fp32 MFMA chain from 0, max over the window, THEN bias and ReLU -- so the two kernels
+// agree bit for bit, but no workgroup-level cooperation at all:
+//   * a WAVE owns a pooled tile of PH rows x 15 columns = a conv patch of (2 PH + 1) rows x 31 columns, held as TWO 16-column MFMA
+//     blocks per conv row split by column PARITY -- block E holds conv columns 2m, block O columns 2m + 1 (im2col is only an LDS
+//     read address, so the split is free) -- times 4 channel blocks -> 8 (2 PH + 1) accumulators;
+//   * its NCHW input patch arrives as the wave-private patch loader of stem.h describes it (StemPatch: buffer-resource LDS-DMA
+//     into a double buffer, hardware zero fill outside the image), retired by a counted s_waitcnt vmcnt;
 //   * im2col = the LDS read address of the B operand (per-lane base + immediates), weights in registers;
-//   * the 3x3 / stride-2 pool runs in REGISTERS: vertical max = v_max3 across the accumulators of three conv rows (same
-//     lane), horizontal max = two v_max_f32 with DPP row_shl:1 / row_shl:2 operands (lane = conv column), bias + ReLU on
-//     the pooled values, one 16-byte store per (pooled row, channel block) from the 7 x 4 lanes that hold a pooled pixel.
+//   * the 3x3 / stride-2 pool runs in REGISTERS: vertical max = v_max3 across the accumulators of three conv rows (same lane);
+//     lane m's window is then E[m], O[m], E[m + 1]: one plain max and one v_max_f32 with a DPP row_shl:1 operand, and 15 of 16
+//     lanes end with a pooled pixel; bias + ReLU on the pooled values, one 16-byte store per (pooled row, channel block).
 // The workgroup kernel above spends 7700 cycles per tile of which 1792 issue MFMAs: two workgroup barriers per tile and
-// the conv-patch round trip through LDS into the pool; here nothing waits for another wave.
-// Needs Win % 4 == 0 and a 16-byte aligned image (else the launcher keeps the workgroup kernel).
-// ---------------------------------------------------------------------------------------------
-struct StemWaveArgs {
-  const float* x; const float* w; const float* bias; float* y; uint8_t* amax;
-  const float* wsq; const float* bsq;       // SQ variant: the next Fire's squeeze (1x1, 64 -> SQ channels, OIHW + bias); y is ITS output
-  float* ysq;                               // ARGMAX + SQ (training): y and amax as without SQ, the squeeze output goes HERE
-  int B, Hin, Win, Ho, Wo, Hp, Wp;
-  int tiles_x, tiles_y, ntiles;
-  unsigned tiles_x_m, tiles_y_m;
-};
-
-// CB = 1: one 16-column block per conv row, lane = conv column, 7 pooled columns per tile (lanes 0, 2, .., 12 end with a pooled
-// pixel).  CB = 2: TWO column blocks per conv row, split by column PARITY -- block E holds conv columns 2m, block O columns 2m + 1
-// (im2col is only an LDS read address, so the split is free) -- so that lane m's window is E[m], O[m], E[m + 1]: one plain max,
-// one DPP max, and 15 of 16 lanes end with a pooled pixel (2.3x fewer vector instructions per pooled pixel than CB = 1; every
-// vector instruction delays the SIMD's matrix pipe).
-// ARGMAX (training forward, CB = 2 only): additionally writes the uint8 code of the FIRST window position (row-major) holding the
+// the conv-patch round trip through LDS into the pool; here nothing waits for another wave.  (One column block per conv row
+// with lane = conv column was measured slower and is gone: DESIGN.md, "Stem kernels".)
+// Runs where stem_wave_ok (stem.h) holds; else the launcher keeps the workgroup kernel.
+//
+// ARGMAX (training forward): additionally writes the uint8 code of the FIRST window position (row-major) holding the
 // pooled value, or 15 where the pooled value is not > 0 -- the codes of stem_pool_kernel<.., ARGMAX = true> / maxpool_fwd_kernel<true,
 // true>.  Positions are compared AFTER the bias add (rounding can create ties that the raw sums do not have); the ReLU needs no
 // compare of its own (a window whose maximum is <= 0 is code 15 whatever its arg-max).  Column E / O of the window: first row holding
 // the column maximum by two compares, candidates 3 dy + dx of the three columns (the third arrives by DPP from lane + 1) merged by
 // one v_min3.
-// SQ > 0 (inference, CB = 2): the first Fire's squeeze (1x1 conv 64 -> SQ = 16 channels + bias + ReLU, src/model/squeezedet.py:17-18)
+// SQ > 0 (16): the first Fire's squeeze (1x1 conv 64 -> SQ channels + bias + ReLU, src/model/squeezedet.py:17-18)
 // is applied to the pooled pixels before they leave the registers, and ONLY its output is written (y: NHWC [B][Hp][Wp][SQ]): a
 // pooled lane holds channels 16j + 4g + t of its pixel = the B operand (k = g, column = pixel) of v_mfma_f32_16x16x4_f32 for input
 // channel 16j + 4g + t, so the squeeze is 16 MFMAs per pooled row against squeeze weights pre-arranged as A operands in LDS
@@ -557,17 +519,19 @@ struct StemWaveArgs {
 // neither written nor read back by a separate squeeze launch.
 // ARGMAX and SQ together (training forward): the pooled tensor and its codes are stored as in the ARGMAX form (the backward needs them)
 // and the squeeze output goes to a.ysq; the squeeze launch that would re-read the 153 MB pooled tensor is gone.
-template <int PH, int CB, bool ARGMAX = false, int SQ = 0>
+// ---------------------------------------------------------------------------------------------
+template <int PH> using StemWavePatch = StemPatch<PH, 15, 17>;      // 15 pooled columns per tile, 17 slots per patch row
+
+template <int PH, bool ARGMAX = false, int SQ = 0>
 __global__ __launch_bounds__(256, 2) void stem_wave_kernel(StemWaveArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int PW = CB == 1 ? 7 : 15, CH = 2 * PH + 1, IH = 2 * CH + 1;
-  constexpr int SL = CB == 1 ? 9 : 17, RP = 4 * SL;                                  // 16-byte slots / floats per patch row
-  constexpr int NSLOT = 3 * IH * SL, N_IT = (NSLOT + 63) / 64, BUFF = N_IT * 64 * 4; // floats per buffer
+  using Patch = StemWavePatch<PH>;
+  constexpr int PW = Patch::PW, CH = 2 * PH + 1, IH = Patch::IH, RP = Patch::RP, BUFF = Patch::BUFF;
+  constexpr int CB = 2;                                                              // column blocks per conv row: E, O
   constexpr int K = 27, KSTEPS = 7, NT = 4, N = 64;
-  constexpr unsigned OOB = 0x80000000u;
+  constexpr unsigned OOB = Patch::OOB;
   constexpr int NST = ARGMAX ? PH * NT * 2 + (SQ ? PH : 0) : (SQ ? PH : PH * NT);    // stores per tile (always issued)
-  static_assert(!ARGMAX || CB == 2, "the arg-max epilogue is written for the parity-split layout");
-  static_assert(SQ == 0 || (SQ == 16 && CB == 2), "fused squeeze: 16 channels, parity-split layout");
+  static_assert(SQ == 0 || SQ == 16, "fused squeeze: 16 channels");
   constexpr int NO = (SQ && !ARGMAX) ? SQ : N;                                       // channels per pixel of the tensor behind a.y
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -588,13 +552,14 @@ __global__ __launch_bounds__(256, 2) void stem_wave_kernel(StemWaveArgs a) {
   typedef __attribute__((address_space(3))) const char* lds_cptr_t;   // 32-bit LDS addresses (a generic pointer costs two registers)
 
   // ---- per-lane constants ----
-  int d_off[N_IT];                                     // byte offset of the lane's 16-byte slot from the patch origin
+  int d_off[Patch::N_IT];                              // byte offset of the lane's 16-byte slots from the patch origin
+  // (kept in the kernel: moved into StemPatch, this loop no longer compiles to the code the kernel had -- same text in stem_wgrad_gather_kernel)
 #pragma unroll
-  for (int it = 0; it < N_IT; ++it) {
+  for (int it = 0; it < Patch::N_IT; ++it) {
+    constexpr int SL = Patch::SL, NSLOT = Patch::NSLOT;
     const int slot = it * 64 + lane;
-    const bool real = slot < NSLOT;
     const int ci = slot / (IH * SL), rem = slot - ci * (IH * SL), row = rem / SL, k4 = rem - row * SL;
-    d_off[it] = real ? ((ci * a.Hin + row) * a.Win + 4 * k4) * 4 : (int)OOB;
+    d_off[it] = slot < NSLOT ? ((ci * a.Hin + row) * a.Win + 4 * k4) * 4 : (int)OOB;
   }
   float wreg[KSTEPS][NT];
   lds_cptr_t bp[KSTEPS];                               // B operand of k-step s, conv row 0, (even) column block, buffer 0
@@ -609,8 +574,7 @@ __global__ __launch_bounds__(256, 2) void stem_wave_kernel(StemWaveArgs a) {
   }
   biasW[lane] = a.bias ? a.bias[lane] : 0.f;           // read back by this wave only (epilogue): no barrier
   const f32x4* const biasL = (const f32x4*)(biasW + 4 * g);
-  // the patch origin (input row 4 PH ty - 1, column 4 PW tx - 4) is never negative relative to this base
-  const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x - (a.Win + 4)), 0, 0x7ffffff0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xres = Patch::resource(a.x, a.Win);
   const __amdgpu_buffer_rsrc_t yres = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t qres = __builtin_amdgcn_make_buffer_rsrc((void*)((ARGMAX && SQ) ? a.ysq : a.y), 0, 0x7ffffff0, 0x00020000);
   // codes: one byte per element; idle lanes carry 2^29 (a quarter of the fp32 streams' idle offset), past this resource's range
@@ -623,12 +587,14 @@ __global__ __launch_bounds__(256, 2) void stem_wave_kernel(StemWaveArgs a) {
     asm volatile("s_nop 1" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
   };
-  // lanes that end up with a pooled pixel: conv columns 0, 2, .., 12 (CB = 1) / pooled columns 0..14 (CB = 2)
-  const bool out_lane = CB == 1 ? ((c & 1) == 0 && c < 2 * PW) : (c < PW);
-  const int pcol = CB == 1 ? (c >> 1) : c;
+  // lanes that end up with a pooled pixel: pooled columns 0..14
+  const bool out_lane = c < PW;
+  const int pcol = c;
   const int o_voff = out_lane ? (pcol * NO + 4 * g) * 4 : (int)OOB;
   const int q_voff = out_lane ? (pcol * SQ + 4 * g) * 4 : (int)OOB;      // (ARGMAX + SQ) the lane's slot in a row of the squeeze output
 
+  // soff / inner and dma_in below are this kernel's OWN COPY of StemPatch::origin and StemPatch::dma_in (stem.h; the gather kernel
+  // calls them): with the calls this kernel's code changes (one vector-memory instruction more at best).  Change both together.
   struct Tile { int ty, tx, inner; unsigned soff, osoff; };
   auto tile_at = [&](int t) {
     Tile q;
@@ -639,13 +605,14 @@ __global__ __launch_bounds__(256, 2) void stem_wave_kernel(StemWaveArgs a) {
     const int iy0 = 4 * PH * q.ty - 1, ix0 = 4 * PW * q.tx - 4;
     q.soff = (unsigned)(((b * 3 * a.Hin + 4 * PH * q.ty) * a.Win + 4 * PW * q.tx) * 4);
     q.inner = iy0 >= 0 && iy0 + IH <= a.Hin && ix0 >= 0 && ix0 + RP <= a.Win;
-    q.osoff = (unsigned)((((b * a.Hp + q.ty * PH) * a.Wp + q.tx * PW) * NO) * 4);
+    q.osoff = (unsigned)((((b * a.Hp + q.ty * PH) * a.Wp + q.tx * PW) * NO) * 4);    // byte offset of the tile's first pooled pixel
     return q;
   };
   auto dma_in = [&](const Tile q, int buf) {
+    constexpr int SL = Patch::SL, NSLOT = Patch::NSLOT;
     const int iy0 = 4 * PH * q.ty - 1, ix0 = 4 * PW * q.tx - 4;
 #pragma unroll
-    for (int it = 0; it < N_IT; ++it) {
+    for (int it = 0; it < Patch::N_IT; ++it) {
       int off = d_off[it];
       if (!q.inner) {                                  // uniform: border tile (the slot's row / column are recomputed here only)
         const int slot = it * 64 + lane;
@@ -712,7 +679,7 @@ __global__ __launch_bounds__(256, 2) void stem_wave_kernel(StemWaveArgs a) {
       const float ninf = -__builtin_inff();
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) {
-        const bool col_out = cx0 + (CB == 1 ? c : 2 * c + cb) >= a.Wo;
+        const bool col_out = cx0 + 2 * c + cb >= a.Wo;
 #pragma unroll
         for (int r = 0; r < CH; ++r) {
           const bool out = col_out || cy0 + r >= a.Ho;
@@ -794,30 +761,15 @@ __global__ __launch_bounds__(256, 2) void stem_wave_kernel(StemWaveArgs a) {
           __builtin_amdgcn_sched_barrier(0);
           continue;
         }
-        if constexpr (CB == 1) {
-          const f32x4 v = vmax3(acc[2 * i][0][j], acc[2 * i + 1][0][j], acc[2 * i + 2][0][j]);
-          asm volatile("s_nop 1\n\t"
-                       "v_max_f32_dpp %0, %4, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %1, %5, %5 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %2, %6, %6 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %3, %7, %7 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %0, %4, %0 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %1, %5, %1 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %2, %6, %2 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %3, %7, %3 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                       : "=&v"(h.x), "=&v"(h.y), "=&v"(h.z), "=&v"(h.w)
-                       : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-        } else {
-          const f32x4 ve = vmax3(acc[2 * i][0][j], acc[2 * i + 1][0][j], acc[2 * i + 2][0][j]);
-          const f32x4 vo = vmax3(acc[2 * i][CB - 1][j], acc[2 * i + 1][CB - 1][j], acc[2 * i + 2][CB - 1][j]);
-          asm volatile("v_max_f32 %0, %4, %8\n\tv_max_f32 %1, %5, %9\n\tv_max_f32 %2, %6, %10\n\tv_max_f32 %3, %7, %11\n\t"
-                       "v_max_f32_dpp %0, %4, %0 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %1, %5, %1 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %2, %6, %2 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                       "v_max_f32_dpp %3, %7, %3 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                       : "=&v"(h.x), "=&v"(h.y), "=&v"(h.z), "=&v"(h.w)
-                       : "v"(ve.x), "v"(ve.y), "v"(ve.z), "v"(ve.w), "v"(vo.x), "v"(vo.y), "v"(vo.z), "v"(vo.w));
-        }
+        const f32x4 ve = vmax3(acc[2 * i][0][j], acc[2 * i + 1][0][j], acc[2 * i + 2][0][j]);
+        const f32x4 vo = vmax3(acc[2 * i][1][j], acc[2 * i + 1][1][j], acc[2 * i + 2][1][j]);
+        asm volatile("v_max_f32 %0, %4, %8\n\tv_max_f32 %1, %5, %9\n\tv_max_f32 %2, %6, %10\n\tv_max_f32 %3, %7, %11\n\t"
+                     "v_max_f32_dpp %0, %4, %0 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_max_f32_dpp %1, %5, %1 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_max_f32_dpp %2, %6, %2 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_max_f32_dpp %3, %7, %3 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                     : "=&v"(h.x), "=&v"(h.y), "=&v"(h.z), "=&v"(h.w)
+                     : "v"(ve.x), "v"(ve.y), "v"(ve.z), "v"(ve.w), "v"(vo.x), "v"(vo.y), "v"(vo.z), "v"(vo.w));
         h += biasL[j * 4];
         asm volatile("v_max_f32 %0, 0, %0\n\tv_max_f32 %1, 0, %1\n\tv_max_f32 %2, 0, %2\n\tv_max_f32 %3, 0, %3"
                      : "+v"(h.x), "+v"(h.y), "+v"(h.z), "+v"(h.w));
@@ -852,18 +804,15 @@ __global__ __launch_bounds__(256, 2) void stem_wave_kernel(StemWaveArgs a) {
 #endif
 }
 
-template <int PH, int CB, bool ARGMAX = false, int SQ = 0>
+template <int PH, bool ARGMAX = false, int SQ = 0>
 static int launch_stem_wave(StemWaveArgs a, hipStream_t s) {
-  constexpr int PW = CB == 1 ? 7 : 15, CH = 2 * PH + 1, IH = 2 * CH + 1, SL = CB == 1 ? 9 : 17;
-  constexpr int NSLOT = 3 * IH * SL, N_IT = (NSLOT + 63) / 64;
-  constexpr size_t lds = (size_t)4 * (2 * N_IT * 64 * 16 + 64 * 4) + (SQ ? (1024 + 16) * 4 : 0);
+  using Patch = StemWavePatch<PH>;
+  // per wave: the double patch buffer + its copy of the bias; per workgroup: the squeeze's A operands + bias
+  constexpr size_t lds = (size_t)4 * (2 * Patch::BUFF + 64) * sizeof(float) + (SQ ? (1024 + 16) * sizeof(float) : 0);
   constexpr int OCC = 2;                                          // workgroups per CU (= waves per SIMD) the kernel is built for
   static_assert(OCC * lds <= 160 * 1024, "OCC workgroups per CU");
-  a.tiles_x = sqd_cdiv(a.Wp, PW); a.tiles_y = sqd_cdiv(a.Hp, PH);
-  a.ntiles = a.B * a.tiles_x * a.tiles_y;
-  a.tiles_x_m = a.tiles_x > 1 ? (unsigned)(((1ull << 32) + a.tiles_x - 1) / a.tiles_x) : 0u;
-  a.tiles_y_m = a.tiles_y > 1 ? (unsigned)(((1ull << 32) + a.tiles_y - 1) / a.tiles_y) : 0u;
-  auto kern = stem_wave_kernel<PH, CB, ARGMAX, SQ>;
+  if (!stem_fill_tiles(a, PH, Patch::PW)) return SQD_ERR_UNSUPPORTED;
+  auto kern = stem_wave_kernel<PH, ARGMAX, SQ>;
   static SqdDevOnce attr_once;                 // (per device: ADVICE round 4)
   if (int rc_attr = lds <= 64 * 1024 ? SQD_OK : sqd_max_lds_once(attr_once, (const void*)kern, (int)lds)) return rc_attr;
   const int gx = sqd_even_grid(sqd_cdiv(a.ntiles, 4), OCC * sqd_num_cus());      // over workgroup-sized runs of 4 tiles
@@ -871,57 +820,42 @@ static int launch_stem_wave(StemWaveArgs a, hipStream_t s) {
   return sqd_launch_status();
 }
 
-// Which kernel runs the inference-mode 3x3 stem: 2 = stem_wave_kernel<2, 2> (default; in the bs=20 step 110.9 us against 154.6 us for
-// the workgroup kernel, gpurun_out/r03z), 3 / 4 = stem_wave_kernel<PH, 1> (117.4 / 113.5 us), 0 = the workgroup kernel
-// stem_pool_kernel.  SQD_STEM_WAVE in the environment overrides it (read per call: the parity tests switch it at run time).
-static int stem_wave_variant() {
-  const char* e = getenv("SQD_STEM_WAVE");
-  return e ? atoi(e) : 2;
-}
-
 // x NCHW [B,3,Hin,Win] -> y NHWC [B,Hp,Wp,N] = MaxPool(3,2,ceil)(ReLU(conv(x))); argmax may be NULL.
+// The 3x3 / 64 stem runs stem_wave_kernel where stem_wave_ok holds: two pooled rows per tile at inference, ONE in the training
+// forward (with two, the arg-max epilogue's temporaries spill 42 registers, and every reload queues behind the next patch's DMA
+// in vmcnt order).  Everything else, and SQD_STEM_WAVE=0 (stem.h), runs the workgroup kernel.
 extern "C" int sqd_stem_conv_relu_pool_fwd(const float* x, const float* w, const float* bias, float* y,
                                            unsigned char* argmax, int B, int Hin, int Win, int N, int ksize,
                                            void* stream) {
   SQD_CHECK_ARG(x && w && y && B > 0 && Hin > 0 && Win > 0);
   SQD_CHECK_ARG(((uintptr_t)y & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0) && ((uintptr_t)argmax & 3) == 0);
+  const StemGeom g = stem_geom(Hin, Win, ksize);
+  SQD_CHECK_ARG(g.Ho >= 3 && g.Wo >= 3);
+  hipStream_t s = (hipStream_t)stream;
+  if (!stem_hook_off("SQD_STEM_WAVE") && stem_wave_ok(g, B, N, x)) {
+    const StemWaveArgs wa = stem_wave_args(g, B, x, w, bias, y, argmax, nullptr, nullptr, nullptr);
+    return argmax ? launch_stem_wave<1, true>(wa, s) : launch_stem_wave<2>(wa, s);
+  }
   StemPoolArgs a;
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.amax = argmax; a.B = B; a.Hin = Hin; a.Win = Win; a.N = N;
-  const int pad = ksize == 3 ? 1 : 3;
-  a.Ho = (Hin + 2 * pad - ksize) / 2 + 1; a.Wo = (Win + 2 * pad - ksize) / 2 + 1;
-  SQD_CHECK_ARG(a.Ho >= 3 && a.Wo >= 3);
-  a.Hp = (a.Ho - 3 + 1) / 2 + 1; a.Wp = (a.Wo - 3 + 1) / 2 + 1;
-  hipStream_t s = (hipStream_t)stream;
-  const int variant = stem_wave_variant();
-  if (ksize == 3 && N == 64 && variant && (Win & 3) == 0 && ((uintptr_t)x & 15) == 0 &&
-      (long long)B * 3 * Hin * Win * 4 < (1ll << 31) && (long long)B * a.Hp * a.Wp * N * 4 < (1ll << 31)) {
-    StemWaveArgs wa;
-    wa.x = x; wa.w = w; wa.bias = bias; wa.y = y; wa.amax = argmax; wa.wsq = nullptr; wa.bsq = nullptr; wa.ysq = nullptr; wa.B = B; wa.Hin = Hin; wa.Win = Win; wa.Ho = a.Ho; wa.Wo = a.Wo; wa.Hp = a.Hp; wa.Wp = a.Wp;
-    // training forward: one pooled row per tile -- with two (variant 5) the arg-max epilogue's temporaries spill 42 registers, and
-    // every reload queues behind the next patch's DMA in vmcnt order
-    if (argmax) return variant == 5 ? launch_stem_wave<2, 2, true>(wa, s) : launch_stem_wave<1, 2, true>(wa, s);
-    return variant == 4 ? launch_stem_wave<4, 1>(wa, s) : (variant == 3 ? launch_stem_wave<3, 1>(wa, s) : launch_stem_wave<2, 2>(wa, s));
-  }
-  if (ksize == 3 && N == 64) return launch_stem_pool<3, 1, 4>(a, s);
-  if (ksize == 7 && N == 96) return launch_stem_pool<7, 3, 6>(a, s);
-  return SQD_ERR_UNSUPPORTED;
+  a.Ho = g.Ho; a.Wo = g.Wo; a.Hp = g.Hp; a.Wp = g.Wp;
+  return stem_dispatch(ksize, N, [&](auto sh) {
+    using S = decltype(sh);
+    return launch_stem_pool<S::KS, S::PAD, S::NT>(a, s);
+  });
 }
 
 // features[0..2] + the first Fire's squeeze in one launch (inference): x NCHW [B,3,Hin,Win] -> y NHWC [B,Hp,Wp,nsq] =
-// ReLU(squeeze(MaxPool(3,2,ceil)(ReLU(conv(x))))).  Only the 3x3 / 64-channel stem with a 16-channel squeeze, Win % 4 == 0 and a
-// 16-byte aligned image (SQD_ERR_UNSUPPORTED otherwise: the caller keeps the two launches).
+// ReLU(squeeze(MaxPool(3,2,ceil)(ReLU(conv(x))))).  Only where stem_wave_ok holds, with a 16-channel squeeze
+// (SQD_ERR_UNSUPPORTED otherwise: the caller keeps the two launches).
 extern "C" int sqd_stem_pool_squeeze_fwd(const float* x, const float* w, const float* bias, const float* wsq, const float* bsq,
                                          float* y, int B, int Hin, int Win, int N, int ksize, int nsq, void* stream) {
   SQD_CHECK_ARG(x && w && wsq && y && B > 0 && Hin > 0 && Win > 0);
   SQD_CHECK_ARG(((uintptr_t)y & 15) == 0 && ((uintptr_t)wsq & 15) == 0);
-  if (!(ksize == 3 && N == 64 && nsq == 16 && (Win & 3) == 0 && ((uintptr_t)x & 15) == 0)) return SQD_ERR_UNSUPPORTED;
-  StemWaveArgs wa;
-  wa.x = x; wa.w = w; wa.bias = bias; wa.y = y; wa.amax = nullptr; wa.wsq = wsq; wa.bsq = bsq; wa.ysq = nullptr; wa.B = B; wa.Hin = Hin; wa.Win = Win;
-  wa.Ho = (Hin + 2 - 3) / 2 + 1; wa.Wo = (Win + 2 - 3) / 2 + 1;
-  SQD_CHECK_ARG(wa.Ho >= 3 && wa.Wo >= 3);
-  wa.Hp = (wa.Ho - 3 + 1) / 2 + 1; wa.Wp = (wa.Wo - 3 + 1) / 2 + 1;
-  if ((long long)B * 3 * Hin * Win * 4 >= (1ll << 31) || (long long)B * wa.Hp * wa.Wp * N * 4 >= (1ll << 31)) return SQD_ERR_UNSUPPORTED;
-  return launch_stem_wave<2, 2, false, 16>(wa, (hipStream_t)stream);
+  const StemGeom g = stem_geom(Hin, Win, ksize);
+  if (nsq != 16 || !stem_wave_ok(g, B, N, x)) return SQD_ERR_UNSUPPORTED;
+  SQD_CHECK_ARG(g.Ho >= 3 && g.Wo >= 3);
+  return launch_stem_wave<2, false, 16>(stem_wave_args(g, B, x, w, bias, y, nullptr, wsq, bsq, nullptr), (hipStream_t)stream);
 }
 
 // Training form of sqd_stem_pool_squeeze_fwd: the pooled tensor y_pooled [B,Hp,Wp,64] and its arg-max / ReLU codes (argmax, one byte
@@ -933,16 +867,12 @@ extern "C" int sqd_stem_pool_squeeze_train_fwd(const float* x, const float* w, c
   SQD_CHECK_ARG(x && w && wsq && y_pooled && argmax && y_sq && B > 0 && Hin > 0 && Win > 0);
   SQD_CHECK_ARG(((uintptr_t)y_pooled & 15) == 0 && ((uintptr_t)y_sq & 15) == 0 && ((uintptr_t)wsq & 15) == 0 && ((uintptr_t)argmax & 3) == 0);
   SQD_CHECK_ARG(!bias || ((uintptr_t)bias & 15) == 0);
-  if (!(ksize == 3 && N == 64 && nsq == 16 && (Win & 3) == 0 && ((uintptr_t)x & 15) == 0)) return SQD_ERR_UNSUPPORTED;
-  StemWaveArgs wa;
-  wa.x = x; wa.w = w; wa.bias = bias; wa.y = y_pooled; wa.amax = argmax; wa.wsq = wsq; wa.bsq = bsq; wa.ysq = y_sq;
-  wa.B = B; wa.Hin = Hin; wa.Win = Win;
-  wa.Ho = (Hin + 2 - 3) / 2 + 1; wa.Wo = (Win + 2 - 3) / 2 + 1;
-  SQD_CHECK_ARG(wa.Ho >= 3 && wa.Wo >= 3);
-  wa.Hp = (wa.Ho - 3 + 1) / 2 + 1; wa.Wp = (wa.Wo - 3 + 1) / 2 + 1;
-  if ((long long)B * 3 * Hin * Win * 4 >= (1ll << 31) || (long long)B * wa.Hp * wa.Wp * N * 4 >= (1ll << 31)) return SQD_ERR_UNSUPPORTED;
-  return launch_stem_wave<1, 2, true, 16>(wa, (hipStream_t)stream);
+  const StemGeom g = stem_geom(Hin, Win, ksize);
+  if (nsq != 16 || !stem_wave_ok(g, B, N, x)) return SQD_ERR_UNSUPPORTED;
+  SQD_CHECK_ARG(g.Ho >= 3 && g.Wo >= 3);
+  return launch_stem_wave<1, true, 16>(stem_wave_args(g, B, x, w, bias, y_pooled, argmax, wsq, bsq, y_sq), (hipStream_t)stream);
 }
+
 
 // ---------------------------------------------------------------------------------------------
 // MaxPool2d(kernel 3, stride 2, ceil_mode=True), NHWC.  Ho = ceil((H-3)/2)+1 (PyTorch additionally

@@ -2,16 +2,13 @@
 // src/model/squeezedet.py:34-36 as autograd derives it).  Its own translation unit because it is built WITHOUT the SLP vectoriser
 // (Makefile): left on, it pairs the scalar tap-0 accumulators into 64-bit register tuples, which on gfx950 must be even-aligned,
 // and the kernel goes from 171 registers to 256 + 62 spilled.
-#include "stem_wgrad.h"
+#include "stem.h"
 #include <type_traits>
-#include <stdlib.h>
-
-typedef __attribute__((address_space(3))) void* wg_lds_ptr_t;
 
 // ---------------------------------------------------------------------------------------------
 // Stem weight gradient behind the fused forward, third generation (round 3): a GATHER on the vector ALU instead of a
 // dense GEMM on the matrix cores.  The gradient of the conv output is dPool routed through the arg-max: of the 4 conv
-// pixels a pooled pixel stands for, ONE per channel is non-zero.  The dense form (stem_wgrad_pooled_kernel above) rebuilds
+// pixels a pooled pixel stands for, ONE per channel is non-zero.  The dense form (stem_wgrad_pooled_kernel, stem_wgrad.hip) rebuilds
 // that 75 %-zero tensor in LDS (a zero fill, four scatter phases, six workgroup barriers per tile) and multiplies all of
 // it: 242 us per batch of 20, a third of its MFMAs for the bias gradient.  Here every (pooled pixel, channel) item is
 // ONE 27-tap dot-product update:
@@ -19,8 +16,8 @@ typedef __attribute__((address_space(3))) void* wg_lds_ptr_t;
 //   * lane = (channel pair cp, pixel sub-index): it owns channels 2cp, 2cp+1 for the whole kernel -- 2 x 27 + 2
 //     accumulators in registers, no reduction before the end -- and walks its wave's pooled tiles (2 x 8 pixels, two
 //     pixels per step across the lane's sub-index; four channels per lane would need 112 accumulators: spills);
-//   * the wave's NCHW image patch arrives by 16-byte buffer-resource LDS-DMA in a wave-private double buffer (same patch
-//     geometry and zero-filled borders as stem_wave_kernel, stem_pool.hip); the arg-max codes (2 channels per load) and
+//   * the wave's NCHW image patch arrives by 16-byte buffer-resource LDS-DMA in a wave-private double buffer (StemPatch, stem.h:
+//     the loader, patch geometry and zero-filled borders of stem_wave_kernel); the arg-max codes (2 channels per load) and
 //     dPool pairs of the NEXT tile are requested into the registers of the pixel group that has just been decoded;
 //   * per channel: code -> window origin in the patch (three integer instructions), then per (plane, tap row) one 4-byte
 //     and one 8-byte LDS read (taps 1, 2 are 8-byte aligned by construction) feeding one v_fma + one v_pk_fma;
@@ -32,18 +29,20 @@ typedef __attribute__((address_space(3))) void* wg_lds_ptr_t;
 // (72 per pixel group of a wave) and by the 306 MB of dPool / codes / image it streams.
 // Needs Win % 4 == 0 and a 16-byte aligned image (else the launcher keeps the dense kernel).
 // ---------------------------------------------------------------------------------------------
+// A wave's tile is 2 x 8 pooled pixels.  Patch rows hold one 16-byte slot more than the 10 the taps need: with a 44-float pitch the
+// three window rows of a pixel (2 RP dy floats apart) start 0 / 24 / 16 banks apart for the 4-byte reads (32 banks) and 0 / 24 / 48
+// for the 8-byte reads (64 banks) -- with 40 floats rows 0 and 2 met on the same banks (2-way conflicts of the 4-byte tap-0 reads)
+typedef StemPatch<2, 8, 11> StemGatherPatch;
+
 // OCC = waves per SIMD the register budget is held to (2: 171 registers; 3: 168 with a few spilled)
 template <bool HAS_PL, int OCC>
 __global__ __launch_bounds__(256, OCC) void stem_wgrad_gather_kernel(StemWgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int PH = 2, PW = 8, N = 64, K = 27;
-  // patch rows, 16-byte slots / floats per row.  One slot more than the 10 the taps need: with a 44-float pitch the three window rows
-  // of a pixel (2 RP dy floats apart) start 0 / 24 / 16 banks apart for the 4-byte reads (32 banks) and 0 / 24 / 48 for the 8-byte
-  // reads (64 banks) -- with 40 floats rows 0 and 2 met on the same banks (2-way conflicts of the 4-byte tap-0 reads)
-  constexpr int IH = 4 * PH + 3, SL = PW + 3, RP = 4 * SL;
-  constexpr int NSLOT = 3 * IH * SL, N_IT = (NSLOT + 63) / 64, BUFF = N_IT * 64 * 4; // floats per buffer
+  using Patch = StemGatherPatch;
+  constexpr int PH = Patch::PH, PW = Patch::PW, N = 64, K = 27;
+  constexpr int IH = Patch::IH, RP = Patch::RP, BUFF = Patch::BUFF;
   constexpr int NG = PH * PW / 2;                                                    // pixel groups (2 pixels) per tile
-  constexpr unsigned OOB = 0x80000000u;
+  constexpr unsigned OOB = Patch::OOB;
   static_assert(PW == 8 && NG == 8, "group -> (row, column) split and the item enumeration below assume a 2 x 8 tile");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   typedef __attribute__((address_space(3))) const char* lds_cptr_t;
@@ -55,14 +54,16 @@ __global__ __launch_bounds__(256, OCC) void stem_wgrad_gather_kernel(StemWgradAr
   const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
   float* const bufW = smem + wave_s * (2 * BUFF);
 
-  int d_off[N_IT];                                     // byte offset of the lane's 16-byte slot from the patch origin
+  int d_off[Patch::N_IT];                              // byte offset of the lane's 16-byte slots from the patch origin
+  // (kept in the kernel: moved into StemPatch, this loop no longer compiles to the code the kernel had -- same text in stem_wave_kernel, stem_pool.hip)
 #pragma unroll
-  for (int it = 0; it < N_IT; ++it) {
+  for (int it = 0; it < Patch::N_IT; ++it) {
+    constexpr int SL = Patch::SL, NSLOT = Patch::NSLOT;
     const int slot = it * 64 + lane;
     const int ci = slot / (IH * SL), rem = slot - ci * (IH * SL), row = rem / SL, k4 = rem - row * SL;
     d_off[it] = slot < NSLOT ? ((ci * a.Hin + row) * a.Win + 4 * k4) * 4 : (int)OOB;
   }
-  const __amdgpu_buffer_rsrc_t xres = __builtin_amdgcn_make_buffer_rsrc((void*)(a.img - (a.Win + 4)), 0, 0x7ffffff0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t xres = Patch::resource(a.img, a.Win);
   const __amdgpu_buffer_rsrc_t dres = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, 0x7ffffff0, 0x00020000);
   const __amdgpu_buffer_rsrc_t cres = __builtin_amdgcn_make_buffer_rsrc((void*)a.amax, 0, a.B * a.Hp * a.Wp * N, 0x00020000);
   const __amdgpu_buffer_rsrc_t pres = __builtin_amdgcn_make_buffer_rsrc((void*)(HAS_PL ? a.pooled : a.dy), 0, 0x7ffffff0, 0x00020000);
@@ -78,25 +79,12 @@ __global__ __launch_bounds__(256, OCC) void stem_wgrad_gather_kernel(StemWgradAr
     z.tx = t - t1 * a.tiles_x;
     const int b = t1 / a.tiles_y;
     z.ty = t1 - b * a.tiles_y;
-    const int iy0 = 4 * PH * z.ty - 1, ix0 = 4 * PW * z.tx - 4;
-    z.soff = (unsigned)(((b * 3 * a.Hin + 4 * PH * z.ty) * a.Win + 4 * PW * z.tx) * 4);
-    z.inner = iy0 >= 0 && iy0 + IH <= a.Hin && ix0 >= 0 && ix0 + RP <= a.Win;
+    Patch::origin(b, z.ty, z.tx, a, z.soff, z.inner);
     z.eoff = (unsigned)(((b * a.Hp + z.ty * PH) * a.Wp + z.tx * PW) * N);       // element index of the tile's first pooled pixel
     return z;
   };
   auto dma_in = [&](const Tile z, int buf) __attribute__((always_inline)) {
-    const int iy0 = 4 * PH * z.ty - 1, ix0 = 4 * PW * z.tx - 4;
-#pragma unroll
-    for (int it = 0; it < N_IT; ++it) {
-      int off = d_off[it];
-      if (!z.inner) {                                  // uniform: border tile
-        const int slot = it * 64 + lane;
-        const int ci = slot / (IH * SL), rem = slot - ci * (IH * SL), row = rem / SL, k4 = rem - row * SL;
-        const bool ok = slot < NSLOT && (unsigned)(iy0 + row) < (unsigned)a.Hin && (unsigned)(ix0 + 4 * k4) < (unsigned)a.Win;
-        off = ok ? off : (int)OOB;
-      }
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xres, (wg_lds_ptr_t)(bufW + buf * BUFF + it * 256), 16, off, (int)z.soff, 0, 0);
-    }
+    Patch::dma_in(xres, bufW + buf * BUFF, d_off, z.ty, z.tx, z.inner, z.soff, lane, a);
   };
   struct Items { unsigned cw[NG]; f32x2 dp[NG]; f32x2 pl[HAS_PL ? NG : 1]; };
   auto fetch_group = [&](const Tile z, Items& it, auto gic, bool want) __attribute__((always_inline)) {
@@ -243,11 +231,11 @@ __global__ __launch_bounds__(256, OCC) void stem_wgrad_gather_kernel(StemWgradAr
 
 // returns the number of slabs written (= workgroups), or a negative status
 int launch_stem_wgrad_gather(StemWgradArgs a, int S, hipStream_t s) {
-  constexpr int IH = 11, SL = 11, N_IT = (3 * IH * SL + 63) / 64;
-  constexpr size_t lds_patch = (size_t)4 * 2 * N_IT * 64 * 16, lds_red = (size_t)4 * 56 * 32 * 4;
+  using Patch = StemGatherPatch;
+  constexpr size_t lds_patch = (size_t)4 * 2 * Patch::BUFF * sizeof(float), lds_red = (size_t)4 * 56 * 32 * 4;
   constexpr size_t lds = lds_patch > lds_red ? lds_patch : lds_red;
   constexpr int OCC = 2;                                 // workgroups per CU the launch is sized for (3 measured no faster)
-  a.tiles_x = sqd_cdiv(a.Wp, 8); a.tiles_y = sqd_cdiv(a.Hp, 2);
+  a.tiles_x = sqd_cdiv(a.Wp, Patch::PW); a.tiles_y = sqd_cdiv(a.Hp, Patch::PH);
   a.nblocks = a.B * a.tiles_x * a.tiles_y;
   int g = sqd_cdiv(a.nblocks, 4);                        // slabs: one resident round at most, and no more than the caller's S
   if (g > OCC * sqd_num_cus()) g = OCC * sqd_num_cus();

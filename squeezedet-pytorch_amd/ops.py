@@ -443,23 +443,32 @@ def pool_squeeze(x, x_coff, C, plan, y, y_coff):
     return y
 
 
+_STEMS = ((3, 64), (7, 96))        # (kernel size, output channels) the library has stem kernels for
+
+
+def _stem_args(name, image, weight, bias, unsupported=None):
+    """The checks every stem forward wrapper starts with, under its own name in the messages (``unsupported``: the wrapper's own
+    message for a weight no stem kernel takes); -> the contiguous operands (image, weight, bias or None) and the geometry
+    B, H, W, N, k, Ho, Wo."""
+    if image.dim() != 4 or image.shape[1] != 3 or image.dtype != torch.float32 or not image.is_cuda:
+        raise ValueError(f'{name}: image must be fp32 CUDA NCHW with 3 channels, got {tuple(image.shape)}')
+    N, ci, k, k2 = weight.shape
+    if ci != 3 or k != k2 or (k, N) not in _STEMS:
+        raise ValueError(unsupported or f'{name}: unsupported weight {tuple(weight.shape)}')
+    B, _, H, W = image.shape
+    Ho, Wo = stem_out_size(H, W, k)
+    return (image.contiguous(), weight.detach().contiguous(), None if bias is None else bias.detach().contiguous(),
+            B, H, W, N, k, Ho, Wo)
+
+
 def stem_conv_relu(image, weight, bias, out=None, relu=True):
     """image NCHW [B,3,H,W]; weight OIHW [N,3,k,k] (the checkpoint tensor as is); -> NHWC [B,Ho,Wo,N]
     (``relu=False``: the bare convolution)."""
-    if image.dim() != 4 or image.shape[1] != 3 or image.dtype != torch.float32 or not image.is_cuda:
-        raise ValueError(f'stem: image must be fp32 CUDA NCHW with 3 channels, got {tuple(image.shape)}')
-    image = image.contiguous()
-    N, ci, k, k2 = weight.shape
-    if ci != 3 or k != k2 or (k, N) not in ((3, 64), (7, 96)):
-        raise ValueError(f'stem: unsupported weight {tuple(weight.shape)}')
-    B, _, H, W = image.shape
-    Ho, Wo = stem_out_size(H, W, k)
+    image, w, b, B, H, W, N, k, Ho, Wo = _stem_args('stem', image, weight, bias)
     if out is None:
         out = torch.empty(B, Ho, Wo, N, device=image.device, dtype=torch.float32)
     elif tuple(out.shape) != (B, Ho, Wo, N):
         raise ValueError('stem: bad out shape')
-    w = weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
     br = _Bracket(f'stem_conv<{k}>', f'stem {H}x{W}', 2.0 * B * Ho * Wo * N * 3 * k * k,
                   4.0 * (B * 3 * H * W + B * Ho * Wo * N)) if timing._timer is not None else None
     rc = nat.lib().sqd_stem_conv_fwd(nat.ptr(image), nat.ptr(w), nat.ptr(b), nat.ptr(out), B, H, W, N, k, int(bool(relu)),
@@ -472,22 +481,13 @@ def stem_conv_relu(image, weight, bias, out=None, relu=True):
 
 def stem_pool(image, weight, bias, argmax=None):
     """Fused conv(3->N,k,s2)+ReLU+MaxPool(3,2,ceil): NCHW image -> NHWC pooled features [B,Hp,Wp,N]."""
-    if image.dim() != 4 or image.shape[1] != 3 or image.dtype != torch.float32 or not image.is_cuda:
-        raise ValueError(f'stem_pool: image must be fp32 CUDA NCHW with 3 channels, got {tuple(image.shape)}')
-    image = image.contiguous()
-    N, ci, k, k2 = weight.shape
-    if ci != 3 or k != k2 or (k, N) not in ((3, 64), (7, 96)):
-        raise ValueError(f'stem_pool: unsupported weight {tuple(weight.shape)}')
-    B, _, H, W = image.shape
-    Ho, Wo = stem_out_size(H, W, k)
+    image, w, b, B, H, W, N, k, Ho, Wo = _stem_args('stem_pool', image, weight, bias)
     if Ho < 3 or Wo < 3:
         raise ValueError('stem_pool: input too small')
     Hp, Wp = pool_out_size(Ho, Wo)
     out = torch.empty(B, Hp, Wp, N, device=image.device, dtype=torch.float32)
     if argmax is not None and (tuple(argmax.shape) != (B, Hp, Wp, N) or argmax.dtype != torch.uint8):
         raise ValueError('stem_pool: bad argmax tensor')
-    w = weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
     br = _Bracket(f'stem_pool<{k}>', f'stem+pool {H}x{W}', 2.0 * B * Ho * Wo * N * 3 * k * k,
                   4.0 * (B * 3 * H * W + B * Hp * Wp * N)) if timing._timer is not None else None
     rc = nat.lib().sqd_stem_conv_relu_pool_fwd(nat.ptr(image), nat.ptr(w), nat.ptr(b), nat.ptr(out), nat.ptr(argmax), B, H, W, N, k,
@@ -509,21 +509,15 @@ def stem_pool_squeeze(image, weight, bias, sq_weight, sq_bias, argmax=None):
     (src/model/squeezedet.py:34-37, :17-18).  Inference (``argmax`` None): NCHW image -> NHWC squeeze output [B,Hp,Wp,16]; the pooled
     tensor is never written.  Training (``argmax``: uint8 [B,Hp,Wp,64]): -> (squeeze output, pooled tensor); the pooled tensor and
     its codes are stored for the backward as by ``stem_pool(argmax=)``."""
-    if image.dim() != 4 or image.shape[1] != 3 or image.dtype != torch.float32 or not image.is_cuda:
-        raise ValueError(f'stem_pool_squeeze: image must be fp32 CUDA NCHW with 3 channels, got {tuple(image.shape)}')
-    image = image.contiguous()
-    N, ci, k, k2 = weight.shape
+    unsupported = f'stem_pool_squeeze: unsupported geometry {tuple(image.shape)} / {tuple(weight.shape)} / {tuple(sq_weight.shape)}'
+    image, w, b, B, H, W, N, k, Ho, Wo = _stem_args('stem_pool_squeeze', image, weight, bias, unsupported)
     nsq = sq_weight.shape[0]
-    if ci != 3 or k != k2 or tuple(sq_weight.shape[1:]) != (N, 1, 1) or not stem_pool_squeeze_ok(image.shape, weight.shape, nsq):
-        raise ValueError(f'stem_pool_squeeze: unsupported geometry {tuple(image.shape)} / {tuple(weight.shape)} / {tuple(sq_weight.shape)}')
-    B, _, H, W = image.shape
-    Ho, Wo = stem_out_size(H, W, k)
+    if tuple(sq_weight.shape[1:]) != (N, 1, 1) or not stem_pool_squeeze_ok(image.shape, weight.shape, nsq):
+        raise ValueError(unsupported)
     Hp, Wp = pool_out_size(Ho, Wo)
     if argmax is not None and (tuple(argmax.shape) != (B, Hp, Wp, N) or argmax.dtype != torch.uint8 or not argmax.is_contiguous()):
         raise ValueError('stem_pool_squeeze: bad argmax tensor')
     out = torch.empty(B, Hp, Wp, nsq, device=image.device, dtype=torch.float32)
-    w = weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
     ws = sq_weight.detach().contiguous()
     bs = None if sq_bias is None else sq_bias.detach().contiguous()
     br = _Bracket(f'stem_pool_sq{"_train" if argmax is not None else ""}<{k}>', f'stem+pool+squeeze {H}x{W} S{nsq}',
@@ -1151,6 +1145,17 @@ def _check_stem_out(dw, db, N, ksize):
         raise ValueError('stem wgrad: out=(dw, db) must be contiguous fp32 [N,3,k,k] / [N]')
 
 
+def _stem_wgrad_buffers(B, Ho, Wo, N, ksize, device, out):
+    """-> (S, slab, dw, db): the split-K workspace of a stem weight gradient (one slab per conv tile of 8 x 16 pixels, at most 1024)
+    and its checked outputs."""
+    S = max(1, min(B * -(-Ho // 8) * -(-Wo // 16), 1024))
+    slab = torch.empty(S * (N * 3 * ksize * ksize + N), device=device, dtype=torch.float32)
+    dw, db = out if out is not None else (torch.empty(N, 3, ksize, ksize, device=device, dtype=torch.float32),
+                                          torch.empty(N, device=device, dtype=torch.float32))
+    _check_stem_out(dw, db, N, ksize)
+    return S, slab, dw, db
+
+
 def stem_wgrad(dy, image, N, ksize, out=None):
     """(dW [N,3,k,k], db [N]) of the stem from dy NHWC [B,Ho,Wo,N] (ReLU-masked) and the NCHW image."""
     _check_nhwc(dy, 'dy')
@@ -1158,15 +1163,10 @@ def stem_wgrad(dy, image, N, ksize, out=None):
     if n != N or image.dim() != 4 or image.shape[0] != B or image.shape[1] != 3 or not image.is_contiguous():
         raise ValueError('stem_wgrad: geometry mismatch')
     H, W = image.shape[2], image.shape[3]
-    if stem_out_size(H, W, ksize) != (Ho, Wo) or (ksize, N) not in ((3, 64), (7, 96)):
+    if stem_out_size(H, W, ksize) != (Ho, Wo) or (ksize, N) not in _STEMS:
         raise ValueError('stem_wgrad: unsupported geometry')
-    nblocks = B * -(-Ho // 8) * -(-Wo // 16)
-    S = max(1, min(nblocks, 1024))
     K = 3 * ksize * ksize
-    slab = torch.empty(S * (N * K + N), device=dy.device, dtype=torch.float32)
-    dw, db = out if out is not None else (torch.empty(N, 3, ksize, ksize, device=dy.device, dtype=torch.float32),
-                                          torch.empty(N, device=dy.device, dtype=torch.float32))
-    _check_stem_out(dw, db, N, ksize)
+    S, slab, dw, db = _stem_wgrad_buffers(B, Ho, Wo, N, ksize, dy.device, out)
     br = _Bracket(f'stem_wgrad<{ksize}>', f'stem wgrad {H}x{W}', 2.0 * B * Ho * Wo * N * K,
                   4.0 * (B * Ho * Wo * N + B * 3 * H * W)) if timing._timer is not None else None
     rc = nat.lib().sqd_stem_wgrad(nat.ptr(dy), nat.ptr(image), nat.ptr(slab), nat.ptr(dw), nat.ptr(db), B, H, W, N, ksize, S,
@@ -1191,15 +1191,10 @@ def stem_wgrad_pooled(dpool, pooled, argmax, image, N, ksize, out=None):
         raise ValueError('stem_wgrad_pooled: bad image')
     H, W = image.shape[2], image.shape[3]
     Ho, Wo = stem_out_size(H, W, ksize)
-    if pool_out_size(Ho, Wo) != (Hp, Wp) or (ksize, N) not in ((3, 64), (7, 96)):
+    if pool_out_size(Ho, Wo) != (Hp, Wp) or (ksize, N) not in _STEMS:
         raise ValueError('stem_wgrad_pooled: unsupported geometry')
-    nblocks = B * -(-Ho // 8) * -(-Wo // 16)
-    S = max(1, min(nblocks, 1024))
     K = 3 * ksize * ksize
-    slab = torch.empty(S * (N * K + N), device=dpool.device, dtype=torch.float32)
-    dw, db = out if out is not None else (torch.empty(N, 3, ksize, ksize, device=dpool.device, dtype=torch.float32),
-                                          torch.empty(N, device=dpool.device, dtype=torch.float32))
-    _check_stem_out(dw, db, N, ksize)
+    S, slab, dw, db = _stem_wgrad_buffers(B, Ho, Wo, N, ksize, dpool.device, out)
     br = _Bracket(f'stem_wgrad_pooled<{ksize}>', f'stem wgrad (pooled) {H}x{W}', 2.0 * B * Ho * Wo * N * K,
                   4.0 * (B * Hp * Wp * N * (2.25 if pooled is not None else 1.25) + B * 3 * H * W)) if timing._timer is not None else None
     rc = nat.lib().sqd_stem_wgrad_pooled(nat.ptr(dpool), nat.ptr(pooled), nat.ptr(argmax), nat.ptr(image), nat.ptr(slab), nat.ptr(dw),

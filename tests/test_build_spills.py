@@ -41,9 +41,9 @@ def test_wave_autonomous_kernels_do_not_spill():
     shipped = [k for k in g if 'stem_wgrad_gather_kernelILb0ELi2E' in k]
     assert shipped and all(g[k] == 0 for k in shipped), {k: g[k] for k in shipped}
     s = _spills('stem_pool.hip', [])
-    want = ['stem_wave_kernelILi2ELi2ELb0ELi0E',       # inference stem
-            'stem_wave_kernelILi2ELi2ELb0ELi16E',      # inference stem + the first Fire's squeeze
-            'stem_wave_kernelILi1ELi2ELb1ELi0E']       # training stem (arg-max codes)
+    want = ['stem_wave_kernelILi2ELb0ELi0E',          # inference stem
+            'stem_wave_kernelILi2ELb0ELi16E',         # inference stem + the first Fire's squeeze
+            'stem_wave_kernelILi1ELb1ELi0E']          # training stem (arg-max codes)
     for w in want:
         hits = [k for k in s if w in k]
         assert hits, (w, sorted(s)[:8])
@@ -69,7 +69,7 @@ def test_counted_wait_kernels_of_the_training_step_do_not_spill():
         assert len(hits) >= 4, (pat, sorted(c)[:6])
         assert all(c[k] == (0, 0) for k in hits), {k: c[k] for k in hits if c[k] != (0, 0)}
     s = _spills('stem_pool.hip', [], scratch=True)
-    hits = [k for k in s if 'stem_wave_kernelILi1ELi2ELb1ELi16E' in k]
+    hits = [k for k in s if 'stem_wave_kernelILi1ELb1ELi16E' in k]
     assert hits and all(s[k] == (0, 0) for k in hits), {k: s[k] for k in hits}
     k = _spills('conv_wino_sk.hip', WINO, scratch=True)
     plain = [n for n in k if 'conv_wino_sk_kernelILb0E' in n]

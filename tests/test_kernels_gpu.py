@@ -187,10 +187,10 @@ def test_fused_stem_pool(k, N, H, W):
     assert torch.equal(ops.stem_pool(x.cuda(), w.cuda(), b.cuda()), y)
 
 
-@pytest.mark.parametrize("variant", ["2", "3", "4"])
+@pytest.mark.parametrize("variant", ["2"])
 @pytest.mark.parametrize("H,W", [(64, 96), (50, 68), (37, 44), (12, 16), (9, 8), (130, 250 * 4)])
 def test_stem_wave_kernels(variant, H, W, monkeypatch):
-    """The wave-autonomous inference stem (stem_wave_kernel<PH, CB>, selected by SQD_STEM_WAVE) == features[0..2] of the reference
+    """The wave-autonomous inference stem (stem_wave_kernel<PH>; SQD_STEM_WAVE=0 selects the workgroup kernel) == features[0..2] of the reference
     (src/model/squeezedet.py:34-36) and, bit for bit, the workgroup kernel it replaces: widths that are a multiple of 4 (its 16-byte
     row DMA), maps smaller than one tile, borders on all four sides, partial last tiles."""
     ops = _ops()

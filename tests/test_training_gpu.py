@@ -241,6 +241,38 @@ def test_stem_wgrad_pooled(k, N, H, W):
     assert torch.equal(dw, dw3) and torch.equal(db, db3)
 
 
+@pytest.mark.parametrize("H,W", [(12, 16), (37, 44), (64, 96)])
+def test_stem_wgrad_pooled_dense_and_gather_agree(H, W, monkeypatch):
+    """The two kernels behind ops.stem_wgrad_pooled for the 3x3 / 64 stem -- the gather kernel (shipped) and the dense
+    stem_wgrad_pooled_kernel (SQD_STEM_WGRAD_GATHER=0, read per call) -- on the SAME arg-max codes: dW and db agree to 1e-5 of
+    max(1, |grad|max) (the bound of tools/fuzz_stem.py: they sum the same terms in different orders), and each is bit-identical
+    run to run.  A map smaller than one tile, partial tiles with all four borders, whole tiles."""
+    from squeezedet_pytorch_amd import ops
+    x = _rand(2, 3, H, W, seed=41)
+    w = _rand(64, 3, 3, 3, seed=42, scale=0.2).requires_grad_(True)
+    b = _rand(64, seed=43, scale=0.1).requires_grad_(True)
+    y = F.max_pool2d(F.relu(F.conv2d(x, w, b, stride=2, padding=1)), 3, 2, ceil_mode=True)
+    dy = _rand(*y.shape, seed=44)
+    y.backward(dy)
+    gmax, bmax = max(1.0, float(w.grad.abs().max())), max(1.0, float(b.grad.abs().max()))
+    xg, dyg = x.cuda(), _nhwc(dy).cuda()
+    am = torch.empty(*_nhwc(y.detach()).shape, dtype=torch.uint8, device='cuda')
+    ops.stem_pool(xg, w.detach().cuda(), b.detach().cuda(), argmax=am)
+    res = {}
+    for gather in ('0', '1'):
+        monkeypatch.setenv('SQD_STEM_WGRAD_GATHER', gather)
+        res[gather] = ops.stem_wgrad_pooled(dyg, None, am, xg, 64, 3)
+        again = ops.stem_wgrad_pooled(dyg, None, am, xg, 64, 3)
+        assert torch.equal(res[gather][0], again[0]) and torch.equal(res[gather][1], again[1]), gather
+    monkeypatch.delenv('SQD_STEM_WGRAD_GATHER')
+    dflt = ops.stem_wgrad_pooled(dyg, None, am, xg, 64, 3)                       # unset = the gather kernel
+    assert torch.equal(dflt[0], res['1'][0]) and torch.equal(dflt[1], res['1'][1])
+    ed = (res['1'][0] - res['0'][0]).abs().max().item() / gmax
+    edb = (res['1'][1] - res['0'][1]).abs().max().item() / bmax
+    print(f'{H}x{W}: dW {ed:.2e}, db {edb:.2e} of the gradient maximum')
+    assert ed <= 1e-5 and edb <= 1e-5, (ed, edb)
+
+
 def test_trainer_epochs_dense_and_sparse_annotations():
     """Trainer.train_epoch / val_epoch (src/engine/trainer.py:18-80) over a list "loader": logged losses match the
     oracle's step-by-step run, and batches with sparse annotations (encoded on the GPU) give the same run as

@@ -1,13 +1,16 @@
 """Is the gfx950 device code of two source trees the same, kernel by kernel?  Needs no GPU.
 
-usage: python tools/device_asm_diff.py OLD_CSRC NEW_CSRC [--work DIR] [--jobs N]
+usage: python tools/device_asm_diff.py OLD_CSRC NEW_CSRC [--work DIR] [--jobs N] [--map OLD_SUBSTR=NEW_SUBSTR ...]
 
-Every file of the Makefile's SRCS is compiled on both sides with the flags the Makefile gives that file, plus
+Every file of each side's Makefile SRCS is compiled with the flags that Makefile gives that file, plus
 --cuda-device-only -S.  The listings are split by kernel symbol; basic-block label numbers (BB<n>_ -> BB_), comments and
 whitespace are normalised; then the kernel symbol sets, each kernel's instruction text and each kernel's .amdhsa_kernel
-descriptor (registers, LDS, scratch) are compared.  Prints one line per file and every difference -- for a kernel that differs also
-its instruction count, its 16-byte vector loads / stores and its VGPR / LDS / scratch figures, before -> after; exit status 1 if any
-kernel differs or exists on one side only (a host-only refactor lists the instantiations it removed on purpose)."""
+descriptor (registers, LDS, scratch) are compared.  A kernel is paired by its symbol wherever it lives: one that moved to another
+file is compared across files and reported under the file that holds it now.  --map pairs a renamed symbol (a template parameter
+that went away changes the mangled name): the substring is replaced in the old side's symbols and text before the comparison.
+Prints one line per file and every difference -- for a kernel that differs also its instruction count, its vector-memory
+instructions (all, and the 16-byte loads / stores) and its VGPR / LDS / scratch figures, before -> after; exit status 1 if any
+kernel differs or exists on one side only (a refactor lists the instantiations it removed on purpose)."""
 import argparse
 import os
 import re
@@ -89,13 +92,14 @@ def kernels(path):
 
 
 WATCHED = ('global_load_dwordx4', 'global_store_dwordx4', 'flat_load_dwordx4', 'flat_store_dwordx4')
+VMEM = ('buffer_', 'global_', 'flat_', 'scratch_')          # every vector-memory instruction (what s_waitcnt vmcnt counts)
 RESOURCES = ('.amdhsa_next_free_vgpr', '.amdhsa_accum_offset', '.amdhsa_group_segment_fixed_size', '.amdhsa_private_segment_fixed_size')
 
 
 def counts(text):
     """instructions (labels and directives left out) and the 16-byte vector memory instructions of one kernel's text"""
     ins = [l.split()[0] for l in text.splitlines() if not l.endswith(':') and not l.startswith('.')]
-    return [len(ins)] + [ins.count(w) for w in WATCHED]
+    return [len(ins), sum(i.startswith(VMEM) for i in ins)] + [ins.count(w) for w in WATCHED]
 
 
 def resources(desc):
@@ -110,38 +114,56 @@ def demangle(names):
     return r.stdout.splitlines() if r.returncode == 0 else list(names)
 
 
+def renamed(text, maps):
+    for old, new in maps:
+        text = text.replace(old, new)
+    return text
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('old')
     ap.add_argument('new')
     ap.add_argument('--work', default=None, help='keeps the listings (old/ and new/) for reuse')
     ap.add_argument('--jobs', type=int, default=4)
+    ap.add_argument('--map', action='append', default=[], metavar='OLD_SUBSTR=NEW_SUBSTR',
+                    help='pair a renamed symbol: the substring is replaced in the old side\'s (mangled) symbols and text; repeatable')
     a = ap.parse_args()
+    maps = [tuple(m.split('=', 1)) for m in a.map]
     work = a.work or tempfile.mkdtemp(prefix='device_asm_diff_')
-    files = srcs(a.old)
-    if files != srcs(a.new):
-        print(f'SRCS differ: {files} vs {srcs(a.new)}')
-        return 1
-    for side in ('old', 'new'):
+    sides = {'old': (a.old, srcs(a.old)), 'new': (a.new, srcs(a.new))}
+    if sides['old'][1] != sides['new'][1]:
+        print(f'SRCS differ: only before {sorted(set(sides["old"][1]) - set(sides["new"][1]))}, only after '
+              f'{sorted(set(sides["new"][1]) - set(sides["old"][1]))}: a kernel is looked for in every file of the other side')
+    for side in sides:
         os.makedirs(os.path.join(work, side), exist_ok=True)
-    jobs = [(side, csrc, f) for f in files for side, csrc in (('old', a.old), ('new', a.new))]
+    jobs = [(side, csrc, f) for side, (csrc, fs) in sides.items() for f in fs]
     with ThreadPoolExecutor(a.jobs) as ex:
         paths = dict(zip([(s, f) for s, _, f in jobs], ex.map(lambda j: listing(j[1], j[2], os.path.join(work, j[0])), jobs)))
+    per = {(s, f): kernels(p) for (s, f), p in paths.items()}
+    per.update({('old', f): {renamed(k, maps): (renamed(t, maps), d) for k, (t, d) in per[('old', f)].items()} for f in sides['old'][1]})
+    home = {s: {k: f for f in fs for k in per[(s, f)]} for s, (_, fs) in sides.items()}      # symbol -> its file
     bad = total = 0
-    for f in files:
-        ko, kn = kernels(paths[('old', f)]), kernels(paths[('new', f)])
+    for f in sorted(set(sides['old'][1]) | set(sides['new'][1]), key=(sides['old'][1] + sides['new'][1]).index):
+        # a file's kernels: those it holds on either side; one that moved is compared where it lives now and reported there
+        ko = {k: per[('old', home['old'][k])][k] for k in home['old'] if home['new'].get(k, home['old'][k]) == f}
+        kn = per.get(('new', f), {})
+        moved = sorted(k for k in ko if home['old'][k] != f)
         gone, added = sorted(set(ko) - set(kn)), sorted(set(kn) - set(ko))
         text = [k for k in sorted(set(ko) & set(kn)) if ko[k][0] != kn[k][0]]
         dsc = [k for k in sorted(set(ko) & set(kn)) if ko[k][1] != kn[k][1]]
         same = len(set(ko) & set(kn)) - len(set(text) | set(dsc))
         print(f'{f}: {len(ko)} kernels before, {len(kn)} after, {same} identical (text and descriptor), '
-              f'{len(gone)} removed, {len(added)} added, {len(text)} text differs, {len(dsc)} descriptor differs')
+              f'{len(gone)} removed, {len(added)} added, {len(text)} text differs, {len(dsc)} descriptor differs'
+              + (f', {len(moved)} came from another file' if moved else ''))
+        for k, name in zip(moved, demangle(moved)):
+            print(f'    moved from {home["old"][k]}: {name}')
         for tag, ks in (('removed', gone), ('added', added), ('TEXT DIFFERS', text), ('DESCRIPTOR DIFFERS', dsc)):
             for k in demangle(ks):
                 print(f'    {tag}: {k}')
         for k, name in zip(sorted(set(text) | set(dsc)), demangle(sorted(set(text) | set(dsc)))):
             o, n = counts(ko[k][0]), counts(kn[k][0])
-            print(f'    counts: {name}: ' + ', '.join(f'{w} {a} -> {b}' for w, a, b in zip(('instructions',) + WATCHED, o, n)) + '; '
+            print(f'    counts: {name}: ' + ', '.join(f'{w} {a} -> {b}' for w, a, b in zip(('instructions', 'vector-memory') + WATCHED, o, n)) + '; '
                   + ', '.join(f'{r[8:]} {a} -> {b}' for r, a, b in zip(RESOURCES, resources(ko[k][1]), resources(kn[k][1]))))
         bad += len(gone) + len(added) + len(set(text) | set(dsc))
         total += len(ko)
