@@ -555,6 +555,53 @@ int sqd_loss_masked_mean_bwd(const float* pred, const int* anchor_idx, const flo
                              int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
                              float w_bbox, void* stream);
 
+/* Box regression by IoU, GIoU, DIoU or CIoU: the loss launches above with the bbox component
+ *   bbox_b = w_bbox * sum_a [mask_a != 0] * (1 - q_a) / n_obj        (masked: 0 where n_obj = 0)
+ * in place of the squared error on the deltas.  With g the gt box, p the clamped decoded box, inter / uni / iou = inter / (uni + eps)
+ * the confidence term's values, eps = 1e-10, (gw, gh) and (pw, ph) the two boxes' sides, (cw, ch) the sides of the smallest box
+ * around both and rho2 the squared distance of the centres:
+ *   iou : q = iou                                   giou: q = iou - (cw*ch - uni) / (cw*ch + eps)
+ *   diou: q = iou - rho2 / (cw^2 + ch^2 + eps)      ciou: q = diou's - alpha * v,
+ *   v = 4/pi^2 * (atan(gw / (gh + eps)) - atan(pw / (ph + eps)))^2, alpha = v / (1 - iou + v + eps), a constant in the backward.
+ * The gt delta columns (dense 5..8, sparse `deltas`) are not read by these kinds; q and its gradient are evaluated in float64 on the
+ * rows with a box.  `iou` has no box gradient where p and g are disjoint.  The gradient follows the conventions of the confidence
+ * path: clamp passes inclusively, min / max ties split 0.5 / 0.5 (the enclosing box compares the intersection's pairs), clamp_min
+ * passes at 0.
+ * box_loss: one of SQD_BOX_*; SQD_BOX_L2 runs the launches of the sixteen entries above and gives their bits; anything else is
+ * status 1.  mean4: NULL for the plain forward, else the batch means [4].  Backward: exactly one of coef [3][B] / gmean (a device
+ * float) is non-NULL.  Every other argument, workspace size, limit and status as in the entry of the same form; the dense pair
+ * serves 1 <= num_classes <= 256 (the <= 16-class kernels up to 16 classes, the many-class ones past it). */
+#define SQD_BOX_L2 0
+#define SQD_BOX_IOU 1
+#define SQD_BOX_GIOU 2
+#define SQD_BOX_DIOU 3
+#define SQD_BOX_CIOU 4
+int sqd_loss_box_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses, float* nobj,
+                     float* mean4, int box_loss, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                     float w_pos, float w_neg, float w_bbox, void* stream);
+int sqd_loss_box_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* coef,
+                     const float* gmean, float* dpred, int box_loss, int B, int A, int num_classes, int input_h, int input_w,
+                     float w_class, float w_pos, float w_neg, float w_bbox, void* stream);
+int sqd_loss_box_sparse_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                            const int* class_ids, const int* offsets, const float* anchors, float* workspace, float* losses,
+                            float* nobj, float* mean4, int box_loss, int total, int B, int A, int num_classes, int input_h,
+                            int input_w, float w_class, float w_pos, float w_neg, float w_bbox, void* stream);
+int sqd_loss_box_sparse_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                            const int* class_ids, const int* offsets, const float* anchors, const float* nobj,
+                            const float* coef, const float* gmean, float* dpred, int box_loss, int total, int B, int A,
+                            int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg, float w_bbox,
+                            void* stream);
+int sqd_loss_box_masked_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                            const int* class_ids, const int* offsets, const unsigned* ignore, const float* anchors,
+                            float* workspace, float* losses, float* counts, float* mean4, int box_loss, int total, int B,
+                            int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                            float w_bbox, void* stream);
+int sqd_loss_box_masked_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                            const int* class_ids, const int* offsets, const unsigned* ignore, const float* anchors,
+                            const float* counts, const float* coef, const float* gmean, float* dpred, int box_loss, int total,
+                            int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                            float w_bbox, void* stream);
+
 
 /* Fire.forward's two expand convolutions + torch.cat (src/model/squeezedet.py:18-22) in ONE Winograd launch (inference):
  * y[..., y_coff3 : +N3] = ReLU(conv3x3(x, w3) + b3), y[..., y_coff1 : +N1] = ReLU(conv1x1(x, w1) + b1).  A 1x1 convolution only

@@ -130,6 +130,12 @@ _SIGNATURES = {
     'sqd_loss_masked_bwd': [c_p] * 11 + [c_i] * 6 + [c_f] * 4 + [c_p],
     'sqd_loss_masked_mean_fwd': [c_p] * 12 + [c_i] * 6 + [c_f] * 4 + [c_p],
     'sqd_loss_masked_mean_bwd': [c_p] * 11 + [c_i] * 6 + [c_f] * 4 + [c_p],
+    'sqd_loss_box_fwd': [c_p] * 7 + [c_i] * 6 + [c_f] * 4 + [c_p],
+    'sqd_loss_box_bwd': [c_p] * 7 + [c_i] * 6 + [c_f] * 4 + [c_p],
+    'sqd_loss_box_sparse_fwd': [c_p] * 11 + [c_i] * 7 + [c_f] * 4 + [c_p],
+    'sqd_loss_box_sparse_bwd': [c_p] * 11 + [c_i] * 7 + [c_f] * 4 + [c_p],
+    'sqd_loss_box_masked_fwd': [c_p] * 12 + [c_i] * 7 + [c_f] * 4 + [c_p],
+    'sqd_loss_box_masked_bwd': [c_p] * 12 + [c_i] * 7 + [c_f] * 4 + [c_p],
     'sqd_det_match_fwd': [c_p] * 12 + [c_i] * 5 + [c_p],
     'sqd_det_ap_fwd': [c_p] * 8 + [c_i] * 4 + [c_p],
 }

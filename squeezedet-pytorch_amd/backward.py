@@ -221,10 +221,14 @@ class BackboneFn(torch.autograd.Function):
 
 
 def _loss_meta(ctx, loss_mod):
-    """ctx.meta = (input_size, num_classes, weights) of the Loss module: what the six loss Functions hand to ops in both passes."""
+    """ctx.meta = (input_size, num_classes, weights) of the Loss module: what the six loss Functions hand to ops in both passes.  A
+    ``bbox_loss`` other than 'l2' rides behind the four weights (``ops.split_loss_weights``)."""
     res = loss_mod.resolver
     ctx.meta = (res.input_size, res.num_classes, (loss_mod.class_loss_weight, loss_mod.positive_score_loss_weight,
                                                   loss_mod.negative_score_loss_weight, loss_mod.bbox_loss_weight))
+    kind = getattr(loss_mod, 'bbox_loss', 'l2')
+    if kind != 'l2':
+        ctx.meta = ctx.meta[:2] + (ctx.meta[2] + (kind,),)
     return ctx.meta
 
 

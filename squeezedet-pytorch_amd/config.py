@@ -32,6 +32,14 @@ def check_geometry(cfg, who):
         raise ValueError(f'{who}: zoom_out shrinks the letterbox window, it needs letterbox=True')
     return letterbox, zoom
 KITTI_CLASS_NAMES = ('Car', 'Pedestrian', 'Cyclist')
+BBOX_LOSSES = ('l2', 'iou', 'giou', 'diou', 'ciou')      # ops.BOX_LOSSES
+
+
+def check_bbox_loss(kind, who):
+    """``cfg.bbox_loss``: one of the five names."""
+    if not isinstance(kind, str) or kind not in BBOX_LOSSES:
+        raise ValueError(f'{who}: bbox_loss must be one of {BBOX_LOSSES}, got {kind!r}')
+    return kind
 
 
 def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_ANCHORS_SEED,
@@ -53,6 +61,8 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         lr=0.01, momentum=0.9, weight_decay=1e-4, grad_norm=5., batch_size=20,
         class_loss_weight=1., positive_score_loss_weight=3.75,
         negative_score_loss_weight=100., bbox_loss_weight=6.,
+        bbox_loss='l2',              # the regression term: 'l2' (squared error on the deltas, the reference) or 1 - q of the decoded box against
+                                     # the gt box, q = 'iou' | 'giou' | 'diou' | 'ciou' (bbox_loss_weight stays the user's to set)
         nms_thresh=0.4, score_thresh=0.3, keep_top_k=64,
         gpus=[0], chunk_sizes=[20], num_iters=-1, print_interval=10, debug=0, num_workers=4, forbid_resize=False,
         flip_prob=0.5, drift_prob=1., seed=42,      # training augmentation (train_data.TrainLoader), src/utils/config.py:53-56
@@ -76,4 +86,5 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
     for k, v in overrides.items():
         setattr(cfg, k, v)
     check_geometry(cfg, 'make_cfg')
+    check_bbox_loss(cfg.bbox_loss, 'make_cfg')
     return cfg

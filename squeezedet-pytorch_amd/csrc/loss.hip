@@ -13,6 +13,15 @@
 //   iou    = IoU(gt_box, decode(delta)) * mask, IoU = inter / (union + 1e-10)   -- NOT detached:
 // the positive-score term back-propagates through iou -> predicted box -> clamp -> exp -> deltas
 // (SURVEY.md section 8a row L).  All per-image ([B] vectors); n_obj = 0 gives NaN like the reference.
+//
+// LossBoxArgs::box (SQD_BOX_IOU .. SQD_BOX_CIOU, the sqd_loss_box_* entries) replaces the bbox term by an IoU-family regression on the
+// same operands as the confidence target, gt columns 5..8 unread:
+//   bbox   = sum_a  w_b * [mask != 0] * (1 - q)                           / n_obj
+//   iou : q = iou          giou: q = iou - (cw*ch - union) / (cw*ch + eps)          diou: q = iou - rho2 / (cw^2 + ch^2 + eps)
+//   ciou: q = diou's - alpha * v,  v = 4/pi^2 (atan(gw / (gh + eps)) - atan(pw / (ph + eps)))^2,  alpha = v / (1 - iou + v + eps)
+// (cw, ch: the enclosing box; rho2: the squared centre distance; alpha: a constant in the backward).  Both the value and the gradient
+// are float64 work on the rows with a box only (box_loss_value, the positive-row branch of anchor_geom_grad_nneg); the BOX = false
+// instantiations of every kernel are the L2 code as it was.  'iou' has no box gradient where the boxes are disjoint.
 #include "sqd_common.h"
 #include "many_class.h"
 #include <math.h>
@@ -21,6 +30,12 @@
 #define LOSS_NPART 16          // partial-sum blocks per image (deterministic two-stage reduction)
 #define LOSS_THREADS 256
 #define LOSS_EPS 1e-10f
+// the box regression kinds (include/sqd_hip.h)
+#define SQD_BOX_L2 0
+#define SQD_BOX_IOU 1
+#define SQD_BOX_GIOU 2
+#define SQD_BOX_DIOU 3
+#define SQD_BOX_CIOU 4
 
 struct LossArgs {
   const float* pred; const float* gt; const float* anchors;
@@ -28,10 +43,11 @@ struct LossArgs {
   float wmax, hmax;
   float w_class, w_pos, w_neg, w_bbox;
 };
+struct LossBoxArgs : LossArgs { int box; };      // + SQD_BOX_*: what the loss_box_* kernels take (the L2 kernels keep LossArgs)
 
 struct AnchorGeom {           // the class-independent part: confidence, box decode, IoU, delta regression
   float mask, conf, iou_raw, e;          // e = iou*mask - conf
-  float bb;                              // sum_j (delta_j - gt_j)^2
+  float bb;                              // sum_j (delta_j - gt_j)^2; BOX: [mask != 0] * (1 - q)
   // box decode intermediates for the backward
   float w, h, ax, ay, aw, ah;
   float x1u, y1u, x2u, y2u;              // unclamped
@@ -46,8 +62,85 @@ struct AnchorTerms : AnchorGeom {        // everything both passes need about on
   float onehot_sum;
 };
 
+// ---- IoU-family box regression: float64, rows with a box only -------------------------------------------------------------------------
+// The clamped predicted box, the gt box and their IoU pieces in float64 (den = uni + eps).
+struct Box64 {
+  double px1, py1, px2, py2, gx1, gy1, gx2, gy2;
+  double lr_raw, tb_raw, lr, tb, inter, uni, den;
+};
+
+// sub-gradients of minimum / maximum toward `mine`: ties split evenly (torch.minimum / maximum backward)
+__device__ __forceinline__ double tie_min(double mine, double other) { return mine < other ? 1.0 : (mine == other ? 0.5 : 0.0); }
+__device__ __forceinline__ double tie_max(double mine, double other) { return mine > other ? 1.0 : (mine == other ? 0.5 : 0.0); }
+
+// pen = iou - q of kind `box`; GRAD: dp = d pen / d (px1, py1, px2, py2), before the clamp rule.  The enclosing box's max / min compare
+// the pairs the intersection's min / max compare, with the same tie rule; alpha is a constant of the derivative.
+template <bool GRAD>
+__device__ __forceinline__ double box_penalty(int box, const Box64& b, double (&dp)[4]) {
+  if (GRAD) dp[0] = dp[1] = dp[2] = dp[3] = 0.0;
+  if (box == SQD_BOX_IOU) return 0.0;
+  const double eps = (double)LOSS_EPS;
+  const double pw = b.px2 - b.px1, ph = b.py2 - b.py1;
+  const double cw = fmax(b.gx2, b.px2) - fmin(b.gx1, b.px1), ch = fmax(b.gy2, b.py2) - fmin(b.gy1, b.py1);
+  // d cw / d (px1, px2), d ch / d (py1, py2)
+  const double cx1 = -tie_min(b.px1, b.gx1), cx2 = tie_max(b.px2, b.gx2), cy1 = -tie_min(b.py1, b.gy1), cy2 = tie_max(b.py2, b.gy2);
+  if (box == SQD_BOX_GIOU) {
+    const double ce = cw * ch + eps;
+    if (GRAD) {
+      const double dix = b.lr_raw >= 0.0 ? b.tb : 0.0, diy = b.tb_raw >= 0.0 ? b.lr : 0.0;       // d inter / d (lr_raw, tb_raw)
+      const double du[4] = {-ph + dix * tie_max(b.px1, b.gx1), -pw + diy * tie_max(b.py1, b.gy1),
+                            ph - dix * tie_min(b.px2, b.gx2), pw - diy * tie_min(b.py2, b.gy2)};   // d uni
+      const double dc[4] = {ch * cx1, cw * cy1, ch * cx2, cw * cy2};                                 // d (cw * ch)
+      const double k1 = b.den / (ce * ce), k2 = 1.0 / ce;
+      for (int j = 0; j < 4; ++j) dp[j] = dc[j] * k1 - du[j] * k2;
+    }
+    return (cw * ch - b.uni) / ce;
+  }
+  const double sx = b.gx1 + b.gx2 - b.px1 - b.px2, sy = b.gy1 + b.gy2 - b.py1 - b.py2;
+  const double rho2 = (sx * sx + sy * sy) * 0.25, c2e = cw * cw + ch * ch + eps;
+  double pen = rho2 / c2e;
+  if (GRAD) {
+    const double k1 = 1.0 / c2e, k2 = 2.0 * rho2 / (c2e * c2e);
+    dp[0] = -0.5 * sx * k1 - cw * cx1 * k2; dp[1] = -0.5 * sy * k1 - ch * cy1 * k2;
+    dp[2] = -0.5 * sx * k1 - cw * cx2 * k2; dp[3] = -0.5 * sy * k1 - ch * cy2 * k2;
+  }
+  if (box == SQD_BOX_CIOU) {
+    const double c4pi2 = 4.0 / (M_PI * M_PI);
+    const double hp = ph + eps, rp = pw / hp;
+    const double da = atan((b.gx2 - b.gx1) / (b.gy2 - b.gy1 + eps)) - atan(rp);
+    const double v = c4pi2 * da * da;
+    const double alpha = v / (1.0 - b.inter / b.den + v + eps);
+    pen += alpha * v;
+    if (GRAD) {
+      const double dpw = alpha * (-2.0 * c4pi2 * da) / ((1.0 + rp * rp) * hp), dph = -dpw * rp;     // alpha * d v / d (pw, ph)
+      dp[0] -= dpw; dp[2] += dpw; dp[1] -= dph; dp[3] += dph;
+    }
+  }
+  return pen;
+}
+
+// [mask != 0] * (1 - q) of a row with a box: the decode and the IoU again in float64 from the row's own operands, rounded once.
+__device__ __forceinline__ float box_loss_value(const LossBoxArgs& a, const float* __restrict__ d, float ax, float ay, float aw_, float ah_,
+                                                float gx1, float gy1, float gx2, float gy2) {
+  const double aw = aw_, ah = ah_, wmax = a.wmax, hmax = a.hmax;
+  const double cx = (double)ax + aw * (double)d[0], cy = (double)ay + ah * (double)d[1];
+  const double w = aw * exp((double)d[2]), h = ah * exp((double)d[3]);
+  Box64 b;
+  b.px1 = fmin(fmax(cx - 0.5 * (w - 1.0), 0.0), wmax); b.py1 = fmin(fmax(cy - 0.5 * (h - 1.0), 0.0), hmax);
+  b.px2 = fmin(fmax(cx + 0.5 * (w - 1.0), 0.0), wmax); b.py2 = fmin(fmax(cy + 0.5 * (h - 1.0), 0.0), hmax);
+  b.gx1 = gx1; b.gy1 = gy1; b.gx2 = gx2; b.gy2 = gy2;
+  b.lr_raw = fmin(b.gx2, b.px2) - fmax(b.gx1, b.px1); b.tb_raw = fmin(b.gy2, b.py2) - fmax(b.gy1, b.py1);
+  b.lr = fmax(b.lr_raw, 0.0); b.tb = fmax(b.tb_raw, 0.0);
+  b.inter = b.lr * b.tb;
+  b.uni = (b.gx2 - b.gx1) * (b.gy2 - b.gy1) + (b.px2 - b.px1) * (b.py2 - b.py1) - b.inter;
+  b.den = b.uni + (double)LOSS_EPS;
+  double unused[4];
+  return (float)(1.0 - (b.inter / b.den - box_penalty<false>(a.box, b, unused)));
+}
+
 // p: the row's C + 5 floats, g: its C + 9 ground-truth floats.  Shared by the <= 16-class and the many-class kernels.
-__device__ __forceinline__ void anchor_geom(const LossArgs& a, const float* __restrict__ p, const float* __restrict__ g,
+template <bool BOX = false, class Args>
+__device__ __forceinline__ void anchor_geom(const Args& a, const float* __restrict__ p, const float* __restrict__ g,
                                             const float* __restrict__ anc, AnchorGeom& t) {
   const int C = a.C;
   t.mask = g[0];
@@ -71,12 +164,17 @@ __device__ __forceinline__ void anchor_geom(const LossArgs& a, const float* __re
   t.uni = (t.gx2 - t.gx1) * (t.gy2 - t.gy1) + (t.px2 - t.px1) * (t.py2 - t.py1) - t.inter;
   t.iou_raw = t.inter / (t.uni + LOSS_EPS);
   t.e = t.iou_raw * t.mask - t.conf;
-  float bb = 0.f;
-  for (int j = 0; j < 4; ++j) { const float df = d[j] - g[5 + j]; bb += df * df; }
-  t.bb = bb;
+  if constexpr (BOX) {
+    t.bb = t.mask != 0.f ? box_loss_value(a, d, ax, ay, t.aw, t.ah, t.gx1, t.gy1, t.gx2, t.gy2) : 0.f;
+  } else {
+    float bb = 0.f;
+    for (int j = 0; j < 4; ++j) { const float df = d[j] - g[5 + j]; bb += df * df; }
+    t.bb = bb;
+  }
 }
 
-__device__ __forceinline__ void anchor_terms(const LossArgs& a, const float* __restrict__ p, const float* __restrict__ g,
+template <bool BOX = false, class Args>
+__device__ __forceinline__ void anchor_terms(const Args& a, const float* __restrict__ p, const float* __restrict__ g,
                                              const float* __restrict__ anc, AnchorTerms& t) {
   const int C = a.C;
   // log-softmax over the class logits
@@ -93,7 +191,7 @@ __device__ __forceinline__ void anchor_terms(const LossArgs& a, const float* __r
     t.prob[c] = t.prob[c] / sum;
   }
   t.ce = ce; t.onehot_sum = ohs;
-  anchor_geom(a, p, g, anc, t);
+  anchor_geom<BOX>(a, p, g, anc, t);
 }
 
 // The anchors [lo, hi) of an image that block blk of LOSS_NPART sums.
@@ -124,8 +222,10 @@ __device__ __forceinline__ void block_reduce_store(const float (&s)[NS], float* 
   }
 }
 
-// partial[b][blk][5] = (n_obj, S_class, S_pos, S_neg, S_bbox) over the block's anchors
-__global__ __launch_bounds__(LOSS_THREADS) void loss_partial_kernel(LossArgs a, float* __restrict__ partial) {
+// partial[b][blk][5] = (n_obj, S_class, S_pos, S_neg, S_bbox) over the block's anchors.  Every kernel below is a body with a BOX
+// parameter and two entries: the L2 kernel under the name it always had, and its loss_box_* twin.
+template <bool BOX, class Args>
+__device__ __forceinline__ void loss_partial_body(const Args a, float* __restrict__ partial) {
   const int b = blockIdx.y, blk = blockIdx.x;
   int lo, hi;
   loss_slice(a.A, blk, lo, hi);
@@ -133,14 +233,21 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_partial_kernel(LossArgs a, 
   for (int i = lo + threadIdx.x; i < hi; i += LOSS_THREADS) {
     const long long row = (long long)b * a.A + i;
     AnchorTerms t;
-    anchor_terms(a, a.pred + row * (a.C + 5), a.gt + row * (a.C + 9), a.anchors + 4 * i, t);
+    anchor_terms<BOX>(a, a.pred + row * (a.C + 5), a.gt + row * (a.C + 9), a.anchors + 4 * i, t);
     s[0] += t.mask;
     s[1] += t.mask * t.ce;
     s[2] += t.mask * (t.e * t.e);
     s[3] += (1.f - t.mask) * (t.e * t.e);
-    s[4] += t.mask * t.bb;
+    s[4] += BOX ? t.bb : t.mask * t.bb;
   }
   block_reduce_store<5, LOSS_THREADS>(s, partial, b, blk);
+}
+
+__global__ __launch_bounds__(LOSS_THREADS) void loss_partial_kernel(LossArgs a, float* __restrict__ partial) {
+  loss_partial_body<false>(a, partial);
+}
+__global__ __launch_bounds__(LOSS_THREADS) void loss_box_partial_kernel(LossBoxArgs a, float* __restrict__ partial) {
+  loss_partial_body<true>(a, partial);
 }
 
 // The second stage, one image: its LOSS_NPART partials -> v = (class, score = pos+neg, bbox, total) and the counts the backward
@@ -224,7 +331,10 @@ __device__ __forceinline__ Upstream upstream_grads(const LossArgs& a, const floa
 // d loss / d (conf logit, 4 deltas) of one anchor: the score terms incl. the un-detached IoU path, and the delta regression.
 // us / ub: upstream gradients of the image's score and bbox components; n = n_obj.  Shared by both backward kernels.
 // nneg: the denominator of the negative score term, A - n_obj (the masked launches: a count that left the ignored anchors out).
-__device__ __forceinline__ void anchor_geom_grad_nneg(const LossArgs& a, const AnchorGeom& t, const float* __restrict__ d,
+// BOX: the delta regression is gone; a row with a box always takes the float64 branch, where the box term adds kq = -ub * w_b / n
+// to d / d iou and -kq * d pen to the clamped box's gradient, ahead of the clamp rule.
+template <bool BOX = false, class Args>
+__device__ __forceinline__ void anchor_geom_grad_nneg(const Args& a, const AnchorGeom& t, const float* __restrict__ d,
                                                       const float* __restrict__ g, float n, float nneg, float us, float ub,
                                                       float (&out)[5]) {
   // score terms: k*(iou*mask - conf)^2, k = w_p*mask/n + w_n*(1-mask)/(A-n)
@@ -236,7 +346,7 @@ __device__ __forceinline__ void anchor_geom_grad_nneg(const LossArgs& a, const A
   // to either side.  Those rows redo the decode and the IoU in float64 from the row's own operands and round once at the end; the
   // branch rules are the forward's (clamp passes inclusively, min / max ties split, clamp_min passes at 0).
   const float dL_dov = dL_de * t.mask;
-  if (dL_dov != 0.f) {
+  if (dL_dov != 0.f || (BOX && t.mask != 0.f)) {
     const double aw = t.aw, ah = t.ah, wmax = a.wmax, hmax = a.hmax;
     const double cx = (double)t.ax + aw * (double)d[0], cy = (double)t.ay + ah * (double)d[1];
     const double w = aw * exp((double)d[2]), h = ah * exp((double)d[3]);
@@ -249,20 +359,32 @@ __device__ __forceinline__ void anchor_geom_grad_nneg(const LossArgs& a, const A
     const double inter = lr * tb;
     const double den = (gx2 - gx1) * (gy2 - gy1) + (px2 - px1) * (py2 - py1) - inter + (double)LOSS_EPS;
     const double e = inter / den * (double)t.mask - (double)t.conf;
-    const double dov = 2.0 * (double)k * e * (double)t.mask;
+    double dov = 2.0 * (double)k * e * (double)t.mask;
+    double kq = 0.0;
+    if constexpr (BOX) {
+      if (t.mask != 0.f) { kq = -(double)ub * (double)a.w_bbox / (double)n; dov += kq; }
+    }
     const double dov_dinter = 1.0 / den + inter / (den * den);      // union contains -inter
     const double dov_dap = -inter / (den * den);                    // pred-box area
     const double dlr = (lr_raw >= 0.0) ? dov * dov_dinter * tb : 0.0;
     const double dtb = (tb_raw >= 0.0) ? dov * dov_dinter * lr : 0.0;
     // min/max sub-gradients: ties split evenly (torch.minimum/maximum backward)
-    auto wmin = [](double mine, double other) { return mine < other ? 1.0 : (mine == other ? 0.5 : 0.0); };
-    auto wmaxf = [](double mine, double other) { return mine > other ? 1.0 : (mine == other ? 0.5 : 0.0); };
+    auto wmin = [](double mine, double other) { return tie_min(mine, other); };
+    auto wmaxf = [](double mine, double other) { return tie_max(mine, other); };
     const double pw = px2 - px1, ph = py2 - py1;
     const double dap = dov * dov_dap;
     double dpx2 = dlr * wmin(px2, gx2) + dap * ph;
     double dpx1 = -dlr * wmaxf(px1, gx1) - dap * ph;
     double dpy2 = dtb * wmin(py2, gy2) + dap * pw;
     double dpy1 = -dtb * wmaxf(py1, gy1) - dap * pw;
+    if constexpr (BOX) {
+      if (kq != 0.0 && a.box != SQD_BOX_IOU) {
+        const Box64 bx = {px1, py1, px2, py2, gx1, gy1, gx2, gy2, lr_raw, tb_raw, lr, tb, inter, den - (double)LOSS_EPS, den};
+        double dpen[4];
+        box_penalty<true>(a.box, bx, dpen);
+        dpx1 -= kq * dpen[0]; dpy1 -= kq * dpen[1]; dpx2 -= kq * dpen[2]; dpy2 -= kq * dpen[3];
+      }
+    }
     // clamp backward: passes where the unclamped value is inside [0, max] (inclusive)
     if (!(x1u >= 0.0 && x1u <= wmax)) dpx1 = 0.0;
     if (!(x2u >= 0.0 && x2u <= wmax)) dpx2 = 0.0;
@@ -272,23 +394,32 @@ __device__ __forceinline__ void anchor_geom_grad_nneg(const LossArgs& a, const A
                           (dpy1 + dpy2) * ah,
                           (dpx2 - dpx1) * 0.5 * w,               // d x2u/d dw = +w/2, d x1u/d dw = -w/2
                           (dpy2 - dpy1) * 0.5 * h};
-    const double kb = (double)ub * (double)a.w_bbox * (double)t.mask / (double)n * 2.0;
-    for (int j = 0; j < 4; ++j) out[1 + j] = (float)(gd[j] + kb * ((double)d[j] - (double)g[5 + j]));
+    if constexpr (BOX) {
+      for (int j = 0; j < 4; ++j) out[1 + j] = (float)gd[j];
+    } else {
+      const double kb = (double)ub * (double)a.w_bbox * (double)t.mask / (double)n * 2.0;
+      for (int j = 0; j < 4; ++j) out[1 + j] = (float)(gd[j] + kb * ((double)d[j] - (double)g[5 + j]));
+    }
+    return;
+  }
+  if constexpr (BOX) {
+    for (int j = 0; j < 4; ++j) out[1 + j] = 0.f;
     return;
   }
   const float kb = ub * a.w_bbox * t.mask / n * 2.f;
   for (int j = 0; j < 4; ++j) out[1 + j] = 0.f + kb * (d[j] - g[5 + j]);      // (0.f +: a row without a box never holds -0)
 }
 
-__device__ __forceinline__ void anchor_geom_grad(const LossArgs& a, const AnchorGeom& t, const float* __restrict__ d,
+template <bool BOX = false, class Args>
+__device__ __forceinline__ void anchor_geom_grad(const Args& a, const AnchorGeom& t, const float* __restrict__ d,
                                                  const float* __restrict__ g, float n, float us, float ub, float (&out)[5]) {
-  anchor_geom_grad_nneg(a, t, d, g, n, (float)a.A - n, us, ub, out);
+  anchor_geom_grad_nneg<BOX>(a, t, d, g, n, (float)a.A - n, us, ub, out);
 }
 
 // dpred[b][a][:] = u_class[b]*d(class_b) + u_score[b]*d(score_b) + u_bbox[b]*d(bbox_b), coef[3][B]
-__global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, const float* __restrict__ nobj,
-                                                                const float* __restrict__ coef, float* __restrict__ dpred,
-                                                                const float* __restrict__ gmean) {
+template <bool BOX, class Args>
+__device__ __forceinline__ void loss_bwd_body(const Args a, const float* __restrict__ nobj, const float* __restrict__ coef,
+                                              float* __restrict__ dpred, const float* __restrict__ gmean) {
   const long long total = (long long)a.B * a.A;
   const int C = a.C;
   for (long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x; row < total; row += (long long)gridDim.x * blockDim.x) {
@@ -296,7 +427,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, cons
     const float* p = a.pred + row * (C + 5);
     const float* g = a.gt + row * (C + 9);
     AnchorTerms t;
-    anchor_terms(a, p, g, a.anchors + 4 * i, t);
+    anchor_terms<BOX>(a, p, g, a.anchors + 4 * i, t);
     const float n = nobj[b];
     const Upstream u = upstream_grads(a, coef, gmean, b);
     const float uc = u.uc, us = u.us, ub = u.ub;
@@ -305,9 +436,20 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, cons
     const float kc = uc * a.w_class * t.mask / n;
     for (int c = 0; c < C; ++c) o[c] = kc * (t.onehot_sum * t.prob[c] - g[9 + c]);
     float og[5];
-    anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
+    anchor_geom_grad<BOX>(a, t, p + C + 1, g, n, us, ub, og);
     for (int j = 0; j < 5; ++j) o[C + j] = og[j];
   }
+}
+
+__global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, const float* __restrict__ nobj,
+                                                                const float* __restrict__ coef, float* __restrict__ dpred,
+                                                                const float* __restrict__ gmean) {
+  loss_bwd_body<false>(a, nobj, coef, dpred, gmean);
+}
+__global__ __launch_bounds__(LOSS_THREADS) void loss_box_bwd_kernel(LossBoxArgs a, const float* __restrict__ nobj,
+                                                                    const float* __restrict__ coef, float* __restrict__ dpred,
+                                                                    const float* __restrict__ gmean) {
+  loss_bwd_body<true>(a, nobj, coef, dpred, gmean);
 }
 
 // ---- many-class loss: 1 <= num_classes <= 256 = 16 lanes x 16 registers (many_class.h) ------------------------------------------------
@@ -316,8 +458,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_bwd_kernel(LossArgs a, cons
 // <= 16-class kernels' own, evaluated by every lane of the group (16 lanes issue it at the cost of one) and taken from lane 0.  The
 // partial sums keep the two-stage reduction over LOSS_NPART blocks per image and share loss_finalize_kernel, so a result does not
 // change from run to run and the plain and the mean forward give the same per-image bits.
-template <int R>
-__global__ __launch_bounds__(MC_THREADS) void loss_many_partial_kernel(LossArgs a, float* __restrict__ partial) {
+template <int R, bool BOX, class Args>
+__device__ __forceinline__ void loss_many_partial_body(const Args a, float* __restrict__ partial) {
   const int b = blockIdx.y, blk = blockIdx.x, C = a.C;
   int lo, hi;
   loss_slice(a.A, blk, lo, hi);
@@ -338,16 +480,25 @@ __global__ __launch_bounds__(MC_THREADS) void loss_many_partial_kernel(LossArgs 
     }
     ce = mc_group_sum(ce);
     AnchorGeom t;
-    anchor_geom(a, p, g, a.anchors + 4 * i, t);
+    anchor_geom<BOX>(a, p, g, a.anchors + 4 * i, t);
     if (j == 0) {                                              // one lane of the group carries the row into the block's sums
       s[0] += t.mask;
       s[1] += t.mask * ce;
       s[2] += t.mask * (t.e * t.e);
       s[3] += (1.f - t.mask) * (t.e * t.e);
-      s[4] += t.mask * t.bb;
+      s[4] += BOX ? t.bb : t.mask * t.bb;
     }
   }
   block_reduce_store<5, MC_THREADS>(s, partial, b, blk);
+}
+
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void loss_many_partial_kernel(LossArgs a, float* __restrict__ partial) {
+  loss_many_partial_body<R, false>(a, partial);
+}
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void loss_box_many_partial_kernel(LossBoxArgs a, float* __restrict__ partial) {
+  loss_many_partial_body<R, true>(a, partial);
 }
 
 // A positive dpred row is written by its 16-lane group: lane j stores classes c = j, j + 16, ... as
@@ -367,10 +518,9 @@ __device__ __forceinline__ void store_positive_row(float* o, int C, int j, float
   if (j < 5) o[C + j] = (j == 0) ? og[0] : (j == 1) ? og[1] : (j == 2) ? og[2] : (j == 3) ? og[3] : og[4];
 }
 
-template <int R>
-__global__ __launch_bounds__(MC_THREADS) void loss_many_bwd_kernel(LossArgs a, const float* __restrict__ nobj,
-                                                                   const float* __restrict__ coef, float* __restrict__ dpred,
-                                                                   const float* __restrict__ gmean) {
+template <int R, bool BOX, class Args>
+__device__ __forceinline__ void loss_many_bwd_body(const Args a, const float* __restrict__ nobj, const float* __restrict__ coef,
+                                                   float* __restrict__ dpred, const float* __restrict__ gmean) {
   const long long total = (long long)a.B * a.A;
   const int C = a.C, j = threadIdx.x & (MC_LANES - 1);
   for (long long row = (long long)blockIdx.x * MC_GROUPS + threadIdx.x / MC_LANES; row < total; row += (long long)gridDim.x * MC_GROUPS) {
@@ -388,15 +538,28 @@ __global__ __launch_bounds__(MC_THREADS) void loss_many_bwd_kernel(LossArgs a, c
     }
     ohs = mc_group_sum(ohs);
     AnchorGeom t;
-    anchor_geom(a, p, g, a.anchors + 4 * i, t);
+    anchor_geom<BOX>(a, p, g, a.anchors + 4 * i, t);
     const float n = nobj[b];
     const Upstream u = upstream_grads(a, coef, gmean, b);
     const float uc = u.uc, us = u.us, ub = u.ub;
     // class logits: w_c*mask/n * (sum(onehot)*softmax_c - onehot_c)
     store_positive_row<R>(dpred + row * (C + 5), C, j, uc * a.w_class * t.mask / n, ohs, e, sum,
                           [&](int r, int) { return oh[r]; },
-                          [&](float (&og)[5]) { anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og); });
+                          [&](float (&og)[5]) { anchor_geom_grad<BOX>(a, t, p + C + 1, g, n, us, ub, og); });
   }
+}
+
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void loss_many_bwd_kernel(LossArgs a, const float* __restrict__ nobj,
+                                                                   const float* __restrict__ coef, float* __restrict__ dpred,
+                                                                   const float* __restrict__ gmean) {
+  loss_many_bwd_body<R, false>(a, nobj, coef, dpred, gmean);
+}
+template <int R>
+__global__ __launch_bounds__(MC_THREADS) void loss_box_many_bwd_kernel(LossBoxArgs a, const float* __restrict__ nobj,
+                                                                       const float* __restrict__ coef, float* __restrict__ dpred,
+                                                                       const float* __restrict__ gmean) {
+  loss_many_bwd_body<R, true>(a, nobj, coef, dpred, gmean);
 }
 
 // ---- host side of the dense launches ---------------------------------------------------------------------------------------------------
@@ -406,6 +569,23 @@ static void fill_common(LossArgs& a, const float* pred, const float* gt, const f
   a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
   a.w_class = w_class; a.w_pos = w_pos; a.w_neg = w_neg; a.w_bbox = w_bbox;
 }
+
+// what a launch hands its kernel: LossArgs, or (BOX) LossBoxArgs with the kind
+template <bool BOX> static auto kernel_args(const LossArgs& a, int box) {
+  if constexpr (BOX) {
+    LossBoxArgs b;
+    static_cast<LossArgs&>(b) = a;
+    b.box = box;
+    return b;
+  } else {
+    return a;
+  }
+}
+// launch K (BOX: its loss_box_ twin) with the kernel arguments ka in front of the rest
+#define LOSS_T2(A_, B_) <A_, B_>
+#define LOSS_LAUNCH(K, TARGS, GRID, BLOCK, ...) do { \
+    if constexpr (BOX) hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_box_##K TARGS), GRID, BLOCK, 0, s, ka, __VA_ARGS__); \
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_##K TARGS), GRID, BLOCK, 0, s, ka, __VA_ARGS__); } while (0)
 
 // the <= 16-class kernels: status 1 for anything malformed, a class count past 16 included
 static int fill_args(LossArgs& a, const float* pred, const float* gt, const float* anchors, int B, int A, int C,
@@ -436,20 +616,22 @@ static void launch_finalize(Kernel kernel, const LossArgs& a, const float* works
 // Forward on a dense gt; MANY: the 16-lane-group kernels (1 <= num_classes <= 256), else the <= 16-class ones.  workspace:
 // float[B * 16 * 5]; losses: float[4][B] = (class, score, bbox, total); nobj: float[B]; mean (the *_mean_fwd entries): mean4 [4] = the
 // batch means of the four, `loss.mean()` of the training step (src/engine/trainer.py:43) computed by the finalize launch itself.
-template <bool MANY>
+// BOX (the sqd_loss_box_* entries with a kind other than L2): the loss_box_* kernels with a.box = box.
+template <bool MANY, bool BOX = false>
 static int loss_dense_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses, float* nobj,
                           float* mean4, bool mean, int B, int A, int C, int input_h, int input_w, float w_class, float w_pos,
-                          float w_neg, float w_bbox, void* stream) {
+                          float w_neg, float w_bbox, void* stream, int box = SQD_BOX_L2) {
   LossArgs a;
   if (int rc = (MANY ? fill_args_many : fill_args)(a, pred, gt, anchors, B, A, C, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
   SQD_CHECK_ARG(workspace && losses && nobj && (mean4 || !mean));
+  const auto ka = kernel_args<BOX>(a, box);
   hipStream_t s = (hipStream_t)stream;
   if constexpr (MANY) {
-#define CALL(R) hipLaunchKernelGGL(loss_many_partial_kernel<R>, dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), 0, s, a, workspace)
+#define CALL(R) LOSS_LAUNCH(many_partial_kernel, <R>, dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), workspace)
     MC_DISPATCH(a.C, CALL);
 #undef CALL
   } else {
-    hipLaunchKernelGGL(loss_partial_kernel, dim3(LOSS_NPART, (unsigned)B), dim3(LOSS_THREADS), 0, s, a, workspace);
+    LOSS_LAUNCH(partial_kernel, , dim3(LOSS_NPART, (unsigned)B), dim3(LOSS_THREADS), workspace);
   }
   launch_finalize(loss_finalize_kernel, a, workspace, losses, nobj, mean4, s);
   return sqd_launch_status();
@@ -458,24 +640,25 @@ static int loss_dense_fwd(const float* pred, const float* gt, const float* ancho
 // Backward on a dense gt, exactly one of coef / gmean.  coef: float[3][B] upstream gradients of (class, score, bbox) per image
 // (total's gradient already added to each).  gmean (backward of mean(total)): a DEVICE float, the gradient arriving at the mean (1 for
 // `loss.mean().backward()`); every image's three components get gmean / B.
-template <bool MANY>
+template <bool MANY, bool BOX = false>
 static int loss_dense_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* coef,
                           const float* gmean, float* dpred, int B, int A, int C, int input_h, int input_w, float w_class, float w_pos,
-                          float w_neg, float w_bbox, void* stream) {
+                          float w_neg, float w_bbox, void* stream, int box = SQD_BOX_L2) {
   LossArgs a;
   if (int rc = (MANY ? fill_args_many : fill_args)(a, pred, gt, anchors, B, A, C, input_h, input_w, w_class, w_pos, w_neg, w_bbox)) return rc;
   SQD_CHECK_ARG(nobj && (coef || gmean) && dpred);
+  const auto ka = kernel_args<BOX>(a, box);
   hipStream_t s = (hipStream_t)stream;
   const long long rows = (long long)B * A;
   if constexpr (MANY) {
     const long long blocks64 = (rows + MC_GROUPS - 1) / MC_GROUPS;
     const unsigned blocks = (unsigned)(blocks64 < (1 << 20) ? blocks64 : (1 << 20));
-#define CALL(R) hipLaunchKernelGGL(loss_many_bwd_kernel<R>, dim3(blocks), dim3(MC_THREADS), 0, s, a, nobj, coef, dpred, gmean)
+#define CALL(R) LOSS_LAUNCH(many_bwd_kernel, <R>, dim3(blocks), dim3(MC_THREADS), nobj, coef, dpred, gmean)
     MC_DISPATCH(a.C, CALL);
 #undef CALL
   } else {
     const int blocks = (int)((rows + LOSS_THREADS - 1) / LOSS_THREADS);
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)blocks), dim3(LOSS_THREADS), 0, s, a, nobj, coef, dpred, gmean);
+    LOSS_LAUNCH(bwd_kernel, , dim3((unsigned)blocks), dim3(LOSS_THREADS), nobj, coef, dpred, gmean);
   }
   return sqd_launch_status();
 }
@@ -583,8 +766,8 @@ __device__ __forceinline__ void sparse_gt_row(const SparseGT& sg, int e, float (
 
 // MASKED: a row that is no positive and whose ignore bit is set adds nothing but a count, the sixth partial sum n_ign
 // (partial [B][LOSS_NPART][6]); the words are read from global memory by the global anchor index (a slice's lo is no multiple of 32).
-template <int R, bool MASKED = false>
-__global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArgs a, SparseArgs<MASKED> sg, float* __restrict__ partial) {
+template <int R, bool MASKED, bool BOX, class Args>
+__device__ __forceinline__ void loss_sparse_partial_body(const Args a, const SparseArgs<MASKED>& sg, float* __restrict__ partial) {
   constexpr int NS = MASKED ? 6 : 5;
   __shared__ unsigned bitmap[LS_BITMAP_WORDS];
   const int b = blockIdx.y, blk = blockIdx.x, C = a.C, tid = threadIdx.x;
@@ -631,7 +814,7 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArg
       if (j + MC_LANES * r == cls && cls < C) ce += -((l[r] - m) - lse);
     ce = mc_group_sum(ce);
     AnchorGeom t;
-    anchor_geom(a, p, g, a.anchors + 4 * i, t);
+    anchor_geom<BOX>(a, p, g, a.anchors + 4 * i, t);
     if (j == 0) {
       s[1] += ce;
       s[2] += t.e * t.e;
@@ -639,6 +822,15 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArg
     }
   }
   block_reduce_store<NS, MC_THREADS>(s, partial, b, blk);
+}
+
+template <int R, bool MASKED = false>
+__global__ __launch_bounds__(MC_THREADS) void loss_sparse_partial_kernel(LossArgs a, SparseArgs<MASKED> sg, float* __restrict__ partial) {
+  loss_sparse_partial_body<R, MASKED, false>(a, sg, partial);
+}
+template <int R, bool MASKED>
+__global__ __launch_bounds__(MC_THREADS) void loss_box_sparse_partial_kernel(LossBoxArgs a, SparseArgs<MASKED> sg, float* __restrict__ partial) {
+  loss_sparse_partial_body<R, MASKED, true>(a, sg, partial);
 }
 
 // The masked forward's second stage: counts [2][B] = (n_obj, n_neg).
@@ -653,10 +845,10 @@ __global__ void loss_masked_finalize_kernel(const float* __restrict__ partial, f
 // MASKED: ``nobj`` is counts [2][B] = (n_obj, n_neg) of the masked forward.  A positive row is what the unmasked kernel writes (the
 // negative denominator reaches it only as w_neg * 0 / n_neg); a row that is no positive and whose ignore bit is set is all +0; every
 // other row carries the confidence gradient with 1 / n_neg, and nothing is NaN because a count is 0.
-template <int R, bool MASKED = false>
-__global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a, SparseArgs<MASKED> sg, const float* __restrict__ nobj,
-                                                                     const float* __restrict__ coef, float* __restrict__ dpred,
-                                                                     const float* __restrict__ gmean) {
+template <int R, bool MASKED, bool BOX, class Args>
+__device__ __forceinline__ void loss_sparse_bwd_body(const Args a, const SparseArgs<MASKED>& sg, const float* __restrict__ nobj,
+                                                     const float* __restrict__ coef, float* __restrict__ dpred,
+                                                     const float* __restrict__ gmean) {
   __shared__ int slot[LS_ROWS];
   __shared__ float cgrad[LS_ROWS];
   __shared__ unsigned char ign[MASKED ? LS_ROWS : 1];
@@ -759,14 +951,27 @@ __global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a,
     const float m = mc_load_logits<R>(p, C, j, l);
     const float sum = mc_exp_sum<R>(C, j, m, l, ex);
     AnchorGeom t;
-    anchor_geom(a, p, g, a.anchors + 4 * (row0 + r), t);
+    anchor_geom<BOX>(a, p, g, a.anchors + 4 * (row0 + r), t);
     store_positive_row<R>(o + (long long)r * W, C, j, uc * a.w_class * t.mask / n, ohs, ex, sum,
                           [&](int, int c) { return c == cls ? 1.f : 0.f; },
                           [&](float (&og)[5]) {
-                            if (MASKED) anchor_geom_grad_nneg(a, t, p + C + 1, g, n, nneg > 0.f ? nneg : 1.f, us, ub, og);      // (mask = 1: w_neg * 0 / n_neg)
-                            else anchor_geom_grad(a, t, p + C + 1, g, n, us, ub, og);
+                            if (MASKED) anchor_geom_grad_nneg<BOX>(a, t, p + C + 1, g, n, nneg > 0.f ? nneg : 1.f, us, ub, og);      // (mask = 1: w_neg * 0 / n_neg)
+                            else anchor_geom_grad<BOX>(a, t, p + C + 1, g, n, us, ub, og);
                           });
   }
+}
+
+template <int R, bool MASKED = false>
+__global__ __launch_bounds__(MC_THREADS) void loss_sparse_bwd_kernel(LossArgs a, SparseArgs<MASKED> sg, const float* __restrict__ nobj,
+                                                                     const float* __restrict__ coef, float* __restrict__ dpred,
+                                                                     const float* __restrict__ gmean) {
+  loss_sparse_bwd_body<R, MASKED, false>(a, sg, nobj, coef, dpred, gmean);
+}
+template <int R, bool MASKED>
+__global__ __launch_bounds__(MC_THREADS) void loss_box_sparse_bwd_kernel(LossBoxArgs a, SparseArgs<MASKED> sg, const float* __restrict__ nobj,
+                                                                         const float* __restrict__ coef, float* __restrict__ dpred,
+                                                                         const float* __restrict__ gmean) {
+  loss_sparse_bwd_body<R, MASKED, true>(a, sg, nobj, coef, dpred, gmean);
 }
 
 // ---- host side of the sparse and the masked launches -----------------------------------------------------------------------------------
@@ -784,18 +989,19 @@ static int fill_args_sparse(LossArgs& a, SparseGT& sg, const float* pred, const 
 
 // Forward on the sparse ground truth (all device pointers).  Workspace (MASKED: float[B * 16 * 6]), losses, mean4 and mean as for
 // loss_dense_fwd; counts: nobj float[B], MASKED: float[2][B] = (n_obj, n_neg), what the backward takes in nobj's place.
-template <bool MASKED>
+template <bool MASKED, bool BOX = false>
 static int loss_sparse_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
                            const int* offsets, const unsigned* ignore, const float* anchors, float* workspace, float* losses,
                            float* counts, float* mean4, bool mean, int total, int B, int A, int C, int input_h, int input_w,
-                           float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
+                           float w_class, float w_pos, float w_neg, float w_bbox, void* stream, int box = SQD_BOX_L2) {
   LossArgs a; SparseGT sg;
   if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, C, input_h, input_w,
                                 w_class, w_pos, w_neg, w_bbox)) return rc;
   SQD_CHECK_ARG((ignore || !MASKED) && workspace && losses && counts && (mean4 || !mean));
+  const auto ka = kernel_args<BOX>(a, box);
   hipStream_t s = (hipStream_t)stream;
   const SparseArgs<MASKED> sa(sg, ignore);
-#define CALL(R) hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_sparse_partial_kernel<R, MASKED>), dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), 0, s, a, sa, workspace)
+#define CALL(R) LOSS_LAUNCH(sparse_partial_kernel, LOSS_T2(R, MASKED), dim3(LOSS_NPART, (unsigned)a.B), dim3(MC_THREADS), sa, workspace)
   MC_DISPATCH(a.C, CALL);
 #undef CALL
   if constexpr (MASKED) launch_finalize(loss_masked_finalize_kernel, a, workspace, losses, counts, mean4, s);
@@ -804,19 +1010,20 @@ static int loss_sparse_fwd(const float* pred, const int* anchor_idx, const float
 }
 
 // Backward on the sparse ground truth, exactly one of coef / gmean (loss_dense_bwd); counts: the forward's.
-template <bool MASKED>
+template <bool MASKED, bool BOX = false>
 static int loss_sparse_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas, const int* class_ids,
                            const int* offsets, const unsigned* ignore, const float* anchors, const float* counts, const float* coef,
                            const float* gmean, float* dpred, int total, int B, int A, int C, int input_h, int input_w, float w_class,
-                           float w_pos, float w_neg, float w_bbox, void* stream) {
+                           float w_pos, float w_neg, float w_bbox, void* stream, int box = SQD_BOX_L2) {
   LossArgs a; SparseGT sg;
   if (int rc = fill_args_sparse(a, sg, pred, anchor_idx, boxes, deltas, class_ids, offsets, anchors, total, B, A, C, input_h, input_w,
                                 w_class, w_pos, w_neg, w_bbox)) return rc;
   SQD_CHECK_ARG((ignore || !MASKED) && counts && (coef || gmean) && dpred);
+  const auto ka = kernel_args<BOX>(a, box);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)sqd_cdiv(a.A, LS_ROWS), (unsigned)a.B);
   const SparseArgs<MASKED> sa(sg, ignore);
-#define CALL(R) hipLaunchKernelGGL(HIP_KERNEL_NAME(loss_sparse_bwd_kernel<R, MASKED>), grid, dim3(MC_THREADS), 0, s, a, sa, counts, coef, dpred, gmean)
+#define CALL(R) LOSS_LAUNCH(sparse_bwd_kernel, LOSS_T2(R, MASKED), grid, dim3(MC_THREADS), sa, counts, coef, dpred, gmean)
   MC_DISPATCH(a.C, CALL);
 #undef CALL
   return sqd_launch_status();
@@ -886,4 +1093,89 @@ extern "C" int sqd_loss_masked_mean_bwd(const float* pred, const int* anchor_idx
                                         int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
                                         float w_bbox, void* stream) {
   return loss_sparse_bwd<true>(SPARSE_LIST, ignore, anchors, counts, nullptr, gmean, dpred, total, LOSS_TAIL);
+}
+
+// ---- any box regression kind: six entries, {dense, sparse, masked} x {fwd, bwd} ---------------------------------------------------------
+// box_loss: SQD_BOX_L2 .. SQD_BOX_CIOU (anything else: status 1).  SQD_BOX_L2 runs the launches of the sixteen entries above, so it
+// gives their bits; the other kinds run the loss_box_* kernels.  mean4: null for the plain forward; backward: exactly one of coef /
+// gmean.  The dense pair serves 1 <= num_classes <= 256: the <= 16-class kernels up to 16 classes, the many-class ones past it.
+#define BOX_DISPATCH(FN, ...) (box_loss == SQD_BOX_L2 ? FN<false>(__VA_ARGS__) : FN<true>(__VA_ARGS__, box_loss))
+#define BOX_KIND_OK(k) ((k) >= SQD_BOX_L2 && (k) <= SQD_BOX_CIOU)
+template <bool BOX> static int box_dense_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses,
+                                             float* nobj, float* mean4, int B, int A, int num_classes, int input_h, int input_w,
+                                             float w_class, float w_pos, float w_neg, float w_bbox, void* stream, int box = SQD_BOX_L2) {
+  if (num_classes <= LOSS_MAX_CLASSES) return loss_dense_fwd<false, BOX>(pred, gt, anchors, workspace, losses, nobj, mean4, mean4 != nullptr, LOSS_TAIL, box);
+  return loss_dense_fwd<true, BOX>(pred, gt, anchors, workspace, losses, nobj, mean4, mean4 != nullptr, LOSS_TAIL, box);
+}
+template <bool BOX> static int box_dense_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj,
+                                             const float* coef, const float* gmean, float* dpred, int B, int A, int num_classes,
+                                             int input_h, int input_w, float w_class, float w_pos, float w_neg, float w_bbox,
+                                             void* stream, int box = SQD_BOX_L2) {
+  if (num_classes <= LOSS_MAX_CLASSES) return loss_dense_bwd<false, BOX>(pred, gt, anchors, nobj, coef, gmean, dpred, LOSS_TAIL, box);
+  return loss_dense_bwd<true, BOX>(pred, gt, anchors, nobj, coef, gmean, dpred, LOSS_TAIL, box);
+}
+template <bool BOX> static int box_sparse_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                              const int* class_ids, const int* offsets, const unsigned* ignore, bool masked,
+                                              const float* anchors, float* workspace, float* losses, float* counts, float* mean4,
+                                              int total, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                                              float w_pos, float w_neg, float w_bbox, void* stream, int box = SQD_BOX_L2) {
+  if (masked) return loss_sparse_fwd<true, BOX>(SPARSE_LIST, ignore, anchors, workspace, losses, counts, mean4, mean4 != nullptr, total, LOSS_TAIL, box);
+  return loss_sparse_fwd<false, BOX>(SPARSE_LIST, nullptr, anchors, workspace, losses, counts, mean4, mean4 != nullptr, total, LOSS_TAIL, box);
+}
+template <bool BOX> static int box_sparse_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                              const int* class_ids, const int* offsets, const unsigned* ignore, bool masked,
+                                              const float* anchors, const float* counts, const float* coef, const float* gmean,
+                                              float* dpred, int total, int B, int A, int num_classes, int input_h, int input_w,
+                                              float w_class, float w_pos, float w_neg, float w_bbox, void* stream, int box = SQD_BOX_L2) {
+  if (masked) return loss_sparse_bwd<true, BOX>(SPARSE_LIST, ignore, anchors, counts, coef, gmean, dpred, total, LOSS_TAIL, box);
+  return loss_sparse_bwd<false, BOX>(SPARSE_LIST, nullptr, anchors, counts, coef, gmean, dpred, total, LOSS_TAIL, box);
+}
+
+extern "C" int sqd_loss_box_fwd(const float* pred, const float* gt, const float* anchors, float* workspace, float* losses, float* nobj,
+                                float* mean4, int box_loss, int B, int A, int num_classes, int input_h, int input_w, float w_class,
+                                float w_pos, float w_neg, float w_bbox, void* stream) {
+  SQD_CHECK_ARG(BOX_KIND_OK(box_loss));
+  return BOX_DISPATCH(box_dense_fwd, pred, gt, anchors, workspace, losses, nobj, mean4, LOSS_TAIL);
+}
+
+extern "C" int sqd_loss_box_bwd(const float* pred, const float* gt, const float* anchors, const float* nobj, const float* coef,
+                                const float* gmean, float* dpred, int box_loss, int B, int A, int num_classes, int input_h, int input_w,
+                                float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
+  SQD_CHECK_ARG(BOX_KIND_OK(box_loss) && (coef != nullptr) != (gmean != nullptr));
+  return BOX_DISPATCH(box_dense_bwd, pred, gt, anchors, nobj, coef, gmean, dpred, LOSS_TAIL);
+}
+
+extern "C" int sqd_loss_box_sparse_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                       const int* class_ids, const int* offsets, const float* anchors, float* workspace, float* losses,
+                                       float* nobj, float* mean4, int box_loss, int total, int B, int A, int num_classes, int input_h,
+                                       int input_w, float w_class, float w_pos, float w_neg, float w_bbox, void* stream) {
+  SQD_CHECK_ARG(BOX_KIND_OK(box_loss));
+  return BOX_DISPATCH(box_sparse_fwd, SPARSE_LIST, nullptr, false, anchors, workspace, losses, nobj, mean4, total, LOSS_TAIL);
+}
+
+extern "C" int sqd_loss_box_sparse_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                       const int* class_ids, const int* offsets, const float* anchors, const float* nobj,
+                                       const float* coef, const float* gmean, float* dpred, int box_loss, int total, int B, int A,
+                                       int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg, float w_bbox,
+                                       void* stream) {
+  SQD_CHECK_ARG(BOX_KIND_OK(box_loss) && (coef != nullptr) != (gmean != nullptr));
+  return BOX_DISPATCH(box_sparse_bwd, SPARSE_LIST, nullptr, false, anchors, nobj, coef, gmean, dpred, total, LOSS_TAIL);
+}
+
+extern "C" int sqd_loss_box_masked_fwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                       const int* class_ids, const int* offsets, const unsigned* ignore, const float* anchors,
+                                       float* workspace, float* losses, float* counts, float* mean4, int box_loss, int total, int B,
+                                       int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                                       float w_bbox, void* stream) {
+  SQD_CHECK_ARG(BOX_KIND_OK(box_loss));
+  return BOX_DISPATCH(box_sparse_fwd, SPARSE_LIST, ignore, true, anchors, workspace, losses, counts, mean4, total, LOSS_TAIL);
+}
+
+extern "C" int sqd_loss_box_masked_bwd(const float* pred, const int* anchor_idx, const float* boxes, const float* deltas,
+                                       const int* class_ids, const int* offsets, const unsigned* ignore, const float* anchors,
+                                       const float* counts, const float* coef, const float* gmean, float* dpred, int box_loss, int total,
+                                       int B, int A, int num_classes, int input_h, int input_w, float w_class, float w_pos, float w_neg,
+                                       float w_bbox, void* stream) {
+  SQD_CHECK_ARG(BOX_KIND_OK(box_loss) && (coef != nullptr) != (gmean != nullptr));
+  return BOX_DISPATCH(box_sparse_bwd, SPARSE_LIST, ignore, true, anchors, counts, coef, gmean, dpred, total, LOSS_TAIL);
 }

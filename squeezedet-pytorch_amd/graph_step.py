@@ -30,12 +30,14 @@ def gt_form(batch):
     return 'masked' if batch.get('gt_ignore') is not None else 'sparse'
 
 
-def step_signature(image_shape, form, cap, training, trainable, clip_on, loss_weights):
+def step_signature(image_shape, form, cap, training, trainable, clip_on, loss_weights, bbox_loss='l2'):
     """What a captured training step is valid for: a step whose signature differs runs other launches, other grids or other buffers.
     ``image_shape``: (B, H, W); ``form``: ``gt_form``; ``cap``: the sparse capacity (0 for dense); ``trainable``: names of the
-    parameters that require grad; ``clip_on``: whether the gradient norm is evaluated; ``loss_weights``: launch arguments of the loss."""
+    parameters that require grad; ``clip_on``: whether the gradient norm is evaluated; ``loss_weights`` and ``bbox_loss``: launch arguments of the
+    loss (the regression kind selects its kernels)."""
     B, H, W = (int(v) for v in image_shape)
-    return (B, H, W, str(form), int(cap), bool(training), tuple(trainable), bool(clip_on), tuple(float(w) for w in loss_weights))
+    return (B, H, W, str(form), int(cap), bool(training), tuple(trainable), bool(clip_on), tuple(float(w) for w in loss_weights),
+            str(bbox_loss))
 
 
 class GraphedStep:
@@ -156,7 +158,8 @@ class GraphedStep:
         if cap is None:
             cap = self._cap.get((B, H, W, form), 0)
         return step_signature((B, H, W), form, cap, self.model.training,
-                              [n for n, p in self.model.named_parameters() if p.requires_grad], self.optimizer.max_norm > 0, weights)
+                              [n for n, p in self.model.named_parameters() if p.requires_grad], self.optimizer.max_norm > 0, weights,
+                              getattr(loss, 'bbox_loss', 'l2'))
 
     def _stage(self, key, batch):
         """Copy the batch into the static buffers of ``key`` (device to device, on the current stream) -> (the static batch, whether the

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .config import check_bbox_loss
 from .plan import conv3x3_cfg
 from .plans import PlanCache, version
 from .synthetic import layer_table, convdet_in_channels
@@ -414,6 +415,8 @@ class Loss(nn.Module):
         self.positive_score_loss_weight = cfg.positive_score_loss_weight
         self.negative_score_loss_weight = cfg.negative_score_loss_weight
         self.bbox_loss_weight = cfg.bbox_loss_weight
+        # 'l2' (the reference's squared error on the deltas) | 'iou' | 'giou' | 'diou' | 'ciou': the regression term of the loss launches
+        self.bbox_loss = check_bbox_loss(getattr(cfg, 'bbox_loss', 'l2'), 'Loss')
 
     def forward(self, pred, gt, ignore=None):
         """``gt``: the dense tensor [B,A,C+9] or an ``ops.SparseGT`` (the positives as a list: the sparse loss launches).  ``ignore``:

@@ -1216,21 +1216,54 @@ def _check_loss_args(pred, gt, anchors, num_classes):
     return B, A
 
 
+BOX_LOSSES = ('l2', 'iou', 'giou', 'diou', 'ciou')      # cfg.bbox_loss; the index is the C ABI's SQD_BOX_*
+
+
+def box_loss_kind(name, box_loss):
+    """``box_loss`` (one of ``BOX_LOSSES``) -> SQD_BOX_*; checked before anything is launched."""
+    if not isinstance(box_loss, str) or box_loss not in BOX_LOSSES:
+        raise ValueError(f'{name}: box_loss must be one of {BOX_LOSSES}, got {box_loss!r}')
+    return BOX_LOSSES.index(box_loss)
+
+
+def split_loss_weights(name, weights):
+    """The ``weights`` argument of every ``loss_*`` wrapper: (w_class, w_pos, w_neg, w_bbox), optionally followed by the box-loss
+    kind (one of ``BOX_LOSSES``; absent: 'l2', the squared error on the deltas).  -> (the four weights, SQD_BOX_*)."""
+    weights = tuple(weights)
+    if len(weights) == 5:
+        return weights[:4], box_loss_kind(name, weights[4])
+    if len(weights) != 4:
+        raise ValueError(f'{name}: weights must be (w_class, w_pos, w_neg, w_bbox[, box_loss]), got {len(weights)} values')
+    return weights, 0
+
+
+def _box_entry(kind):
+    """The sqd_loss_box_* entry of a launch-record kind ('loss_fwd', 'loss_sparse_bwd', ...): one per family and pass."""
+    return 'sqd_' + kind.replace('loss_', 'loss_box_', 1)
+
+
 def _run_loss_fwd(entry, pred, mid, anchors, lead, B, A, num_classes, input_size, weights, ws_width, count_rows, mean, kind, nbytes):
     """What the eight forward wrappers do once their operands are checked.  ``mid``: the contiguous tensors between pred and anchors
     in the entry's argument list (gt, or the five list members, then the bitmap); ``lead``: the integers in front of B (``total`` of
     the sparse entries); ``ws_width``: partial sums per block (5, masked 6); ``count_rows``: () for nobj [B], (2,) for counts [2,B];
     ``mean``: the entry also takes mean4 [4]; ``nbytes(B, A, *lead, num_classes)``: the bracket's bytes, asked only when a timer
-    runs.  -> (losses, nobj or counts[, mean4])."""
+    runs; ``weights`` with a box-loss kind other than 'l2' (``split_loss_weights``): the family's sqd_loss_box_* entry (same
+    operands, records and bytes).  -> (losses, nobj or counts[, mean4])."""
+    weights, box = split_loss_weights(entry, weights)
     pred, anchors = pred.contiguous(), anchors.contiguous()
     ws = torch.empty(B * 16 * ws_width, device=pred.device, dtype=torch.float32)
     out = [torch.empty(4, B, device=pred.device, dtype=torch.float32), torch.empty(*count_rows, B, device=pred.device, dtype=torch.float32)]
     if mean:
         out.append(torch.empty(4, device=pred.device, dtype=torch.float32))
     br = _Bracket(kind, f'loss A{A}', 0.0, nbytes(B, A, *lead, num_classes)) if timing._timer is not None else None
-    rc = getattr(nat.lib(), entry)(nat.ptr(pred), *[nat.ptr(t) for t in mid], nat.ptr(anchors), nat.ptr(ws), *[nat.ptr(t) for t in out],
-                                   *lead, B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights],
-                                   nat.stream_handle(pred.device))
+    entry = _box_entry(kind) if box else entry
+    fn = getattr(nat.lib(), entry)
+    tail = (*lead, B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights], nat.stream_handle(pred.device))
+    if box:
+        rc = fn(nat.ptr(pred), *[nat.ptr(t) for t in mid], nat.ptr(anchors), nat.ptr(ws), nat.ptr(out[0]), nat.ptr(out[1]),
+                nat.ptr(out[2] if mean else None), box, *tail)
+    else:
+        rc = fn(nat.ptr(pred), *[nat.ptr(t) for t in mid], nat.ptr(anchors), nat.ptr(ws), *[nat.ptr(t) for t in out], *tail)
     nat.check(rc, entry)
     if br is not None:
         br.done()
@@ -1240,13 +1273,21 @@ def _run_loss_fwd(entry, pred, mid, anchors, lead, B, A, num_classes, input_size
 def _run_loss_bwd(entry, pred, mid, anchors, counts, upstream, out, lead, B, A, num_classes, input_size, weights, kind, nbytes):
     """What the eight backward wrappers do once their operands are checked: ``mid`` / ``lead`` / ``nbytes`` as for ``_run_loss_fwd``; ``counts``:
     the forward's nobj or counts; ``upstream``: coef or gmean, whichever the entry takes; ``out``: a checked tensor to write, or None
-    for a new one.  -> dpred."""
+    for a new one; ``weights`` with a box-loss kind other than 'l2': the family's sqd_loss_box_* entry, which takes coef and gmean
+    side by side (the one ``entry`` does not take is null).  -> dpred."""
+    weights, box = split_loss_weights(entry, weights)
     pred, anchors = pred.contiguous(), anchors.contiguous()
     dpred = torch.empty_like(pred) if out is None else out
     br = _Bracket(kind, f'lossbwd A{A}', 0.0, nbytes(B, A, *lead, num_classes)) if timing._timer is not None else None
-    rc = getattr(nat.lib(), entry)(nat.ptr(pred), *[nat.ptr(t) for t in mid], nat.ptr(anchors), nat.ptr(counts), nat.ptr(upstream),
-                                   nat.ptr(dpred), *lead, B, A, num_classes, int(input_size[0]), int(input_size[1]),
-                                   *[float(w) for w in weights], nat.stream_handle(pred.device))
+    gmean = 'mean' in entry
+    entry = _box_entry(kind) if box else entry
+    fn = getattr(nat.lib(), entry)
+    tail = (*lead, B, A, num_classes, int(input_size[0]), int(input_size[1]), *[float(w) for w in weights], nat.stream_handle(pred.device))
+    if box:
+        rc = fn(nat.ptr(pred), *[nat.ptr(t) for t in mid], nat.ptr(anchors), nat.ptr(counts), nat.ptr(None if gmean else upstream),
+                nat.ptr(upstream if gmean else None), nat.ptr(dpred), box, *tail)
+    else:
+        rc = fn(nat.ptr(pred), *[nat.ptr(t) for t in mid], nat.ptr(anchors), nat.ptr(counts), nat.ptr(upstream), nat.ptr(dpred), *tail)
     nat.check(rc, entry)
     if br is not None:
         br.done()
