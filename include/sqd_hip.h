@@ -266,6 +266,26 @@ int sqd_filter_many_fwd(const long long* class_ids, const float* scores, const f
                         long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
                         int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words, void* stream);
 
+/* NMS modes: the wide fused detect / dense filter for either head form (1 <= num_classes <= 256, 1 <= keep_top_k <= 1024,
+ * 1 <= A <= 2^20; workspace: sqd_detect_wide_workspace_words) with the suppression rule as an argument.  nms_mode: 0 hard, 1 linear
+ * Soft-NMS (s_j *= 1 - u where u > nms_thresh), 2 Gaussian Soft-NMS (s_j *= expf(-(u * u) / nms_sigma) for every j; nms_sigma finite
+ * and > 0, read in this mode only; nms_thresh unused).  nms_agnostic != 0: one group for all classes instead of one per class.  Rows
+ * come out in class order (agnostic: one group), within a group in pick order, det_score holding the decayed score at pick time; rows
+ * whose score fell to score_thresh or below are gone.  (hard, class-wise) equals sqd_detect_wide_fwd / sqd_filter_wide_fwd (and the
+ * _many_ pair) bit for bit.  keys_ready != 0 (sqd_detect_nms_fwd with num_classes <= 16 only): keys_ws already holds the keys of this
+ * pred ([B][ceil4(A)] uint32, written by sqd_conv_wino_vs_keys_fwd with the same score_thresh earlier on the same stream; the pad
+ * words may hold anything) and no scoring launch runs.  Status 1 for anything malformed -- a null pointer, an unknown nms_mode, a
+ * sigma that is not finite and positive in mode 2, score_thresh < 0, keys_ready where it cannot apply, a short or misaligned
+ * workspace; status 2 past the limits; nothing is launched then. */
+int sqd_detect_nms_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                       int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                       int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                       int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, void* stream);
+int sqd_filter_nms_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
+                       long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                       int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words,
+                       int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, void* stream);
+
 /* GPU-side input pipeline: whiten + cv2.resize(INTER_LINEAR) + HWC->CHW of
  * DataWrapper.__getitem__ / BaseDataset.preprocess / whiten / resize (src/engine/detector.py:132-142,
  * src/datasets/base.py:43-59, src/utils/image.py:9-19,77-88) for a batch of uint8 RGB images of arbitrary sizes.

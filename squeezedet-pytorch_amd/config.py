@@ -42,6 +42,25 @@ def check_bbox_loss(kind, who):
     return kind
 
 
+NMS_MODES = ('hard', 'linear', 'gaussian')               # ops.NMS_MODES; the index is the C ABI's nms_mode
+
+
+def check_nms(cfg, who):
+    """The suppression rule of ``cfg``: (nms_mode, nms_sigma, nms_agnostic).  ``nms_mode`` is one of the three names, ``nms_sigma`` a
+    finite float > 0 (the Gaussian mode's only reader, checked in every mode), ``nms_agnostic`` a bool.  A cfg without the fields
+    (the reference's own namespace) means ('hard', 0.5, False)."""
+    mode = getattr(cfg, 'nms_mode', 'hard')
+    if not isinstance(mode, str) or mode not in NMS_MODES:
+        raise ValueError(f'{who}: nms_mode must be one of {NMS_MODES}, got {mode!r}')
+    sigma = getattr(cfg, 'nms_sigma', 0.5)
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.floating, np.integer)) or not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f'{who}: nms_sigma must be a finite number > 0, got {sigma!r}')
+    agnostic = getattr(cfg, 'nms_agnostic', False)
+    if not isinstance(agnostic, (bool, np.bool_)):
+        raise ValueError(f'{who}: nms_agnostic must be a bool, got {agnostic!r}')
+    return mode, float(sigma), bool(agnostic)
+
+
 def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_ANCHORS_SEED,
              num_classes=3, class_names=None, device='cuda', **overrides):
     """Namespace with the reference's defaults (src/utils/config.py:23-85) plus the
@@ -64,6 +83,10 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         bbox_loss='l2',              # the regression term: 'l2' (squared error on the deltas, the reference) or 1 - q of the decoded box against
                                      # the gt box, q = 'iou' | 'giou' | 'diou' | 'ciou' (bbox_loss_weight stays the user's to set)
         nms_thresh=0.4, score_thresh=0.3, keep_top_k=64,
+        nms_mode='hard',             # 'hard' (the reference) | 'linear' | 'gaussian': Soft-NMS decays the score of an overlapped box instead of
+                                     # deleting it ("NMS modes"); nms_sigma: the Gaussian mode's width
+        nms_sigma=0.5,
+        nms_agnostic=False,          # True: one suppression group for all classes instead of one per class
         gpus=[0], chunk_sizes=[20], num_iters=-1, print_interval=10, debug=0, num_workers=4, forbid_resize=False,
         flip_prob=0.5, drift_prob=1., seed=42,      # training augmentation (train_data.TrainLoader), src/utils/config.py:53-56
         brightness_jitter=0., contrast_jitter=0., saturation_jitter=0.,      # colour jitter amounts (augment.draw_color); 0 = off
@@ -87,4 +110,5 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         setattr(cfg, k, v)
     check_geometry(cfg, 'make_cfg')
     check_bbox_loss(cfg.bbox_loss, 'make_cfg')
+    check_nms(cfg, 'make_cfg')
     return cfg

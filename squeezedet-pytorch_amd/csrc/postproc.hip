@@ -586,6 +586,21 @@ __device__ __forceinline__ void detw_hist_add(unsigned* hist, bool act, unsigned
   if (act) atomicAdd(&hist[bin], 1u);
 }
 
+// One detection row -- row `pos` of image b, boxes_postprocess' scale division and padding / crops shift folded in (see detect_kernel)
+// -- for every placement of the wide kernels.  A macro, not a function, for the reason given in detw_select_body.h: the text is what
+// detect_wide_select_kernel always held, so its device code stays what it was.
+#define DETW_STORE_ROW(a, b, K, pos, cls, score, idx, bx) do { \
+    float sx = 1.f, sy = 1.f; \
+    if ((a).scales) { sy = (a).scales[2 * (b)]; sx = (a).scales[2 * (b) + 1]; } \
+    const long long o = (long long)(b) * (K) + (pos); \
+    (a).det_class[o] = (cls); \
+    (a).det_score[o] = (score); \
+    (a).det_anchor[o] = (idx); \
+    f32x4 ob = (f32x4){(bx).x1 / sx, (bx).y1 / sy, (bx).x2 / sx, (bx).y2 / sy}; \
+    if ((a).shifts) { const float dy = (a).shifts[2 * (b)], dx = (a).shifts[2 * (b) + 1]; ob.x += dx; ob.y += dy; ob.z += dx; ob.w += dy; } \
+    *(f32x4*)((a).det_box + 4 * o) = ob; \
+  } while (0)
+
 // MANY = false: the <= 16-class form (thread r re-decodes rank r with anchor_score, placement from per-wave per-class counts).
 // MANY = true: the many-class form (see "many-class head" below); everything that does not depend on C is shared.
 template <bool MANY>
@@ -602,139 +617,9 @@ __global__ __launch_bounds__(DETW_THREADS) void detect_wide_select_kernel(DetArg
   unsigned* sv = (unsigned*)(aliveL + 16);                    // prefix, need, appended
   unsigned long long* mat = (unsigned long long*)(sv + 4);    // [64 Wn][Wn] suppression bits, Wn = ceil(candidates / 64) <= Kp / 64
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = (int)blockIdx.x;
-  const int A = a.A, C = a.C, A4 = (A + 3) & ~3, nq = A4 >> 2;
-  const u32x4_w* __restrict__ ws4 = (const u32x4_w*)(a.keys + (long long)b * A4);
-  const bool dense = a.in_score != nullptr;
-
-  if (tid == 0) { sv[0] = 0u; sv[1] = (unsigned)K; sv[2] = 0u; }
-  if (tid < Kp) { clsL[tid] = -1; boxL[tid] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-  __syncthreads();
-
-  // 1. radix select of the K-th largest key among the M non-zero keys (pass 0 counts M)
-  unsigned mask = 0u, M = 0u;
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    if (tid < 256) hist[tid] = 0u;
-    __syncthreads();
-    const unsigned prefix = sv[0];
-    for (int q0 = 0; q0 < nq; q0 += DETW_THREADS) {
-      const int q = q0 + tid;
-      u32x4_w v = (u32x4_w){0u, 0u, 0u, 0u};
-      if (q < nq) v = ws4[q];
-      const unsigned ks[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) detw_hist_add(hist, ks[e] != 0u && (ks[e] & mask) == prefix, (ks[e] >> shift) & 255u, lane);
-    }
-    __syncthreads();
-    const unsigned need = sv[1];
-    const unsigned h = (tid < 256) ? hist[255 - tid] : 0u;     // thread t owns bin 255 - t: the scan counts the keys in higher bins
-    unsigned tot;
-    const unsigned above = detw_excl_scan(h, tot, wave_tot, lane, wave);
-    if (pass == 0) { M = tot; if (M <= (unsigned)K) break; }   // (uniform) every candidate is taken
-    if (tid < 256 && above < need && above + h >= need) {      // exactly one thread
-      sv[1] = need - above;
-      sv[0] = prefix | ((unsigned)(255 - tid) << shift);
-    }
-    mask |= 255u << shift;
-    __syncthreads();
-  }
-  const bool sel = M > (unsigned)K;
-  const unsigned tkey = sel ? sv[0] : 0u;                      // K-th largest key (>= 1), or 0: take every non-zero key
-  const unsigned need = sel ? sv[1] : 0u;                      // keys == tkey to take, in ascending anchor order
-  const unsigned n_gt = sel ? (unsigned)K - need : M;
-  const int ncand = sel ? K : (int)M;
-
-  // 2. one ordered sweep, a contiguous run of quads per thread: keys above tkey are appended in any order (ranked below), the ties
-  //    at tkey take the slots behind them in anchor order
-  {
-    const int chunk = (nq + DETW_THREADS - 1) / DETW_THREADS;
-    const int lo = min(nq, tid * chunk), hi = min(nq, lo + chunk);
-    unsigned r = 0u;
-    if (sel) {
-      unsigned c2 = 0u;
-      for (int q = lo; q < hi; ++q) {
-        const u32x4_w v = ws4[q];
-        c2 += (v.x == tkey ? 1u : 0u) + (v.y == tkey ? 1u : 0u) + (v.z == tkey ? 1u : 0u) + (v.w == tkey ? 1u : 0u);
-      }
-      unsigned tot2;
-      r = detw_excl_scan(c2, tot2, wave_tot, lane, wave);
-    }
-    for (int q = lo; q < hi; ++q) {
-      const u32x4_w v = ws4[q];
-      const unsigned ks[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned k = ks[e];
-        const unsigned long long word = ((unsigned long long)k << 32) | (unsigned long long)(0xffffffffu - (unsigned)(4 * q + e));
-        if (k > tkey) {
-          const unsigned pos = atomicAdd(&sv[2], 1u);
-          if (pos < n_gt) cand[pos] = word;
-        } else if (sel && k == tkey && r < need) {
-          cand[n_gt + r] = word; ++r;
-        }
-      }
-    }
-  }
-  __syncthreads();
-
-  // 3. rank: score descending, anchor index ascending = the 64-bit words descending; they are distinct, so the ranks are a permutation
-  {
-    unsigned long long mine = 0ull;
-    int rank = 0;
-    if (tid < ncand) {
-      mine = cand[tid];
-      for (int j = 0; j < ncand; ++j) rank += (cand[j] > mine) ? 1 : 0;
-    }
-    __syncthreads();
-    if (tid < ncand) cand[rank] = mine;
-    __syncthreads();
-  }
-
-  // 4. thread r decodes the candidate of rank r
-  const bool ok = tid < ncand;
-  float score = 0.f; int cls = -1, idx = 0;
-  BoxF bx = {0.f, 0.f, 0.f, 0.f};
-  if (MANY && !dense) {
-    // a 16-lane group per candidate (64 groups, <= 16 rounds): the class comes from the same mc_anchor_score that made the key, so
-    // the score IS the key; lane 0 of the group decodes the box
-    const int j = tid & (MC_LANES - 1);
-    for (int r = tid / MC_LANES; r < ncand; r += DETW_THREADS / MC_LANES) {
-      const int ai = (int)(0xffffffffu - (unsigned)(cand[r] & 0xffffffffull));
-      const float* p = a.pred + ((long long)b * A + ai) * (C + 5);
-      float s; int c;
-      mc_anchor_score<MC_REGS>(p, C, j, s, c);
-      if (j == 0) {
-        const BoxF bb = anchor_box(p + C + 1, a.anchors + 4 * ai, a.wmax, a.hmax);
-        boxL[r] = (f32x4){bb.x1, bb.y1, bb.x2, bb.y2};
-        clsL[r] = c;
-      }
-    }
-    __syncthreads();
-    if (ok) {
-      idx = (int)(0xffffffffu - (unsigned)(cand[tid] & 0xffffffffull));
-      score = __uint_as_float((unsigned)(cand[tid] >> 32));
-      cls = clsL[tid];
-      const f32x4 v = boxL[tid];
-      bx.x1 = v.x; bx.y1 = v.y; bx.x2 = v.z; bx.y2 = v.w;
-    }
-  } else if (ok) {
-    idx = (int)(0xffffffffu - (unsigned)(cand[tid] & 0xffffffffull));
-    if (dense) {
-      const long long o = (long long)b * A + idx;
-      score = a.in_score[o]; cls = (int)a.in_class[o];
-      const f32x4 v = *(const f32x4*)(a.in_box + 4 * o);
-      bx.x1 = v.x; bx.y1 = v.y; bx.x2 = v.z; bx.y2 = v.w;
-    } else {
-      const float* p = a.pred + ((long long)b * A + idx) * (C + 5);
-      anchor_score(p, C, score, cls);
-      bx = anchor_box(p + C + 1, a.anchors + 4 * idx, a.wmax, a.hmax);
-    }
-    boxL[tid] = (f32x4){bx.x1, bx.y1, bx.x2, bx.y2};
-    clsL[tid] = cls;
-  }
-  __syncthreads();
+#define DETW_PAD_ANY false
+#include "detw_select_body.h"     // 1.-4. select, sweep, rank, decode: tid, lane, wave, b, A, C, ncand, ok, score, cls, idx, bx
+#undef DETW_PAD_ANY
 
   // 5. suppression matrix: bit j of row i set if j ranks after i, same class, IoU > thresh.  Only blocks on or above the diagonal
   //    can hold bits: those Wn (Wn + 1) / 2 blocks of 64 rows x 64 columns go round-robin to the waves, lane = row; the rest is zeroed
@@ -808,15 +693,7 @@ __global__ __launch_bounds__(DETW_THREADS) void detect_wide_select_kernel(DetArg
         const int cr = clsL[r];
         pos += (cr >= 0 && (cr < cls || (cr == cls && r < tid))) ? 1u : 0u;
       }
-      float sx = 1.f, sy = 1.f;
-      if (a.scales) { sy = a.scales[2 * b]; sx = a.scales[2 * b + 1]; }
-      const long long o = (long long)b * K + pos;
-      a.det_class[o] = cls;
-      a.det_score[o] = score;
-      a.det_anchor[o] = idx;
-      f32x4 ob = (f32x4){bx.x1 / sx, bx.y1 / sy, bx.x2 / sx, bx.y2 / sy};
-      if (a.shifts) { const float dy = a.shifts[2 * b], dx = a.shifts[2 * b + 1]; ob.x += dx; ob.y += dy; ob.z += dx; ob.w += dy; }
-      *(f32x4*)(a.det_box + 4 * o) = ob;
+      DETW_STORE_ROW(a, b, K, pos, cls, score, idx, bx);
     }
     return;
   }
@@ -839,16 +716,7 @@ __global__ __launch_bounds__(DETW_THREADS) void detect_wide_select_kernel(DetArg
       for (int c = 0; c < cls; ++c) pos += cls_cnt[w * 16 + c];
       if (w < wave) pos += cls_cnt[w * 16 + cls];
     }
-    float sx = 1.f, sy = 1.f;
-    if (a.scales) { sy = a.scales[2 * b]; sx = a.scales[2 * b + 1]; }
-    const long long o = (long long)b * K + pos;
-    a.det_class[o] = cls;
-    a.det_score[o] = score;
-    a.det_anchor[o] = idx;
-    f32x4 ob = (f32x4){bx.x1 / sx, bx.y1 / sy, bx.x2 / sx, bx.y2 / sy};
-    // (the padding / crops shift: see detect_kernel)
-    if (a.shifts) { const float dy = a.shifts[2 * b], dx = a.shifts[2 * b + 1]; ob.x += dx; ob.y += dy; ob.z += dx; ob.w += dy; }
-    *(f32x4*)(a.det_box + 4 * o) = ob;
+    DETW_STORE_ROW(a, b, K, pos, cls, score, idx, bx);
   }
 }
 
@@ -1093,4 +961,267 @@ extern "C" int sqd_filter_many_fwd(const long long* class_ids, const float* scor
   a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
   a.wmax = 0.f; a.hmax = 0.f; a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
   return launch_detect_many(a, ws_words, (hipStream_t)stream);
+}
+
+// ---- NMS modes: Soft-NMS (linear / Gaussian, Bodla et al. 2017) and class-agnostic NMS ------------------------------------------------
+// The wide two-launch structure with another suppression step: the scoring launch (or ConvDet's epilogue: keys_ready) fills the key
+// workspace, detect_nms_select_kernel -- one 1024-thread workgroup per image -- runs detw_select_body.h (the selection, ranking and
+// decode of detect_wide_select_kernel, the same text) and then, instead of the bit matrix, the rule of DESIGN.md section 3 "NMS modes":
+//   groups = the classes 0 .. C-1 (agnostic: one group of all candidates).  Within a group, repeatedly pick the candidate with the
+//   largest current score (tie: the lower rank); stop when that score is not above score_thresh; emit it with its current score; then
+//   for every remaining candidate j of the group, with u = IoU(pick, j) -- detect_kernel's fp32 expression
+//   inter / ((area_i + area_j) - inter) --   hard: drop j if u > nms_thresh;   linear: if u > nms_thresh, s_j = s_j * (1 - u);
+//   gaussian: s_j = s_j * expf(-(u * u) / sigma) for every j.  Output: groups in class order, each in pick order.
+// Why stopping at the first pick at or below the threshold equals thresholding after a full scan: scores only fall (every factor is in
+// [0, 1]), so once the largest current score of a group is at or below the threshold every remaining one is and stays there, and a
+// pick at or below the threshold could only decay candidates that the same threshold drops anyway -- the emitted rows and their scores
+// are those of the full scan followed by the threshold (the argument of the pre-filter above, applied to the tail of the scan).
+// A soft pick changes the scores that decide the next pick, so the scan is sequential; its state is ONE float per candidate (the
+// current score; -1 = emitted or dropped, never picked again) and the IoUs are computed at pick time, one per remaining candidate
+// per step -- no K x K matrix.  The candidates are first ordered by (group, rank), every group a contiguous segment, then:
+//   * class-wise: the groups are dealt to the 16 waves.  A group of <= 64 candidates is one wave with box and score in registers:
+//     a step = a 6-step cross-lane max, a ballot (lowest lane = lowest rank wins a tie), one broadcast LDS read of the pick's box,
+//     one IoU per lane; no barrier.  A longer group strides over the lanes of its wave with the scores in LDS, each step one fused
+//     pass (apply the pick, find the lane's next maximum);
+//   * agnostic with more than 64 candidates -- the one case where a single group is worth more than a wave: candidate p sits in
+//     thread p's registers, a step = wave-local argmax, one slot per wave in LDS, ONE barrier (the slots alternate between two
+//     banks, so the next step's writes never meet this step's reads), then every wave reduces the 16 slots redundantly.
+// Steps = emitted rows + 1 per group, not K.  The placement is that of the hard kernels: a row = (rows of earlier groups) + pick order.
+// NaN: a current score that becomes NaN (Gaussian mode on two zero-area boxes: u = 0 / 0) is never picked and never emitted.
+#define NMS_HARD 0
+#define NMS_LINEAR 1
+#define NMS_GAUSSIAN 2
+#define NMS_LDS_FIXED (256 * 4 + 16 * 4 + 16 + 4 * 256 * 4 + 2 * 16 * 8)     // histogram, wave totals, scalars, 4 group tables, argmax slots
+
+struct NmsArgs { int mode; float sigma; int agnostic; };
+
+__device__ __forceinline__ float nms_wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+
+__device__ __forceinline__ int nms_wave_min(int v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
+  return v;
+}
+
+// current score s of a remaining candidate after the pick `pk` (area pa) was emitted; o = the candidate's box
+__device__ __forceinline__ float nms_decay(const NmsArgs n, float nms_thresh, const f32x4 pk, float pa, const f32x4 o, float s) {
+  const float oa = (o.z - o.x) * (o.w - o.y);
+  const float iw = fmaxf(0.f, fminf(pk.z, o.z) - fmaxf(pk.x, o.x));
+  const float ih = fmaxf(0.f, fminf(pk.w, o.w) - fmaxf(pk.y, o.y));
+  const float inter = iw * ih;
+  const float u = inter / ((pa + oa) - inter);
+  if (n.mode == NMS_GAUSSIAN) return s * expf(-(u * u) / n.sigma);
+  if (u > nms_thresh) return n.mode == NMS_LINEAR ? s * (1.f - u) : -1.f;
+  return s;
+}
+
+template <bool MANY>
+__global__ __launch_bounds__(DETW_THREADS) void detect_nms_select_kernel(DetArgs a, NmsArgs n) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int K = a.K, Kp = (K + 63) & ~63;                     // Kp <= 1024: one candidate slot per thread
+  unsigned long long* cand = (unsigned long long*)smem_raw;   // [Kp] as detect_wide_select_kernel
+  f32x4* boxL = (f32x4*)(cand + Kp);                          // [Kp] boxes in rank order
+  f32x4* boxP = boxL + Kp;                                    // [Kp] boxes in (group, rank) order
+  int* clsL = (int*)(boxP + Kp);                              // [Kp] classes in rank order
+  int* grpL = clsL + Kp;                                      // [Kp] group of rank r, -1: none (no candidate, class outside 0 .. C-1)
+  float* curL = (float*)(grpL + Kp);                          // [Kp] current scores in (group, rank) order
+  float* outS = curL + Kp;                                    // [Kp] score at pick time
+  int* emitL = (int*)(outS + Kp);                             // [Kp] pick order within the group, -1: not emitted
+  unsigned* hist = (unsigned*)(emitL + Kp);                   // [256]
+  unsigned* wave_tot = hist + 256;                            // [16]
+  unsigned* sv = wave_tot + 16;                               // prefix, need, appended
+  int* gstart = (int*)(sv + 4);                               // [256] first slot of a group
+  int* glen = gstart + 256;                                   // [256] its candidates
+  unsigned* gcnt = (unsigned*)(glen + 256);                   // [256] its emitted rows
+  unsigned* goff = gcnt + 256;                                // [256] rows of the groups before it
+  float* slot_s = (float*)(goff + 256);                       // [2][16] a wave's best current score ...
+  int* slot_p = (int*)(slot_s + 32);                          // [2][16] ... and its slot
+
+#define DETW_PAD_ANY true
+#include "detw_select_body.h"     // 1.-4. select, sweep, rank, decode: tid, lane, wave, b, A, C, ncand, ok, score, cls, idx, bx
+#undef DETW_PAD_ANY
+  const int G = n.agnostic ? 1 : C;
+  const float thr = a.score_thresh;
+
+  // 5. order by (group, rank): slot = candidates of earlier groups + earlier ranks of my group
+  const int g = (ok && cls >= 0 && cls < C) ? (n.agnostic ? 0 : cls) : -1;
+  if (tid < Kp) { grpL[tid] = g; curL[tid] = -1.f; emitL[tid] = -1; }
+  if (tid < 256) { glen[tid] = 0; gstart[tid] = 0; gcnt[tid] = 0u; }
+  __syncthreads();
+  int slot = 0;
+  if (n.agnostic) {
+    unsigned tot;
+    slot = (int)detw_excl_scan(g >= 0 ? 1u : 0u, tot, wave_tot, lane, wave);
+    if (tid == 0) glen[0] = (int)tot;
+  } else if (g >= 0) {
+    int before = 0, same_before = 0, same = 0;
+    for (int r = 0; r < ncand; ++r) {
+      const int gr = grpL[r];
+      before += (gr >= 0 && (gr < g || (gr == g && r < tid))) ? 1 : 0;
+      same_before += (gr == g && r < tid) ? 1 : 0;
+      same += (gr == g) ? 1 : 0;
+    }
+    slot = before;
+    if (same_before == 0) { gstart[g] = before; glen[g] = same; }
+  }
+  if (g >= 0) { boxP[slot] = (f32x4){bx.x1, bx.y1, bx.x2, bx.y2}; curL[slot] = score; }     // slot < ncand <= Kp
+  __syncthreads();
+
+  // 6. the scan
+  if (n.agnostic && glen[0] > 64) {
+    // one group on the whole workgroup: slot p in thread p's registers (glen[0] <= ncand <= 1024 = the threads)
+    const int len = glen[0];
+    const f32x4 me = boxP[tid < len ? tid : 0];
+    float cur = tid < len ? curL[tid] : -1.f;
+    int t = 0;
+    for (;; ++t) {                                             // <= len + 1 rounds: every round but the last retires one candidate
+      const float wm = nms_wave_max(cur);
+      const unsigned long long hit = __ballot(cur == wm);
+      float* ss = slot_s + 16 * (t & 1); int* sp = slot_p + 16 * (t & 1);
+      if (lane == 0) { ss[wave] = wm; sp[wave] = hit ? wave * 64 + (__ffsll((long long)hit) - 1) : 0; }
+      __syncthreads();
+      const float v = lane < 16 ? ss[lane] : -1.f;
+      const float m = nms_wave_max(v);
+      if (!(m > thr)) break;                                   // (the same m in every wave: the whole workgroup leaves together)
+      const unsigned long long wh = __ballot(lane < 16 && v == m);          // != 0: m is one of the v
+      const int pp = sp[__ffsll((long long)wh) - 1];           // lowest wave = lowest slot = lowest rank
+      const f32x4 pk = boxP[pp];
+      const float pa = (pk.z - pk.x) * (pk.w - pk.y);
+      if (tid == pp) { emitL[tid] = t; outS[tid] = m; cur = -1.f; }
+      else if (cur >= 0.f) cur = nms_decay(n, a.nms_thresh, pk, pa, me, cur);
+    }
+    if (tid == 0) gcnt[0] = (unsigned)t;
+  } else {
+    for (int gi = wave; gi < G; gi += DETW_THREADS / 64) {
+      const int s0 = gstart[gi], len = glen[gi];
+      int t = 0;
+      if (len <= 64) {
+        const bool in = lane < len;
+        const f32x4 me = boxP[in ? s0 + lane : 0];
+        float cur = in ? curL[s0 + lane] : -1.f;
+        for (; t < len; ++t) {
+          const float m = nms_wave_max(cur);
+          if (!(m > thr)) break;
+          const int pl = __ffsll((long long)__ballot(cur == m)) - 1;        // (m > thr >= ... is one of the cur: the ballot is not empty)
+          const f32x4 pk = boxP[s0 + pl];
+          const float pa = (pk.z - pk.x) * (pk.w - pk.y);
+          if (lane == pl) { emitL[s0 + lane] = t; outS[s0 + lane] = m; cur = -1.f; }
+          else if (cur >= 0.f) cur = nms_decay(n, a.nms_thresh, pk, pa, me, cur);
+        }
+      } else {
+        // the group strides over the lanes: slot s0 + lane + 64 i belongs to this lane alone, so curL needs no ordering between lanes
+        float lm = -1.f; int lp = 0x7fffffff;
+        for (int p = s0 + lane; p < s0 + len; p += 64) { const float c = curL[p]; if (c > lm) { lm = c; lp = p; } }
+        for (; t < len; ++t) {
+          const float m = nms_wave_max(lm);
+          if (!(m > thr)) break;
+          const int pp = nms_wave_min(lm == m ? lp : 0x7fffffff);           // lowest slot among the ties
+          const f32x4 pk = boxP[pp];
+          const float pa = (pk.z - pk.x) * (pk.w - pk.y);
+          lm = -1.f; lp = 0x7fffffff;
+          for (int p = s0 + lane; p < s0 + len; p += 64) {
+            float c = curL[p];
+            if (p == pp) { emitL[p] = t; outS[p] = m; c = -1.f; curL[p] = c; }
+            else if (c >= 0.f) { c = nms_decay(n, a.nms_thresh, pk, pa, boxP[p], c); curL[p] = c; }
+            if (c > lm) { lm = c; lp = p; }
+          }
+        }
+      }
+      if (lane == 0) gcnt[gi] = (unsigned)t;
+    }
+  }
+  __syncthreads();
+
+  // 7. placement: rows of the earlier groups + pick order
+  {
+    unsigned total;
+    const unsigned off = detw_excl_scan((tid < G) ? gcnt[tid & 255] : 0u, total, wave_tot, lane, wave);
+    if (tid < 256) goff[tid] = off;
+    if (tid == 0) a.det_count[b] = (int)total;
+  }
+  __syncthreads();
+  if (g >= 0) {
+    const int t = emitL[slot];
+    if (t >= 0) DETW_STORE_ROW(a, b, K, goff[g] + (unsigned)t, cls, outS[slot], idx, bx);
+  }
+}
+
+static int launch_detect_nms(DetArgs a, NmsArgs n, int ws_words, hipStream_t stream) {
+  SQD_CHECK_ARG(a.B > 0 && a.A > 0 && a.C >= 1 && a.K >= 1);
+  SQD_CHECK_ARG(n.mode == NMS_HARD || n.mode == NMS_LINEAR || n.mode == NMS_GAUSSIAN);
+  SQD_CHECK_ARG(n.mode != NMS_GAUSSIAN || (isfinite(n.sigma) && n.sigma > 0.f));
+  SQD_CHECK_ARG(a.score_thresh >= 0.f);                       // (the keys: see ops._check_score_thresh; the scan's -1 marks rely on it too)
+  if (a.K > DETW_MAX_K || a.A > DETW_MAX_A || a.C > SQD_MANY_MAX_CLASSES) return SQD_ERR_UNSUPPORTED;
+  const int words = sqd_detect_wide_workspace_words(a.B, a.A, a.K);
+  if (words < 0) return SQD_ERR_UNSUPPORTED;                  // (B x ceil4(A) past 2^31 - 1 words)
+  SQD_CHECK_ARG(a.keys && ws_words >= words && ((uintptr_t)a.keys & 15) == 0);
+  const bool many = a.C > SQD_MAX_CLASSES;
+  SQD_CHECK_ARG(!a.keys_ready || (a.pred && !many));          // ConvDet's epilogue writes the <= 16-class keys of a pred
+  const int Kp = (a.K + 63) & ~63, A4 = (a.A + 3) & ~3;
+  const size_t lds = (size_t)Kp * (8 + 16 + 16 + 4 * 5) + NMS_LDS_FIXED;           // <= 67 KB at K = 1024
+  static SqdDevOnce once_few, once_many;
+  if (lds > 48 * 1024 && (many ? sqd_max_lds_once(once_many, (const void*)detect_nms_select_kernel<true>, 96 * 1024)
+                               : sqd_max_lds_once(once_few, (const void*)detect_nms_select_kernel<false>, 96 * 1024)) != SQD_OK)
+    return SQD_ERR_LAUNCH;
+  if (!a.keys_ready) {
+    if (many) {
+      const int slabs = (A4 + MC_THREADS - 1) / MC_THREADS;
+#define CALL(R) hipLaunchKernelGGL(detect_many_score_kernel<R>, dim3((unsigned)(a.B * slabs)), dim3(MC_THREADS), 0, stream, a)
+      MC_DISPATCH(a.C, CALL);
+#undef CALL
+    } else {
+      const int slabs = (A4 + DETW_SCORE_THREADS - 1) / DETW_SCORE_THREADS;
+      hipLaunchKernelGGL(detect_wide_score_kernel, dim3((unsigned)(a.B * slabs)), dim3(DETW_SCORE_THREADS), 0, stream, a);
+    }
+  }
+  if (many) hipLaunchKernelGGL(detect_nms_select_kernel<true>, dim3((unsigned)a.B), dim3(DETW_THREADS), lds, stream, a, n);
+  else hipLaunchKernelGGL(detect_nms_select_kernel<false>, dim3((unsigned)a.B), dim3(DETW_THREADS), lds, stream, a, n);
+  return sqd_launch_status();
+}
+
+// sqd_detect_wide_fwd / sqd_detect_many_fwd (either head form: 1 <= num_classes <= 256) with the suppression rule as an argument:
+// nms_mode 0 hard, 1 linear, 2 gaussian (nms_sigma finite and > 0, read in that mode only); nms_agnostic != 0: one group for all
+// classes.  keys_ready != 0 (num_classes <= 16): keys_ws already holds the keys of this pred ([B][ceil4(A)], written by
+// sqd_conv_wino_vs_keys_fwd with the same score_thresh earlier on the same stream; the pad words may hold anything) -- no scoring
+// launch.  (hard, class-wise) gives sqd_detect_wide_fwd's rows bit for bit.  Status 1 for anything malformed, an unknown mode, a bad
+// sigma or a negative score_thresh included; 2 past the limits; nothing is launched then.
+extern "C" int sqd_detect_nms_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                                  int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                  int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                                  int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, void* stream) {
+  SQD_CHECK_ARG(pred && anchors && keys_ws && det_count && det_class && det_score && det_box && det_anchor);
+  SQD_CHECK_ARG(((uintptr_t)det_box & 15) == 0 && (num_classes > SQD_MAX_CLASSES || ((uintptr_t)pred & 15) == 0));
+  DetArgs a;
+  a.shifts = shifts;
+  a.pred = pred; a.anchors = anchors; a.scales = scales; a.in_class = nullptr; a.in_score = nullptr; a.in_box = nullptr; a.keys = keys_ws;
+  a.keys_ready = keys_ready ? 1 : 0;
+  a.S = 1; a.per = 0;
+  a.det_count = det_count; a.det_class = det_class; a.det_score = det_score; a.det_box = det_box; a.det_anchor = det_anchor;
+  a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
+  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
+  a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
+  const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
+  return launch_detect_nms(a, n, ws_words, (hipStream_t)stream);
+}
+
+// sqd_filter_wide_fwd / sqd_filter_many_fwd with the same four arguments (keys_ready must be 0: dense scores have no ConvDet keys)
+extern "C" int sqd_filter_nms_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
+                                  long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                  int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words,
+                                  int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, void* stream) {
+  SQD_CHECK_ARG(class_ids && scores && boxes && keys_ws && det_count && det_class && det_score && det_box && det_anchor);
+  SQD_CHECK_ARG(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)det_box & 15) == 0 && !keys_ready);
+  DetArgs a;
+  a.shifts = nullptr;
+  a.pred = nullptr; a.anchors = nullptr; a.scales = nullptr; a.in_class = class_ids; a.in_score = scores; a.in_box = boxes; a.keys = keys_ws;
+  a.S = 1; a.per = 0;
+  a.det_count = det_count; a.det_class = det_class; a.det_score = det_score; a.det_box = det_box; a.det_anchor = det_anchor;
+  a.B = B; a.A = A; a.C = num_classes; a.K = keep_top_k;
+  a.wmax = 0.f; a.hmax = 0.f; a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
+  const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
+  return launch_detect_nms(a, n, ws_words, (hipStream_t)stream);
 }

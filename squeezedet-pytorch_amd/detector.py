@@ -20,6 +20,7 @@ import torch.utils.data
 
 from . import ops
 from .boxes import boxes_postprocess
+from .config import check_nms
 
 
 class Detector(object):
@@ -33,12 +34,15 @@ class Detector(object):
     def detect_device(self, image, scales=None, out=None, shifts=None):
         """image [B,3,H,W] on the GPU -> (count [B] i32, class_ids [B,K] i64, scores [B,K], boxes [B,K,4],
         anchor_idx [B,K] i32), all on the GPU; rows >= count[b] are padding.  ``scales`` / ``shifts`` [B,2]: ``boxes_postprocess``'
-        scale division and padding / crops terms, folded into the detect kernel."""
+        scale division and padding / crops terms, folded into the detect kernel.  The suppression rule is ``cfg``'s (``nms_mode``,
+        ``nms_sigma``, ``nms_agnostic``: hard class-wise by default; under a Soft-NMS rule ``scores`` are the decayed ones)."""
         cfg = self.cfg
         base = self.model.base
         B, A, K = int(image.shape[0]), int(cfg.num_anchors), int(cfg.keep_top_k)
-        fused = ops.detect_fn(cfg.num_classes, K, A)
-        if not (getattr(base, 'fuse_detect_keys', False) and fused is ops.detect and int(cfg.num_classes) == 3
+        mode, sigma, agnostic = check_nms(cfg, 'Detector')
+        plain = mode == 'hard' and not agnostic                  # the reference's rule: the launches of every earlier version
+        fused = ops.detect_fn(cfg.num_classes, K, A, mode, agnostic, sigma)
+        if not (getattr(base, 'fuse_detect_keys', False) and (fused is ops.detect or not plain) and int(cfg.num_classes) == 3
                 and float(cfg.score_thresh) >= 0.0 and isinstance(image, torch.Tensor) and image.is_cuda):
             pred = base(image)
             anchors = self.model.resolver.anchors_on(pred.device)
@@ -56,8 +60,9 @@ class Detector(object):
         keys = ops.DetKeys(bufs[5], cfg.score_thresh, cfg.anchors_per_grid, cfg.num_classes)
         pred = backbone_apply(base, image, det_keys=keys)
         anchors = self.model.resolver.anchors_on(pred.device)
-        return ops.detect(pred, anchors, cfg.input_size, cfg.num_classes, K, cfg.nms_thresh, cfg.score_thresh, scales=scales,
-                          out=bufs, shifts=shifts, keys_ready=keys.written)
+        # (either launch takes the keys: ops.detect for the plain rule, ops.detect_nms with the rule bound for the others)
+        return fused(pred, anchors, cfg.input_size, cfg.num_classes, K, cfg.nms_thresh, cfg.score_thresh, scales=scales,
+                     out=bufs, shifts=shifts, keys_ready=keys.written)
 
     @torch.no_grad()
     def detect(self, batch):
@@ -249,7 +254,8 @@ class Detector(object):
         """One image's dense ``{'class_ids' [A], 'scores' [A], 'boxes' [A,4]}`` (GPU tensors) ->
         filtered dict of GPU tensors (plus ``anchor_idx``) or ``None``."""
         cfg = self.cfg
-        dense = ops.filter_fn(cfg.num_classes, cfg.keep_top_k, det['scores'].shape[0])
+        mode, sigma, agnostic = check_nms(cfg, 'Detector.filter')
+        dense = ops.filter_fn(cfg.num_classes, cfg.keep_top_k, det['scores'].shape[0], mode, agnostic, sigma)
         cnt, cls, sc, bx, idx = dense(det['class_ids'][None], det['scores'][None], det['boxes'][None],
                                       cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh, cfg.score_thresh)
         n = int(cnt[0].item())

@@ -4,7 +4,8 @@ this module scores everything else:
 
 * ``DetectionAP`` accumulates straight from ``Detector.detect_device``'s packed output and the ground truth that training already
   uploads (``annotations.pack_annotations`` / ``ops.SparseGT``): one match launch per batch, no host synchronisation, no copy;
-  ``compute()`` orders the pool (torch stable sorts), runs the AP launch and copies the result out once.
+  ``compute()`` orders the pool (torch stable sorts), runs the AP launch and copies the result out once.  Under a Soft-NMS rule
+  (``cfg.nms_mode`` 'linear' / 'gaussian') ``detect_device``'s scores are the decayed ones: those are what the pool is ranked by.
 * ``evaluate_results`` takes the host-side result dicts of ``Detector.detect_images`` / ``detect_dataset`` instead.
 """
 from __future__ import annotations

@@ -12,6 +12,8 @@ writing ``ops.choose_cfg`` / ``ops.ConvPlan`` / ``ops.KernelTimer``.
 from __future__ import annotations
 
 import ctypes
+import functools
+import math
 import threading
 from typing import NamedTuple
 
@@ -987,17 +989,116 @@ def filter_dense_many(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_
     return _filter_dense_wide('sqd_filter_many_fwd', class_ids, scores, boxes, num_classes, keep_top_k, nms_thresh, score_thresh)
 
 
-def detect_fn(num_classes, keep_top_k, A):
+NMS_MODES = ('hard', 'linear', 'gaussian')               # cfg.nms_mode; the index is the C ABI's nms_mode
+
+
+def nms_mode_index(name, nms_mode, nms_sigma=0.5, nms_agnostic=False):
+    """(C ABI mode, sigma, agnostic as int) of a suppression rule; ValueError for an unknown mode, a sigma that is not a finite number
+    > 0 (checked in every mode, read by 'gaussian' only) or an agnostic flag that is not a bool."""
+    if not isinstance(nms_mode, str) or nms_mode not in NMS_MODES:
+        raise ValueError(f'{name}: nms_mode must be one of {NMS_MODES}, got {nms_mode!r}')
+    try:
+        sigma = float(nms_sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name}: nms_sigma must be a finite number > 0, got {nms_sigma!r}') from None
+    if isinstance(nms_sigma, bool) or not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError(f'{name}: nms_sigma must be a finite number > 0, got {nms_sigma!r}')
+    if not isinstance(nms_agnostic, bool) and type(nms_agnostic).__name__ != 'bool_':
+        raise ValueError(f'{name}: nms_agnostic must be a bool, got {nms_agnostic!r}')
+    return NMS_MODES.index(nms_mode), sigma, int(bool(nms_agnostic))
+
+
+def detect_nms(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None,
+               nms_mode='hard', nms_sigma=0.5, nms_agnostic=False, keys_ready=False):
+    """``detect_wide`` / ``detect_many`` (any 1 <= ``keep_top_k`` <= 1024, up to 2^20 anchors, 1 <= ``num_classes`` <= 256) with the
+    suppression rule as an argument: ``nms_mode`` 'hard' | 'linear' | 'gaussian' (Soft-NMS: an overlapped box keeps a decayed score
+    -- times 1 - IoU where IoU > ``nms_thresh``, or times exp(-IoU^2 / ``nms_sigma``) -- instead of being deleted), ``nms_agnostic``:
+    one suppression group for all classes.  Rows come out in class order (agnostic: one group), each group in pick order, ``scores``
+    holding the decayed score; rows whose score fell to ``score_thresh`` or below are gone.  ('hard', False) equals ``detect_wide`` /
+    ``detect_many`` bit for bit.  ``keys_ready`` (<= 16 classes): the workspace in ``out`` already holds the keys of this ``pred`` for
+    this ``score_thresh`` (``DetKeys``) -- no scoring launch."""
+    mode, sigma, agnostic = nms_mode_index('detect_nms', nms_mode, nms_sigma, nms_agnostic)
+    if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
+        raise ValueError(f'detect_nms: bad pred {tuple(pred.shape)}')
+    head_path(num_classes)
+    _check_score_thresh('detect_nms', score_thresh)
+    pred = pred.contiguous()
+    B, A, _ = pred.shape
+    K = int(keep_top_k)
+    detect_path(K, A)                                      # ValueError naming the limit, before anything is allocated or written
+    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
+        raise ValueError('detect_nms: anchors must be fp32 [A,4] on the same device')
+    if scales is not None and (tuple(scales.shape) != (B, 2) or scales.dtype != torch.float32 or scales.device != pred.device):
+        raise ValueError('detect_nms: scales must be fp32 [B,2] (sy, sx)')
+    if shifts is not None and (tuple(shifts.shape) != (B, 2) or shifts.dtype != torch.float32 or shifts.device != pred.device or not shifts.is_contiguous()):
+        raise ValueError('detect_nms: shifts must be contiguous fp32 [B,2] (dy, dx)')
+    if out is not None:
+        _check_det_out(out, B, K, pred.device)
+    bufs = tuple(out) if out is not None else _det_buffers(B, K, pred.device)
+    keys = _wide_workspace('detect_nms', bufs, B, A, K, pred.device)
+    if keys_ready and (len(bufs) != 6 or keys is not bufs[5] or head_path(num_classes) != 'narrow'):
+        raise ValueError('detect_nms: keys_ready needs the 16-byte aligned workspace the keys were written to (<= 16 classes)')
+    cnt, cls, sc, bx, idx = bufs[:5]
+    br = _Bracket('detect', f'detect_nms A{A} K{K}', 0.0, 4.0 * B * A * (num_classes + 5)) if timing._timer is not None else None
+    rc = nat.lib().sqd_detect_nms_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
+                                      nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                      int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
+                                      keys.numel(), mode, sigma, agnostic, int(bool(keys_ready)), nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_detect_nms_fwd')
+    if br is not None:
+        br.done()
+    return bufs[:5]
+
+
+def filter_dense_nms(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, out=None,
+                     nms_mode='hard', nms_sigma=0.5, nms_agnostic=False):
+    """``filter_dense_wide`` / ``filter_dense_many`` with the suppression rule of ``detect_nms``.  ``out``: the five result tensors
+    (checked against B and ``keep_top_k``) and optionally a workspace of ``det_workspace_words_wide`` int32."""
+    mode, sigma, agnostic = nms_mode_index('filter_nms', nms_mode, nms_sigma, nms_agnostic)
+    if scores.dim() != 2 or class_ids.shape != scores.shape or tuple(boxes.shape) != tuple(scores.shape) + (4,):
+        raise ValueError('filter_nms: shape mismatch')
+    if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda \
+            or class_ids.device != scores.device or boxes.device != scores.device:
+        raise ValueError('filter_nms: dtype/device mismatch')
+    head_path(num_classes)
+    _check_score_thresh('filter_nms', score_thresh)
+    B, A = scores.shape
+    K = int(keep_top_k)
+    detect_path(K, A)
+    if out is not None:
+        _check_det_out(out, B, K, scores.device)
+    bufs = tuple(out) if out is not None else _det_buffers(B, K, scores.device)
+    keys = _wide_workspace('filter_nms', bufs, B, A, K, scores.device)
+    cnt, cls, sc, bx, idx = bufs[:5]
+    rc = nat.lib().sqd_filter_nms_fwd(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
+                                      nat.ptr(keys), nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                      K, float(nms_thresh), float(score_thresh), keys.numel(), mode, sigma, agnostic, 0,
+                                      nat.stream_handle(scores.device))
+    nat.check(rc, 'sqd_filter_nms_fwd')
+    return bufs[:5]
+
+
+def detect_fn(num_classes, keep_top_k, A, nms_mode='hard', nms_agnostic=False, nms_sigma=0.5):
     """The fused detect that serves (num_classes, keep_top_k, A): ``detect`` / ``detect_wide`` up to 16 classes (``detect_path``),
-    ``detect_many`` past them."""
+    ``detect_many`` past them.  Any rule but ('hard', class-wise): ``detect_nms`` with the rule bound, for every K, A and class count."""
+    nms_mode_index('detect_fn', nms_mode, nms_sigma, nms_agnostic)
+    if nms_mode != 'hard' or nms_agnostic:
+        head_path(num_classes)
+        detect_path(keep_top_k, A)
+        return functools.partial(detect_nms, nms_mode=nms_mode, nms_sigma=float(nms_sigma), nms_agnostic=bool(nms_agnostic))
     if head_path(num_classes) == 'many':
         detect_path(keep_top_k, A)
         return detect_many
     return detect if detect_path(keep_top_k, A) == 'narrow' else detect_wide
 
 
-def filter_fn(num_classes, keep_top_k, A):
-    """The dense filter that serves (num_classes, keep_top_k, A), as ``detect_fn``."""
+def filter_fn(num_classes, keep_top_k, A, nms_mode='hard', nms_agnostic=False, nms_sigma=0.5):
+    """The dense filter that serves (num_classes, keep_top_k, A) and the rule, as ``detect_fn``."""
+    nms_mode_index('filter_fn', nms_mode, nms_sigma, nms_agnostic)
+    if nms_mode != 'hard' or nms_agnostic:
+        head_path(num_classes)
+        detect_path(keep_top_k, A)
+        return functools.partial(filter_dense_nms, nms_mode=nms_mode, nms_sigma=float(nms_sigma), nms_agnostic=bool(nms_agnostic))
     if head_path(num_classes) == 'many':
         detect_path(keep_top_k, A)
         return filter_dense_many
