@@ -348,6 +348,24 @@ int sqd_preprocess_u8_letterbox_aug_color_fwd(const unsigned char* src, const lo
                                               const int* win, const float* color, const unsigned long long* sums, float* out, float* scales,
                                               float* shifts, const float* mean3, const float* std3, int B, int H, int W, void* stream);
 
+/* Mosaic (no reference counterpart; DESIGN.md 6b, "Mosaic"; training only, so there is no eval form): an output image is composed of
+ * up to four tiles, each a rectangle of the canvas showing part of one SOURCE image's letterbox window.  Arguments as the letterbox
+ * _aug_ / _aug_color_ entries with these changes: offsets, sizes, aug and sums have one row per source image, S rows (1 <= S <= 4 B);
+ * tiles: DEVICE int32 [B][4][9] = (src, top, left, h1, w1, y0, x0, y1, x1) per output image and tile -- src the source's row, (top, left,
+ * h1, w1) a letterbox window that may extend past the canvas on any side, [y0, y1) x [x0, x1) the tile's rectangle inside canvas and
+ * window; src < 0 ends an image's list.  A pixel of a rectangle is the letterbox rule's value for that window (destination size (h1, w1),
+ * evaluated at (y - top, x - left) on the drifted, flipped, whitened source), a pixel of no rectangle is exactly +0.0f, and where
+ * rectangles overlap the first tile of the list owns the pixel.  Clamped, whatever the buffer holds: src to S - 1, h1 / w1 to 1..65535,
+ * top / left to -65535..65535, the rectangle into canvas and window (an empty one contributes nothing).  color stays [B][3], one row per
+ * OUTPUT image; the contrast pivot is the mean luma of each tile's own source (sums[src]).  No scales / shifts: the tile list is the
+ * record.  B, H and W each in 1..65535.  An image whose one tile has rectangle == window inside the canvas has the bits of
+ * sqd_preprocess_u8_letterbox_aug_fwd / _aug_color_fwd for that window. */
+int sqd_preprocess_u8_mosaic_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug, const int* tiles,
+                                     float* out, const float* mean3, const float* std3, int B, int S, int H, int W, void* stream);
+int sqd_preprocess_u8_mosaic_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                           const int* tiles, const float* color, const unsigned long long* sums, float* out,
+                                           const float* mean3, const float* std3, int B, int S, int H, int W, void* stream);
+
 /* Dataset statistics (src/utils/compute_dataset_mean_and_std.py:35-41 computes torch.mean / torch.std per image in float32; here
  * the exact integer sums they follow from): for a packed batch of uint8 HWC RGB images -- src, offsets [B] (bytes from src, no
  * alignment required), sizes [B][2] = (H, W), exactly as sqd_preprocess_u8_fwd takes them -- sums [B][3][2] uint64 = per image and

@@ -76,6 +76,8 @@ _SIGNATURES = {
     'sqd_preprocess_u8_letterbox_fwd': [c_p] * 7 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],
     'sqd_preprocess_u8_letterbox_aug_fwd': [c_p] * 8 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],
     'sqd_preprocess_u8_letterbox_aug_color_fwd': [c_p] * 10 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],
+    'sqd_preprocess_u8_mosaic_aug_fwd': [c_p] * 6 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_i, c_p],
+    'sqd_preprocess_u8_mosaic_aug_color_fwd': [c_p] * 8 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_i, c_p],
     'sqd_image_stats_u8': [c_p] * 4 + [c_i, c_p],
     'sqd_pool_squeeze_fwd': [c_p] * 4 + [c_i] * 10 + [c_p],
     'sqd_fire_expand_fwd': [c_p] * 4 + [c_i] * 11 + [c_p],

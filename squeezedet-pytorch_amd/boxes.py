@@ -164,14 +164,18 @@ def letterbox_window(size, canvas):
     return (H - h1) // 2, (W - w1) // 2, h1, w1
 
 
-def letterbox_meta(size, window, canvas):
+def letterbox_meta(size, window, canvas, overhang=False):
     """The ``image_meta`` entries of an image of ``size`` = (Hd, Wd) letterboxed into ``window`` = (top, left, h1, w1) of ``canvas``:
     ``scales`` float32 [2] = (h1 / Hd, w1 / Wd) (float64 division, then cast), ``padding`` float32 [4] = (top / sy, bottom / sy, left / sx,
     right / sx) -- the padding in original-image pixels, float32 divisions --, ``letterbox`` int32 [4] = the window.  With them
-    ``boxes_postprocess`` (divide by ``scales``, then subtract ``padding``) undoes the transform unchanged."""
+    ``boxes_postprocess`` (divide by ``scales``, then subtract ``padding``) undoes the transform unchanged.  ``overhang``: a mosaic tile's
+    window, which may extend past the canvas (the padding on that side is then negative)."""
     top, left, h1, w1 = (int(v) for v in window)
     H, W = int(canvas[0]), int(canvas[1])
-    if not (1 <= h1 <= H and 1 <= w1 <= W and 0 <= top <= H - h1 and 0 <= left <= W - w1):
+    if overhang:
+        if h1 < 1 or w1 < 1:
+            raise ValueError(f'letterbox_meta: empty window {(top, left, h1, w1)}')
+    elif not (1 <= h1 <= H and 1 <= w1 <= W and 0 <= top <= H - h1 and 0 <= left <= W - w1):
         raise ValueError(f'letterbox_meta: window {(top, left, h1, w1)} outside the canvas {(H, W)}')
     scales = np.array([h1 / int(size[0]), w1 / int(size[1])], dtype=np.float32)
     pads = np.array([top, H - h1 - top, left, W - w1 - left], dtype=np.float32)

@@ -31,6 +31,38 @@ def check_geometry(cfg, who):
     if zoom > 0 and not letterbox:
         raise ValueError(f'{who}: zoom_out shrinks the letterbox window, it needs letterbox=True')
     return letterbox, zoom
+
+
+def check_mosaic(cfg, who):
+    """The mosaic augmentation of ``cfg`` (DESIGN.md 6b "Mosaic"): (mosaic_prob, (lo, hi), mosaic_min_visible).  ``mosaic_prob`` is finite and
+    in [0, 1]; ``mosaic_scale`` = (lo, hi) with 0 < lo <= hi <= 2; ``mosaic_min_visible`` in [0, 1].  ``mosaic_prob > 0`` needs ``letterbox=True``
+    (which excludes ``forbid_resize``).  A cfg without the fields means off: (0.0, (0.5, 1.0), 0.25)."""
+    def number(name, default):
+        v = getattr(cfg, name, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(v):
+            raise ValueError(f'{who}: {name} must be a finite number, got {v!r}')
+        return float(v)
+    prob = number('mosaic_prob', 0.)
+    if not 0. <= prob <= 1.:
+        raise ValueError(f'{who}: mosaic_prob must be in [0, 1], got {prob!r}')
+    scale = getattr(cfg, 'mosaic_scale', (0.5, 1.0))
+    try:
+        lo, hi = (float(v) for v in scale)
+    except (TypeError, ValueError):
+        raise ValueError(f'{who}: mosaic_scale must be a (lo, hi) pair, got {scale!r}') from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0. < lo <= hi <= 2.):
+        raise ValueError(f'{who}: mosaic_scale must satisfy 0 < lo <= hi <= 2, got {scale!r}')
+    vis = number('mosaic_min_visible', 0.25)
+    if not 0. <= vis <= 1.:
+        raise ValueError(f'{who}: mosaic_min_visible must be in [0, 1], got {vis!r}')
+    if prob > 0:
+        if bool(getattr(cfg, 'forbid_resize', False)):
+            raise ValueError(f'{who}: mosaic composes letterbox windows, it excludes forbid_resize')
+        if not bool(getattr(cfg, 'letterbox', False)):
+            raise ValueError(f'{who}: mosaic composes letterbox windows, it needs letterbox=True')
+    return prob, (lo, hi), vis
+
+
 KITTI_CLASS_NAMES = ('Car', 'Pedestrian', 'Cyclist')
 BBOX_LOSSES = ('l2', 'iou', 'giou', 'diou', 'ciou')      # ops.BOX_LOSSES
 
@@ -92,6 +124,10 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         brightness_jitter=0., contrast_jitter=0., saturation_jitter=0.,      # colour jitter amounts (augment.draw_color); 0 = off
         letterbox=False,             # input geometry: resize with the aspect ratio kept, pad the rest with the whitened mean (excludes forbid_resize)
         zoom_out=0.,                 # training, with letterbox: shrink the window by uniform(1 - zoom_out, 1) and place it at random; 0 = off
+        mosaic_prob=0.,              # training, with letterbox: the share of images composed of four sources around a random centre (DESIGN.md 6b
+                                     # "Mosaic"); mosaic_scale: each source's zoom on its letterbox window, uniform(lo, hi); mosaic_min_visible:
+                                     # a box cut by its tile's rectangle stays a positive while this share of its area is visible
+        mosaic_scale=(0.5, 1.0), mosaic_min_visible=0.25,
         sparse_gt=False,             # training ground truth as the list of positives (ops.SparseGT in batch['gt_sparse']) instead of dense
         ignore_overlap=None,         # None: off.  A float in (0, 1] (0.5 is the documented value; needs sparse_gt): anchors covered to that share
                                      # by a flagged box (DontCare / difficult / crowd) leave the loss (batch['gt_ignore'], ops.loss_masked_*)
@@ -109,6 +145,7 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
     for k, v in overrides.items():
         setattr(cfg, k, v)
     check_geometry(cfg, 'make_cfg')
+    check_mosaic(cfg, 'make_cfg')
     check_bbox_loss(cfg.bbox_loss, 'make_cfg')
     check_nms(cfg, 'make_cfg')
     return cfg

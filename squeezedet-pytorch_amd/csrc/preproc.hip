@@ -15,6 +15,8 @@
 // Three geometries (resize, crop_or_pad, letterbox) x three forms (eval, AUG, AUG + COLOR) = nine kernels and nine entry points, from
 // two device bodies (preprocess_bilinear_body: resize and letterbox; preprocess_padcrop_body) that share the per-image prologue
 // (pre_image), the whitening table (pre_build_table) and the staging (pre_stage), and one host-side check / fill / launch path.
+// Mosaic (training only: AUG, AUG + COLOR) adds two kernels and two entry points from a third body, preprocess_mosaic_body, which
+// composes up to four source images per output image with the same prologue, table, staging and tap arithmetic.
 #include "sqd_common.h"
 
 struct PreArgs {
@@ -71,15 +73,19 @@ struct PreColor {
   bool per_tap;                  // fs != 1: the table holds t(v), not whiten(t(v))
 };
 
-__device__ __forceinline__ PreColor pre_color_of(const float* color, const unsigned long long* sums, int b, int H0, int W0) {
+// the factors at ``c`` = (fb, fc, fs) with the channel sums at ``s`` = [3][2] of an H0 x W0 image (mosaic: an output image's factors, a source's sums)
+__device__ __forceinline__ PreColor pre_color_rows(const float* c, const unsigned long long* s, int H0, int W0) {
   PreColor k;
-  k.fb = color[3 * b]; k.fc = color[3 * b + 1]; k.fs = color[3 * b + 2];
-  const unsigned long long* s = sums + 6ll * b;     // [3][2] = (sum x, sum x*x) per channel
+  k.fb = c[0]; k.fc = c[1]; k.fs = c[2];
   const double g64 = (0.299 * (double)s[0] + 0.587 * (double)s[2] + 0.114 * (double)s[4]) / ((double)H0 * (double)W0);
   const float p = fminf(k.fb * (float)g64, 255.f);
   k.cp = (1.f - k.fc) * p;
   k.per_tap = k.fs != 1.f;
   return k;
+}
+
+__device__ __forceinline__ PreColor pre_color_of(const float* color, const unsigned long long* sums, int b, int H0, int W0) {
+  return pre_color_rows(color + 3 * b, sums + 6ll * b, H0, W0);      // sums: [3][2] = (sum x, sum x*x) per channel
 }
 
 __device__ __forceinline__ float pre_color_t(const PreColor& k, float v) {
@@ -88,15 +94,10 @@ __device__ __forceinline__ float pre_color_t(const PreColor& k, float v) {
 
 // The workgroup's table (256 threads): whiten(v), or COLOR whiten(t(v)), per channel; COLOR with per_tap only t(v).
 template <bool COLOR>
-__device__ __forceinline__ PreColor pre_build_table(float* lut, const float* color, const unsigned long long* sums, int b, int H0, int W0,
-                                                    const float (&mean)[3], const float (&stdv)[3]) {
-  PreColor k = {};
-  if (COLOR) {
-    k = pre_color_of(color, sums, b, H0, W0);
-    if (k.per_tap) {
-      lut[threadIdx.x] = pre_color_t(k, (float)threadIdx.x);
-      return k;
-    }
+__device__ __forceinline__ void pre_fill_table(float* lut, const PreColor& k, const float (&mean)[3], const float (&stdv)[3]) {
+  if (COLOR && k.per_tap) {
+    lut[threadIdx.x] = pre_color_t(k, (float)threadIdx.x);
+    return;
   }
   const float m0 = mean[0], m1 = mean[1], m2 = mean[2], s0 = stdv[0], s1 = stdv[1], s2 = stdv[2];
   for (int i = threadIdx.x; i < 768; i += 256) {
@@ -104,6 +105,14 @@ __device__ __forceinline__ PreColor pre_build_table(float* lut, const float* col
     const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
     lut[i] = ((COLOR ? pre_color_t(k, (float)v) : (float)v) - m) / sd;
   }
+}
+
+template <bool COLOR>
+__device__ __forceinline__ PreColor pre_build_table(float* lut, const float* color, const unsigned long long* sums, int b, int H0, int W0,
+                                                    const float (&mean)[3], const float (&stdv)[3]) {
+  PreColor k = {};
+  if (COLOR) k = pre_color_of(color, sums, b, H0, W0);
+  pre_fill_table<COLOR>(lut, k, mean, stdv);
   return k;
 }
 
@@ -389,7 +398,167 @@ __device__ __forceinline__ void preprocess_padcrop_body(const PadCropArgs& a, co
   }
 }
 
-// The nine kernels: geometry x (eval, AUG, AUG + COLOR).
+// ---------------------------------------------------------------------------------------------------------------------
+// Mosaic (no reference counterpart; DESIGN.md 6b, "Mosaic"; training only): an output image is a list of at most four TILES,
+// tiles[b][t] = (src, top, left, h1, w1, y0, x0, y1, x1).  src indexes the S SOURCE images of the upload (offsets, sizes, aug and
+// sums have one row per source), (top, left, h1, w1) is a letterbox window that may hang over the canvas on any side, and
+// [y0, y1) x [x0, x1) is the tile's rectangle inside canvas and window.  A pixel of the rectangle holds the letterbox rule's
+// value for that window -- the expressions of preprocess_bilinear_body, restated below op for op, so that a one-tile image
+// whose rectangle is its window has the letterbox_aug kernel's bits --, a pixel in no rectangle is +0.0f, and where
+// rectangles overlap the first tile of the list owns the pixel.  src < 0 ends the list.
+// Whatever the buffer holds: src is clamped to S - 1, h1 / w1 to 1..65535, top / left to -65535..65535 and the rectangle into
+// canvas and window; an empty rectangle contributes nothing.  No side outputs: the tile list is the record.
+// A workgroup walks the tiles in order (uniform control flow).  For each tile that meets its 256 x PRE_ROWS block it builds
+// the table (COLOR: of the output image's factors and THAT source's mean luma; rebuilt only when src changes, without COLOR
+// built once), stages the one or two source row segments bounded by its columns inside the rectangle, and stores the pixels
+// of the rectangle no earlier tile owned; a per-thread bit per row records ownership, and what is left at the end is
+// stored as zero.  Every pixel is stored exactly once.  One table and two row buffers, as the bilinear body: a table per tile
+// would cost 3 KB of LDS each for a rebuild that only seam-crossing workgroups of the colour form ever run.
+// ---------------------------------------------------------------------------------------------------------------------
+struct MosaicArgs {
+  const unsigned char* src; const long long* offsets; const int* sizes;
+  const int* tiles;              // [B][4][9]
+  float* out;
+  float mean[3], stdv[3];
+  int B, S, H, W;
+};
+constexpr int PRE_TILES = 4, PRE_TILE_INTS = 9, PRE_WIN_MAX = 65535;
+
+template <bool COLOR>
+__device__ __forceinline__ void preprocess_mosaic_body(const MosaicArgs& a, const int* aug, const float* color, const unsigned long long* sums) {
+  __shared__ float lut[768];
+  __shared__ unsigned rows[2][PRE_ROWB / 4];
+  const int b = blockIdx.z;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const long long plane = (long long)a.H * a.W;
+  const int xa = blockIdx.x * 256, xb = min(a.W, xa + 256) - 1;
+  const int ya = blockIdx.y * PRE_ROWS, yb = min(a.H, ya + PRE_ROWS) - 1;
+  const int xc = min(x, a.W - 1);
+  float* const obase = a.out + (long long)b * 3 * plane + x;
+  unsigned owned = 0;                                // bit r: row ya + r of this thread's column is stored
+  int lut_src = -1;                                  // the source the table was built for (!COLOR: any)
+  bool used = false;                                 // LDS has readers since the last barrier
+  PreColor kc = {};
+  for (int t = 0; t < PRE_TILES; ++t) {              // (everything but the per-thread column is uniform)
+    const int* tl = a.tiles + ((long long)b * PRE_TILES + t) * PRE_TILE_INTS;
+    if (tl[0] < 0) break;
+    const int s = min(tl[0], a.S - 1);
+    const int h1 = max(min(tl[3], PRE_WIN_MAX), 1), w1 = max(min(tl[4], PRE_WIN_MAX), 1);
+    const int top = max(min(tl[1], PRE_WIN_MAX), -PRE_WIN_MAX), left = max(min(tl[2], PRE_WIN_MAX), -PRE_WIN_MAX);
+    const int y0 = max(max(tl[5], 0), top), x0 = max(max(tl[6], 0), left);
+    const int y1 = min(min(tl[7], a.H), top + h1), x1 = min(min(tl[8], a.W), left + w1);
+    // the workgroup's columns and rows inside the rectangle
+    const int ia = max(xa, x0), ib = min(xb, x1 - 1);
+    const int ja = max(ya, y0), jb = min(yb, y1 - 1);
+    if (ia > ib || ja > jb) continue;                // (also: an empty rectangle)
+    const int H0 = a.sizes[2 * s], W0 = a.sizes[2 * s + 1];
+    const PreView im = pre_view<true>(aug, s, H0, W0);
+    const int dy = im.dy, Hd = im.Hd, Wd = im.Wd;
+    const unsigned char* img = a.src + a.offsets[s];
+    const unsigned char* img_end = img + (long long)H0 * W0 * 3;
+    const double sclx = (double)Wd / (double)w1, scly = (double)Hd / (double)h1;
+    auto src_x = [&](int xx, float& f) {
+      f = (float)((xx + 0.5) * sclx - 0.5);
+      int sx = (int)floorf(f); f -= (float)sx;
+      if (sx < 0) { sx = 0; f = 0.f; }
+      if (sx >= Wd - 1) { sx = Wd - 1; f = 0.f; }
+      return sx;
+    };
+    float fdummy;
+    int lo = src_x(ia - left, fdummy), hi = min(src_x(ib - left, fdummy) + 1, Wd - 1);
+    {
+      const int ca = im.col<true>(lo), cb = im.col<true>(hi);
+      lo = max(min(ca, cb), 0); hi = min(max(ca, cb), W0 - 1);
+    }
+    const bool seg = hi >= lo;                       // false: every column of the workgroup in the rectangle lies in the drift fill
+    const int len = (hi - lo + 1) * 3;
+    const bool staged = len + 8 <= PRE_ROWB;
+    const bool xin = xc >= x0 && xc < x1;
+    float fx;
+    const int sx = src_x(min(max(xc - left, 0), w1 - 1), fx);     // (a thread outside the rectangle: some window column, never read)
+    const int sx1 = min(sx + 1, Wd - 1);
+    const int cx0 = im.col<true>(sx), cx1 = im.col<true>(sx1);
+    const bool vx0 = cx0 >= 0, vx1 = cx1 >= 0;
+    const int ux0 = max(cx0, 0), ux1 = max(cx1, 0);
+    const float ax0 = 1.f - fx, ax1 = fx;
+    if (used) __syncthreads();                       // the previous tile's readers are done with the table and the segments
+    used = true;
+    if (COLOR ? s != lut_src : lut_src < 0) {
+      if (COLOR) kc = pre_color_rows(color + 3 * b, sums + 6ll * s, H0, W0);
+      pre_fill_table<COLOR>(lut, kc, a.mean, a.stdv);
+      lut_src = s;
+    }
+    for (int y = ja; y <= jb; ++y) {
+      float fy = (float)((min(max(y - top, 0), h1 - 1) + 0.5) * scly - 0.5);
+      int sy = (int)floorf(fy); fy -= (float)sy;
+      if (sy < 0) { sy = 0; fy = 0.f; }
+      if (sy >= Hd - 1) { sy = Hd - 1; fy = 0.f; }
+      const int sy1 = min(sy + 1, Hd - 1);
+      const int ry0 = sy + dy, ry1 = sy1 + dy;       // image rows (negative = fill)
+      const bool vy0 = ry0 >= 0, vy1 = ry1 >= 0;
+      const int uy0 = max(ry0, 0), uy1 = max(ry1, 0);
+      int sh0 = 0, sh1 = 0;
+      if (y > ja) __syncthreads();                   // the previous row's readers are done with the segments
+      if (staged && seg) {
+        if (vy0) sh0 = pre_stage(rows[0], img, img_end, ((long long)uy0 * W0 + lo) * 3, len);
+        if (vy1) sh1 = pre_stage(rows[1], img, img_end, ((long long)uy1 * W0 + lo) * 3, len);
+      }
+      __syncthreads();
+      const unsigned bit = 1u << (y - ya);
+      if (x >= a.W || !xin || (owned & bit)) continue;            // off the canvas, outside the rectangle, or an earlier tile's pixel
+      owned |= bit;
+      float* o = obase + (long long)y * a.W;
+      const float ay0 = 1.f - fy, ay1 = fy;
+      const unsigned char *p00, *p01, *p10, *p11;
+      if (staged) {
+        const unsigned char* r0 = (const unsigned char*)rows[0] + sh0;
+        const unsigned char* r1 = (const unsigned char*)rows[1] + sh1;
+        const int ox0 = vx0 ? ux0 - lo : 0, ox1 = vx1 ? ux1 - lo : 0;
+        p00 = r0 + ox0 * 3; p01 = r0 + ox1 * 3; p10 = r1 + ox0 * 3; p11 = r1 + ox1 * 3;
+      } else {
+        p00 = img + ((long long)uy0 * W0 + ux0) * 3; p01 = img + ((long long)uy0 * W0 + ux1) * 3;
+        p10 = img + ((long long)uy1 * W0 + ux0) * 3; p11 = img + ((long long)uy1 * W0 + ux1) * 3;
+      }
+      const bool t00 = vy0 && vx0, t01 = vy0 && vx1, t10 = vy1 && vx0, t11 = vy1 && vx1;
+      if (COLOR && kc.per_tap) {                     // (uniform)
+        float v00[3] = {0.f, 0.f, 0.f}, v01[3] = {0.f, 0.f, 0.f}, v10[3] = {0.f, 0.f, 0.f}, v11[3] = {0.f, 0.f, 0.f};     // (fill: 0)
+        if (t00) pre_color_tap(lut, kc, p00, a.mean, a.stdv, v00);
+        if (t01) pre_color_tap(lut, kc, p01, a.mean, a.stdv, v01);
+        if (t10) pre_color_tap(lut, kc, p10, a.mean, a.stdv, v10);
+        if (t11) pre_color_tap(lut, kc, p11, a.mean, a.stdv, v11);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float r0 = v00[c] * ax0 + v01[c] * ax1;
+          const float r1 = v10[c] * ax0 + v11[c] * ax1;
+          o[c * plane] = r0 * ay0 + r1 * ay1;
+        }
+        continue;
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float* l = lut + 256 * c;
+        const float v00 = t00 ? l[p00[c]] : 0.f, v01 = t01 ? l[p01[c]] : 0.f;
+        const float v10 = t10 ? l[p10[c]] : 0.f, v11 = t11 ? l[p11[c]] : 0.f;
+        const float r0 = v00 * ax0 + v01 * ax1;
+        const float r1 = v10 * ax0 + v11 * ax1;
+        o[c * plane] = r0 * ay0 + r1 * ay1;
+      }
+    }
+  }
+  if (x >= a.W) return;
+  for (int y = ya; y <= yb; ++y) {                   // in no rectangle: the whitened mean
+    if (owned & (1u << (y - ya))) continue;
+    float* o = obase + (long long)y * a.W;
+    o[0] = 0.f; o[plane] = 0.f; o[2 * plane] = 0.f;
+  }
+}
+
+// The nine kernels: geometry x (eval, AUG, AUG + COLOR), and the two mosaic ones (training only: AUG, AUG + COLOR).
+__global__ __launch_bounds__(256) void preprocess_mosaic_aug_kernel(MosaicArgs a, const int* aug) { preprocess_mosaic_body<false>(a, aug, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void preprocess_mosaic_aug_color_kernel(MosaicArgs a, const int* aug, const float* color,
+                                                                          const unsigned long long* sums) {
+  preprocess_mosaic_body<true>(a, aug, color, sums);
+}
 __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) { preprocess_bilinear_body<false, false, false>(a, nullptr, nullptr, nullptr); }
 __global__ __launch_bounds__(256) void preprocess_aug_kernel(PreArgs a, const int* aug) { preprocess_bilinear_body<false, true, false>(a, aug, nullptr, nullptr); }
 __global__ __launch_bounds__(256) void preprocess_aug_color_kernel(PreArgs a, const int* aug, const float* color, const unsigned long long* sums) {
@@ -518,4 +687,32 @@ extern "C" int sqd_preprocess_u8_letterbox_aug_color_fwd(const unsigned char* sr
   LetterboxArgs a; a.win = win; a.scales = scales; a.shifts = shifts;
   SQD_CHECK_ARG(pre_blocks(PRE_AUG | PRE_COLOR, aug, color, sums, win) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W));
   return pre_launch(preprocess_letterbox_aug_color_kernel, B, H, W, stream, a, aug, color, sums);
+}
+
+// Mosaic forms (training only).  Arguments as the letterbox _aug_ / _aug_color_ entries with these changes: offsets, sizes, aug and sums
+// have one row per SOURCE image, S rows (1 <= S <= 4 B); tiles: device int32 [B][4][9] = (src, top, left, h1, w1, y0, x0, y1, x1) per
+// output image and tile, src < 0 ends an image's list; color stays [B][3], one row per output image (the contrast pivot is the mean
+// luma of each tile's own source, sums[src]); no scales / shifts outputs.  B, H and W each in 1..65535.
+static inline bool mosaic_args(MosaicArgs& a, const int* tiles, int B, int S, int W) {
+  if (!(tiles && ((uintptr_t)tiles & 3) == 0 && W <= 65535 && S >= 1 && (long long)S <= 4ll * B)) return false;
+  a.tiles = tiles; a.S = S;
+  return true;
+}
+
+extern "C" int sqd_preprocess_u8_mosaic_aug_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                                const int* tiles, float* out, const float* mean3, const float* std3, int B, int S, int H, int W,
+                                                void* stream) {
+  MosaicArgs a;
+  SQD_CHECK_ARG(pre_blocks(PRE_AUG, aug, nullptr, nullptr, nullptr) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W) &&
+                mosaic_args(a, tiles, B, S, W));
+  return pre_launch(preprocess_mosaic_aug_kernel, B, H, W, stream, a, aug);
+}
+
+extern "C" int sqd_preprocess_u8_mosaic_aug_color_fwd(const unsigned char* src, const long long* offsets, const int* sizes, const int* aug,
+                                                      const int* tiles, const float* color, const unsigned long long* sums, float* out,
+                                                      const float* mean3, const float* std3, int B, int S, int H, int W, void* stream) {
+  MosaicArgs a;
+  SQD_CHECK_ARG(pre_blocks(PRE_AUG | PRE_COLOR, aug, color, sums, nullptr) && pre_args(a, src, offsets, sizes, out, mean3, std3, B, H, W) &&
+                mosaic_args(a, tiles, B, S, W));
+  return pre_launch(preprocess_mosaic_aug_color_kernel, B, H, W, stream, a, aug, color, sums);
 }

@@ -21,7 +21,8 @@ KITTI_RGB_MEAN = np.array([93.877, 98.801, 95.923], dtype=np.float32)      # src
 KITTI_RGB_STD = np.array([78.782, 80.130, 81.200], dtype=np.float32)       # src/datasets/kitti.py:18
 
 
-_ENTRY_STEM = {'resize': 'sqd_preprocess_u8', 'padcrop': 'sqd_preprocess_u8_padcrop', 'letterbox': 'sqd_preprocess_u8_letterbox'}
+_ENTRY_STEM = {'resize': 'sqd_preprocess_u8', 'padcrop': 'sqd_preprocess_u8_padcrop', 'letterbox': 'sqd_preprocess_u8_letterbox',
+               'mosaic': 'sqd_preprocess_u8_mosaic'}
 _Float3 = ctypes.c_float * 3
 
 
@@ -31,23 +32,32 @@ def c_float3(values):
 
 
 def entry_name(geometry, aug=False, color=False):
-    """The C entry point of one of the nine input kernels (csrc/preproc.hip): geometry x (eval, aug, aug + colour)."""
+    """The C entry point of one of the input kernels (csrc/preproc.hip): geometry x (eval, aug, aug + colour); 'mosaic' (training
+    only) has the two aug forms."""
     if geometry not in _ENTRY_STEM:
-        raise ValueError(f"launch_u8: geometry must be 'resize', 'padcrop' or 'letterbox', got {geometry!r}")
+        raise ValueError(f"launch_u8: geometry must be 'resize', 'padcrop', 'letterbox' or 'mosaic', got {geometry!r}")
+    if geometry == 'mosaic' and not aug:
+        raise ValueError('launch_u8: mosaic is a training geometry, it has no eval entry (give aug)')
     if color and not aug:
         raise ValueError('launch_u8: the colour forms exist only with aug (there is no eval-time colour entry)')
     return _ENTRY_STEM[geometry] + ('_aug' if aug else '') + ('_color' if color else '') + '_fwd'
 
 
 def launch_u8(geometry, src, offsets, sizes, out, B, H, W, mean, std, device, *, aug=None, color=None, sums=None, win=None,
-              scales=None, shifts=None, padcrop=None, stream=None):
+              scales=None, shifts=None, padcrop=None, tiles=None, S=None, stream=None):
     """The one launch of the uint8 input pipeline: picks the entry point from (``geometry``, ``aug`` given, ``color`` given), puts its
     arguments in the entry's order (include/sqd_hip.h) and checks its status.  Pointer arguments are device tensors, ``ctypes.c_void_p``
     addresses (blocks inside a packed upload) or None; ``mean`` / ``std`` anything ``c_float3`` takes.  Argument blocks per geometry:
     ``aug`` int32 [B,3] (any geometry); ``color`` fp32 [B,3] with ``sums`` [B,3,2] of ``ops.image_stats_u8`` (only with ``aug``); ``win`` int32
     [B,4] (letterbox only); outputs ``scales`` (resize, letterbox), ``shifts`` (padcrop, letterbox), ``padcrop`` int32 [B,8] (padcrop).
+    ``geometry='mosaic'`` (DESIGN.md 6b "Mosaic"): ``tiles`` int32 [B,4,9] and ``S``, the number of source images -- ``offsets``, ``sizes``,
+    ``aug`` and ``sums`` then have S rows, ``color`` stays [B,3]; no side outputs.
     ``stream``: a raw stream handle instead of ``device``'s current stream.  A combination without an entry raises ValueError."""
     name = entry_name(geometry, aug is not None, color is not None)
+    if (tiles is not None or S is not None) != (geometry == 'mosaic') or (geometry == 'mosaic' and (tiles is None or S is None)):
+        raise ValueError('launch_u8: tiles and S belong to the mosaic geometry, which needs both')
+    if geometry == 'mosaic' and (scales is not None or shifts is not None):
+        raise ValueError('launch_u8: mosaic writes no scales or shifts (the tile list is the record)')
     if (color is None) != (sums is None):
         raise ValueError('launch_u8: color and sums go together')
     if win is not None and geometry != 'letterbox':
@@ -62,11 +72,14 @@ def launch_u8(geometry, src, offsets, sizes, out, B, H, W, mean, std, device, *,
         args.append(p(aug))
     if geometry == 'letterbox':
         args.append(p(win))
+    if geometry == 'mosaic':
+        args.append(p(tiles))
     if color is not None:
         args += [p(color), p(sums)]
     args.append(p(out))
-    args += {'resize': [p(scales)], 'padcrop': [p(shifts), p(padcrop)], 'letterbox': [p(scales), p(shifts)]}[geometry]
-    rc = getattr(nat.lib(), name)(*args, c_float3(mean), c_float3(std), B, H, W, nat.stream_handle(device) if stream is None else stream)
+    args += {'resize': [p(scales)], 'padcrop': [p(shifts), p(padcrop)], 'letterbox': [p(scales), p(shifts)], 'mosaic': []}[geometry]
+    dims = (B, int(S), H, W) if geometry == 'mosaic' else (B, H, W)
+    rc = getattr(nat.lib(), name)(*args, c_float3(mean), c_float3(std), *dims, nat.stream_handle(device) if stream is None else stream)
     nat.check(rc, name)
 
 
