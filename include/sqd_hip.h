@@ -528,7 +528,7 @@ int sqd_loss_many_mean_bwd(const float* pred, const float* gt, const float* anch
  * coordinates: dense columns 1..4), deltas [total][4] fp32 (dense columns 5..8), class_ids [total] int32, offsets [B+1] int32
  * (image b owns entries offsets[b] .. offsets[b+1]-1) -- what sqd_encode_gt_fwd takes and returns.  Meaning: the dense gt with
  * mask = 1, box, deltas and a one-hot class at anchor_idx, zeros elsewhere.  Contract: within one image the anchor indices are
- * distinct (the encoder's greedy assignment guarantees it); the order within an image is free; an entry with anchor_idx
+ * distinct (the encoder's greedy assignment guarantees it, and so does sqd_anchor_match_fwd); the order within an image is free; an entry with anchor_idx
  * outside [0, A) (the encoder's "unassigned" value A) is ignored and does not count toward n_obj; a class id outside [0, C)
  * gives a row with no class term (as the dense encoder leaves its one-hot empty); total = 0 (the four list pointers may then
  * be NULL) and images without entries are legal and give the NaNs of n_obj = 0.  A negative row costs one float of pred (its
@@ -564,6 +564,33 @@ int sqd_loss_sparse_mean_bwd(const float* pred, const int* anchor_idx, const flo
  * (0, 1] included), 2 for A > 2^20, B > 65535 or total > 65535 B (at most 65535 ignore boxes per image). */
 int sqd_anchor_ignore_fwd(const float* ign_boxes, const int* ign_offsets, const double* anchors, unsigned* mask,
                           const double* overlap, int total, int B, int A, void* stream);
+
+/* IoU-threshold anchor matching (RPN / SSD / RetinaNet style, YOLOv3's ignore threshold) on top of sqd_encode_gt_fwd's greedy
+ * assignment: extra positives and an ignore band.  Inputs (device): boxes [total][4] fp32 xyxy, class_ids [total], box_offsets [B+1]
+ * as given to the encoder, anchor_idx [total] and deltas [total][4] as the encoder returned them (the PRIMARIES), anchors [A][4]
+ * FLOAT64 (cx,cy,w,h), ignore_in uint32 [B][ceil(A/32)] (sqd_anchor_ignore_fwd's bitmap) or NULL.  thresholds: HOST pointer to two
+ * doubles (pos_iou, ign_iou), read before the launch.  Rule, per image, all overlap arithmetic float64: ov(i, j) is the encoder's
+ * overlap of box i and anchor j (corners c -+ 0.5 (s - 1); the box area (x2 - x1) (y2 - y1) a float32 product, widened afterwards;
+ * inter / (union + 1e-10)).  For every anchor j that is not a primary of the image: m = max_i ov(i, j), i* the LOWEST box index
+ * attaining it; m >= pos_iou: j is an extra positive of box i*; else m >= ign_iou: j is a band anchor; else a negative.  A primary
+ * is never re-assigned (every box keeps its positive); an image without boxes has no extras and no band.  The first max_extra
+ * extras of an image by ascending anchor index are kept, the others are overflow.
+ * Outputs (device), every element written: the list out_anchor_idx / out_class_ids [total + B * max_extra], out_boxes / out_deltas
+ * [total + B * max_extra][4], out_offsets [B+1] with out_offsets[b] = box_offsets[b] + b * max_extra -- the operands of
+ * sqd_loss_sparse_* / sqd_loss_masked_*.  Image b's segment: its primaries in box order (copied; an unassigned one keeps
+ * anchor_idx = A and gets zero deltas, which the encoder leaves unwritten), the kept extras in ascending anchor order (anchor_idx
+ * = j, box and class id of i*, deltas by the encoder's arithmetic: float32 box cx, cy, w, h; float64 divide and log; rounded to
+ * float32), then padding entries (anchor_idx = A, zeros).  Anchor indices within an image stay distinct.  ignore_out uint32
+ * [B][ceil(A/32)]: bit = ignore_in bit | band | overflow (bits at and past A are 0; may be ignore_in itself); overflow int32 [B]:
+ * the overflow anchors per image.  workspace: 4 * B * (A + ceil(A / 256)) bytes of device memory.  Two launches, no
+ * floating-point atomics, no host synchronisation: the same operands give the same bits.  total = 0 is legal (all padding; the
+ * five total-sized inputs may be NULL, and so may the four list outputs if max_extra = 0 too).  Status 1 for anything malformed
+ * (a NULL pointer, !(0 < ign_iou <= pos_iou <= 1), max_extra < 0), 2 for A > 2^20, B > 65535 or total + B * max_extra >= 2^31. */
+int sqd_anchor_match_fwd(const float* boxes, const int* class_ids, const int* box_offsets, const int* anchor_idx,
+                         const float* deltas, const double* anchors, const unsigned* ignore_in, const double* thresholds,
+                         void* workspace, int* out_anchor_idx, float* out_boxes, float* out_deltas, int* out_class_ids,
+                         int* out_offsets, unsigned* ignore_out, int* overflow, int total, int B, int A, int max_extra,
+                         void* stream);
 
 /* The sparse loss launches with an ignore bitmap (sqd_anchor_ignore_fwd's layout): ignore uint32 [B][ceil(A/32)].  Per image:
  * pos = the list's valid entries; ign = the anchors whose bit is set and that are not in pos (a positive wins over its own bit);

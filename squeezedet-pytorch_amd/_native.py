@@ -130,6 +130,7 @@ _SIGNATURES = {
     'sqd_loss_sparse_mean_fwd': [c_p] * 11 + [c_i] * 6 + [c_f] * 4 + [c_p],
     'sqd_loss_sparse_mean_bwd': [c_p] * 10 + [c_i] * 6 + [c_f] * 4 + [c_p],
     'sqd_anchor_ignore_fwd': [c_p] * 4 + [ctypes.POINTER(ctypes.c_double)] + [c_i] * 3 + [c_p],
+    'sqd_anchor_match_fwd': [c_p] * 7 + [ctypes.POINTER(ctypes.c_double)] + [c_p] * 8 + [c_i] * 4 + [c_p],
     'sqd_loss_masked_fwd': [c_p] * 11 + [c_i] * 6 + [c_f] * 4 + [c_p],
     'sqd_loss_masked_bwd': [c_p] * 11 + [c_i] * 6 + [c_f] * 4 + [c_p],
     'sqd_loss_masked_mean_fwd': [c_p] * 12 + [c_i] * 6 + [c_f] * 4 + [c_p],

@@ -106,16 +106,26 @@ def encode_ignore_boxes(ignore_boxes_list, anchors, overlap, device='cuda'):
 
 
 def encode_annotations(class_ids_list, boxes_list, anchors, num_classes, device='cuda', return_sparse=False, dense=True,
-                       ignore_boxes_list=None, ignore_overlap=None):
+                       ignore_boxes_list=None, ignore_overlap=None, match=None, return_overflow=False):
     """Batch version of ``prepare_annotations``: lists (one entry per image) of class ids [n_i] and xyxy boxes
     [n_i,4] in network-input coordinates -> gt fp32 [B, A, num_classes+9] on ``device``.  With ``return_sparse``
     also returns (anchor_idx [total] i32, deltas [total,4] f32, box_offsets [B+1] i32), all on the device.
     ``dense=False``: -> an ``ops.SparseGT`` (the positives as a list, what ``ops.loss_sparse_*`` consume); the dense
     tensor is neither allocated nor written.  An image may have no boxes, and so may the whole batch (then no encoder launch
     runs and the ``SparseGT`` is empty).  ``ignore_boxes_list`` + ``ignore_overlap`` (both, with ``dense=False``): per-image ignore
-    boxes -> (SparseGT, anchor ignore bitmap int32 [B, ceil(A/32)]), the operands of ``ops.loss_masked_*``."""
+    boxes -> (SparseGT, anchor ignore bitmap int32 [B, ceil(A/32)]), the operands of ``ops.loss_masked_*``.  ``match`` = (pos_iou,
+    ign_iou, max_extra) (``config.check_match``; with ``dense=False``): the IoU-threshold matcher runs on the encoder's list
+    (``ops.anchor_match``) -> (SparseGT with the extra positives, bitmap = band | overflow, ORed onto the region bitmap when both are
+    given); ``return_overflow``: also the per-image overflow counts int32 [B] (a device tensor nothing waits on)."""
     if (ignore_boxes_list is None) != (ignore_overlap is None):
         raise ValueError('encode_annotations: ignore_boxes_list and ignore_overlap go together')
+    if match is not None:
+        if dense:
+            raise ValueError('encode_annotations: match needs dense=False (the dense loss has no masked form)')
+        from .boxes import check_match_thresholds
+        match = check_match_thresholds('encode_annotations', *match)
+    elif return_overflow:
+        raise ValueError('encode_annotations: return_overflow goes with match')
     if ignore_boxes_list is not None:
         if dense:
             raise ValueError('encode_annotations: ignore regions need dense=False (the dense loss has no masked form)')
@@ -135,6 +145,10 @@ def encode_annotations(class_ids_list, boxes_list, anchors, num_classes, device=
     if not dense:
         _, idx, deltas = ops.encode_gt(d_boxes, d_cls, d_offs, anchors_f64_on(anchors, dev), num_classes, dense=False)
         sgt = ops.SparseGT(idx, d_boxes, deltas, d_cls, d_offs)
+        if match is not None:
+            regions = None if ignore_boxes_list is None else encode_ignore_boxes(ignore_boxes_list, anchors, ignore_overlap, dev)
+            sgt, ignore, overflow = ops.anchor_match(sgt, anchors_f64_on(anchors, dev), *match, ignore=regions)
+            return (sgt, ignore, overflow) if return_overflow else (sgt, ignore)
         if ignore_boxes_list is not None:
             return sgt, encode_ignore_boxes(ignore_boxes_list, anchors, ignore_overlap, dev)
         return sgt

@@ -207,6 +207,92 @@ def anchor_ignore_mask(anchors, ign_boxes, overlap):
     return hit & (area > 0.0)
 
 
+def check_match_thresholds(name, pos_iou, ign_iou, max_extra):
+    """The matcher's arguments: finite floats with ``0 < ign_iou <= pos_iou <= 1`` (``ign_iou`` None: equal to ``pos_iou``, no band) and
+    an int ``max_extra >= 0``.  -> (pos_iou, ign_iou, max_extra)."""
+    try:
+        pos = float(pos_iou)
+        ign = pos if ign_iou is None else float(ign_iou)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name}: match thresholds must be numbers, got {pos_iou!r}, {ign_iou!r}') from None
+    if not (0.0 < ign <= pos <= 1.0):                   # (NaN fails)
+        raise ValueError(f'{name}: match thresholds must satisfy 0 < ignore <= pos <= 1, got pos {pos_iou!r}, ignore {ign_iou!r}')
+    if isinstance(max_extra, (bool, np.bool_)) or not isinstance(max_extra, (int, np.integer)) or max_extra < 0:
+        raise ValueError(f'{name}: max_extra must be an int >= 0, got {max_extra!r}')
+    return pos, ign, int(max_extra)
+
+
+def anchor_match(anchors, boxes_list, anchor_idx_list, pos_iou, ign_iou, max_extra, ignore=None):
+    """IoU-threshold anchor matching on top of the greedy assignment, the host twin of ``ops.anchor_match`` (DESIGN.md section 3,
+    "IoU-threshold matching").  anchors [A,4] (cx,cy,w,h); per image: boxes float32 [n,4] xyxy (the unflagged ones, input order) and
+    the encoder's ``anchor_idx`` int [n] for them (the primaries; A = unassigned); ``ignore``: bool [B,A] or None.
+
+    Per image, all overlap arithmetic float64: ``ov(i, j)`` is ``compute_deltas``' overlap (the box area a float32 product, widened
+    afterwards; ``inter / (union + 1e-10)``).  For every anchor j that is no primary of the image: ``m = max_i ov(i, j)``, ``i*`` the
+    lowest box index attaining it; ``m >= pos_iou``: an extra positive of box ``i*``; else ``m >= ign_iou``: a band anchor; else a
+    negative.  An image without boxes has neither; a primary is never re-assigned.  The first ``max_extra`` extras by ascending anchor
+    index are kept, the rest are overflow.
+
+    -> (anchor_idx int32 [T], box_idx int64 [T], deltas float32 [T,4], offsets int32 [B+1], ignore bool [B,A], overflow int32 [B]) with
+    T = total + B * max_extra and ``offsets[b] = box_offsets[b] + b * max_extra``.  Image b's segment: its primaries in box order, the
+    kept extras in ascending anchor order, padding (``anchor_idx`` A, ``box_idx`` -1, zero deltas).  ``box_idx`` indexes the concatenated
+    boxes; ``deltas`` are ``compute_deltas``' expression for every entry with an anchor (zero for an unassigned primary); ``ignore`` =
+    the given bits | band | overflow."""
+    pos_iou, ign_iou, max_extra = check_match_thresholds('anchor_match', pos_iou, ign_iou, max_extra)
+    a = np.asarray(anchors, dtype=np.float64).reshape(-1, 4)
+    A, B = a.shape[0], len(boxes_list)
+    if B == 0 or len(anchor_idx_list) != B:
+        raise ValueError('anchor_match: need one box array and one anchor_idx array per image')
+    x0, y0 = a[:, 0] - 0.5 * (a[:, 2] - 1.0), a[:, 1] - 0.5 * (a[:, 3] - 1.0)
+    x1, y1 = a[:, 0] + 0.5 * (a[:, 2] - 1.0), a[:, 1] + 0.5 * (a[:, 3] - 1.0)
+    aarea = (x1 - x0) * (y1 - y0)
+    ign_out = np.zeros((B, A), dtype=bool) if ignore is None else np.array(ignore, dtype=bool).reshape(B, A)
+    overflow = np.zeros(B, np.int32)
+    offsets = np.zeros(B + 1, np.int32)
+    idx_out, box_out, delta_out = [], [], []
+    first = 0
+    for b in range(B):
+        bx = np.asarray(boxes_list[b], dtype=np.float32).reshape(-1, 4)
+        prim = np.asarray(anchor_idx_list[b]).reshape(-1).astype(np.int64)
+        n = bx.shape[0]
+        if prim.shape[0] != n:
+            raise ValueError(f'anchor_match: image {b}: {prim.shape[0]} anchor indices for {n} boxes')
+        barea = ((bx[:, 2] - bx[:, 0]) * (bx[:, 3] - bx[:, 1])).astype(np.float64)      # float32 product, widened afterwards
+        b64 = bx.astype(np.float64)
+        m, best = np.full(A, -1.0), np.full(A, -1, np.int64)
+        for i in range(n):                              # strict >: ties stay with the lowest box index
+            lr = np.maximum(np.minimum(x1, b64[i, 2]) - np.maximum(x0, b64[i, 0]), 0.0)
+            tb = np.maximum(np.minimum(y1, b64[i, 3]) - np.maximum(y0, b64[i, 1]), 0.0)
+            inter = lr * tb
+            ov = inter / ((aarea + barea[i] - inter) + 1e-10)
+            better = ov > m
+            m[better], best[better] = ov[better], i
+        scored = best >= 0
+        scored[prim[(prim >= 0) & (prim < A)]] = False
+        extra = scored & (m >= pos_iou)
+        band = scored & ~extra & (m >= ign_iou)
+        ex = np.nonzero(extra)[0]
+        kept, over = ex[:max_extra], ex[max_extra:]
+        overflow[b] = over.shape[0]
+        ign_out[b] |= band
+        ign_out[b, over] = True
+        seg_idx = np.concatenate([prim, kept, np.full(max_extra - kept.shape[0], A, np.int64)])
+        seg_box = np.concatenate([np.arange(n, dtype=np.int64), best[kept], np.full(max_extra - kept.shape[0], -1, np.int64)])
+        d = np.zeros((seg_idx.shape[0], 4), np.float32)
+        for k in np.nonzero((seg_idx >= 0) & (seg_idx < A) & (seg_box >= 0))[0]:
+            q, an = bx[seg_box[k]], a[seg_idx[k]]
+            bcx, bcy = (q[0] + q[2]) / np.float32(2), (q[1] + q[3]) / np.float32(2)           # float32, as xyxy_to_xywh
+            bw, bh = q[2] - q[0] + np.float32(1), q[3] - q[1] + np.float32(1)
+            d[k] = [(np.float64(bcx) - an[0]) / an[2], (np.float64(bcy) - an[1]) / an[3],
+                    np.log(np.float64(bw) / an[2]), np.log(np.float64(bh) / an[3])]
+        idx_out.append(seg_idx.astype(np.int32))
+        box_out.append(np.where(seg_box >= 0, seg_box + first, -1))
+        delta_out.append(d)
+        first += n
+        offsets[b + 1] = offsets[b] + seg_idx.shape[0]
+    return np.concatenate(idx_out), np.concatenate(box_out), np.concatenate(delta_out, 0), offsets, ign_out, overflow
+
+
 def pack_ignore_bits(mask):
     """bool [..., A] -> int32 [..., ceil(A/32)]: anchor a in bit ``a & 31`` of word ``a >> 5`` (the layout of
     ``ops.anchor_ignore_mask``); the bits at and past A are 0."""

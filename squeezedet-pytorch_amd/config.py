@@ -63,6 +63,38 @@ def check_mosaic(cfg, who):
     return prob, (lo, hi), vis
 
 
+def check_match(cfg, who):
+    """The IoU-threshold matcher of ``cfg`` ("IoU-threshold matching"): None (``match_iou`` None or absent: off),
+    or (match_iou, match_ignore_iou, match_max_extra) -- finite floats with ``0 < ignore <= pos <= 1`` (``match_ignore_iou`` None: equal
+    to ``match_iou``, no band) and an int ``match_max_extra >= 0`` (default 512).  ``match_iou`` needs ``sparse_gt``: only the sparse loss
+    has a masked form.  The other two fields are checked whenever they are there, whether the matcher is on or off."""
+    pos = getattr(cfg, 'match_iou', None)
+    ign = getattr(cfg, 'match_ignore_iou', None)
+    extra = getattr(cfg, 'match_max_extra', 512)
+
+    def number(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(v):
+            raise ValueError(f'{who}: {name} must be a finite number in (0, 1], got {v!r}')
+        return float(v)
+    if isinstance(extra, (bool, np.bool_)) or not isinstance(extra, (int, np.integer)) or extra < 0:
+        raise ValueError(f'{who}: match_max_extra must be an int >= 0, got {extra!r}')
+    if ign is not None and not 0. < number('match_ignore_iou', ign) <= 1.:
+        raise ValueError(f'{who}: match_ignore_iou must be in (0, 1], got {ign!r}')
+    if pos is None:
+        if ign is not None:
+            raise ValueError(f'{who}: match_ignore_iou is the lower edge of match_iou\'s band, it needs match_iou')
+        return None
+    pos = number('match_iou', pos)
+    ign = pos if ign is None else float(ign)
+    if not 0. < ign <= pos <= 1.:
+        raise ValueError(f'{who}: the match thresholds must satisfy 0 < match_ignore_iou <= match_iou <= 1, got match_iou {pos!r}, '
+                         f'match_ignore_iou {ign!r}')
+    if not bool(getattr(cfg, 'sparse_gt', False)):
+        raise ValueError(f'{who}: match_iou needs sparse_gt (the band and the overflow leave the loss through the masked launches, '
+                         'which the dense loss does not have)')
+    return pos, ign, int(extra)
+
+
 KITTI_CLASS_NAMES = ('Car', 'Pedestrian', 'Cyclist')
 BBOX_LOSSES = ('l2', 'iou', 'giou', 'diou', 'ciou')      # ops.BOX_LOSSES
 
@@ -131,6 +163,11 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         sparse_gt=False,             # training ground truth as the list of positives (ops.SparseGT in batch['gt_sparse']) instead of dense
         ignore_overlap=None,         # None: off.  A float in (0, 1] (0.5 is the documented value; needs sparse_gt): anchors covered to that share
                                      # by a flagged box (DontCare / difficult / crowd) leave the loss (batch['gt_ignore'], ops.loss_masked_*)
+        match_iou=None,              # None: off (one anchor per box, the reference).  A float in (0, 1] (needs sparse_gt): anchors that overlap a
+                                     # box by that IoU are positives too (ops.anchor_match); match_ignore_iou: anchors whose best IoU is in
+                                     # [match_ignore_iou, match_iou) leave the loss (None: no band); match_max_extra: extra positives kept per
+                                     # image, the rest leave the loss too (batch['gt_match_overflow'] counts them)
+        match_ignore_iou=None, match_max_extra=512,
         graph_step=False,            # training: replay the step as one captured hipGraph (trainer.GraphedStep; needs a FusedClipSGD or a
                                      # FusedClipAdamW, one process)
         optimizer='sgd',             # 'sgd' | 'adamw': which fused optimizer trainer.make_train_step builds (FusedClipSGD / FusedClipAdamW)
@@ -148,4 +185,5 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
     check_mosaic(cfg, 'make_cfg')
     check_bbox_loss(cfg.bbox_loss, 'make_cfg')
     check_nms(cfg, 'make_cfg')
+    check_match(cfg, 'make_cfg')
     return cfg

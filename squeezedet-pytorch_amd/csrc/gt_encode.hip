@@ -281,3 +281,208 @@ extern "C" int sqd_anchor_ignore_fwd(const float* ign_boxes, const int* ign_offs
                      (hipStream_t)stream, ign_boxes, ign_offsets, anchors, mask, *overlap, total, A);
   return sqd_launch_status();
 }
+
+// ---- IoU-threshold matching: extra positives and an ignore band on top of the greedy assignment -----------------------------------------
+// The encoder above gives every box ONE anchor (its primary).  Here every other anchor j of the image is scored against the image's boxes
+// with the encoder's own overlap expression (float64; the box area a float32 product, widened afterwards; inter / (union + 1e-10)):
+//   m = max_i ov(i, j), i* = the LOWEST box index that attains it;  m >= pos_iou: j is an EXTRA positive of box i*;  else m >= ign_iou: j
+//   is a BAND anchor (left out of the loss);  else a negative.  A primary is never re-assigned; an image without boxes has neither.
+// The first max_extra extras of an image by ascending anchor index are kept, the rest are OVERFLOW and leave the loss with the band.
+// Output list, a fixed total + B * max_extra entries, image b at out_offsets[b] = box_offsets[b] + b * max_extra: its primaries in box
+// order (index, box, deltas, class copied; an unassigned one keeps A and gets zero deltas, which the encoder leaves unwritten), the kept
+// extras in ascending anchor order (deltas by commit's arithmetic above), then padding (index A, zeros).  ignore_out = ignore_in | band |
+// overflow, every word written, bits at and past A zero; overflow [B] = the overflow anchors per image.
+//
+// Two launches after the encoder's (one workgroup per image would leave most CUs idle at B = 20, and the scoring is the A x n part):
+//   anchor_match_score_kernel    grid (ceil(A / 256), B), one thread per anchor: the image's boxes pass through LDS in chunks, the slice's
+//                                primaries are marked in an LDS bitmap from anchor_idx; out: the best box per extra anchor (-1 otherwise),
+//                                the band bits by wave ballot, the extras of the block in a count table.
+//   anchor_match_compact_kernel  one workgroup per image: wave 0 scans the count table, then every wave walks whole 256-anchor blocks
+//                                (skipping those without extras) and ranks its extras by ballot + popcount -- no barrier in the walk, no
+//                                atomics anywhere: each ignore word is touched by one lane, each list entry written by one thread.
+constexpr int AM_THREADS = 256;                        // anchors per scoring block = the granule of the count table
+constexpr int AM_CHUNK = 256;                          // boxes staged per LDS pass
+constexpr int AM_CTHREADS = 1024;
+constexpr int AM_MAX_BLOCKS = (1 << 20) / AM_THREADS;  // A <= 2^20
+
+struct MatchArgs {
+  const float* boxes; const int* class_ids; const int* box_offsets; const int* anchor_idx; const float* deltas;
+  const double* anchors; const unsigned* ignore_in;
+  int* best; int* counts;                              // workspace: [B][A], [B][nblk]
+  int* out_idx; float* out_boxes; float* out_deltas; int* out_cls; int* out_offsets;
+  unsigned* ignore_out; int* overflow;
+  double pos_iou, ign_iou;
+  int total, B, A, max_extra, nblk;
+};
+
+__global__ __launch_bounds__(AM_THREADS) void anchor_match_score_kernel(MatchArgs a) {
+  __shared__ double s_box[AM_CHUNK][5];                // x1, y1, x2, y2 widened, and the float32 area widened
+  __shared__ unsigned s_prim[AM_THREADS / 32];
+  __shared__ int s_cnt[AM_THREADS / 64];
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, base = blockIdx.x * AM_THREADS, j = base + tid;
+  const int beg = max(0, a.box_offsets[b]), end = min(a.total, a.box_offsets[b + 1]);      // (a malformed table reads nothing out of bounds)
+  if (tid < AM_THREADS / 32) s_prim[tid] = 0u;
+  __syncthreads();
+  for (int i = beg + tid; i < end; i += AM_THREADS) {
+    const int p = a.anchor_idx[i] - base;
+    if (p >= 0 && p < AM_THREADS) atomicOr(&s_prim[p >> 5], 1u << (p & 31));               // (integer: order-free)
+  }
+  double x0 = 0.0, y0 = 0.0, x1 = 0.0, y1 = 0.0, aarea = 0.0;
+  if (j < a.A) {
+    const double ax = a.anchors[4 * j], ay = a.anchors[4 * j + 1], aw = a.anchors[4 * j + 2], ah = a.anchors[4 * j + 3];
+    x0 = ax - 0.5 * (aw - 1.0); y0 = ay - 0.5 * (ah - 1.0);
+    x1 = ax + 0.5 * (aw - 1.0); y1 = ay + 0.5 * (ah - 1.0);
+    aarea = (x1 - x0) * (y1 - y0);
+  }
+  double m = -1.0;
+  int bi = -1;
+  for (int c = beg; c < end; c += AM_CHUNK) {           // (block-uniform)
+    const int n = min(AM_CHUNK, end - c);
+    __syncthreads();
+    if (tid < n) {
+      const float* bx = a.boxes + 4 * (long long)(c + tid);
+      const float b0 = bx[0], b1 = bx[1], b2 = bx[2], b3 = bx[3];
+      s_box[tid][0] = (double)b0; s_box[tid][1] = (double)b1; s_box[tid][2] = (double)b2; s_box[tid][3] = (double)b3;
+      s_box[tid][4] = (double)((b2 - b0) * (b3 - b1));
+    }
+    __syncthreads();
+    if (j < a.A) {
+      for (int k = 0; k < n; ++k) {
+        const double lr = fmax(fmin(x1, s_box[k][2]) - fmax(x0, s_box[k][0]), 0.0);
+        const double tb = fmax(fmin(y1, s_box[k][3]) - fmax(y0, s_box[k][1]), 0.0);
+        const double inter = lr * tb;
+        const double uni = aarea + s_box[k][4] - inter;
+        const double ov = inter / (uni + 1e-10);
+        if (ov > m) { m = ov; bi = c + k; }             // strict: ties stay with the lowest box index
+      }
+    }
+  }
+  __syncthreads();                                      // (s_prim complete also for an image whose boxes skipped the loop's barriers)
+  const bool scored = j < a.A && bi >= 0 && !(s_prim[tid >> 5] & (1u << (tid & 31)));
+  const bool extra = scored && m >= a.pos_iou;
+  const bool band = scored && !extra && m >= a.ign_iou;
+  if (j < a.A) a.best[(long long)b * a.A + j] = extra ? bi : -1;
+  const unsigned long long bal = __ballot(band), ebal = __ballot(extra);
+  const int nwords = (a.A + 31) >> 5, w0 = (base + (tid & ~63)) >> 5;
+  const long long row = (long long)b * nwords;
+  if (lane == 0 && w0 < nwords) a.ignore_out[row + w0] = (unsigned)(bal & 0xffffffffull) | (a.ignore_in ? a.ignore_in[row + w0] : 0u);
+  if (lane == 32 && w0 + 1 < nwords) a.ignore_out[row + w0 + 1] = (unsigned)(bal >> 32) | (a.ignore_in ? a.ignore_in[row + w0 + 1] : 0u);
+  if (lane == 0) s_cnt[tid >> 6] = __popcll(ebal);
+  __syncthreads();
+  if (tid == 0) a.counts[(long long)b * a.nblk + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+__global__ __launch_bounds__(AM_CTHREADS) void anchor_match_compact_kernel(MatchArgs a) {
+  __shared__ int s_pref[AM_MAX_BLOCKS + 1];            // exclusive prefix of the image's block counts, [nblk] = the image's extras
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int beg = max(0, a.box_offsets[b]), end = max(beg, min(a.total, a.box_offsets[b + 1]));
+  const int nb = end - beg;
+  const long long out0 = (long long)beg + (long long)b * a.max_extra;     // (beg <= total: a malformed table writes nothing out of bounds)
+  const int* cnt = a.counts + (long long)b * a.nblk;
+  if (wv == 0) {                                        // the scan: a contiguous run of the table per lane, then across the lanes
+    const int per = (a.nblk + 63) / 64, q0 = min(a.nblk, lane * per), q1 = min(a.nblk, q0 + per);
+    int s = 0;
+    for (int q = q0; q < q1; ++q) s += cnt[q];
+    int inc = s;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int v = __shfl_up(inc, off);
+      if (lane >= off) inc += v;
+    }
+    int run = inc - s;
+    for (int q = q0; q < q1; ++q) { s_pref[q] = run; run += cnt[q]; }
+    if (lane == 63) s_pref[a.nblk] = inc;
+  }
+  __syncthreads();
+  const int E = s_pref[a.nblk], kept = min(E, a.max_extra);
+  if (tid == 0) {
+    a.overflow[b] = E - kept;
+    a.out_offsets[b] = (int)out0;
+    if (b == a.B - 1) a.out_offsets[a.B] = a.total + a.B * a.max_extra;
+  }
+  // the primaries, in box order
+  for (int i = tid; i < nb; i += AM_CTHREADS) {
+    const long long src = beg + i, dst = out0 + i;
+    const int idx = a.anchor_idx[src];
+    const bool assigned = idx >= 0 && idx < a.A;
+    a.out_idx[dst] = idx;
+    a.out_cls[dst] = a.class_ids[src];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      a.out_boxes[4 * dst + k] = a.boxes[4 * src + k];
+      a.out_deltas[4 * dst + k] = assigned ? a.deltas[4 * src + k] : 0.f;
+    }
+  }
+  // padding
+  for (int i = kept + tid; i < a.max_extra; i += AM_CTHREADS) {
+    const long long dst = out0 + nb + i;
+    a.out_idx[dst] = a.A; a.out_cls[dst] = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { a.out_boxes[4 * dst + k] = 0.f; a.out_deltas[4 * dst + k] = 0.f; }
+  }
+  if (E == 0) return;                                   // (block-uniform)
+  // the extras: wave wv takes the 256-anchor blocks wv, wv + 16, ...; rank = the block's prefix + the extras before it in the block
+  const int nwords = (a.A + 31) >> 5;
+  unsigned* irow = a.ignore_out + (long long)b * nwords;
+  const int* best = a.best + (long long)b * a.A;
+  for (int q = wv; q < a.nblk; q += AM_CTHREADS / 64) {
+    int run = s_pref[q];
+    if (s_pref[q + 1] == run) continue;                 // (wave-uniform)
+    for (int s = 0; s < AM_THREADS / 64; ++s) {
+      const int j = q * AM_THREADS + s * 64 + lane;
+      const int bi = j < a.A ? best[j] : -1;
+      const bool ex = bi >= 0 && bi < a.total;
+      const unsigned long long bal = __ballot(ex);
+      const int r = run + __popcll(bal & ((1ull << lane) - 1ull));
+      const bool over = ex && r >= a.max_extra;
+      if (ex && !over) {
+        const long long dst = out0 + nb + r;
+        const float b0 = a.boxes[4 * (long long)bi], b1 = a.boxes[4 * (long long)bi + 1];
+        const float b2 = a.boxes[4 * (long long)bi + 2], b3 = a.boxes[4 * (long long)bi + 3];
+        const float bcx = (b0 + b2) / 2.f, bcy = (b1 + b3) / 2.f, bw = b2 - b0 + 1.f, bh = b3 - b1 + 1.f;
+        const double ax = a.anchors[4 * j], ay = a.anchors[4 * j + 1], aw = a.anchors[4 * j + 2], ah = a.anchors[4 * j + 3];
+        a.out_idx[dst] = j; a.out_cls[dst] = a.class_ids[bi];
+        a.out_boxes[4 * dst] = b0; a.out_boxes[4 * dst + 1] = b1; a.out_boxes[4 * dst + 2] = b2; a.out_boxes[4 * dst + 3] = b3;
+        a.out_deltas[4 * dst] = (float)(((double)bcx - ax) / aw); a.out_deltas[4 * dst + 1] = (float)(((double)bcy - ay) / ah);
+        a.out_deltas[4 * dst + 2] = (float)log((double)bw / aw); a.out_deltas[4 * dst + 3] = (float)log((double)bh / ah);
+      }
+      const unsigned long long obal = __ballot(over);
+      const int w0 = (q * AM_THREADS + s * 64) >> 5;    // this wave step's two words: no other lane of the launch touches them
+      if (lane == 0 && w0 < nwords && (unsigned)(obal & 0xffffffffull)) irow[w0] |= (unsigned)(obal & 0xffffffffull);
+      if (lane == 32 && w0 + 1 < nwords && (unsigned)(obal >> 32)) irow[w0 + 1] |= (unsigned)(obal >> 32);
+      run += __popcll(bal);
+    }
+  }
+}
+
+// boxes [total][4] fp32 xyxy, class_ids [total], box_offsets [B+1] and the encoder's anchor_idx [total] / deltas [total][4] for them;
+// anchors [A][4] float64; ignore_in uint32 [B][ceil(A/32)] or NULL -- device pointers.  thresholds: HOST pointer to two doubles
+// (pos_iou, ign_iou), 0 < ign_iou <= pos_iou <= 1.  workspace: 4 * B * (A + ceil(A / 256)) bytes of device memory.  Outputs (device):
+// out_anchor_idx / out_class_ids [total + B * max_extra], out_boxes / out_deltas [..][4], out_offsets [B+1], ignore_out uint32
+// [B][ceil(A/32)] (may be ignore_in itself: a word is read and written by one lane of the first launch), overflow int32 [B].  Everything
+// is written.  Status 1 for anything malformed, 2 for A > 2^20, B > 65535 or total + B * max_extra >= 2^31 (include/sqd_hip.h).
+extern "C" int sqd_anchor_match_fwd(const float* boxes, const int* class_ids, const int* box_offsets, const int* anchor_idx,
+                                    const float* deltas, const double* anchors, const unsigned* ignore_in, const double* thresholds,
+                                    void* workspace, int* out_anchor_idx, float* out_boxes, float* out_deltas, int* out_class_ids,
+                                    int* out_offsets, unsigned* ignore_out, int* overflow, int total, int B, int A, int max_extra,
+                                    void* stream) {
+  SQD_CHECK_ARG(box_offsets && anchors && thresholds && workspace && out_offsets && ignore_out && overflow);
+  SQD_CHECK_ARG(B > 0 && A > 0 && total >= 0 && max_extra >= 0);
+  SQD_CHECK_ARG(total == 0 || (boxes && class_ids && anchor_idx && deltas));
+  SQD_CHECK_ARG(thresholds[1] > 0.0 && thresholds[1] <= thresholds[0] && thresholds[0] <= 1.0);     // (NaN fails)
+  if (A > (1 << 20) || B > 65535 || (long long)total + (long long)B * max_extra >= (1ll << 31)) return SQD_ERR_UNSUPPORTED;
+  SQD_CHECK_ARG((total == 0 && max_extra == 0) || (out_anchor_idx && out_boxes && out_deltas && out_class_ids));
+  SQD_CHECK_ARG(((uintptr_t)workspace & 3) == 0);
+  MatchArgs a;
+  a.boxes = boxes; a.class_ids = class_ids; a.box_offsets = box_offsets; a.anchor_idx = anchor_idx; a.deltas = deltas;
+  a.anchors = anchors; a.ignore_in = ignore_in;
+  a.nblk = sqd_cdiv(A, AM_THREADS);
+  a.best = (int*)workspace; a.counts = a.best + (long long)B * A;
+  a.out_idx = out_anchor_idx; a.out_boxes = out_boxes; a.out_deltas = out_deltas; a.out_cls = out_class_ids; a.out_offsets = out_offsets;
+  a.ignore_out = ignore_out; a.overflow = overflow;
+  a.pos_iou = thresholds[0]; a.ign_iou = thresholds[1];
+  a.total = total; a.B = B; a.A = A; a.max_extra = max_extra;
+  hipLaunchKernelGGL(anchor_match_score_kernel, dim3((unsigned)a.nblk, (unsigned)B), dim3(AM_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(anchor_match_compact_kernel, dim3((unsigned)B), dim3(AM_CTHREADS), 0, (hipStream_t)stream, a);
+  return sqd_launch_status();
+}

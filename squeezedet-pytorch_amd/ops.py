@@ -1508,8 +1508,8 @@ class SparseGT(NamedTuple):
     ``offsets`` int32 [B+1]: image b owns the entries ``offsets[b] .. offsets[b+1]``.  Meaning: the dense gt with mask = 1, these boxes
     and deltas and a one-hot class at ``anchor_idx``, zeros elsewhere.
 
-    Contract (include/sqd_hip.h): within one image the anchor indices are distinct (the encoder's greedy assignment guarantees it);
-    the order within an image is free; an entry with ``anchor_idx`` outside [0, A) -- the encoder's "unassigned" value A -- is ignored
+    Contract (include/sqd_hip.h): within one image the anchor indices are distinct (the encoder's greedy assignment guarantees it, and
+    ``anchor_match`` keeps it: an extra positive is never a primary and appears once); the order within an image is free; an entry with ``anchor_idx`` outside [0, A) -- the encoder's "unassigned" value A -- is ignored
     and does not count toward n_obj; a class id outside [0, C) gives a row with no class term, as the dense encoder does; ``total = 0``
     and images without entries are legal and give the NaNs that n_obj = 0 gives with a dense gt."""
     anchor_idx: torch.Tensor
@@ -1686,6 +1686,78 @@ def anchor_ignore_mask(ign_boxes, ign_offsets, anchors64, overlap, out=None):
     if br is not None:
         br.done()
     return mask
+
+
+def anchor_match(sgt, anchors64, pos_iou, ign_iou, max_extra, ignore=None, out=None):
+    """IoU-threshold anchor matching on top of the encoder's greedy assignment (csrc/gt_encode.hip; rule: DESIGN.md section 3,
+    "IoU-threshold matching", and ``boxes.anchor_match``, its host twin): ``sgt``, the ``SparseGT`` of the encoder (one entry per box:
+    the primaries), anchors64 float64 [A,4] (cx,cy,w,h), ``0 < ign_iou <= pos_iou <= 1`` (``ign_iou`` None: no band), ``max_extra``
+    >= 0, ``ignore``: the int32 [B, ceil(A/32)] bitmap of ``anchor_ignore_mask`` or None -- all on the GPU.
+
+    -> (SparseGT of ``total + B * max_extra`` entries, ignore int32 [B, ceil(A/32)], overflow int32 [B]).  Image b's segment starts at
+    ``sgt.offsets[b] + b * max_extra``: its primaries, then the anchors that are no primaries and overlap some box by ``pos_iou`` or more
+    (the first ``max_extra`` by ascending anchor index; box and class of the lowest best-overlapping box), then padding entries
+    (``anchor_idx`` A, which the loss skips).  ``ignore`` out = the given bits | the band (best overlap in [ign_iou, pos_iou)) | the
+    overflow (extras past ``max_extra``, counted per image in ``overflow``).  Two launches, every element written, nothing waits.
+    ``out``: (SparseGT, ignore, overflow) of contiguous device tensors of those shapes to write instead (they need no clearing)."""
+    from .boxes import check_match_thresholds
+    pos_iou, ign_iou, max_extra = check_match_thresholds('anchor_match', pos_iou, ign_iou, max_extra)
+    if not isinstance(sgt, SparseGT):
+        raise ValueError('anchor_match: sgt must be an ops.SparseGT (the encoder\'s list)')
+    fields = ((sgt.anchor_idx, 'anchor_idx', torch.int32), (sgt.boxes, 'boxes', torch.float32), (sgt.deltas, 'deltas', torch.float32),
+              (sgt.class_ids, 'class_ids', torch.int32), (sgt.offsets, 'offsets', torch.int32))
+    for t, nm, dt in fields:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f'anchor_match: sgt.{nm} must be a {dt} tensor')
+    if sgt.offsets.dim() != 1 or sgt.offsets.shape[0] < 2:
+        raise ValueError('anchor_match: sgt.offsets must be int32 [B+1], B >= 1')
+    total = sgt.anchor_idx.shape[0] if sgt.anchor_idx.dim() == 1 else -1
+    if total < 0 or tuple(sgt.boxes.shape) != (total, 4) or tuple(sgt.deltas.shape) != (total, 4) or tuple(sgt.class_ids.shape) != (total,):
+        raise ValueError('anchor_match: anchor_idx [total], boxes [total,4], deltas [total,4], class_ids [total] must agree on total')
+    if not isinstance(anchors64, torch.Tensor) or anchors64.dtype != torch.float64 or anchors64.dim() != 2 or anchors64.shape[1] != 4 \
+            or anchors64.shape[0] < 1:
+        raise ValueError('anchor_match: anchors must be float64 [A,4]')
+    B, A = sgt.offsets.shape[0] - 1, anchors64.shape[0]
+    out_total = total + B * max_extra
+    if A > 2 ** 20 or B > 65535 or out_total >= 2 ** 31:
+        raise ValueError(f'anchor_match: at most 2^20 anchors, 65535 images and 2^31 - 1 output entries, got A={A} B={B} '
+                         f'total + B * max_extra = {out_total}')
+    if ignore is not None and (not isinstance(ignore, torch.Tensor) or ignore.dtype != torch.int32 or tuple(ignore.shape) != (B, ignore_words(A))):
+        raise ValueError(f'anchor_match: ignore must be int32 [B, ceil(A/32)] = [{B}, {ignore_words(A)}] (ops.anchor_ignore_mask) or None')
+    if not anchors64.is_cuda:
+        raise ValueError(f'anchor_match: anchors must be on the GPU, got {anchors64.device}')
+    dev = anchors64.device
+    for t, nm in [(t, 'sgt.' + nm) for t, nm, _ in fields] + ([(ignore, 'ignore')] if ignore is not None else []):
+        if t.device != dev:
+            raise ValueError(f'anchor_match: {nm} is on {t.device}, anchors on {dev}')
+    sgt = SparseGT(*(t.contiguous() for t in sgt))
+    anchors64 = anchors64.contiguous()
+    ignore = None if ignore is None else ignore.contiguous()
+    shapes = (((out_total,), torch.int32), ((out_total, 4), torch.float32), ((out_total, 4), torch.float32), ((out_total,), torch.int32),
+              ((B + 1,), torch.int32), ((B, ignore_words(A)), torch.int32), ((B,), torch.int32))
+    if out is None:
+        flat = [torch.empty(*s, device=dev, dtype=dt) for s, dt in shapes]
+    else:
+        flat = [*out[0], out[1], out[2]] if isinstance(out, (tuple, list)) and len(out) == 3 and isinstance(out[0], SparseGT) else []
+        if len(flat) != 7 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.dtype != dt or t.device != dev or not t.is_contiguous()
+                                 for t, (s, dt) in zip(flat, shapes)):
+            raise ValueError(f'anchor_match: out must be (SparseGT of {out_total} entries and offsets [{B + 1}], int32 [{B}, {ignore_words(A)}], '
+                             f'int32 [{B}]), contiguous, on the device of the anchors')
+    out, mask, overflow = SparseGT(*flat[:5]), flat[5], flat[6]
+    ws = torch.empty(B * (A + -(-A // 256)), device=dev, dtype=torch.int32)      # best box per anchor, extras per 256-anchor block
+    br = _Bracket('anchor_match', f'match A{A}', 0.0, 32.0 * A + B * (16.0 * A + 8.0 * ignore_words(A)) + 80.0 * out_total) \
+        if timing._timer is not None else None
+    rc = nat.lib().sqd_anchor_match_fwd(
+        nat.ptr(sgt.boxes) if total else None, nat.ptr(sgt.class_ids) if total else None, nat.ptr(sgt.offsets),
+        nat.ptr(sgt.anchor_idx) if total else None, nat.ptr(sgt.deltas) if total else None, nat.ptr(anchors64), nat.ptr(ignore),
+        (ctypes.c_double * 2)(pos_iou, ign_iou), nat.ptr(ws), nat.ptr(out.anchor_idx) if out_total else None,
+        nat.ptr(out.boxes) if out_total else None, nat.ptr(out.deltas) if out_total else None,
+        nat.ptr(out.class_ids) if out_total else None, nat.ptr(out.offsets), nat.ptr(mask), nat.ptr(overflow), int(total), B, A, max_extra,
+        nat.stream_handle(dev))
+    nat.check(rc, 'sqd_anchor_match_fwd')
+    if br is not None:
+        br.done()
+    return out, mask, overflow
 
 
 def _check_masked_loss_args(name, pred, sgt, ignore, anchors, num_classes):

@@ -8,7 +8,9 @@ augmented the reference's train-phase way (``augment``), ready for ``Trainer.run
 same with and without its flagged boxes.  With ``cfg.ignore_overlap`` unset the flagged boxes are dropped (what the reference's KITTI
 loader does to ``DontCare``); with it set (``cfg.sparse_gt`` only) they follow the image's draw, are clipped to the network input and
 become ``'gt_ignore'``, the anchor ignore bitmap of ``ops.anchor_ignore_mask`` that the masked loss reads.  An image without an
-unflagged box is a legal, object-free image.
+unflagged box is a legal, object-free image.  With ``cfg.match_iou`` set (``cfg.sparse_gt`` only; ``config.check_match``) the IoU-threshold
+matcher (``ops.anchor_match``) runs after the encoder: ``'gt_sparse'`` then holds its extra positives too, ``'gt_ignore'`` its band and
+overflow (ORed onto the regions' bits), and ``'gt_match_overflow'`` the per-image overflow counts, a device tensor nothing waits on.
 
 ``cfg.num_workers`` threads load the next batch and pack its raw pixels into a pinned staging buffer owned by the loader (two,
 used alternately; one is refilled only after an event shows its previous host-to-device copy has finished).  The main thread
@@ -37,7 +39,7 @@ import numpy as np
 import torch
 
 from . import augment
-from .config import check_geometry, check_mosaic
+from .config import check_geometry, check_match, check_mosaic
 from .annotations import clip_ignore_boxes, encode_annotations, ignore_overlap_of, split_flagged
 from .trainer import shard_sizes
 
@@ -69,7 +71,7 @@ class TrainLoader:
     """Iterable of device-resident training batches over ``dataset`` (see the module docstring).
 
     cfg fields read: batch_size (global), input_size, num_workers, device, drift_prob, flip_prob, seed, forbid_resize, anchors,
-    num_classes, brightness_jitter, contrast_jitter, saturation_jitter, sparse_gt, ignore_overlap, letterbox, zoom_out.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState
+    num_classes, brightness_jitter, contrast_jitter, saturation_jitter, sparse_gt, ignore_overlap, match_iou, match_ignore_iou, match_max_extra, letterbox, zoom_out.  ``seed`` (default ``cfg.seed``) seeds the loader's RandomState
     once (and, as ``[seed mod 2^32, COLOR_STREAM]``, the colour one; as ``[seed mod 2^32, ZOOM_STREAM]``, the zoom-out one); each epoch
     (``iter``) continues them.  ``cfg.letterbox``: the letterbox geometry (DESIGN.md 6b "Letterbox and zoom-out"), the window of every
     image in ``plan()``'s ``'window'`` and ``image_meta['letterbox']``; ``cfg.zoom_out`` = d in (0, 1) shrinks and places it
@@ -84,6 +86,7 @@ class TrainLoader:
             raise ValueError(f'TrainLoader: rank {rank} outside world {world}')
         self.batch_size = int(cfg.batch_size)
         self.ignore_overlap = ignore_overlap_of(cfg, 'TrainLoader')
+        self.match = check_match(cfg, 'TrainLoader')
         seed = getattr(cfg, 'seed', 42) if seed is None else seed
         self.rng = np.random.RandomState(seed)
         self.color_rng = np.random.RandomState(None if seed is None else np.append(np.asarray(seed, np.int64).reshape(-1) & 0xFFFFFFFF, COLOR_STREAM))
@@ -321,8 +324,12 @@ class TrainLoader:
             augment.launch_mosaic(dev_buf, B, len(sizes), hdr, self.cfg.input_size, out, self.rgb_mean, self.rgb_std, color=color is not None)
             sizes = gsizes[lo:hi]                         # (image_meta speaks of the output images' own sources)
         sparse = bool(getattr(self.cfg, 'sparse_gt', False))      # the positives as a list (ops.SparseGT): no dense tensor is built
-        ignore = None
-        if self.ignore_overlap is not None:
+        ignore = overflow = None
+        if self.match is not None:
+            gt, ignore, overflow = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device, dense=False,
+                                                      ignore_boxes_list=p.get('ignore_boxes'), ignore_overlap=self.ignore_overlap,
+                                                      match=self.match, return_overflow=True)
+        elif self.ignore_overlap is not None:
             gt, ignore = encode_annotations(p['class_ids'], tb, self.cfg.anchors, self.cfg.num_classes, device=self.device, dense=False,
                                             ignore_boxes_list=p['ignore_boxes'], ignore_overlap=self.ignore_overlap)
         else:
@@ -336,6 +343,8 @@ class TrainLoader:
         batch = {'image': out, 'image_meta': meta, 'gt_sparse' if sparse else 'gt': gt}
         if ignore is not None:
             batch['gt_ignore'] = ignore
+        if overflow is not None:
+            batch['gt_match_overflow'] = overflow
         return batch
 
     def __iter__(self):

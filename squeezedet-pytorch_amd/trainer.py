@@ -27,13 +27,24 @@ def encode_sparse_batch(batch, cfg):
     ``'gt_sparse'`` (an ``ops.SparseGT``: the positives as a list, read by the sparse loss launches) instead and no dense tensor is
     built.  Dense batches pass through, whatever the flag.  ``cfg.ignore_overlap`` (needs ``cfg.sparse_gt``): ``batch['gt_ignore_boxes']``,
     a per-image list of ignore boxes (xyxy, network-input coordinates; absent: none), becomes ``'gt_ignore'``, the anchor ignore
-    bitmap the masked loss reads; with the field unset the ignore boxes are dropped."""
+    bitmap the masked loss reads; with the field unset the ignore boxes are dropped.  ``cfg.match_iou`` (needs ``cfg.sparse_gt``;
+    ``config.check_match``): the IoU-threshold matcher adds its extra positives to ``'gt_sparse'``, its band and overflow to ``'gt_ignore'``
+    (on top of the regions' bits, if any), and the batch gets ``'gt_match_overflow'``, int32 [B] on the device."""
     from .annotations import encode_annotations, ignore_overlap_of
+    from .config import check_match
     overlap = ignore_overlap_of(cfg, 'encode_sparse_batch')
+    match = check_match(cfg, 'encode_sparse_batch')
     if 'gt' in batch or 'gt_sparse' in batch or 'gt_boxes' not in batch:
         return batch
     out = {k: v for k, v in batch.items() if k not in ('gt_boxes', 'gt_class_ids', 'gt_ignore_boxes')}
     sparse = bool(getattr(cfg, 'sparse_gt', False))
+    if match is not None:
+        ign = batch.get('gt_ignore_boxes') if overlap is not None else None
+        ign = [[] for _ in batch['gt_boxes']] if (ign is None and overlap is not None) else ign
+        out['gt_sparse'], out['gt_ignore'], out['gt_match_overflow'] = encode_annotations(
+            batch['gt_class_ids'], batch['gt_boxes'], cfg.anchors, cfg.num_classes, device=cfg.device, dense=False, ignore_boxes_list=ign,
+            ignore_overlap=overlap, match=match, return_overflow=True)
+        return out
     if overlap is not None:
         ign = batch.get('gt_ignore_boxes')
         ign = [[] for _ in batch['gt_boxes']] if ign is None else ign
