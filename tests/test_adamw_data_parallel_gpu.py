@@ -1,7 +1,8 @@
 """GPU tier, two processes on one GPU (the launch pattern of tests/test_data_parallel_gpu.py): after ``attach_data_parallel`` -- which
 replicates rank 0's weights and, in place, the floating-point optimizer state: both moments and the EMA are views of flat buffers in
 ``optimizer.state`` -- and three steps of ``FusedClipAdamW`` with the EMA on unequal shards, both ranks hold bit-identical parameters,
-moments and EMA, and equal device counts."""
+moments and EMA, and equal device counts.  The first step's exchanged gradient is the count-weighted mean of the two ranks' local
+gradients within 2^-18 M on every element (tests/dp_exchange_ref.py)."""
 import os
 import sys
 
@@ -10,7 +11,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from test_data_parallel_gpu import ROOT, _setup
+from test_data_parallel_gpu import ROOT, _local_gradient, _setup, check_exchange_against_local_gradients
 
 pytestmark = pytest.mark.gpu
 
@@ -32,15 +33,19 @@ def _worker(rank, world, port, out_dir):
     if rank == 1:
         opt.exp_avg_flat.fill_(0.5); opt.exp_avg_sq_flat.fill_(0.25)
     attach_data_parallel(m, opt)
-    for _ in range(3):
+    local = _local_gradient(m, batch)                       # (on the replicated weights, before the first step)
+    for it in range(3):
         loss, _ = m(batch)
         opt.zero_grad()
         loss.mean().backward()
+        if it == 0:
+            torch.cuda.synchronize()
+            first_grad = m.base.last_grad_flat.detach().cpu().clone()
         opt.step()
     torch.cuda.synchronize()
     w = torch.cat([p.detach().reshape(-1) for p in m.parameters()]).cpu()
     torch.save({'weights': w, 'm': opt.exp_avg_flat.cpu(), 'v': opt.exp_avg_sq_flat.cpu(), 'ema': opt.ema_flat.cpu(),
-                'counts': opt.step_counts()}, os.path.join(out_dir, f'r{rank}.pt'))
+                'counts': opt.step_counts(), 'local': local, 'grad': first_grad}, os.path.join(out_dir, f'r{rank}.pt'))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -51,6 +56,8 @@ def test_two_ranks_hold_identical_adamw_and_ema_state(tmp_path):
     mp.spawn(_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     r0 = torch.load(str(tmp_path / 'r0.pt')); r1 = torch.load(str(tmp_path / 'r1.pt'))
     assert r0['counts'] == r1['counts'] == (3, 3)
+    assert torch.equal(r0['grad'], r1['grad']), 'ranks disagree after the first exchange'
+    check_exchange_against_local_gradients(r0['grad'], [r0['local'], r1['local']], (3, 2), 'two processes (3, 2), AdamW step 0')
     for k in ('weights', 'm', 'v', 'ema'):
         assert bool(torch.isfinite(r0[k]).all()), k
         assert torch.equal(r0[k].view(torch.int32), r1[k].view(torch.int32)), f'ranks disagree in {k} after three steps'
