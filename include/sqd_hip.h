@@ -286,6 +286,21 @@ int sqd_filter_nms_fwd(const long long* class_ids, const float* scores, const fl
                        int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words,
                        int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, void* stream);
 
+/* Pooled views (DESIGN.md section 3 "Pooled views"): V network views of one image -- test-time augmentation, tiles of a large frame --
+ * whose candidates meet in ONE top-k and ONE suppression, in image coordinates.  pred [B * V][A][C + 5], view v of image b = row
+ * b * V + v; view_xf fp32 [B * V][6] = (sy, sx, dy, dx, flip, mirror).  Candidates of image b: all (v, a), pooled index p = v * A + a;
+ * key and threshold as every detect entry; top keep_top_k by (score descending, p ascending); a candidate's box is the canvas box
+ * mapped in fp32 by x' = x / sx + dx, y' = y / sy + dy and, if flip != 0, (x1'', x2'') = (mirror - x2', mirror - x1'); then the NMS
+ * modes' rule (nms_mode, nms_sigma, nms_agnostic as sqd_detect_nms_fwd) on those image boxes.  Outputs [B] / [B][keep_top_k]: det_box
+ * is the image box, det_anchor = p.  V = 1 with view_xf = (1, 1, 0, 0, 0, 0) equals sqd_detect_nms_fwd bit for bit.  keys_ws: 16-byte
+ * aligned, ws_words >= sqd_detect_wide_workspace_words(B * V, A, keep_top_k), any contents.  Status 2 past the limits (V * ceil4(A) >
+ * 2^20, keep_top_k > 1024, num_classes > 256); 1 for anything malformed (a null pointer, V < 1, a short or misaligned workspace, an
+ * unknown nms_mode, a bad sigma, score_thresh < 0); nothing is launched then. */
+int sqd_detect_views_fwd(const float* pred, const float* anchors, const float* view_xf, unsigned* keys_ws, int* det_count,
+                         long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int V, int A,
+                         int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                         int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, void* stream);
+
 /* GPU-side input pipeline: whiten + cv2.resize(INTER_LINEAR) + HWC->CHW of
  * DataWrapper.__getitem__ / BaseDataset.preprocess / whiten / resize (src/engine/detector.py:132-142,
  * src/datasets/base.py:43-59, src/utils/image.py:9-19,77-88) for a batch of uint8 RGB images of arbitrary sizes.

@@ -125,6 +125,29 @@ def check_nms(cfg, who):
     return mode, float(sigma), bool(agnostic)
 
 
+def check_tta(cfg, who):
+    """The test-time augmentation of ``cfg`` (DESIGN.md section 3 "Pooled views"): (tta_flip, tta_zooms) -- ``tta_flip`` a bool,
+    ``tta_zooms`` None or a non-empty sequence of finite zooms in (0, 16] -- and whether either is set.  A cfg without the fields means
+    off.  Set, they are the default ``views`` of ``Detector.detect_images``; pooled views place a resize window, so they exclude
+    ``forbid_resize``.  -> (flip, zooms or None, on)."""
+    flip = getattr(cfg, 'tta_flip', False)
+    if not isinstance(flip, (bool, np.bool_)):
+        raise ValueError(f'{who}: tta_flip must be a bool, got {flip!r}')
+    zooms = getattr(cfg, 'tta_zooms', None)
+    if zooms is not None:
+        try:
+            z = tuple(float(v) for v in zooms)
+        except (TypeError, ValueError):
+            raise ValueError(f'{who}: tta_zooms must be None or a sequence of numbers, got {zooms!r}') from None
+        if not z or any(isinstance(v, (bool, np.bool_)) for v in zooms) or not all(np.isfinite(v) and 0. < v <= 16. for v in z):
+            raise ValueError(f'{who}: tta_zooms must be a non-empty sequence of finite numbers in (0, 16], got {zooms!r}')
+        zooms = z
+    on = bool(flip) or zooms is not None
+    if on and bool(getattr(cfg, 'forbid_resize', False)):
+        raise ValueError(f'{who}: tta_flip / tta_zooms pool views of a resize window, they exclude forbid_resize')
+    return bool(flip), zooms, on
+
+
 def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_ANCHORS_SEED,
              num_classes=3, class_names=None, device='cuda', **overrides):
     """Namespace with the reference's defaults (src/utils/config.py:23-85) plus the
@@ -174,6 +197,10 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
         ema_decay=0.,                # > 0: the optimizer keeps an exponential moving average of the weights inside its step launch
         ema_warmup=False,            # the EMA's decay starts at min(ema_decay, (1 + n) / (10 + n)) after n averaged steps
         ema_eval=False,              # Trainer.val_epoch runs on the averaged weights (optimizer.averaged_weights())
+        tta_flip=False,              # test-time augmentation (DESIGN.md section 3 "Pooled views"; off by default): Detector.detect_images also runs
+                                     # the mirror image, and / or the zooms of tta_zooms (None: off; e.g. (1.0, 0.75)), and pools all
+                                     # candidates of an image into one top-k and one NMS (views.tta_views); not in the captured lanes
+        tta_zooms=None,
         inflight=2,                  # batches in flight on the device in Detector.stream / detect_dataset (lanes.DetectStream)
         input_size=tuple(input_size), num_classes=num_classes, class_names=tuple(class_names),
         anchors=anchors, anchors_per_grid=int(np.asarray(anchors_seed).shape[0]),
@@ -186,4 +213,5 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
     check_bbox_loss(cfg.bbox_loss, 'make_cfg')
     check_nms(cfg, 'make_cfg')
     check_match(cfg, 'make_cfg')
+    check_tta(cfg, 'make_cfg')
     return cfg

@@ -9,10 +9,20 @@
 // read as 0; false: the scoring launch wrote them as 0.  Every thread of the 1024-thread workgroup runs it.  It leaves in scope:
 // tid, lane, wave, b, A, C, ncand, and for thread r < ncand (ok) the candidate of rank r: score, cls, idx, bx; boxL / clsL hold all
 // of them in rank order (clsL = -1, boxL = 0 from ncand up to Kp).
+// DETW_VIEWS (off for those two kernels; detect_views_select_kernel defines it as its view count, with DETW_VIEW_XF = the view table
+// [B * V][6]): the pooled-views form of DESIGN.md section 3 "Pooled views" -- steps 1-3 run over the V key rows of the image as one
+// row, step 4 maps every box into image coordinates; pred only, no dense inputs.
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = (int)blockIdx.x;
+#ifdef DETW_VIEWS
+  // pooled views: the key rows of the image's V views, ceil4(A) words each, lie back to back and ARE one row of V * ceil4(A) words
+  // (the scoring launch wrote every pad word as 0); a candidate's index below is s = v * ceil4(A) + anchor, ascending in (v, anchor)
+  const int A = a.A, C = a.C, A4 = (A + 3) & ~3, nq = ((DETW_VIEWS) * A4) >> 2;
+  const u32x4_w* __restrict__ ws4 = (const u32x4_w*)(a.keys + (long long)b * (DETW_VIEWS) * A4);
+#else
   const int A = a.A, C = a.C, A4 = (A + 3) & ~3, nq = A4 >> 2;
   const u32x4_w* __restrict__ ws4 = (const u32x4_w*)(a.keys + (long long)b * A4);
+#endif
   const bool dense = a.in_score != nullptr;
 
   if (tid == 0) { sv[0] = 0u; sv[1] = (unsigned)K; sv[2] = 0u; }
@@ -106,6 +116,46 @@
   const bool ok = tid < ncand;
   float score = 0.f; int cls = -1, idx = 0;
   BoxF bx = {0.f, 0.f, 0.f, 0.f};
+#ifdef DETW_VIEWS
+  // the view-aware decode: candidate s belongs to view v = s / ceil4(A), row b * V + v of pred and of the view table; its box is
+  // anchor_box's, mapped into image coordinates by detv_map BEFORE any IoU is taken; idx becomes the pooled index p = v * A + anchor
+  if (MANY) {
+    const int j = tid & (MC_LANES - 1);
+    for (int r = tid / MC_LANES; r < ncand; r += DETW_THREADS / MC_LANES) {
+      const int s = (int)(0xffffffffu - (unsigned)(cand[r] & 0xffffffffull));
+      const int v = s / A4, ai = s - v * A4;
+      const long long row = (long long)b * (DETW_VIEWS) + v;
+      const float* p = a.pred + (row * A + ai) * (C + 5);
+      float sc; int c;
+      mc_anchor_score<MC_REGS>(p, C, j, sc, c);
+      if (j == 0) {
+        const BoxF bb = detv_map(anchor_box(p + C + 1, a.anchors + 4 * ai, a.wmax, a.hmax), (DETW_VIEW_XF) + 6 * row);
+        boxL[r] = (f32x4){bb.x1, bb.y1, bb.x2, bb.y2};
+        clsL[r] = c;
+      }
+    }
+    __syncthreads();
+    if (ok) {
+      const int s = (int)(0xffffffffu - (unsigned)(cand[tid] & 0xffffffffull));
+      const int v = s / A4;
+      idx = v * A + (s - v * A4);
+      score = __uint_as_float((unsigned)(cand[tid] >> 32));
+      cls = clsL[tid];
+      const f32x4 bv = boxL[tid];
+      bx.x1 = bv.x; bx.y1 = bv.y; bx.x2 = bv.z; bx.y2 = bv.w;
+    }
+  } else if (ok) {
+    const int s = (int)(0xffffffffu - (unsigned)(cand[tid] & 0xffffffffull));
+    const int v = s / A4, ai = s - v * A4;
+    const long long row = (long long)b * (DETW_VIEWS) + v;
+    const float* p = a.pred + (row * A + ai) * (C + 5);
+    idx = v * A + ai;
+    anchor_score(p, C, score, cls);
+    bx = detv_map(anchor_box(p + C + 1, a.anchors + 4 * ai, a.wmax, a.hmax), (DETW_VIEW_XF) + 6 * row);
+    boxL[tid] = (f32x4){bx.x1, bx.y1, bx.x2, bx.y2};
+    clsL[tid] = cls;
+  }
+#else
   if (MANY && !dense) {
     // a 16-lane group per candidate (64 groups, <= 16 rounds): the class comes from the same mc_anchor_score that made the key, so
     // the score IS the key; lane 0 of the group decodes the box
@@ -144,4 +194,5 @@
     boxL[tid] = (f32x4){bx.x1, bx.y1, bx.x2, bx.y2};
     clsL[tid] = cls;
   }
+#endif
   __syncthreads();

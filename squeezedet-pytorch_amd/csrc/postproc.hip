@@ -1044,110 +1044,9 @@ __global__ __launch_bounds__(DETW_THREADS) void detect_nms_select_kernel(DetArgs
 #define DETW_PAD_ANY true
 #include "detw_select_body.h"     // 1.-4. select, sweep, rank, decode: tid, lane, wave, b, A, C, ncand, ok, score, cls, idx, bx
 #undef DETW_PAD_ANY
-  const int G = n.agnostic ? 1 : C;
-  const float thr = a.score_thresh;
-
-  // 5. order by (group, rank): slot = candidates of earlier groups + earlier ranks of my group
-  const int g = (ok && cls >= 0 && cls < C) ? (n.agnostic ? 0 : cls) : -1;
-  if (tid < Kp) { grpL[tid] = g; curL[tid] = -1.f; emitL[tid] = -1; }
-  if (tid < 256) { glen[tid] = 0; gstart[tid] = 0; gcnt[tid] = 0u; }
-  __syncthreads();
-  int slot = 0;
-  if (n.agnostic) {
-    unsigned tot;
-    slot = (int)detw_excl_scan(g >= 0 ? 1u : 0u, tot, wave_tot, lane, wave);
-    if (tid == 0) glen[0] = (int)tot;
-  } else if (g >= 0) {
-    int before = 0, same_before = 0, same = 0;
-    for (int r = 0; r < ncand; ++r) {
-      const int gr = grpL[r];
-      before += (gr >= 0 && (gr < g || (gr == g && r < tid))) ? 1 : 0;
-      same_before += (gr == g && r < tid) ? 1 : 0;
-      same += (gr == g) ? 1 : 0;
-    }
-    slot = before;
-    if (same_before == 0) { gstart[g] = before; glen[g] = same; }
-  }
-  if (g >= 0) { boxP[slot] = (f32x4){bx.x1, bx.y1, bx.x2, bx.y2}; curL[slot] = score; }     // slot < ncand <= Kp
-  __syncthreads();
-
-  // 6. the scan
-  if (n.agnostic && glen[0] > 64) {
-    // one group on the whole workgroup: slot p in thread p's registers (glen[0] <= ncand <= 1024 = the threads)
-    const int len = glen[0];
-    const f32x4 me = boxP[tid < len ? tid : 0];
-    float cur = tid < len ? curL[tid] : -1.f;
-    int t = 0;
-    for (;; ++t) {                                             // <= len + 1 rounds: every round but the last retires one candidate
-      const float wm = nms_wave_max(cur);
-      const unsigned long long hit = __ballot(cur == wm);
-      float* ss = slot_s + 16 * (t & 1); int* sp = slot_p + 16 * (t & 1);
-      if (lane == 0) { ss[wave] = wm; sp[wave] = hit ? wave * 64 + (__ffsll((long long)hit) - 1) : 0; }
-      __syncthreads();
-      const float v = lane < 16 ? ss[lane] : -1.f;
-      const float m = nms_wave_max(v);
-      if (!(m > thr)) break;                                   // (the same m in every wave: the whole workgroup leaves together)
-      const unsigned long long wh = __ballot(lane < 16 && v == m);          // != 0: m is one of the v
-      const int pp = sp[__ffsll((long long)wh) - 1];           // lowest wave = lowest slot = lowest rank
-      const f32x4 pk = boxP[pp];
-      const float pa = (pk.z - pk.x) * (pk.w - pk.y);
-      if (tid == pp) { emitL[tid] = t; outS[tid] = m; cur = -1.f; }
-      else if (cur >= 0.f) cur = nms_decay(n, a.nms_thresh, pk, pa, me, cur);
-    }
-    if (tid == 0) gcnt[0] = (unsigned)t;
-  } else {
-    for (int gi = wave; gi < G; gi += DETW_THREADS / 64) {
-      const int s0 = gstart[gi], len = glen[gi];
-      int t = 0;
-      if (len <= 64) {
-        const bool in = lane < len;
-        const f32x4 me = boxP[in ? s0 + lane : 0];
-        float cur = in ? curL[s0 + lane] : -1.f;
-        for (; t < len; ++t) {
-          const float m = nms_wave_max(cur);
-          if (!(m > thr)) break;
-          const int pl = __ffsll((long long)__ballot(cur == m)) - 1;        // (m > thr >= ... is one of the cur: the ballot is not empty)
-          const f32x4 pk = boxP[s0 + pl];
-          const float pa = (pk.z - pk.x) * (pk.w - pk.y);
-          if (lane == pl) { emitL[s0 + lane] = t; outS[s0 + lane] = m; cur = -1.f; }
-          else if (cur >= 0.f) cur = nms_decay(n, a.nms_thresh, pk, pa, me, cur);
-        }
-      } else {
-        // the group strides over the lanes: slot s0 + lane + 64 i belongs to this lane alone, so curL needs no ordering between lanes
-        float lm = -1.f; int lp = 0x7fffffff;
-        for (int p = s0 + lane; p < s0 + len; p += 64) { const float c = curL[p]; if (c > lm) { lm = c; lp = p; } }
-        for (; t < len; ++t) {
-          const float m = nms_wave_max(lm);
-          if (!(m > thr)) break;
-          const int pp = nms_wave_min(lm == m ? lp : 0x7fffffff);           // lowest slot among the ties
-          const f32x4 pk = boxP[pp];
-          const float pa = (pk.z - pk.x) * (pk.w - pk.y);
-          lm = -1.f; lp = 0x7fffffff;
-          for (int p = s0 + lane; p < s0 + len; p += 64) {
-            float c = curL[p];
-            if (p == pp) { emitL[p] = t; outS[p] = m; c = -1.f; curL[p] = c; }
-            else if (c >= 0.f) { c = nms_decay(n, a.nms_thresh, pk, pa, boxP[p], c); curL[p] = c; }
-            if (c > lm) { lm = c; lp = p; }
-          }
-        }
-      }
-      if (lane == 0) gcnt[gi] = (unsigned)t;
-    }
-  }
-  __syncthreads();
-
-  // 7. placement: rows of the earlier groups + pick order
-  {
-    unsigned total;
-    const unsigned off = detw_excl_scan((tid < G) ? gcnt[tid & 255] : 0u, total, wave_tot, lane, wave);
-    if (tid < 256) goff[tid] = off;
-    if (tid == 0) a.det_count[b] = (int)total;
-  }
-  __syncthreads();
-  if (g >= 0) {
-    const int t = emitL[slot];
-    if (t >= 0) DETW_STORE_ROW(a, b, K, goff[g] + (unsigned)t, cls, outS[slot], idx, bx);
-  }
+#define DETN_STORE(pos, sc) DETW_STORE_ROW(a, b, K, pos, cls, sc, idx, bx)
+#include "detn_scan_body.h"     // 5.-7. (group, rank) order, the scan, the placement
+#undef DETN_STORE
 }
 
 static int launch_detect_nms(DetArgs a, NmsArgs n, int ws_words, hipStream_t stream) {
@@ -1224,4 +1123,141 @@ extern "C" int sqd_filter_nms_fwd(const long long* class_ids, const float* score
   a.wmax = 0.f; a.hmax = 0.f; a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
   const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
   return launch_detect_nms(a, n, ws_words, (hipStream_t)stream);
+}
+
+// ---- pooled views: V network views of one image, one top-k and one suppression in image coordinates (DESIGN.md section 3 "Pooled views") ----
+// Test-time augmentation (the image, its mirror image, other scales) and sliced inference (overlapping tiles of a large frame) are the
+// same operation: pred holds V rows per image -- view v of image b is row b * V + v -- and view_xf [B * V][6] = (sy, sx, dy, dx, flip,
+// mirror) says how a row's canvas maps into the image.  The rule:
+//   candidates of image b = all pairs (v, a), pooled index p = v * A + a; key = the score key of every other detect launch (score >
+//   score_thresh), so the scoring launches run unchanged on the B * V rows; top K of the pool by (score descending, p ascending) --
+//   equal scores in two views go to the lower view; the box of a candidate is anchor_box's (clamped to the canvas), then in fp32, op
+//   for op (no contraction: -ffp-contract=off)   x' = x / sx + dx,   y' = y / sy + dy   -- DETW_STORE_ROW's expression: one division,
+//   one addition --   and, if flip != 0,   (x1'', x2'') = (mirror - x2', mirror - x1');   then the rule of "NMS modes" (hard, linear,
+//   Gaussian; class-wise or agnostic) on those IMAGE-coordinate boxes.  Rows come out in class order and pick order, det_box is the
+//   image box (nothing more is applied at the store), det_anchor = p (view = p / A, anchor = p % A), det_score the current score at
+//   pick time.
+// The division comes before the IoU because the views have different scales: two canvas boxes of different views are not comparable.
+// V = 1 with view_xf = (1, 1, 0, 0, 0, 0) gives sqd_detect_nms_fwd's rows bit for bit; with another scale it need not (that launch
+// suppresses on canvas boxes and divides afterwards).
+// Two launches, as the other wide forms: the scoring kernel of the head form on B * V rows -> the workspace [B * V][ceil4(A)], pad words
+// 0, so that the V key rows of an image ARE one pooled row of V * ceil4(A) words; then detect_views_select_kernel, one 1024-thread
+// workgroup per image: steps 1-3 of detw_select_body.h over the pooled row, its view-aware step 4 (DETW_VIEWS), and the scan of
+// detect_nms_select_kernel (detn_scan_body.h), the same text.  LDS: that kernel's.  The view data is a kernel argument of its own, so
+// DetArgs and every other kernel stay what they were.  Limits: V >= 1, V * ceil4(A) <= 2^20, K <= 1024, C <= 256.
+struct ViewArgs { const float* xf; int V; };
+
+// a canvas box of a view in image coordinates; xf = (sy, sx, dy, dx, flip, mirror) of that view
+__device__ __forceinline__ BoxF detv_map(BoxF c, const float* __restrict__ xf) {
+  const float sy = xf[0], sx = xf[1], dy = xf[2], dx = xf[3];
+  BoxF m;
+  m.x1 = c.x1 / sx + dx;
+  m.y1 = c.y1 / sy + dy;
+  m.x2 = c.x2 / sx + dx;
+  m.y2 = c.y2 / sy + dy;
+  if (xf[4] != 0.f) {
+    const float mirror = xf[5], t = mirror - m.x2;
+    m.x2 = mirror - m.x1;
+    m.x1 = t;
+  }
+  return m;
+}
+
+// one detection row of the pooled launch: the box is already the image box
+#define DETV_STORE_ROW(a, b, K, pos, cls, score, idx, bx) do { \
+    const long long o = (long long)(b) * (K) + (pos); \
+    (a).det_class[o] = (cls); \
+    (a).det_score[o] = (score); \
+    (a).det_anchor[o] = (idx); \
+    *(f32x4*)((a).det_box + 4 * o) = (f32x4){(bx).x1, (bx).y1, (bx).x2, (bx).y2}; \
+  } while (0)
+
+template <bool MANY>
+__global__ __launch_bounds__(DETW_THREADS) void detect_views_select_kernel(DetArgs a, NmsArgs n, ViewArgs vw) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int K = a.K, Kp = (K + 63) & ~63;                     // the layout of detect_nms_select_kernel
+  unsigned long long* cand = (unsigned long long*)smem_raw;
+  f32x4* boxL = (f32x4*)(cand + Kp);
+  f32x4* boxP = boxL + Kp;
+  int* clsL = (int*)(boxP + Kp);
+  int* grpL = clsL + Kp;
+  float* curL = (float*)(grpL + Kp);
+  float* outS = curL + Kp;
+  int* emitL = (int*)(outS + Kp);
+  unsigned* hist = (unsigned*)(emitL + Kp);
+  unsigned* wave_tot = hist + 256;
+  unsigned* sv = wave_tot + 16;
+  int* gstart = (int*)(sv + 4);
+  int* glen = gstart + 256;
+  unsigned* gcnt = (unsigned*)(glen + 256);
+  unsigned* goff = gcnt + 256;
+  float* slot_s = (float*)(goff + 256);
+  int* slot_p = (int*)(slot_s + 32);
+
+#define DETW_PAD_ANY false
+#define DETW_VIEWS vw.V
+#define DETW_VIEW_XF vw.xf
+#include "detw_select_body.h"     // 1.-3. over the pooled row, 4. the view-aware decode: idx = p, bx = the image box
+#undef DETW_VIEW_XF
+#undef DETW_VIEWS
+#undef DETW_PAD_ANY
+#define DETN_STORE(pos, sc) DETV_STORE_ROW(a, b, K, pos, cls, sc, idx, bx)
+#include "detn_scan_body.h"       // 5.-7. (group, rank) order, the scan, the placement
+#undef DETN_STORE
+}
+
+// Pooled-view fused detect: pred [B * V][A][C + 5] (view v of image b = row b * V + v), anchors [A][4], view_xf fp32 [B * V][6] =
+// (sy, sx, dy, dx, flip, mirror); the five result buffers are [B] / [B][K].  keys_ws: 16-byte aligned, ws_words >=
+// sqd_detect_wide_workspace_words(B * V, A, keep_top_k) = B * V * ceil4(A) uint32, any contents.  Either head form (1 <= num_classes
+// <= 256); nms_mode / nms_sigma / nms_agnostic as sqd_detect_nms_fwd.  Status 2 past the limits (V * ceil4(A) > 2^20, keep_top_k >
+// 1024, num_classes > 256, a workspace past 2^31 - 1 words); 1 for anything malformed (a null pointer, V < 1, a short or misaligned
+// workspace, an unknown mode, a bad sigma, a negative score_thresh); nothing is launched in either case.
+extern "C" int sqd_detect_views_fwd(const float* pred, const float* anchors, const float* view_xf, unsigned* keys_ws, int* det_count,
+                                    long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int V, int A,
+                                    int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                                    int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, void* stream) {
+  SQD_CHECK_ARG(pred && anchors && view_xf && keys_ws && det_count && det_class && det_score && det_box && det_anchor);
+  SQD_CHECK_ARG(((uintptr_t)det_box & 15) == 0 && (num_classes > SQD_MAX_CLASSES || ((uintptr_t)pred & 15) == 0));
+  SQD_CHECK_ARG(B > 0 && V >= 1 && A > 0 && num_classes >= 1 && keep_top_k >= 1);
+  SQD_CHECK_ARG(nms_mode == NMS_HARD || nms_mode == NMS_LINEAR || nms_mode == NMS_GAUSSIAN);
+  SQD_CHECK_ARG(nms_mode != NMS_GAUSSIAN || (isfinite(nms_sigma) && nms_sigma > 0.f));
+  SQD_CHECK_ARG(score_thresh >= 0.f);
+  if (keep_top_k > DETW_MAX_K || A > DETW_MAX_A || num_classes > SQD_MANY_MAX_CLASSES) return SQD_ERR_UNSUPPORTED;
+  const int A4 = (A + 3) & ~3;
+  if ((long long)V * A4 > DETW_MAX_A || (long long)B * V > 0x7fffffffll) return SQD_ERR_UNSUPPORTED;
+  const int rows = B * V;
+  const int words = sqd_detect_wide_workspace_words(rows, A, keep_top_k);
+  if (words < 0) return SQD_ERR_UNSUPPORTED;                  // (B x V x ceil4(A) past 2^31 - 1 words)
+  SQD_CHECK_ARG(ws_words >= words && ((uintptr_t)keys_ws & 15) == 0);
+  DetArgs a;
+  a.shifts = nullptr;
+  a.pred = pred; a.anchors = anchors; a.scales = nullptr; a.in_class = nullptr; a.in_score = nullptr; a.in_box = nullptr; a.keys = keys_ws;
+  a.S = 1; a.per = 0;
+  a.det_count = det_count; a.det_class = det_class; a.det_score = det_score; a.det_box = det_box; a.det_anchor = det_anchor;
+  a.B = rows; a.A = A; a.C = num_classes; a.K = keep_top_k;
+  a.wmax = (float)(input_w - 1); a.hmax = (float)(input_h - 1);
+  a.nms_thresh = nms_thresh; a.score_thresh = score_thresh;
+  const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
+  const ViewArgs vw = {view_xf, V};
+  const bool many = num_classes > SQD_MAX_CLASSES;
+  const int Kp = (keep_top_k + 63) & ~63;
+  const size_t lds = (size_t)Kp * (8 + 16 + 16 + 4 * 5) + NMS_LDS_FIXED;           // detect_nms_select_kernel's: <= 67 KB at K = 1024
+  static SqdDevOnce once_few, once_many;
+  if (lds > 48 * 1024 && (many ? sqd_max_lds_once(once_many, (const void*)detect_views_select_kernel<true>, 96 * 1024)
+                               : sqd_max_lds_once(once_few, (const void*)detect_views_select_kernel<false>, 96 * 1024)) != SQD_OK)
+    return SQD_ERR_LAUNCH;
+  hipStream_t st = (hipStream_t)stream;
+  if (many) {                                                 // the scoring launch of the head form, on the B * V rows
+    const int slabs = (A4 + MC_THREADS - 1) / MC_THREADS;
+#define CALL(R) hipLaunchKernelGGL(detect_many_score_kernel<R>, dim3((unsigned)((long long)rows * slabs)), dim3(MC_THREADS), 0, st, a)
+    MC_DISPATCH(a.C, CALL);
+#undef CALL
+  } else {
+    const int slabs = (A4 + DETW_SCORE_THREADS - 1) / DETW_SCORE_THREADS;
+    hipLaunchKernelGGL(detect_wide_score_kernel, dim3((unsigned)((long long)rows * slabs)), dim3(DETW_SCORE_THREADS), 0, st, a);
+  }
+  a.B = B;
+  if (many) hipLaunchKernelGGL(detect_views_select_kernel<true>, dim3((unsigned)B), dim3(DETW_THREADS), lds, st, a, n, vw);
+  else hipLaunchKernelGGL(detect_views_select_kernel<false>, dim3((unsigned)B), dim3(DETW_THREADS), lds, st, a, n, vw);
+  return sqd_launch_status();
 }

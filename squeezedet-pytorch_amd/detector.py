@@ -20,7 +20,7 @@ import torch.utils.data
 
 from . import ops
 from .boxes import boxes_postprocess
-from .config import check_nms
+from .config import check_nms, check_tta
 
 
 class Detector(object):
@@ -65,6 +65,61 @@ class Detector(object):
                      out=bufs, shifts=shifts, keys_ready=keys.written)
 
     @torch.no_grad()
+    def detect_views_device(self, image, V, view_xf, out=None):
+        """The pooled-view sibling of ``detect_device`` (DESIGN.md section 3 "Pooled views"): image [B*V,3,H,W] on the GPU holds V views
+        of each of B images (view v of image b = row b*V + v), ``view_xf`` fp32 [B*V,6] maps each row's boxes into its image
+        (``ops.detect_views``) -> (count [B], class_ids [B,K], scores [B,K], boxes [B,K,4] in image coordinates, pooled_idx [B,K] =
+        v * A + anchor), all on the GPU.  One backbone pass on B*V rows, one pooled detect; the suppression rule is ``cfg``'s."""
+        cfg = self.cfg
+        mode, sigma, agnostic = check_nms(cfg, 'Detector')
+        pred = self.model.base(image)
+        anchors = self.model.resolver.anchors_on(pred.device)
+        return ops.detect_views(pred, anchors, cfg.input_size, cfg.num_classes, V, view_xf, cfg.keep_top_k, cfg.nms_thresh,
+                                cfg.score_thresh, out=out, nms_mode=mode, nms_sigma=sigma, nms_agnostic=agnostic)
+
+    def _default_views(self):
+        """``cfg.tta_flip`` / ``cfg.tta_zooms`` as a view list, or None while both are off."""
+        from .views import tta_views
+        flip, zooms, on = check_tta(self.cfg, 'Detector')
+        return tta_views(flip=flip, zooms=zooms if zooms is not None else (1.0,)) if on else None
+
+    def _no_pooled_lanes(self, who):
+        if check_tta(self.cfg, 'Detector')[2]:
+            raise NotImplementedError(f'{who}: cfg.tta_flip / cfg.tta_zooms are set, and the captured lanes do not pool views; '
+                                      'use detect_images (or unset them)')
+
+    def _detect_images_views(self, images, image_ids, kw, views):
+        """``detect_images`` with views: per group of images with the same view count one upload, one mosaic input launch, the backbone
+        on B*V rows, one pooled detect, one D2H copy."""
+        from .preprocess import KITTI_RGB_MEAN, KITTI_RGB_STD
+        from .views import per_image_views, plan_views, render_views
+        cfg = self.cfg
+        n = len(images)
+        per = per_image_views(views, n)
+        A = int(cfg.num_anchors)
+        mean, std = kw.get('rgb_mean', KITTI_RGB_MEAN), kw.get('rgb_std', KITTI_RGB_STD)
+        results = [None] * n
+        for V in sorted({len(p) for p in per}):
+            members = [i for i in range(n) if len(per[i]) == V]
+            ims = [images[i] for i in members]
+            plan = plan_views([im.shape[:2] for im in ims], [per[i] for i in members], cfg.input_size,
+                              letterbox=bool(getattr(cfg, 'letterbox', False)), forbid_resize=bool(getattr(cfg, 'forbid_resize', False)))
+            canvases, xf = render_views(ims, plan, cfg.input_size, cfg.device, mean, std)
+            cnt, cls, sc, bx, idx = (t.cpu().numpy() for t in self.detect_views_device(canvases, V, xf))
+            for b, i in enumerate(members):
+                k = int(cnt[b])
+                m = {'orig_size': np.array(tuple(ims[b].shape[:2]) + (3,), np.int32), 'index': i,
+                     'image_id': image_ids[i] if image_ids is not None else str(i),
+                     'view_windows': plan.windows[b * V:(b + 1) * V].copy()}
+                if k == 0:
+                    results[i] = {'image_meta': m}
+                    continue
+                p = idx[b, :k].astype(np.int64)
+                results[i] = {'class_ids': cls[b, :k].copy(), 'scores': sc[b, :k].copy(), 'boxes': bx[b, :k].copy(),
+                              'anchor_idx': p % A, 'view_idx': p // A, 'image_meta': m}
+        return results
+
+    @torch.no_grad()
     def detect(self, batch):
         image = batch['image']
         B = image.shape[0]
@@ -103,12 +158,18 @@ class Detector(object):
         return results
 
     @torch.no_grad()
-    def detect_images(self, images, image_ids=None, rgb_mean=None, rgb_std=None):
+    def detect_images(self, images, image_ids=None, rgb_mean=None, rgb_std=None, views=None):
         """Raw path: list of uint8 HWC RGB images (any sizes) -> detections in original-image coordinates.
         Upload of the uint8 pixels, GPU pre-processing (whiten + resize -- or, with ``cfg.forbid_resize``, whiten + crop_or_pad; with
         ``cfg.letterbox``, whiten + aspect-preserving resize into a zero canvas -- + CHW), backbone, fused detection with the per-image
         scale division (or un-pad / un-crop shift; letterbox: both), one compact D2H copy.  Boxes are not clamped to the original image.
-        ``rgb_mean`` / ``rgb_std``: the dataset's whitening statistics (default: ``cfg.rgb_mean`` / ``cfg.rgb_std``, else KITTI's)."""
+        ``rgb_mean`` / ``rgb_std``: the dataset's whitening statistics (default: ``cfg.rgb_mean`` / ``cfg.rgb_std``, else KITTI's).
+        ``views`` (DESIGN.md section 3 "Pooled views"; default: ``cfg.tta_flip`` / ``cfg.tta_zooms``, else None = exactly the launches
+        above): a list of ``views.View`` for every image (``views.tta_views``), or one list per image (``views.tile_views`` of each frame).
+        Every image then runs as V network views -- one upload with each image's pixels stored once, ONE mosaic input launch, the backbone
+        on B*V rows, ONE pooled detect (one top-k and one NMS per image over the candidates of all its views, in original-image
+        coordinates), one D2H copy; images with different view counts run as one such pass per count.  The results then carry
+        ``'view_idx'`` next to ``'anchor_idx'`` (the anchor within the view).  Not available with ``cfg.forbid_resize``."""
         from .preprocess import preprocess_batch
         cfg = self.cfg
         mean = rgb_mean if rgb_mean is not None else getattr(cfg, 'rgb_mean', None)
@@ -116,6 +177,10 @@ class Detector(object):
         kw = {} if mean is None or std is None else {'rgb_mean': np.asarray(mean).reshape(-1), 'rgb_std': np.asarray(std).reshape(-1)}
         forbid = bool(getattr(cfg, 'forbid_resize', False))
         letterbox = bool(getattr(cfg, 'letterbox', False))
+        if views is None:
+            views = self._default_views()
+        if views is not None:
+            return self._detect_images_views(images, image_ids, kw, views)
         image, aux, meta = preprocess_batch(images, cfg.input_size, device=cfg.device, forbid_resize=forbid, letterbox=letterbox, **kw)
         if letterbox:
             dets = self.detect_device(image, scales=aux[0], shifts=aux[1])
@@ -143,6 +208,7 @@ class Detector(object):
         captured hipGraph of preprocess -> backbone -> fused detect; uint8 upload on a copy stream, ONE packed result copy per
         batch into pinned memory, results handed out late.  ``cfg.inflight`` (default 2) is the default lane count."""
         from .lanes import DetectStream
+        self._no_pooled_lanes('Detector.stream')
         lanes = int(lanes if lanes is not None else getattr(self.cfg, 'inflight', 2))
         key = (lanes, bool(graph), None if rgb_mean is None else tuple(np.asarray(rgb_mean, np.float32).reshape(-1).tolist()),
                None if rgb_std is None else tuple(np.asarray(rgb_std, np.float32).reshape(-1).tolist()),
@@ -160,6 +226,7 @@ class Detector(object):
         """Generator: an iterable of batches (lists of uint8 HWC RGB images of any sizes, or ``(images, image_ids)`` pairs) -> per
         batch, in order, the list of per-image result dicts ``detect_images`` would return -- bit for bit -- while the batches
         overlap on the device (see ``stream``).  Results trail the input by up to ``2 * lanes - 1`` batches."""
+        self._no_pooled_lanes('Detector.detect_stream')
         ex = self.stream(lanes=lanes, rgb_mean=rgb_mean, rgb_std=rgb_std)
         if ex.pending():
             raise RuntimeError('detect_stream: the detector\'s stream still holds un-fetched batches')
@@ -174,6 +241,7 @@ class Detector(object):
         are not uint8-representable (a dataset that hands out pre-whitened floats) take the reference's own route instead:
         ``dataset.preprocess`` on the host, then ``detect``.  Same printed lines and the same result dicts
         (``image_meta['index']`` = dataset index) as the reference; identical, bit for bit, to ``detect_images`` batch by batch."""
+        self._no_pooled_lanes('Detector.detect_dataset')
         cfg = self.cfg
         n = len(dataset)
         bs = max(1, int(getattr(cfg, 'batch_size', 1)))

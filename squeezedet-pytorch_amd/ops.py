@@ -1050,6 +1050,57 @@ def detect_nms(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh
     return bufs[:5]
 
 
+DET_VIEWS_MAX_ROW = 1 << 20    # key words of one pooled row, V * ceil4(A): the wide select's row limit
+
+
+def detect_views(pred, anchors, input_size, num_classes, V, view_xf, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, out=None,
+                 nms_mode='hard', nms_sigma=0.5, nms_agnostic=False):
+    """Pooled-view fused detect (DESIGN.md section 3 "Pooled views"): ``pred`` [B*V, A, C+5] holds ``V`` network views of each of B
+    images (view v of image b = row b*V + v), ``view_xf`` fp32 [B*V, 6] = (sy, sx, dy, dx, flip, mirror) maps a row's canvas boxes
+    into its image -- ``x / sx + dx``, ``y / sy + dy``, then, where ``flip`` != 0, ``(x1, x2) <- (mirror - x2, mirror - x1)`` -- and the
+    candidates of an image's views meet in ONE top-``keep_top_k`` (score descending, ties to the lower view, then the lower anchor)
+    and ONE suppression (the rule of ``detect_nms``) on the image-coordinate boxes.  Returns (count int32 [B], class_ids int64 [B,K],
+    scores [B,K], boxes [B,K,4] in image coordinates, pooled_idx int32 [B,K] = v * A + anchor).  ``out``: the five result tensors
+    (checked against B and ``keep_top_k``) and optionally a workspace of ``det_workspace_words_wide(B*V, A, keep_top_k)`` int32.
+    ``V`` = 1 with ``view_xf`` = (1, 1, 0, 0, 0, 0) equals ``detect_nms`` bit for bit.  Limits: ``V * ceil4(A) <= 2^20``, K <= 1024,
+    1 <= ``num_classes`` <= 256."""
+    mode, sigma, agnostic = nms_mode_index('detect_views', nms_mode, nms_sigma, nms_agnostic)
+    if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
+        raise ValueError(f'detect_views: bad pred {tuple(pred.shape)}')
+    head_path(num_classes)
+    _check_score_thresh('detect_views', score_thresh)
+    if isinstance(V, bool) or not hasattr(V, '__index__') or int(V) < 1:
+        raise ValueError(f'detect_views: V must be an int >= 1, got {V!r}')
+    V = int(V)
+    pred = pred.contiguous()
+    rows, A, _ = pred.shape
+    if rows < V or rows % V:
+        raise ValueError(f'detect_views: pred has {rows} rows, not a positive multiple of V = {V}')
+    B, K = rows // V, int(keep_top_k)
+    detect_path(K, A)                                      # ValueError naming the limit, before anything is allocated or written
+    if V * (-(-A // 4) * 4) > DET_VIEWS_MAX_ROW:
+        raise ValueError(f'detect_views: {V} views of {A} anchors exceed the pooled row limit V * ceil4(A) <= {DET_VIEWS_MAX_ROW} (2^20)')
+    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
+        raise ValueError('detect_views: anchors must be fp32 [A,4] on the same device')
+    if not isinstance(view_xf, torch.Tensor) or tuple(view_xf.shape) != (rows, 6) or view_xf.dtype != torch.float32 \
+            or view_xf.device != pred.device or not view_xf.is_contiguous():
+        raise ValueError('detect_views: view_xf must be contiguous fp32 [B*V,6] (sy, sx, dy, dx, flip, mirror) on the same device')
+    if out is not None:
+        _check_det_out(out, B, K, pred.device)
+    bufs = tuple(out) if out is not None else _det_buffers(B, K, pred.device)
+    keys = _wide_workspace('detect_views', bufs, rows, A, K, pred.device)
+    cnt, cls, sc, bx, idx = bufs[:5]
+    br = _Bracket('detect', f'detect_views V{V} A{A} K{K}', 0.0, 4.0 * rows * A * (num_classes + 5)) if timing._timer is not None else None
+    rc = nat.lib().sqd_detect_views_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(view_xf), nat.ptr(keys), nat.ptr(cnt),
+                                        nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, V, A, num_classes,
+                                        int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
+                                        keys.numel(), mode, sigma, agnostic, nat.stream_handle(pred.device))
+    nat.check(rc, 'sqd_detect_views_fwd')
+    if br is not None:
+        br.done()
+    return bufs[:5]
+
+
 def filter_dense_nms(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, out=None,
                      nms_mode='hard', nms_sigma=0.5, nms_agnostic=False):
     """``filter_dense_wide`` / ``filter_dense_many`` with the suppression rule of ``detect_nms``.  ``out``: the five result tensors
