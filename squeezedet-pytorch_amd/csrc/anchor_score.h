@@ -1,4 +1,4 @@
-// Per-anchor score of the detection head, shared by the post-processing kernels (postproc.hip) and by ConvDet's key-writing
+// Per-anchor score of the detection head, shared by the post-processing kernels (postproc.hip, detect_wide.hip) and by ConvDet's key-writing
 // epilogue (conv_wino_vs.hip): both must produce the same bits, so there is one copy of the arithmetic.  Every translation unit
 // that includes this is built with -ffp-contract=off and IEEE division (the Makefile's common flags): the expressions mirror the
 // fp32 reference op for op.

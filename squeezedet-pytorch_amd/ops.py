@@ -841,6 +841,70 @@ def _check_det_out(bufs, B, K, device):
         raise ValueError('detect: out[3] (boxes) must be 16-byte aligned')
 
 
+def _pred_side(name, pred, anchors, num_classes, score_thresh, K=None, scales=None, shifts=None, many=False, V=None):
+    """The pred-side argument block of every fused detect, in the order all of them check: pred, the class count (``many``: the
+    functions that take up to 256), ``score_thresh``, the view count (``V`` given: pred holds V rows per image), the wide limits
+    (``K`` given: ValueError naming the limit, before anything is allocated or written), anchors, scales, shifts.
+    -> (contiguous pred, B, A)."""
+    if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
+        raise ValueError(f'{name}: bad pred {tuple(pred.shape)}')
+    if many:
+        head_path(num_classes)
+    _check_score_thresh(name, score_thresh)
+    if V is not None and (isinstance(V, bool) or not hasattr(V, '__index__') or int(V) < 1):
+        raise ValueError(f'{name}: V must be an int >= 1, got {V!r}')
+    pred = pred.contiguous()
+    B, A, _ = pred.shape
+    if V is not None:
+        if B < int(V) or B % int(V):
+            raise ValueError(f'{name}: pred has {B} rows, not a positive multiple of V = {int(V)}')
+        B //= int(V)
+    if K is not None:
+        detect_path(K, A)
+    if V is not None and int(V) * (-(-A // 4) * 4) > DET_VIEWS_MAX_ROW:
+        raise ValueError(f'{name}: {int(V)} views of {A} anchors exceed the pooled row limit V * ceil4(A) <= {DET_VIEWS_MAX_ROW} (2^20)')
+    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
+        raise ValueError(f'{name}: anchors must be fp32 [A,4] on the same device')
+    if scales is not None and (tuple(scales.shape) != (B, 2) or scales.dtype != torch.float32 or scales.device != pred.device):
+        raise ValueError(f'{name}: scales must be fp32 [B,2] (sy, sx)')
+    if shifts is not None and (tuple(shifts.shape) != (B, 2) or shifts.dtype != torch.float32 or shifts.device != pred.device or not shifts.is_contiguous()):
+        raise ValueError(f'{name}: shifts must be contiguous fp32 [B,2] (dy, dx)')
+    return pred, B, A
+
+
+def _dense_side(name, class_ids, scores, boxes, num_classes, score_thresh, K=None, many=False):
+    """The dense-side argument block of every filter (class_ids int64 [B,A], scores [B,A], boxes [B,A,4]), then the class count
+    (``many``), ``score_thresh`` and the wide limits (``K`` given).  -> (B, A)."""
+    if scores.dim() != 2 or class_ids.shape != scores.shape or tuple(boxes.shape) != tuple(scores.shape) + (4,):
+        raise ValueError(f'{name}: shape mismatch')
+    if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda \
+            or class_ids.device != scores.device or boxes.device != scores.device:
+        raise ValueError(f'{name}: dtype/device mismatch')
+    if many:
+        head_path(num_classes)
+    _check_score_thresh(name, score_thresh)
+    B, A = scores.shape
+    if K is not None:
+        detect_path(K, A)
+    return B, A
+
+
+def _wide_out(name, out, B, A, K, device, rows=None):
+    """Result buffers and key workspace of a wide launch: the caller's ``out`` (checked against B and K) or fresh tensors; the
+    workspace -- ``rows`` (default B) key rows -- is the caller's sixth ``out`` tensor if it is large enough, else a fresh one.
+    -> (bufs, keys)."""
+    if out is not None:
+        _check_det_out(out, B, K, device)
+    bufs = tuple(out) if out is not None else _det_buffers(B, K, device)
+    need = det_workspace_words_wide(B if rows is None else rows, A, K)
+    keys = bufs[5] if len(bufs) == 6 else None
+    if keys is not None and (not isinstance(keys, torch.Tensor) or keys.dtype != torch.int32 or keys.device != device):
+        raise ValueError(f'{name}: workspace must be an int32 tensor on the same device')
+    if keys is None or keys.numel() < need or not keys.is_contiguous() or keys.data_ptr() % 16:
+        keys = torch.empty(need, device=device, dtype=torch.int32)
+    return bufs, keys
+
+
 def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None,
            keys_ready=False):
     """Fused decode + top-k + class-wise NMS + threshold for a batch.  ``keys_ready``: the workspace in ``out`` already holds the keys
@@ -850,17 +914,7 @@ def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4
     ``boxes_postprocess``, src/utils/boxes.py:149-155).  ``out``: the five result tensors (checked against B and ``keep_top_k``) and
     optionally the key workspace; a workspace smaller than ``det_workspace_words`` means one workgroup per image.
     ``score_thresh`` must be >= 0."""
-    if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
-        raise ValueError(f'detect: bad pred {tuple(pred.shape)}')
-    _check_score_thresh('detect', score_thresh)
-    pred = pred.contiguous()
-    B, A, _ = pred.shape
-    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
-        raise ValueError('detect: anchors must be fp32 [A,4] on the same device')
-    if scales is not None and (tuple(scales.shape) != (B, 2) or scales.dtype != torch.float32 or scales.device != pred.device):
-        raise ValueError('detect: scales must be fp32 [B,2] (sy, sx)')
-    if shifts is not None and (tuple(shifts.shape) != (B, 2) or shifts.dtype != torch.float32 or shifts.device != pred.device or not shifts.is_contiguous()):
-        raise ValueError('detect: shifts must be contiguous fp32 [B,2] (dy, dx)')
+    pred, B, A = _pred_side('detect', pred, anchors, num_classes, score_thresh, scales=scales, shifts=shifts)
     if out is not None:
         _check_det_out(out, B, int(keep_top_k), pred.device)
     bufs = out if out is not None else _det_buffers(B, keep_top_k, pred.device, A)
@@ -887,13 +941,7 @@ def detect(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4
 
 def filter_dense(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3):
     """``Detector.filter`` on already decoded dense tensors ([B,A] / [B,A,4]).  ``score_thresh`` must be >= 0."""
-    if scores.dim() != 2 or class_ids.shape != scores.shape or tuple(boxes.shape) != tuple(scores.shape) + (4,):
-        raise ValueError('filter: shape mismatch')
-    if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda \
-            or class_ids.device != scores.device or boxes.device != scores.device:
-        raise ValueError('filter: dtype/device mismatch')
-    _check_score_thresh('filter', score_thresh)
-    B, A = scores.shape
+    B, A = _dense_side('filter', class_ids, scores, boxes, num_classes, score_thresh)
     bufs = _det_buffers(B, keep_top_k, scores.device, A)
     cnt, cls, sc, bx, idx, keys = bufs
     rc = nat.lib().sqd_filter_fwd(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
@@ -901,17 +949,6 @@ def filter_dense(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thres
                                   int(keep_top_k), float(nms_thresh), float(score_thresh), nat.stream_handle(scores.device))
     nat.check(rc, 'sqd_filter_fwd')
     return bufs[:5]
-
-
-def _wide_workspace(name, bufs, B, A, K, device):
-    """The key workspace of a wide launch: the caller's sixth ``out`` tensor if it is large enough, else a fresh one."""
-    need = det_workspace_words_wide(B, A, K)
-    keys = bufs[5] if len(bufs) == 6 else None
-    if keys is not None and (not isinstance(keys, torch.Tensor) or keys.dtype != torch.int32 or keys.device != device):
-        raise ValueError(f'{name}: workspace must be an int32 tensor on the same device')
-    if keys is None or keys.numel() < need or not keys.is_contiguous() or keys.data_ptr() % 16:
-        keys = torch.empty(need, device=device, dtype=torch.int32)
-    return keys
 
 
 def detect_wide(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None):
@@ -922,23 +959,9 @@ def detect_wide(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thres
 
 
 def _detect_wide(_entry, pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None):
-    if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
-        raise ValueError(f'detect_wide: bad pred {tuple(pred.shape)}')
-    _check_score_thresh('detect_wide', score_thresh)
-    pred = pred.contiguous()
-    B, A, _ = pred.shape
+    pred, B, A = _pred_side('detect_wide', pred, anchors, num_classes, score_thresh, keep_top_k, scales, shifts)
     K = int(keep_top_k)
-    detect_path(K, A)                                      # ValueError naming the limit, before anything is allocated or written
-    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
-        raise ValueError('detect_wide: anchors must be fp32 [A,4] on the same device')
-    if scales is not None and (tuple(scales.shape) != (B, 2) or scales.dtype != torch.float32 or scales.device != pred.device):
-        raise ValueError('detect_wide: scales must be fp32 [B,2] (sy, sx)')
-    if shifts is not None and (tuple(shifts.shape) != (B, 2) or shifts.dtype != torch.float32 or shifts.device != pred.device or not shifts.is_contiguous()):
-        raise ValueError('detect_wide: shifts must be contiguous fp32 [B,2] (dy, dx)')
-    if out is not None:
-        _check_det_out(out, B, K, pred.device)
-    bufs = tuple(out) if out is not None else _det_buffers(B, K, pred.device)
-    keys = _wide_workspace('detect_wide', bufs, B, A, K, pred.device)
+    bufs, keys = _wide_out('detect_wide', out, B, A, K, pred.device)
     cnt, cls, sc, bx, idx = bufs[:5]
     br = _Bracket('detect', f'{_entry[4:-4]} A{A} K{K}', 0.0, 4.0 * B * A * (num_classes + 5)) if timing._timer is not None else None
     rc = getattr(nat.lib(), _entry)(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
@@ -964,17 +987,9 @@ def filter_dense_wide(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_
 
 
 def _filter_dense_wide(_entry, class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3):
-    if scores.dim() != 2 or class_ids.shape != scores.shape or tuple(boxes.shape) != tuple(scores.shape) + (4,):
-        raise ValueError('filter_wide: shape mismatch')
-    if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda \
-            or class_ids.device != scores.device or boxes.device != scores.device:
-        raise ValueError('filter_wide: dtype/device mismatch')
-    _check_score_thresh('filter_wide', score_thresh)
-    B, A = scores.shape
+    B, A = _dense_side('filter_wide', class_ids, scores, boxes, num_classes, score_thresh, keep_top_k)
     K = int(keep_top_k)
-    detect_path(K, A)
-    bufs = _det_buffers(B, K, scores.device)
-    keys = _wide_workspace('filter_wide', bufs, B, A, K, scores.device)
+    bufs, keys = _wide_out('filter_wide', None, B, A, K, scores.device)
     cnt, cls, sc, bx, idx = bufs
     rc = getattr(nat.lib(), _entry)(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
                                     nat.ptr(keys), nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
@@ -1018,24 +1033,9 @@ def detect_nms(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh
     ``detect_many`` bit for bit.  ``keys_ready`` (<= 16 classes): the workspace in ``out`` already holds the keys of this ``pred`` for
     this ``score_thresh`` (``DetKeys``) -- no scoring launch."""
     mode, sigma, agnostic = nms_mode_index('detect_nms', nms_mode, nms_sigma, nms_agnostic)
-    if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
-        raise ValueError(f'detect_nms: bad pred {tuple(pred.shape)}')
-    head_path(num_classes)
-    _check_score_thresh('detect_nms', score_thresh)
-    pred = pred.contiguous()
-    B, A, _ = pred.shape
+    pred, B, A = _pred_side('detect_nms', pred, anchors, num_classes, score_thresh, keep_top_k, scales, shifts, many=True)
     K = int(keep_top_k)
-    detect_path(K, A)                                      # ValueError naming the limit, before anything is allocated or written
-    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
-        raise ValueError('detect_nms: anchors must be fp32 [A,4] on the same device')
-    if scales is not None and (tuple(scales.shape) != (B, 2) or scales.dtype != torch.float32 or scales.device != pred.device):
-        raise ValueError('detect_nms: scales must be fp32 [B,2] (sy, sx)')
-    if shifts is not None and (tuple(shifts.shape) != (B, 2) or shifts.dtype != torch.float32 or shifts.device != pred.device or not shifts.is_contiguous()):
-        raise ValueError('detect_nms: shifts must be contiguous fp32 [B,2] (dy, dx)')
-    if out is not None:
-        _check_det_out(out, B, K, pred.device)
-    bufs = tuple(out) if out is not None else _det_buffers(B, K, pred.device)
-    keys = _wide_workspace('detect_nms', bufs, B, A, K, pred.device)
+    bufs, keys = _wide_out('detect_nms', out, B, A, K, pred.device)
     if keys_ready and (len(bufs) != 6 or keys is not bufs[5] or head_path(num_classes) != 'narrow'):
         raise ValueError('detect_nms: keys_ready needs the 16-byte aligned workspace the keys were written to (<= 16 classes)')
     cnt, cls, sc, bx, idx = bufs[:5]
@@ -1065,30 +1065,12 @@ def detect_views(pred, anchors, input_size, num_classes, V, view_xf, keep_top_k=
     ``V`` = 1 with ``view_xf`` = (1, 1, 0, 0, 0, 0) equals ``detect_nms`` bit for bit.  Limits: ``V * ceil4(A) <= 2^20``, K <= 1024,
     1 <= ``num_classes`` <= 256."""
     mode, sigma, agnostic = nms_mode_index('detect_views', nms_mode, nms_sigma, nms_agnostic)
-    if pred.dim() != 3 or pred.shape[2] != num_classes + 5 or pred.dtype != torch.float32 or not pred.is_cuda:
-        raise ValueError(f'detect_views: bad pred {tuple(pred.shape)}')
-    head_path(num_classes)
-    _check_score_thresh('detect_views', score_thresh)
-    if isinstance(V, bool) or not hasattr(V, '__index__') or int(V) < 1:
-        raise ValueError(f'detect_views: V must be an int >= 1, got {V!r}')
-    V = int(V)
-    pred = pred.contiguous()
-    rows, A, _ = pred.shape
-    if rows < V or rows % V:
-        raise ValueError(f'detect_views: pred has {rows} rows, not a positive multiple of V = {V}')
-    B, K = rows // V, int(keep_top_k)
-    detect_path(K, A)                                      # ValueError naming the limit, before anything is allocated or written
-    if V * (-(-A // 4) * 4) > DET_VIEWS_MAX_ROW:
-        raise ValueError(f'detect_views: {V} views of {A} anchors exceed the pooled row limit V * ceil4(A) <= {DET_VIEWS_MAX_ROW} (2^20)')
-    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != pred.device:
-        raise ValueError('detect_views: anchors must be fp32 [A,4] on the same device')
+    pred, B, A = _pred_side('detect_views', pred, anchors, num_classes, score_thresh, keep_top_k, many=True, V=V)
+    V, K, rows = int(V), int(keep_top_k), pred.shape[0]
     if not isinstance(view_xf, torch.Tensor) or tuple(view_xf.shape) != (rows, 6) or view_xf.dtype != torch.float32 \
             or view_xf.device != pred.device or not view_xf.is_contiguous():
         raise ValueError('detect_views: view_xf must be contiguous fp32 [B*V,6] (sy, sx, dy, dx, flip, mirror) on the same device')
-    if out is not None:
-        _check_det_out(out, B, K, pred.device)
-    bufs = tuple(out) if out is not None else _det_buffers(B, K, pred.device)
-    keys = _wide_workspace('detect_views', bufs, rows, A, K, pred.device)
+    bufs, keys = _wide_out('detect_views', out, B, A, K, pred.device, rows=rows)
     cnt, cls, sc, bx, idx = bufs[:5]
     br = _Bracket('detect', f'detect_views V{V} A{A} K{K}', 0.0, 4.0 * rows * A * (num_classes + 5)) if timing._timer is not None else None
     rc = nat.lib().sqd_detect_views_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(view_xf), nat.ptr(keys), nat.ptr(cnt),
@@ -1106,20 +1088,9 @@ def filter_dense_nms(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_t
     """``filter_dense_wide`` / ``filter_dense_many`` with the suppression rule of ``detect_nms``.  ``out``: the five result tensors
     (checked against B and ``keep_top_k``) and optionally a workspace of ``det_workspace_words_wide`` int32."""
     mode, sigma, agnostic = nms_mode_index('filter_nms', nms_mode, nms_sigma, nms_agnostic)
-    if scores.dim() != 2 or class_ids.shape != scores.shape or tuple(boxes.shape) != tuple(scores.shape) + (4,):
-        raise ValueError('filter_nms: shape mismatch')
-    if class_ids.dtype != torch.int64 or scores.dtype != torch.float32 or boxes.dtype != torch.float32 or not scores.is_cuda \
-            or class_ids.device != scores.device or boxes.device != scores.device:
-        raise ValueError('filter_nms: dtype/device mismatch')
-    head_path(num_classes)
-    _check_score_thresh('filter_nms', score_thresh)
-    B, A = scores.shape
+    B, A = _dense_side('filter_nms', class_ids, scores, boxes, num_classes, score_thresh, keep_top_k, many=True)
     K = int(keep_top_k)
-    detect_path(K, A)
-    if out is not None:
-        _check_det_out(out, B, K, scores.device)
-    bufs = tuple(out) if out is not None else _det_buffers(B, K, scores.device)
-    keys = _wide_workspace('filter_nms', bufs, B, A, K, scores.device)
+    bufs, keys = _wide_out('filter_nms', out, B, A, K, scores.device)
     cnt, cls, sc, bx, idx = bufs[:5]
     rc = nat.lib().sqd_filter_nms_fwd(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
                                       nat.ptr(keys), nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,

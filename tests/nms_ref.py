@@ -1,4 +1,4 @@
-"""Plain-numpy reference of the NMS modes ("NMS modes"; csrc/postproc.hip ``detect_nms_select_kernel``).
+"""Plain-numpy reference of the NMS modes ("NMS modes"; csrc/detect_wide.hip ``detect_nms_select_kernel``).
 
 ``soft_filter``: the rule for one image in fp32, op for op -- the candidates (top K of the anchors with score > score_thresh, score
 descending, ties by lower anchor index), the groups (classes 0 .. C-1, or one group with ``agnostic``), and within a group: pick the

@@ -1,4 +1,4 @@
-"""The wide fused detect (csrc/postproc.hip ``detect_wide_score_kernel`` + ``detect_wide_select_kernel``: 1 <= K <= 1024, up to 2^20
+"""The wide fused detect (csrc/detect_wide.hip ``detect_wide_score_kernel`` + ``detect_wide_select_kernel``: 1 <= K <= 1024, up to 2^20
 anchors) against ``oracle.filter_detections``, and every layer above it: ``ops.detect_wide`` / ``ops.filter_dense_wide``, the
 ``Detector`` entry points that choose the path with ``ops.detect_path``, and the lane executor.
 

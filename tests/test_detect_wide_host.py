@@ -1,4 +1,4 @@
-"""CPU tier: the wide fused detect's host side (csrc/postproc.hip ``sqd_detect_wide_fwd`` / ``sqd_filter_wide_fwd`` /
+"""CPU tier: the wide fused detect's host side (csrc/detect_wide.hip ``sqd_detect_wide_fwd`` / ``sqd_filter_wide_fwd`` /
 ``sqd_detect_wide_workspace_words``, ``ops.detect_path``).  Every refusal is decided before any launch, so the status codes can be
 exercised without a GPU: the pointers handed in are host buffers that a refused call never touches."""
 import ctypes
@@ -77,6 +77,73 @@ def test_filter_wide_status_codes():
     assert f(*_filter_args(A=A_MAX + 1)) == 2
     assert f(*_filter_args(C=17)) == 2
     assert f(*_filter_args(A=101, ws_words=103)) == 1
+
+
+WIDE_ENTRIES = ('sqd_detect_wide_fwd', 'sqd_filter_wide_fwd', 'sqd_detect_many_fwd', 'sqd_filter_many_fwd', 'sqd_detect_nms_fwd',
+                'sqd_filter_nms_fwd', 'sqd_detect_views_fwd')
+
+# two faults in one call: which of them the entry point reports.  `mode` exists for the rule-taking entry points only, `ready`
+# (keys_ready) for the two nms ones, V for the views one; a fault an entry point cannot express is not in its row below.
+DOUBLE_FAULTS = {
+    'K limit + short workspace': dict(K=1025, ws_words=0),
+    'A limit + short workspace': dict(A=A_MAX + 1, ws_words=0),
+    'class limit + short workspace': dict(C=257, ws_words=0),
+    'K limit + bad mode': dict(K=1025, mode=3),
+    'K limit + negative score_thresh': dict(K=1025, thr=-0.1),
+    'null pointer + K limit': dict(null=True, K=1025),
+    'null pointer + short workspace': dict(null=True, ws_words=0),
+    'keys_ready + 17 classes': dict(ready=1, C=17),
+    'keys_ready + class limit': dict(ready=1, C=257),
+    'keys_ready + short workspace': dict(ready=1, ws_words=0),
+    'V = 0 + K = 1025': dict(V=0, K=1025),
+    'pooled row limit + short workspace': dict(V=1 << 18, A=5, ws_words=0),
+}
+
+
+def _double_fault_call(lib, entry, B=1, A=100, C=3, K=64, V=2, ws_words=None, null=False, mode=None, thr=None, ready=None):
+    """The status of one call, or None where the entry point has no such argument."""
+    stream = ctypes.c_void_p(0)
+    views, rule, nms = entry == 'sqd_detect_views_fwd', entry in WIDE_ENTRIES[4:], entry.endswith('_nms_fwd')
+    if ((mode is not None or thr is not None) and not rule) or (ready is not None and not nms) or (V != 2 and not views):
+        return None
+    mode, thr, ready = mode or 0, 0.3 if thr is None else thr, ready or 0
+    first = ctypes.c_void_p(0) if null else _buf()
+    if views:
+        if ws_words is None:
+            ws_words = B * max(V, 1) * (-(-A // 4) * 4)
+        return lib.sqd_detect_views_fwd(first, *[_buf() for _ in range(8)], B, V, A, C, 384, 1248, K, 0.4, thr, ws_words, mode, 0.5, 0, stream)
+    args = (_filter_args if 'filter' in entry else _detect_args)(B, A, C, K, ws_words)
+    args[0] = first
+    args[-3] = thr
+    if nms:
+        args = args[:-1] + [mode, 0.5, 0, ready, stream]
+    return getattr(lib, entry)(*args)
+
+
+def _double_fault_statuses(lib):
+    return {e: {name: s for name, kw in DOUBLE_FAULTS.items() if (s := _double_fault_call(lib, e, **kw)) is not None} for e in WIDE_ENTRIES}
+
+
+# recorded from the library before the family moved behind one launcher (csrc/detect_wide.hip: launch_wide), by this very table
+_BIT_MATRIX_ROW = {'K limit + short workspace': 2, 'A limit + short workspace': 2, 'class limit + short workspace': 2,
+                   'null pointer + K limit': 1, 'null pointer + short workspace': 1}
+_RULE_ROW = dict(_BIT_MATRIX_ROW, **{'K limit + bad mode': 1, 'K limit + negative score_thresh': 1})
+DOUBLE_FAULT_STATUS = {
+    'sqd_detect_wide_fwd': _BIT_MATRIX_ROW, 'sqd_filter_wide_fwd': _BIT_MATRIX_ROW,
+    'sqd_detect_many_fwd': _BIT_MATRIX_ROW, 'sqd_filter_many_fwd': _BIT_MATRIX_ROW,
+    'sqd_detect_nms_fwd': dict(_RULE_ROW, **{'keys_ready + 17 classes': 1, 'keys_ready + class limit': 2, 'keys_ready + short workspace': 1}),
+    'sqd_filter_nms_fwd': dict(_RULE_ROW, **{'keys_ready + 17 classes': 1, 'keys_ready + class limit': 1, 'keys_ready + short workspace': 1}),
+    'sqd_detect_views_fwd': dict(_RULE_ROW, **{'V = 0 + K = 1025': 1, 'pooled row limit + short workspace': 2}),
+}
+
+
+def test_refusal_precedence_of_two_faults_at_once():
+    """Every wide-family entry point refuses a call with two faults with the status it always gave: a null pointer or a size below 1
+    (status 1) before a bad rule (1), before a limit (2), before the workspace (1), before keys_ready misuse (1).  Nothing is launched."""
+    got = _double_fault_statuses(nat.lib())
+    assert set(DOUBLE_FAULT_STATUS) == set(WIDE_ENTRIES) and all(len(v) >= 5 for v in DOUBLE_FAULT_STATUS.values())
+    for e in WIDE_ENTRIES:
+        assert got[e] == DOUBLE_FAULT_STATUS[e], e
 
 
 def test_wide_workspace_words():

@@ -1,4 +1,4 @@
-"""GPU tier: Soft-NMS (linear / Gaussian) and class-agnostic NMS in the fused detect launches (csrc/postproc.hip
+"""GPU tier: Soft-NMS (linear / Gaussian) and class-agnostic NMS in the fused detect launches (csrc/detect_wide.hip
 ``detect_nms_select_kernel``; ``ops.detect_nms`` / ``ops.filter_dense_nms``; ``cfg.nms_mode`` / ``nms_sigma`` / ``nms_agnostic``).
 
 What each mode is held to: 'hard' and 'linear' equal ``nms_ref.soft_filter`` bit for bit (count, class, anchor, score bits, boxes);
@@ -204,6 +204,38 @@ def test_from_pred_equals_the_dense_filter_on_the_decode(C):
                 sy, sx, dy, dx = s_h[b, 0], s_h[b, 1], t_h[b, 0], t_h[b, 1]
                 exp = np.stack([wb[:, 0] / sx + dx, wb[:, 1] / sy + dy, wb[:, 2] / sx + dx, wb[:, 3] / sy + dy], 1).astype(np.float32)
                 assert np.array_equal(_bits(got[3][b, :n]), _bits(exp)), (C, K, mode, agnostic, b)
+
+
+@pytest.mark.parametrize('A', (5, 6, 7))
+def test_keys_ready_reads_arbitrary_pad_words_as_zero(A):
+    """With ``keys_ready`` the words A .. ceil4(A)-1 of an image's key row hold whatever ConvDet's launch left there, and the select
+    reads them as 0 (3, 2 and 1 pad words here; every Detector-driven case has A divisible by 4).  The scoring launch of a first call
+    fills the workspace, the pad words are overwritten with the largest finite key, and a ``keys_ready`` call on that workspace must
+    give the first call's five tensors bit for bit.  Image 0 has A candidates (the radix select runs at both K), image 1 two (at K = 4
+    every candidate is taken).  ``pred`` and ``anchors`` are views of larger tensors: a select that took a pad word would decode a row
+    that exists, and fail here by mismatch."""
+    B, C, size = 2, 3, (64, 96)
+    rs = np.random.RandomState(40 + A)
+    store = (0.3 * rs.standard_normal((B + 1, A, C + 5))).astype(np.float32)
+    np.put_along_axis(store[..., :C], rs.randint(0, C, (B + 1, A, 1)), 6.0, axis=2)      # one peaked class per anchor
+    store[..., C] += 2.0                                                                  # every score above THR ...
+    store[1, 2:, C] = -6.0                                                                # ... but two candidates only in image 1
+    anc = np.concatenate([rs.uniform(30, 60, (A + 4, 1)), rs.uniform(20, 40, (A + 4, 3))], 1).astype(np.float32)
+    pred, anchors = torch.from_numpy(store).cuda()[:B], torch.from_numpy(anc).cuda()[:A]
+    A4 = -(-A // 4) * 4
+    for K in (1, 4):
+        for mode in ref.MODES:
+            ws = torch.zeros(ops.det_workspace_words_wide(B, A, K), device='cuda', dtype=torch.int32)
+            first = ops.detect_nms(pred, anchors, size, C, K, NMS, THR, out=ops._det_buffers(B, K, pred.device) + (ws,),
+                                   nms_mode=mode, nms_sigma=SIGMA)
+            keys = ws.view(B, A4)
+            assert (keys[:, :A] != 0).sum(1).tolist() == [A, 2] and not bool(keys[:, A:].any()), (A, K, mode)
+            assert first[0].tolist()[0] >= 1 and first[0].tolist()[1] >= 1, (A, K, mode)
+            keys[:, A:] = 0x7f7fffff
+            second = ops.detect_nms(pred, anchors, size, C, K, NMS, THR, out=ops._det_buffers(B, K, pred.device) + (ws,),
+                                    nms_mode=mode, nms_sigma=SIGMA, keys_ready=True)
+            for i, (f, s) in enumerate(zip(first, second)):
+                assert f.cpu().numpy().tobytes() == s.cpu().numpy().tobytes(), (A, K, mode, i)
 
 
 def _detector(K=64, **kw):

@@ -1,4 +1,4 @@
-"""Plain-numpy reference of the pooled-view detect (DESIGN.md section 3 "Pooled views"; csrc/postproc.hip ``detect_views_select_kernel``).
+"""Plain-numpy reference of the pooled-view detect (DESIGN.md section 3 "Pooled views"; csrc/detect_wide.hip ``detect_views_select_kernel``).
 No torch.
 
 ``map_boxes``: a view's canvas boxes in image coordinates, fp32 op for op -- ``x / sx + dx``, ``y / sy + dy`` (one division, one
