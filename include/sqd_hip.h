@@ -301,6 +301,31 @@ int sqd_detect_views_fwd(const float* pred, const float* anchors, const float* v
                          int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
                          int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, void* stream);
 
+/* Box voting (DESIGN.md section 3 "Box voting"; Gidaris & Komodakis 2015): sqd_detect_nms_fwd / sqd_filter_nms_fwd /
+ * sqd_detect_views_fwd with `float vote_iou, int* det_votes` before the stream.  The suppression is the sibling's, untouched: det_count,
+ * det_class, det_score and det_anchor are its rows bit for bit.  det_box of an emitted candidate i becomes the score-weighted mean of its
+ * voters V_i = { r among the image's <= keep_top_k candidates : class_r == class_i and (r == i or u(i, r) >= vote_iou) }, u = the fp32
+ * IoU expression of the suppression (a NaN u compares false), suppressed, decayed and emitted candidates alike: W = sum (double)s_r,
+ * X_k = sum (double)s_r * (double)box_r[k] in ascending rank with the ORIGINAL scores s_r, coordinate = (float)(X_k / W); the boxes are
+ * those the suppression compares (canvas boxes; image boxes in the pooled form), and the sibling's store follows (x / sx + dx from
+ * scales / shifts in sqd_detect_vote_fwd).  A row with one voter keeps the sibling's box bit for bit.  Under nms_agnostic only the row's
+ * own class votes.  det_votes: int32 [B][keep_top_k] = |V_i| per row, or NULL (not written).  vote_iou: finite, in (0, 1]; NaN, <= 0 or
+ * > 1 is status 1 (decided with the rule, before the limits); every other status as the sibling; nothing is launched on a refusal. */
+int sqd_detect_vote_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                        int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                        int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                        int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, float vote_iou,
+                        int* det_votes, void* stream);
+int sqd_filter_vote_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
+                        long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                        int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words,
+                        int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, float vote_iou, int* det_votes, void* stream);
+int sqd_detect_views_vote_fwd(const float* pred, const float* anchors, const float* view_xf, unsigned* keys_ws, int* det_count,
+                              long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int V, int A,
+                              int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                              int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, float vote_iou, int* det_votes,
+                              void* stream);
+
 /* GPU-side input pipeline: whiten + cv2.resize(INTER_LINEAR) + HWC->CHW of
  * DataWrapper.__getitem__ / BaseDataset.preprocess / whiten / resize (src/engine/detector.py:132-142,
  * src/datasets/base.py:43-59, src/utils/image.py:9-19,77-88) for a batch of uint8 RGB images of arbitrary sizes.

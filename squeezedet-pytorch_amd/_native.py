@@ -68,6 +68,9 @@ _SIGNATURES = {
     'sqd_detect_nms_fwd': [c_p] * 10 + [c_i] * 6 + [c_f, c_f, c_i, c_i, c_f, c_i, c_i, c_p],
     'sqd_filter_nms_fwd': [c_p] * 9 + [c_i] * 4 + [c_f, c_f, c_i, c_i, c_f, c_i, c_i, c_p],
     'sqd_detect_views_fwd': [c_p] * 9 + [c_i] * 7 + [c_f, c_f, c_i, c_i, c_f, c_i, c_p],
+    'sqd_detect_vote_fwd': [c_p] * 10 + [c_i] * 6 + [c_f, c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_p, c_p],
+    'sqd_filter_vote_fwd': [c_p] * 9 + [c_i] * 4 + [c_f, c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_p, c_p],
+    'sqd_detect_views_vote_fwd': [c_p] * 9 + [c_i] * 7 + [c_f, c_f, c_i, c_i, c_f, c_i, c_f, c_p, c_p],
     'sqd_preprocess_u8_fwd':[c_p] * 5 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],
     'sqd_preprocess_u8_padcrop_fwd': [c_p] * 6 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],
     'sqd_preprocess_u8_aug_fwd': [c_p] * 6 + [ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_i, c_i, c_i, c_p],

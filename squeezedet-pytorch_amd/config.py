@@ -125,6 +125,18 @@ def check_nms(cfg, who):
     return mode, float(sigma), bool(agnostic)
 
 
+def check_box_vote(cfg, who):
+    """``cfg.box_vote_iou`` (DESIGN.md section 3 "Box voting"): None -- or a cfg without the field -- means off; else a finite number in
+    (0, 1], not a bool: every detection's box becomes the score-weighted mean of the same-class candidates that overlap it by that IoU.
+    -> None or the float."""
+    v = getattr(cfg, 'box_vote_iou', None)
+    if v is None:
+        return None
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.floating, np.integer)) or not (np.isfinite(v) and 0 < v <= 1):
+        raise ValueError(f'{who}: box_vote_iou must be None or a finite number in (0, 1], got {v!r}')
+    return float(v)
+
+
 def check_tta(cfg, who):
     """The test-time augmentation of ``cfg`` (DESIGN.md section 3 "Pooled views"): (tta_flip, tta_zooms) -- ``tta_flip`` a bool,
     ``tta_zooms`` None or a non-empty sequence of finite zooms in (0, 16] -- and whether either is set.  A cfg without the fields means
@@ -174,6 +186,8 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
                                      # deleting it ("NMS modes"); nms_sigma: the Gaussian mode's width
         nms_sigma=0.5,
         nms_agnostic=False,          # True: one suppression group for all classes instead of one per class
+        box_vote_iou=None,           # None: off.  A float in (0, 1] (0.5 .. 0.8 are usual): box voting -- every kept box becomes the mean, weighted
+                                     # by score, of the same-class candidates overlapping it by that IoU ("Box voting")
         gpus=[0], chunk_sizes=[20], num_iters=-1, print_interval=10, debug=0, num_workers=4, forbid_resize=False,
         flip_prob=0.5, drift_prob=1., seed=42,      # training augmentation (train_data.TrainLoader), src/utils/config.py:53-56
         brightness_jitter=0., contrast_jitter=0., saturation_jitter=0.,      # colour jitter amounts (augment.draw_color); 0 = off
@@ -212,6 +226,7 @@ def make_cfg(arch='squeezedet', input_size=KITTI_INPUT_SIZE, anchors_seed=KITTI_
     check_mosaic(cfg, 'make_cfg')
     check_bbox_loss(cfg.bbox_loss, 'make_cfg')
     check_nms(cfg, 'make_cfg')
+    check_box_vote(cfg, 'make_cfg')
     check_match(cfg, 'make_cfg')
     check_tta(cfg, 'make_cfg')
     return cfg

@@ -16,7 +16,9 @@
 //        alive mask held one 64-bit word per lane and eight row loads in flight ahead of the alive tests, and every thread places its
 //        own survivor;
 //      * detect_nms_select_kernel<MANY>, any rule ("NMS modes" below), and detect_views_select_kernel<MANY>, the same on the pooled
-//        candidates of V views ("pooled views" below): the sequential scan of detn_scan_body.h.
+//        candidates of V views ("pooled views" below): the sequential scan of detn_scan_body.h;
+//      * detect_vote_select_kernel<MANY> and detect_views_vote_select_kernel<MANY>: those two with the voting step between the scan
+//        and the store ("box voting" below).
 // The select kernels keep the device code they always had: steps 1-4 and the scan are shared as included text, steered by
 // DETW_PAD_ANY / DETW_VIEWS / DETN_STORE.  As __forceinline__ functions they computed the same rows bit for bit, but every one of
 // them had a figure slower than the parent build's slowest repeat (profiles/detect_family_refactor_ab.json), so that form was kept back.
@@ -331,27 +333,31 @@ __device__ __forceinline__ float nms_decay(const NmsArgs n, float nms_thresh, co
   return s;
 }
 
+// the LDS arrays of a scan select kernel, carved from the launch's dynamic LDS in the order detn_scan_lds_bytes counts them
+#define DETN_SCAN_CARVE \
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[]; \
+  const int K = a.K, Kp = (K + 63) & ~63;                     /* Kp <= 1024: one candidate slot per thread */ \
+  unsigned long long* cand = (unsigned long long*)smem_raw;   /* [Kp] as detect_wide_select_kernel */ \
+  f32x4* boxL = (f32x4*)(cand + Kp);                          /* [Kp] boxes in rank order */ \
+  f32x4* boxP = boxL + Kp;                                    /* [Kp] boxes in (group, rank) order */ \
+  int* clsL = (int*)(boxP + Kp);                              /* [Kp] classes in rank order */ \
+  int* grpL = clsL + Kp;                                      /* [Kp] group of rank r, -1: none (no candidate, class outside 0 .. C-1) */ \
+  float* curL = (float*)(grpL + Kp);                          /* [Kp] current scores in (group, rank) order */ \
+  float* outS = curL + Kp;                                    /* [Kp] score at pick time */ \
+  int* emitL = (int*)(outS + Kp);                             /* [Kp] pick order within the group, -1: not emitted */ \
+  unsigned* hist = (unsigned*)(emitL + Kp);                   /* [256] */ \
+  unsigned* wave_tot = hist + 256;                            /* [16] */ \
+  unsigned* sv = wave_tot + 16;                               /* prefix, need, appended */ \
+  int* gstart = (int*)(sv + 4);                               /* [256] first slot of a group */ \
+  int* glen = gstart + 256;                                   /* [256] its candidates */ \
+  unsigned* gcnt = (unsigned*)(glen + 256);                   /* [256] its emitted rows */ \
+  unsigned* goff = gcnt + 256;                                /* [256] rows of the groups before it */ \
+  float* slot_s = (float*)(goff + 256);                       /* [2][16] a wave's best current score ... */ \
+  int* slot_p = (int*)(slot_s + 32);                          /* [2][16] ... and its slot */
+
 template <bool MANY>
 __global__ __launch_bounds__(DETW_THREADS) void detect_nms_select_kernel(DetArgs a, NmsArgs n) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int K = a.K, Kp = (K + 63) & ~63;                     // Kp <= 1024: one candidate slot per thread
-  unsigned long long* cand = (unsigned long long*)smem_raw;   // [Kp] as detect_wide_select_kernel
-  f32x4* boxL = (f32x4*)(cand + Kp);                          // [Kp] boxes in rank order
-  f32x4* boxP = boxL + Kp;                                    // [Kp] boxes in (group, rank) order
-  int* clsL = (int*)(boxP + Kp);                              // [Kp] classes in rank order
-  int* grpL = clsL + Kp;                                      // [Kp] group of rank r, -1: none (no candidate, class outside 0 .. C-1)
-  float* curL = (float*)(grpL + Kp);                          // [Kp] current scores in (group, rank) order
-  float* outS = curL + Kp;                                    // [Kp] score at pick time
-  int* emitL = (int*)(outS + Kp);                             // [Kp] pick order within the group, -1: not emitted
-  unsigned* hist = (unsigned*)(emitL + Kp);                   // [256]
-  unsigned* wave_tot = hist + 256;                            // [16]
-  unsigned* sv = wave_tot + 16;                               // prefix, need, appended
-  int* gstart = (int*)(sv + 4);                               // [256] first slot of a group
-  int* glen = gstart + 256;                                   // [256] its candidates
-  unsigned* gcnt = (unsigned*)(glen + 256);                   // [256] its emitted rows
-  unsigned* goff = gcnt + 256;                                // [256] rows of the groups before it
-  float* slot_s = (float*)(goff + 256);                       // [2][16] a wave's best current score ...
-  int* slot_p = (int*)(slot_s + 32);                          // [2][16] ... and its slot
+  DETN_SCAN_CARVE
 
 #define DETW_PAD_ANY true
 #include "detw_select_body.h"     // 1.-4. select, sweep, rank, decode: tid, lane, wave, b, A, C, ncand, ok, score, cls, idx, bx
@@ -410,25 +416,7 @@ __device__ __forceinline__ BoxF detv_map(BoxF c, const float* __restrict__ xf) {
 
 template <bool MANY>
 __global__ __launch_bounds__(DETW_THREADS) void detect_views_select_kernel(DetArgs a, NmsArgs n, ViewArgs vw) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int K = a.K, Kp = (K + 63) & ~63;                     // the layout of detect_nms_select_kernel
-  unsigned long long* cand = (unsigned long long*)smem_raw;
-  f32x4* boxL = (f32x4*)(cand + Kp);
-  f32x4* boxP = boxL + Kp;
-  int* clsL = (int*)(boxP + Kp);
-  int* grpL = clsL + Kp;
-  float* curL = (float*)(grpL + Kp);
-  float* outS = curL + Kp;
-  int* emitL = (int*)(outS + Kp);
-  unsigned* hist = (unsigned*)(emitL + Kp);
-  unsigned* wave_tot = hist + 256;
-  unsigned* sv = wave_tot + 16;
-  int* gstart = (int*)(sv + 4);
-  int* glen = gstart + 256;
-  unsigned* gcnt = (unsigned*)(glen + 256);
-  unsigned* goff = gcnt + 256;
-  float* slot_s = (float*)(goff + 256);
-  int* slot_p = (int*)(slot_s + 32);
+  DETN_SCAN_CARVE                                             // the layout of detect_nms_select_kernel
 
 #define DETW_PAD_ANY false
 #define DETW_VIEWS vw.V
@@ -439,6 +427,91 @@ __global__ __launch_bounds__(DETW_THREADS) void detect_views_select_kernel(DetAr
 #undef DETW_PAD_ANY
 #define DETN_STORE(pos, sc) DETV_STORE_ROW(a, b, K, pos, cls, sc, idx, bx)
 #include "detn_scan_body.h"       // 5.-7. (group, rank) order, the scan, the placement
+#undef DETN_STORE
+}
+
+// ---- box voting: an emitted box becomes the score-weighted mean of its cluster (DESIGN.md section 3 "Box voting") ----------------------
+// Gidaris & Komodakis 2015 / Detectron's bbox_vote, as a step between the scan and the store of the two scan select kernels.  The scan
+// is untouched: the emitted set, its order, det_count / det_class / det_score / det_anchor are those of the launch without voting.
+// For an emitted candidate i (rank order, c = class, s = ORIGINAL fp32 score, b = the box the scan took its IoUs on):
+//   voters V_i = { r : c_r == c_i and (r == i or u(i, r) >= vote_iou) },  u = nms_decay's fp32 expression, a NaN u compares false;
+//   (c_r == c_i with c_i in 0 .. C-1 makes r eligible -- grpL[r] >= 0 -- in either grouping, so grpL is not read; under nms_agnostic the
+//   classes still vote apart);  W = sum (double)s_r,  X_k = sum (double)s_r * (double)b_r[k]  over V_i in ascending r, in float64;
+//   voted coordinate = (float)(X_k / W).  Voters include suppressed, decayed and emitted candidates; weights are never the decayed scores.
+// A row nobody agreed with (|V_i| = 1) keeps its box bit for bit: (s * b) / s is exact in fp64 and b is an fp32 value.
+// All inputs are resident in LDS in rank order when the scan ends (boxL, clsL, the score bits in cand's upper half) and the scan wrote
+// none of them: the thread of every emitted candidate walks the ranks 0 .. ncand-1 -- the threads of a wave read the same rank at the same
+// time, LDS broadcasts -- and hands the voted box to the store the launch always did (DETW_STORE_ROW's x / sx + dx; the plain store of
+// the pooled launch).  No new global traffic but the optional det_votes [B][K] (|V_i| per row), no new launch, the LDS of the scan kernels.
+struct VoteArgs { float iou; int* votes; };
+
+// the voted box of the emitted candidate of rank i (class cls, box bx) -> bx; returns |V_i|
+__device__ __forceinline__ int detn_vote(const unsigned long long* cand, const f32x4* boxL, const int* clsL, int ncand, int i, int cls,
+                                         float vote_iou, BoxF& bx) {
+  const f32x4 pk = (f32x4){bx.x1, bx.y1, bx.x2, bx.y2};
+  const float pa = (pk.z - pk.x) * (pk.w - pk.y);
+  double W = 0.0, X0 = 0.0, X1 = 0.0, X2 = 0.0, X3 = 0.0;
+  int nv = 0;
+  // four ranks per trip: their IoUs are independent (the walk is bound by the latency of one LDS read and one division chain, not by
+  // their number), the sums then take the voters in ascending rank.  The ranks ncand .. Kp-1 a last trip may touch exist in LDS with
+  // class -1 (detw_select_body.h), so they never vote; Kp is a multiple of 64.
+  for (int r0 = 0; r0 < ncand; r0 += 4) {
+    f32x4 o[4];
+    bool in[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int r = r0 + e;
+      o[e] = boxL[r];
+      const float oa = (o[e].z - o[e].x) * (o[e].w - o[e].y);
+      const float iw = fmaxf(0.f, fminf(pk.z, o[e].z) - fmaxf(pk.x, o[e].x));
+      const float ih = fmaxf(0.f, fminf(pk.w, o[e].w) - fmaxf(pk.y, o[e].y));
+      const float inter = iw * ih;
+      const float u = inter / ((pa + oa) - inter);
+      in[e] = clsL[r] == cls && (r == i || u >= vote_iou);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (in[e]) {
+        const double s = (double)__uint_as_float((unsigned)(cand[r0 + e] >> 32));
+        W += s;
+        X0 += s * (double)o[e].x; X1 += s * (double)o[e].y; X2 += s * (double)o[e].z; X3 += s * (double)o[e].w;
+        ++nv;
+      }
+    }
+  }
+  bx.x1 = (float)(X0 / W); bx.y1 = (float)(X1 / W); bx.x2 = (float)(X2 / W); bx.y2 = (float)(X3 / W);   // (W >= s_i > score_thresh >= 0)
+  return nv;
+}
+
+// detect_nms_select_kernel with the voting step
+template <bool MANY>
+__global__ __launch_bounds__(DETW_THREADS) void detect_vote_select_kernel(DetArgs a, NmsArgs n, VoteArgs vt) {
+  DETN_SCAN_CARVE
+#define DETW_PAD_ANY true
+#include "detw_select_body.h"
+#undef DETW_PAD_ANY
+#define DETN_STORE(pos, sc) DETW_STORE_ROW(a, b, K, pos, cls, sc, idx, bx)
+#define DETN_VOTE vt
+#include "detn_scan_body.h"
+#undef DETN_VOTE
+#undef DETN_STORE
+}
+
+// detect_views_select_kernel with the voting step: the vote runs on the image-coordinate boxes, across the views
+template <bool MANY>
+__global__ __launch_bounds__(DETW_THREADS) void detect_views_vote_select_kernel(DetArgs a, NmsArgs n, ViewArgs vw, VoteArgs vt) {
+  DETN_SCAN_CARVE
+#define DETW_PAD_ANY false
+#define DETW_VIEWS vw.V
+#define DETW_VIEW_XF vw.xf
+#include "detw_select_body.h"
+#undef DETW_VIEW_XF
+#undef DETW_VIEWS
+#undef DETW_PAD_ANY
+#define DETN_STORE(pos, sc) DETV_STORE_ROW(a, b, K, pos, cls, sc, idx, bx)
+#define DETN_VOTE vt
+#include "detn_scan_body.h"
+#undef DETN_VOTE
 #undef DETN_STORE
 }
 
@@ -465,17 +538,18 @@ static void launch_wide_score(DetArgs a, bool many, int rows, hipStream_t stream
   }
 }
 
-// Every wide launch: (bit matrix | scan rule `n`) x (few | many classes) x (views | not).  a.B images of vw.V views each; `many` is the
-// head form and sets the class limit (16 or 256).  Refuses in this order, launching nothing: a size below 1, then (with a rule) an
-// unknown mode, a bad sigma or a negative score_thresh: status 1; past a limit: 2; a short or misaligned workspace, then keys_ready
-// without a <= 16-class pred: 1.
-static int launch_wide(DetArgs a, int ws_words, bool many, const NmsArgs* n, ViewArgs vw, hipStream_t stream) {
+// Every wide launch: (bit matrix | scan rule `n`) x (few | many classes) x (views | not) x (box voting `vt` | not; with a rule only).
+// a.B images of vw.V views each; `many` is the head form and sets the class limit (16 or 256).  Refuses in this order, launching
+// nothing: a size below 1, then (with a rule) an unknown mode, a bad sigma, a negative score_thresh or a vote_iou outside (0, 1]:
+// status 1; past a limit: 2; a short or misaligned workspace, then keys_ready without a <= 16-class pred: 1.
+static int launch_wide(DetArgs a, int ws_words, bool many, const NmsArgs* n, ViewArgs vw, const VoteArgs* vt, hipStream_t stream) {
   SQD_CHECK_ARG(a.B > 0 && vw.V >= 1 && a.A > 0 && a.C >= 1 && a.K >= 1);
   if (n) {
     SQD_CHECK_ARG(n->mode == NMS_HARD || n->mode == NMS_LINEAR || n->mode == NMS_GAUSSIAN);
     SQD_CHECK_ARG(n->mode != NMS_GAUSSIAN || (isfinite(n->sigma) && n->sigma > 0.f));
     SQD_CHECK_ARG(a.score_thresh >= 0.f);                     // (the keys: see ops._check_score_thresh; the scan's -1 marks rely on it too)
   }
+  SQD_CHECK_ARG(!vt || (n && vt->iou > 0.f && vt->iou <= 1.f));   // (a NaN compares false)
   if (a.K > DETW_MAX_K || a.A > DETW_MAX_A || a.C > (many ? SQD_MANY_MAX_CLASSES : SQD_MAX_CLASSES)) return SQD_ERR_UNSUPPORTED;
   if ((long long)vw.V * ((a.A + 3) & ~3) > DETW_MAX_A || (long long)a.B * vw.V > 0x7fffffffll) return SQD_ERR_UNSUPPORTED;
   const int rows = a.B * vw.V;
@@ -484,16 +558,23 @@ static int launch_wide(DetArgs a, int ws_words, bool many, const NmsArgs* n, Vie
   SQD_CHECK_ARG(a.keys && ws_words >= words && det_aligned16(a.keys));
   SQD_CHECK_ARG(!a.keys_ready || (a.pred && !many));          // ConvDet's epilogue writes the <= 16-class keys of a pred
   // the select kernel of the form; the dynamic-LDS cap is raised once per device and instantiation
-  static const void* const kernels[3][2] = {
+  static const void* const kernels[5][2] = {
       {(const void*)detect_wide_select_kernel<false>, (const void*)detect_wide_select_kernel<true>},
       {(const void*)detect_nms_select_kernel<false>, (const void*)detect_nms_select_kernel<true>},
-      {(const void*)detect_views_select_kernel<false>, (const void*)detect_views_select_kernel<true>}};
-  static SqdDevOnce once[3][2];
-  const int form = !n ? 0 : !vw.xf ? 1 : 2, Kp = (a.K + 63) & ~63;
+      {(const void*)detect_views_select_kernel<false>, (const void*)detect_views_select_kernel<true>},
+      {(const void*)detect_vote_select_kernel<false>, (const void*)detect_vote_select_kernel<true>},
+      {(const void*)detect_views_vote_select_kernel<false>, (const void*)detect_views_vote_select_kernel<true>}};
+  static SqdDevOnce once[5][2];
+  const int form = !n ? 0 : (!vw.xf ? 1 : 2) + (vt ? 2 : 0), Kp = (a.K + 63) & ~63;
   const size_t lds = n ? detn_scan_lds_bytes(Kp) : detw_matrix_lds_bytes(Kp);
   if (lds > 48 * 1024 && sqd_max_lds_once(once[form][many], kernels[form][many], n ? 96 * 1024 : 160 * 1024) != SQD_OK) return SQD_ERR_LAUNCH;
   if (!a.keys_ready) launch_wide_score(a, many, rows, stream);
-  void* args[] = {&a, (void*)n, &vw};                         // (a kernel takes as many as it has parameters)
+  void* args[4];                                              // DetArgs, then what the form has: NmsArgs, ViewArgs, VoteArgs
+  int na = 0;
+  args[na++] = &a;
+  if (n) args[na++] = (void*)n;
+  if (n && vw.xf) args[na++] = &vw;
+  if (vt) args[na++] = (void*)vt;
   (void)hipLaunchKernel(kernels[form][many], dim3((unsigned)a.B), dim3(DETW_THREADS), args, lds, stream);
   return sqd_launch_status();
 }
@@ -511,7 +592,7 @@ extern "C" int sqd_detect_wide_fwd(const float* pred, const float* anchors, cons
   const DetArgs a = det_args_pred(pred, anchors, scales, shifts, keys_ws, det_count, det_class, det_score, det_box, det_anchor, B, A,
                                   num_classes, input_h, input_w, keep_top_k, nms_thresh, score_thresh);
   SQD_CHECK_ARG(det_ptrs_ok(a) && keys_ws && det_aligned16(pred));
-  return launch_wide(a, ws_words, false, nullptr, NO_VIEWS, (hipStream_t)stream);
+  return launch_wide(a, ws_words, false, nullptr, NO_VIEWS, nullptr, (hipStream_t)stream);
 }
 
 // sqd_filter_fwd for the same ranges (dense class_ids int64 [B][A], scores [B][A], boxes [B][A][4])
@@ -521,7 +602,7 @@ extern "C" int sqd_filter_wide_fwd(const long long* class_ids, const float* scor
   const DetArgs a = det_args_dense(class_ids, scores, boxes, keys_ws, det_count, det_class, det_score, det_box, det_anchor, B, A,
                                    num_classes, keep_top_k, nms_thresh, score_thresh);
   SQD_CHECK_ARG(det_ptrs_ok(a) && keys_ws);
-  return launch_wide(a, ws_words, false, nullptr, NO_VIEWS, (hipStream_t)stream);
+  return launch_wide(a, ws_words, false, nullptr, NO_VIEWS, nullptr, (hipStream_t)stream);
 }
 
 // sqd_detect_wide_fwd for 1 <= num_classes <= 256 (the many-class head form at every class count; pred needs no alignment): same
@@ -533,7 +614,7 @@ extern "C" int sqd_detect_many_fwd(const float* pred, const float* anchors, cons
   const DetArgs a = det_args_pred(pred, anchors, scales, shifts, keys_ws, det_count, det_class, det_score, det_box, det_anchor, B, A,
                                   num_classes, input_h, input_w, keep_top_k, nms_thresh, score_thresh);
   SQD_CHECK_ARG(det_ptrs_ok(a) && keys_ws);
-  return launch_wide(a, ws_words, true, nullptr, NO_VIEWS, (hipStream_t)stream);
+  return launch_wide(a, ws_words, true, nullptr, NO_VIEWS, nullptr, (hipStream_t)stream);
 }
 
 // sqd_filter_wide_fwd for class ids up to 255
@@ -543,7 +624,7 @@ extern "C" int sqd_filter_many_fwd(const long long* class_ids, const float* scor
   const DetArgs a = det_args_dense(class_ids, scores, boxes, keys_ws, det_count, det_class, det_score, det_box, det_anchor, B, A,
                                    num_classes, keep_top_k, nms_thresh, score_thresh);
   SQD_CHECK_ARG(det_ptrs_ok(a) && keys_ws);
-  return launch_wide(a, ws_words, true, nullptr, NO_VIEWS, (hipStream_t)stream);
+  return launch_wide(a, ws_words, true, nullptr, NO_VIEWS, nullptr, (hipStream_t)stream);
 }
 
 // sqd_detect_wide_fwd / sqd_detect_many_fwd (either head form: 1 <= num_classes <= 256) with the suppression rule as an argument:
@@ -562,7 +643,7 @@ extern "C" int sqd_detect_nms_fwd(const float* pred, const float* anchors, const
   const bool many = num_classes > SQD_MAX_CLASSES;
   SQD_CHECK_ARG(det_ptrs_ok(a) && keys_ws && (many || det_aligned16(pred)));
   const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
-  return launch_wide(a, ws_words, many, &n, NO_VIEWS, (hipStream_t)stream);
+  return launch_wide(a, ws_words, many, &n, NO_VIEWS, nullptr, (hipStream_t)stream);
 }
 
 // sqd_filter_wide_fwd / sqd_filter_many_fwd with the same four arguments (keys_ready must be 0: dense scores have no ConvDet keys)
@@ -574,7 +655,7 @@ extern "C" int sqd_filter_nms_fwd(const long long* class_ids, const float* score
                                    num_classes, keep_top_k, nms_thresh, score_thresh);
   SQD_CHECK_ARG(det_ptrs_ok(a) && keys_ws && !keys_ready);
   const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
-  return launch_wide(a, ws_words, num_classes > SQD_MAX_CLASSES, &n, NO_VIEWS, (hipStream_t)stream);
+  return launch_wide(a, ws_words, num_classes > SQD_MAX_CLASSES, &n, NO_VIEWS, nullptr, (hipStream_t)stream);
 }
 
 // Pooled-view fused detect: pred [B * V][A][C + 5] (view v of image b = row b * V + v), anchors [A][4], view_xf fp32 [B * V][6] =
@@ -592,5 +673,53 @@ extern "C" int sqd_detect_views_fwd(const float* pred, const float* anchors, con
   const bool many = num_classes > SQD_MAX_CLASSES;
   SQD_CHECK_ARG(det_ptrs_ok(a) && view_xf && keys_ws && (many || det_aligned16(pred)));
   const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
-  return launch_wide(a, ws_words, many, &n, ViewArgs{view_xf, V}, (hipStream_t)stream);
+  return launch_wide(a, ws_words, many, &n, ViewArgs{view_xf, V}, nullptr, (hipStream_t)stream);
+}
+
+// Box voting (DESIGN.md section 3 "Box voting"): sqd_detect_nms_fwd / sqd_filter_nms_fwd / sqd_detect_views_fwd with `float vote_iou,
+// int* det_votes` before the stream.  The scan, det_count, det_class, det_score and det_anchor are those of the sibling; det_box of every
+// row is the score-weighted mean (float64 sums in rank order, original scores) of the same-class candidates that overlap the row's own
+// box by u >= vote_iou, the row's candidate included -- the canvas box in the first two (then the sibling's store: x / sx + dx), the
+// image box in the pooled form.  det_votes: int32 [B][keep_top_k], the number of voters per row, or null: not written.  vote_iou: in
+// (0, 1]; NaN, <= 0 or > 1 is status 1, checked with the rule (before the limits); everything else as the sibling.
+extern "C" int sqd_detect_vote_fwd(const float* pred, const float* anchors, const float* scales, const float* shifts, unsigned* keys_ws,
+                                   int* det_count, long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                   int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                                   int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, float vote_iou,
+                                   int* det_votes, void* stream) {
+  DetArgs a = det_args_pred(pred, anchors, scales, shifts, keys_ws, det_count, det_class, det_score, det_box, det_anchor, B, A,
+                            num_classes, input_h, input_w, keep_top_k, nms_thresh, score_thresh);
+  a.keys_ready = keys_ready ? 1 : 0;
+  const bool many = num_classes > SQD_MAX_CLASSES;
+  SQD_CHECK_ARG(det_ptrs_ok(a) && keys_ws && (many || det_aligned16(pred)));
+  const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
+  const VoteArgs vt = {vote_iou, det_votes};
+  return launch_wide(a, ws_words, many, &n, NO_VIEWS, &vt, (hipStream_t)stream);
+}
+
+extern "C" int sqd_filter_vote_fwd(const long long* class_ids, const float* scores, const float* boxes, unsigned* keys_ws, int* det_count,
+                                   long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int A,
+                                   int num_classes, int keep_top_k, float nms_thresh, float score_thresh, int ws_words,
+                                   int nms_mode, float nms_sigma, int nms_agnostic, int keys_ready, float vote_iou, int* det_votes,
+                                   void* stream) {
+  const DetArgs a = det_args_dense(class_ids, scores, boxes, keys_ws, det_count, det_class, det_score, det_box, det_anchor, B, A,
+                                   num_classes, keep_top_k, nms_thresh, score_thresh);
+  SQD_CHECK_ARG(det_ptrs_ok(a) && keys_ws && !keys_ready);
+  const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
+  const VoteArgs vt = {vote_iou, det_votes};
+  return launch_wide(a, ws_words, num_classes > SQD_MAX_CLASSES, &n, NO_VIEWS, &vt, (hipStream_t)stream);
+}
+
+extern "C" int sqd_detect_views_vote_fwd(const float* pred, const float* anchors, const float* view_xf, unsigned* keys_ws, int* det_count,
+                                         long long* det_class, float* det_score, float* det_box, int* det_anchor, int B, int V, int A,
+                                         int num_classes, int input_h, int input_w, int keep_top_k, float nms_thresh, float score_thresh,
+                                         int ws_words, int nms_mode, float nms_sigma, int nms_agnostic, float vote_iou, int* det_votes,
+                                         void* stream) {
+  const DetArgs a = det_args_pred(pred, anchors, nullptr, nullptr, keys_ws, det_count, det_class, det_score, det_box, det_anchor, B, A,
+                                  num_classes, input_h, input_w, keep_top_k, nms_thresh, score_thresh);
+  const bool many = num_classes > SQD_MAX_CLASSES;
+  SQD_CHECK_ARG(det_ptrs_ok(a) && view_xf && keys_ws && (many || det_aligned16(pred)));
+  const NmsArgs n = {nms_mode, nms_sigma, nms_agnostic ? 1 : 0};
+  const VoteArgs vt = {vote_iou, det_votes};
+  return launch_wide(a, ws_words, many, &n, ViewArgs{view_xf, V}, &vt, (hipStream_t)stream);
 }

@@ -4,6 +4,8 @@
 // always held, so its device code stays what it was.  The including kernel provides what detw_select_body.h left in scope, `n`
 // (NmsArgs), the LDS arrays boxP, grpL, curL, outS, emitL [Kp], gstart, glen, gcnt, goff [256], slot_s, slot_p [2][16] and the macro
 // DETN_STORE(pos, sc): store this thread's candidate as row `pos` of its image with the score `sc`.
+// DETN_VOTE (off for those two kernels; the voting kernels define it as their VoteArgs): DESIGN.md section 3 "Box voting" -- between the
+// scan and the store the thread of every emitted candidate replaces `bx` by the voted box (detn_vote) and writes its voter count.
   const int G = n.agnostic ? 1 : C;
   const float thr = a.score_thresh;
 
@@ -106,5 +108,13 @@
   __syncthreads();
   if (g >= 0) {
     const int t = emitL[slot];
+#ifdef DETN_VOTE
+    // box voting (the voting kernels define DETN_VOTE as their VoteArgs): the scan above is done and wrote none of cand / boxL / clsL,
+    // so the thread of an emitted candidate replaces its box by the score-weighted mean of its cluster before the same store
+    if (t >= 0) {
+      const int nv = detn_vote(cand, boxL, clsL, ncand, tid, cls, (DETN_VOTE).iou, bx);
+      if ((DETN_VOTE).votes) (DETN_VOTE).votes[(long long)b * K + (goff[g] + (unsigned)t)] = nv;
+    }
+#endif
     if (t >= 0) DETN_STORE(goff[g] + (unsigned)t, outS[slot]);
   }

@@ -20,7 +20,7 @@ import torch.utils.data
 
 from . import ops
 from .boxes import boxes_postprocess
-from .config import check_nms, check_tta
+from .config import check_box_vote, check_nms, check_tta
 
 
 class Detector(object):
@@ -35,13 +35,15 @@ class Detector(object):
         """image [B,3,H,W] on the GPU -> (count [B] i32, class_ids [B,K] i64, scores [B,K], boxes [B,K,4],
         anchor_idx [B,K] i32), all on the GPU; rows >= count[b] are padding.  ``scales`` / ``shifts`` [B,2]: ``boxes_postprocess``'
         scale division and padding / crops terms, folded into the detect kernel.  The suppression rule is ``cfg``'s (``nms_mode``,
-        ``nms_sigma``, ``nms_agnostic``: hard class-wise by default; under a Soft-NMS rule ``scores`` are the decayed ones)."""
+        ``nms_sigma``, ``nms_agnostic``: hard class-wise by default; under a Soft-NMS rule ``scores`` are the decayed ones); with
+        ``cfg.box_vote_iou`` set the boxes are the voted ones (DESIGN.md section 3 "Box voting")."""
         cfg = self.cfg
         base = self.model.base
         B, A, K = int(image.shape[0]), int(cfg.num_anchors), int(cfg.keep_top_k)
         mode, sigma, agnostic = check_nms(cfg, 'Detector')
-        plain = mode == 'hard' and not agnostic                  # the reference's rule: the launches of every earlier version
-        fused = ops.detect_fn(cfg.num_classes, K, A, mode, agnostic, sigma)
+        vote = check_box_vote(cfg, 'Detector')
+        plain = mode == 'hard' and not agnostic and vote is None   # the reference's rule: the launches of every earlier version
+        fused = ops.detect_fn(cfg.num_classes, K, A, mode, agnostic, sigma, vote_iou=vote)
         if not (getattr(base, 'fuse_detect_keys', False) and (fused is ops.detect or not plain) and int(cfg.num_classes) == 3
                 and float(cfg.score_thresh) >= 0.0 and isinstance(image, torch.Tensor) and image.is_cuda):
             pred = base(image)
@@ -75,7 +77,8 @@ class Detector(object):
         pred = self.model.base(image)
         anchors = self.model.resolver.anchors_on(pred.device)
         return ops.detect_views(pred, anchors, cfg.input_size, cfg.num_classes, V, view_xf, cfg.keep_top_k, cfg.nms_thresh,
-                                cfg.score_thresh, out=out, nms_mode=mode, nms_sigma=sigma, nms_agnostic=agnostic)
+                                cfg.score_thresh, out=out, nms_mode=mode, nms_sigma=sigma, nms_agnostic=agnostic,
+                                vote_iou=check_box_vote(cfg, 'Detector'))
 
     def _default_views(self):
         """``cfg.tta_flip`` / ``cfg.tta_zooms`` as a view list, or None while both are off."""
@@ -323,7 +326,8 @@ class Detector(object):
         filtered dict of GPU tensors (plus ``anchor_idx``) or ``None``."""
         cfg = self.cfg
         mode, sigma, agnostic = check_nms(cfg, 'Detector.filter')
-        dense = ops.filter_fn(cfg.num_classes, cfg.keep_top_k, det['scores'].shape[0], mode, agnostic, sigma)
+        dense = ops.filter_fn(cfg.num_classes, cfg.keep_top_k, det['scores'].shape[0], mode, agnostic, sigma,
+                              vote_iou=check_box_vote(cfg, 'Detector.filter'))
         cnt, cls, sc, bx, idx = dense(det['class_ids'][None], det['scores'][None], det['boxes'][None],
                                       cfg.num_classes, cfg.keep_top_k, cfg.nms_thresh, cfg.score_thresh)
         n = int(cnt[0].item())

@@ -21,7 +21,7 @@ the second time it is captured; afterwards it replays.  The ragged last batch of
 replay, eager launches and ``Detector.detect_images`` produce the same bits (tests/test_lanes_gpu.py).  A failed capture keeps
 that shape on eager launches and sets ``degraded`` (bench.py reports it next to ``value``).  New weights drop the captured steps;
 new detection parameters (``cfg.keep_top_k``, ``nms_thresh``, ``score_thresh``, ``nms_mode``, ``nms_sigma``, ``nms_agnostic``,
-``input_size``, ``num_classes``, the model's ``fuse_detect_keys``) drop the captured steps and the result buffers as well.
+``box_vote_iou``, ``input_size``, ``num_classes``, the model's ``fuse_detect_keys``) drop the captured steps and the result buffers as well.
 """
 from __future__ import annotations
 
@@ -484,7 +484,8 @@ class DetectStream:
         return (int(cfg.keep_top_k), float(cfg.nms_thresh), float(cfg.score_thresh), tuple(int(v) for v in cfg.input_size),
                 int(cfg.num_classes), int(cfg.num_anchors), bool(getattr(self.det.model.base, 'fuse_detect_keys', False)),
                 # the suppression rule picks the detect launch and is baked into its arguments: a captured step replays the old one
-                str(getattr(cfg, 'nms_mode', 'hard')), float(getattr(cfg, 'nms_sigma', 0.5)), bool(getattr(cfg, 'nms_agnostic', False)))
+                str(getattr(cfg, 'nms_mode', 'hard')), float(getattr(cfg, 'nms_sigma', 0.5)), bool(getattr(cfg, 'nms_agnostic', False)),
+                getattr(cfg, 'box_vote_iou', None))                # (box voting picks the voting launch and is baked into it as well)
 
     def discard(self, st):
         """Give an un-submitted ``Staging`` back (its batch takes another route)."""

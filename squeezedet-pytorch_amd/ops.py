@@ -1023,38 +1023,67 @@ def nms_mode_index(name, nms_mode, nms_sigma=0.5, nms_agnostic=False):
     return NMS_MODES.index(nms_mode), sigma, int(bool(nms_agnostic))
 
 
+def check_vote_iou(name, vote_iou):
+    """``vote_iou`` of box voting: None (off) or a finite number in (0, 1], not a bool -> None or the float; ValueError otherwise."""
+    if vote_iou is None:
+        return None
+    try:
+        v = float(vote_iou)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name}: vote_iou must be None or a finite number in (0, 1], got {vote_iou!r}') from None
+    if type(vote_iou).__name__ in ('bool', 'bool_') or not (math.isfinite(v) and 0.0 < v <= 1.0):
+        raise ValueError(f'{name}: vote_iou must be None or a finite number in (0, 1], got {vote_iou!r}')
+    return v
+
+
+def _votes_out(vote, return_votes, B, K, device):
+    """The int32 [B, K] voter counts of a launch, where asked for: zeros for the voting launch to fill (rows past count stay 0), ones
+    without voting (every row is its own only voter)."""
+    if not return_votes:
+        return None
+    return (torch.zeros if vote is not None else torch.ones)(B, K, device=device, dtype=torch.int32)
+
+
 def detect_nms(pred, anchors, input_size, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, scales=None, out=None, shifts=None,
-               nms_mode='hard', nms_sigma=0.5, nms_agnostic=False, keys_ready=False):
+               nms_mode='hard', nms_sigma=0.5, nms_agnostic=False, keys_ready=False, vote_iou=None, return_votes=False):
     """``detect_wide`` / ``detect_many`` (any 1 <= ``keep_top_k`` <= 1024, up to 2^20 anchors, 1 <= ``num_classes`` <= 256) with the
     suppression rule as an argument: ``nms_mode`` 'hard' | 'linear' | 'gaussian' (Soft-NMS: an overlapped box keeps a decayed score
     -- times 1 - IoU where IoU > ``nms_thresh``, or times exp(-IoU^2 / ``nms_sigma``) -- instead of being deleted), ``nms_agnostic``:
     one suppression group for all classes.  Rows come out in class order (agnostic: one group), each group in pick order, ``scores``
     holding the decayed score; rows whose score fell to ``score_thresh`` or below are gone.  ('hard', False) equals ``detect_wide`` /
     ``detect_many`` bit for bit.  ``keys_ready`` (<= 16 classes): the workspace in ``out`` already holds the keys of this ``pred`` for
-    this ``score_thresh`` (``DetKeys``) -- no scoring launch."""
+    this ``score_thresh`` (``DetKeys``) -- no scoring launch.
+    ``vote_iou`` (None: off; else in (0, 1]): box voting (DESIGN.md section 3 "Box voting") -- the rows, their order, classes, scores and
+    ``anchor_idx`` stay those of the same call without it; every emitted box becomes the mean, weighted by the original scores, of the
+    same-class candidates that overlap it by IoU >= ``vote_iou`` (itself included; suppressed candidates vote too).
+    ``return_votes``: an int32 [B,K] tensor with each row's number of voters is appended to the returned tuple."""
     mode, sigma, agnostic = nms_mode_index('detect_nms', nms_mode, nms_sigma, nms_agnostic)
+    vote = check_vote_iou('detect_nms', vote_iou)
     pred, B, A = _pred_side('detect_nms', pred, anchors, num_classes, score_thresh, keep_top_k, scales, shifts, many=True)
     K = int(keep_top_k)
     bufs, keys = _wide_out('detect_nms', out, B, A, K, pred.device)
     if keys_ready and (len(bufs) != 6 or keys is not bufs[5] or head_path(num_classes) != 'narrow'):
         raise ValueError('detect_nms: keys_ready needs the 16-byte aligned workspace the keys were written to (<= 16 classes)')
     cnt, cls, sc, bx, idx = bufs[:5]
+    votes = _votes_out(vote, return_votes, B, K, pred.device)
     br = _Bracket('detect', f'detect_nms A{A} K{K}', 0.0, 4.0 * B * A * (num_classes + 5)) if timing._timer is not None else None
-    rc = nat.lib().sqd_detect_nms_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
-                                      nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
-                                      int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
-                                      keys.numel(), mode, sigma, agnostic, int(bool(keys_ready)), nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_detect_nms_fwd')
+    entry = 'sqd_detect_nms_fwd' if vote is None else 'sqd_detect_vote_fwd'
+    rc = getattr(nat.lib(), entry)(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(scales), nat.ptr(shifts), nat.ptr(keys),
+                                   nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                   int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
+                                   keys.numel(), mode, sigma, agnostic, int(bool(keys_ready)),
+                                   *(() if vote is None else (vote, nat.ptr(votes))), nat.stream_handle(pred.device))
+    nat.check(rc, entry)
     if br is not None:
         br.done()
-    return bufs[:5]
+    return tuple(bufs[:5]) + ((votes,) if return_votes else ())
 
 
 DET_VIEWS_MAX_ROW = 1 << 20    # key words of one pooled row, V * ceil4(A): the wide select's row limit
 
 
 def detect_views(pred, anchors, input_size, num_classes, V, view_xf, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, out=None,
-                 nms_mode='hard', nms_sigma=0.5, nms_agnostic=False):
+                 nms_mode='hard', nms_sigma=0.5, nms_agnostic=False, vote_iou=None, return_votes=False):
     """Pooled-view fused detect (DESIGN.md section 3 "Pooled views"): ``pred`` [B*V, A, C+5] holds ``V`` network views of each of B
     images (view v of image b = row b*V + v), ``view_xf`` fp32 [B*V, 6] = (sy, sx, dy, dx, flip, mirror) maps a row's canvas boxes
     into its image -- ``x / sx + dx``, ``y / sy + dy``, then, where ``flip`` != 0, ``(x1, x2) <- (mirror - x2, mirror - x1)`` -- and the
@@ -1063,8 +1092,10 @@ def detect_views(pred, anchors, input_size, num_classes, V, view_xf, keep_top_k=
     scores [B,K], boxes [B,K,4] in image coordinates, pooled_idx int32 [B,K] = v * A + anchor).  ``out``: the five result tensors
     (checked against B and ``keep_top_k``) and optionally a workspace of ``det_workspace_words_wide(B*V, A, keep_top_k)`` int32.
     ``V`` = 1 with ``view_xf`` = (1, 1, 0, 0, 0, 0) equals ``detect_nms`` bit for bit.  Limits: ``V * ceil4(A) <= 2^20``, K <= 1024,
-    1 <= ``num_classes`` <= 256."""
+    1 <= ``num_classes`` <= 256.  ``vote_iou`` / ``return_votes``: box voting as in ``detect_nms``, on the image-coordinate boxes -- the
+    near-duplicate boxes the views give of one object are merged instead of dropped; a row seen by one view only has few voters."""
     mode, sigma, agnostic = nms_mode_index('detect_views', nms_mode, nms_sigma, nms_agnostic)
+    vote = check_vote_iou('detect_views', vote_iou)
     pred, B, A = _pred_side('detect_views', pred, anchors, num_classes, score_thresh, keep_top_k, many=True, V=V)
     V, K, rows = int(V), int(keep_top_k), pred.shape[0]
     if not isinstance(view_xf, torch.Tensor) or tuple(view_xf.shape) != (rows, 6) or view_xf.dtype != torch.float32 \
@@ -1072,38 +1103,51 @@ def detect_views(pred, anchors, input_size, num_classes, V, view_xf, keep_top_k=
         raise ValueError('detect_views: view_xf must be contiguous fp32 [B*V,6] (sy, sx, dy, dx, flip, mirror) on the same device')
     bufs, keys = _wide_out('detect_views', out, B, A, K, pred.device, rows=rows)
     cnt, cls, sc, bx, idx = bufs[:5]
+    votes = _votes_out(vote, return_votes, B, K, pred.device)
     br = _Bracket('detect', f'detect_views V{V} A{A} K{K}', 0.0, 4.0 * rows * A * (num_classes + 5)) if timing._timer is not None else None
-    rc = nat.lib().sqd_detect_views_fwd(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(view_xf), nat.ptr(keys), nat.ptr(cnt),
-                                        nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, V, A, num_classes,
-                                        int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
-                                        keys.numel(), mode, sigma, agnostic, nat.stream_handle(pred.device))
-    nat.check(rc, 'sqd_detect_views_fwd')
+    entry = 'sqd_detect_views_fwd' if vote is None else 'sqd_detect_views_vote_fwd'
+    rc = getattr(nat.lib(), entry)(nat.ptr(pred), nat.ptr(anchors.contiguous()), nat.ptr(view_xf), nat.ptr(keys), nat.ptr(cnt),
+                                   nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, V, A, num_classes,
+                                   int(input_size[0]), int(input_size[1]), K, float(nms_thresh), float(score_thresh),
+                                   keys.numel(), mode, sigma, agnostic, *(() if vote is None else (vote, nat.ptr(votes))),
+                                   nat.stream_handle(pred.device))
+    nat.check(rc, entry)
     if br is not None:
         br.done()
-    return bufs[:5]
+    return tuple(bufs[:5]) + ((votes,) if return_votes else ())
 
 
 def filter_dense_nms(class_ids, scores, boxes, num_classes, keep_top_k=64, nms_thresh=0.4, score_thresh=0.3, out=None,
-                     nms_mode='hard', nms_sigma=0.5, nms_agnostic=False):
+                     nms_mode='hard', nms_sigma=0.5, nms_agnostic=False, vote_iou=None, return_votes=False):
     """``filter_dense_wide`` / ``filter_dense_many`` with the suppression rule of ``detect_nms``.  ``out``: the five result tensors
-    (checked against B and ``keep_top_k``) and optionally a workspace of ``det_workspace_words_wide`` int32."""
+    (checked against B and ``keep_top_k``) and optionally a workspace of ``det_workspace_words_wide`` int32.  ``vote_iou`` /
+    ``return_votes``: box voting as in ``detect_nms``."""
     mode, sigma, agnostic = nms_mode_index('filter_nms', nms_mode, nms_sigma, nms_agnostic)
+    vote = check_vote_iou('filter_nms', vote_iou)
     B, A = _dense_side('filter_nms', class_ids, scores, boxes, num_classes, score_thresh, keep_top_k, many=True)
     K = int(keep_top_k)
     bufs, keys = _wide_out('filter_nms', out, B, A, K, scores.device)
     cnt, cls, sc, bx, idx = bufs[:5]
-    rc = nat.lib().sqd_filter_nms_fwd(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
-                                      nat.ptr(keys), nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
-                                      K, float(nms_thresh), float(score_thresh), keys.numel(), mode, sigma, agnostic, 0,
-                                      nat.stream_handle(scores.device))
-    nat.check(rc, 'sqd_filter_nms_fwd')
-    return bufs[:5]
+    votes = _votes_out(vote, return_votes, B, K, scores.device)
+    entry = 'sqd_filter_nms_fwd' if vote is None else 'sqd_filter_vote_fwd'
+    rc = getattr(nat.lib(), entry)(nat.ptr(class_ids.contiguous()), nat.ptr(scores.contiguous()), nat.ptr(boxes.contiguous()),
+                                   nat.ptr(keys), nat.ptr(cnt), nat.ptr(cls), nat.ptr(sc), nat.ptr(bx), nat.ptr(idx), B, A, num_classes,
+                                   K, float(nms_thresh), float(score_thresh), keys.numel(), mode, sigma, agnostic, 0,
+                                   *(() if vote is None else (vote, nat.ptr(votes))), nat.stream_handle(scores.device))
+    nat.check(rc, entry)
+    return tuple(bufs[:5]) + ((votes,) if return_votes else ())
 
 
-def detect_fn(num_classes, keep_top_k, A, nms_mode='hard', nms_agnostic=False, nms_sigma=0.5):
+def detect_fn(num_classes, keep_top_k, A, nms_mode='hard', nms_agnostic=False, nms_sigma=0.5, vote_iou=None):
     """The fused detect that serves (num_classes, keep_top_k, A): ``detect`` / ``detect_wide`` up to 16 classes (``detect_path``),
-    ``detect_many`` past them.  Any rule but ('hard', class-wise): ``detect_nms`` with the rule bound, for every K, A and class count."""
+    ``detect_many`` past them.  Any rule but ('hard', class-wise): ``detect_nms`` with the rule bound, for every K, A and class count.
+    ``vote_iou`` set (box voting): ``detect_nms`` with the rule and ``vote_iou`` bound, under every rule."""
     nms_mode_index('detect_fn', nms_mode, nms_sigma, nms_agnostic)
+    vote = check_vote_iou('detect_fn', vote_iou)
+    if vote is not None:
+        head_path(num_classes)
+        detect_path(keep_top_k, A)
+        return functools.partial(detect_nms, nms_mode=nms_mode, nms_sigma=float(nms_sigma), nms_agnostic=bool(nms_agnostic), vote_iou=vote)
     if nms_mode != 'hard' or nms_agnostic:
         head_path(num_classes)
         detect_path(keep_top_k, A)
@@ -1114,9 +1158,15 @@ def detect_fn(num_classes, keep_top_k, A, nms_mode='hard', nms_agnostic=False, n
     return detect if detect_path(keep_top_k, A) == 'narrow' else detect_wide
 
 
-def filter_fn(num_classes, keep_top_k, A, nms_mode='hard', nms_agnostic=False, nms_sigma=0.5):
-    """The dense filter that serves (num_classes, keep_top_k, A) and the rule, as ``detect_fn``."""
+def filter_fn(num_classes, keep_top_k, A, nms_mode='hard', nms_agnostic=False, nms_sigma=0.5, vote_iou=None):
+    """The dense filter that serves (num_classes, keep_top_k, A), the rule and ``vote_iou``, as ``detect_fn``."""
     nms_mode_index('filter_fn', nms_mode, nms_sigma, nms_agnostic)
+    vote = check_vote_iou('filter_fn', vote_iou)
+    if vote is not None:
+        head_path(num_classes)
+        detect_path(keep_top_k, A)
+        return functools.partial(filter_dense_nms, nms_mode=nms_mode, nms_sigma=float(nms_sigma), nms_agnostic=bool(nms_agnostic),
+                                 vote_iou=vote)
     if nms_mode != 'hard' or nms_agnostic:
         head_path(num_classes)
         detect_path(keep_top_k, A)
